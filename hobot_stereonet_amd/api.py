@@ -53,6 +53,12 @@ class SnAutoState(C.Structure):
                 ("running_px", C.c_double), ("switches", C.c_uint64)]
 
 
+class SnCamera(C.Structure):
+    """sn_camera (include/stereonet_hip.h); pointcloud.Camera is the Python face of it."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("baseline_mm", C.c_float),
+                ("z_min_m", C.c_float), ("z_max_m", C.c_float), ("step", C.c_int)]
+
+
 class StereoNetError(RuntimeError):
     def __init__(self, code: int, where: str, detail: str = ""):
         self.code = code
@@ -129,6 +135,7 @@ def load_library(path: Optional[str] = None):
     lib.sn_dbg_read.argtypes = [vp, C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.sn_dbg_copy_limited.argtypes = [vp, vp, C.c_size_t, ip, vp]
     lib.sn_depth_from_raw.argtypes = [vp, ip, i32p, C.c_float, C.c_float, fp, fp, ip, vp]
+    lib.sn_pointcloud_from_raw.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnCamera), ip, fp, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
     lib.sn_auto_init.argtypes = [C.POINTER(SnAutoState), ip]
     lib.sn_auto_observe.argtypes = [C.POINTER(SnAutoState), C.c_double]
@@ -140,7 +147,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -341,6 +348,53 @@ class StereoNetHIP:
         self._check(self._lib.sn_depth_from_raw(self._h, n, r.ctypes.data, focal_px, baseline_mm, depth.ctypes.data,
                                                 _np_ptr(disp), SN_MEM_HOST, None), "sn_depth_from_raw")
         return (depth, disp) if want_disp else depth
+
+    def _camera(self, cam) -> "SnCamera":
+        from . import pointcloud
+        c = (cam or pointcloud.Camera()).resolved(self.width, self.height)
+        return SnCamera(c.fx, c.fy, c.cx, c.cy, c.baseline_mm, c.z_min_m, c.z_max_m, c.step)
+
+    def pointcloud(self, raw: np.ndarray, cam=None, layout: int = 0, nv12: Optional[np.ndarray] = None,
+                   nv12_pitch: int = 0):
+        """sn_pointcloud_from_raw on host buffers: int32 (H,W) or (n,H,W) -> (points float32, counts uint32 (n,)), points
+        (n, Ho, Wo, 4) for pointcloud.ORGANISED and (n, Ho*Wo, 4) for pointcloud.COMPACT (map k's first counts[k] rows are
+        its points; the rest is unspecified), leading n dropped for a 2-D raw.  cam: pointcloud.Camera (default: the
+        reference's intrinsics, principal point at the centre).  nv12: n frames of pointcloud.nv12_frame_bytes(nv12_pitch,
+        H) bytes (W for a plain left image, 2W for the side-by-side frame) colour the points."""
+        from . import pointcloud
+        r = np.ascontiguousarray(raw, dtype=np.int32)
+        # the call reads n * H * W elements of the MODEL's size: anything else would run past these arrays
+        if r.ndim not in (2, 3) or r.shape[-2:] != (self.height, self.width):
+            raise StereoNetError(-1, "pointcloud", f"raw shape {r.shape} != ([n,] {self.height}, {self.width})")
+        n = 1 if r.ndim == 2 else r.shape[0]
+        if n < 1 or n > self.max_batch:
+            raise StereoNetError(-1, "pointcloud", f"{n} maps, the engine was created for 1..{self.max_batch}")
+        c = self._camera(cam)
+        f = None
+        if nv12 is not None:
+            f = np.ascontiguousarray(nv12, dtype=np.uint8)
+            if nv12_pitch < self.width or f.size != n * pointcloud.nv12_frame_bytes(nv12_pitch, self.height):
+                raise StereoNetError(-1, "pointcloud", f"nv12 of {f.size} bytes at pitch {nv12_pitch} is not {n} frames of "
+                                                       f"{self.width}x{self.height}")
+        ho, wo = pointcloud.Camera(step=c.step).out_shape(self.width, self.height)
+        shape = (n, ho, wo, 4) if layout == pointcloud.ORGANISED else (n, ho * wo, 4)
+        pts = np.empty(int(np.prod(shape)) + 4, np.float32)         # points must be 16-byte aligned
+        off = (-pts.ctypes.data % 16) // 4
+        pts = pts[off:off + int(np.prod(shape))].reshape(shape)
+        counts = np.zeros(n, np.uint32)
+        self._check(self._lib.sn_pointcloud_from_raw(self._h, n, r.ctypes.data, _np_ptr(f), nv12_pitch, C.byref(c), layout,
+                                                     pts.ctypes.data, counts.ctypes.data, SN_MEM_HOST, None),
+                    "sn_pointcloud_from_raw")
+        return (pts[0], counts[:1]) if r.ndim == 2 else (pts, counts)
+
+    def pointcloud_device(self, n: int, raw_ptr: int, cam, points_ptr: int, counts_ptr: int, nv12_ptr: int = 0,
+                          nv12_pitch: int = 0, layout: int = 0, stream: int = 0):
+        """sn_pointcloud_from_raw on device pointers (e.g. torch tensors' data_ptr()); stream = hipStream_t as int
+        (0: the point cloud's own stream, and the call returns after completion)."""
+        c = self._camera(cam)
+        self._check(self._lib.sn_pointcloud_from_raw(self._h, n, raw_ptr, nv12_ptr or None, nv12_pitch, C.byref(c), layout,
+                                                     points_ptr, counts_ptr or None, SN_MEM_DEVICE, stream or None),
+                    "sn_pointcloud_from_raw")
 
     def synchronize(self):
         self._check(self._lib.sn_synchronize(self._h), "sn_synchronize")

@@ -11,6 +11,7 @@
 // reused across frames, and the inference behind DnnNode::Run is libstereonet_hip.so.
 #pragma once
 
+#include <atomic>
 #include <cstdint>
 #include <future>
 #include <memory>
@@ -19,10 +20,12 @@
 
 #include "rclcpp/rclcpp.hpp"
 #include "sensor_msgs/msg/image.hpp"
+#include "sensor_msgs/msg/point_cloud2.hpp"
 #include "ai_msgs/msg/perception_targets.hpp"
 #include "hbm_img_msgs/msg/hbm_msg1080_p.hpp"
 
 #include "dnn_node/dnn_node.h"
+#include "stereonet_hip.h"
 #include "bin_data.h"
 #include "preprocess.h"
 
@@ -36,6 +39,8 @@ struct StereonetNodeOutput : public hobot::dnn_node::DnnNodeOutput {
   // this implementation's own: set when the left-eye JPEG of this request is being encoded on a worker thread
   // (sp_left_nv12->jpeg is complete once it yields true); PostProcess waits for it
   std::shared_future<bool> jpeg_ready;
+  // kept only while the point cloud is on (STEREONET_POINTCLOUD): the frame whose left eye colours the cloud
+  hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame;
 };
 
 class JpegPool;      // worker threads that encode the left-eye JPEGs of requests in flight (stereonet_node.cpp)
@@ -73,11 +78,19 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
                                       // STEREONET_JPEG_SLICES overrides
     int feed_start_pause_ms = 1000;   // the reference waits for the viewer before / between offline frames
     int feed_frame_pause_ms = 300;    // (stereonet_node.cpp:890,974); STEREONET_FEED_PAUSE_MS overrides both
+    // this implementation's own: sensor_msgs/PointCloud2 on /stereonet_pointcloud2 (sn_pointcloud_from_raw).
+    // STEREONET_POINTCLOUD=organised|compact turns it on (unset: off, nothing of it exists);
+    // STEREONET_CAMERA=fx,fy,cx,cy,baseline_mm (cx, cy default to the map's centre), STEREONET_POINTCLOUD_STEP=1|2|4,
+    // STEREONET_POINTCLOUD_Z=min,max (metres; max <= 0: no upper bound)
+    int pointcloud_layout = -1;       // -1 off, else SN_PC_ORGANISED / SN_PC_COMPACT
+    sn_camera camera{};
   };
 
   void DeclareAndReadParameters();
   void LogModelIo();
   void OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame);   // the FeedImg role
+  void ReadPointCloudSettings();
+  void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
 
   Settings cfg_;
   bool ready_ = false;
@@ -90,6 +103,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   rclcpp::Subscription<hbm_img_msgs::msg::HbmMsg1080P>::ConstSharedPtr frames_in_;
   rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr disparity_out_;
   rclcpp::Publisher<ai_msgs::msg::PerceptionTargets>::SharedPtr targets_out_;   // created for parity, never used
+  rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pointcloud_out_;   // only while the cloud is on
+  std::atomic<bool> cloud_uncoloured_logged_{false};
 };
 
 }  // namespace stereonet

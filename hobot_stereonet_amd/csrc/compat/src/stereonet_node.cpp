@@ -12,7 +12,9 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -90,6 +92,8 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
       cfg_.image_topic, 10, [this](hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr m) { OnStereoFrame(m); });
   targets_out_ = create_publisher<ai_msgs::msg::PerceptionTargets>("/Stereonet_node_sample", 10);
   disparity_out_ = create_publisher<sensor_msgs::msg::Image>(cfg_.output_topic, 10);
+  ReadPointCloudSettings();
+  if (cfg_.pointcloud_layout >= 0) pointcloud_out_ = create_publisher<sensor_msgs::msg::PointCloud2>("/stereonet_pointcloud2", 10);
   ready_ = true;
 }
 
@@ -110,6 +114,90 @@ void StereonetNode::DeclareAndReadParameters() {
   RCLCPP_WARN_STREAM(kLog, "\n config_file: " << cfg_.config_file << "\n model_file: " << cfg_.model_file
                                               << "\n sub_hbmem_topic_name: " << cfg_.image_topic
                                               << "\n ros_img_topic_name: " << cfg_.output_topic);
+}
+
+void StereonetNode::ReadPointCloudSettings() {
+  const char* e = getenv("STEREONET_POINTCLOUD");
+  if (!e || !*e) return;
+  if (!strcmp(e, "organised")) {
+    cfg_.pointcloud_layout = SN_PC_ORGANISED;
+  } else if (!strcmp(e, "compact")) {
+    cfg_.pointcloud_layout = SN_PC_COMPACT;
+  } else {
+    RCLCPP_ERROR_STREAM(kLog, "STEREONET_POINTCLOUD=" << e << " is neither organised nor compact: no point cloud");
+    return;
+  }
+  sn_camera& c = cfg_.camera;
+  c = sn_camera{527.1931762695312f, 527.1931762695312f, net_w_ / 2.0f, net_h_ / 2.0f, 119.89382172f, 0.f, 0.f, 1};
+  // checked once here: settings sn_pointcloud_from_raw would reject turn the cloud off instead of failing every frame
+  std::string bad;
+  char end = 0;
+  if (const char* v = getenv("STEREONET_CAMERA"))
+    if (sscanf(v, "%f,%f,%f,%f,%f%c", &c.fx, &c.fy, &c.cx, &c.cy, &c.baseline_mm, &end) != 5)
+      bad = std::string("STEREONET_CAMERA=") + v + " is not fx,fy,cx,cy,baseline_mm";
+  if (const char* v = getenv("STEREONET_POINTCLOUD_STEP"))
+    if (sscanf(v, "%d%c", &c.step, &end) != 1) bad = std::string("STEREONET_POINTCLOUD_STEP=") + v + " is not 1, 2 or 4";
+  if (const char* v = getenv("STEREONET_POINTCLOUD_Z"))
+    if (sscanf(v, "%f,%f%c", &c.z_min_m, &c.z_max_m, &end) != 2)
+      bad = std::string("STEREONET_POINTCLOUD_Z=") + v + " is not min,max";
+  if (bad.empty() && !(c.fx > 0.f && std::isfinite(c.fx) && c.fy > 0.f && std::isfinite(c.fy) && c.baseline_mm > 0.f &&
+                       std::isfinite(c.cx) && std::isfinite(c.cy)))
+    bad = "STEREONET_CAMERA: fx, fy and baseline_mm must be positive and every value finite";
+  if (bad.empty() && c.step != 1 && c.step != 2 && c.step != 4) bad = "STEREONET_POINTCLOUD_STEP must be 1, 2 or 4";
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no point cloud");
+    cfg_.pointcloud_layout = -1;
+    return;
+  }
+  RCLCPP_WARN_STREAM(kLog, "point cloud: " << e << " on /stereonet_pointcloud2, fx " << c.fx << " fy " << c.fy << " cx " << c.cx
+                                           << " cy " << c.cy << " baseline_mm " << c.baseline_mm << " step " << c.step
+                                           << " z " << c.z_min_m << ".." << c.z_max_m);
+}
+
+// sensor_msgs/PointCloud2 of the request's map: x, y, z (+ rgb) FLOAT32 at 0 / 4 / 8 / 12, 16 bytes a point, the header of
+// the disparity message; organised = the sampled image grid with NaN for invalid samples, compact = one row of valid points
+void StereonetNode::PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw) {
+  const sn_camera& cam = cfg_.camera;
+  const int wo = (net_w_ + cam.step - 1) / cam.step, ho = (net_h_ + cam.step - 1) / cam.step;
+  const auto& f = request.frame;
+  const bool colour = f && (int)f->width == 2 * net_w_ && (int)f->height == net_h_ &&
+                      f->data.size() >= (size_t)2 * net_w_ * (net_h_ + (net_h_ + 1) / 2);
+  if (!colour && !cloud_uncoloured_logged_.exchange(true))
+    RCLCPP_WARN(kLog, "point cloud without colour: no side-by-side frame of the model's size for this request");
+  sensor_msgs::msg::PointCloud2 msg;
+  msg.header = *request.msg_header;
+  msg.data.resize((size_t)ho * wo * 16);
+  uint32_t count = 0;
+  const int rc = sn_pointcloud_from_raw(net_->engine(), 1, raw, colour ? f->data.data() : nullptr, 2 * net_w_, &cam,
+                                        cfg_.pointcloud_layout, reinterpret_cast<float*>(msg.data.data()), &count,
+                                        SN_MEM_HOST, nullptr);
+  if (rc != SN_OK) {
+    RCLCPP_ERROR(kLog, "point cloud failed: %s", sn_last_error(net_->engine()));
+    return;
+  }
+  const char* names[4] = {"x", "y", "z", "rgb"};
+  for (int k = 0; k < (colour ? 4 : 3); ++k) {
+    sensor_msgs::msg::PointField pf;
+    pf.name = names[k];
+    pf.offset = 4 * k;
+    pf.datatype = sensor_msgs::msg::PointField::FLOAT32;
+    pf.count = 1;
+    msg.fields.push_back(pf);
+  }
+  msg.is_bigendian = false;
+  msg.point_step = 16;
+  if (cfg_.pointcloud_layout == SN_PC_ORGANISED) {
+    msg.height = ho;
+    msg.width = wo;
+    msg.is_dense = false;
+  } else {
+    msg.height = 1;
+    msg.width = count;
+    msg.is_dense = true;
+    msg.data.resize((size_t)count * 16);
+  }
+  msg.row_step = 16 * msg.width;
+  pointcloud_out_->publish(std::move(msg));
 }
 
 void StereonetNode::LogModelIo() {
@@ -162,6 +250,7 @@ void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSha
   request->msg_header = std::make_shared<std_msgs::msg::Header>();
   request->msg_header->frame_id = std::to_string(frame->index);
   request->msg_header->stamp = frame->time_stamp;
+  if (cfg_.pointcloud_layout >= 0) request->frame = frame;
 
   const auto t_pre = std::chrono::steady_clock::now();
   // STEREONET_INGEST=tensor keeps the reference's host steps (split both eyes, CvtNV12Data2Tensors, Run on the int8
@@ -349,6 +438,8 @@ int StereonetNode::PostProcess(const std::shared_ptr<hobot::dnn_node::DnnNodeOut
   } else {
     RCLCPP_INFO(kLog, "publish is unable");
   }
+  if (pointcloud_out_ && !request->output_tensors.empty())
+    PublishPointCloud(*request, static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
   const auto& st = node_output->rt_stat;
   if (st && st->fps_updated)
     RCLCPP_WARN(kLog,

@@ -27,6 +27,7 @@
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
 #include "sn_kernels.hpp"
+#include "sn_pointcloud.hpp"
 
 namespace {
 
@@ -237,12 +238,28 @@ struct sn_handle {
   int dom_pairs = 0;
   float stage_ms[SN_STAGE_COUNT] = {};
   mutable std::string err;
+  mutable std::mutex err_mu;  // err is written by failing calls on any thread (sn_pointcloud_from_raw beside sn_wait)
+  // sn_pointcloud_from_raw: everything of its own (it may run beside sn_submit / sn_wait), created on its first call
+  struct PointCloud {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev = nullptr;           // the last enqueue that used `scratch`
+    uint32_t* scratch = nullptr;       // compact form: valid samples per tile
+    size_t scratch_bytes = 0;
+    void* dev[4] = {};                 // host mode: raw, nv12, points, counts
+    size_t dev_bytes[4] = {};
+    void* pin[2] = {};                 // host mode: pinned staging of raw and nv12
+    size_t pin_bytes[2] = {};
+  } pc;
 };
 
 namespace {
 
 void set_err(const sn_handle* h, const std::string& s) {
-  if (h) h->err = s;
+  if (h) {
+    std::lock_guard<std::mutex> lk(h->err_mu);
+    h->err = s;
+  }
 }
 void set_err(std::nullptr_t, const std::string&) {}
 
@@ -2106,7 +2123,13 @@ static int create_fail(int code, const char* what) {
   return code;
 }
 
-const char* sn_last_error(const sn_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+const char* sn_last_error(const sn_handle* h) {
+  if (!h) return g_create_err.c_str();
+  thread_local std::string copy;      // the caller's own copy: another thread's failure cannot change it under the caller
+  std::lock_guard<std::mutex> lk(h->err_mu);
+  copy = h->err;
+  return copy.c_str();
+}
 
 int sn_create(const char* model_file, const sn_config* cfg, sn_handle** out) {
   return sn_create_prio(model_file, cfg, -1, out);
@@ -2419,6 +2442,12 @@ int sn_destroy(sn_handle* h) {
     hipFree(T.rout.w);
   }
   hipFree(h->dump);
+  hipFree(h->pc.scratch);
+  for (void* p : h->pc.dev) hipFree(p);
+  for (void* p : h->pc.pin)
+    if (p) hipHostFree(p);
+  if (h->pc.ev) hipEventDestroy(h->pc.ev);
+  if (h->pc.stream) hipStreamDestroy(h->pc.stream);
   hipFree(h->aout.w);
   hipFree(h->aout.pfrag);
   for (auto p : h->chk) hipFree(p);
@@ -3704,6 +3733,97 @@ int sn_depth_from_raw(sn_handle* h, int n, const int32_t* raw, float focal_px, f
     if (disp_px) HIP_TRY(h, hipMemcpyAsync(disp_px, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
   }
+  return SN_OK;
+}
+
+// Grows a buffer of the point-cloud state; a buffer is only ever replaced by a larger one, so a warm caller allocates nothing.
+static hipError_t pc_grow(void** p, size_t* have, size_t bytes, bool pinned) {
+  if (bytes <= *have) return hipSuccess;
+  if (*p) {
+    if (pinned) hipHostFree(*p);
+    else hipFree(*p);
+  }
+  *p = nullptr;
+  *have = 0;
+  const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+  if (e == hipSuccess) *have = bytes;
+  return e;
+}
+
+int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_t* nv12, int nv12_pitch, const sn_camera* cam,
+                           int layout, float* points, uint32_t* counts, int mem, void* stream) {
+  if (!h || !raw || !cam || !points || n <= 0 || n > h->max_batch || ((uintptr_t)points & 15) ||
+      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) || (layout != SN_PC_ORGANISED && layout != SN_PC_COMPACT) ||
+      (layout == SN_PC_COMPACT && !counts))
+    return SN_ERR_ARG;
+  if (!(cam->fx > 0.f) || !std::isfinite(cam->fx) || !(cam->fy > 0.f) || !std::isfinite(cam->fy) ||
+      !(cam->baseline_mm > 0.f) || (cam->step != 1 && cam->step != 2 && cam->step != 4))
+    return SN_ERR_ARG;
+  if (nv12 && (nv12_pitch < h->W || (nv12_pitch & 1))) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  auto& pc = h->pc;
+  std::lock_guard<std::mutex> lk(pc.mu);
+  if (!pc.stream) HIP_TRY(h, hipStreamCreateWithFlags(&pc.stream, hipStreamNonBlocking));
+  if (!pc.ev) HIP_TRY(h, hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
+  const int W = h->W, H = h->H, step = cam->step;
+  const int Wo = (W + step - 1) / step, Ho = (H + step - 1) / step;
+  const int tiles = (Ho * Wo + kPcTile - 1) / kPcTile;
+  const size_t raw_bytes = (size_t)n * H * W * 4, pts_bytes = (size_t)n * Ho * Wo * 16;
+  const size_t frame = (size_t)nv12_pitch * (H + (H + 1) / 2);    // an odd height has ceil(H/2) chroma rows
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : pc.stream;
+  HIP_TRY(h, hipStreamWaitEvent(st, pc.ev, 0));      // the previous call (any stream) is done with the scratch
+  if (layout == SN_PC_COMPACT && (size_t)n * tiles * 4 > pc.scratch_bytes) {
+    HIP_TRY(h, hipEventSynchronize(pc.ev));
+    HIP_TRY(h, pc_grow(reinterpret_cast<void**>(&pc.scratch), &pc.scratch_bytes, (size_t)n * tiles * 4, false));
+  }
+  PcArgs a{raw, nv12, reinterpret_cast<float4*>(points), counts, pc.scratch, frame, W, H, Wo, Ho, step, nv12_pitch, tiles,
+           kOutScale, cam->fx * cam->baseline_mm, cam->fx, cam->fy, cam->cx, cam->cy, cam->z_min_m, cam->z_max_m, 0};
+  if (mem == SN_MEM_HOST) {
+    HIP_TRY(h, pc_grow(&pc.pin[0], &pc.pin_bytes[0], raw_bytes, true));
+    HIP_TRY(h, pc_grow(&pc.dev[0], &pc.dev_bytes[0], raw_bytes, false));
+    HIP_TRY(h, pc_grow(&pc.dev[2], &pc.dev_bytes[2], pts_bytes, false));
+    HIP_TRY(h, pc_grow(&pc.dev[3], &pc.dev_bytes[3], (size_t)n * 4, false));
+    memcpy(pc.pin[0], raw, raw_bytes);
+    HIP_TRY(h, hipMemcpyAsync(pc.dev[0], pc.pin[0], raw_bytes, hipMemcpyHostToDevice, st));
+    if (nv12) {
+      HIP_TRY(h, pc_grow(&pc.pin[1], &pc.pin_bytes[1], n * frame, true));
+      HIP_TRY(h, pc_grow(&pc.dev[1], &pc.dev_bytes[1], n * frame, false));
+      memcpy(pc.pin[1], nv12, n * frame);
+      HIP_TRY(h, hipMemcpyAsync(pc.dev[1], pc.pin[1], n * frame, hipMemcpyHostToDevice, st));
+      a.nv12 = static_cast<const uint8_t*>(pc.dev[1]);
+    }
+    a.raw = static_cast<const int32_t*>(pc.dev[0]);
+    a.pts = static_cast<float4*>(pc.dev[2]);
+    a.counts = counts ? static_cast<uint32_t*>(pc.dev[3]) : nullptr;
+  }
+  a.vec = step == 1 && (W & 3) == 0 && ((uintptr_t)a.raw & 15) == 0;
+  if (layout == SN_PC_ORGANISED) {
+    if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 4, st));
+    const int nseg = Ho * ((Wo + 255) / 256);            // 256-column row segments, one per wave and iteration
+    const int per_map = std::max(1, std::min((nseg + 3) / 4, 2048 / n));
+    if (a.nv12) hipLaunchKernelGGL(k_pc_organised<true>, dim3(per_map, n), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_pc_organised<false>, dim3(per_map, n), dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(k_pc_count, dim3(tiles, n), dim3(256), 0, st, a);
+    if (a.nv12) hipLaunchKernelGGL(k_pc_write<true>, dim3(tiles, n), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_pc_write<false>, dim3(tiles, n), dim3(256), 0, st, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(pc.ev, st));
+  if (mem == SN_MEM_HOST) {
+    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, a.counts, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (layout == SN_PC_ORGANISED) {
+      HIP_TRY(h, hipMemcpyAsync(points, a.pts, pts_bytes, hipMemcpyDeviceToHost, st));
+    } else {
+      HIP_TRY(h, hipStreamSynchronize(st));      // the counts say how much of every map to copy
+      for (int k = 0; k < n; ++k)
+        if (counts[k])
+          HIP_TRY(h, hipMemcpyAsync(points + (size_t)k * Ho * Wo * 4, a.pts + (size_t)k * Ho * Wo, (size_t)counts[k] * 16,
+                                    hipMemcpyDeviceToHost, st));
+    }
+  }
+  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }
 

@@ -3,11 +3,12 @@
 D1) needed to score the output against dataset ground truth.
 
     python -m hobot_stereonet_amd.filelist --model m.snw --left left.list --right right.list \
-        [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32]
+        [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
+        [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
-GPU) -> int32 wire tensor + float disparity.  Error behaviour mirrors the reference: an unreadable list, a
+GPU) -> int32 wire tensor + float disparity [-> coloured point cloud, `sn_pointcloud_from_raw`, one PLY per pair].  Error behaviour mirrors the reference: an unreadable list, a
 missing image or lists of different length stop the run before any inference.  There is no CPU path.
 """
 import argparse
@@ -82,16 +83,18 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
-                gt_list: Optional[str] = None, log=None) -> List[dict]:
+                gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
-    {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"]}; with `out_dir` also
-    writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map)."""
+    {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
+    writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
+    compact point cloud of the pair coloured by its left eye (camera: pointcloud.Camera, default intrinsics if None)."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
         raise FileListError(f"Imgs size error! left_imgs.size: {len(left)}, gt.size: {len(gts)}")
-    if out_dir:
-        os.makedirs(out_dir, exist_ok=True)
+    for d in (out_dir, ply_dir):
+        if d:
+            os.makedirs(d, exist_ok=True)
     w, h = engine.width, engine.height
     results = []
     for i, (lp, rp) in enumerate(zip(left, right)):
@@ -103,8 +106,13 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             if bgr.shape[:2] != (h, w):
                 raise FileListError(f"BGRToNv12 Fail: {p} is {bgr.shape[1]}x{bgr.shape[0]}, model input is {w}x{h}")
             eyes.append(images.bgr_to_nv12(bgr))
-        disp, raw = engine.infer_sbs_nv12(images.sbs_from_eyes(eyes[0], eyes[1], w, h))
+        sbs = images.sbs_from_eyes(eyes[0], eyes[1], w, h)
+        disp, raw = engine.infer_sbs_nv12(sbs)
         rec = {"frame_id": str(i), "left": lp, "right": rp, "raw": raw, "disp": disp}
+        if ply_dir:
+            from . import pointcloud
+            pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
+            rec["points"] = pointcloud.write_ply(os.path.join(ply_dir, f"{i}.ply"), pts, int(cnt[0]))
         if gts is not None:
             gt, valid = images.read_disparity(gts[i])
             rec["metrics"] = score(disp, gt, valid, float(engine.dmax))
@@ -127,13 +135,23 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default=None)
     ap.add_argument("--precision", choices=["auto", "f16", "f16x3", "fp32"], default="auto")
     ap.add_argument("--device", type=int, default=-1)
+    ap.add_argument("--ply", default=None, metavar="DIR", help="write <i>.ply, the pair's coloured point cloud (GPU)")
+    ap.add_argument("--camera", default=None, metavar="fx,fy,cx,cy,baseline_mm",
+                    help="intrinsics of the rectified left eye for --ply (default: the reference's, centred)")
     args = ap.parse_args(argv)
-    from . import api
+    from . import api, pointcloud
+    cam = None
+    if args.camera:
+        v = [float(t) for t in args.camera.split(",")]
+        if len(v) != 5:
+            ap.error("--camera takes fx,fy,cx,cy,baseline_mm")
+        cam = pointcloud.Camera(fx=v[0], fy=v[1], cx=v[2], cy=v[3], baseline_mm=v[4])
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
-            recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr))
+            recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
+                               ply_dir=args.ply, camera=cam)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5

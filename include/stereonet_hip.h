@@ -132,7 +132,9 @@ int sn_destroy(sn_handle *h);
 int sn_get_io_info(const sn_handle *h, sn_io_info *info);
 const char *sn_strerror(int code);
 const char *sn_last_error(const sn_handle *h);   /* detail of the last failure on this handle; h = NULL: of the
-                                                  * last failed sn_create on the calling thread */
+                                                  * last failed sn_create on the calling thread.  Safe beside calls on
+                                                  * other threads: the text is copied for the calling thread and stays
+                                                  * valid until its next sn_last_error */
 
 /* Refinement statistic and SN_PREC_AUTO --------------------------------------------------------------------------
  * The reference loads an opaque model_file and only checks that it exists (stereonet_node.cpp:131-136); whether the
@@ -357,6 +359,43 @@ int sn_dbg_read(sn_handle *h, const char *what, float *dst, size_t cap, size_t *
  * raw / depth_m: host or device buffers per `mem`; disp_px (nullable) receives dis * 16 * 12 as Parse's disparity. */
 int sn_depth_from_raw(sn_handle *h, int n, const int32_t *raw, float focal_px, float baseline_mm, float *depth_m,
                       float *disp_px, int mem, void *stream);
+
+/* ---- point cloud from the int32 map (what a sensor_msgs/PointCloud2 carries) --------------------------------------------
+ * Camera of the rectified left eye, in pixels of the model's W x H map. */
+typedef struct sn_camera {
+  float fx, fy, cx, cy;   /* pinhole intrinsics                                                                     */
+  float baseline_mm;      /* as sn_depth_from_raw (the reference's 119.89382172)                                    */
+  float z_min_m, z_max_m; /* keep points with z_min_m <= Z <= z_max_m; z_max_m <= 0: no upper bound                 */
+  int step;               /* 1, 2 or 4: every step-th row and column from 0; Ho = ceil(H/step), Wo = ceil(W/step)    */
+} sn_camera;
+enum { SN_PC_ORGANISED = 0, SN_PC_COMPACT = 1 };
+/* n maps raw [n][H][W] -> points, 16 bytes {X, Y, Z, rgb} per point (`points` 16-byte aligned).  For output sample (i, j),
+ * u = j*step, v = i*step, r = raw[k][v][u]:
+ *   Z = sn_depth_from_raw's depth with focal_px = fx (the same float / double mix, bit for bit):
+ *       Z = (float)((double)(fx * baseline_mm) / ((double)((float)r * out_scale) * 16.0 * 12.0) / 1000.0)
+ *   X = ((float)u - cx) * Z / fx,  Y = ((float)v - cy) * Z / fy   (fp32, left to right, every step rounded, no FMA)
+ *   valid: r > 0 && z_min_m <= Z && (z_max_m <= 0 || Z <= z_max_m)
+ *   rgb: 0 without colour (nv12 == NULL); else the PCL packing 0x00RRGGBB of NV12 frame k.  nv12 holds n frames of
+ *       F = nv12_pitch*(H + ceil(H/2)) bytes each (H luma rows, then ceil(H/2) interleaved chroma rows; for an even H that
+ *       is nv12_pitch*H*3/2), frame k at nv12 + k*F (luma pitch nv12_pitch: W for a plain left image, 2W for FeedImg's
+ *       side-by-side frame, whose left eye is the left half of every row), uv = frame + nv12_pitch*H,
+ *       Y = y[v*pitch + u], U = uv[(v>>1)*pitch + (u&~1)], V = the byte after it (true NV12), and JFIF full-range BT.601
+ *       in integers (>> arithmetic, clamp to 0..255): Uc = U-128, Vc = V-128,
+ *       R = clamp(Y + ((91881*Vc + 32768) >> 16)), G = clamp(Y + ((-22554*Uc - 46802*Vc + 32768) >> 16)),
+ *       B = clamp(Y + ((116130*Uc + 32768) >> 16))
+ * SN_PC_ORGANISED: points [n][Ho][Wo][4]; an invalid sample is {0x7fc00000 x 3, 0} as bits; counts (nullable) [n] = valid
+ *   samples per map.
+ * SN_PC_COMPACT: map k's valid points in raster order from points + k*Ho*Wo*4, counts [n] (required) = how many; the
+ *   words past the count are unspecified.
+ * mem / stream as sn_depth_from_raw, except that a NULL stream is the point cloud's own stream (never the inference
+ * stream); the call returns after completion when mem is SN_MEM_HOST or stream is NULL.  SN_ERR_ARG: n outside
+ * 1..max_batch, a required pointer NULL, points misaligned, fx or fy <= 0 or not finite, baseline_mm <= 0, step not 1/2/4,
+ * unknown layout, nv12 with nv12_pitch < W or odd.
+ * May run concurrently with sn_submit / sn_wait on the same handle: it has its own stream, scratch and staging (created
+ * on first use, reused, freed by sn_destroy), and device-mode calls on different streams are ordered on that scratch by an
+ * event. */
+int sn_pointcloud_from_raw(sn_handle *h, int n, const int32_t *raw, const uint8_t *nv12, int nv12_pitch,
+                           const sn_camera *cam, int layout, float *points, uint32_t *counts, int mem, void *stream);
 
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
