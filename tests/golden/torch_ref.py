@@ -1,8 +1,13 @@
-"""SN-K4 expressed with torch.nn.functional on CPU (fp32) — an independent
-second implementation used to validate the C oracle.  This is not
+"""SN-K4 expressed with torch.nn.functional on CPU — an independent second implementation used to validate the C
+oracle, in fp32 (the default; the committed goldens) or, with dtype=torch.float64, as the ground truth
+every precision mode and the oracle itself are judged against (`truth`).  The dtype is passed down
+explicitly: the suite shares one process, so the process-global default dtype is never touched.  This is not
 reference code: the reference has no network arithmetic.
 """
 from __future__ import annotations
+
+import contextlib
+import os
 
 import numpy as np
 import torch
@@ -11,8 +16,8 @@ import torch.nn.functional as F
 from hobot_stereonet_amd import spec, weights as W
 
 
-def _t(blob, name):
-    return torch.from_numpy(W.tensor(blob, name).copy())
+def _t(blob, name, dtype=torch.float32):
+    return torch.from_numpy(W.tensor(blob, name).copy()).to(dtype)      # fp32 -> float64 widens exactly
 
 
 def lrelu(x):
@@ -20,23 +25,24 @@ def lrelu(x):
 
 
 def res_block(blob, prefix, x, dil):
-    t = lrelu(F.conv2d(x, _t(blob, prefix + ".1.w"), _t(blob, prefix + ".1.b"), padding=dil, dilation=dil))
-    t = F.conv2d(t, _t(blob, prefix + ".2.w"), _t(blob, prefix + ".2.b"), padding=dil, dilation=dil)
+    dt = x.dtype
+    t = lrelu(F.conv2d(x, _t(blob, prefix + ".1.w", dt), _t(blob, prefix + ".1.b", dt), padding=dil, dilation=dil))
+    t = F.conv2d(t, _t(blob, prefix + ".2.w", dt), _t(blob, prefix + ".2.b", dt), padding=dil, dilation=dil)
     return lrelu(x + t)
 
 
 def features(blob, planes):              # planes: (1,3,hp,wp)
-    x = planes
+    x, dt = planes, planes.dtype
     for i in range(spec.N_DOWN):
-        x = F.conv2d(x, _t(blob, f"feat.down{i}.w"), _t(blob, f"feat.down{i}.b"), stride=2, padding=2)
+        x = F.conv2d(x, _t(blob, f"feat.down{i}.w", dt), _t(blob, f"feat.down{i}.b", dt), stride=2, padding=2)
     for i in range(spec.N_FEAT_RES):
         x = res_block(blob, f"feat.res{i}", x, 1)
-    return F.conv2d(x, _t(blob, "feat.out.w"), _t(blob, "feat.out.b"), padding=1)
+    return F.conv2d(x, _t(blob, "feat.out.w", dt), _t(blob, "feat.out.b", dt), padding=1)
 
 
 def cost_volume(fl, fr, dl):             # (1,C,h,w) -> (1,C,dl,h,w)
     _, c, h, w = fl.shape
-    cv = torch.zeros(1, c, dl, h, w)
+    cv = torch.zeros(1, c, dl, h, w, dtype=fl.dtype)
     for d in range(dl):
         if d == 0:
             cv[:, :, 0] = fl - fr
@@ -46,24 +52,25 @@ def cost_volume(fl, fr, dl):             # (1,C,h,w) -> (1,C,dl,h,w)
 
 
 def aggregate(blob, fl, fr, dl):
-    x = cost_volume(fl, fr, dl)
+    x, dt = cost_volume(fl, fr, dl), fl.dtype
     for i in range(spec.N_AGG):
-        x = lrelu(F.conv3d(x, _t(blob, f"agg.conv{i}.w"), _t(blob, f"agg.conv{i}.b"), padding=1))
-    return F.conv3d(x, _t(blob, "agg.out.w"), _t(blob, "agg.out.b"), padding=1)[:, 0]   # (1,dl,h,w)
+        x = lrelu(F.conv3d(x, _t(blob, f"agg.conv{i}.w", dt), _t(blob, f"agg.conv{i}.b", dt), padding=1))
+    return F.conv3d(x, _t(blob, "agg.out.w", dt), _t(blob, "agg.out.b", dt), padding=1)[:, 0]   # (1,dl,h,w)
 
 
 def soft_argmin(cost):                   # (1,dl,h,w) -> (1,h,w)
     p = torch.softmax(-cost, dim=1)
-    d = torch.arange(cost.shape[1], dtype=torch.float32).view(1, -1, 1, 1)
+    d = torch.arange(cost.shape[1], dtype=cost.dtype).view(1, -1, 1, 1)
     return (p * d).sum(1)
 
 
 def refine(blob, disp_up, img, dmax, prefix="ref"):    # (1,1,hp,wp), (1,3,hp,wp)
+    dt = disp_up.dtype
     x = torch.cat([disp_up / dmax, img], 1)
-    x = lrelu(F.conv2d(x, _t(blob, prefix + ".in.w"), _t(blob, prefix + ".in.b"), padding=1))
+    x = lrelu(F.conv2d(x, _t(blob, prefix + ".in.w", dt), _t(blob, prefix + ".in.b", dt), padding=1))
     for i, dil in enumerate(spec.REF_DILATIONS):
         x = res_block(blob, f"{prefix}.res{i}", x, dil)
-    r = F.conv2d(x, _t(blob, prefix + ".out.w"), _t(blob, prefix + ".out.b"), padding=1)
+    r = F.conv2d(x, _t(blob, prefix + ".out.w", dt), _t(blob, prefix + ".out.b", dt), padding=1)
     return F.relu(disp_up + dmax * r)
 
 
@@ -81,12 +88,16 @@ def refine_multi(blob, low, img, dmax, levels):
     return d, per_level
 
 
-def forward(blob, in6: np.ndarray, dmax: int):
-    """in6 int8 (6,h,w) -> dict(disp (h,w) f32, disp_low, cost)"""
+def forward(blob, in6: np.ndarray, dmax: int, dtype=torch.float32):
+    """in6 int8 (6,h,w) -> dict(disp (h,w), disp_low, cost, fl, fr, levels), every array of `dtype`: float32 (the
+    committed goldens), or float64 with the int8 input / 128 and the fp32 weights widened exactly and no fp32 step"""
     _, h, w = in6.shape
     hp, wp = spec.ceil16(h), spec.ceil16(w)
-    x = torch.zeros(1, 6, hp, wp)
-    x[0, :, :h, :w] = torch.from_numpy(in6.astype(np.float32) / 128.0)
+    x = torch.zeros(1, 6, hp, wp, dtype=dtype)
+    if dtype == torch.float32:
+        x[0, :, :h, :w] = torch.from_numpy(in6.astype(np.float32) / 128.0)
+    else:
+        x[0, :, :h, :w] = torch.from_numpy(in6.astype(np.int32)).to(dtype) / 128.0       # exact: |in6| <= 128, / 2^7
     with torch.no_grad():
         fl = features(blob, x[:, :3])
         fr = features(blob, x[:, 3:])
@@ -101,3 +112,30 @@ def forward(blob, in6: np.ndarray, dmax: int):
             disp, per_level = refine_multi(blob, low, x[:, :3], dmax, levels)
     return {"levels": per_level, "disp": disp[0, 0, :h, :w].numpy().copy(), "disp_low": low[0].numpy().copy(),
             "cost": cost[0].numpy().copy(), "fl": fl[0].numpy().copy(), "fr": fr[0].numpy().copy()}
+
+
+def env_threads() -> int:
+    """The thread count the environment grants this process (OMP_NUM_THREADS, else the CPUs it may run on, 16 at the
+    most: the convolutions here do not scale further) — never the machine's CPU count, which on a shared box is many
+    times what one job may use."""
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        n = 0
+    return n if n > 0 else max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+@contextlib.contextmanager
+def torch_threads(n=None):
+    before = torch.get_num_threads()
+    torch.set_num_threads(n or env_threads())
+    try:
+        yield
+    finally:
+        torch.set_num_threads(before)
+
+
+def truth(blob, in6: np.ndarray, dmax: int):
+    """The float64 ground truth of one input: forward() in float64 -> dict(disp, disp_low, cost, fl, fr, levels)."""
+    with torch_threads():
+        return forward(blob, in6, dmax, torch.float64)

@@ -10,7 +10,10 @@ import pytest
 from hobot_stereonet_amd import spec, synth, weights
 
 CASES = [("c96x64_d48", 96, 64, 48, 3), ("c160x96_d96", 160, 96, 96, 4), ("c100x52_d32", 100, 52, 32, 5)]
-TOL = 2e-4   # px; fp32 summation-order noise between the C loops and torch's kernels
+# px; fp32 summation-order noise between the C loops and torch's kernels: twice the largest oracle-vs-torch-fp32 mean over
+# this file's cases (2.2e-5 at 160x96 D=96, 1.6e-5 at 112x80, 6.5e-6 at 96x64, 3.4e-6 at 100x52; both sit 2e-5 or less from
+# the float64 truth there, tests/test_truth64.py) — torch's fp32 conv kernels differ between builds, hence the factor
+TOL = 4.4e-5
 
 
 def sha(a):
