@@ -59,6 +59,15 @@ class SnCamera(C.Structure):
                 ("z_min_m", C.c_float), ("z_max_m", C.c_float), ("step", C.c_int)]
 
 
+class SnLrcParams(C.Structure):
+    """sn_lrc_params (include/stereonet_hip.h): tolerances of the left-right consistency check."""
+    _fields_ = [("tau_px", C.c_float), ("tau_rel", C.c_float), ("right_mirrored", C.c_int)]
+
+
+SN_LRC_KEPT, SN_LRC_INVALID_IN, SN_LRC_OUT_OF_VIEW, SN_LRC_NO_PARTNER, SN_LRC_INCONSISTENT = 0, 1, 2, 4, 8
+SN_LRC_IN_TENSOR, SN_LRC_IN_SBS_NV12 = 0, 1
+
+
 class StereoNetError(RuntimeError):
     def __init__(self, code: int, where: str, detail: str = ""):
         self.code = code
@@ -136,6 +145,9 @@ def load_library(path: Optional[str] = None):
     lib.sn_dbg_copy_limited.argtypes = [vp, vp, C.c_size_t, ip, vp]
     lib.sn_depth_from_raw.argtypes = [vp, ip, i32p, C.c_float, C.c_float, fp, fp, ip, vp]
     lib.sn_pointcloud_from_raw.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnCamera), ip, fp, vp, ip, vp]
+    lib.sn_mirror_pair_i8.argtypes = [vp, ip, i8p, i8p, ip, vp]
+    lib.sn_lr_check.argtypes = [vp, ip, i32p, i32p, C.POINTER(SnLrcParams), i32p, fp, u8p, vp, ip, vp]
+    lib.sn_infer_lrc.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnLrcParams), i32p, fp, i32p, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
     lib.sn_auto_init.argtypes = [C.POINTER(SnAutoState), ip]
     lib.sn_auto_observe.argtypes = [C.POINTER(SnAutoState), C.c_double]
@@ -147,7 +159,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -395,6 +407,105 @@ class StereoNetHIP:
         self._check(self._lib.sn_pointcloud_from_raw(self._h, n, raw_ptr, nv12_ptr or None, nv12_pitch, C.byref(c), layout,
                                                      points_ptr, counts_ptr or None, SN_MEM_DEVICE, stream or None),
                     "sn_pointcloud_from_raw")
+
+    # -- left-right consistency check -----------------------------------------------------------------
+    def _maps(self, a, where: str, dtype=np.int32) -> np.ndarray:
+        r = np.ascontiguousarray(a, dtype=dtype)
+        # the calls move n * H * W elements of the MODEL's size: anything else would run past these arrays
+        if r.ndim not in (2, 3) or r.shape[-2:] != (self.height, self.width):
+            raise StereoNetError(-1, where, f"map shape {r.shape} != ([n,] {self.height}, {self.width})")
+        n = 1 if r.ndim == 2 else r.shape[0]
+        if n < 1 or n > self.max_batch:
+            raise StereoNetError(-1, where, f"{n} maps, the engine was created for 1..{self.max_batch}")
+        return r
+
+    def mirror_pair(self, in6: np.ndarray) -> np.ndarray:
+        """sn_mirror_pair_i8 on host buffers: int8 (6,H,W) or (n,6,H,W) -> the pair with the eyes swapped and every row
+        reversed (lrcheck.mirror_pair is the numpy twin)."""
+        x = np.ascontiguousarray(in6, dtype=np.int8)
+        if x.ndim not in (3, 4) or x.shape[-3:] != (6, self.height, self.width):
+            raise StereoNetError(-1, "mirror_pair", f"input shape {x.shape} != ([n,] 6, {self.height}, {self.width})")
+        n = 1 if x.ndim == 3 else x.shape[0]
+        out = np.empty_like(x)
+        self._check(self._lib.sn_mirror_pair_i8(self._h, n, x.ctypes.data, out.ctypes.data, SN_MEM_HOST, None),
+                    "sn_mirror_pair_i8")
+        return out
+
+    def mirror_pair_device(self, n: int, in_ptr: int, out_ptr: int, stream: int = 0):
+        self._check(self._lib.sn_mirror_pair_i8(self._h, n, in_ptr, out_ptr, SN_MEM_DEVICE, stream or None),
+                    "sn_mirror_pair_i8")
+
+    def lr_check(self, raw_left: np.ndarray, raw_right: np.ndarray, tau_px: float = 1.0, tau_rel: float = 0.0,
+                 mirrored: bool = False, disp: Optional[np.ndarray] = None):
+        """sn_lr_check on host buffers: int32 (H,W) or (n,H,W) maps -> (out_raw int32, mask uint8, kept uint32 (n,)); `disp`
+        (float32, same shape) gets 0.0 written IN PLACE at the rejected pixels.  mirrored: raw_right is stored
+        column-reversed, as the network wrote the map of the mirrored pair.  lrcheck.reference is the numpy twin."""
+        l = self._maps(raw_left, "lr_check")
+        r = self._maps(raw_right, "lr_check")
+        if l.shape != r.shape:
+            raise StereoNetError(-1, "lr_check", f"maps of shape {l.shape} and {r.shape}")
+        if disp is not None and (disp.dtype != np.float32 or disp.shape != l.shape or not disp.flags.c_contiguous):
+            raise StereoNetError(-1, "lr_check", "disp must be a C-contiguous float32 array of the maps' shape")
+        n = 1 if l.ndim == 2 else l.shape[0]
+        out = np.empty_like(l)
+        mask = np.empty(l.shape, np.uint8)
+        kept = np.zeros(n, np.uint32)
+        p = SnLrcParams(tau_px, tau_rel, int(bool(mirrored)))
+        self._check(self._lib.sn_lr_check(self._h, n, l.ctypes.data, r.ctypes.data, C.byref(p), out.ctypes.data,
+                                          _np_ptr(disp), mask.ctypes.data, kept.ctypes.data, SN_MEM_HOST, None), "sn_lr_check")
+        return out, mask, kept
+
+    def lr_check_device(self, n: int, left_ptr: int, right_ptr: int, tau_px: float, tau_rel: float, mirrored: bool,
+                        out_raw_ptr: int = 0, disp_ptr: int = 0, mask_ptr: int = 0, kept_ptr: int = 0, stream: int = 0):
+        """sn_lr_check on device pointers (out_raw_ptr may equal left_ptr); stream = hipStream_t as int."""
+        p = SnLrcParams(tau_px, tau_rel, int(bool(mirrored)))
+        self._check(self._lib.sn_lr_check(self._h, n, left_ptr, right_ptr, C.byref(p), out_raw_ptr or None, disp_ptr or None,
+                                          mask_ptr or None, kept_ptr or None, SN_MEM_DEVICE, stream or None), "sn_lr_check")
+
+    def infer_lrc(self, x: np.ndarray, tau_px: float = 1.0, tau_rel: float = 0.0, want_right: bool = False):
+        """sn_infer_lrc on host buffers.  x: the int8 model tensor (6,H,W) / (n,6,H,W), or uint8 side-by-side NV12 frames
+        (3*H*W bytes each: flat, or (n, 3*H*W)).  -> (disp float32, raw int32, mask uint8, kept uint32 (n,)[, right_raw
+        int32]): the left map with rejected pixels at 0, the reason per pixel, kept pixels per map and, with want_right, the
+        right eye's own map in right-image coordinates (unmasked).  The leading n is dropped for a single tensor / frame."""
+        a = np.asarray(x)
+        frame = 3 * self.width * self.height
+        if a.dtype == np.uint8:
+            kind = SN_LRC_IN_SBS_NV12
+            single = a.ndim == 1 or a.size == frame
+            a = np.ascontiguousarray(a).reshape(-1)
+            if a.size == 0 or a.size % frame:
+                raise StereoNetError(-1, "infer_lrc", f"{a.size} bytes are not side-by-side NV12 frames of {frame} bytes")
+            n = a.size // frame
+        else:
+            kind = SN_LRC_IN_TENSOR
+            a = np.ascontiguousarray(a, dtype=np.int8)
+            single = a.ndim == 3
+            if a.ndim not in (3, 4) or a.shape[-3:] != (6, self.height, self.width):
+                raise StereoNetError(-1, "infer_lrc", f"input shape {a.shape} != ([n,] 6, {self.height}, {self.width})")
+            n = 1 if single else a.shape[0]
+        shape = (n, self.height, self.width)
+        disp, raw = np.empty(shape, np.float32), np.empty(shape, np.int32)
+        mask, kept = np.empty(shape, np.uint8), np.zeros(n, np.uint32)
+        right = np.empty(shape, np.int32) if want_right else None
+        p = SnLrcParams(tau_px, tau_rel, 1)
+        self._check(self._lib.sn_infer_lrc(self._h, n, a.ctypes.data, kind, 2 * self.width, self.height, C.byref(p),
+                                           raw.ctypes.data, disp.ctypes.data, _np_ptr(right), mask.ctypes.data,
+                                           kept.ctypes.data, SN_MEM_HOST, None), "sn_infer_lrc")
+        out = [disp, raw, mask] if not single else [disp[0], raw[0], mask[0]]
+        out.append(kept)
+        if want_right:
+            out.append(right[0] if single else right)
+        return tuple(out)
+
+    def infer_lrc_device(self, n: int, in_ptr: int, tau_px: float, tau_rel: float, raw_ptr: int = 0, disp_ptr: int = 0,
+                         right_ptr: int = 0, mask_ptr: int = 0, kept_ptr: int = 0, in_kind: int = SN_LRC_IN_TENSOR,
+                         stream: int = 0):
+        """sn_infer_lrc on device pointers (e.g. torch tensors' data_ptr()); stream = hipStream_t as int (0: the engine's own
+        stream, and the call returns after completion)."""
+        p = SnLrcParams(tau_px, tau_rel, 1)
+        self._check(self._lib.sn_infer_lrc(self._h, n, in_ptr, in_kind, 2 * self.width, self.height, C.byref(p),
+                                           raw_ptr or None, disp_ptr or None, right_ptr or None, mask_ptr or None,
+                                           kept_ptr or None, SN_MEM_DEVICE, stream or None), "sn_infer_lrc")
 
     def synchronize(self):
         self._check(self._lib.sn_synchronize(self._h), "sn_synchronize")

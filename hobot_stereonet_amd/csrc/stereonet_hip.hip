@@ -28,6 +28,7 @@
 #include "sn_internal.h"
 #include "sn_kernels.hpp"
 #include "sn_pointcloud.hpp"
+#include "sn_lrcheck.hpp"
 
 namespace {
 
@@ -251,6 +252,12 @@ struct sn_handle {
     void* pin[2] = {};                 // host mode: pinned staging of raw and nv12
     size_t pin_bytes[2] = {};
   } pc;
+  // sn_mirror_pair_i8 / sn_lr_check / sn_infer_lrc: device buffers of their own, created on first use and only ever grown
+  struct LrCheck {
+    enum { kIn = 0, kMirror, kLeft, kRight, kDisp, kRightOut, kMask, kKept, kCount };
+    void* dev[kCount] = {};            // input tensor, mirrored tensor, left map, second map, float map, right map, mask, kept
+    size_t dev_bytes[kCount] = {};
+  } lrc;
 };
 
 namespace {
@@ -2448,6 +2455,7 @@ int sn_destroy(sn_handle* h) {
     if (p) hipHostFree(p);
   if (h->pc.ev) hipEventDestroy(h->pc.ev);
   if (h->pc.stream) hipStreamDestroy(h->pc.stream);
+  for (void* p : h->lrc.dev) hipFree(p);
   hipFree(h->aout.w);
   hipFree(h->aout.pfrag);
   for (auto p : h->chk) hipFree(p);
@@ -3824,6 +3832,196 @@ int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_
     }
   }
   if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// ---- left-right consistency check (csrc/sn_lrcheck.hpp) --------------------------------------------------------------
+static bool lrc_params_ok(const sn_lrc_params* p) {
+  return p && std::isfinite(p->tau_px) && std::isfinite(p->tau_rel) && p->tau_px >= 0.f && p->tau_rel >= 0.f;
+}
+
+// buffer `which` of the handle's LrCheck state, at least `bytes` large (nullptr: the allocation failed)
+static void* lrc_buf(sn_handle* h, int which, size_t bytes) {
+  return pc_grow(&h->lrc.dev[which], &h->lrc.dev_bytes[which], bytes, false) == hipSuccess ? h->lrc.dev[which] : nullptr;
+}
+#define LRC_BUF(h, dst, type, which, bytes)                                     \
+  do {                                                                          \
+    if (!((dst) = static_cast<type>(lrc_buf(h, sn_handle::LrCheck::which, bytes)))) {   \
+      set_err(h, "left-right check: out of device memory");                     \
+      return SN_ERR_NOMEM;                                                      \
+    }                                                                           \
+  } while (0)
+
+static int mirror_launch(sn_handle* h, hipStream_t st, int n, const int8_t* in, int8_t* out) {
+  MirrorArgs a{in, out, n, h->H, h->W};
+  const bool vec = (h->W & 15) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+  const size_t items = (size_t)n * 6 * h->H * (vec ? h->W >> 4 : h->W);
+  const unsigned grid = (unsigned)std::min<size_t>((items + 255) / 256, 8192);
+  if (vec) hipLaunchKernelGGL(k_mirror_pair<true>, dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_mirror_pair<false>, dim3(grid), dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+// device pointers; right_out (nullable) receives the right map in right-image coordinates
+static int lrc_launch(sn_handle* h, hipStream_t st, int n, const int32_t* left, const int32_t* right, const sn_lrc_params* p,
+                      int32_t* out_raw, float* disp, uint8_t* mask, uint32_t* kept, int32_t* right_out) {
+  LrcArgs a{left, right, out_raw, disp, mask, kept, right_out, h->W, h->H, (float)((double)kOutScale * kWireFactor),
+            p->tau_px, p->tau_rel, p->right_mirrored != 0};
+  const bool vec = (h->W & 3) == 0 &&
+                   (((uintptr_t)left | (uintptr_t)right | (uintptr_t)out_raw | (uintptr_t)right_out) & 15) == 0 &&
+                   ((uintptr_t)mask & 3) == 0;
+  if (kept) HIP_TRY(h, hipMemsetAsync(kept, 0, (size_t)n * 4, st));
+  const int nseg = h->H * ((h->W + 255) / 256);
+  const int per_map = std::max(1, std::min((nseg + 3) / 4, 4096 / n));
+  if (vec) hipLaunchKernelGGL(k_lr_check<true>, dim3(per_map, n), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_lr_check<false>, dim3(per_map, n), dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+int sn_mirror_pair_i8(sn_handle* h, int n, const int8_t* in, int8_t* out, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  const size_t bytes = (size_t)(n > 0 ? n : 0) * 6 * h->H * h->W;
+  if (!in || !out || n <= 0 || n > h->max_batch || (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) ||
+      ((uintptr_t)in < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)in + bytes)) {
+    set_err(h, "sn_mirror_pair_i8: bad arguments");
+    return SN_ERR_ARG;
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  const int8_t* din = in;
+  int8_t* dout = out;
+  if (mem == SN_MEM_HOST) {
+    int8_t* stage;
+    LRC_BUF(h, stage, int8_t*, kIn, bytes);
+    LRC_BUF(h, dout, int8_t*, kMirror, bytes);
+    HIP_TRY(h, hipMemcpyAsync(stage, in, bytes, hipMemcpyHostToDevice, st));
+    din = stage;
+  }
+  if ((rc = mirror_launch(h, st, n, din, dout))) return rc;
+  if (mem == SN_MEM_HOST) HIP_TRY(h, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
+  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+int sn_lr_check(sn_handle* h, int n, const int32_t* raw_left, const int32_t* raw_right, const sn_lrc_params* p,
+                int32_t* out_raw, float* disp_inout, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!raw_left || !raw_right || !lrc_params_ok(p) || (!out_raw && !mask) || n <= 0 || n > h->max_batch ||
+      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) {
+    set_err(h, "sn_lr_check: bad arguments");
+    return SN_ERR_ARG;
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  const size_t cnt = (size_t)n * h->H * h->W;
+  const int32_t *dl = raw_left, *dr = raw_right;
+  int32_t* dout = out_raw;
+  float* ddisp = disp_inout;
+  uint8_t* dmask = mask;
+  uint32_t* dkept = kept;
+  if (mem == SN_MEM_HOST) {
+    int32_t *l, *r;
+    LRC_BUF(h, l, int32_t*, kLeft, cnt * 4);
+    LRC_BUF(h, r, int32_t*, kRight, cnt * 4);
+    HIP_TRY(h, hipMemcpyAsync(l, raw_left, cnt * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(r, raw_right, cnt * 4, hipMemcpyHostToDevice, st));
+    dl = l;
+    dr = r;
+    dout = out_raw ? l : nullptr;            // masked in place
+    if (disp_inout) {
+      LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
+      HIP_TRY(h, hipMemcpyAsync(ddisp, disp_inout, cnt * 4, hipMemcpyHostToDevice, st));
+    }
+    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
+    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
+  }
+  if ((rc = lrc_launch(h, st, n, dl, dr, p, dout, ddisp, dmask, dkept, nullptr))) return rc;
+  if (mem == SN_MEM_HOST) {
+    if (out_raw) HIP_TRY(h, hipMemcpyAsync(out_raw, dout, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (disp_inout) HIP_TRY(h, hipMemcpyAsync(disp_inout, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
+    if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// L = forward(in), M = forward(mirror(in)), then the check of L against M in its mirrored storage: two run_forward calls, so
+// each is counted, folded into the refinement statistic and (SN_PREC_AUTO, blocking) repeated by the usual rule.
+int sn_infer_lrc(sn_handle* h, int n, const void* in, int in_kind, int w2, int h_px, const sn_lrc_params* p, int32_t* out_i32,
+                 float* out_disp, int32_t* out_right_i32, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!in || !lrc_params_ok(p) || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch ||
+      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) || (in_kind != SN_LRC_IN_TENSOR && in_kind != SN_LRC_IN_SBS_NV12)) {
+    set_err(h, "sn_infer_lrc: bad arguments");
+    return SN_ERR_ARG;
+  }
+  if (in_kind == SN_LRC_IN_SBS_NV12 && (!pre_args_ok(h, w2 / 2, h_px) || (w2 & 7) || (h_px & 1) ||
+                                        (mem == SN_MEM_DEVICE && ((uintptr_t)in & 3)))) {
+    set_err(h, "sn_infer_lrc: image size does not match the model input");
+    return SN_ERR_ARG;
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  const bool host = mem == SN_MEM_HOST, blocking = host || !stream;
+  const size_t HW = (size_t)h->H * h->W, cnt = (size_t)n * HW;
+  const int8_t* din = static_cast<const int8_t*>(in);
+  int8_t* dmir;
+  int32_t *dleft = out_i32, *dsecond, *dright = out_right_i32;
+  float* ddisp = out_disp;
+  uint8_t* dmask = mask;
+  uint32_t* dkept = kept;
+  LRC_BUF(h, dmir, int8_t*, kMirror, cnt * 6);
+  LRC_BUF(h, dsecond, int32_t*, kRight, cnt * 4);
+  if (host || !out_i32) LRC_BUF(h, dleft, int32_t*, kLeft, cnt * 4);
+  if (host) {
+    if (out_disp) LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
+    if (out_right_i32) LRC_BUF(h, dright, int32_t*, kRightOut, cnt * 4);
+    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
+    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
+  }
+  if (in_kind == SN_LRC_IN_SBS_NV12) {
+    int8_t* ten;
+    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
+    const int w = w2 / 2;
+    const long total = 6L * h_px * (w >> 2);
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    for (int i = 0; i < n; ++i) {
+      const uint8_t* src = static_cast<const uint8_t*>(in) + (size_t)i * 3 * HW;
+      if (host) {                         // one frame at a time through the NV12 staging buffer
+        HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, src, 3 * HW, hipMemcpyHostToDevice, st));
+        src = h->ws.nv12;
+      }
+      hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, src, src + w, w2, w, h_px, ten + (size_t)i * 6 * HW);
+    }
+    HIP_TRY(h, hipGetLastError());
+    din = ten;
+  } else if (host) {
+    int8_t* ten;
+    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
+    HIP_TRY(h, hipMemcpyAsync(ten, in, cnt * 6, hipMemcpyHostToDevice, st));
+    din = ten;
+  }
+  auto nothing = []() -> int { return SN_OK; };
+  if ((rc = run_forward(h, st, n, din, ddisp, dleft, n == 1, blocking, nothing))) return rc;
+  if ((rc = mirror_launch(h, st, n, din, dmir))) return rc;
+  if ((rc = run_forward(h, st, n, dmir, nullptr, dsecond, false, blocking, nothing))) return rc;
+  sn_lrc_params q = *p;
+  q.right_mirrored = 1;
+  if ((rc = lrc_launch(h, st, n, dleft, dsecond, &q, dleft, ddisp, dmask, dkept, dright))) return rc;
+  if (host) {
+    if (out_i32) HIP_TRY(h, hipMemcpyAsync(out_i32, dleft, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (out_disp) HIP_TRY(h, hipMemcpyAsync(out_disp, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (out_right_i32) HIP_TRY(h, hipMemcpyAsync(out_right_i32, dright, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
+    if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (blocking) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }
 

@@ -4,12 +4,16 @@ D1) needed to score the output against dataset ground truth.
 
     python -m hobot_stereonet_amd.filelist --model m.snw --left left.list --right right.list \
         [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
-        [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]]
+        [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
 GPU) -> int32 wire tensor + float disparity [-> coloured point cloud, `sn_pointcloud_from_raw`, one PLY per pair].  Error behaviour mirrors the reference: an unreadable list, a
 missing image or lists of different length stop the run before any inference.  There is no CPU path.
+
+--lrc runs every pair through the left-right consistency check (`sn_infer_lrc`: a second forward on the mirrored pair, then
+the check of the two maps): pixels the right eye does not confirm get raw = 0 in every output, <i>.mask.pgm holds the reason per
+pixel (lrcheck.REASONS), the metrics are taken over kept pixels with ground truth, and the summary gains "density".
 """
 import argparse
 import json
@@ -83,11 +87,14 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
-                gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None) -> List[dict]:
+                gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
+                lrc=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
-    compact point cloud of the pair coloured by its left eye (camera: pointcloud.Camera, default intrinsics if None)."""
+    compact point cloud of the pair coloured by its left eye (camera: pointcloud.Camera, default intrinsics if None).
+    lrc = (tau_px, tau_rel): the maps are those of engine.infer_lrc (rejected pixels at 0), the record gains "mask" and
+    "density", <i>.mask.pgm is written beside the other files and the metrics cover kept pixels only."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -107,14 +114,22 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
                 raise FileListError(f"BGRToNv12 Fail: {p} is {bgr.shape[1]}x{bgr.shape[0]}, model input is {w}x{h}")
             eyes.append(images.bgr_to_nv12(bgr))
         sbs = images.sbs_from_eyes(eyes[0], eyes[1], w, h)
-        disp, raw = engine.infer_sbs_nv12(sbs)
+        if lrc is None:
+            disp, raw = engine.infer_sbs_nv12(sbs)
+        else:
+            disp, raw, mask, kept = engine.infer_lrc(sbs, lrc[0], lrc[1])
         rec = {"frame_id": str(i), "left": lp, "right": rp, "raw": raw, "disp": disp}
+        if lrc is not None:
+            rec["mask"] = mask
+            rec["density"] = float(kept[0]) / float(w * h)
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
             rec["points"] = pointcloud.write_ply(os.path.join(ply_dir, f"{i}.ply"), pts, int(cnt[0]))
         if gts is not None:
             gt, valid = images.read_disparity(gts[i])
+            if lrc is not None:
+                valid = (mask == 0) if valid is None else (valid & (mask == 0))
             rec["metrics"] = score(disp, gt, valid, float(engine.dmax))
         if out_dir:
             raw.tofile(os.path.join(out_dir, f"{i}.raw.bin"))
@@ -122,6 +137,8 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             from . import render
             _, depth = render.disparity_and_depth(raw.view(np.uint32))
             images.write_ppm(os.path.join(out_dir, f"{i}.depth.ppm"), render.colorize_depth(depth)[..., ::-1])
+            if lrc is not None:
+                images.write_ppm(os.path.join(out_dir, f"{i}.mask.pgm"), mask)      # 2-D: written as a P5 greymap
         results.append(rec)
     return results
 
@@ -138,6 +155,9 @@ def main(argv=None) -> int:
     ap.add_argument("--ply", default=None, metavar="DIR", help="write <i>.ply, the pair's coloured point cloud (GPU)")
     ap.add_argument("--camera", default=None, metavar="fx,fy,cx,cy,baseline_mm",
                     help="intrinsics of the rectified left eye for --ply (default: the reference's, centred)")
+    ap.add_argument("--lrc", default=None, metavar="TAU_PX[,TAU_REL]",
+                    help="left-right consistency check: drop pixels whose right-eye disparity differs by more than "
+                         "TAU_PX + TAU_REL * disparity px (one more forward per pair)")
     args = ap.parse_args(argv)
     from . import api, pointcloud
     cam = None
@@ -146,12 +166,21 @@ def main(argv=None) -> int:
         if len(v) != 5:
             ap.error("--camera takes fx,fy,cx,cy,baseline_mm")
         cam = pointcloud.Camera(fx=v[0], fy=v[1], cx=v[2], cy=v[3], baseline_mm=v[4])
+    lrc = None
+    if args.lrc:
+        try:
+            v = [float(t) for t in args.lrc.split(",")]
+        except ValueError:
+            v = []
+        if len(v) not in (1, 2) or not all(np.isfinite(t) and t >= 0 for t in v):
+            ap.error("--lrc takes TAU_PX[,TAU_REL], both finite and >= 0")
+        lrc = (v[0], v[1] if len(v) == 2 else 0.0)
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
-                               ply_dir=args.ply, camera=cam)
+                               ply_dir=args.ply, camera=cam, lrc=lrc)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -159,6 +188,8 @@ def main(argv=None) -> int:
     if args.gt and recs:
         for k in ("epe", "bad1", "bad3", "d1"):
             summary[k] = float(np.nanmean([r["metrics"][k] for r in recs]))
+    if lrc is not None and recs:
+        summary["density"] = float(np.mean([r["density"] for r in recs]))
     print(json.dumps(summary))
     return 0
 

@@ -397,6 +397,55 @@ enum { SN_PC_ORGANISED = 0, SN_PC_COMPACT = 1 };
 int sn_pointcloud_from_raw(sn_handle *h, int n, const int32_t *raw, const uint8_t *nv12, int nv12_pitch,
                            const sn_camera *cam, int layout, float *points, uint32_t *counts, int mem, void *stream);
 
+/* ---- left-right consistency check: which pixels of the left map does the right eye confirm? --------------------------------
+ * The network is left-referenced, so the right eye's map comes from the same weights: feed the mirrored pair (eyes swapped,
+ * every row reversed) and reverse the rows of the result.  A left pixel is KEPT when the right map, sampled where the pixel's
+ * own disparity sends it, holds the same disparity; occluded and out-of-view pixels do not.  A rejected pixel gets raw = 0,
+ * which sn_depth_from_raw, sn_pointcloud_from_raw and Parse already read as "no measurement". */
+typedef struct sn_lrc_params {
+  float tau_px;         /* >= 0, finite: absolute tolerance in full-resolution pixels                    */
+  float tau_rel;        /* >= 0, finite: plus this fraction of the left disparity (0 = absolute only)    */
+  int   right_mirrored; /* sn_lr_check only: raw_right is stored column-reversed (the map of the mirrored
+                           pair exactly as the network wrote it); 0 = right-image coordinates            */
+} sn_lrc_params;
+enum { SN_LRC_KEPT = 0, SN_LRC_INVALID_IN = 1, SN_LRC_OUT_OF_VIEW = 2, SN_LRC_NO_PARTNER = 4, SN_LRC_INCONSISTENT = 8 };
+enum { SN_LRC_IN_TENSOR = 0, SN_LRC_IN_SBS_NV12 = 1 };
+/* Common to the three functions: mem / stream as sn_infer_batch (NULL stream = the handle's own stream and the call returns
+ * after completion; device buffers + a caller stream = work is only enqueued), calls on one handle must not overlap, n in
+ * 1..max_batch.  SN_ERR_ARG: a required pointer NULL, a negative or non-finite tau_*, an unknown in_kind.  Their device
+ * buffers (mirrored tensor, second map, copies of host data) are created on first use, only ever grown and freed by
+ * sn_destroy.  Not covered: the asynchronous sn_submit* slots.
+ *
+ * sn_mirror_pair_i8: n model inputs [n][6][H][W] -> out[k][c][v][u] = in[k][(c + 3) % 6][v][W - 1 - u] (eyes swapped, rows
+ *   reversed).  in and out must not overlap (SN_ERR_ARG).
+ *
+ * sn_lr_check: per map k, row v, column u, in fp32 with every operation rounded (no FMA contraction).  With
+ *   S = (float)((double)out_scale * 192.0) and R(x) = raw_right[k][v][x] (raw_right[k][v][W - 1 - x] if right_mirrored):
+ *     1. rl = raw_left[k][v][u];  rl <= 0 -> SN_LRC_INVALID_IN
+ *     2. d = (float)rl * S;  xr = (float)u - d;  xr < 0 -> SN_LRC_OUT_OF_VIEW
+ *     3. x0 = floor(xr), t = xr - (float)x0, x1 = min(x0 + 1, W - 1), r0 = R(x0), r1 = R(x1), d0 = (float)r0 * S,
+ *        d1 = (float)r1 * S;  r0 <= 0 and r1 <= 0 -> SN_LRC_NO_PARTNER;  exactly one > 0: dr = its disparity;
+ *        else dr = d0 + t * (d1 - d0)   (sub, mul, add, each rounded)
+ *     4. !(fabsf(d - dr) <= tau_px + tau_rel * d) -> SN_LRC_INCONSISTENT
+ *     5. otherwise SN_LRC_KEPT.  The first reason that applies wins.
+ *   mask (nullable) [n][H][W] = the reason;  out_raw (nullable; out_raw == raw_left allowed) = rl where kept, 0 elsewhere;
+ *   disp_inout (nullable) float [n][H][W]: 0.0f is written at exactly the rejected pixels, nothing else is touched;
+ *   kept (nullable) [n] = kept pixels per map (integer sums: deterministic).  At least one of out_raw and mask is required;
+ *   raw_right must not alias an output.
+ *
+ * sn_infer_lrc = L = sn_infer_batch(in);  M = sn_infer_batch(sn_mirror_pair_i8(in));  sn_lr_check(L, M, right_mirrored = 1), in
+ *   the arithmetic the handle runs (two calls for sn_get_refine_stats; under SN_PREC_AUTO each forward follows the usual rule).
+ *   out_i32 / out_disp (each nullable, not both) = the masked left map;  out_right_i32 (nullable) = M[..][W - 1 - x], the
+ *   right eye's own disparity map in right-image coordinates, unmasked;  p->right_mirrored is ignored.
+ *   in_kind SN_LRC_IN_TENSOR: in = int8 [n][6][H][W], w2 / h_px ignored;  SN_LRC_IN_SBS_NV12: in = n side-by-side NV12 frames as
+ *   sn_preprocess_sbs_nv12_batch takes them (w2 = 2W, h_px = H, the same geometry restrictions and SN_ERR_ARG). */
+int sn_mirror_pair_i8(sn_handle *h, int n, const int8_t *in_nchw6, int8_t *out_nchw6, int mem, void *stream);
+int sn_lr_check(sn_handle *h, int n, const int32_t *raw_left, const int32_t *raw_right, const sn_lrc_params *p,
+                int32_t *out_raw, float *disp_inout, uint8_t *mask, uint32_t *kept, int mem, void *stream);
+int sn_infer_lrc(sn_handle *h, int n, const void *in, int in_kind, int w2, int h_px, const sn_lrc_params *p,
+                 int32_t *out_i32, float *out_disp, int32_t *out_right_i32, uint8_t *mask, uint32_t *kept,
+                 int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
