@@ -1,0 +1,654 @@
+// sn_dbg_hooks.hpp — the sn_dbg_* entry points (parity hooks: one kernel or block on caller-supplied tensors, as the
+// pipeline launches it) and the host-side marshalling they share: split-slot tensors, their zero-bordered grids
+// (PaddedSlots) and the fp16 tower layout (RefHost).  Part of the single translation unit stereonet_hip.hip.
+#pragma once
+
+namespace {
+
+// host <-> split-slot layout (SlotIn): src/dst fp32 [nimg][32][H][W]
+void host_to_slots(const float* src, int nimg, int H, int W, std::vector<_Float16>& dst) {
+  const size_t plane = (size_t)H * W;
+  dst.assign((size_t)nimg * 8 * plane * 8, (_Float16)0.f);
+  for (int img = 0; img < nimg; ++img)
+    for (int c = 0; c < kC; ++c)
+      for (size_t i = 0; i < plane; ++i) {
+        const float v = src[((size_t)img * kC + c) * plane + i];
+        const _Float16 hi = (_Float16)v;
+        const size_t base = (((size_t)img * 4 + (c >> 3)) * 2) * plane;
+        dst[(base + i) * 8 + (c & 7)] = hi;
+        dst[(base + plane + i) * 8 + (c & 7)] = (_Float16)((v - (float)hi) * kSplitScale);
+      }
+}
+void host_from_slots(const std::vector<_Float16>& src, int nimg, int H, int W, float* dst) {
+  const size_t plane = (size_t)H * W;
+  for (int img = 0; img < nimg; ++img)
+    for (int c = 0; c < kC; ++c)
+      for (size_t i = 0; i < plane; ++i) {
+        const size_t base = (((size_t)img * 4 + (c >> 3)) * 2) * plane;
+        dst[((size_t)img * kC + c) * plane + i] =
+            (float)src[(base + i) * 8 + (c & 7)] + (float)src[(base + plane + i) * 8 + (c & 7)] * kSplitInv;
+      }
+}
+
+template <class V>
+hipError_t to_dev(void* dev, const V& v) {
+  return hipMemcpy(dev, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
+}
+template <class V>
+hipError_t from_dev(V& v, const void* dev) {
+  return hipMemcpy(v.data(), dev, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost);
+}
+
+// Host image of split-slot (block, part) planes inside a zero-bordered grid (FeatPad, SlotGeom, VolPad): `nplanes` planes
+// of g.PH x g.PW slots with the H x W image at (g.py, g.px), and `lead` all-zero planes in front of and behind them
+// (VolPad: one disparity plane = 8).  The plain counterpart is [nplanes][H][W] slots (host_to_slots).
+struct PaddedSlots {
+  SlotGeom g;
+  int H, W;
+  size_t nplanes, lead;
+  std::vector<_Float16> v;
+  PaddedSlots(const SlotGeom& g_, int H_, int W_, size_t nplanes_, size_t lead_ = 0)
+      : g(g_), H(H_), W(W_), nplanes(nplanes_), lead(lead_), v((nplanes_ + 2 * lead_) * g_.PH * g_.PW * 8, (_Float16)0.f) {}
+  size_t row(size_t plane, int y) const { return (((plane + lead) * g.PH + y + g.py) * g.PW + g.px) * 8; }
+  void put(const std::vector<_Float16>& plain) {
+    for (size_t p = 0; p < nplanes; ++p)
+      for (int y = 0; y < H; ++y) memcpy(&v[row(p, y)], &plain[((p * H + y) * W) * 8], (size_t)W * 16);
+  }
+  void get(std::vector<_Float16>& plain) const {
+    for (size_t p = 0; p < nplanes; ++p)
+      for (int y = 0; y < H; ++y) memcpy(&plain[((p * H + y) * W) * 8], &v[row(p, y)], (size_t)W * 16);
+  }
+  bool outside_is_zero() const {
+    const size_t phw = (size_t)g.PH * g.PW;
+    for (size_t i = 0; i < v.size(); ++i) {
+      const size_t sl = i / 8, p = sl / phw, y = (sl % phw) / g.PW, x = sl % g.PW;
+      const bool inside = p >= lead && p < lead + nplanes && y >= (size_t)g.py && y < (size_t)H + g.py && x >= (size_t)g.px &&
+                          x < (size_t)W + g.px;
+      if (!inside && (float)v[i] != 0.f) return false;
+    }
+    return true;
+  }
+};
+
+// Host image of the fp16 tower tensors: n images of 32 x h x w as NCHW8c inside the zero border of RefGeom g.  split: the
+// layout holds a lo tensor lo_slots behind the hi tensor; slack: each part is followed by ref_slack(g) slots.
+struct RefHost {
+  RefGeom g;
+  int n, h, w;
+  size_t lo_slots;
+  std::vector<_Float16> v;
+  RefHost(const RefGeom& g_, int n_, int h_, int w_, bool split, bool slack)
+      : g(g_), n(n_), h(h_), w(w_), lo_slots(ref16_slots(g_, n_) + (slack ? ref_slack(g_) : 0)), v((split ? 2 : 1) * lo_slots * 8) {}
+  size_t slots() const { return v.size() / 8; }
+  size_t at(int i, int c, int y, int x) const {
+    return ((((size_t)i * 4 + (c >> 3)) * g.Hs + y + kRefPad) * g.Ws + x + kRefPad) * 8 + (c & 7);
+  }
+  void pack(const float* src, bool split) {      // src fp32 [n][32][h][w]
+    v.assign(v.size(), (_Float16)0.f);
+    for (int i = 0; i < n; ++i)
+      for (int c = 0; c < kC; ++c)
+        for (int y = 0; y < h; ++y)
+          for (int x = 0; x < w; ++x) {
+            const float f = src[(((size_t)i * kC + c) * h + y) * w + x];
+            const _Float16 hi = (_Float16)f;
+            v[at(i, c, y, x)] = hi;
+            if (split) v[lo_slots * 8 + at(i, c, y, x)] = (_Float16)((f - (float)hi) * kSplitScale);
+          }
+  }
+  void unpack(float* dst, bool split) const {
+    for (int i = 0; i < n; ++i)
+      for (int c = 0; c < kC; ++c)
+        for (int y = 0; y < h; ++y)
+          for (int x = 0; x < w; ++x) {
+            float f = (float)v[at(i, c, y, x)];
+            if (split) f += (float)v[lo_slots * 8 + at(i, c, y, x)] * kSplitInv;
+            dst[(((size_t)i * kC + c) * h + y) * w + x] = f;
+          }
+  }
+  bool border_is_zero(int parts) const {      // the zero border of the hi (and lo) tensor survived a kernel
+    for (int part = 0; part < parts; ++part)
+      for (int plane = 0; plane < 4 * n; ++plane)
+        for (int y = 0; y < g.Hs; ++y)
+          for (int x = 0; x < g.Ws; ++x) {
+            if (y >= kRefPad && y < kRefPad + h && x >= kRefPad && x < kRefPad + w) continue;
+            for (int e = 0; e < 8; ++e)
+              if ((float)v[part * lo_slots * 8 + (((size_t)plane * g.Hs + y) * g.Ws + x) * 8 + e] != 0.f) return false;
+          }
+    return true;
+  }
+};
+
+// a zeroed fp16 tower tensor behind its front rows (alloc_ref16), owned by ds
+hipError_t alloc_ref16(DevScope& ds, const RefGeom& g, size_t tensor_and_slack_slots, uint4** base) {
+  uint4* raw = nullptr;
+  const hipError_t e = alloc_ref16(g, tensor_and_slack_slots, &raw, base);
+  ds.track(raw);
+  return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- parity hooks ----------------------------------------------------------------------------------------
+int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const float* wt, const float* bias,
+                  int k, int stride, int dil, int lrelu, const float* residual, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in || !wt || !bias || !out || cin <= 0 || cin > kC) return SN_ERR_ARG;
+  if (!((k == 3 && stride == 1) || (k == 5 && stride == 2 && dil == 1))) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const int taps = k * k;
+  const int Ho = stride == 1 ? h_px : h_px / 2, Wo = stride == 1 ? w : w / 2;
+  if (stride == 2 && ((h_px & 1) || (w & 1))) return SN_ERR_ARG;
+  const bool x3 = (lrelu & 2) != 0, slots = (lrelu & 4) != 0;
+  const bool tower32 = (lrelu & 8) != 0;     // bit 3: the fp32 tower kernel (k_ref_conv_f32) instead of the generic one
+  const bool dma = (lrelu & 16) != 0;        // bit 4 (5x5 stride 2 on slots): k_down_x3s_dma on zero-bordered tensors
+  lrelu &= 1;
+  if (x3 != slots || (x3 && !(cin == kC && dil == 1))) return SN_ERR_ARG;     // the split-operand kernel reads slots
+  if (dma && !(slots && (k == 3 || !residual))) return SN_ERR_ARG;
+  ConvLayer L;
+  rc = upload_conv2d(h, HostLayer{wt, bias, kC, cin, taps}, slots ? 8 : (k == 5 || cin <= 4) ? 4 : 8, &L);
+  if (!rc && slots)
+    rc = upload_x3(h, kC, [&](int co, int c, int tap) { return wt[((size_t)co * kC + c) * taps + tap]; }, &L, taps);
+  ds.adopt(L);
+  if (rc) return rc;
+  hipStream_t st = h->stream;
+  if (slots) {          // split-slot tensors in and out through the weights-stationary kernel (fp16 modes' low-res path)
+    std::vector<_Float16> hin, hres, hout((size_t)8 * Ho * Wo * 8);
+    host_to_slots(in, 1, h_px, w, hin);
+    if (residual) host_to_slots(residual, 1, Ho, Wo, hres);
+    if (dma) {      // zero-bordered tensors: k_feat_x3s_dma (3x3; input, output and residual in FeatPad) or k_down_x3s_dma
+      const FeatPad fp = feat_pad(h_px, w);
+      // (5x5 stride 2: an output grid with a border of its own, 3 pixels of slack)
+      PaddedSlots pin(k == 3 ? SlotGeom{fp.PH, fp.PW, 1, 1} : down_in_geom(Ho, Wo), h_px, w, 8);
+      PaddedSlots pout(k == 3 ? pin.g : SlotGeom{Ho + 5, Wo + 7, 2, 3}, Ho, Wo, 8);
+      pin.put(hin);
+      if (residual) pout.put(hres);
+      uint4 *pdin = nullptr, *pdout = nullptr;
+      HIP_TRY(h, ds.alloc(&pdin, pin.v.size() / 8));
+      HIP_TRY(h, ds.alloc(&pdout, pout.v.size() / 8));
+      HIP_TRY(h, to_dev(pdin, pin.v));
+      HIP_TRY(h, to_dev(pdout, pout.v));
+      HIP_TRY(h, hipDeviceSynchronize());
+      if (k == 5)
+        HIP_TRY(h, launch_down_dma(st, L, pdin, 1, Ho, Wo, pdout, pout.g, lrelu != 0, h->num_cu));
+      else if (residual)
+        HIP_TRY(h, (launch_feat_dma<true, true>(st, L, pdin, fp, 1, pdout, pdout, lrelu != 0, h->num_cu)));     // in place, as the pipeline
+      else
+        HIP_TRY(h, (launch_feat_dma<true, false>(st, L, pdin, fp, 1, pdout, nullptr, lrelu != 0, h->num_cu)));
+      HIP_TRY(h, hipStreamSynchronize(st));
+      HIP_TRY(h, from_dev(pout.v, pdout));
+      pout.get(hout);
+      if (!pout.outside_is_zero()) {
+        set_err(h, k == 3 ? "k_feat_x3s_dma wrote outside the image" : "k_down_x3s_dma wrote outside the image");
+        return SN_ERR_DEVICE;
+      }
+    } else {
+      uint4 *din = nullptr, *dout = nullptr;
+      HIP_TRY(h, ds.alloc(&din, hin.size() / 8));
+      HIP_TRY(h, ds.alloc(&dout, hout.size() / 8));
+      HIP_TRY(h, to_dev(din, hin));
+      if (residual) HIP_TRY(h, to_dev(dout, hres));
+      const float* dres = residual ? reinterpret_cast<const float*>(dout) : nullptr;
+      SlotIn ls{din, 0, h_px, w};
+      HIP_TRY(h, k == 5 ? (launch_conv_x3s<5, 2, 32, 4, 32, 32, 1, true, SlotIn>(st, L, ls, 1, Ho, Wo, reinterpret_cast<float*>(dout), dres, lrelu != 0, h->num_cu))
+                        : (launch_conv_x3s<3, 1, 32, 8, 16, 16, 2, true, SlotIn>(st, L, ls, 1, Ho, Wo, reinterpret_cast<float*>(dout), dres, lrelu != 0, h->num_cu)));
+      HIP_TRY(h, hipStreamSynchronize(st));
+      HIP_TRY(h, from_dev(hout, dout));
+    }
+    host_from_slots(hout, 1, Ho, Wo, out);
+    return SN_OK;
+  }
+  float *din = nullptr, *dout = nullptr;
+  const size_t nin = (size_t)cin * h_px * w, nout = (size_t)kC * Ho * Wo;
+  HIP_TRY(h, ds.alloc(&din, nin));
+  HIP_TRY(h, ds.alloc(&dout, nout));
+  HIP_TRY(h, hipMemcpy(din, in, nin * 4, hipMemcpyHostToDevice));
+  const float* dres = nullptr;
+  if (residual) {   // in-place form, as the pipeline uses it
+    HIP_TRY(h, hipMemcpy(dout, residual, nout * 4, hipMemcpyHostToDevice));
+    dres = dout;
+  }
+  LoadF32 ld{din, cin, h_px, w};
+  hipError_t e;
+  if (k == 5) {
+    e = (Ho * Wo <= 64 * 128) ? launch_conv<5, 2, 1, 4, 4, 32>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0)
+                              : launch_conv<5, 2, 1, 4, 8, 64>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0);
+  } else if (cin <= 4) {
+    if (dil != 1) return SN_ERR_ARG;
+    e = (Ho * Wo <= 64 * 128) ? launch_conv<3, 1, 1, 4, 4, 32>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0)
+                              : launch_conv<3, 1, 1, 4, 8, 64>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0);
+  } else {
+    if (tower32 && ((w & 3) != 0 || cin != kC)) return SN_ERR_ARG;
+    e = conv3x3(st, L, din, 1, h_px, w, dil, dout, dres, lrelu != 0, tower32 ? h->num_cu : 0);
+  }
+  HIP_TRY(h, e);
+  HIP_TRY(h, hipStreamSynchronize(st));
+  HIP_TRY(h, hipMemcpy(out, dout, nout * 4, hipMemcpyDeviceToHost));
+  return SN_OK;
+}
+
+int sn_dbg_down0(sn_handle* h, const int8_t* in6, int h_px, int w, const float* wt, const float* bias, int tc,
+                 float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in6 || !wt || !bias || !out || h_px <= 0 || w <= 0 || tc != 32) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16, Ho = Hp / 2, Wo = Wp / 2;
+  Down0F16 L;
+  rc = upload_down0_f16(h, HostLayer{wt, bias, kC, 3, 25}, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  int8_t* din = nullptr;
+  float *dout = nullptr, *dbias = nullptr;
+  const size_t nin = (size_t)6 * h_px * w, nout = (size_t)2 * kC * Ho * Wo;     // split slots: same bytes as fp32
+  HIP_TRY(h, ds.alloc(&din, nin));
+  HIP_TRY(h, ds.alloc(&dout, nout));
+  HIP_TRY(h, ds.alloc(&dbias, kC));
+  HIP_TRY(h, hipMemcpy(din, in6, nin, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dbias, bias, kC * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, launch_down0_f16(h->stream, L, dbias, din, h_px, w, 2, Ho, Wo, dout, h->num_cu));   // the pipeline's kernel
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  std::vector<_Float16> hs(nout * 2);
+  HIP_TRY(h, from_dev(hs, dout));
+  host_from_slots(hs, 2, Ho, Wo, out);
+  return SN_OK;
+}
+
+int sn_dbg_round_kernels_f16(const float* w, int nkernels, float* out) {
+  if (!w || !out || nkernels < 0) return SN_ERR_ARG;
+  for (int k = 0; k < nkernels; ++k) {          // host only: no device needed
+    _Float16 q[9];
+    round_kernel_sum_preserving(w + (size_t)k * 9, q);
+    for (int t = 0; t < 9; ++t) out[(size_t)k * 9 + t] = (float)q[t];
+  }
+  return SN_OK;
+}
+
+int sn_dbg_compose_down01(const float* w0, const float* b0, const float* w1, const float* b1, float* weff, float* beff) {
+  if (!w0 || !b0 || !w1 || !b1 || !weff || !beff) return SN_ERR_ARG;
+  std::vector<double> we, be;
+  compose_down01(w0, b0, w1, b1, we, be);         // host only: no device needed
+  for (size_t i = 0; i < we.size(); ++i) weff[i] = (float)we[i];
+  for (size_t i = 0; i < be.size(); ++i) beff[i] = (float)be[i];
+  return SN_OK;
+}
+
+int sn_dbg_down01(sn_handle* h, const int8_t* in6, int h_px, int w, const float* w0, const float* b0, const float* w1,
+                  const float* b1, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in6 || !w0 || !b0 || !w1 || !b1 || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16, Ho = Hp / 4, Wo = Wp / 4;
+  Down01W L;
+  rc = upload_down01(h, HostLayer{w0, b0, kC, 3, 25}, HostLayer{w1, b1, kC, kC, 25}, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  int8_t* din = nullptr;
+  uint4* dout = nullptr;
+  const size_t nin = (size_t)6 * h_px * w, nout = (size_t)2 * kC * Ho * Wo;     // split slots: same bytes as fp32
+  HIP_TRY(h, ds.alloc(&din, nin));
+  HIP_TRY(h, ds.alloc(&dout, nout / 4));
+  HIP_TRY(h, hipMemcpy(din, in6, nin, hipMemcpyHostToDevice));
+  HIP_TRY(h, launch_down01(h->stream, L, din, h_px, w, 2, Ho, Wo, dout, SlotGeom{Ho, Wo, 0, 0}, h->num_cu));   // the pipeline's kernels
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  std::vector<_Float16> hs(nout * 2);
+  HIP_TRY(h, from_dev(hs, dout));
+  host_from_slots(hs, 2, Ho, Wo, out);
+  return SN_OK;
+}
+
+int sn_dbg_refin(sn_handle* h, const float* disp_low, const int8_t* in6, int h_px, int w, int dmax, const float* wt,
+                 const float* bias, int split, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !disp_low || !in6 || !wt || !bias || !out || h_px <= 0 || w <= 0 || dmax <= 0) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16, hl = Hp / 16, wl = Wp / 16;
+  RefHost t(make_ref_geom(Hp, Wp), 1, Hp, Wp, true, true);      // [hi | slack | lo | slack] whatever `split` says
+  Down0F16 L;
+  rc = upload_refin_f16(h, HostLayer{wt, bias, kC, 4, 9}, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  float *ddl = nullptr, *dbias = nullptr;
+  int8_t* din = nullptr;
+  uint4* dout = nullptr;
+  HIP_TRY(h, ds.alloc(&ddl, (size_t)hl * wl));
+  HIP_TRY(h, ds.alloc(&dbias, kC));
+  HIP_TRY(h, ds.alloc(&din, (size_t)6 * h_px * w));
+  HIP_TRY(h, ds.alloc(&dout, t.slots()));
+  HIP_TRY(h, hipMemcpy(ddl, disp_low, (size_t)hl * wl * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dbias, bias, kC * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(din, in6, (size_t)6 * h_px * w, hipMemcpyHostToDevice));
+  HIP_TRY(h, memset_now(dout, 0, t.slots() * 16));
+  HIP_TRY(h, launch_refin_f16(h->stream, L, dbias, ddl, din, false, hl, wl, h_px, w, 1.0f / (float)dmax,
+                              UpScale{1.0f / 16.0f, 16.0f}, t.g, 1, dout, split != 0, t.lo_slots * 16, h->num_cu));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, from_dev(t.v, dout));
+  t.unpack(out, split != 0);
+  if (!t.border_is_zero(1)) {
+    set_err(h, "ref.in wrote into the zero border");
+    return SN_ERR_DEVICE;
+  }
+  return SN_OK;
+}
+
+int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const float* wt, const float* bias,
+                  int lrelu, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in || !wt || !bias || !out || d <= 0) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const bool x3 = (lrelu & 2) != 0, slots = (lrelu & 4) != 0, dma = (lrelu & 8) != 0;   // dma: zero-bordered volumes
+  lrelu &= 1;
+  if (slots != x3 || (dma && !slots)) return SN_ERR_ARG;        // the split-operand kernels read split-slot volumes
+  ConvLayer L;
+  rc = upload_conv3d(h, HostLayer{wt, bias, kC, kC, 27}, &L);
+  if (!rc && x3)
+    rc = upload_x3(h, 96, [&](int co, int c, int tap) { return wt[(((size_t)co * kC + (c & 31)) * 3 + (c >> 5)) * 9 + tap]; }, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  const size_t plane = (size_t)h_px * w, n = (size_t)kC * d * plane;
+  // caller layout [ci][d][h][w] (PyTorch) <-> device layout [d][ci][h][w]
+  std::vector<float> tmp(n);
+  for (int ci = 0; ci < kC; ++ci)
+    for (int z = 0; z < d; ++z)
+      memcpy(&tmp[((size_t)z * kC + ci) * plane], &in[((size_t)ci * d + z) * plane], plane * 4);
+  float *din = nullptr, *dout = nullptr;
+  HIP_TRY(h, ds.alloc(&din, n));
+  HIP_TRY(h, ds.alloc(&dout, n));
+  if (slots) {       // the volume as d split-slot images (same byte count as fp32)
+    std::vector<_Float16> hs, ho(n * 2);
+    host_to_slots(tmp.data(), d, h_px, w, hs);
+    if (dma) {         // k_agg_x3s_dma on the padded layout: planes 1 .. d of d + 2, every (block, part) image with its border
+      const VolPad g = vol_pad(d, h_px, w);
+      PaddedSlots pin(SlotGeom{g.PH, g.PW, 1, 1}, h_px, w, (size_t)d * 8, 8), pout = pin;
+      pin.put(hs);
+      uint4 *pdin = nullptr, *pdout = nullptr;
+      HIP_TRY(h, ds.alloc(&pdin, pin.v.size() / 8));
+      HIP_TRY(h, ds.alloc(&pdout, pout.v.size() / 8));
+      HIP_TRY(h, to_dev(pdin, pin.v));
+      HIP_TRY(h, memset_now(pdout, 0, pout.v.size() * 2));
+      HIP_TRY(h, launch_agg_dma<true>(h->stream, L, pdin, g, 1, pdout, lrelu != 0, h->num_cu));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      HIP_TRY(h, from_dev(pout.v, pdout));
+      pout.get(ho);
+      if (!pout.outside_is_zero()) {      // the borders must still hold the zeros of the allocation
+        set_err(h, "k_agg_x3s_dma wrote outside the image");
+        return SN_ERR_DEVICE;
+      }
+    } else {
+      HIP_TRY(h, to_dev(din, hs));
+      SlotIn ls{reinterpret_cast<const uint4*>(din), d, h_px, w};
+      HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, true, SlotIn>(h->stream, L, ls, d, h_px, w, dout, nullptr, lrelu != 0, h->num_cu)));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      HIP_TRY(h, from_dev(ho, dout));
+    }
+    host_from_slots(ho, d, h_px, w, tmp.data());
+  } else {
+    HIP_TRY(h, to_dev(din, tmp));
+    LoadVol3D lv{din, d, h_px, w};
+    HIP_TRY(h, (launch_conv<3, 1, 1, 8, 4, 32>(h->stream, L, lv, d, h_px, w, dout, nullptr, lrelu != 0)));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, from_dev(tmp, dout));
+  }
+  for (int co = 0; co < kC; ++co)
+    for (int z = 0; z < d; ++z)
+      memcpy(&out[((size_t)co * d + z) * plane], &tmp[((size_t)z * kC + co) * plane], plane * 4);
+  return SN_OK;
+}
+
+int sn_dbg_ref_conv_f16(sn_handle* h, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
+                        int lrelu, const float* residual, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, false, false);
+  RefLayerF16 L;
+  rc = upload_ref_f16(h, HostLayer{wt, bias, kC, kC, 9}, switches_at_create().w_round_sum_preserving, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  uint4 *din = nullptr, *dout = nullptr;
+  HIP_TRY(h, ds.alloc(&din, t.slots()));
+  HIP_TRY(h, ds.alloc(&dout, t.slots()));
+  t.pack(in, false);
+  HIP_TRY(h, to_dev(din, t.v));
+  if (residual) {
+    t.pack(residual, false);
+    HIP_TRY(h, to_dev(dout, t.v));
+  } else {
+    HIP_TRY(h, memset_now(dout, 0, t.slots() * 16));
+  }
+  unsigned* ctr = h->ws.tile_ctr;
+  if (!ctr) {
+    set_err(h, "sn_dbg_ref_conv_f16 needs an engine created in an fp16 mode");
+    return SN_ERR_ARG;
+  }
+  HIP_TRY(h, hipMemsetAsync(ctr, 0, kTileCtrBytes, h->stream));
+  // lrelu bits 1 / 2: force the 8x64 / 8x32 tile variant of the dilation-1 / -2 kernels (default: chosen per launch)
+  HIP_TRY(h, ref_conv_f16(h->stream, L, t.g, h->num_cu, dil, din, dout, residual ? dout : nullptr, 1, (lrelu & 1) != 0, ctr,
+                          (lrelu & 2) ? 64 : (lrelu & 4) ? 32 : 0));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, from_dev(t.v, dout));
+  t.unpack(out, false);
+  if (!t.border_is_zero(1)) {      // the kernel never writes outside the valid area
+    set_err(h, "fp16 conv wrote into the zero border");
+    return SN_ERR_DEVICE;
+  }
+  return SN_OK;
+}
+
+int sn_dbg_ref_conv_f16x3(sn_handle* h, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
+                          int lrelu, const float* residual, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, true, true);      // [hi | slack | lo | slack]
+  RefLayerF16 L;
+  rc = upload_ref_f16x3(h, HostLayer{wt, bias, kC, kC, 9}, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  uint4 *din = nullptr, *dout = nullptr;
+  HIP_TRY(h, ds.alloc(&din, t.slots()));
+  HIP_TRY(h, ds.alloc(&dout, t.slots()));
+  t.pack(in, true);
+  HIP_TRY(h, to_dev(din, t.v));
+  if (residual) {
+    t.pack(residual, true);
+    HIP_TRY(h, to_dev(dout, t.v));
+  } else {
+    HIP_TRY(h, memset_now(dout, 0, t.slots() * 16));
+  }
+  HIP_TRY(h, ref_conv_f16x3(h->stream, L, t.g, h->num_cu, dil, din, dout, residual ? dout : nullptr, t.lo_slots, 1, lrelu != 0));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, from_dev(t.v, dout));
+  t.unpack(out, true);
+  if (!t.border_is_zero(2)) {
+    set_err(h, "f16x3 conv wrote into the zero border");
+    return SN_ERR_DEVICE;
+  }
+  return SN_OK;
+}
+
+int sn_dbg_ref_block_f16x3(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1, const float* w2,
+                           const float* b2, int dil, int form, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
+  if (form != 0 && form != 1) return SN_ERR_ARG;            // 0 = two k_ref_conv_f16x3 launches, 1 = the streamed block
+  if (form == 1 && !stream_x3_supports(dil)) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, true, true);      // [hi | slack | lo | slack]
+  RefLayerF16 L1, L2;
+  rc = upload_ref_f16x3(h, HostLayer{w1, b1, kC, kC, 9}, &L1);
+  if (!rc) rc = upload_ref_f16x3(h, HostLayer{w2, b2, kC, kC, 9}, &L2);
+  ds.adopt(L1);
+  ds.adopt(L2);
+  if (rc) return rc;
+  uint4 *cur = nullptr, *oth = nullptr;
+  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots(), &cur));
+  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots(), &oth));
+  t.pack(in, true);
+  HIP_TRY(h, to_dev(cur, t.v));
+  HIP_TRY(h, ref_block_f16x3(h->stream, L1, L2, t.g, h->num_cu, dil, &cur, &oth, t.lo_slots, 1, form == 1));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, from_dev(t.v, cur));
+  t.unpack(out, true);
+  if (!t.border_is_zero(2)) {
+    set_err(h, "f16x3 residual block wrote into the zero border");
+    return SN_ERR_DEVICE;
+  }
+  return SN_OK;
+}
+
+int sn_dbg_ref_block_f16(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1,
+                         const float* w2, const float* b2, int dil, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  // tests: bits 8.. select the form: 0 = two launches, 2 = row-streaming fused kernel (1 was the tile-fused kernel of round 2)
+  const int form = dil >> 8;
+  if (form != 0 && form != 2) return SN_ERR_ARG;
+  const int fuse_mode = form == 2 ? 4 : 0;
+  dil &= 0xff;
+  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
+  if (fuse_mode == 4 && !stream_block_supports(dil)) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, false, false);
+  const bool sp = switches_at_create().w_round_sum_preserving;
+  RefLayerF16 L1, L2;
+  rc = upload_ref_f16(h, HostLayer{w1, b1, kC, kC, 9}, sp, &L1);
+  if (!rc) rc = upload_ref_f16(h, HostLayer{w2, b2, kC, kC, 9}, sp, &L2);
+  ds.adopt(L1);
+  ds.adopt(L2);
+  if (rc) return rc;
+  uint4 *cur = nullptr, *oth = nullptr;
+  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots() + ref_slack(t.g), &cur));
+  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots() + ref_slack(t.g), &oth));
+  t.pack(in, false);
+  HIP_TRY(h, to_dev(cur, t.v));
+  if (!h->ws.tile_ctr) {
+    set_err(h, "sn_dbg_ref_block_f16 needs an engine created in an fp16 mode");
+    return SN_ERR_ARG;
+  }
+  HIP_TRY(h, hipMemsetAsync(h->ws.tile_ctr, 0, kTileCtrBytes, h->stream));
+  HIP_TRY(h, ref_block_f16(h->stream, L1, L2, t.g, h->num_cu, dil, &cur, &oth, 1, h->ws.tile_ctr, fuse_mode, h->dump));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, from_dev(t.v, cur));
+  t.unpack(out, false);
+  if (!t.border_is_zero(1)) {      // the zero border of the result tensor
+    set_err(h, "fp16 residual block wrote into the zero border");
+    return SN_ERR_DEVICE;
+  }
+  return SN_OK;
+}
+
+int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, const float* w1, const float* b1, const float* w2,
+                        const float* b2, const float* head_w, float head_b, const float* low, int ups, float dnorm, int h_out,
+                        int w_out, int form, float* out_disp, int32_t* out_raw) {
+  DevScope ds;
+  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !head_w || !low || !out_disp || !out_raw) return SN_ERR_ARG;
+  if (n <= 0 || hk <= 0 || wk <= 0 || h_out <= 0 || w_out <= 0 || h_out > hk || w_out > wk || (ups != 16 && ups != 2) ||
+      hk % ups || wk % ups || (form != 0 && form != 1) || !(dnorm > 0.f))
+    return SN_ERR_ARG;
+  if (h->precision != SN_PREC_F16 && h->precision != SN_PREC_AUTO) {
+    set_err(h, "sn_dbg_ref_tail_f16 needs an engine created with SN_PREC_F16 or SN_PREC_AUTO");
+    return SN_ERR_ARG;
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  const RefGeom g = make_ref_geom(hk, wk);
+  if ((ref16_slots(g, n) + ref_slack(g) + ref_front(g)) * 16 >= ((size_t)1 << 32)) return SN_ERR_ARG;      // 32-bit byte offsets inside a tensor
+  RefHost t(g, n, hk, wk, false, false);
+  t.pack(in, false);
+  const bool sp = switches_at_create().w_round_sum_preserving;
+  RefLayerF16 L1, L2;
+  HeadLayer hd;
+  rc = upload_ref_f16(h, HostLayer{w1, b1, kC, kC, 9}, sp, &L1);
+  if (!rc) rc = upload_ref_f16(h, HostLayer{w2, b2, kC, kC, 9}, sp, &L2);
+  if (!rc) rc = upload_head(h, HostLayer{head_w, &head_b, 1, kC, 9}, &hd);
+  ds.adopt(L1);
+  ds.adopt(L2);
+  ds.adopt(hd);
+  if (rc) return rc;
+  uint4 *da = nullptr, *db = nullptr;
+  HIP_TRY(h, alloc_ref16(ds, g, t.slots() + ref_slack(g), &da));
+  HIP_TRY(h, alloc_ref16(ds, g, t.slots() + ref_slack(g), &db));
+  HIP_TRY(h, to_dev(da, t.v));
+  const int sh = hk / ups, sw = wk / ups;
+  const size_t nlow = (size_t)n * sh * sw, nout = (size_t)n * h_out * w_out;
+  float *dlow = nullptr, *dd = nullptr;
+  int32_t* dr = nullptr;
+  HIP_TRY(h, ds.alloc(&dlow, nlow));
+  HIP_TRY(h, ds.alloc(&dd, nout));
+  HIP_TRY(h, ds.alloc(&dr, nout));
+  HIP_TRY(h, hipMemcpy(dlow, low, nlow * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, memset_now(dd, 0xff, nout * 4));        // NaN / -1: a pixel the kernel does not write shows up
+  HIP_TRY(h, memset_now(dr, 0xff, nout * 4));
+  const float inv_q = (float)(1.0 / (kWireFactor * (double)kOutScale));
+  const UpScale us{1.0f / (float)ups, (float)ups};
+  if (form == 1) {
+    StreamHeadArgs ha{hd.w, dlow, dd, dr, hd.bias, dnorm, inv_q, sh, sw, h_out, w_out, us};
+    HIP_TRY(h, ref_block_stream_tail(h->stream, L1, L2, g, h->num_cu, da, n, h->dump, ha));
+  } else {
+    HIP_TRY(h, ref_block_stream(h->stream, L1, L2, g, h->num_cu, 1, da, db, n, h->dump));
+    HIP_TRY(h, launch_head_final_f16(h->stream, false, db, 0, g, hd.w, hd.bias, dlow, sh, sw, h_out, w_out, dnorm, inv_q, us, dd, dr, n));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(out_disp, dd, nout * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(out_raw, dr, nout * 4, hipMemcpyDeviceToHost));
+  return SN_OK;
+}
+
+__global__ __launch_bounds__(256) void k_copy_limited(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t n16) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+}
+
+int sn_dbg_copy_limited(void* dst, const void* src, size_t bytes, int workgroups, void* stream) {
+  if (!dst || !src || (bytes & 15) || workgroups <= 0 || workgroups > 65535 || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15)) return SN_ERR_ARG;
+  hipLaunchKernelGGL(k_copy_limited, dim3((unsigned)workgroups), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<uint4*>(dst), static_cast<const uint4*>(src), bytes / 16);
+  return hipGetLastError() == hipSuccess ? SN_OK : SN_ERR_DEVICE;
+}
+
+int sn_dbg_read(sn_handle* h, const char* what, float* dst, size_t cap, size_t* n) {
+  if (!h || !what || !n) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const size_t hw = (size_t)h->hl * h->wl;
+  const float* src = nullptr;
+  size_t cnt = 0;
+  if (!strcmp(what, "stream_prio")) {      // host state: 1 = the pipeline streams were created with the highest priority
+    *n = 1;
+    if (dst && cap >= 1) dst[0] = h->stream_prio ? 1.f : 0.f;
+    return (dst && cap < 1) ? SN_ERR_ARG : SN_OK;
+  }
+  if (!strcmp(what, "feat_l")) { src = h->ws.feat; cnt = kC * hw; }
+  else if (!strcmp(what, "feat_r")) { src = h->ws.feat + kC * hw; cnt = kC * hw; }
+  else if (!strcmp(what, "cost")) { src = h->ws.cost; cnt = h->Dl * hw; }
+  else if (!strcmp(what, "disp_low")) { src = h->ws.disp_low; cnt = hw; }
+  else if (!strcmp(what, "tile_ctr") && h->ws.tile_ctr) { src = reinterpret_cast<const float*>(h->ws.tile_ctr); cnt = kTileCtrBytes / 4 * h->ws.n_chunks; }
+  else if (!strcmp(what, "refine_x") && h->precision == SN_PREC_FP32) { src = h->ws.ref[0]; cnt = (size_t)kC * h->Hp * h->Wp; }
+  else if (!strncmp(what, "level", 5) && what[5] >= '1' && what[5] < '0' + h->levels && what[6] == 0) {
+    // hierarchical refinement: the map of level k (first pair of the last piece)
+    const int k = what[5] - '0';
+    src = h->ws.lvl_disp[k];
+    cnt = (size_t)h->tw[k].Hk * h->tw[k].Wk;
+  }
+  else return SN_ERR_ARG;
+  *n = cnt;
+  if (!dst) return SN_OK;
+  if (cap < cnt) return SN_ERR_ARG;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(dst, src, cnt * 4, hipMemcpyDeviceToHost));
+  return SN_OK;
+}
+
+}  // extern "C"

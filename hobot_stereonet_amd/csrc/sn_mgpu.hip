@@ -26,6 +26,7 @@
 
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
+#include "sn_switches.hpp"
 
 namespace {
 
@@ -246,7 +247,8 @@ int sn_mgpu_create(const char* model_file, const sn_config* cfg, const int* devi
   if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) return SN_ERR_DEVICE;
   // SN_MGPU_ALLOW_DUP=1 (tests): several shards may name the same device, so the worker threads, the shard
   // arithmetic and the gather run for ndev > 1 on a one-GPU box.  RCCL needs distinct devices: peer copies then.
-  const bool allow_dup = getenv("SN_MGPU_ALLOW_DUP") != nullptr && atoi(getenv("SN_MGPU_ALLOW_DUP")) == 1;
+  const sn::Switches sw = sn::switches_at_create();
+  const bool allow_dup = sw.mgpu_allow_dup;
   bool distinct = true;
   for (int k = 0; k < ndev; ++k) {
     const int d = devices ? devices[k] : k;
@@ -267,10 +269,8 @@ int sn_mgpu_create(const char* model_file, const sn_config* cfg, const int* devi
   m->per_dev = (m->max_batch + ndev - 1) / ndev;
   // the north-star's exchange is RCCL over xGMI: the default whenever it can run; SN_MGPU_GATHER=peer / rccl force one
   m->gather = (ndev > 1 && distinct) ? 2 : 1;
-  if (const char* e = getenv("SN_MGPU_GATHER")) {
-    if (!strcmp(e, "peer")) m->gather = 1;
-    else if (!strcmp(e, "rccl") && distinct) m->gather = 2;      // (also with ndev = 1: loads RCCL, builds the communicator, runs an empty group)
-  }
+  if (sw.mgpu_gather == 1) m->gather = 1;
+  else if (sw.mgpu_gather == 2 && distinct) m->gather = 2;      // (also with ndev = 1: loads RCCL, builds the communicator, runs an empty group)
   if (m->gather == 2 && !m->rccl.load()) m->gather = 1;
   int rc = SN_OK;
   for (int k = 0; k < ndev && rc == SN_OK; ++k) {

@@ -12,7 +12,7 @@ cp -r hobot_stereonet_amd/csrc $TMP/csrc
 mkdir -p $TMP/include && cp include/stereonet_hip.h $TMP/include/
 sed -i 's|      buf\[ur \* T::COLS + 4 \* uq + k\] = \*reinterpret_cast<const uint4\*>(&sl);|      buf[(256 * k + tid) % T::BUF] = *reinterpret_cast<const uint4*>(\&sl);   /* PROBE: conflict-free, wrong */|' $TMP/csrc/sn_kernels.hpp
 grep -c "PROBE: conflict-free" $TMP/csrc/sn_kernels.hpp | sed 's/^/patched lines: /'
-sed -i 's|#include "../../include/stereonet_hip.h"|#include "'$TMP'/include/stereonet_hip.h"|' $TMP/csrc/*.hip $TMP/csrc/sn_internal.h
+sed -i 's|#include "../../include/stereonet_hip.h"|#include "'$TMP'/include/stereonet_hip.h"|' $TMP/csrc/*.hip $TMP/csrc/sn_internal.h $TMP/csrc/sn_switches.hpp
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-value -I $TMP/include -ldl -lpthread \
   -o $TMP/libsn_probe.so $TMP/csrc/stereonet_hip.hip $TMP/csrc/sn_mgpu.hip || exit 1
 cd /tmp && export TMPDIR=/tmp

@@ -88,7 +88,7 @@ def test_large_residuals_need_and_get_the_split_mode(oracle, tmp_path, shape):
 def test_sum_preserving_weight_rounding_removes_the_offset(oracle, tmp_path, monkeypatch, shape, seed):
     """The two weight draws on which round-to-nearest fp16 weights cost the most (profiles/r05_epe_sensitivity.txt: 7.8e-4
     px at 1280x720 for seed 6, 1.12e-3 px — over the bound — for the hierarchical model at 1242x375 with seed 3): the
-    library's sum-preserving rounding of every 3x3 kernel (stereonet_hip.hip round_kernel_sum_preserving) must take out the
+    library's sum-preserving rounding of every 3x3 kernel (sn_weights.hpp round_kernel_sum_preserving) must take out the
     coherent offset those errors add up to, measured against the oracle on the same input; SN_W_ROUND=rne is the A/B."""
     w, h, d, levels = SHAPES[shape]
     blob = weights.synthetic(seed, levels)

@@ -1,5 +1,5 @@
 """Host logic: the sum-preserving fp16 rounding of the refinement towers' 3x3 weights (SN_PREC_F16, model load;
-hobot_stereonet_amd/csrc/stereonet_hip.hip round_kernel_sum_preserving).  The model file is opaque to the reference
+hobot_stereonet_amd/csrc/sn_weights.hpp round_kernel_sum_preserving).  The model file is opaque to the reference
 (stereonet_infer/src/stereonet_node.cpp:131-136 only checks that it exists); how its float weights become fp16 operands
 is this build's business, and this is the rule.  CPU only."""
 import numpy as np
