@@ -64,6 +64,12 @@ class SnLrcParams(C.Structure):
     _fields_ = [("tau_px", C.c_float), ("tau_rel", C.c_float), ("right_mirrored", C.c_int)]
 
 
+class SnFilterParams(C.Structure):
+    """sn_filter_params (include/stereonet_hip.h): speckle removal and hole filling of the int32 map."""
+    _fields_ = [("speckle_max_px", C.c_int), ("speckle_diff_px", C.c_float), ("fill_max_px", C.c_int)]
+
+
+SN_FLT_INVALID_IN, SN_FLT_SPECKLE, SN_FLT_FILLED = 1, 16, 32
 SN_LRC_KEPT, SN_LRC_INVALID_IN, SN_LRC_OUT_OF_VIEW, SN_LRC_NO_PARTNER, SN_LRC_INCONSISTENT = 0, 1, 2, 4, 8
 SN_LRC_IN_TENSOR, SN_LRC_IN_SBS_NV12 = 0, 1
 
@@ -148,6 +154,7 @@ def load_library(path: Optional[str] = None):
     lib.sn_mirror_pair_i8.argtypes = [vp, ip, i8p, i8p, ip, vp]
     lib.sn_lr_check.argtypes = [vp, ip, i32p, i32p, C.POINTER(SnLrcParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_infer_lrc.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnLrcParams), i32p, fp, i32p, u8p, vp, ip, vp]
+    lib.sn_filter_raw.argtypes = [vp, ip, i32p, C.POINTER(SnFilterParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
     lib.sn_auto_init.argtypes = [C.POINTER(SnAutoState), ip]
     lib.sn_auto_observe.argtypes = [C.POINTER(SnAutoState), C.c_double]
@@ -159,7 +166,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -506,6 +513,33 @@ class StereoNetHIP:
         self._check(self._lib.sn_infer_lrc(self._h, n, in_ptr, in_kind, 2 * self.width, self.height, C.byref(p),
                                            raw_ptr or None, disp_ptr or None, right_ptr or None, mask_ptr or None,
                                            kept_ptr or None, SN_MEM_DEVICE, stream or None), "sn_infer_lrc")
+
+    # -- speckle removal and hole filling ---------------------------------------------------------------
+    def filter_raw(self, raw: np.ndarray, speckle_max_px: int = 0, speckle_diff_px: float = 1.0, fill_max_px: int = 0,
+                   disp: Optional[np.ndarray] = None):
+        """sn_filter_raw on host buffers: int32 (H,W) or (n,H,W) -> (out int32, mask uint8, counts uint32 (n,3) = {valid,
+        removed, filled} per map); `disp` (float32, same shape) is rewritten IN PLACE where the mask is not 0 (0.0 at pixels
+        that end invalid, the dequantised value at filled ones).  dispfilter.reference is the numpy twin."""
+        r = self._maps(raw, "filter_raw")
+        if disp is not None and (disp.dtype != np.float32 or disp.shape != r.shape or not disp.flags.c_contiguous):
+            raise StereoNetError(-1, "filter_raw", "disp must be a C-contiguous float32 array of the maps' shape")
+        n = 1 if r.ndim == 2 else r.shape[0]
+        out = np.empty_like(r)
+        mask = np.empty(r.shape, np.uint8)
+        counts = np.zeros((n, 3), np.uint32)
+        p = SnFilterParams(int(speckle_max_px), speckle_diff_px, int(fill_max_px))
+        self._check(self._lib.sn_filter_raw(self._h, n, r.ctypes.data, C.byref(p), out.ctypes.data, _np_ptr(disp),
+                                            mask.ctypes.data, counts.ctypes.data, SN_MEM_HOST, None), "sn_filter_raw")
+        return out, mask, counts
+
+    def filter_raw_device(self, n: int, raw_ptr: int, speckle_max_px: int, speckle_diff_px: float, fill_max_px: int,
+                          out_raw_ptr: int = 0, mask_ptr: int = 0, disp_ptr: int = 0, counts_ptr: int = 0, stream: int = 0):
+        """sn_filter_raw on device pointers (out_raw_ptr may equal raw_ptr); stream = hipStream_t as int (0: the filter's own
+        stream, and the call returns after completion)."""
+        p = SnFilterParams(int(speckle_max_px), speckle_diff_px, int(fill_max_px))
+        self._check(self._lib.sn_filter_raw(self._h, n, raw_ptr or None, C.byref(p), out_raw_ptr or None, disp_ptr or None,
+                                            mask_ptr or None, counts_ptr or None, SN_MEM_DEVICE, stream or None),
+                    "sn_filter_raw")
 
     def synchronize(self):
         self._check(self._lib.sn_synchronize(self._h), "sn_synchronize")

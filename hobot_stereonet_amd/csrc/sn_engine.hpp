@@ -219,6 +219,16 @@ struct sn_handle {
     void* dev[kCount] = {};            // input tensor, mirrored tensor, left map, second map, float map, right map, mask, kept
     size_t dev_bytes[kCount] = {};
   } lrc;
+  // sn_filter_raw: everything of its own as the point cloud has (it may run beside sn_submit / sn_wait), created on first use
+  struct Filter {
+    enum { kRaw = 0, kDisp, kMask, kCounts, kCount };
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev = nullptr;           // the last enqueue that used `scratch`
+    uint32_t* scratch = nullptr;       // label[slice][H][W], then size[slice][H][W]
+    void* dev[kCount] = {};            // host mode: map (filtered in place), float map, mask, counts
+    size_t dev_bytes[kCount] = {};
+  } flt;
 };
 
 namespace {

@@ -25,9 +25,10 @@
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
 #include "sn_switches.hpp"      // the SN_* environment switches
-#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp)
+#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp)
 #include "sn_pointcloud.hpp"
 #include "sn_lrcheck.hpp"
+#include "sn_dispfilter.hpp"
 #include "sn_engine.hpp"        // handle, workspace and layer types, error and allocation helpers
 #include "sn_weights.hpp"       // .snw reader, weight packing and upload
 #include "sn_launch.hpp"        // kernel launchers and tensor geometry
@@ -383,6 +384,10 @@ int sn_destroy(sn_handle* h) {
   if (h->pc.ev) hipEventDestroy(h->pc.ev);
   if (h->pc.stream) hipStreamDestroy(h->pc.stream);
   for (void* p : h->lrc.dev) hipFree(p);
+  hipFree(h->flt.scratch);
+  for (void* p : h->flt.dev) hipFree(p);
+  if (h->flt.ev) hipEventDestroy(h->flt.ev);
+  if (h->flt.stream) hipStreamDestroy(h->flt.stream);
   hipFree(h->aout.w);
   hipFree(h->aout.pfrag);
   for (auto p : h->chk) hipFree(p);
@@ -1259,6 +1264,100 @@ int sn_infer_lrc(sn_handle* h, int n, const void* in, int in_kind, int w2, int h
     if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   }
   if (blocking) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// ---- speckle removal and hole filling (csrc/sn_dispfilter.hpp) ---------------------------------------------------------------
+int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_params* p, int32_t* out_raw, float* disp_inout,
+                  uint8_t* mask, uint32_t* counts, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  const size_t HW = (size_t)h->H * h->W;
+  if (!raw || !p || (!out_raw && !mask) || n <= 0 || n > h->max_batch || (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) ||
+      p->speckle_max_px < 0 || (size_t)p->speckle_max_px > HW || !std::isfinite(p->speckle_diff_px) ||
+      p->speckle_diff_px < 0.f || p->fill_max_px < 0 || (p->speckle_max_px == 0 && p->fill_max_px == 0) || HW > 0x7fffffffu) {
+    set_err(h, "sn_filter_raw: bad arguments");
+    return SN_ERR_ARG;
+  }
+  const size_t cnt = (size_t)n * HW;
+  {      // out_raw == raw is the one overlap the kernels are written for
+    const uintptr_t lo[5] = {(uintptr_t)raw, (uintptr_t)out_raw, (uintptr_t)disp_inout, (uintptr_t)mask, (uintptr_t)counts};
+    const size_t len[5] = {cnt * 4, cnt * 4, cnt * 4, cnt, (size_t)n * 12};
+    for (int i = 0; i < 5; ++i)
+      for (int j = i + 1; j < 5; ++j)
+        if (lo[i] && lo[j] && !(i == 0 && j == 1 && lo[0] == lo[1]) && lo[i] < lo[j] + len[j] && lo[j] < lo[i] + len[i]) {
+          set_err(h, "sn_filter_raw: overlapping buffers (only out_raw == raw is allowed)");
+          return SN_ERR_ARG;
+        }
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  auto& f = h->flt;
+  std::lock_guard<std::mutex> lk(f.mu);
+  if (!f.stream) HIP_TRY(h, hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
+  if (!f.ev) HIP_TRY(h, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+  const int slice = std::min(h->max_batch, kFltSlice);
+  if (p->speckle_max_px && !f.scratch && hipMalloc(reinterpret_cast<void**>(&f.scratch), (size_t)slice * HW * 8) != hipSuccess) {
+    f.scratch = nullptr;
+    set_err(h, "sn_filter_raw: out of device memory");
+    return SN_ERR_NOMEM;
+  }
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : f.stream;
+  HIP_TRY(h, hipStreamWaitEvent(st, f.ev, 0));      // the previous call (any stream) is done with the scratch and the staging
+  const float S = (float)((double)kOutScale * kWireFactor);
+  const float q = floorf(p->speckle_diff_px / S);
+  FltArgs a{raw, out_raw, disp_inout, mask, counts, f.scratch, f.scratch ? f.scratch + (size_t)slice * HW : nullptr, h->W, h->H,
+            (h->W + kFltTW - 1) / kFltTW, (h->H + kFltTH - 1) / kFltTH, q >= 4294967296.f ? 4294967296ll : (long long)q,
+            (uint32_t)p->speckle_max_px, p->fill_max_px, S};
+  if (mem == SN_MEM_HOST) {
+    using F = sn_handle::Filter;
+    HIP_TRY(h, pc_grow(&f.dev[F::kRaw], &f.dev_bytes[F::kRaw], cnt * 4, false));
+    HIP_TRY(h, hipMemcpyAsync(f.dev[F::kRaw], raw, cnt * 4, hipMemcpyHostToDevice, st));
+    a.raw = static_cast<const int32_t*>(f.dev[F::kRaw]);
+    a.out_raw = out_raw ? static_cast<int32_t*>(f.dev[F::kRaw]) : nullptr;      // filtered in place
+    if (disp_inout) {
+      HIP_TRY(h, pc_grow(&f.dev[F::kDisp], &f.dev_bytes[F::kDisp], cnt * 4, false));
+      HIP_TRY(h, hipMemcpyAsync(f.dev[F::kDisp], disp_inout, cnt * 4, hipMemcpyHostToDevice, st));
+      a.disp = static_cast<float*>(f.dev[F::kDisp]);
+    }
+    if (mask) {
+      HIP_TRY(h, pc_grow(&f.dev[F::kMask], &f.dev_bytes[F::kMask], cnt, false));
+      a.mask = static_cast<uint8_t*>(f.dev[F::kMask]);
+    }
+    if (counts) {
+      HIP_TRY(h, pc_grow(&f.dev[F::kCounts], &f.dev_bytes[F::kCounts], (size_t)n * 12, false));
+      a.counts = static_cast<uint32_t*>(f.dev[F::kCounts]);
+    }
+  }
+  const FltArgs all = a;
+  if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 12, st));
+  const bool vec = (h->W & 3) == 0 && ((uintptr_t)a.mask & 3) == 0;
+  const int pairs = (a.tiles_x - 1) * h->H + (a.tiles_y - 1) * h->W;
+  for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` maps: walk the batch on the stream
+    const int m = std::min(slice, n - k0);
+    const size_t off = (size_t)k0 * HW;
+    a.raw = all.raw + off;
+    a.out_raw = all.out_raw ? all.out_raw + off : nullptr;
+    a.disp = all.disp ? all.disp + off : nullptr;
+    a.mask = all.mask ? all.mask + off : nullptr;
+    a.counts = all.counts ? all.counts + (size_t)k0 * 3 : nullptr;
+    if (a.max_px) {
+      hipLaunchKernelGGL(k_flt_label, dim3(a.tiles_x * a.tiles_y, m), dim3(256), 0, st, a);
+      if (pairs) hipLaunchKernelGGL(k_flt_seam, dim3((pairs + 255) / 256, m), dim3(256), 0, st, a);
+      hipLaunchKernelGGL(k_flt_flatten, dim3((unsigned)((HW + 255) / 256), m), dim3(256), 0, st, a);
+    }
+    const int per_map = std::max(1, std::min((h->H + 3) / 4, 4096 / m));
+    if (vec) hipLaunchKernelGGL(k_flt_apply<true>, dim3(per_map, m), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_flt_apply<false>, dim3(per_map, m), dim3(256), 0, st, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  if (mem == SN_MEM_HOST) {
+    if (out_raw) HIP_TRY(h, hipMemcpyAsync(out_raw, all.out_raw, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (disp_inout) HIP_TRY(h, hipMemcpyAsync(disp_inout, all.disp, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, all.mask, cnt, hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, all.counts, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(h, hipEventRecord(f.ev, st));
+  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }
 

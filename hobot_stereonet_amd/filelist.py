@@ -4,7 +4,8 @@ D1) needed to score the output against dataset ground truth.
 
     python -m hobot_stereonet_amd.filelist --model m.snw --left left.list --right right.list \
         [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
-        [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]]
+        [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
+        [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -14,6 +15,12 @@ missing image or lists of different length stop the run before any inference.  T
 --lrc runs every pair through the left-right consistency check (`sn_infer_lrc`: a second forward on the mirrored pair, then
 the check of the two maps): pixels the right eye does not confirm get raw = 0 in every output, <i>.mask.pgm holds the reason per
 pixel (lrcheck.REASONS), the metrics are taken over kept pixels with ground truth, and the summary gains "density".
+
+--speckle / --fill run the map (after the check when --lrc is given too) through `sn_filter_raw`: connected components of at most
+MAX_PX pixels whose neighbours differ by at most DIFF_PX (default 1) are removed, then row gaps of at most MAX_PX pixels take
+the smaller of their two bounding disparities.  The filtered map feeds the metrics, --ply and --out; <i>.filter.pgm holds the
+mask (dispfilter.BITS), every record gains "removed" and "filled", the summary their totals and "density".  With ground truth
+the metrics cover the measured pixels that survive; the filled ones are interpolation and are scored apart ("filled_epe").
 """
 import argparse
 import json
@@ -88,13 +95,16 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
-                lrc=None) -> List[dict]:
+                lrc=None, flt=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
     compact point cloud of the pair coloured by its left eye (camera: pointcloud.Camera, default intrinsics if None).
     lrc = (tau_px, tau_rel): the maps are those of engine.infer_lrc (rejected pixels at 0), the record gains "mask" and
-    "density", <i>.mask.pgm is written beside the other files and the metrics cover kept pixels only."""
+    "density", <i>.mask.pgm is written beside the other files and the metrics cover kept pixels only.
+    flt = (speckle_max_px, speckle_diff_px, fill_max_px): the maps then pass through engine.filter_raw; the record gains
+    "filter_mask", "removed", "filled" and "density" (pixels > 0 after the filter), <i>.filter.pgm is written, "metrics" cover the
+    surviving measurements and "metrics_filled" the filled pixels."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -122,14 +132,23 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
         if lrc is not None:
             rec["mask"] = mask
             rec["density"] = float(kept[0]) / float(w * h)
+        if flt is not None:
+            raw, fmask, counts = engine.filter_raw(raw, flt[0], flt[1], flt[2], disp=disp)
+            rec.update(raw=raw, filter_mask=fmask, removed=int(counts[0][1]), filled=int(counts[0][2]),
+                       density=float(counts[0][0]) / float(w * h))
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
             rec["points"] = pointcloud.write_ply(os.path.join(ply_dir, f"{i}.ply"), pts, int(cnt[0]))
         if gts is not None:
-            gt, valid = images.read_disparity(gts[i])
+            gt, gt_valid = images.read_disparity(gts[i])
+            valid = gt_valid
             if lrc is not None:
                 valid = (mask == 0) if valid is None else (valid & (mask == 0))
+            if flt is not None:      # fmask == 0: a measurement that survived both the check (its raw were 0 otherwise) and the filter
+                filled = (fmask & 32) != 0
+                rec["metrics_filled"] = score(disp, gt, filled if gt_valid is None else (gt_valid & filled), float(engine.dmax))
+                valid = (fmask == 0) if gt_valid is None else (gt_valid & (fmask == 0))
             rec["metrics"] = score(disp, gt, valid, float(engine.dmax))
         if out_dir:
             raw.tofile(os.path.join(out_dir, f"{i}.raw.bin"))
@@ -139,6 +158,8 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             images.write_ppm(os.path.join(out_dir, f"{i}.depth.ppm"), render.colorize_depth(depth)[..., ::-1])
             if lrc is not None:
                 images.write_ppm(os.path.join(out_dir, f"{i}.mask.pgm"), mask)      # 2-D: written as a P5 greymap
+            if flt is not None:
+                images.write_ppm(os.path.join(out_dir, f"{i}.filter.pgm"), fmask)
         results.append(rec)
     return results
 
@@ -158,6 +179,11 @@ def main(argv=None) -> int:
     ap.add_argument("--lrc", default=None, metavar="TAU_PX[,TAU_REL]",
                     help="left-right consistency check: drop pixels whose right-eye disparity differs by more than "
                          "TAU_PX + TAU_REL * disparity px (one more forward per pair)")
+    ap.add_argument("--speckle", default=None, metavar="MAX_PX[,DIFF_PX]",
+                    help="remove connected components of at most MAX_PX pixels; neighbours belong together when their "
+                         "disparities differ by at most DIFF_PX px (default 1)")
+    ap.add_argument("--fill", default=None, metavar="MAX_PX",
+                    help="fill row gaps of at most MAX_PX pixels with the smaller bounding disparity (after --speckle)")
     args = ap.parse_args(argv)
     from . import api, pointcloud
     cam = None
@@ -175,12 +201,31 @@ def main(argv=None) -> int:
         if len(v) not in (1, 2) or not all(np.isfinite(t) and t >= 0 for t in v):
             ap.error("--lrc takes TAU_PX[,TAU_REL], both finite and >= 0")
         lrc = (v[0], v[1] if len(v) == 2 else 0.0)
+    flt = None
+    if args.speckle is not None or args.fill is not None:
+        smax, sdiff, fmax = 0, 1.0, 0
+        if args.speckle is not None:
+            t = args.speckle.split(",")
+            try:
+                smax, sdiff = int(t[0]), float(t[1]) if len(t) == 2 else 1.0
+            except ValueError:
+                smax = -1
+            if len(t) not in (1, 2) or smax < 1 or smax > 2 ** 31 - 1 or not (np.isfinite(sdiff) and sdiff >= 0):
+                ap.error("--speckle takes MAX_PX[,DIFF_PX]: an integer >= 1 and a finite difference >= 0")
+        if args.fill is not None:
+            try:
+                fmax = int(args.fill)
+            except ValueError:
+                fmax = -1
+            if fmax < 1 or fmax > 2 ** 31 - 1:
+                ap.error("--fill takes MAX_PX, an integer >= 1")
+        flt = (smax, sdiff, fmax)
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
-                               ply_dir=args.ply, camera=cam, lrc=lrc)
+                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -188,7 +233,12 @@ def main(argv=None) -> int:
     if args.gt and recs:
         for k in ("epe", "bad1", "bad3", "d1"):
             summary[k] = float(np.nanmean([r["metrics"][k] for r in recs]))
-    if lrc is not None and recs:
+    if args.gt and flt is not None and recs:
+        summary["filled_epe"] = float(np.nanmean([r["metrics_filled"]["epe"] for r in recs]))
+    if flt is not None and recs:
+        summary["removed"] = int(sum(r["removed"] for r in recs))
+        summary["filled"] = int(sum(r["filled"] for r in recs))
+    if (lrc is not None or flt is not None) and recs:
         summary["density"] = float(np.mean([r["density"] for r in recs]))
     print(json.dumps(summary))
     return 0

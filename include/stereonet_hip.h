@@ -446,6 +446,49 @@ int sn_infer_lrc(sn_handle *h, int n, const void *in, int in_kind, int w2, int h
                  int32_t *out_i32, float *out_disp, int32_t *out_right_i32, uint8_t *mask, uint32_t *kept,
                  int mem, void *stream);
 
+/* ---- speckle removal and hole filling of the int32 map: what a consistency check leaves behind ---------------------------------
+ * sn_infer_lrc zeroes what the right eye does not confirm.  Two things remain: SPECKLES, small islands of surviving pixels
+ * (and small patches whose disparity is unlike everything around them), and HOLES, the occlusion strip behind a foreground
+ * edge and single rejected pixels.  sn_filter_raw removes the first and fills the second, on the GPU, in integers. */
+typedef struct sn_filter_params {
+  int   speckle_max_px;   /* 0: no speckle removal; else 1..H*W: components of at most this many pixels are removed */
+  float speckle_diff_px;  /* >= 0, finite: 4-neighbours belong together when their disparities differ by at most this */
+  int   fill_max_px;      /* 0: no filling; else >= 1: row gaps of at most this many pixels are filled */
+} sn_filter_params;
+enum { SN_FLT_INVALID_IN = 1, SN_FLT_SPECKLE = 16, SN_FLT_FILLED = 32 };   /* bits; 0 = untouched measurement */
+/* sn_filter_raw: n maps raw [n][H][W] of the model's size, each on its own.  All per-pixel arithmetic is integer.  With
+ *   S = (float)((double)out_scale * 192.0) as for sn_lr_check, the link threshold in units of raw is
+ *   dq = (int64_t)floorf(speckle_diff_px / S), one fp32 division on the host (a quotient of 2^32 or more is taken as 2^32: two
+ *   int32 values never differ by that much).
+ *   Stage 1, speckles (speckle_max_px > 0).  A pixel is valid when raw > 0.  Two 4-neighbours a, b are LINKED when both are
+ *     valid and |(int64_t)a - (int64_t)b| <= dq (64 bits: INT32_MAX beside 1 does not wrap).  The components are the connected
+ *     components of that graph, an equivalence relation, so nothing depends on the order of traversal.  Every pixel of a
+ *     component of at most speckle_max_px pixels gets the value 0 and the bit SN_FLT_SPECKLE.  (OpenCV's filterSpeckles:
+ *     4-connectivity, <= maxDiff, <= maxSpeckleSize.)  M = the map after this stage (raw <= 0 counts as 0).
+ *   Stage 2, fill (fill_max_px > 0), per row v.  For a column u with M[v][u] <= 0: ul = the nearest column left of u with
+ *     M > 0, ur = the nearest to the right.  Neither exists: the pixel is untouched.  Otherwise
+ *     gap = (ur or W) - (ul or -1) - 1, and if gap <= fill_max_px the pixel takes min(M[v][ul], M[v][ur]) — the smaller
+ *     disparity is the background, which is what an occlusion hides — or the one bounding value where the gap touches an
+ *     image border, and the bit SN_FLT_FILLED.  Sources are pixels of M only, never filled values: rows are independent.
+ *   mask (nullable) [n][H][W] = OR of the bits, SN_FLT_INVALID_IN where raw <= 0: one of 0, 1, 16, 33, 48; the result is > 0
+ *     exactly where mask == 0 or SN_FLT_FILLED is set.
+ *   out_raw (nullable) = the final value, 0 at every pixel that ends invalid (a negative input becomes 0); out_raw == raw is
+ *     allowed, any other overlap between the buffers is SN_ERR_ARG.
+ *   disp_inout (nullable) float [n][H][W]: where mask != 0, 0.0f if the pixel ends invalid, else (float)value * S (one rounded
+ *     multiply); nothing else is touched.
+ *   counts (nullable) [n][3] = {pixels with result > 0, with SN_FLT_SPECKLE, with SN_FLT_FILLED} per map (integer sums:
+ *     deterministic).  At least one of out_raw and mask is required.
+ * SN_ERR_ARG: n outside 1..max_batch, p or raw NULL, speckle_max_px outside 0..H*W, speckle_diff_px negative or not finite,
+ * fill_max_px < 0, both stages off, neither out_raw nor mask, overlapping buffers.
+ * mem / stream as sn_pointcloud_from_raw: a NULL stream is the filter's own stream (never the inference stream); the call
+ * returns after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller stream only enqueue.  May run
+ * concurrently with sn_submit / sn_wait on the same handle: stream, scratch and staging are its own (created on first use,
+ * reused, freed by sn_destroy), and calls on different streams are ordered on the scratch by an event.  The scratch (a label
+ * and a size, 8 bytes per pixel) holds min(max_batch, 8) maps; a larger n is walked in slices of 8 maps on the stream.
+ * Not covered: the asynchronous sn_submit* slots. */
+int sn_filter_raw(sn_handle *h, int n, const int32_t *raw, const sn_filter_params *p, int32_t *out_raw,
+                  float *disp_inout, uint8_t *mask, uint32_t *counts, int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
