@@ -1,7 +1,9 @@
 """Judging a disparity map (or any stage of the network) against the float64 truth (torch_ref.truth) — shared by
-tests/test_truth64.py (what the CPU checkers themselves are worth) and tests/test_gpu_truth64.py (every precision mode
-of the HIP path).  Nothing here looks at a HIP result to set a bound: E_ref / M_ref come from the two CPU fp32
-implementations (the C oracle and the fp32 torch run) on the same input, and there is no exclusion mask.
+tests/test_truth64.py (what the CPU checkers themselves are worth), tests/test_gpu_truth64.py (every precision mode
+of the HIP path) and the two files that carry both across the input domain (tests/test_truth64_domain.py on the CPU,
+tests/test_gpu_truth64_domain.py on the GPU: DOMAIN below is their grid, class_failures their judge).  Nothing here looks
+at a HIP result to set a bound: E_ref / M_ref come from the two CPU fp32 implementations (the C oracle and the fp32 torch
+run) on the same input, and there is no exclusion mask.
 
     E(a) = mean |a - truth|      M(a) = max |a - truth|      S(a) = mean (a - truth)   (signed: the coherent part)
 """
@@ -12,11 +14,16 @@ import time
 import numpy as np
 
 import torch_ref
+from hobot_stereonet_amd import spec, synth, weights
 
 BUDGET = 1e-3          # px: the project's bound on the mean error of a full-size map (north star; F16_TOL)
 X3_TOL = 2e-4          # px: what "fp32-class" has promised for SN_PREC_F16X3 since round 4
 FP32_FACTOR = 3.0      # a third fp32 summation order next to the two CPU ones (they differ by 1.4x from each other)
 X3_FACTOR = 4.0        # 22-bit split operands: unit round-off 4x that of fp32's 24 bits
+# The "factor x the CPU checkers' own error" criteria (stage_failures, fp32_class_failures) are statistics: 24 values is
+# the smallest count they have been applied to (the 3x8 low-resolution map of 124x38).  A stage with fewer values is
+# still compared on every element, but against the absolute bounds of tests/test_gpu_parity.py (small_failures).
+MIN_STAGE_VALUES = 24
 
 
 def err(a, t):
@@ -117,3 +124,164 @@ def assert_float64(r):
         for m in (v if k == "levels" else [v]):
             assert m.dtype == np.float64, (k, m.dtype)
 
+
+
+# ---- the input domain (tests/test_truth64_domain.py, tests/test_gpu_truth64_domain.py) -------------------------------------
+def scaled(blob, layer, gain, levels):
+    """-> a copy of `blob` with the weights and the bias of `layer` multiplied by `gain`"""
+    out = blob.copy()
+    table = spec.offsets(levels)
+    for suffix in (".w", ".b"):
+        off, shape = table[layer + suffix]
+        n = int(np.prod(shape))
+        out[off:off + n] *= np.float32(gain)
+    return out
+
+
+def describe(truth):
+    """-> (mean over the low-resolution pixels of the largest softmax probability of -cost, share of the pixels of `disp`
+    that are exactly zero): how sharp the soft-argmin is and how much the final relu clamps"""
+    c = -np.asarray(truth["cost"], np.float64)
+    p = np.exp(c - c.max(0, keepdims=True))
+    p /= p.sum(0, keepdims=True)
+    return float(p.max(0).mean()), float((truth["disp"] == 0).mean())
+
+
+SHAPE_S, SHAPE_P = (160, 96, 96), (96, 64, 256)
+MULTI = spec.MULTI_LEVELS
+# name: (w, h, D, levels, weights, input); weights = dict(act_scale, head_gain, agg_out) over seed 0, input = a seed of
+# synth.model_input_i8 or the name of a pattern (domain_input)
+DOMAIN = {}
+for _n, _shape, _lv, _wk in (("S-act0.5", SHAPE_S, 1, {"act_scale": 0.5}), ("S-act2", SHAPE_S, 1, {"act_scale": 2.0}), ("S-act4", SHAPE_S, 1, {"act_scale": 4.0}),
+                             ("S-agg/16", SHAPE_S, 1, {"agg_out": 1 / 16}), ("S-aggx16", SHAPE_S, 1, {"agg_out": 16.0}), ("S-aggx64", SHAPE_S, 1, {"agg_out": 64.0}),
+                             ("P-aggx16", SHAPE_P, 1, {"agg_out": 16.0}), ("P-act4", SHAPE_P, 1, {"act_scale": 4.0}),
+                             ("Sm-act4", SHAPE_S, MULTI, {"act_scale": 4.0}), ("Sm-act2-g8", SHAPE_S, MULTI, {"act_scale": 2.0, "head_gain": 8.0})):
+    DOMAIN[_n] = (*_shape, _lv, _wk, 4)
+for _n, _lv, _wk, _in in (("S-max", 1, {}, "max"), ("S-min", 1, {}, "min"), ("S-zero", 1, {}, "zero"), ("S-noise", 1, {}, "noise"),
+                          ("S-checker", 1, {}, "checker"), ("S-step", 1, {}, "step"), ("Sm-noise", MULTI, {}, "noise"),
+                          ("S-noise-g8", 1, {"head_gain": 8.0}, "noise")):
+    DOMAIN[_n] = (*SHAPE_S, _lv, _wk, _in)
+for _w, _h, _d, _lv in ((250, 16, 48, 1), (16, 250, 48, 1), (96, 64, 16, 1), (48, 32, 256, 1), (48, 32, 256, MULTI), (33, 47, 64, 1),
+                        (17, 16, 32, 1), (16, 16, 256, 1), (16, 16, 16, 1), (16, 16, 16, MULTI), (8, 8, 32, MULTI), (8, 8, 16, 1),
+                        (5, 3, 32, 1), (1, 1, 16, 1)):             # largest first
+    DOMAIN[f"{_w}x{_h}-d{_d}{'m' if _lv > 1 else ''}"] = (_w, _h, _d, _lv, {}, 7)
+SHARP = ("S-aggx16", "S-aggx64", "P-aggx16")                        # peak probability > 0.9, zero pixels in the truth
+FLAT = ("S-agg/16", "S-zero")                                       # peak probability < 0.2
+ACT4 = ("S-act4", "Sm-act4")                                        # peak probability > 0.75 over 6 planes
+ACT4_DEEP = ("P-act4",)                                             # ... > 0.6 over 16 planes (measured 0.70; 16 planes share the mass)
+CLAMPED = ("S-aggx16", "S-aggx64", "S-step")                        # the final relu clamps pixels of the truth
+D16 = tuple(n for n, g in DOMAIN.items() if g[2] == 16)
+_domain_cache = {}
+
+
+def domain_input(w, h, d, kind):
+    """int8 (6, h, w): a seed of synth.model_input_i8, or one of the patterns that reach the int8 limits"""
+    if isinstance(kind, int):
+        return synth.model_input_i8(w, h, d, kind)
+    x = np.empty((6, h, w), np.int8)
+    if kind in ("max", "min", "zero"):
+        x[:] = {"max": 127, "min": -128, "zero": 0}[kind]
+    elif kind == "noise":
+        x[:] = np.random.default_rng(1).integers(-128, 128, (6, h, w), dtype=np.int8)
+    elif kind == "checker":                                         # pixel frequency, the same in all six planes
+        x[:] = np.where((np.arange(h)[:, None] + np.arange(w)[None, :]) % 2 == 0, 127, -128)
+    elif kind == "step":
+        x[:, :, :w // 2] = 127
+        x[:, :, w // 2:] = -128
+    else:
+        raise ValueError(kind)
+    return x
+
+
+def domain_blob(levels, wk):
+    blob = weights.synthetic(0, levels, head_gain=wk.get("head_gain", 1.0), act_scale=wk.get("act_scale", 1.0))
+    return scaled(blob, "agg.out", wk["agg_out"], levels) if "agg_out" in wk else blob
+
+
+def domain_point(oracle, name):
+    """-> (blob, x, x_other, Refs) of a grid point, computed once per process.  x_other is the second input of the liveness
+    check: uniform int8 noise of another seed than the grid's noise input (the two eyes differ at every size, so the matching
+    costs move even at 1x1, where the texture generator saturates both eyes to the same byte)."""
+    if name not in _domain_cache:
+        w, h, d, levels, wk, kind = DOMAIN[name]
+        blob, x = domain_blob(levels, wk), domain_input(w, h, d, kind)
+        x_other = np.random.default_rng(2).integers(-128, 128, (6, h, w), dtype=np.int8)
+        _domain_cache[name] = (blob, x, x_other, Refs(oracle, blob, x, d))
+    return _domain_cache[name]
+
+
+def small_failures(stage, a, truth):
+    """A stage or map of fewer than MIN_STAGE_VALUES values: every element against the truth under the absolute bounds of
+    tests/test_gpu_parity.py — disp_low max < 1e-4, cost max < 2e-4 max(1, max |cost|), a map in pixels (the final one and,
+    in their own pixels, the coarse level maps) mean < X3_TOL and max < 20 BUDGET.  Feature maps have 32 channels: never
+    fewer than 32 values."""
+    e, m, _ = err(a, truth)
+    bad = []
+    if not np.isfinite(np.asarray(a)).all():
+        bad.append("not finite")
+    if stage == "disp_low":
+        if not m < 1e-4:
+            bad.append(f"max {m:.3e} >= 1e-4")
+    elif stage == "cost":
+        lim = 2e-4 * max(1.0, float(np.abs(truth).max()))
+        if not m < lim:
+            bad.append(f"max {m:.3e} >= {lim:.3e}")
+    elif stage == "disp" or stage.startswith("level"):
+        if not e < X3_TOL:
+            bad.append(f"mean {e:.3e} >= X3_TOL")
+        if not m < 20 * BUDGET:
+            bad.append(f"max {m:.3e} >= 20 x BUDGET")
+    else:
+        raise ValueError(f"{stage}: no absolute bound for a stage of {np.size(truth)} values")
+    return bad
+
+
+def class_failures(r, out, factor, x3=False, stages=None):
+    """What a result that claims to be fp32-class misses at one grid point: `out` maps "disp" and the stage names of
+    sn_dbg_read (disp_low, cost, feat_l, feat_r, level1..) to arrays.  Stages and maps of at least MIN_STAGE_VALUES values:
+    stage_failures / fp32_class_failures with `factor` (and E < X3_TOL with x3); smaller ones: small_failures.
+    -> list of "stage: condition missed".  One function for the CPU teeth and for any HIP mode judged on the grid."""
+    bad = []
+    for s in (stages if stages is not None else out):
+        t = r.truth["disp"] if s == "disp" else r.stage_truth(s)
+        a = np.asarray(out[s]).reshape(t.shape)
+        if t.size < MIN_STAGE_VALUES:
+            msgs = small_failures(s, a, t)
+        elif s == "disp":
+            msgs = fp32_class_failures(a, t, r.E_ref, r.M_ref, factor)
+            if x3 and not err(a, t)[0] < X3_TOL:
+                msgs.append(f"E {err(a, t)[0]:.3e} >= X3_TOL")
+        else:
+            msgs = stage_failures(a, t, r.stage_ref(s), factor)
+        bad += [f"{s}: {m}" for m in msgs]
+    return bad
+
+
+def forward_as_stages(res):
+    """torch_ref.forward's dict under the names class_failures expects"""
+    out = {"disp": res["disp"], "disp_low": res["disp_low"], "cost": res["cost"], "feat_l": res["fl"], "feat_r": res["fr"]}
+    out.update({f"level{k}": m for k, m in level_maps(res).items()})
+    return out
+
+
+# ---- one engine run (GPU) --------------------------------------------------------------------------------------------------
+STAGES_SINGLE = ("disp_low", "cost", "feat_l", "feat_r")   # what a mode keeps in memory after a single-pair call
+
+
+def read_stages(eng, levels):
+    names = STAGES_SINGLE + tuple(f"level{k}" for k in range(1, levels))
+    return {s: eng.dbg_read(s).copy() for s in names}
+
+
+def run_engine(path, prec, x, x_other, levels):
+    """fresh handle, one single-pair call on x (the engine keeps `cost` only then), its stages; then a call on another
+    input and the stages again — a stage that the second input does not change is not a live readout"""
+    from hobot_stereonet_amd import api
+    with api.StereoNetHIP(path, precision=prec) as eng:
+        disp, raw = eng.infer(x)
+        st = eng.refine_stats()
+        stages = read_stages(eng, levels)
+        eng.infer(x_other)
+        again = read_stages(eng, levels)
+    live = {s: not np.array_equal(stages[s], again[s]) for s in stages}
+    return disp, raw, st, stages, live

@@ -37,8 +37,6 @@ GRID = [("pad", 0, 1.0, 22), ("C1", 0, 1.0, 21), ("C2", 0, 1.0, 0), ("C5m", 0, 1
         ("C2", 6, 1.0, 506), ("C2", 7, 1.0, 507), ("C2", 1, 8.0, 501),
         ("C5m", 3, 1.0, 503), ("C5m", 7, 1.0, 507), ("C5m", 1, 8.0, 501)]
 MODES = [("fp32", api.PREC_FP32), ("f16x3", api.PREC_F16X3), ("f16", api.PREC_F16), ("auto", api.PREC_DEFAULT)]
-# stages a mode keeps in memory after a single-pair call (a stage missing here would be reported, not compared)
-STAGES_SINGLE = ("disp_low", "cost", "feat_l", "feat_r")
 _cache = {}
 _t_refs = [0.0]
 
@@ -67,22 +65,11 @@ def _model(tmp_path, blob, w, h, d):
     return p
 
 
-def _read_stages(eng, levels):
-    names = STAGES_SINGLE + tuple(f"level{k}" for k in range(1, levels))
-    return {s: eng.dbg_read(s).copy() for s in names}
-
-
 def _run(path, prec, x, x_other, levels):
-    """fresh handle, one single-pair call on x (the engine keeps `cost` only then), its stages; then a call on another
-    input and the stages again — a stage that the second input does not change is not a live readout"""
-    with api.StereoNetHIP(path, precision=prec) as eng:
-        disp, raw = eng.infer(x)
-        st = eng.refine_stats()
-        stages = _read_stages(eng, levels)
-        eng.infer(x_other)
-        again = _read_stages(eng, levels)
-    live = {s: not np.array_equal(stages[s], again[s]) for s in stages}
-    return disp, raw, st, stages, live
+    """truth_compare.run_engine (shared with tests/test_gpu_truth64_domain.py): fresh handle, one single-pair call, the
+    stages, and whether a second input changes each readout"""
+    import truth_compare as tc
+    return tc.run_engine(path, prec, x, x_other, levels)
 
 
 @pytest.mark.parametrize("g", GRID, ids=_id)
