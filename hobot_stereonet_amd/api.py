@@ -69,7 +69,13 @@ class SnFilterParams(C.Structure):
     _fields_ = [("speckle_max_px", C.c_int), ("speckle_diff_px", C.c_float), ("fill_max_px", C.c_int)]
 
 
+class SnConfParams(C.Structure):
+    """sn_conf_params (include/stereonet_hip.h): the confidence threshold, 0..1."""
+    _fields_ = [("min_conf", C.c_float)]
+
+
 SN_FLT_INVALID_IN, SN_FLT_SPECKLE, SN_FLT_FILLED = 1, 16, 32
+SN_CONF_KEPT, SN_CONF_INVALID_IN, SN_CONF_LOW = 0, 1, 64
 SN_LRC_KEPT, SN_LRC_INVALID_IN, SN_LRC_OUT_OF_VIEW, SN_LRC_NO_PARTNER, SN_LRC_INCONSISTENT = 0, 1, 2, 4, 8
 SN_LRC_IN_TENSOR, SN_LRC_IN_SBS_NV12 = 0, 1
 
@@ -155,6 +161,8 @@ def load_library(path: Optional[str] = None):
     lib.sn_lr_check.argtypes = [vp, ip, i32p, i32p, C.POINTER(SnLrcParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_infer_lrc.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnLrcParams), i32p, fp, i32p, u8p, vp, ip, vp]
     lib.sn_filter_raw.argtypes = [vp, ip, i32p, C.POINTER(SnFilterParams), i32p, fp, u8p, vp, ip, vp]
+    lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
+    lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
     lib.sn_auto_init.argtypes = [C.POINTER(SnAutoState), ip]
     lib.sn_auto_observe.argtypes = [C.POINTER(SnAutoState), C.c_double]
@@ -166,7 +174,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -469,27 +477,28 @@ class StereoNetHIP:
         self._check(self._lib.sn_lr_check(self._h, n, left_ptr, right_ptr, C.byref(p), out_raw_ptr or None, disp_ptr or None,
                                           mask_ptr or None, kept_ptr or None, SN_MEM_DEVICE, stream or None), "sn_lr_check")
 
+    def _pair_input(self, x, where: str):
+        """-> (contiguous array, in_kind, n, single) of an int8 model tensor or uint8 side-by-side NV12 frames (what infer_lrc and infer_conf take)"""
+        a = np.asarray(x)
+        frame = 3 * self.width * self.height
+        if a.dtype == np.uint8:
+            single = a.ndim == 1 or a.size == frame
+            a = np.ascontiguousarray(a).reshape(-1)
+            if a.size == 0 or a.size % frame:
+                raise StereoNetError(-1, where, f"{a.size} bytes are not side-by-side NV12 frames of {frame} bytes")
+            return a, SN_LRC_IN_SBS_NV12, a.size // frame, single
+        a = np.ascontiguousarray(a, dtype=np.int8)
+        single = a.ndim == 3
+        if a.ndim not in (3, 4) or a.shape[-3:] != (6, self.height, self.width):
+            raise StereoNetError(-1, where, f"input shape {a.shape} != ([n,] 6, {self.height}, {self.width})")
+        return a, SN_LRC_IN_TENSOR, (1 if single else a.shape[0]), single
+
     def infer_lrc(self, x: np.ndarray, tau_px: float = 1.0, tau_rel: float = 0.0, want_right: bool = False):
         """sn_infer_lrc on host buffers.  x: the int8 model tensor (6,H,W) / (n,6,H,W), or uint8 side-by-side NV12 frames
         (3*H*W bytes each: flat, or (n, 3*H*W)).  -> (disp float32, raw int32, mask uint8, kept uint32 (n,)[, right_raw
         int32]): the left map with rejected pixels at 0, the reason per pixel, kept pixels per map and, with want_right, the
         right eye's own map in right-image coordinates (unmasked).  The leading n is dropped for a single tensor / frame."""
-        a = np.asarray(x)
-        frame = 3 * self.width * self.height
-        if a.dtype == np.uint8:
-            kind = SN_LRC_IN_SBS_NV12
-            single = a.ndim == 1 or a.size == frame
-            a = np.ascontiguousarray(a).reshape(-1)
-            if a.size == 0 or a.size % frame:
-                raise StereoNetError(-1, "infer_lrc", f"{a.size} bytes are not side-by-side NV12 frames of {frame} bytes")
-            n = a.size // frame
-        else:
-            kind = SN_LRC_IN_TENSOR
-            a = np.ascontiguousarray(a, dtype=np.int8)
-            single = a.ndim == 3
-            if a.ndim not in (3, 4) or a.shape[-3:] != (6, self.height, self.width):
-                raise StereoNetError(-1, "infer_lrc", f"input shape {a.shape} != ([n,] 6, {self.height}, {self.width})")
-            n = 1 if single else a.shape[0]
+        a, kind, n, single = self._pair_input(x, "infer_lrc")
         shape = (n, self.height, self.width)
         disp, raw = np.empty(shape, np.float32), np.empty(shape, np.int32)
         mask, kept = np.empty(shape, np.uint8), np.zeros(n, np.uint32)
@@ -513,6 +522,67 @@ class StereoNetHIP:
         self._check(self._lib.sn_infer_lrc(self._h, n, in_ptr, in_kind, 2 * self.width, self.height, C.byref(p),
                                            raw_ptr or None, disp_ptr or None, right_ptr or None, mask_ptr or None,
                                            kept_ptr or None, SN_MEM_DEVICE, stream or None), "sn_infer_lrc")
+
+    # -- confidence of the soft-argmin distribution and the mask on it ---------------------------------------------
+    def infer_conf(self, x: np.ndarray, min_conf: Optional[float] = None):
+        """sn_infer_conf on host buffers: ONE forward pass.  x as for infer_lrc (int8 model tensor (6,H,W) / (n,6,H,W), or uint8
+        side-by-side NV12 frames).  min_conf None: no masking -> (disp float32, raw int32, conf float32), the plain map of
+        infer plus the confidence.  Otherwise -> (disp, raw, conf, mask uint8, kept uint32 (n,)): pixels with
+        conf < min_conf (or raw <= 0) at 0, the reason per pixel, kept pixels per map.  The leading n is dropped for a
+        single tensor / frame.  confidence.low / upsample / mask are the numpy twin."""
+        a, kind, n, single = self._pair_input(x, "infer_conf")
+        shape = (n, self.height, self.width)
+        disp, raw, conf = np.empty(shape, np.float32), np.empty(shape, np.int32), np.empty(shape, np.float32)
+        masking = min_conf is not None
+        mask = np.empty(shape, np.uint8) if masking else None
+        kept = np.zeros(n, np.uint32) if masking else None
+        p = SnConfParams(min_conf) if masking else None
+        self._check(self._lib.sn_infer_conf(self._h, n, a.ctypes.data, kind, 2 * self.width, self.height,
+                                            C.byref(p) if masking else None, raw.ctypes.data, disp.ctypes.data, conf.ctypes.data,
+                                            _np_ptr(mask), _np_ptr(kept), SN_MEM_HOST, None), "sn_infer_conf")
+        out = [disp, raw, conf] + ([mask] if masking else [])
+        if single:
+            out = [o[0] for o in out]
+        if masking:
+            out.append(kept)
+        return tuple(out)
+
+    def infer_conf_device(self, n: int, in_ptr: int, min_conf: Optional[float] = None, raw_ptr: int = 0, disp_ptr: int = 0,
+                          conf_ptr: int = 0, mask_ptr: int = 0, kept_ptr: int = 0, in_kind: int = SN_LRC_IN_TENSOR,
+                          stream: int = 0):
+        """sn_infer_conf on device pointers (e.g. torch tensors' data_ptr()); min_conf None: no masking (mask_ptr / kept_ptr
+        must be 0); stream = hipStream_t as int (0: the engine's own stream, and the call returns after completion)."""
+        p = SnConfParams(min_conf) if min_conf is not None else None
+        self._check(self._lib.sn_infer_conf(self._h, n, in_ptr, in_kind, 2 * self.width, self.height,
+                                            C.byref(p) if p is not None else None, raw_ptr or None, disp_ptr or None,
+                                            conf_ptr or None, mask_ptr or None, kept_ptr or None, SN_MEM_DEVICE, stream or None),
+                    "sn_infer_conf")
+
+    def conf_mask(self, raw: np.ndarray, conf: np.ndarray, min_conf: float, disp: Optional[np.ndarray] = None):
+        """sn_conf_mask on host buffers: int32 raw and float32 conf, (H,W) or (n,H,W) -> (out_raw int32, mask uint8, kept uint32
+        (n,)); `disp` (float32, same shape) gets 0.0 written IN PLACE at the rejected pixels.  confidence.mask is the twin."""
+        r = self._maps(raw, "conf_mask")
+        c = self._maps(conf, "conf_mask", np.float32)
+        if r.shape != c.shape:
+            raise StereoNetError(-1, "conf_mask", f"maps of shape {r.shape} and {c.shape}")
+        if disp is not None and (disp.dtype != np.float32 or disp.shape != r.shape or not disp.flags.c_contiguous):
+            raise StereoNetError(-1, "conf_mask", "disp must be a C-contiguous float32 array of the maps' shape")
+        n = 1 if r.ndim == 2 else r.shape[0]
+        out = np.empty_like(r)
+        mask = np.empty(r.shape, np.uint8)
+        kept = np.zeros(n, np.uint32)
+        p = SnConfParams(min_conf)
+        self._check(self._lib.sn_conf_mask(self._h, n, r.ctypes.data, c.ctypes.data, C.byref(p), out.ctypes.data, _np_ptr(disp),
+                                           mask.ctypes.data, kept.ctypes.data, SN_MEM_HOST, None), "sn_conf_mask")
+        return out, mask, kept
+
+    def conf_mask_device(self, n: int, raw_ptr: int, conf_ptr: int, min_conf: float, out_raw_ptr: int = 0, disp_ptr: int = 0,
+                         mask_ptr: int = 0, kept_ptr: int = 0, stream: int = 0):
+        """sn_conf_mask on device pointers (out_raw_ptr may equal raw_ptr); stream = hipStream_t as int."""
+        p = SnConfParams(min_conf)
+        self._check(self._lib.sn_conf_mask(self._h, n, raw_ptr or None, conf_ptr or None, C.byref(p), out_raw_ptr or None,
+                                           disp_ptr or None, mask_ptr or None, kept_ptr or None, SN_MEM_DEVICE, stream or None),
+                    "sn_conf_mask")
 
     # -- speckle removal and hole filling ---------------------------------------------------------------
     def filter_raw(self, raw: np.ndarray, speckle_max_px: int = 0, speckle_diff_px: float = 1.0, fill_max_px: int = 0,

@@ -634,6 +634,7 @@ int sn_dbg_read(sn_handle* h, const char* what, float* dst, size_t cap, size_t* 
   else if (!strcmp(what, "feat_r")) { src = h->ws.feat + kC * hw; cnt = kC * hw; }
   else if (!strcmp(what, "cost")) { src = h->ws.cost; cnt = h->Dl * hw; }
   else if (!strcmp(what, "disp_low")) { src = h->ws.disp_low; cnt = hw; }
+  else if (!strcmp(what, "conf_low")) { src = h->ws.conf_low; cnt = hw; }      // first pair of the last sn_infer_conf; other calls leave it alone (zeros before the first)
   else if (!strcmp(what, "tile_ctr") && h->ws.tile_ctr) { src = reinterpret_cast<const float*>(h->ws.tile_ctr); cnt = kTileCtrBytes / 4 * h->ws.n_chunks; }
   else if (!strcmp(what, "refine_x") && h->precision == SN_PREC_FP32) { src = h->ws.ref[0]; cnt = (size_t)kC * h->Hp * h->Wp; }
   else if (!strncmp(what, "level", 5) && what[5] >= '1' && what[5] < '0' + h->levels && what[6] == 0) {

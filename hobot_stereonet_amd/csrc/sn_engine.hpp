@@ -86,6 +86,7 @@ struct Workspace {          // activations for up to `nb` pairs
   uint4* downp[3] = {nullptr, nullptr, nullptr};   // zero-bordered inputs of down-convs 1..3 (fp16 modes, DownDma)   // zero-bordered split-slot volumes of the aggregation layers (fp16 modes, VolPad)
   float* cost = nullptr;     // [nb][Dl][hl][wl] (debug / parity)
   float* disp_low = nullptr;
+  float* conf_low = nullptr; // [nb][hl][wl]: the soft-argmin's confidence plane (calls that ask for it: sn_infer_conf)
   int ns = 1;                 // tower streams this workspace serves: one (x, t) activation pair per stream
   float* ref[2 * kMaxTowerStreams] = {};
   uint4* ref16[2 * kMaxTowerStreams] = {};   // fp16 NCHW8c padded (fp16 modes): [2 * stream + {x, t}]
@@ -213,10 +214,10 @@ struct sn_handle {
     void* pin[2] = {};                 // host mode: pinned staging of raw and nv12
     size_t pin_bytes[2] = {};
   } pc;
-  // sn_mirror_pair_i8 / sn_lr_check / sn_infer_lrc: device buffers of their own, created on first use and only ever grown
+  // sn_mirror_pair_i8 / sn_lr_check / sn_infer_lrc / sn_infer_conf / sn_conf_mask: device buffers of their own, created on first use and only ever grown
   struct LrCheck {
-    enum { kIn = 0, kMirror, kLeft, kRight, kDisp, kRightOut, kMask, kKept, kCount };
-    void* dev[kCount] = {};            // input tensor, mirrored tensor, left map, second map, float map, right map, mask, kept
+    enum { kIn = 0, kMirror, kLeft, kRight, kDisp, kRightOut, kMask, kKept, kConf, kCount };
+    void* dev[kCount] = {};            // input tensor, mirrored tensor, left map, second map, float map, right map, mask, kept, confidence
     size_t dev_bytes[kCount] = {};
   } lrc;
   // sn_filter_raw: everything of its own as the point cloud has (it may run beside sn_submit / sn_wait), created on first use

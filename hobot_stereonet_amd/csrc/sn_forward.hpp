@@ -71,6 +71,8 @@ int alloc_ws(sn_handle* h, Workspace* ws, int nb, int rb, int ns, int rb_x3 = 0)
   }
   HIP_TRY(h, dalloc(&ws->cost, (size_t)nb * h->Dl * hw));
   HIP_TRY(h, dalloc(&ws->disp_low, (size_t)nb * hw));
+  HIP_TRY(h, dalloc(&ws->conf_low, (size_t)nb * hw));
+  HIP_TRY(h, memset_now(ws->conf_low, 0, (size_t)nb * hw * sizeof(float)));      // sn_dbg_read("conf_low") before any sn_infer_conf: zeros
   // hi tensor (+ lo tensor behind it in SN_PREC_F16X3).  An AUTO handle keeps the fp16 layout for rb pairs and puts the lo
   // tensor of its (smaller) split chunks BEHIND that region: the split mode's hi tensor then sits where the fp16 tensors of
   // the first pairs do — same image pixels, same zero borders — and the lo tensor never touches a border of the fp16
@@ -135,6 +137,7 @@ void free_ws(Workspace* ws) {
   for (auto p : ws->lowp) hipFree(p);
   hipFree(ws->cost);
   hipFree(ws->disp_low);
+  hipFree(ws->conf_low);
   for (auto p : ws->ref) hipFree(p);
   for (auto p : ws->ref16_raw) hipFree(p);
   for (auto& lv : ws->ref_lv)
@@ -152,14 +155,33 @@ void free_ws(Workspace* ws) {
 }
 
 // ---- the forward pass on device buffers ------------------------------------------------------------
+// k_head_softargmin on the last aggregation volume `v` of pairs [p0, p0 + m) (SN_PREC_FP32, SN_HEAD_FOLD=0 and the plain
+// volumes): disp_low, and cost / conf_low on request
+int launch_head_softargmin(sn_handle* h, Workspace& ws, hipStream_t st, const float* v, int p0, int m, bool want_cost,
+                           bool want_conf) {
+  const int hl = h->hl, wl = h->wl, Dl = h->Dl, npix = m * hl * wl;
+  float* const disp_low = ws.disp_low + (size_t)p0 * hl * wl;
+  float* const cost_out = want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr;
+  if (want_conf)
+    hipLaunchKernelGGL((k_head_softargmin<16, true>), dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w,
+                       h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out, ws.conf_low + (size_t)p0 * hl * wl);
+  else
+    hipLaunchKernelGGL(k_head_softargmin<16>, dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w, h->aout.bias, Dl,
+                       hl, wl, npix, disp_low, cost_out, nullptr);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
 // Low-resolution branch for pairs [p0, p0+m): Siamese features -> cost volume -> 3-D aggregation ->
-// soft-argmin.  Intermediate buffers are piece-local; disp_low (and cost) are indexed by p0.
+// soft-argmin.  Intermediate buffers are piece-local; disp_low (and cost, conf_low) are indexed by p0.  want_conf: the
+// soft-argmin epilogue also writes the confidence plane conf_low (sn_infer_conf); the default path launches the kernels it
+// always did.
 // Low-resolution branch of the fp16 modes on split-slot activations (SlotIn): every layer's epilogue writes the
 // hi/lo fp16 pair its consumer's split-operand MFMAs read, the weights-stationary kernel stages them as plain
 // 16-byte copies.  Only the tensors other kernels read stay fp32 NCHW: the feature map (cost-volume loader, parity
 // hook) and the last aggregation volume (soft-argmin head).
 int lowres_slots(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, const int8_t* in6, bool want_cost,
-                 bool prof) {
+                 bool want_conf, bool prof) {
   const int Hp = h->Hp, Wp = h->Wp, hl = h->hl, wl = h->wl, Dl = h->Dl;
   const size_t HW = (size_t)h->H * h->W;
   const int8_t* in = in6 + (size_t)p0 * 6 * HW;
@@ -245,9 +267,14 @@ int lowres_slots(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, con
     }
     if (switches().head_fold && h->aout.pfrag) {       // soft-argmin on the partial sums P [m Dl][27][hl][wl]
       const int npix = m * hl * wl;
-      hipLaunchKernelGGL(k_softargmin_p<16>, dim3((npix + 63) / 64), dim3(64 * Dl), 0, st, ws.vol[(kNAgg - 1) & 1], h->aout.bias,
-                         Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl,
-                         want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr);
+      float* const cost_out = want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr;
+      if (want_conf)
+        hipLaunchKernelGGL((k_softargmin_p<16, true>), dim3((npix + 63) / 64), dim3(64 * Dl), 0, st, ws.vol[(kNAgg - 1) & 1],
+                           h->aout.bias, Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl, cost_out,
+                           ws.conf_low + (size_t)p0 * hl * wl);
+      else
+        hipLaunchKernelGGL(k_softargmin_p<16>, dim3((npix + 63) / 64), dim3(64 * Dl), 0, st, ws.vol[(kNAgg - 1) & 1], h->aout.bias,
+                           Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl, cost_out, nullptr);
       HIP_TRY(h, hipGetLastError());
       return SN_OK;
     }
@@ -270,19 +297,15 @@ int lowres_slots(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, con
   }
   }
   const float* v = ws.vol[(kNAgg - 1) & 1];
-  const int npix = m * hl * wl;
-  hipLaunchKernelGGL(k_head_softargmin<16>, dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w, h->aout.bias, Dl,
-                     hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl,
-                     want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr);
-  HIP_TRY(h, hipGetLastError());
-  return SN_OK;
+  return launch_head_softargmin(h, ws, st, v, p0, m, want_cost, want_conf);
 }
 
-int lowres(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, const int8_t* in6, bool want_cost, bool prof) {
+int lowres(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, const int8_t* in6, bool want_cost, bool want_conf,
+           bool prof) {
   const int Hp = h->Hp, Wp = h->Wp, hl = h->hl, wl = h->wl, Dl = h->Dl;
   const size_t HW = (size_t)h->H * h->W;
   const int8_t* in = in6 + (size_t)p0 * 6 * HW;
-  if (h->precision != SN_PREC_FP32) return lowres_slots(h, ws, st, p0, m, in6, want_cost, prof);
+  if (h->precision != SN_PREC_FP32) return lowres_slots(h, ws, st, p0, m, in6, want_cost, want_conf, prof);
   // SN_PREC_FP32: every layer on the exact-fp32 MFMA, fp32 NCHW activations
   // --- Siamese feature tower: images = 2m (left, right interleaved), shared weights ---
   {
@@ -313,12 +336,7 @@ int lowres(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, const int
     HIP_TRY(h, (launch_conv<3, 1, 1, 8, 4, 32>(st, h->agg[i], lv, m * Dl, hl, wl, ws.vol[i & 1], nullptr, true)));
   }
   const float* v = ws.vol[(kNAgg - 1) & 1];
-  const int npix = m * hl * wl;
-  hipLaunchKernelGGL(k_head_softargmin<16>, dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w, h->aout.bias, Dl,
-                     hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl,
-                     want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr);
-  HIP_TRY(h, hipGetLastError());
-  return SN_OK;
+  return launch_head_softargmin(h, ws, st, v, p0, m, want_cost, want_conf);
 }
 
 // Pieces of one forward(): [p0, p0 + m), ws.pb pairs each.  Rounds 1-4 started with a short piece (2-4 pairs: the towers
@@ -540,7 +558,7 @@ int refine_chunk(sn_handle* h, Workspace& ws, hipStream_t st, int sidx, int* ctr
 // mode: the arithmetic of this call (SN_PREC_F16 / F16X3 / FP32; 0 = the handle's current one).  Ends with the copy of the
 // refinement statistic to the workspace's pinned twin, in stream order.
 int forward(sn_handle* h, Workspace& ws, hipStream_t st, int n, const int8_t* in6, float* out_disp,
-            int32_t* out_raw, bool want_cost, int mode = 0) {
+            int32_t* out_raw, bool want_cost, int mode = 0, bool want_conf = false) {
   if (mode == 0) mode = h->precision == SN_PREC_AUTO ? h->actl.st.mode : h->precision;
   const int rb = chunk_pairs(h, ws, mode);
   const bool prof = h->profiling && (&ws == &h->ws);
@@ -565,7 +583,7 @@ int forward(sn_handle* h, Workspace& ws, hipStream_t st, int n, const int8_t* in
     if (prof) HIP_TRY(h, hipEventRecord(h->ev[0], st));
     for (int p0 = 0, m = 0; p0 < n; p0 += m) {
       m = (n - p0) < ws.pb ? (n - p0) : ws.pb;
-      if ((rc = lowres(h, ws, st, p0, m, in6, want_cost, prof && p0 == 0))) return rc;
+      if ((rc = lowres(h, ws, st, p0, m, in6, want_cost, want_conf, prof && p0 == 0))) return rc;
       if (prof && p0 == 0) HIP_TRY(h, hipEventRecord(h->ev[2], st));
       if (h->levels > 1 && (rc = refine_coarse(h, ws, st, p0, m, in6, &ctr_block, mode))) return rc;
       for (int q0 = p0; q0 < p0 + m; q0 += rb) {
@@ -583,8 +601,8 @@ int forward(sn_handle* h, Workspace& ws, hipStream_t st, int n, const int8_t* in
   int k = 0, chunk = 0;
   for (int p0 = 0, m = 0; p0 < n; p0 += m, ++k) {
     m = p0 == 0 ? first_piece(h, ws, n) : ((n - p0) < ws.pb ? (n - p0) : ws.pb);
-    // the piece-local low-res buffers are reused by the next piece: only disp_low crosses streams
-    if ((rc = lowres(h, ws, h->s_low, p0, m, in6, want_cost, false))) return rc;
+    // the piece-local low-res buffers are reused by the next piece: only disp_low (and conf_low, read after the join) cross streams
+    if ((rc = lowres(h, ws, h->s_low, p0, m, in6, want_cost, want_conf, false))) return rc;
     hipEvent_t e = h->ev_piece[k % kMaxPieceEvents];
     HIP_TRY(h, hipEventRecord(e, h->s_low));
     bool waited[kMaxTowerStreams] = {};
@@ -750,13 +768,14 @@ int fold_pending(sn_handle* h, bool wait) {
 }
 
 // forward() on the handle's own workspace for the synchronous entry points.  post() enqueues what follows the network
-// (device-to-host copies).  blocking: the entry point returns after completion — the statistic is folded in before it
+// (device-to-host copies; sn_infer_conf: the confidence kernel, which reads ws.conf_low — want_conf — and the maps after the
+// towers have joined, and runs again after a repeat so that its outputs belong to the arithmetic that returned).  blocking: the entry point returns after completion — the statistic is folded in before it
 // does and, under SN_PREC_AUTO, a call that left the fp16 tower's envelope is REPEATED in SN_PREC_F16X3.  Not blocking
 // (work only enqueued on the caller's stream): the statistic is folded in by a later call; an AUTO handle that has not had
 // its self-check yet blocks once.
 template <class Post>
 int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* ddisp, int32_t* draw, bool want_cost,
-                bool blocking, Post post) {
+                bool blocking, Post post, bool want_conf = false) {
   const bool is_auto = h->precision == SN_PREC_AUTO;
   AutoCtl& a = h->actl;
   int rc = fold_pending(h, false);
@@ -768,7 +787,7 @@ int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* d
     calibrated = a.calibrated;
   }
   const bool check = is_auto && mode == SN_PREC_F16 && !calibrated;
-  if ((rc = forward(h, h->ws, st, n, din, ddisp, draw, want_cost, mode))) return rc;
+  if ((rc = forward(h, h->ws, st, n, din, ddisp, draw, want_cost, mode, want_conf))) return rc;
   if ((rc = post())) return rc;
   count_call(h, n);
   if (!blocking && !check) {
@@ -784,7 +803,7 @@ int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* d
   if (check && (rc = auto_selfcheck(h, h->ws, st, din))) return rc;
   const int next = fold_stats(h, lvl, res, n, mode);
   if (is_auto && mode == SN_PREC_F16 && next == SN_PREC_F16X3) {
-    if ((rc = forward(h, h->ws, st, n, din, ddisp, draw, want_cost, SN_PREC_F16X3))) return rc;
+    if ((rc = forward(h, h->ws, st, n, din, ddisp, draw, want_cost, SN_PREC_F16X3, want_conf))) return rc;
     if ((rc = post())) return rc;
     HIP_TRY(h, hipStreamSynchronize(st));
     read_stats(h, h->ws, n, lvl, &res);

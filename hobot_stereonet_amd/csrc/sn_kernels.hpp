@@ -1024,6 +1024,29 @@ __global__ __launch_bounds__(256, 2) void k_down0_f16(const int8_t* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------
+// Confidence of a soft-argmin pixel (sn_infer_conf; the contract is in include/stereonet_hip.h): the probability mass on the
+// two planes that bracket the expectation,
+//   Dl == 1: 1.0f;  else k = min((int)floorf(dhat), Dl - 2),  conf = (e_k + e_{k+1}) / se,  e_d = expf(-cost[d] - m)
+// with cost[], m, se and dhat = sd / se exactly what the caller's soft-argmin computed (dhat is the float it stores).
+// The two costs are picked by an unrolled compare-and-select over the register array (a dynamic index would move cost[]
+// to scratch) and e_k, e_{k+1} are recomputed from them: the same expf of the same argument, so the same bits as the terms
+// of se, without keeping all Dl exponentials alive.  Shared by k_head_softargmin and k_softargmin_p (WANT_CONF).
+// ------------------------------------------------------------------------------------------
+template <int DLMAX>
+__device__ __forceinline__ float softargmin_conf(const float (&cost)[DLMAX], int Dl, float m, float se, float dhat) {
+  if (Dl == 1) return 1.0f;
+  const int k = min((int)floorf(dhat), Dl - 2);          // dhat in [0, Dl - 1]: always a valid plane
+  float c0 = cost[0], c1 = cost[DLMAX > 1 ? 1 : 0];
+#pragma unroll
+  for (int d = 1; d + 1 < DLMAX; ++d)
+    if (k == d) {
+      c0 = cost[d];
+      c1 = cost[d + 1];
+    }
+  return (expf(-c0 - m) + expf(-c1 - m)) / se;
+}
+
+// ------------------------------------------------------------------------------------------
 // K6: final 3x3x3 conv 32->1 fused with soft-argmin.
 //   cost[d] = b + sum_{ci,dz,ky,kx} w[ci][dz][ky][kx] * vol[n][d+dz-1][ci][y+ky-1][x+kx-1]
 //   disp    = sum_d d * softmax_d(-cost)
@@ -1036,12 +1059,15 @@ __global__ __launch_bounds__(256, 2) void k_down0_f16(const int8_t* __restrict__
 // (68 MB of scratch writes per launch against 1.4 MB of output).
 // ------------------------------------------------------------------------------------------
 constexpr int kSamWaves = 16;
-template <int DLMAX>
+// WANT_CONF: also writes the confidence plane conf_out [n][H][W] (softargmin_conf); the default instantiation never
+// touches conf_out and is, instruction for instruction, the kernel it was before the parameter existed.
+template <int DLMAX, bool WANT_CONF = false>
 __global__ __launch_bounds__(64 * kSamWaves) void k_head_softargmin(const float* __restrict__ vol,   // [n][Dl][32][H][W]
                                                                     const float* __restrict__ w,     // [32][27] (ci, dz*9+ky*3+kx)
                                                                     float bias, int Dl, int H, int W, int npix_total,
                                                                     float* __restrict__ disp_low,    // [n][H][W]
-                                                                    float* __restrict__ cost_out) {  // nullable [n][Dl][H][W]
+                                                                    float* __restrict__ cost_out,    // nullable [n][Dl][H][W]
+                                                                    float* __restrict__ conf_out) {  // WANT_CONF: [n][H][W]
   __shared__ float s_part[kSamWaves][DLMAX][64];
   constexpr int CPW = kC / kSamWaves;           // channels per wave
   const int lane = threadIdx.x & 63;
@@ -1117,6 +1143,7 @@ __global__ __launch_bounds__(64 * kSamWaves) void k_head_softargmin(const float*
     }
   if (live) {
     disp_low[gp] = sd / se;
+    if (WANT_CONF) conf_out[gp] = softargmin_conf<DLMAX>(cost, Dl, m, se, sd / se);
     if (cost_out) {
 #pragma unroll
       for (int d = 0; d < DLMAX; ++d)
@@ -1134,11 +1161,12 @@ __global__ __launch_bounds__(64 * kSamWaves) void k_head_softargmin(const float*
 // one P image; each element of P is read by exactly one (d, pixel)), the Dl costs of a pixel meet in LDS and wave 0 does
 // the soft-argmin exactly as k_head_softargmin does.
 // ------------------------------------------------------------------------------------------
-template <int DLMAX>
+template <int DLMAX, bool WANT_CONF = false>
 __global__ __launch_bounds__(64 * DLMAX) void k_softargmin_p(const float* __restrict__ P,      // [n][Dl][27][H][W]
                                                           float bias, int Dl, int H, int W, int npix_total,
                                                           float* __restrict__ disp_low,     // [n][H][W]
-                                                          float* __restrict__ cost_out) {   // nullable [n][Dl][H][W]
+                                                          float* __restrict__ cost_out,     // nullable [n][Dl][H][W]
+                                                          float* __restrict__ conf_out) {   // WANT_CONF: [n][H][W]
   __shared__ float s_cost[DLMAX][64];
   const int lane = threadIdx.x & 63;
   const int d = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);        // this wave's plane (blockDim = 64 * Dl)
@@ -1188,6 +1216,7 @@ __global__ __launch_bounds__(64 * DLMAX) void k_softargmin_p(const float* __rest
     }
   if (live) {
     disp_low[gp] = sd / se;
+    if (WANT_CONF) conf_out[gp] = softargmin_conf<DLMAX>(cost, Dl, m, se, sd / se);
     if (cost_out) {
 #pragma unroll
       for (int k = 0; k < DLMAX; ++k)

@@ -25,10 +25,11 @@
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
 #include "sn_switches.hpp"      // the SN_* environment switches
-#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp)
+#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp)
 #include "sn_pointcloud.hpp"
 #include "sn_lrcheck.hpp"
 #include "sn_dispfilter.hpp"
+#include "sn_confidence.hpp"
 #include "sn_engine.hpp"        // handle, workspace and layer types, error and allocation helpers
 #include "sn_weights.hpp"       // .snw reader, weight packing and upload
 #include "sn_launch.hpp"        // kernel launchers and tensor geometry
@@ -1264,6 +1265,151 @@ int sn_infer_lrc(sn_handle* h, int n, const void* in, int in_kind, int w2, int h
     if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   }
   if (blocking) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// ---- confidence of the soft-argmin distribution and the mask on it (csrc/sn_confidence.hpp) ------------------------------------
+static bool conf_params_ok(const sn_conf_params* p) {
+  return p && std::isfinite(p->min_conf) && p->min_conf >= 0.f && p->min_conf <= 1.f;
+}
+
+// device pointers.  low: conf_in is a low-resolution plane [n][hl][wl] (upsampled, out_conf nullable); else a full-resolution
+// map.  p == nullptr: no masking (out_conf only)
+static int conf_launch(sn_handle* h, hipStream_t st, int n, bool low, const float* conf_in, const int32_t* raw,
+                       const sn_conf_params* p, float* out_conf, int32_t* out_raw, float* disp, uint8_t* mask, uint32_t* kept) {
+  if (!p && !(low && out_conf)) return SN_OK;      // nothing to write
+  ConfArgs a{conf_in, raw, out_conf, out_raw, disp, mask, kept, h->hl, h->wl, h->H, h->W, p ? p->min_conf : 0.f, p != nullptr};
+  if (p && kept) HIP_TRY(h, hipMemsetAsync(kept, 0, (size_t)n * 4, st));
+  const int blocks = (int)(((size_t)h->H * h->W + 255) / 256);      // about 1024 workgroups per call: see k_conf_apply
+  const dim3 grid((unsigned)std::max(1, std::min(blocks, 1024 / n)), (unsigned)n);
+  if (low) hipLaunchKernelGGL(k_conf_apply<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_conf_apply<false>, grid, dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+// One forward pass whose soft-argmin epilogue also writes the confidence plane; the upsample + mask kernel is run_forward's
+// `post`, so a call that SN_PREC_AUTO repeats in SN_PREC_F16X3 masks the repeated maps.
+int sn_infer_conf(sn_handle* h, int n, const void* in, int in_kind, int w2, int h_px, const sn_conf_params* p, int32_t* out_i32,
+                  float* out_disp, float* out_conf, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!in || (p && !conf_params_ok(p)) || (!p && (mask || kept)) || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch ||
+      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) || (in_kind != SN_LRC_IN_TENSOR && in_kind != SN_LRC_IN_SBS_NV12)) {
+    set_err(h, "sn_infer_conf: bad arguments");
+    return SN_ERR_ARG;
+  }
+  if (in_kind == SN_LRC_IN_SBS_NV12 && (!pre_args_ok(h, w2 / 2, h_px) || (w2 & 7) || (h_px & 1) ||
+                                        (mem == SN_MEM_DEVICE && ((uintptr_t)in & 3)))) {
+    set_err(h, "sn_infer_conf: image size does not match the model input");
+    return SN_ERR_ARG;
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  const bool host = mem == SN_MEM_HOST, blocking = host || !stream;
+  const size_t HW = (size_t)h->H * h->W, cnt = (size_t)n * HW;
+  const int8_t* din = static_cast<const int8_t*>(in);
+  int32_t* draw = out_i32;
+  float *ddisp = out_disp, *dconf = out_conf;
+  uint8_t* dmask = mask;
+  uint32_t* dkept = kept;
+  if ((host && out_i32) || (p && !out_i32)) LRC_BUF(h, draw, int32_t*, kLeft, cnt * 4);      // the mask rules read the map
+  if (host) {
+    if (out_disp) LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
+    if (out_conf) LRC_BUF(h, dconf, float*, kConf, cnt * 4);
+    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
+    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
+  }
+  if (in_kind == SN_LRC_IN_SBS_NV12) {
+    int8_t* ten;
+    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
+    const int w = w2 / 2;
+    const long total = 6L * h_px * (w >> 2);
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    for (int i = 0; i < n; ++i) {
+      const uint8_t* src = static_cast<const uint8_t*>(in) + (size_t)i * 3 * HW;
+      if (host) {                         // one frame at a time through the NV12 staging buffer
+        HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, src, 3 * HW, hipMemcpyHostToDevice, st));
+        src = h->ws.nv12;
+      }
+      hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, src, src + w, w2, w, h_px, ten + (size_t)i * 6 * HW);
+    }
+    HIP_TRY(h, hipGetLastError());
+    din = ten;
+  } else if (host) {
+    int8_t* ten;
+    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
+    HIP_TRY(h, hipMemcpyAsync(ten, in, cnt * 6, hipMemcpyHostToDevice, st));
+    din = ten;
+  }
+  auto post = [&]() -> int {
+    const int prc = conf_launch(h, st, n, true, h->ws.conf_low, draw, p, dconf, draw, ddisp, dmask, dkept);
+    if (prc) return prc;
+    if (host) {
+      if (out_i32) HIP_TRY(h, hipMemcpyAsync(out_i32, draw, cnt * 4, hipMemcpyDeviceToHost, st));
+      if (out_disp) HIP_TRY(h, hipMemcpyAsync(out_disp, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
+      if (out_conf) HIP_TRY(h, hipMemcpyAsync(out_conf, dconf, cnt * 4, hipMemcpyDeviceToHost, st));
+      if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
+      if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    }
+    return SN_OK;
+  };
+  return run_forward(h, st, n, din, ddisp, draw, n == 1, blocking, post, true);
+}
+
+int sn_conf_mask(sn_handle* h, int n, const int32_t* raw, const float* conf, const sn_conf_params* p, int32_t* out_raw,
+                 float* disp_inout, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!raw || !conf || !conf_params_ok(p) || (!out_raw && !mask) || n <= 0 || n > h->max_batch ||
+      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) {
+    set_err(h, "sn_conf_mask: bad arguments");
+    return SN_ERR_ARG;
+  }
+  const size_t cnt = (size_t)n * h->H * h->W;
+  {      // conf is read by every pixel's thread: it must not be one of the outputs
+    const uintptr_t lo[4] = {(uintptr_t)out_raw, (uintptr_t)disp_inout, (uintptr_t)mask, (uintptr_t)kept};
+    const size_t len[4] = {cnt * 4, cnt * 4, cnt, (size_t)n * 4};
+    const uintptr_t c = (uintptr_t)conf;
+    for (int i = 0; i < 4; ++i)
+      if (lo[i] && lo[i] < c + cnt * 4 && c < lo[i] + len[i]) {
+        set_err(h, "sn_conf_mask: conf overlaps an output");
+        return SN_ERR_ARG;
+      }
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  const int32_t* draw = raw;
+  const float* dconf = conf;
+  int32_t* dout = out_raw;
+  float* ddisp = disp_inout;
+  uint8_t* dmask = mask;
+  uint32_t* dkept = kept;
+  if (mem == SN_MEM_HOST) {
+    int32_t* r;
+    float* c;
+    LRC_BUF(h, r, int32_t*, kLeft, cnt * 4);
+    LRC_BUF(h, c, float*, kConf, cnt * 4);
+    HIP_TRY(h, hipMemcpyAsync(r, raw, cnt * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(c, conf, cnt * 4, hipMemcpyHostToDevice, st));
+    draw = r;
+    dconf = c;
+    dout = out_raw ? r : nullptr;            // masked in place
+    if (disp_inout) {
+      LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
+      HIP_TRY(h, hipMemcpyAsync(ddisp, disp_inout, cnt * 4, hipMemcpyHostToDevice, st));
+    }
+    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
+    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
+  }
+  if ((rc = conf_launch(h, st, n, false, dconf, draw, p, nullptr, dout, ddisp, dmask, dkept))) return rc;
+  if (mem == SN_MEM_HOST) {
+    if (out_raw) HIP_TRY(h, hipMemcpyAsync(out_raw, dout, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (disp_inout) HIP_TRY(h, hipMemcpyAsync(disp_inout, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
+    if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }
 

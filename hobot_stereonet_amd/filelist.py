@@ -5,7 +5,7 @@ D1) needed to score the output against dataset ground truth.
     python -m hobot_stereonet_amd.filelist --model m.snw --left left.list --right right.list \
         [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
         [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
-        [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX]
+        [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -21,6 +21,12 @@ MAX_PX pixels whose neighbours differ by at most DIFF_PX (default 1) are removed
 the smaller of their two bounding disparities.  The filtered map feeds the metrics, --ply and --out; <i>.filter.pgm holds the
 mask (dispfilter.BITS), every record gains "removed" and "filled", the summary their totals and "density".  With ground truth
 the metrics cover the measured pixels that survive; the filled ones are interpolation and are scored apart ("filled_epe").
+
+--conf masks every output by the confidence of the soft-argmin distribution (`sn_infer_conf`, no second forward): pixels whose
+confidence is below MIN get raw = 0, <i>.conf.pfm holds the confidence, <i>.mask.pgm the reason per pixel (confidence.LOW = 64),
+the metrics are taken over kept pixels and the summary gains "density".  With --lrc the public calls are composed with two
+forwards, not three: infer_conf unmasked, the mirrored pair through infer, lr_check, conf_mask on its result; the mask is the OR
+of the two.  --speckle / --fill run last, as without it.
 """
 import argparse
 import json
@@ -95,7 +101,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
-                lrc=None, flt=None) -> List[dict]:
+                lrc=None, flt=None, conf: Optional[float] = None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -104,7 +110,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     "density", <i>.mask.pgm is written beside the other files and the metrics cover kept pixels only.
     flt = (speckle_max_px, speckle_diff_px, fill_max_px): the maps then pass through engine.filter_raw; the record gains
     "filter_mask", "removed", "filled" and "density" (pixels > 0 after the filter), <i>.filter.pgm is written, "metrics" cover the
-    surviving measurements and "metrics_filled" the filled pixels."""
+    surviving measurements and "metrics_filled" the filled pixels.
+    conf = min_conf: the maps are those of engine.infer_conf (pixels below the threshold at 0); the record gains "conf", "mask"
+    and "density", <i>.conf.pfm and <i>.mask.pgm are written.  With lrc as well: infer_conf unmasked, infer on the mirrored pair,
+    lr_check, conf_mask — two forwards — and "mask" is the OR of the two masks."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -124,14 +133,26 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
                 raise FileListError(f"BGRToNv12 Fail: {p} is {bgr.shape[1]}x{bgr.shape[0]}, model input is {w}x{h}")
             eyes.append(images.bgr_to_nv12(bgr))
         sbs = images.sbs_from_eyes(eyes[0], eyes[1], w, h)
-        if lrc is None:
+        cf = None
+        if conf is not None and lrc is not None:
+            disp, raw, cf = engine.infer_conf(sbs)
+            _, raw_m = engine.infer(engine.mirror_pair(engine.preprocess_sbs_nv12(sbs).reshape(6, h, w)))
+            raw, mask, _ = engine.lr_check(raw, raw_m.reshape(h, w), lrc[0], lrc[1], True, disp)
+            raw, cmask, kept = engine.conf_mask(raw, cf, conf, disp)
+            mask = mask | cmask
+        elif conf is not None:
+            disp, raw, cf, mask, kept = engine.infer_conf(sbs, conf)
+        elif lrc is None:
             disp, raw = engine.infer_sbs_nv12(sbs)
         else:
             disp, raw, mask, kept = engine.infer_lrc(sbs, lrc[0], lrc[1])
+        masked = lrc is not None or conf is not None
         rec = {"frame_id": str(i), "left": lp, "right": rp, "raw": raw, "disp": disp}
-        if lrc is not None:
+        if masked:
             rec["mask"] = mask
             rec["density"] = float(kept[0]) / float(w * h)
+        if cf is not None:
+            rec["conf"] = cf
         if flt is not None:
             raw, fmask, counts = engine.filter_raw(raw, flt[0], flt[1], flt[2], disp=disp)
             rec.update(raw=raw, filter_mask=fmask, removed=int(counts[0][1]), filled=int(counts[0][2]),
@@ -143,7 +164,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
         if gts is not None:
             gt, gt_valid = images.read_disparity(gts[i])
             valid = gt_valid
-            if lrc is not None:
+            if masked:
                 valid = (mask == 0) if valid is None else (valid & (mask == 0))
             if flt is not None:      # fmask == 0: a measurement that survived both the check (its raw were 0 otherwise) and the filter
                 filled = (fmask & 32) != 0
@@ -156,8 +177,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             from . import render
             _, depth = render.disparity_and_depth(raw.view(np.uint32))
             images.write_ppm(os.path.join(out_dir, f"{i}.depth.ppm"), render.colorize_depth(depth)[..., ::-1])
-            if lrc is not None:
+            if masked:
                 images.write_ppm(os.path.join(out_dir, f"{i}.mask.pgm"), mask)      # 2-D: written as a P5 greymap
+            if cf is not None:
+                images.write_pfm(os.path.join(out_dir, f"{i}.conf.pfm"), cf)
             if flt is not None:
                 images.write_ppm(os.path.join(out_dir, f"{i}.filter.pgm"), fmask)
         results.append(rec)
@@ -184,6 +207,8 @@ def main(argv=None) -> int:
                          "disparities differ by at most DIFF_PX px (default 1)")
     ap.add_argument("--fill", default=None, metavar="MAX_PX",
                     help="fill row gaps of at most MAX_PX pixels with the smaller bounding disparity (after --speckle)")
+    ap.add_argument("--conf", default=None, metavar="MIN",
+                    help="drop pixels whose soft-argmin confidence (0..1) is below MIN (no second forward)")
     args = ap.parse_args(argv)
     from . import api, pointcloud
     cam = None
@@ -201,6 +226,14 @@ def main(argv=None) -> int:
         if len(v) not in (1, 2) or not all(np.isfinite(t) and t >= 0 for t in v):
             ap.error("--lrc takes TAU_PX[,TAU_REL], both finite and >= 0")
         lrc = (v[0], v[1] if len(v) == 2 else 0.0)
+    conf = None
+    if args.conf is not None:
+        try:
+            conf = float(args.conf)
+        except ValueError:
+            conf = -1.0
+        if not (np.isfinite(conf) and 0.0 <= conf <= 1.0):
+            ap.error("--conf takes MIN, a confidence in 0..1")
     flt = None
     if args.speckle is not None or args.fill is not None:
         smax, sdiff, fmax = 0, 1.0, 0
@@ -225,7 +258,7 @@ def main(argv=None) -> int:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
-                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt)
+                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -238,7 +271,7 @@ def main(argv=None) -> int:
     if flt is not None and recs:
         summary["removed"] = int(sum(r["removed"] for r in recs))
         summary["filled"] = int(sum(r["filled"] for r in recs))
-    if (lrc is not None or flt is not None) and recs:
+    if (lrc is not None or flt is not None or conf is not None) and recs:
         summary["density"] = float(np.mean([r["density"] for r in recs]))
     print(json.dumps(summary))
     return 0

@@ -350,7 +350,10 @@ int sn_dbg_ref_tail_f16(sn_handle *h, int n, const float *in, int hk, int wk, co
                         float dnorm, int h_out, int w_out, int form, float *out_disp, int32_t *out_raw);
 /* intermediates of the most recent batch-1 inference: "feat_l" / "feat_r" [32][hl][wl],
  * "cost" [Dl][hl][wl], "disp_low" [hl][wl], and for a hierarchical model "level1" .. "level3" (the map of that
- * refinement level, [Hp/2^k][Wp/2^k]); returns the element count in *n (dst may be NULL to query). */
+ * refinement level, [Hp/2^k][Wp/2^k]); returns the element count in *n (dst may be NULL to query).
+ * "conf_low" [hl][wl] is the confidence plane of the first pair of the most recent sn_infer_conf and meaningful only after
+ * one: no other call writes it, so it reads zeros before the first sn_infer_conf and, after a later sn_infer, still that
+ * earlier call's plane. */
 int sn_dbg_read(sn_handle *h, const char *what, float *dst, size_t cap, size_t *n);
 /* Parse()'s dequantisation + depth (stereonet_infer/src/parser.cpp:84-86) on the GPU, for n maps of the model's size:
  *     dis = (float)raw * out_scale;   depth_m = (float)((double)(focal_px * baseline_mm) / (dis * 16.0 * 12.0) / 1000.0)
@@ -445,6 +448,52 @@ int sn_lr_check(sn_handle *h, int n, const int32_t *raw_left, const int32_t *raw
 int sn_infer_lrc(sn_handle *h, int n, const void *in, int in_kind, int w2, int h_px, const sn_lrc_params *p,
                  int32_t *out_i32, float *out_disp, int32_t *out_right_i32, uint8_t *mask, uint32_t *kept,
                  int mem, void *stream);
+
+/* ---- confidence: how much of a pixel's matching distribution lies under the disparity it reports? ---------------------------
+ * The soft-argmin holds the whole matching distribution of a low-resolution pixel and reports its expectation.  Whether that
+ * expectation summarises one peak or averages two far-apart ones is the confidence; unlike the left-right check it costs no
+ * second forward pass.
+ *
+ * Low resolution, per pair and per pixel of the hl x wl grid (hl = Hp / 16, wl = Wp / 16, Dl = D / 16).  With cost[d],
+ *   m = max_d -cost[d], e_d = expf(-cost[d] - m), se = sum e_d, sd = sum d * e_d and dhat = sd / se exactly what the soft-argmin
+ *   computes (dhat is the float it stores as its low-resolution disparity):
+ *     Dl == 1 (D = 16): conf_low = 1.0f
+ *     otherwise         k = min((int)floorf(dhat), Dl - 2);  conf_low = (e_k + e_{k+1}) / se
+ *   — the probability mass on the two planes that bracket the expectation.  A single peak gives 1, and so does a peak shared by
+ *   two neighbouring planes (an honest sub-plane disparity); two peaks j >= 2 planes apart give about the mass that happens to
+ *   lie under their mean; a flat distribution gives 2 / Dl.  dhat lies in [0, Dl - 1], so k is always a valid plane.
+ * Full resolution: conf[y][x] = the bilinear x16 upsample of conf_low (half-pixel centres, edge clamp: align_corners = False)
+ *   for y < H, x < W — the function and the convention that feed the refinement its disparity, with factor 1 on the values, and
+ *   the same for single-scale and hierarchical models (the confidence describes the cost volume).  The sample positions are
+ *   multiples of 1/32: the bilinear weights are exact in fp32.
+ * Mask, per pixel, with r = raw[k][v][u] and c = conf[k][v][u]:
+ *     1. r <= 0              -> SN_CONF_INVALID_IN (1)
+ *     2. !(c >= min_conf)    -> SN_CONF_LOW (64): a NaN confidence is rejected at every threshold
+ *     3. otherwise kept (0).
+ *   64 is disjoint from the SN_LRC_* bits (1, 2, 4, 8) and the SN_FLT_* bits (16, 32): masks can be OR-ed.
+ *   Outputs as sn_lr_check's: out_raw (out_raw == raw allowed) = r where kept, 0 elsewhere; disp_inout gets 0.0f at exactly
+ *   the rejected pixels, nothing else is touched; kept[n] = kept pixels per map (integer sums: deterministic). */
+typedef struct sn_conf_params { float min_conf; } sn_conf_params;   /* 0..1, finite; 0 rejects only NaN */
+enum { SN_CONF_KEPT = 0, SN_CONF_INVALID_IN = 1, SN_CONF_LOW = 64 };
+/* sn_infer_conf: ONE forward pass (one call for sn_get_refine_stats; under SN_PREC_AUTO a blocking call follows the usual
+ *   rule, and a repeated call's outputs all belong to the arithmetic that returned).  in / in_kind / w2 / h_px / mem / stream /
+ *   blocking / n in 1..max_batch exactly as sn_infer_lrc (SN_LRC_IN_TENSOR, SN_LRC_IN_SBS_NV12); the NULL stream is the
+ *   handle's inference stream.  out_i32 / out_disp (each nullable, not both) = the map, masked when p is given;
+ *   out_conf (nullable) float [n][H][W] = conf;  p == NULL: no masking — the outputs are the plain map of sn_infer_batch plus
+ *   out_conf, and mask and kept must then be NULL;  mask (nullable) [n][H][W], kept (nullable) [n] as above.
+ * sn_conf_mask: stateless — the mask rules on any map raw [n][H][W] of the model's size and a full-resolution conf [n][H][W]
+ *   (that of sn_infer_conf, also after sn_lr_check or sn_filter_raw have worked on the map).  At least one of out_raw and mask
+ *   is required.
+ * SN_ERR_ARG: a required pointer NULL, min_conf outside [0, 1] or not finite, an unknown in_kind, an image size that does not
+ *   match the model input, n outside 1..max_batch, conf overlapping an output.  Device buffers (copies of host data, the map the
+ *   rules read when the caller asks for the float map alone) are shared with the left-right check: created on first use, only
+ *   ever grown, freed by sn_destroy; calls on one handle must not overlap.  Not covered: the asynchronous sn_submit* slots and
+ *   the node. */
+int sn_infer_conf(sn_handle *h, int n, const void *in, int in_kind, int w2, int h_px, const sn_conf_params *p,
+                  int32_t *out_i32, float *out_disp, float *out_conf, uint8_t *mask, uint32_t *kept,
+                  int mem, void *stream);
+int sn_conf_mask(sn_handle *h, int n, const int32_t *raw, const float *conf, const sn_conf_params *p,
+                 int32_t *out_raw, float *disp_inout, uint8_t *mask, uint32_t *kept, int mem, void *stream);
 
 /* ---- speckle removal and hole filling of the int32 map: what a consistency check leaves behind ---------------------------------
  * sn_infer_lrc zeroes what the right eye does not confirm.  Two things remain: SPECKLES, small islands of surviving pixels
