@@ -359,17 +359,39 @@ class StereoNetHIP:
         self._check(self._lib.sn_wait(self._h, ticket, C.byref(ms)), "sn_wait")
         return ms.value
 
+    # -- int32 / float32 maps of the model's size: what the post-processing calls take and return ------------------------
+    def _maps(self, a, where: str, dtype=np.int32) -> np.ndarray:
+        r = np.ascontiguousarray(a, dtype=dtype)
+        # the calls move n * H * W elements of the MODEL's size: anything else would run past these arrays
+        if r.ndim not in (2, 3) or r.shape[-2:] != (self.height, self.width):
+            raise StereoNetError(-1, where, f"map shape {r.shape} != ([n,] {self.height}, {self.width})")
+        n = self._count(r)
+        if n < 1 or n > self.max_batch:
+            raise StereoNetError(-1, where, f"{n} maps, the engine was created for 1..{self.max_batch}")
+        return r
+
+    @staticmethod
+    def _count(r: np.ndarray) -> int:
+        return 1 if r.ndim == 2 else r.shape[0]
+
+    @staticmethod
+    def _disp_ptr(disp: Optional[np.ndarray], shape, where: str):
+        """The optional float map a call rewrites IN PLACE: checked, -> its address (None without one)."""
+        if disp is not None and (disp.dtype != np.float32 or disp.shape != shape or not disp.flags.c_contiguous):
+            raise StereoNetError(-1, where, "disp must be a C-contiguous float32 array of the maps' shape")
+        return _np_ptr(disp)
+
+    def _mask_outputs(self, r: np.ndarray, per_map: int = 1):
+        """-> (n, out, mask, counter) for the validated maps r: the map and mask of r's shape, per_map uint32 counters per map."""
+        n = self._count(r)
+        return n, np.empty_like(r), np.empty(r.shape, np.uint8), np.zeros(n if per_map == 1 else (n, per_map), np.uint32)
+
     def depth_from_raw(self, raw: np.ndarray, focal_px: float = 527.1931762695312, baseline_mm: float = 119.89382172,
                        want_disp: bool = False):
         """Parse()'s dequantisation + depth (parser.cpp:84-86) on the GPU: int32 (H,W) or (n,H,W) -> depth in metres
         (float32, inf where raw == 0) [, disparity px]; bit-identical to the host Parse."""
-        r = np.ascontiguousarray(raw, dtype=np.int32)
-        # sn_depth_from_raw moves n * H * W elements of the MODEL's size: anything else would run past these arrays
-        if r.ndim not in (2, 3) or r.shape[-2:] != (self.height, self.width):
-            raise StereoNetError(-1, "depth_from_raw", f"raw shape {r.shape} != ([n,] {self.height}, {self.width})")
-        n = 1 if r.ndim == 2 else r.shape[0]
-        if n < 1 or n > self.max_batch:
-            raise StereoNetError(-1, "depth_from_raw", f"{n} maps, the engine was created for 1..{self.max_batch}")
+        r = self._maps(raw, "depth_from_raw")
+        n = self._count(r)
         depth = np.empty(r.shape, np.float32)
         disp = np.empty(r.shape, np.float32) if want_disp else None
         self._check(self._lib.sn_depth_from_raw(self._h, n, r.ctypes.data, focal_px, baseline_mm, depth.ctypes.data,
@@ -389,13 +411,8 @@ class StereoNetHIP:
         reference's intrinsics, principal point at the centre).  nv12: n frames of pointcloud.nv12_frame_bytes(nv12_pitch,
         H) bytes (W for a plain left image, 2W for the side-by-side frame) colour the points."""
         from . import pointcloud
-        r = np.ascontiguousarray(raw, dtype=np.int32)
-        # the call reads n * H * W elements of the MODEL's size: anything else would run past these arrays
-        if r.ndim not in (2, 3) or r.shape[-2:] != (self.height, self.width):
-            raise StereoNetError(-1, "pointcloud", f"raw shape {r.shape} != ([n,] {self.height}, {self.width})")
-        n = 1 if r.ndim == 2 else r.shape[0]
-        if n < 1 or n > self.max_batch:
-            raise StereoNetError(-1, "pointcloud", f"{n} maps, the engine was created for 1..{self.max_batch}")
+        r = self._maps(raw, "pointcloud")
+        n = self._count(r)
         c = self._camera(cam)
         f = None
         if nv12 is not None:
@@ -424,16 +441,6 @@ class StereoNetHIP:
                     "sn_pointcloud_from_raw")
 
     # -- left-right consistency check -----------------------------------------------------------------
-    def _maps(self, a, where: str, dtype=np.int32) -> np.ndarray:
-        r = np.ascontiguousarray(a, dtype=dtype)
-        # the calls move n * H * W elements of the MODEL's size: anything else would run past these arrays
-        if r.ndim not in (2, 3) or r.shape[-2:] != (self.height, self.width):
-            raise StereoNetError(-1, where, f"map shape {r.shape} != ([n,] {self.height}, {self.width})")
-        n = 1 if r.ndim == 2 else r.shape[0]
-        if n < 1 or n > self.max_batch:
-            raise StereoNetError(-1, where, f"{n} maps, the engine was created for 1..{self.max_batch}")
-        return r
-
     def mirror_pair(self, in6: np.ndarray) -> np.ndarray:
         """sn_mirror_pair_i8 on host buffers: int8 (6,H,W) or (n,6,H,W) -> the pair with the eyes swapped and every row
         reversed (lrcheck.mirror_pair is the numpy twin)."""
@@ -459,15 +466,11 @@ class StereoNetHIP:
         r = self._maps(raw_right, "lr_check")
         if l.shape != r.shape:
             raise StereoNetError(-1, "lr_check", f"maps of shape {l.shape} and {r.shape}")
-        if disp is not None and (disp.dtype != np.float32 or disp.shape != l.shape or not disp.flags.c_contiguous):
-            raise StereoNetError(-1, "lr_check", "disp must be a C-contiguous float32 array of the maps' shape")
-        n = 1 if l.ndim == 2 else l.shape[0]
-        out = np.empty_like(l)
-        mask = np.empty(l.shape, np.uint8)
-        kept = np.zeros(n, np.uint32)
+        dp = self._disp_ptr(disp, l.shape, "lr_check")
+        n, out, mask, kept = self._mask_outputs(l)
         p = SnLrcParams(tau_px, tau_rel, int(bool(mirrored)))
         self._check(self._lib.sn_lr_check(self._h, n, l.ctypes.data, r.ctypes.data, C.byref(p), out.ctypes.data,
-                                          _np_ptr(disp), mask.ctypes.data, kept.ctypes.data, SN_MEM_HOST, None), "sn_lr_check")
+                                          dp, mask.ctypes.data, kept.ctypes.data, SN_MEM_HOST, None), "sn_lr_check")
         return out, mask, kept
 
     def lr_check_device(self, n: int, left_ptr: int, right_ptr: int, tau_px: float, tau_rel: float, mirrored: bool,
@@ -565,14 +568,10 @@ class StereoNetHIP:
         c = self._maps(conf, "conf_mask", np.float32)
         if r.shape != c.shape:
             raise StereoNetError(-1, "conf_mask", f"maps of shape {r.shape} and {c.shape}")
-        if disp is not None and (disp.dtype != np.float32 or disp.shape != r.shape or not disp.flags.c_contiguous):
-            raise StereoNetError(-1, "conf_mask", "disp must be a C-contiguous float32 array of the maps' shape")
-        n = 1 if r.ndim == 2 else r.shape[0]
-        out = np.empty_like(r)
-        mask = np.empty(r.shape, np.uint8)
-        kept = np.zeros(n, np.uint32)
+        dp = self._disp_ptr(disp, r.shape, "conf_mask")
+        n, out, mask, kept = self._mask_outputs(r)
         p = SnConfParams(min_conf)
-        self._check(self._lib.sn_conf_mask(self._h, n, r.ctypes.data, c.ctypes.data, C.byref(p), out.ctypes.data, _np_ptr(disp),
+        self._check(self._lib.sn_conf_mask(self._h, n, r.ctypes.data, c.ctypes.data, C.byref(p), out.ctypes.data, dp,
                                            mask.ctypes.data, kept.ctypes.data, SN_MEM_HOST, None), "sn_conf_mask")
         return out, mask, kept
 
@@ -591,14 +590,10 @@ class StereoNetHIP:
         removed, filled} per map); `disp` (float32, same shape) is rewritten IN PLACE where the mask is not 0 (0.0 at pixels
         that end invalid, the dequantised value at filled ones).  dispfilter.reference is the numpy twin."""
         r = self._maps(raw, "filter_raw")
-        if disp is not None and (disp.dtype != np.float32 or disp.shape != r.shape or not disp.flags.c_contiguous):
-            raise StereoNetError(-1, "filter_raw", "disp must be a C-contiguous float32 array of the maps' shape")
-        n = 1 if r.ndim == 2 else r.shape[0]
-        out = np.empty_like(r)
-        mask = np.empty(r.shape, np.uint8)
-        counts = np.zeros((n, 3), np.uint32)
+        dp = self._disp_ptr(disp, r.shape, "filter_raw")
+        n, out, mask, counts = self._mask_outputs(r, 3)
         p = SnFilterParams(int(speckle_max_px), speckle_diff_px, int(fill_max_px))
-        self._check(self._lib.sn_filter_raw(self._h, n, r.ctypes.data, C.byref(p), out.ctypes.data, _np_ptr(disp),
+        self._check(self._lib.sn_filter_raw(self._h, n, r.ctypes.data, C.byref(p), out.ctypes.data, dp,
                                             mask.ctypes.data, counts.ctypes.data, SN_MEM_HOST, None), "sn_filter_raw")
         return out, mask, counts
 

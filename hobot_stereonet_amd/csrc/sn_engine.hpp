@@ -1,5 +1,5 @@
 // sn_engine.hpp — the engine's data: layer, workspace, tower, async-slot and SN_PREC_AUTO types, the handle (sn_handle), and
-// the helpers every other part uses (HIP_TRY, set_err, memset_now, dalloc, DevScope, check_device).  No kernel is launched
+// the helpers every other part uses (HIP_TRY, set_err, memset_now, GrowBuf, dalloc, DevScope, check_device).  No kernel is launched
 // here.  Part of the single translation unit stereonet_hip.hip.
 #pragma once
 
@@ -33,6 +33,26 @@ inline hipError_t memset_now(void* p, int v, size_t bytes) {
   if (e != hipSuccess) return e;
   return hipStreamSynchronize(nullptr);
 }
+
+// A device (or pinned host) buffer that is only ever replaced by a larger one, so a warm caller allocates nothing.
+struct GrowBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool pinned = false;
+  hipError_t reserve(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    const hipError_t e = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    else p = nullptr;
+    return e;
+  }
+  void release() {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+};
 
 struct ConvLayer {
   uint4* wx3 = nullptr;    // device, split fp16 A-fragments [cin_pad/16][9][hi|lo][64 lanes] (fp16 modes, 3x3 layers)
@@ -204,31 +224,29 @@ struct sn_handle {
   mutable std::mutex err_mu;  // err is written by failing calls on any thread (sn_pointcloud_from_raw beside sn_wait)
   // sn_pointcloud_from_raw: everything of its own (it may run beside sn_submit / sn_wait), created on its first call
   struct PointCloud {
+    // compact form: valid samples per tile; host mode: raw, nv12, points, counts, and the pinned staging of raw and nv12
+    enum { kScratch = 0, kRaw, kNv12, kPoints, kCounts, kPinRaw, kPinNv12, kCount };
     std::mutex mu;
     hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;           // the last enqueue that used `scratch`
-    uint32_t* scratch = nullptr;       // compact form: valid samples per tile
-    size_t scratch_bytes = 0;
-    void* dev[4] = {};                 // host mode: raw, nv12, points, counts
-    size_t dev_bytes[4] = {};
-    void* pin[2] = {};                 // host mode: pinned staging of raw and nv12
-    size_t pin_bytes[2] = {};
+    hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
+    GrowBuf buf[kCount];
+    PointCloud() { buf[kPinRaw].pinned = buf[kPinNv12].pinned = true; }
   } pc;
-  // sn_mirror_pair_i8 / sn_lr_check / sn_infer_lrc / sn_infer_conf / sn_conf_mask: device buffers of their own, created on first use and only ever grown
-  struct LrCheck {
+  // The staging of the calls that run on the inference stream (sn_mirror_pair_i8 / sn_lr_check / sn_infer_lrc / sn_infer_conf /
+  // sn_conf_mask): host-mode copies and the composites' intermediate maps.  No lock: calls on one handle must not overlap.
+  struct InferStaging {
+    // input tensor, mirrored tensor, left map (masked in place), second map, float map, right map, mask, kept, confidence
     enum { kIn = 0, kMirror, kLeft, kRight, kDisp, kRightOut, kMask, kKept, kConf, kCount };
-    void* dev[kCount] = {};            // input tensor, mirrored tensor, left map, second map, float map, right map, mask, kept, confidence
-    size_t dev_bytes[kCount] = {};
-  } lrc;
+    GrowBuf buf[kCount];
+  } stage;
   // sn_filter_raw: everything of its own as the point cloud has (it may run beside sn_submit / sn_wait), created on first use
   struct Filter {
-    enum { kRaw = 0, kDisp, kMask, kCounts, kCount };
+    // label[slice][H][W] then size[slice][H][W]; host mode: map (filtered in place), float map, mask, counts
+    enum { kScratch = 0, kRaw, kDisp, kMask, kCounts, kCount };
     std::mutex mu;
     hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;           // the last enqueue that used `scratch`
-    uint32_t* scratch = nullptr;       // label[slice][H][W], then size[slice][H][W]
-    void* dev[kCount] = {};            // host mode: map (filtered in place), float map, mask, counts
-    size_t dev_bytes[kCount] = {};
+    hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
+    GrowBuf buf[kCount];
   } flt;
 };
 

@@ -36,6 +36,16 @@ __device__ __forceinline__ float pc_depth(int32_t r, float scale, float fB) {
   return (float)((double)fB / ((double)dis * 16.0 * 12.0) / 1000.0);
 }
 
+// Parse's arithmetic per element (parser.cpp:84-86): the product f * B is a float, everything after it is double
+__global__ __launch_bounds__(256) void k_depth_from_raw(const int32_t* __restrict__ raw, size_t n, float scale, float fB,
+                                                        float* __restrict__ depth, float* __restrict__ disp) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float dis = (float)raw[i] * scale;
+    depth[i] = (float)((double)fB / ((double)dis * 16.0 * 12.0) / 1000.0);
+    if (disp) disp[i] = dis * 16.0f * 12.0f;
+  }
+}
+
 __device__ __forceinline__ bool pc_valid(int32_t r, float z, const PcArgs& a) {
   return r > 0 && a.zmin <= z && (a.zmax <= 0.f || z <= a.zmax);
 }

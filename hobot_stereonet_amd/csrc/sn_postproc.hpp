@@ -1,0 +1,562 @@
+// sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
+// entry preamble, the k_pre_nv12 launcher, the pair-input staging, the per-call host staging and the overlap predicate — and
+// the C ABI of depth, point cloud, mirror, left-right check, confidence and filter.  The kernels are in sn_pointcloud.hpp,
+// sn_lrcheck.hpp, sn_confidence.hpp and sn_dispfilter.hpp.  Part of the single translation unit stereonet_hip.hip.
+#pragma once
+
+namespace {
+
+// ---- entry preamble ---------------------------------------------------------------------------------------------------
+struct Call {
+  hipStream_t st = nullptr;      // the caller's stream, or the default stream of the entry point
+  bool host = false;             // SN_MEM_HOST: the call stages its buffers and returns after completion
+  bool blocking = false;         // ... as does a device-mode call without a stream of the caller's
+};
+
+// What every entry point does after its own argument checks: `mem` is one of the two kinds, the handle's device is current,
+// and the call runs on `stream` or else on *own (h->stream; the point cloud's and the filter's are created on first use).
+int enter(sn_handle* h, const char* where, int mem, void* stream, hipStream_t* own, Call* c) {
+  if (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) {
+    set_err(h, std::string(where) + ": bad arguments");
+    return SN_ERR_ARG;
+  }
+  const int rc = check_device(h);
+  if (rc) return rc;
+  if (!*own) HIP_TRY(h, hipStreamCreateWithFlags(own, hipStreamNonBlocking));
+  c->st = stream ? static_cast<hipStream_t>(stream) : *own;
+  c->host = mem == SN_MEM_HOST;
+  c->blocking = c->host || !stream;
+  return SN_OK;
+}
+
+// ---- overlap ------------------------------------------------------------------------------------------------------------
+struct Span {
+  const void* p;
+  size_t bytes;
+};
+
+// a span of `a` shares a byte with a span of `b` (a null span shares none)
+bool overlap(std::initializer_list<Span> a, std::initializer_list<Span> b) {
+  for (const Span& x : a)
+    for (const Span& y : b) {
+      const uintptr_t xl = (uintptr_t)x.p, yl = (uintptr_t)y.p;
+      if (xl && yl && xl < yl + y.bytes && yl < xl + x.bytes) return true;
+    }
+  return false;
+}
+
+// ---- NV12 input ---------------------------------------------------------------------------------------------------------
+// k_pre_nv12 for one pair: the eyes at `left` / `right` in rows of `pitch` bytes -> the int8 tensor `out` (w % 4 == 0 and
+// 4-byte aligned pointers are the caller's checks, as is hipGetLastError)
+void launch_pre_nv12(hipStream_t st, const uint8_t* left, const uint8_t* right, int pitch, int w, int h_px, int8_t* out) {
+  const long total = 6L * h_px * (w >> 2);
+  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, left, right, pitch, w, h_px, out);
+}
+
+// geometry check of FeedImg (stereonet_node.cpp:682-690) for a side-by-side frame: height == model h, width == 2 * model w
+bool sbs_frame_ok(const sn_handle* h, int w2, int h_px) { return w2 / 2 == h->W && h_px == h->H && !(w2 & 7) && !(h_px & 1); }
+
+// FeedImg's split + CvtNV12Data2Tensors for n side-by-side frames -> n int8 tensors at `out` (device).  Host frames go one at
+// a time through the workspace's NV12 staging buffer.
+int sbs_to_tensors(sn_handle* h, hipStream_t st, int n, const uint8_t* sbs, int w2, int h_px, bool host, int8_t* out) {
+  const size_t HW = (size_t)h->H * h->W;
+  for (int i = 0; i < n; ++i) {
+    const uint8_t* src = sbs + (size_t)i * 3 * HW;
+    if (host) {
+      HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, src, 3 * HW, hipMemcpyHostToDevice, st));
+      src = h->ws.nv12;
+    }
+    launch_pre_nv12(st, src, src + w2 / 2, w2, w2 / 2, h_px, out + (size_t)i * 6 * HW);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+// ---- host staging of one call ------------------------------------------------------------------------------------------
+// Decides the device pointer of every buffer of a call.  Device mode: the caller's.  Host mode: a slot of the feature's
+// grow-only buffers, inputs uploaded as they are named, outputs remembered and copied back by download(), all on the call's
+// stream and in the order they were named.  A failure sticks in `rc` (SN_ERR_NOMEM for an allocation) and turns everything
+// after it into a no-op, so a call names all its buffers and tests `rc` once.
+struct Staging {
+  sn_handle* h;
+  const char* where;      // the entry point, for sn_last_error
+  hipStream_t st;
+  bool host;
+  GrowBuf* slots;         // the feature's buffers, indexed by its enum
+  int rc = SN_OK;
+  struct Back {
+    void* user;
+    const void* dev;
+    size_t bytes;
+  } back[6] = {};
+  int n_back = 0;
+
+  int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, kind, st));
+    return SN_OK;
+  }
+  template <class T>
+  T* staged(int which) const { return static_cast<T*>(slots[which].p); }
+  // slot `which`, at least `bytes` large, in either mode
+  template <class T>
+  T* scratch(int which, size_t bytes) {
+    if (rc) return nullptr;
+    if (slots[which].reserve(bytes) != hipSuccess) {
+      set_err(h, std::string(where) + ": out of device memory");
+      rc = SN_ERR_NOMEM;
+      return nullptr;
+    }
+    return staged<T>(which);
+  }
+  template <class T>
+  const T* in(int which, const T* user, size_t bytes) {
+    if (!host) return user;
+    T* d = scratch<T>(which, bytes);
+    if (d && (rc = copy(d, user, bytes, hipMemcpyHostToDevice))) return nullptr;
+    return d;
+  }
+  // a nullable output.  needed: the call itself reads it, so it has a device buffer even where the caller wants none
+  template <class T>
+  T* out(int which, T* user, size_t bytes, bool needed = false) {
+    if (user ? !host : !needed) return user;
+    return keep(user, scratch<T>(which, bytes), bytes);
+  }
+  // a nullable buffer the call reads and rewrites in place
+  template <class T>
+  T* inout(int which, T* user, size_t bytes) {
+    if (!host || !user) return user;
+    return keep(user, const_cast<T*>(in<T>(which, user, bytes)), bytes);
+  }
+  // a nullable output that the call writes into `dev`, a buffer it has staged already (host mode: filtered IN PLACE)
+  template <class T>
+  T* alias(T* user, T* dev, size_t bytes) {
+    return host ? keep(user, user ? dev : nullptr, bytes) : user;
+  }
+  // host mode: download() copies `dev` to `user`
+  template <class T>
+  T* keep(T* user, T* dev, size_t bytes) {
+    if (host && user && dev) back[n_back++] = Back{user, dev, bytes};
+    return dev;
+  }
+  int download() {
+    for (int i = 0; i < n_back; ++i)
+      if (int e = copy(back[i].user, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost)) return e;
+    return SN_OK;
+  }
+};
+
+// The `in` of sn_infer_lrc / sn_infer_conf — n int8 model tensors or n side-by-side NV12 frames, host or device — checked ...
+int pair_input_check(sn_handle* h, const char* where, const void* in, int in_kind, int w2, int h_px, int mem) {
+  if (in_kind != SN_LRC_IN_TENSOR && in_kind != SN_LRC_IN_SBS_NV12) {
+    set_err(h, std::string(where) + ": bad arguments");
+    return SN_ERR_ARG;
+  }
+  if (in_kind == SN_LRC_IN_SBS_NV12 && (!sbs_frame_ok(h, w2, h_px) || (mem == SN_MEM_DEVICE && ((uintptr_t)in & 3)))) {
+    set_err(h, std::string(where) + ": image size does not match the model input");
+    return SN_ERR_ARG;
+  }
+  return SN_OK;
+}
+
+// ... and brought to the device as tensors (s.rc on failure)
+const int8_t* pair_input(Staging& s, int n, const void* in, int in_kind, int w2, int h_px) {
+  using S = sn_handle::InferStaging;
+  const size_t bytes = (size_t)n * 6 * s.h->H * s.h->W;
+  if (in_kind != SN_LRC_IN_SBS_NV12) return s.in(S::kIn, static_cast<const int8_t*>(in), bytes);
+  int8_t* ten = s.scratch<int8_t>(S::kIn, bytes);
+  if (ten && (s.rc = sbs_to_tensors(s.h, s.st, n, static_cast<const uint8_t*>(in), w2, h_px, s.host, ten))) return nullptr;
+  return ten;
+}
+
+// ---- kernel launches (device pointers) ---------------------------------------------------------------------------------
+bool lrc_params_ok(const sn_lrc_params* p) {
+  return p && std::isfinite(p->tau_px) && std::isfinite(p->tau_rel) && p->tau_px >= 0.f && p->tau_rel >= 0.f;
+}
+
+bool conf_params_ok(const sn_conf_params* p) {
+  return p && std::isfinite(p->min_conf) && p->min_conf >= 0.f && p->min_conf <= 1.f;
+}
+
+int mirror_launch(sn_handle* h, hipStream_t st, int n, const int8_t* in, int8_t* out) {
+  MirrorArgs a{in, out, n, h->H, h->W};
+  const bool vec = (h->W & 15) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+  const size_t items = (size_t)n * 6 * h->H * (vec ? h->W >> 4 : h->W);
+  const unsigned grid = (unsigned)std::min<size_t>((items + 255) / 256, 8192);
+  if (vec) hipLaunchKernelGGL(k_mirror_pair<true>, dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_mirror_pair<false>, dim3(grid), dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+// right_out (nullable) receives the right map in right-image coordinates
+int lrc_launch(sn_handle* h, hipStream_t st, int n, const int32_t* left, const int32_t* right, const sn_lrc_params* p,
+               int32_t* out_raw, float* disp, uint8_t* mask, uint32_t* kept, int32_t* right_out) {
+  LrcArgs a{left, right, out_raw, disp, mask, kept, right_out, h->W, h->H, (float)((double)kOutScale * kWireFactor),
+            p->tau_px, p->tau_rel, p->right_mirrored != 0};
+  const bool vec = (h->W & 3) == 0 &&
+                   (((uintptr_t)left | (uintptr_t)right | (uintptr_t)out_raw | (uintptr_t)right_out) & 15) == 0 &&
+                   ((uintptr_t)mask & 3) == 0;
+  if (kept) HIP_TRY(h, hipMemsetAsync(kept, 0, (size_t)n * 4, st));
+  const int nseg = h->H * ((h->W + 255) / 256);
+  const int per_map = std::max(1, std::min((nseg + 3) / 4, 4096 / n));
+  if (vec) hipLaunchKernelGGL(k_lr_check<true>, dim3(per_map, n), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_lr_check<false>, dim3(per_map, n), dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+// low: conf_in is a low-resolution plane [n][hl][wl] (upsampled, out_conf nullable); else a full-resolution map.
+// p == nullptr: no masking (out_conf only)
+int conf_launch(sn_handle* h, hipStream_t st, int n, bool low, const float* conf_in, const int32_t* raw, const sn_conf_params* p,
+                float* out_conf, int32_t* out_raw, float* disp, uint8_t* mask, uint32_t* kept) {
+  if (!p && !(low && out_conf)) return SN_OK;      // nothing to write
+  ConfArgs a{conf_in, raw, out_conf, out_raw, disp, mask, kept, h->hl, h->wl, h->H, h->W, p ? p->min_conf : 0.f, p != nullptr};
+  if (p && kept) HIP_TRY(h, hipMemsetAsync(kept, 0, (size_t)n * 4, st));
+  const int blocks = (int)(((size_t)h->H * h->W + 255) / 256);      // about 1024 workgroups per call: see k_conf_apply
+  const dim3 grid((unsigned)std::max(1, std::min(blocks, 1024 / n)), (unsigned)n);
+  if (low) hipLaunchKernelGGL(k_conf_apply<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_conf_apply<false>, grid, dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- depth: Parse's dequantisation (k_depth_from_raw); per-call device buffers in host mode --------------------------------
+int sn_depth_from_raw(sn_handle* h, int n, const int32_t* raw, float focal_px, float baseline_mm, float* depth_m, float* disp_px,
+                      int mem, void* stream) {
+  if (!h || !raw || !depth_m || n <= 0 || n > h->max_batch) return SN_ERR_ARG;
+  Call c;
+  int rc = enter(h, "sn_depth_from_raw", mem, stream, &h->stream, &c);
+  if (rc) return rc;
+  const size_t cnt = (size_t)n * h->H * h->W;
+  const float fB = focal_px * baseline_mm;      // float product, as in the reference expression
+  const int32_t* draw = raw;
+  float *ddepth = depth_m, *ddisp = disp_px;
+  DevScope ds;
+  if (c.host) {
+    int32_t* a = nullptr;
+    float *b = nullptr, *d = nullptr;
+    HIP_TRY(h, ds.alloc(&a, cnt));
+    HIP_TRY(h, ds.alloc(&b, cnt));
+    if (disp_px) HIP_TRY(h, ds.alloc(&d, cnt));
+    HIP_TRY(h, hipMemcpyAsync(a, raw, cnt * 4, hipMemcpyHostToDevice, c.st));
+    draw = a;
+    ddepth = b;
+    ddisp = d;
+  }
+  unsigned grid = (unsigned)((cnt + 255) / 256);
+  if (grid > 4096) grid = 4096;
+  hipLaunchKernelGGL(k_depth_from_raw, dim3(grid), dim3(256), 0, c.st, draw, cnt, kOutScale, fB, ddepth, ddisp);
+  HIP_TRY(h, hipGetLastError());
+  if (c.host) {
+    HIP_TRY(h, hipMemcpyAsync(depth_m, ddepth, cnt * 4, hipMemcpyDeviceToHost, c.st));
+    if (disp_px) HIP_TRY(h, hipMemcpyAsync(disp_px, ddisp, cnt * 4, hipMemcpyDeviceToHost, c.st));
+    HIP_TRY(h, hipStreamSynchronize(c.st));
+  }
+  return SN_OK;
+}
+
+// ---- point cloud (csrc/sn_pointcloud.hpp): its own stream and mutex; host mode stages through pinned memory -----------------
+int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_t* nv12, int nv12_pitch, const sn_camera* cam,
+                           int layout, float* points, uint32_t* counts, int mem, void* stream) {
+  if (!h || !raw || !cam || !points || n <= 0 || n > h->max_batch || ((uintptr_t)points & 15) ||
+      (layout != SN_PC_ORGANISED && layout != SN_PC_COMPACT) || (layout == SN_PC_COMPACT && !counts))
+    return SN_ERR_ARG;
+  if (!(cam->fx > 0.f) || !std::isfinite(cam->fx) || !(cam->fy > 0.f) || !std::isfinite(cam->fy) ||
+      !(cam->baseline_mm > 0.f) || (cam->step != 1 && cam->step != 2 && cam->step != 4))
+    return SN_ERR_ARG;
+  if (nv12 && (nv12_pitch < h->W || (nv12_pitch & 1))) return SN_ERR_ARG;
+  using P = sn_handle::PointCloud;
+  auto& pc = h->pc;
+  std::lock_guard<std::mutex> lk(pc.mu);
+  Call c;
+  const int rc = enter(h, "sn_pointcloud_from_raw", mem, stream, &pc.stream, &c);
+  if (rc) return rc;
+  if (!pc.ev) HIP_TRY(h, hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
+  const int W = h->W, H = h->H, step = cam->step;
+  const int Wo = (W + step - 1) / step, Ho = (H + step - 1) / step;
+  const int tiles = (Ho * Wo + kPcTile - 1) / kPcTile;
+  const size_t raw_bytes = (size_t)n * H * W * 4, pts_bytes = (size_t)n * Ho * Wo * 16;
+  const size_t frame = (size_t)nv12_pitch * (H + (H + 1) / 2);    // an odd height has ceil(H/2) chroma rows
+  hipStream_t st = c.st;
+  HIP_TRY(h, hipStreamWaitEvent(st, pc.ev, 0));      // the previous call (any stream) is done with the scratch
+  if (layout == SN_PC_COMPACT && (size_t)n * tiles * 4 > pc.buf[P::kScratch].cap) {
+    HIP_TRY(h, hipEventSynchronize(pc.ev));
+    HIP_TRY(h, pc.buf[P::kScratch].reserve((size_t)n * tiles * 4));
+  }
+  PcArgs a{raw, nv12, reinterpret_cast<float4*>(points), counts, static_cast<uint32_t*>(pc.buf[P::kScratch].p), frame, W, H, Wo,
+           Ho, step, nv12_pitch, tiles, kOutScale, cam->fx * cam->baseline_mm, cam->fx, cam->fy, cam->cx, cam->cy, cam->z_min_m,
+           cam->z_max_m, 0};
+  if (c.host) {
+    // through pinned memory: the caller's pages may be pageable, and the call may run beside sn_submit / sn_wait
+    auto upload = [&](int pin, int dev, const void* src, size_t bytes) -> int {
+      HIP_TRY(h, pc.buf[pin].reserve(bytes));
+      HIP_TRY(h, pc.buf[dev].reserve(bytes));
+      memcpy(pc.buf[pin].p, src, bytes);
+      HIP_TRY(h, hipMemcpyAsync(pc.buf[dev].p, pc.buf[pin].p, bytes, hipMemcpyHostToDevice, st));
+      return SN_OK;
+    };
+    HIP_TRY(h, pc.buf[P::kPoints].reserve(pts_bytes));
+    HIP_TRY(h, pc.buf[P::kCounts].reserve((size_t)n * 4));
+    if (int e = upload(P::kPinRaw, P::kRaw, raw, raw_bytes)) return e;
+    if (nv12) {
+      if (int e = upload(P::kPinNv12, P::kNv12, nv12, n * frame)) return e;
+      a.nv12 = static_cast<const uint8_t*>(pc.buf[P::kNv12].p);
+    }
+    a.raw = static_cast<const int32_t*>(pc.buf[P::kRaw].p);
+    a.pts = static_cast<float4*>(pc.buf[P::kPoints].p);
+    a.counts = counts ? static_cast<uint32_t*>(pc.buf[P::kCounts].p) : nullptr;
+  }
+  a.vec = step == 1 && (W & 3) == 0 && ((uintptr_t)a.raw & 15) == 0;
+  if (layout == SN_PC_ORGANISED) {
+    if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 4, st));
+    const int nseg = Ho * ((Wo + 255) / 256);            // 256-column row segments, one per wave and iteration
+    const int per_map = std::max(1, std::min((nseg + 3) / 4, 2048 / n));
+    if (a.nv12) hipLaunchKernelGGL(k_pc_organised<true>, dim3(per_map, n), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_pc_organised<false>, dim3(per_map, n), dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(k_pc_count, dim3(tiles, n), dim3(256), 0, st, a);
+    if (a.nv12) hipLaunchKernelGGL(k_pc_write<true>, dim3(tiles, n), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_pc_write<false>, dim3(tiles, n), dim3(256), 0, st, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(pc.ev, st));
+  if (c.host) {
+    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, a.counts, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (layout == SN_PC_ORGANISED) {
+      HIP_TRY(h, hipMemcpyAsync(points, a.pts, pts_bytes, hipMemcpyDeviceToHost, st));
+    } else {
+      HIP_TRY(h, hipStreamSynchronize(st));      // the counts say how much of every map to copy
+      for (int k = 0; k < n; ++k)
+        if (counts[k])
+          HIP_TRY(h, hipMemcpyAsync(points + (size_t)k * Ho * Wo * 4, a.pts + (size_t)k * Ho * Wo, (size_t)counts[k] * 16,
+                                    hipMemcpyDeviceToHost, st));
+    }
+  }
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// ---- left-right consistency check (csrc/sn_lrcheck.hpp) --------------------------------------------------------------
+int sn_mirror_pair_i8(sn_handle* h, int n, const int8_t* in, int8_t* out, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  const size_t bytes = (size_t)(n > 0 ? n : 0) * 6 * h->H * h->W;
+  if (!in || !out || n <= 0 || n > h->max_batch || overlap({{in, bytes}}, {{out, bytes}})) {
+    set_err(h, "sn_mirror_pair_i8: bad arguments (in and out must not overlap)");
+    return SN_ERR_ARG;
+  }
+  Call c;
+  int rc = enter(h, "sn_mirror_pair_i8", mem, stream, &h->stream, &c);
+  if (rc) return rc;
+  using S = sn_handle::InferStaging;
+  Staging s{h, "sn_mirror_pair_i8", c.st, c.host, h->stage.buf};
+  const int8_t* din = s.in(S::kIn, in, bytes);
+  int8_t* dout = s.out(S::kMirror, out, bytes);
+  if (s.rc) return s.rc;
+  if ((rc = mirror_launch(h, c.st, n, din, dout))) return rc;
+  if ((rc = s.download())) return rc;
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
+  return SN_OK;
+}
+
+int sn_lr_check(sn_handle* h, int n, const int32_t* raw_left, const int32_t* raw_right, const sn_lrc_params* p,
+                int32_t* out_raw, float* disp_inout, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!raw_left || !raw_right || !lrc_params_ok(p) || (!out_raw && !mask) || n <= 0 || n > h->max_batch) {
+    set_err(h, "sn_lr_check: bad arguments");
+    return SN_ERR_ARG;
+  }
+  Call c;
+  int rc = enter(h, "sn_lr_check", mem, stream, &h->stream, &c);
+  if (rc) return rc;
+  using S = sn_handle::InferStaging;
+  Staging s{h, "sn_lr_check", c.st, c.host, h->stage.buf};
+  const size_t cnt = (size_t)n * h->H * h->W;
+  const int32_t* dl = s.in(S::kLeft, raw_left, cnt * 4);
+  const int32_t* dr = s.in(S::kRight, raw_right, cnt * 4);
+  int32_t* dout = s.alias(out_raw, s.staged<int32_t>(S::kLeft), cnt * 4);      // host mode: masked in place
+  float* ddisp = s.inout(S::kDisp, disp_inout, cnt * 4);
+  uint8_t* dmask = s.out(S::kMask, mask, cnt);
+  uint32_t* dkept = s.out(S::kKept, kept, (size_t)n * 4);
+  if (s.rc) return s.rc;
+  if ((rc = lrc_launch(h, c.st, n, dl, dr, p, dout, ddisp, dmask, dkept, nullptr))) return rc;
+  if ((rc = s.download())) return rc;
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
+  return SN_OK;
+}
+
+// L = forward(in), M = forward(mirror(in)), then the check of L against M in its mirrored storage: two run_forward calls, so
+// each is counted, folded into the refinement statistic and (SN_PREC_AUTO, blocking) repeated by the usual rule.
+int sn_infer_lrc(sn_handle* h, int n, const void* in, int in_kind, int w2, int h_px, const sn_lrc_params* p, int32_t* out_i32,
+                 float* out_disp, int32_t* out_right_i32, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!in || !lrc_params_ok(p) || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch) {
+    set_err(h, "sn_infer_lrc: bad arguments");
+    return SN_ERR_ARG;
+  }
+  int rc = pair_input_check(h, "sn_infer_lrc", in, in_kind, w2, h_px, mem);
+  if (rc) return rc;
+  Call c;
+  if ((rc = enter(h, "sn_infer_lrc", mem, stream, &h->stream, &c))) return rc;
+  using S = sn_handle::InferStaging;
+  Staging s{h, "sn_infer_lrc", c.st, c.host, h->stage.buf};
+  const size_t cnt = (size_t)n * h->H * h->W;
+  int8_t* dmir = s.scratch<int8_t>(S::kMirror, cnt * 6);
+  int32_t* dsecond = s.scratch<int32_t>(S::kRight, cnt * 4);
+  int32_t* dleft = s.out(S::kLeft, out_i32, cnt * 4, true);      // the check reads the left map, and masks it in place
+  float* ddisp = s.out(S::kDisp, out_disp, cnt * 4);
+  int32_t* dright = s.out(S::kRightOut, out_right_i32, cnt * 4);
+  uint8_t* dmask = s.out(S::kMask, mask, cnt);
+  uint32_t* dkept = s.out(S::kKept, kept, (size_t)n * 4);
+  const int8_t* din = pair_input(s, n, in, in_kind, w2, h_px);
+  if (s.rc) return s.rc;
+  auto nothing = []() -> int { return SN_OK; };
+  if ((rc = run_forward(h, c.st, n, din, ddisp, dleft, n == 1, c.blocking, nothing))) return rc;
+  if ((rc = mirror_launch(h, c.st, n, din, dmir))) return rc;
+  if ((rc = run_forward(h, c.st, n, dmir, nullptr, dsecond, false, c.blocking, nothing))) return rc;
+  sn_lrc_params q = *p;
+  q.right_mirrored = 1;
+  if ((rc = lrc_launch(h, c.st, n, dleft, dsecond, &q, dleft, ddisp, dmask, dkept, dright))) return rc;
+  if ((rc = s.download())) return rc;
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
+  return SN_OK;
+}
+
+// ---- confidence of the soft-argmin distribution and the mask on it (csrc/sn_confidence.hpp) ------------------------------------
+// One forward pass whose soft-argmin epilogue also writes the confidence plane; the upsample + mask kernel and the downloads
+// are run_forward's `post`, so a call that SN_PREC_AUTO repeats in SN_PREC_F16X3 masks and hands back the repeated maps.
+int sn_infer_conf(sn_handle* h, int n, const void* in, int in_kind, int w2, int h_px, const sn_conf_params* p, int32_t* out_i32,
+                  float* out_disp, float* out_conf, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!in || (p && !conf_params_ok(p)) || (!p && (mask || kept)) || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch) {
+    set_err(h, "sn_infer_conf: bad arguments");
+    return SN_ERR_ARG;
+  }
+  int rc = pair_input_check(h, "sn_infer_conf", in, in_kind, w2, h_px, mem);
+  if (rc) return rc;
+  Call c;
+  if ((rc = enter(h, "sn_infer_conf", mem, stream, &h->stream, &c))) return rc;
+  using S = sn_handle::InferStaging;
+  Staging s{h, "sn_infer_conf", c.st, c.host, h->stage.buf};
+  const size_t cnt = (size_t)n * h->H * h->W;
+  int32_t* draw = s.out(S::kLeft, out_i32, cnt * 4, p != nullptr);      // the mask rules read the map
+  float* ddisp = s.out(S::kDisp, out_disp, cnt * 4);
+  float* dconf = s.out(S::kConf, out_conf, cnt * 4);
+  uint8_t* dmask = s.out(S::kMask, mask, cnt);
+  uint32_t* dkept = s.out(S::kKept, kept, (size_t)n * 4);
+  const int8_t* din = pair_input(s, n, in, in_kind, w2, h_px);
+  if (s.rc) return s.rc;
+  auto post = [&]() -> int {
+    const int prc = conf_launch(h, c.st, n, true, h->ws.conf_low, draw, p, dconf, draw, ddisp, dmask, dkept);
+    return prc ? prc : s.download();
+  };
+  return run_forward(h, c.st, n, din, ddisp, draw, n == 1, c.blocking, post, true);
+}
+
+int sn_conf_mask(sn_handle* h, int n, const int32_t* raw, const float* conf, const sn_conf_params* p, int32_t* out_raw,
+                 float* disp_inout, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!raw || !conf || !conf_params_ok(p) || (!out_raw && !mask) || n <= 0 || n > h->max_batch) {
+    set_err(h, "sn_conf_mask: bad arguments");
+    return SN_ERR_ARG;
+  }
+  const size_t cnt = (size_t)n * h->H * h->W;
+  // conf is read by every pixel's thread: it must not be one of the outputs
+  if (overlap({{conf, cnt * 4}}, {{out_raw, cnt * 4}, {disp_inout, cnt * 4}, {mask, cnt}, {kept, (size_t)n * 4}})) {
+    set_err(h, "sn_conf_mask: conf overlaps an output");
+    return SN_ERR_ARG;
+  }
+  Call c;
+  int rc = enter(h, "sn_conf_mask", mem, stream, &h->stream, &c);
+  if (rc) return rc;
+  using S = sn_handle::InferStaging;
+  Staging s{h, "sn_conf_mask", c.st, c.host, h->stage.buf};
+  const int32_t* draw = s.in(S::kLeft, raw, cnt * 4);
+  const float* dconf = s.in(S::kConf, conf, cnt * 4);
+  int32_t* dout = s.alias(out_raw, s.staged<int32_t>(S::kLeft), cnt * 4);      // host mode: masked in place
+  float* ddisp = s.inout(S::kDisp, disp_inout, cnt * 4);
+  uint8_t* dmask = s.out(S::kMask, mask, cnt);
+  uint32_t* dkept = s.out(S::kKept, kept, (size_t)n * 4);
+  if (s.rc) return s.rc;
+  if ((rc = conf_launch(h, c.st, n, false, dconf, draw, p, nullptr, dout, ddisp, dmask, dkept))) return rc;
+  if ((rc = s.download())) return rc;
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
+  return SN_OK;
+}
+
+// ---- speckle removal and hole filling (csrc/sn_dispfilter.hpp): its own stream and mutex -----------------------------------------
+int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_params* p, int32_t* out_raw, float* disp_inout,
+                  uint8_t* mask, uint32_t* counts, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  const size_t HW = (size_t)h->H * h->W;
+  if (!raw || !p || (!out_raw && !mask) || n <= 0 || n > h->max_batch || p->speckle_max_px < 0 ||
+      (size_t)p->speckle_max_px > HW || !std::isfinite(p->speckle_diff_px) || p->speckle_diff_px < 0.f || p->fill_max_px < 0 ||
+      (p->speckle_max_px == 0 && p->fill_max_px == 0) || HW > 0x7fffffffu) {
+    set_err(h, "sn_filter_raw: bad arguments");
+    return SN_ERR_ARG;
+  }
+  const size_t cnt = (size_t)n * HW;
+  {      // out_raw == raw is the one overlap the kernels are written for
+    const Span r{raw, cnt * 4}, o{out_raw, cnt * 4}, d{disp_inout, cnt * 4}, m{mask, cnt}, k{counts, (size_t)n * 12};
+    if ((out_raw != raw && overlap({r}, {o})) || overlap({r, o}, {d, m, k}) || overlap({d}, {m, k}) || overlap({m}, {k})) {
+      set_err(h, "sn_filter_raw: overlapping buffers (only out_raw == raw is allowed)");
+      return SN_ERR_ARG;
+    }
+  }
+  using F = sn_handle::Filter;
+  auto& f = h->flt;
+  std::lock_guard<std::mutex> lk(f.mu);
+  Call c;
+  const int rc = enter(h, "sn_filter_raw", mem, stream, &f.stream, &c);
+  if (rc) return rc;
+  if (!f.ev) HIP_TRY(h, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+  hipStream_t st = c.st;
+  Staging s{h, "sn_filter_raw", st, c.host, f.buf};
+  const int slice = std::min(h->max_batch, kFltSlice);
+  uint32_t* scratch = p->speckle_max_px ? s.scratch<uint32_t>(F::kScratch, (size_t)slice * HW * 8) : s.staged<uint32_t>(F::kScratch);
+  if (s.rc) return s.rc;
+  HIP_TRY(h, hipStreamWaitEvent(st, f.ev, 0));      // the previous call (any stream) is done with the scratch and the staging
+  const float S = (float)((double)kOutScale * kWireFactor);
+  const float q = floorf(p->speckle_diff_px / S);
+  const int32_t* draw = s.in(F::kRaw, raw, cnt * 4);
+  int32_t* dout = s.alias(out_raw, s.staged<int32_t>(F::kRaw), cnt * 4);      // host mode: filtered in place
+  float* ddisp = s.inout(F::kDisp, disp_inout, cnt * 4);
+  uint8_t* dmask = s.out(F::kMask, mask, cnt);
+  uint32_t* dcounts = s.out(F::kCounts, counts, (size_t)n * 12);
+  if (s.rc) return s.rc;
+  FltArgs a{draw, dout, ddisp, dmask, dcounts, scratch, scratch ? scratch + (size_t)slice * HW : nullptr, h->W, h->H,
+            (h->W + kFltTW - 1) / kFltTW, (h->H + kFltTH - 1) / kFltTH, q >= 4294967296.f ? 4294967296ll : (long long)q,
+            (uint32_t)p->speckle_max_px, p->fill_max_px, S};
+  const FltArgs all = a;
+  if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 12, st));
+  const bool vec = (h->W & 3) == 0 && ((uintptr_t)a.mask & 3) == 0;
+  const int pairs = (a.tiles_x - 1) * h->H + (a.tiles_y - 1) * h->W;
+  for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` maps: walk the batch on the stream
+    const int m = std::min(slice, n - k0);
+    const size_t off = (size_t)k0 * HW;
+    a.raw = all.raw + off;
+    a.out_raw = all.out_raw ? all.out_raw + off : nullptr;
+    a.disp = all.disp ? all.disp + off : nullptr;
+    a.mask = all.mask ? all.mask + off : nullptr;
+    a.counts = all.counts ? all.counts + (size_t)k0 * 3 : nullptr;
+    if (a.max_px) {
+      hipLaunchKernelGGL(k_flt_label, dim3(a.tiles_x * a.tiles_y, m), dim3(256), 0, st, a);
+      if (pairs) hipLaunchKernelGGL(k_flt_seam, dim3((pairs + 255) / 256, m), dim3(256), 0, st, a);
+      hipLaunchKernelGGL(k_flt_flatten, dim3((unsigned)((HW + 255) / 256), m), dim3(256), 0, st, a);
+    }
+    const int per_map = std::max(1, std::min((h->H + 3) / 4, 4096 / m));
+    if (vec) hipLaunchKernelGGL(k_flt_apply<true>, dim3(per_map, m), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_flt_apply<false>, dim3(per_map, m), dim3(256), 0, st, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  if (int e = s.download()) return e;
+  HIP_TRY(h, hipEventRecord(f.ev, st));
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,8 @@
 // stereonet_hip.hip — the one translation unit of the engine of libstereonet_hip.so: the headers below, one concern each and
-// included in order, then the public C ABI (include/stereonet_hip.h): create, destroy, infer, submit / wait, preprocess,
-// measurement, depth, point cloud, left-right check.  DESIGN.md §6 has the source map.
+// included in order, then the engine's own part of the public C ABI (include/stereonet_hip.h): create / destroy, io info,
+// SN_PREC_AUTO's state machine, infer, preprocess, submit / wait and the measurement hooks.  The entry points that follow the
+// network — depth, point cloud, mirror, left-right check, confidence, filter — and the host helpers they share with the ones
+// here (entry preamble, NV12 launcher) are in sn_postproc.hpp.  DESIGN.md §6 has the source map.
 //
 // Replaces, for the StereoNet hot path, what the reference obtains from the closed dnn_node /
 // libdnn runtime: model load (DnnNode::Init, stereonet_infer/src/stereonet_node.cpp:44), tensor
@@ -34,6 +36,7 @@
 #include "sn_weights.hpp"       // .snw reader, weight packing and upload
 #include "sn_launch.hpp"        // kernel launchers and tensor geometry
 #include "sn_forward.hpp"       // workspace allocation, forward pass, refinement statistic, SN_PREC_AUTO
+#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter
 #include "sn_dbg_hooks.hpp"     // sn_dbg_* parity hooks
 
 // =====================================================================================================
@@ -378,15 +381,11 @@ int sn_destroy(sn_handle* h) {
     hipFree(T.rout.w);
   }
   hipFree(h->dump);
-  hipFree(h->pc.scratch);
-  for (void* p : h->pc.dev) hipFree(p);
-  for (void* p : h->pc.pin)
-    if (p) hipHostFree(p);
+  for (GrowBuf& b : h->pc.buf) b.release();
+  for (GrowBuf& b : h->stage.buf) b.release();
+  for (GrowBuf& b : h->flt.buf) b.release();
   if (h->pc.ev) hipEventDestroy(h->pc.ev);
   if (h->pc.stream) hipStreamDestroy(h->pc.stream);
-  for (void* p : h->lrc.dev) hipFree(p);
-  hipFree(h->flt.scratch);
-  for (void* p : h->flt.dev) hipFree(p);
   if (h->flt.ev) hipEventDestroy(h->flt.ev);
   if (h->flt.stream) hipStreamDestroy(h->flt.stream);
   hipFree(h->aout.w);
@@ -538,54 +537,54 @@ int sn_get_refine_stats(sn_handle* h, sn_refine_stats* out) {
 int sn_infer_batch(sn_handle* h, int n, const int8_t* in, int32_t* out_i32, float* out_disp, int mem,
                    void* stream) {
   if (!h) return SN_ERR_ARG;
-  if (!in || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch || (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) {
+  if (!in || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch) {
     set_err(h, "sn_infer_batch: bad arguments");
     return SN_ERR_ARG;
   }
-  int rc = check_device(h);
+  Call c;
+  const int rc = enter(h, "sn_infer_batch", mem, stream, &h->stream, &c);
   if (rc) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = c.st;
   const size_t HW = (size_t)h->H * h->W;
   const int8_t* din = in;
   int32_t* draw = out_i32;
   float* ddisp = out_disp;
-  if (mem == SN_MEM_HOST) {
+  if (c.host) {
     HIP_TRY(h, hipMemcpyAsync(h->ws.in6, in, (size_t)n * 6 * HW, hipMemcpyHostToDevice, st));
     din = h->ws.in6;
     draw = out_i32 ? h->ws.out_raw : nullptr;
     ddisp = out_disp ? h->ws.out_disp : nullptr;
   }
   auto post = [&]() -> int {
-    if (mem == SN_MEM_HOST) {
+    if (c.host) {
       if (out_i32) HIP_TRY(h, hipMemcpyAsync(out_i32, draw, (size_t)n * HW * 4, hipMemcpyDeviceToHost, st));
       if (out_disp) HIP_TRY(h, hipMemcpyAsync(out_disp, ddisp, (size_t)n * HW * 4, hipMemcpyDeviceToHost, st));
     }
     return SN_OK;
   };
-  return run_forward(h, st, n, din, ddisp, draw, n == 1, mem == SN_MEM_HOST || !stream, post);
+  return run_forward(h, st, n, din, ddisp, draw, n == 1, c.blocking, post);
 }
 
 int sn_infer_i8(sn_handle* h, const int8_t* in, int32_t* out_i32, float* out_disp, int mem, void* stream) {
   return sn_infer_batch(h, 1, in, out_i32, out_disp, mem, stream);
 }
 
-static int pre_args_ok(sn_handle* h, int w, int hp) { return w == h->W && hp == h->H; }
-
 int sn_preprocess_nv12(sn_handle* h, const uint8_t* left, const uint8_t* right, int w, int h_px,
                        int8_t* out6, int mem, void* stream) {
   if (!h) return SN_ERR_ARG;
   if (!left || !right || !out6 || w <= 0 || h_px <= 0 || (w & 3) || (h_px & 1) ||
-      (size_t)w * h_px > (size_t)h->W * h->H || (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) {
+      (size_t)w * h_px > (size_t)h->W * h->H) {
     set_err(h, "sn_preprocess_nv12: bad arguments");
     return SN_ERR_ARG;
   }
-  int rc = check_device(h);
+  Call c;
+  const int rc = enter(h, "sn_preprocess_nv12", mem, stream, &h->stream, &c);
   if (rc) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = c.st;
   const size_t eye = (size_t)w * h_px * 3 / 2;
   const uint8_t *dl = left, *dr = right;
   int8_t* dout = out6;
-  if (mem == SN_MEM_HOST) {
+  if (c.host) {
     HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, left, eye, hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(h->ws.nv12 + eye, right, eye, hipMemcpyHostToDevice, st));
     dl = h->ws.nv12;
@@ -594,57 +593,50 @@ int sn_preprocess_nv12(sn_handle* h, const uint8_t* left, const uint8_t* right, 
   } else if (((uintptr_t)left | (uintptr_t)right | (uintptr_t)out6) & 3) {
     return SN_ERR_ARG;
   }
-  const long total = 6L * h_px * (w >> 2);
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, dl, dr, w, w, h_px, dout);
+  launch_pre_nv12(st, dl, dr, w, w, h_px, dout);
   HIP_TRY(h, hipGetLastError());
-  if (mem == SN_MEM_HOST)
-    HIP_TRY(h, hipMemcpyAsync(out6, dout, (size_t)6 * w * h_px, hipMemcpyDeviceToHost, st));
-  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
+  if (c.host) HIP_TRY(h, hipMemcpyAsync(out6, dout, (size_t)6 * w * h_px, hipMemcpyDeviceToHost, st));
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }
 
 int sn_infer_sbs_nv12(sn_handle* h, const uint8_t* sbs, int w2, int h_px, int32_t* out_i32, float* out_disp,
                       int8_t* out_tensor, int mem, void* stream) {
   if (!h) return SN_ERR_ARG;
-  // geometry check of FeedImg (stereonet_node.cpp:682-690): height == model h, width == 2 * model w
-  if (!sbs || (!out_i32 && !out_disp) || !pre_args_ok(h, w2 / 2, h_px) || (w2 & 7) || (h_px & 1) ||
-      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) {
+  if (!sbs || (!out_i32 && !out_disp) || !sbs_frame_ok(h, w2, h_px)) {
     set_err(h, "sn_infer_sbs_nv12: image size does not match the model input");
     return SN_ERR_ARG;
   }
-  int rc = check_device(h);
+  Call c;
+  const int rc = enter(h, "sn_infer_sbs_nv12", mem, stream, &h->stream, &c);
   if (rc) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  const int w = w2 / 2;
+  hipStream_t st = c.st;
   const size_t HW = (size_t)h->H * h->W;
   const uint8_t* dsrc = sbs;
-  if (mem == SN_MEM_HOST) {
+  if (c.host) {
     HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, sbs, HW * 3, hipMemcpyHostToDevice, st));
     dsrc = h->ws.nv12;
   } else if ((uintptr_t)sbs & 3) {
     return SN_ERR_ARG;
   }
-  int8_t* din = (mem == SN_MEM_DEVICE && out_tensor) ? out_tensor : h->ws.in6;
-  const long total = 6L * h_px * (w >> 2);
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, dsrc, dsrc + w, w2, w, h_px, din);
+  int8_t* din = (!c.host && out_tensor) ? out_tensor : h->ws.in6;
+  launch_pre_nv12(st, dsrc, dsrc + w2 / 2, w2, w2 / 2, h_px, din);
   HIP_TRY(h, hipGetLastError());
   int32_t* draw = out_i32;
   float* ddisp = out_disp;
-  if (mem == SN_MEM_HOST) {
+  if (c.host) {
     draw = out_i32 ? h->ws.out_raw : nullptr;
     ddisp = out_disp ? h->ws.out_disp : nullptr;
   }
   auto post = [&]() -> int {
-    if (mem == SN_MEM_HOST) {
+    if (c.host) {
       if (out_i32) HIP_TRY(h, hipMemcpyAsync(out_i32, draw, HW * 4, hipMemcpyDeviceToHost, st));
       if (out_disp) HIP_TRY(h, hipMemcpyAsync(out_disp, ddisp, HW * 4, hipMemcpyDeviceToHost, st));
       if (out_tensor) HIP_TRY(h, hipMemcpyAsync(out_tensor, din, HW * 6, hipMemcpyDeviceToHost, st));
     }
     return SN_OK;
   };
-  return run_forward(h, st, 1, din, ddisp, draw, true, mem == SN_MEM_HOST || !stream, post);
+  return run_forward(h, st, 1, din, ddisp, draw, true, c.blocking, post);
 }
 
 // FeedImg's split + CvtNV12Data2Tensors for a batch of side-by-side frames (device or host buffers): n frames of
@@ -653,32 +645,18 @@ int sn_infer_sbs_nv12(sn_handle* h, const uint8_t* sbs, int w2, int h_px, int32_
 int sn_preprocess_sbs_nv12_batch(sn_handle* h, int n, const uint8_t* sbs, int w2, int h_px, int8_t* out6, int mem,
                                  void* stream) {
   if (!h) return SN_ERR_ARG;
-  if (!sbs || !out6 || n <= 0 || !pre_args_ok(h, w2 / 2, h_px) || (w2 & 7) || (h_px & 1) ||
-      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) || (mem == SN_MEM_HOST && n > h->max_batch)) {
+  if (!sbs || !out6 || n <= 0 || !sbs_frame_ok(h, w2, h_px) || (mem == SN_MEM_HOST && n > h->max_batch)) {
     set_err(h, "sn_preprocess_sbs_nv12_batch: bad arguments");
     return SN_ERR_ARG;
   }
   if (mem == SN_MEM_DEVICE && (((uintptr_t)sbs | (uintptr_t)out6) & 3)) return SN_ERR_ARG;
-  int rc = check_device(h);
+  Call c;
+  int rc = enter(h, "sn_preprocess_sbs_nv12_batch", mem, stream, &h->stream, &c);
   if (rc) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  const int w = w2 / 2;
   const size_t HW = (size_t)h->H * h->W;
-  const long total = 6L * h_px * (w >> 2);
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  for (int i = 0; i < n; ++i) {
-    const uint8_t* src = sbs + (size_t)i * 3 * HW;
-    int8_t* dst = out6 + (size_t)i * 6 * HW;
-    if (mem == SN_MEM_HOST) {           // one frame at a time through the NV12 staging buffer
-      HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, src, 3 * HW, hipMemcpyHostToDevice, st));
-      src = h->ws.nv12;
-      dst = h->ws.in6 + (size_t)i * 6 * HW;
-    }
-    hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, src, src + w, w2, w, h_px, dst);
-  }
-  HIP_TRY(h, hipGetLastError());
-  if (mem == SN_MEM_HOST) HIP_TRY(h, hipMemcpyAsync(out6, h->ws.in6, (size_t)n * 6 * HW, hipMemcpyDeviceToHost, st));
-  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
+  if ((rc = sbs_to_tensors(h, c.st, n, sbs, w2, h_px, c.host, c.host ? h->ws.in6 : out6))) return rc;
+  if (c.host) HIP_TRY(h, hipMemcpyAsync(out6, h->ws.in6, (size_t)n * 6 * HW, hipMemcpyDeviceToHost, c.st));
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
   return SN_OK;
 }
 
@@ -759,10 +737,7 @@ static int submit_common(sn_handle* h, const void* in, int kind, int32_t* out_i3
   auto enqueue = [&]() -> int {
     if (kind == 1) {
       HIP_TRY(h, hipMemcpyAsync(s->ws.nv12, s->pin_in, 3 * HW, hipMemcpyHostToDevice, s->stream));
-      const long total = 6L * h->H * (h->W >> 2);
-      const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-      hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, s->stream, s->ws.nv12, s->ws.nv12 + h->W, 2 * h->W, h->W,
-                         h->H, s->ws.in6);
+      launch_pre_nv12(s->stream, s->ws.nv12, s->ws.nv12 + h->W, 2 * h->W, h->W, h->H, s->ws.in6);
       HIP_TRY(h, hipGetLastError());
     } else {
       HIP_TRY(h, hipMemcpyAsync(s->ws.in6, s->pin_in, 6 * HW, hipMemcpyHostToDevice, s->stream));
@@ -816,7 +791,7 @@ int sn_submit_nv12(sn_handle* h, const uint8_t* sbs, int w2, int h_px, int32_t* 
                    int timeout_ms, uint64_t* ticket) {
   if (!h) return SN_ERR_ARG;
   // geometry check of FeedImg (stereonet_node.cpp:682-690): height == model h, width == 2 * model w
-  if (!pre_args_ok(h, w2 / 2, h_px) || (w2 & 7) || (h_px & 1)) {
+  if (!sbs_frame_ok(h, w2, h_px)) {
     set_err(h, "sn_submit_nv12: image size does not match the model input");
     return SN_ERR_ARG;
   }
@@ -940,570 +915,6 @@ int sn_get_dominant_kernel(sn_handle* h, char* name, size_t cap, int* launches, 
   // algorithmic HBM bytes per launch: read the 32-channel input once + write the output once, plus the
   // residual read on the launches that have one, averaged; element = 2 B (fp16) or 4 B (fp32)
   if (bytes) *bytes = px * kC * (f16 ? 2.0 : 4.0) * (2.0 * n_plain + 3.0 * n_res) / (double)(n_plain + n_res);
-  return SN_OK;
-}
-
-// Parse's arithmetic per element (parser.cpp:84-86): the product f * B is a float, everything after it is double
-__global__ __launch_bounds__(256) void k_depth_from_raw(const int32_t* __restrict__ raw, size_t n, float scale, float fB,
-                                                        float* __restrict__ depth, float* __restrict__ disp) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    const float dis = (float)raw[i] * scale;
-    depth[i] = (float)((double)fB / ((double)dis * 16.0 * 12.0) / 1000.0);
-    if (disp) disp[i] = dis * 16.0f * 12.0f;
-  }
-}
-
-int sn_depth_from_raw(sn_handle* h, int n, const int32_t* raw, float focal_px, float baseline_mm, float* depth_m, float* disp_px,
-                      int mem, void* stream) {
-  if (!h || !raw || !depth_m || n <= 0 || n > h->max_batch || (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) return SN_ERR_ARG;
-  int rc = check_device(h);
-  if (rc) return rc;
-  const size_t cnt = (size_t)n * h->H * h->W;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  const float fB = focal_px * baseline_mm;      // float product, as in the reference expression
-  const int32_t* draw = raw;
-  float *ddepth = depth_m, *ddisp = disp_px;
-  DevScope ds;
-  if (mem == SN_MEM_HOST) {
-    int32_t* a = nullptr;
-    float *b = nullptr, *c = nullptr;
-    HIP_TRY(h, ds.alloc(&a, cnt));
-    HIP_TRY(h, ds.alloc(&b, cnt));
-    if (disp_px) HIP_TRY(h, ds.alloc(&c, cnt));
-    HIP_TRY(h, hipMemcpyAsync(a, raw, cnt * 4, hipMemcpyHostToDevice, st));
-    draw = a;
-    ddepth = b;
-    ddisp = c;
-  }
-  unsigned grid = (unsigned)((cnt + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(k_depth_from_raw, dim3(grid), dim3(256), 0, st, draw, cnt, kOutScale, fB, ddepth, ddisp);
-  HIP_TRY(h, hipGetLastError());
-  if (mem == SN_MEM_HOST) {
-    HIP_TRY(h, hipMemcpyAsync(depth_m, ddepth, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (disp_px) HIP_TRY(h, hipMemcpyAsync(disp_px, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-  }
-  return SN_OK;
-}
-
-// Grows a buffer of the point-cloud state; a buffer is only ever replaced by a larger one, so a warm caller allocates nothing.
-static hipError_t pc_grow(void** p, size_t* have, size_t bytes, bool pinned) {
-  if (bytes <= *have) return hipSuccess;
-  if (*p) {
-    if (pinned) hipHostFree(*p);
-    else hipFree(*p);
-  }
-  *p = nullptr;
-  *have = 0;
-  const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
-  if (e == hipSuccess) *have = bytes;
-  return e;
-}
-
-int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_t* nv12, int nv12_pitch, const sn_camera* cam,
-                           int layout, float* points, uint32_t* counts, int mem, void* stream) {
-  if (!h || !raw || !cam || !points || n <= 0 || n > h->max_batch || ((uintptr_t)points & 15) ||
-      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) || (layout != SN_PC_ORGANISED && layout != SN_PC_COMPACT) ||
-      (layout == SN_PC_COMPACT && !counts))
-    return SN_ERR_ARG;
-  if (!(cam->fx > 0.f) || !std::isfinite(cam->fx) || !(cam->fy > 0.f) || !std::isfinite(cam->fy) ||
-      !(cam->baseline_mm > 0.f) || (cam->step != 1 && cam->step != 2 && cam->step != 4))
-    return SN_ERR_ARG;
-  if (nv12 && (nv12_pitch < h->W || (nv12_pitch & 1))) return SN_ERR_ARG;
-  int rc = check_device(h);
-  if (rc) return rc;
-  auto& pc = h->pc;
-  std::lock_guard<std::mutex> lk(pc.mu);
-  if (!pc.stream) HIP_TRY(h, hipStreamCreateWithFlags(&pc.stream, hipStreamNonBlocking));
-  if (!pc.ev) HIP_TRY(h, hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
-  const int W = h->W, H = h->H, step = cam->step;
-  const int Wo = (W + step - 1) / step, Ho = (H + step - 1) / step;
-  const int tiles = (Ho * Wo + kPcTile - 1) / kPcTile;
-  const size_t raw_bytes = (size_t)n * H * W * 4, pts_bytes = (size_t)n * Ho * Wo * 16;
-  const size_t frame = (size_t)nv12_pitch * (H + (H + 1) / 2);    // an odd height has ceil(H/2) chroma rows
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : pc.stream;
-  HIP_TRY(h, hipStreamWaitEvent(st, pc.ev, 0));      // the previous call (any stream) is done with the scratch
-  if (layout == SN_PC_COMPACT && (size_t)n * tiles * 4 > pc.scratch_bytes) {
-    HIP_TRY(h, hipEventSynchronize(pc.ev));
-    HIP_TRY(h, pc_grow(reinterpret_cast<void**>(&pc.scratch), &pc.scratch_bytes, (size_t)n * tiles * 4, false));
-  }
-  PcArgs a{raw, nv12, reinterpret_cast<float4*>(points), counts, pc.scratch, frame, W, H, Wo, Ho, step, nv12_pitch, tiles,
-           kOutScale, cam->fx * cam->baseline_mm, cam->fx, cam->fy, cam->cx, cam->cy, cam->z_min_m, cam->z_max_m, 0};
-  if (mem == SN_MEM_HOST) {
-    HIP_TRY(h, pc_grow(&pc.pin[0], &pc.pin_bytes[0], raw_bytes, true));
-    HIP_TRY(h, pc_grow(&pc.dev[0], &pc.dev_bytes[0], raw_bytes, false));
-    HIP_TRY(h, pc_grow(&pc.dev[2], &pc.dev_bytes[2], pts_bytes, false));
-    HIP_TRY(h, pc_grow(&pc.dev[3], &pc.dev_bytes[3], (size_t)n * 4, false));
-    memcpy(pc.pin[0], raw, raw_bytes);
-    HIP_TRY(h, hipMemcpyAsync(pc.dev[0], pc.pin[0], raw_bytes, hipMemcpyHostToDevice, st));
-    if (nv12) {
-      HIP_TRY(h, pc_grow(&pc.pin[1], &pc.pin_bytes[1], n * frame, true));
-      HIP_TRY(h, pc_grow(&pc.dev[1], &pc.dev_bytes[1], n * frame, false));
-      memcpy(pc.pin[1], nv12, n * frame);
-      HIP_TRY(h, hipMemcpyAsync(pc.dev[1], pc.pin[1], n * frame, hipMemcpyHostToDevice, st));
-      a.nv12 = static_cast<const uint8_t*>(pc.dev[1]);
-    }
-    a.raw = static_cast<const int32_t*>(pc.dev[0]);
-    a.pts = static_cast<float4*>(pc.dev[2]);
-    a.counts = counts ? static_cast<uint32_t*>(pc.dev[3]) : nullptr;
-  }
-  a.vec = step == 1 && (W & 3) == 0 && ((uintptr_t)a.raw & 15) == 0;
-  if (layout == SN_PC_ORGANISED) {
-    if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 4, st));
-    const int nseg = Ho * ((Wo + 255) / 256);            // 256-column row segments, one per wave and iteration
-    const int per_map = std::max(1, std::min((nseg + 3) / 4, 2048 / n));
-    if (a.nv12) hipLaunchKernelGGL(k_pc_organised<true>, dim3(per_map, n), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_pc_organised<false>, dim3(per_map, n), dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(k_pc_count, dim3(tiles, n), dim3(256), 0, st, a);
-    if (a.nv12) hipLaunchKernelGGL(k_pc_write<true>, dim3(tiles, n), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_pc_write<false>, dim3(tiles, n), dim3(256), 0, st, a);
-  }
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipEventRecord(pc.ev, st));
-  if (mem == SN_MEM_HOST) {
-    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, a.counts, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (layout == SN_PC_ORGANISED) {
-      HIP_TRY(h, hipMemcpyAsync(points, a.pts, pts_bytes, hipMemcpyDeviceToHost, st));
-    } else {
-      HIP_TRY(h, hipStreamSynchronize(st));      // the counts say how much of every map to copy
-      for (int k = 0; k < n; ++k)
-        if (counts[k])
-          HIP_TRY(h, hipMemcpyAsync(points + (size_t)k * Ho * Wo * 4, a.pts + (size_t)k * Ho * Wo, (size_t)counts[k] * 16,
-                                    hipMemcpyDeviceToHost, st));
-    }
-  }
-  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
-}
-
-// ---- left-right consistency check (csrc/sn_lrcheck.hpp) --------------------------------------------------------------
-static bool lrc_params_ok(const sn_lrc_params* p) {
-  return p && std::isfinite(p->tau_px) && std::isfinite(p->tau_rel) && p->tau_px >= 0.f && p->tau_rel >= 0.f;
-}
-
-// buffer `which` of the handle's LrCheck state, at least `bytes` large (nullptr: the allocation failed)
-static void* lrc_buf(sn_handle* h, int which, size_t bytes) {
-  return pc_grow(&h->lrc.dev[which], &h->lrc.dev_bytes[which], bytes, false) == hipSuccess ? h->lrc.dev[which] : nullptr;
-}
-#define LRC_BUF(h, dst, type, which, bytes)                                     \
-  do {                                                                          \
-    if (!((dst) = static_cast<type>(lrc_buf(h, sn_handle::LrCheck::which, bytes)))) {   \
-      set_err(h, "left-right check: out of device memory");                     \
-      return SN_ERR_NOMEM;                                                      \
-    }                                                                           \
-  } while (0)
-
-static int mirror_launch(sn_handle* h, hipStream_t st, int n, const int8_t* in, int8_t* out) {
-  MirrorArgs a{in, out, n, h->H, h->W};
-  const bool vec = (h->W & 15) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-  const size_t items = (size_t)n * 6 * h->H * (vec ? h->W >> 4 : h->W);
-  const unsigned grid = (unsigned)std::min<size_t>((items + 255) / 256, 8192);
-  if (vec) hipLaunchKernelGGL(k_mirror_pair<true>, dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_mirror_pair<false>, dim3(grid), dim3(256), 0, st, a);
-  HIP_TRY(h, hipGetLastError());
-  return SN_OK;
-}
-
-// device pointers; right_out (nullable) receives the right map in right-image coordinates
-static int lrc_launch(sn_handle* h, hipStream_t st, int n, const int32_t* left, const int32_t* right, const sn_lrc_params* p,
-                      int32_t* out_raw, float* disp, uint8_t* mask, uint32_t* kept, int32_t* right_out) {
-  LrcArgs a{left, right, out_raw, disp, mask, kept, right_out, h->W, h->H, (float)((double)kOutScale * kWireFactor),
-            p->tau_px, p->tau_rel, p->right_mirrored != 0};
-  const bool vec = (h->W & 3) == 0 &&
-                   (((uintptr_t)left | (uintptr_t)right | (uintptr_t)out_raw | (uintptr_t)right_out) & 15) == 0 &&
-                   ((uintptr_t)mask & 3) == 0;
-  if (kept) HIP_TRY(h, hipMemsetAsync(kept, 0, (size_t)n * 4, st));
-  const int nseg = h->H * ((h->W + 255) / 256);
-  const int per_map = std::max(1, std::min((nseg + 3) / 4, 4096 / n));
-  if (vec) hipLaunchKernelGGL(k_lr_check<true>, dim3(per_map, n), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_lr_check<false>, dim3(per_map, n), dim3(256), 0, st, a);
-  HIP_TRY(h, hipGetLastError());
-  return SN_OK;
-}
-
-int sn_mirror_pair_i8(sn_handle* h, int n, const int8_t* in, int8_t* out, int mem, void* stream) {
-  if (!h) return SN_ERR_ARG;
-  const size_t bytes = (size_t)(n > 0 ? n : 0) * 6 * h->H * h->W;
-  if (!in || !out || n <= 0 || n > h->max_batch || (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) ||
-      ((uintptr_t)in < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)in + bytes)) {
-    set_err(h, "sn_mirror_pair_i8: bad arguments");
-    return SN_ERR_ARG;
-  }
-  int rc = check_device(h);
-  if (rc) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  const int8_t* din = in;
-  int8_t* dout = out;
-  if (mem == SN_MEM_HOST) {
-    int8_t* stage;
-    LRC_BUF(h, stage, int8_t*, kIn, bytes);
-    LRC_BUF(h, dout, int8_t*, kMirror, bytes);
-    HIP_TRY(h, hipMemcpyAsync(stage, in, bytes, hipMemcpyHostToDevice, st));
-    din = stage;
-  }
-  if ((rc = mirror_launch(h, st, n, din, dout))) return rc;
-  if (mem == SN_MEM_HOST) HIP_TRY(h, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
-  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
-}
-
-int sn_lr_check(sn_handle* h, int n, const int32_t* raw_left, const int32_t* raw_right, const sn_lrc_params* p,
-                int32_t* out_raw, float* disp_inout, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
-  if (!h) return SN_ERR_ARG;
-  if (!raw_left || !raw_right || !lrc_params_ok(p) || (!out_raw && !mask) || n <= 0 || n > h->max_batch ||
-      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) {
-    set_err(h, "sn_lr_check: bad arguments");
-    return SN_ERR_ARG;
-  }
-  int rc = check_device(h);
-  if (rc) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  const size_t cnt = (size_t)n * h->H * h->W;
-  const int32_t *dl = raw_left, *dr = raw_right;
-  int32_t* dout = out_raw;
-  float* ddisp = disp_inout;
-  uint8_t* dmask = mask;
-  uint32_t* dkept = kept;
-  if (mem == SN_MEM_HOST) {
-    int32_t *l, *r;
-    LRC_BUF(h, l, int32_t*, kLeft, cnt * 4);
-    LRC_BUF(h, r, int32_t*, kRight, cnt * 4);
-    HIP_TRY(h, hipMemcpyAsync(l, raw_left, cnt * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(r, raw_right, cnt * 4, hipMemcpyHostToDevice, st));
-    dl = l;
-    dr = r;
-    dout = out_raw ? l : nullptr;            // masked in place
-    if (disp_inout) {
-      LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
-      HIP_TRY(h, hipMemcpyAsync(ddisp, disp_inout, cnt * 4, hipMemcpyHostToDevice, st));
-    }
-    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
-    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
-  }
-  if ((rc = lrc_launch(h, st, n, dl, dr, p, dout, ddisp, dmask, dkept, nullptr))) return rc;
-  if (mem == SN_MEM_HOST) {
-    if (out_raw) HIP_TRY(h, hipMemcpyAsync(out_raw, dout, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (disp_inout) HIP_TRY(h, hipMemcpyAsync(disp_inout, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
-    if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  }
-  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
-}
-
-// L = forward(in), M = forward(mirror(in)), then the check of L against M in its mirrored storage: two run_forward calls, so
-// each is counted, folded into the refinement statistic and (SN_PREC_AUTO, blocking) repeated by the usual rule.
-int sn_infer_lrc(sn_handle* h, int n, const void* in, int in_kind, int w2, int h_px, const sn_lrc_params* p, int32_t* out_i32,
-                 float* out_disp, int32_t* out_right_i32, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
-  if (!h) return SN_ERR_ARG;
-  if (!in || !lrc_params_ok(p) || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch ||
-      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) || (in_kind != SN_LRC_IN_TENSOR && in_kind != SN_LRC_IN_SBS_NV12)) {
-    set_err(h, "sn_infer_lrc: bad arguments");
-    return SN_ERR_ARG;
-  }
-  if (in_kind == SN_LRC_IN_SBS_NV12 && (!pre_args_ok(h, w2 / 2, h_px) || (w2 & 7) || (h_px & 1) ||
-                                        (mem == SN_MEM_DEVICE && ((uintptr_t)in & 3)))) {
-    set_err(h, "sn_infer_lrc: image size does not match the model input");
-    return SN_ERR_ARG;
-  }
-  int rc = check_device(h);
-  if (rc) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  const bool host = mem == SN_MEM_HOST, blocking = host || !stream;
-  const size_t HW = (size_t)h->H * h->W, cnt = (size_t)n * HW;
-  const int8_t* din = static_cast<const int8_t*>(in);
-  int8_t* dmir;
-  int32_t *dleft = out_i32, *dsecond, *dright = out_right_i32;
-  float* ddisp = out_disp;
-  uint8_t* dmask = mask;
-  uint32_t* dkept = kept;
-  LRC_BUF(h, dmir, int8_t*, kMirror, cnt * 6);
-  LRC_BUF(h, dsecond, int32_t*, kRight, cnt * 4);
-  if (host || !out_i32) LRC_BUF(h, dleft, int32_t*, kLeft, cnt * 4);
-  if (host) {
-    if (out_disp) LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
-    if (out_right_i32) LRC_BUF(h, dright, int32_t*, kRightOut, cnt * 4);
-    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
-    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
-  }
-  if (in_kind == SN_LRC_IN_SBS_NV12) {
-    int8_t* ten;
-    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
-    const int w = w2 / 2;
-    const long total = 6L * h_px * (w >> 2);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    for (int i = 0; i < n; ++i) {
-      const uint8_t* src = static_cast<const uint8_t*>(in) + (size_t)i * 3 * HW;
-      if (host) {                         // one frame at a time through the NV12 staging buffer
-        HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, src, 3 * HW, hipMemcpyHostToDevice, st));
-        src = h->ws.nv12;
-      }
-      hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, src, src + w, w2, w, h_px, ten + (size_t)i * 6 * HW);
-    }
-    HIP_TRY(h, hipGetLastError());
-    din = ten;
-  } else if (host) {
-    int8_t* ten;
-    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
-    HIP_TRY(h, hipMemcpyAsync(ten, in, cnt * 6, hipMemcpyHostToDevice, st));
-    din = ten;
-  }
-  auto nothing = []() -> int { return SN_OK; };
-  if ((rc = run_forward(h, st, n, din, ddisp, dleft, n == 1, blocking, nothing))) return rc;
-  if ((rc = mirror_launch(h, st, n, din, dmir))) return rc;
-  if ((rc = run_forward(h, st, n, dmir, nullptr, dsecond, false, blocking, nothing))) return rc;
-  sn_lrc_params q = *p;
-  q.right_mirrored = 1;
-  if ((rc = lrc_launch(h, st, n, dleft, dsecond, &q, dleft, ddisp, dmask, dkept, dright))) return rc;
-  if (host) {
-    if (out_i32) HIP_TRY(h, hipMemcpyAsync(out_i32, dleft, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (out_disp) HIP_TRY(h, hipMemcpyAsync(out_disp, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (out_right_i32) HIP_TRY(h, hipMemcpyAsync(out_right_i32, dright, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
-    if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  }
-  if (blocking) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
-}
-
-// ---- confidence of the soft-argmin distribution and the mask on it (csrc/sn_confidence.hpp) ------------------------------------
-static bool conf_params_ok(const sn_conf_params* p) {
-  return p && std::isfinite(p->min_conf) && p->min_conf >= 0.f && p->min_conf <= 1.f;
-}
-
-// device pointers.  low: conf_in is a low-resolution plane [n][hl][wl] (upsampled, out_conf nullable); else a full-resolution
-// map.  p == nullptr: no masking (out_conf only)
-static int conf_launch(sn_handle* h, hipStream_t st, int n, bool low, const float* conf_in, const int32_t* raw,
-                       const sn_conf_params* p, float* out_conf, int32_t* out_raw, float* disp, uint8_t* mask, uint32_t* kept) {
-  if (!p && !(low && out_conf)) return SN_OK;      // nothing to write
-  ConfArgs a{conf_in, raw, out_conf, out_raw, disp, mask, kept, h->hl, h->wl, h->H, h->W, p ? p->min_conf : 0.f, p != nullptr};
-  if (p && kept) HIP_TRY(h, hipMemsetAsync(kept, 0, (size_t)n * 4, st));
-  const int blocks = (int)(((size_t)h->H * h->W + 255) / 256);      // about 1024 workgroups per call: see k_conf_apply
-  const dim3 grid((unsigned)std::max(1, std::min(blocks, 1024 / n)), (unsigned)n);
-  if (low) hipLaunchKernelGGL(k_conf_apply<true>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_conf_apply<false>, grid, dim3(256), 0, st, a);
-  HIP_TRY(h, hipGetLastError());
-  return SN_OK;
-}
-
-// One forward pass whose soft-argmin epilogue also writes the confidence plane; the upsample + mask kernel is run_forward's
-// `post`, so a call that SN_PREC_AUTO repeats in SN_PREC_F16X3 masks the repeated maps.
-int sn_infer_conf(sn_handle* h, int n, const void* in, int in_kind, int w2, int h_px, const sn_conf_params* p, int32_t* out_i32,
-                  float* out_disp, float* out_conf, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
-  if (!h) return SN_ERR_ARG;
-  if (!in || (p && !conf_params_ok(p)) || (!p && (mask || kept)) || (!out_i32 && !out_disp) || n <= 0 || n > h->max_batch ||
-      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) || (in_kind != SN_LRC_IN_TENSOR && in_kind != SN_LRC_IN_SBS_NV12)) {
-    set_err(h, "sn_infer_conf: bad arguments");
-    return SN_ERR_ARG;
-  }
-  if (in_kind == SN_LRC_IN_SBS_NV12 && (!pre_args_ok(h, w2 / 2, h_px) || (w2 & 7) || (h_px & 1) ||
-                                        (mem == SN_MEM_DEVICE && ((uintptr_t)in & 3)))) {
-    set_err(h, "sn_infer_conf: image size does not match the model input");
-    return SN_ERR_ARG;
-  }
-  int rc = check_device(h);
-  if (rc) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  const bool host = mem == SN_MEM_HOST, blocking = host || !stream;
-  const size_t HW = (size_t)h->H * h->W, cnt = (size_t)n * HW;
-  const int8_t* din = static_cast<const int8_t*>(in);
-  int32_t* draw = out_i32;
-  float *ddisp = out_disp, *dconf = out_conf;
-  uint8_t* dmask = mask;
-  uint32_t* dkept = kept;
-  if ((host && out_i32) || (p && !out_i32)) LRC_BUF(h, draw, int32_t*, kLeft, cnt * 4);      // the mask rules read the map
-  if (host) {
-    if (out_disp) LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
-    if (out_conf) LRC_BUF(h, dconf, float*, kConf, cnt * 4);
-    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
-    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
-  }
-  if (in_kind == SN_LRC_IN_SBS_NV12) {
-    int8_t* ten;
-    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
-    const int w = w2 / 2;
-    const long total = 6L * h_px * (w >> 2);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    for (int i = 0; i < n; ++i) {
-      const uint8_t* src = static_cast<const uint8_t*>(in) + (size_t)i * 3 * HW;
-      if (host) {                         // one frame at a time through the NV12 staging buffer
-        HIP_TRY(h, hipMemcpyAsync(h->ws.nv12, src, 3 * HW, hipMemcpyHostToDevice, st));
-        src = h->ws.nv12;
-      }
-      hipLaunchKernelGGL(k_pre_nv12, dim3(blocks), dim3(256), 0, st, src, src + w, w2, w, h_px, ten + (size_t)i * 6 * HW);
-    }
-    HIP_TRY(h, hipGetLastError());
-    din = ten;
-  } else if (host) {
-    int8_t* ten;
-    LRC_BUF(h, ten, int8_t*, kIn, cnt * 6);
-    HIP_TRY(h, hipMemcpyAsync(ten, in, cnt * 6, hipMemcpyHostToDevice, st));
-    din = ten;
-  }
-  auto post = [&]() -> int {
-    const int prc = conf_launch(h, st, n, true, h->ws.conf_low, draw, p, dconf, draw, ddisp, dmask, dkept);
-    if (prc) return prc;
-    if (host) {
-      if (out_i32) HIP_TRY(h, hipMemcpyAsync(out_i32, draw, cnt * 4, hipMemcpyDeviceToHost, st));
-      if (out_disp) HIP_TRY(h, hipMemcpyAsync(out_disp, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
-      if (out_conf) HIP_TRY(h, hipMemcpyAsync(out_conf, dconf, cnt * 4, hipMemcpyDeviceToHost, st));
-      if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
-      if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    }
-    return SN_OK;
-  };
-  return run_forward(h, st, n, din, ddisp, draw, n == 1, blocking, post, true);
-}
-
-int sn_conf_mask(sn_handle* h, int n, const int32_t* raw, const float* conf, const sn_conf_params* p, int32_t* out_raw,
-                 float* disp_inout, uint8_t* mask, uint32_t* kept, int mem, void* stream) {
-  if (!h) return SN_ERR_ARG;
-  if (!raw || !conf || !conf_params_ok(p) || (!out_raw && !mask) || n <= 0 || n > h->max_batch ||
-      (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE)) {
-    set_err(h, "sn_conf_mask: bad arguments");
-    return SN_ERR_ARG;
-  }
-  const size_t cnt = (size_t)n * h->H * h->W;
-  {      // conf is read by every pixel's thread: it must not be one of the outputs
-    const uintptr_t lo[4] = {(uintptr_t)out_raw, (uintptr_t)disp_inout, (uintptr_t)mask, (uintptr_t)kept};
-    const size_t len[4] = {cnt * 4, cnt * 4, cnt, (size_t)n * 4};
-    const uintptr_t c = (uintptr_t)conf;
-    for (int i = 0; i < 4; ++i)
-      if (lo[i] && lo[i] < c + cnt * 4 && c < lo[i] + len[i]) {
-        set_err(h, "sn_conf_mask: conf overlaps an output");
-        return SN_ERR_ARG;
-      }
-  }
-  int rc = check_device(h);
-  if (rc) return rc;
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  const int32_t* draw = raw;
-  const float* dconf = conf;
-  int32_t* dout = out_raw;
-  float* ddisp = disp_inout;
-  uint8_t* dmask = mask;
-  uint32_t* dkept = kept;
-  if (mem == SN_MEM_HOST) {
-    int32_t* r;
-    float* c;
-    LRC_BUF(h, r, int32_t*, kLeft, cnt * 4);
-    LRC_BUF(h, c, float*, kConf, cnt * 4);
-    HIP_TRY(h, hipMemcpyAsync(r, raw, cnt * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(c, conf, cnt * 4, hipMemcpyHostToDevice, st));
-    draw = r;
-    dconf = c;
-    dout = out_raw ? r : nullptr;            // masked in place
-    if (disp_inout) {
-      LRC_BUF(h, ddisp, float*, kDisp, cnt * 4);
-      HIP_TRY(h, hipMemcpyAsync(ddisp, disp_inout, cnt * 4, hipMemcpyHostToDevice, st));
-    }
-    if (mask) LRC_BUF(h, dmask, uint8_t*, kMask, cnt);
-    if (kept) LRC_BUF(h, dkept, uint32_t*, kKept, (size_t)n * 4);
-  }
-  if ((rc = conf_launch(h, st, n, false, dconf, draw, p, nullptr, dout, ddisp, dmask, dkept))) return rc;
-  if (mem == SN_MEM_HOST) {
-    if (out_raw) HIP_TRY(h, hipMemcpyAsync(out_raw, dout, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (disp_inout) HIP_TRY(h, hipMemcpyAsync(disp_inout, ddisp, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, dmask, cnt, hipMemcpyDeviceToHost, st));
-    if (kept) HIP_TRY(h, hipMemcpyAsync(kept, dkept, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  }
-  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
-}
-
-// ---- speckle removal and hole filling (csrc/sn_dispfilter.hpp) ---------------------------------------------------------------
-int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_params* p, int32_t* out_raw, float* disp_inout,
-                  uint8_t* mask, uint32_t* counts, int mem, void* stream) {
-  if (!h) return SN_ERR_ARG;
-  const size_t HW = (size_t)h->H * h->W;
-  if (!raw || !p || (!out_raw && !mask) || n <= 0 || n > h->max_batch || (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) ||
-      p->speckle_max_px < 0 || (size_t)p->speckle_max_px > HW || !std::isfinite(p->speckle_diff_px) ||
-      p->speckle_diff_px < 0.f || p->fill_max_px < 0 || (p->speckle_max_px == 0 && p->fill_max_px == 0) || HW > 0x7fffffffu) {
-    set_err(h, "sn_filter_raw: bad arguments");
-    return SN_ERR_ARG;
-  }
-  const size_t cnt = (size_t)n * HW;
-  {      // out_raw == raw is the one overlap the kernels are written for
-    const uintptr_t lo[5] = {(uintptr_t)raw, (uintptr_t)out_raw, (uintptr_t)disp_inout, (uintptr_t)mask, (uintptr_t)counts};
-    const size_t len[5] = {cnt * 4, cnt * 4, cnt * 4, cnt, (size_t)n * 12};
-    for (int i = 0; i < 5; ++i)
-      for (int j = i + 1; j < 5; ++j)
-        if (lo[i] && lo[j] && !(i == 0 && j == 1 && lo[0] == lo[1]) && lo[i] < lo[j] + len[j] && lo[j] < lo[i] + len[i]) {
-          set_err(h, "sn_filter_raw: overlapping buffers (only out_raw == raw is allowed)");
-          return SN_ERR_ARG;
-        }
-  }
-  int rc = check_device(h);
-  if (rc) return rc;
-  auto& f = h->flt;
-  std::lock_guard<std::mutex> lk(f.mu);
-  if (!f.stream) HIP_TRY(h, hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
-  if (!f.ev) HIP_TRY(h, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
-  const int slice = std::min(h->max_batch, kFltSlice);
-  if (p->speckle_max_px && !f.scratch && hipMalloc(reinterpret_cast<void**>(&f.scratch), (size_t)slice * HW * 8) != hipSuccess) {
-    f.scratch = nullptr;
-    set_err(h, "sn_filter_raw: out of device memory");
-    return SN_ERR_NOMEM;
-  }
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : f.stream;
-  HIP_TRY(h, hipStreamWaitEvent(st, f.ev, 0));      // the previous call (any stream) is done with the scratch and the staging
-  const float S = (float)((double)kOutScale * kWireFactor);
-  const float q = floorf(p->speckle_diff_px / S);
-  FltArgs a{raw, out_raw, disp_inout, mask, counts, f.scratch, f.scratch ? f.scratch + (size_t)slice * HW : nullptr, h->W, h->H,
-            (h->W + kFltTW - 1) / kFltTW, (h->H + kFltTH - 1) / kFltTH, q >= 4294967296.f ? 4294967296ll : (long long)q,
-            (uint32_t)p->speckle_max_px, p->fill_max_px, S};
-  if (mem == SN_MEM_HOST) {
-    using F = sn_handle::Filter;
-    HIP_TRY(h, pc_grow(&f.dev[F::kRaw], &f.dev_bytes[F::kRaw], cnt * 4, false));
-    HIP_TRY(h, hipMemcpyAsync(f.dev[F::kRaw], raw, cnt * 4, hipMemcpyHostToDevice, st));
-    a.raw = static_cast<const int32_t*>(f.dev[F::kRaw]);
-    a.out_raw = out_raw ? static_cast<int32_t*>(f.dev[F::kRaw]) : nullptr;      // filtered in place
-    if (disp_inout) {
-      HIP_TRY(h, pc_grow(&f.dev[F::kDisp], &f.dev_bytes[F::kDisp], cnt * 4, false));
-      HIP_TRY(h, hipMemcpyAsync(f.dev[F::kDisp], disp_inout, cnt * 4, hipMemcpyHostToDevice, st));
-      a.disp = static_cast<float*>(f.dev[F::kDisp]);
-    }
-    if (mask) {
-      HIP_TRY(h, pc_grow(&f.dev[F::kMask], &f.dev_bytes[F::kMask], cnt, false));
-      a.mask = static_cast<uint8_t*>(f.dev[F::kMask]);
-    }
-    if (counts) {
-      HIP_TRY(h, pc_grow(&f.dev[F::kCounts], &f.dev_bytes[F::kCounts], (size_t)n * 12, false));
-      a.counts = static_cast<uint32_t*>(f.dev[F::kCounts]);
-    }
-  }
-  const FltArgs all = a;
-  if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 12, st));
-  const bool vec = (h->W & 3) == 0 && ((uintptr_t)a.mask & 3) == 0;
-  const int pairs = (a.tiles_x - 1) * h->H + (a.tiles_y - 1) * h->W;
-  for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` maps: walk the batch on the stream
-    const int m = std::min(slice, n - k0);
-    const size_t off = (size_t)k0 * HW;
-    a.raw = all.raw + off;
-    a.out_raw = all.out_raw ? all.out_raw + off : nullptr;
-    a.disp = all.disp ? all.disp + off : nullptr;
-    a.mask = all.mask ? all.mask + off : nullptr;
-    a.counts = all.counts ? all.counts + (size_t)k0 * 3 : nullptr;
-    if (a.max_px) {
-      hipLaunchKernelGGL(k_flt_label, dim3(a.tiles_x * a.tiles_y, m), dim3(256), 0, st, a);
-      if (pairs) hipLaunchKernelGGL(k_flt_seam, dim3((pairs + 255) / 256, m), dim3(256), 0, st, a);
-      hipLaunchKernelGGL(k_flt_flatten, dim3((unsigned)((HW + 255) / 256), m), dim3(256), 0, st, a);
-    }
-    const int per_map = std::max(1, std::min((h->H + 3) / 4, 4096 / m));
-    if (vec) hipLaunchKernelGGL(k_flt_apply<true>, dim3(per_map, m), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_flt_apply<false>, dim3(per_map, m), dim3(256), 0, st, a);
-  }
-  HIP_TRY(h, hipGetLastError());
-  if (mem == SN_MEM_HOST) {
-    if (out_raw) HIP_TRY(h, hipMemcpyAsync(out_raw, all.out_raw, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (disp_inout) HIP_TRY(h, hipMemcpyAsync(disp_inout, all.disp, cnt * 4, hipMemcpyDeviceToHost, st));
-    if (mask) HIP_TRY(h, hipMemcpyAsync(mask, all.mask, cnt, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, all.counts, (size_t)n * 12, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(h, hipEventRecord(f.ev, st));
-  if (mem == SN_MEM_HOST || !stream) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }
 
