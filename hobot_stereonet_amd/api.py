@@ -74,7 +74,14 @@ class SnConfParams(C.Structure):
     _fields_ = [("min_conf", C.c_float)]
 
 
+class SnSmoothParams(C.Structure):
+    """sn_smooth_params (include/stereonet_hip.h): guided weighted-median smoothing of the int32 map."""
+    _fields_ = [("radius", C.c_int), ("sigma_luma", C.c_int), ("min_valid", C.c_int)]
+
+
 SN_FLT_INVALID_IN, SN_FLT_SPECKLE, SN_FLT_FILLED = 1, 16, 32
+SN_SMOOTH_INVALID_IN, SN_SMOOTH_CHANGED = 1, 128
+SN_GUIDE_NV12, SN_GUIDE_TENSOR = 0, 1
 SN_CONF_KEPT, SN_CONF_INVALID_IN, SN_CONF_LOW = 0, 1, 64
 SN_LRC_KEPT, SN_LRC_INVALID_IN, SN_LRC_OUT_OF_VIEW, SN_LRC_NO_PARTNER, SN_LRC_INCONSISTENT = 0, 1, 2, 4, 8
 SN_LRC_IN_TENSOR, SN_LRC_IN_SBS_NV12 = 0, 1
@@ -161,6 +168,7 @@ def load_library(path: Optional[str] = None):
     lib.sn_lr_check.argtypes = [vp, ip, i32p, i32p, C.POINTER(SnLrcParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_infer_lrc.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnLrcParams), i32p, fp, i32p, u8p, vp, ip, vp]
     lib.sn_filter_raw.argtypes = [vp, ip, i32p, C.POINTER(SnFilterParams), i32p, fp, u8p, vp, ip, vp]
+    lib.sn_smooth_raw.argtypes = [vp, ip, i32p, vp, ip, ip, C.POINTER(SnSmoothParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -174,7 +182,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -605,6 +613,48 @@ class StereoNetHIP:
         self._check(self._lib.sn_filter_raw(self._h, n, raw_ptr or None, C.byref(p), out_raw_ptr or None, disp_ptr or None,
                                             mask_ptr or None, counts_ptr or None, SN_MEM_DEVICE, stream or None),
                     "sn_filter_raw")
+
+    # -- guided weighted-median smoothing ------------------------------------------------------------------
+    def smooth_raw(self, raw: np.ndarray, guide: Optional[np.ndarray] = None, guide_kind: int = SN_GUIDE_NV12,
+                   guide_pitch: int = 0, radius: int = 2, sigma_luma: int = 12, min_valid: int = 0,
+                   disp: Optional[np.ndarray] = None):
+        """sn_smooth_raw on host buffers: int32 (H,W) or (n,H,W) -> (out int32, mask uint8, counts uint32 (n,3) = {valid,
+        smoothed measurements, filled pixels} per map).  guide: the left image's luma, either uint8 NV12 frames (guide_kind
+        SN_GUIDE_NV12; guide_pitch = the luma pitch, 0 = the width, 2 * width for side-by-side frames; the luma rows alone
+        are enough for one map) or the int8 model input ([n,] 6, H, W) (SN_GUIDE_TENSOR); None only with sigma_luma = 0.
+        `disp` (float32, the maps' shape) is rewritten IN PLACE where the mask has SN_SMOOTH_CHANGED.  smooth.reference is the
+        numpy twin."""
+        r = self._maps(raw, "smooth_raw")
+        dp = self._disp_ptr(disp, r.shape, "smooth_raw")
+        n, out, mask, counts = self._mask_outputs(r, 3)
+        g = None
+        w, h = self.width, self.height
+        if guide is not None:
+            if guide_kind == SN_GUIDE_TENSOR:
+                g = np.ascontiguousarray(guide, dtype=np.int8)
+                if g.shape not in ((6, h, w), (n, 6, h, w)) or g.size != n * 6 * h * w:
+                    raise StereoNetError(-1, "smooth_raw", f"guide shape {g.shape} != ([{n},] 6, {h}, {w})")
+            else:
+                g = np.ascontiguousarray(guide, dtype=np.uint8).reshape(-1)
+                guide_pitch = guide_pitch or w
+                need = (n - 1) * guide_pitch * (h + (h + 1) // 2) + guide_pitch * (h - 1) + w
+                if guide_pitch < w or g.size < need:      # the library cannot see how long a host buffer is
+                    raise StereoNetError(-1, "smooth_raw", f"guide of {g.size} bytes, {n} frames of pitch {guide_pitch} take {need}")
+        p = SnSmoothParams(int(radius), int(sigma_luma), int(min_valid))
+        self._check(self._lib.sn_smooth_raw(self._h, n, r.ctypes.data, _np_ptr(g), guide_kind, guide_pitch, C.byref(p),
+                                            out.ctypes.data, dp, mask.ctypes.data, counts.ctypes.data, SN_MEM_HOST, None),
+                    "sn_smooth_raw")
+        return out, mask, counts
+
+    def smooth_raw_device(self, n: int, raw_ptr: int, guide_ptr: int, guide_kind: int, guide_pitch: int, radius: int,
+                          sigma_luma: int, min_valid: int, out_raw_ptr: int = 0, mask_ptr: int = 0, disp_ptr: int = 0,
+                          counts_ptr: int = 0, stream: int = 0):
+        """sn_smooth_raw on device pointers (out_raw_ptr may equal raw_ptr); stream = hipStream_t as int (0: the smoother's own
+        stream, and the call returns after completion)."""
+        p = SnSmoothParams(int(radius), int(sigma_luma), int(min_valid))
+        self._check(self._lib.sn_smooth_raw(self._h, n, raw_ptr or None, guide_ptr or None, guide_kind, guide_pitch, C.byref(p),
+                                            out_raw_ptr or None, disp_ptr or None, mask_ptr or None, counts_ptr or None,
+                                            SN_MEM_DEVICE, stream or None), "sn_smooth_raw")
 
     def synchronize(self):
         self._check(self._lib.sn_synchronize(self._h), "sn_synchronize")

@@ -248,6 +248,15 @@ struct sn_handle {
     hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
     GrowBuf buf[kCount];
   } flt;
+  // sn_smooth_raw: everything of its own, as the filter has
+  struct Smooth {
+    // the copy of a slice that an in-place call reads; host mode: map, guide, result, float map, mask, counts
+    enum { kScratch = 0, kRaw, kGuide, kOut, kDisp, kMask, kCounts, kCount };
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
+    GrowBuf buf[kCount];
+  } smo;
 };
 
 namespace {

@@ -1,7 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the pair-input staging, the per-call host staging and the overlap predicate — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence and filter.  The kernels are in sn_pointcloud.hpp,
-// sn_lrcheck.hpp, sn_confidence.hpp and sn_dispfilter.hpp.  Part of the single translation unit stereonet_hip.hip.
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter and smoother.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp and sn_smooth.hpp.  Part of the single translation
+// unit stereonet_hip.hip.
 #pragma once
 
 namespace {
@@ -551,6 +552,92 @@ int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_param
     const int per_map = std::max(1, std::min((h->H + 3) / 4, 4096 / m));
     if (vec) hipLaunchKernelGGL(k_flt_apply<true>, dim3(per_map, m), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_flt_apply<false>, dim3(per_map, m), dim3(256), 0, st, a);
+  }
+  HIP_TRY(h, hipGetLastError());
+  if (int e = s.download()) return e;
+  HIP_TRY(h, hipEventRecord(f.ev, st));
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// ---- guided weighted-median smoothing (csrc/sn_smooth.hpp): its own stream and mutex ------------------------------------------
+int sn_smooth_raw(sn_handle* h, int n, const int32_t* raw, const void* guide, int guide_kind, int guide_pitch,
+                  const sn_smooth_params* p, int32_t* out_raw, float* disp_inout, uint8_t* mask, uint32_t* counts, int mem,
+                  void* stream) {
+  if (!h) return SN_ERR_ARG;
+  const size_t HW = (size_t)h->H * h->W;
+  const bool nv12 = guide_kind == SN_GUIDE_NV12;
+  if (!raw || !p || (!out_raw && !mask) || n <= 0 || n > h->max_batch || p->radius < 1 || p->radius > 3 || p->sigma_luma < 0 ||
+      p->sigma_luma > 255 || (p->sigma_luma > 0 && !guide) || (!nv12 && guide_kind != SN_GUIDE_TENSOR) ||
+      (nv12 && guide && (guide_pitch < h->W || (guide_pitch & 1))) || p->min_valid < 0 ||
+      p->min_valid > (2 * p->radius + 1) * (2 * p->radius + 1)) {
+    set_err(h, "sn_smooth_raw: bad arguments");
+    return SN_ERR_ARG;
+  }
+  const size_t cnt = (size_t)n * HW;
+  const bool weighted = p->sigma_luma > 0;      // sigma_luma == 0: the guide is ignored altogether
+  // frame k of the guide starts at k * frame; the call reads its luma rows alone, so the last frame ends with the last of them
+  const size_t frame = nv12 ? (size_t)guide_pitch * (h->H + (h->H + 1) / 2) : 6 * HW;
+  const size_t guide_bytes = !weighted ? 0 : (n - 1) * frame + (nv12 ? (size_t)guide_pitch * (h->H - 1) + h->W : HW);
+  {      // out_raw == raw is the one overlap the call is written for
+    const Span r{raw, cnt * 4}, o{out_raw, cnt * 4}, d{disp_inout, cnt * 4}, m{mask, cnt}, k{counts, (size_t)n * 12};
+    const Span g{weighted ? guide : nullptr, guide_bytes};
+    if ((out_raw != raw && overlap({r}, {o})) || overlap({r, o}, {d, m, k}) || overlap({d}, {m, k}) || overlap({m}, {k}) ||
+        overlap({g}, {o, d, m, k})) {
+      set_err(h, "sn_smooth_raw: overlapping buffers (only out_raw == raw is allowed)");
+      return SN_ERR_ARG;
+    }
+  }
+  using M = sn_handle::Smooth;
+  auto& f = h->smo;
+  std::lock_guard<std::mutex> lk(f.mu);
+  Call c;
+  const int rc = enter(h, "sn_smooth_raw", mem, stream, &f.stream, &c);
+  if (rc) return rc;
+  if (!f.ev) HIP_TRY(h, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+  hipStream_t st = c.st;
+  Staging s{h, "sn_smooth_raw", st, c.host, f.buf};
+  const int slice = std::min(h->max_batch, kSmSlice);
+  const bool in_place = !c.host && out_raw == raw;      // the kernel reads its neighbours' pixels: it works on a copy
+  int32_t* scratch = in_place ? s.scratch<int32_t>(M::kScratch, (size_t)slice * HW * 4) : nullptr;
+  if (s.rc) return s.rc;
+  HIP_TRY(h, hipStreamWaitEvent(st, f.ev, 0));      // the previous call (any stream) is done with the scratch and the staging
+  const int32_t* draw = s.in(M::kRaw, raw, cnt * 4);
+  const uint8_t* dguide = weighted ? s.in(M::kGuide, static_cast<const uint8_t*>(guide), guide_bytes) : nullptr;
+  int32_t* dout = s.out(M::kOut, out_raw, cnt * 4);
+  float* ddisp = s.inout(M::kDisp, disp_inout, cnt * 4);
+  uint8_t* dmask = s.out(M::kMask, mask, cnt);
+  uint32_t* dcounts = s.out(M::kCounts, counts, (size_t)n * 12);
+  if (s.rc) return s.rc;
+  SmArgs a{draw, dguide, dout, ddisp, dmask, dcounts, frame, nv12 ? guide_pitch : h->W, nv12 ? 0u : 0x80u, h->W, h->H,
+           (h->W + kSmTW - 1) / kSmTW, p->min_valid, (float)((double)kOutScale * kWireFactor), {}};
+  const long long ss = (long long)p->sigma_luma * p->sigma_luma;
+  for (int j = 0; j < 256; ++j) a.table[j] = (uint16_t)(weighted ? (256 * ss) / (ss + (long long)j * j) : 1);
+  const SmArgs all = a;
+  if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 12, st));
+  const int tiles = a.tiles_x * ((h->H + kSmTH - 1) / kSmTH);
+  for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` maps: walk the batch on the stream
+    const int m = std::min(slice, n - k0);
+    const size_t off = (size_t)k0 * HW;
+    a.raw = all.raw + off;
+    if (in_place) {
+      HIP_TRY(h, hipMemcpyAsync(scratch, a.raw, (size_t)m * HW * 4, hipMemcpyDeviceToDevice, st));
+      a.raw = scratch;
+    }
+    a.luma = all.luma ? all.luma + (size_t)k0 * frame : nullptr;
+    a.out_raw = all.out_raw ? all.out_raw + off : nullptr;
+    a.disp = all.disp ? all.disp + off : nullptr;
+    a.mask = all.mask ? all.mask + off : nullptr;
+    a.counts = all.counts ? all.counts + (size_t)k0 * 3 : nullptr;
+    const dim3 grid(tiles, m), block(256);
+    switch (p->radius * 2 + (weighted ? 1 : 0)) {
+      case 2: hipLaunchKernelGGL((k_smooth<1, false>), grid, block, 0, st, a); break;
+      case 3: hipLaunchKernelGGL((k_smooth<1, true>), grid, block, 0, st, a); break;
+      case 4: hipLaunchKernelGGL((k_smooth<2, false>), grid, block, 0, st, a); break;
+      case 5: hipLaunchKernelGGL((k_smooth<2, true>), grid, block, 0, st, a); break;
+      case 6: hipLaunchKernelGGL((k_smooth<3, false>), grid, block, 0, st, a); break;
+      default: hipLaunchKernelGGL((k_smooth<3, true>), grid, block, 0, st, a); break;
+    }
   }
   HIP_TRY(h, hipGetLastError());
   if (int e = s.download()) return e;

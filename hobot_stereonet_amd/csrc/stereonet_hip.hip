@@ -1,7 +1,7 @@
 // stereonet_hip.hip — the one translation unit of the engine of libstereonet_hip.so: the headers below, one concern each and
 // included in order, then the engine's own part of the public C ABI (include/stereonet_hip.h): create / destroy, io info,
 // SN_PREC_AUTO's state machine, infer, preprocess, submit / wait and the measurement hooks.  The entry points that follow the
-// network — depth, point cloud, mirror, left-right check, confidence, filter — and the host helpers they share with the ones
+// network — depth, point cloud, mirror, left-right check, confidence, filter, smoother — and the host helpers they share with the ones
 // here (entry preamble, NV12 launcher) are in sn_postproc.hpp.  DESIGN.md §6 has the source map.
 //
 // Replaces, for the StereoNet hot path, what the reference obtains from the closed dnn_node /
@@ -27,16 +27,17 @@
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
 #include "sn_switches.hpp"      // the SN_* environment switches
-#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp)
+#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp, sn_smooth.hpp)
 #include "sn_pointcloud.hpp"
 #include "sn_lrcheck.hpp"
 #include "sn_dispfilter.hpp"
 #include "sn_confidence.hpp"
+#include "sn_smooth.hpp"
 #include "sn_engine.hpp"        // handle, workspace and layer types, error and allocation helpers
 #include "sn_weights.hpp"       // .snw reader, weight packing and upload
 #include "sn_launch.hpp"        // kernel launchers and tensor geometry
 #include "sn_forward.hpp"       // workspace allocation, forward pass, refinement statistic, SN_PREC_AUTO
-#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter
+#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter, smoother
 #include "sn_dbg_hooks.hpp"     // sn_dbg_* parity hooks
 
 // =====================================================================================================
@@ -384,10 +385,13 @@ int sn_destroy(sn_handle* h) {
   for (GrowBuf& b : h->pc.buf) b.release();
   for (GrowBuf& b : h->stage.buf) b.release();
   for (GrowBuf& b : h->flt.buf) b.release();
+  for (GrowBuf& b : h->smo.buf) b.release();
   if (h->pc.ev) hipEventDestroy(h->pc.ev);
   if (h->pc.stream) hipStreamDestroy(h->pc.stream);
   if (h->flt.ev) hipEventDestroy(h->flt.ev);
   if (h->flt.stream) hipStreamDestroy(h->flt.stream);
+  if (h->smo.ev) hipEventDestroy(h->smo.ev);
+  if (h->smo.stream) hipStreamDestroy(h->smo.stream);
   hipFree(h->aout.w);
   hipFree(h->aout.pfrag);
   for (auto p : h->chk) hipFree(p);

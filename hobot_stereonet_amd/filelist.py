@@ -5,7 +5,7 @@ D1) needed to score the output against dataset ground truth.
     python -m hobot_stereonet_amd.filelist --model m.snw --left left.list --right right.list \
         [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
         [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
-        [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN]
+        [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -26,7 +26,15 @@ the metrics cover the measured pixels that survive; the filled ones are interpol
 confidence is below MIN get raw = 0, <i>.conf.pfm holds the confidence, <i>.mask.pgm the reason per pixel (confidence.LOW = 64),
 the metrics are taken over kept pixels and the summary gains "density".  With --lrc the public calls are composed with two
 forwards, not three: infer_conf unmasked, the mirrored pair through infer, lr_check, conf_mask on its result; the mask is the OR
-of the two.  --speckle / --fill run last, as without it.
+of the two.  --speckle / --fill run after them, as without it.
+
+--smooth runs the map last of all (after --lrc / --speckle / --fill / --conf) through `sn_smooth_raw`: every pixel takes the
+weighted median of its (2 RADIUS + 1)^2 window, weighted by the likeness of the left eye's luma (SIGMA, default 12; 0 = a plain
+median), and with MIN_VALID > 0 (default 0) a pixel without a measurement takes it too when that many window pixels hold one.
+The guide is the side-by-side NV12 frame the harness holds anyway.  The smoothed map feeds the metrics, --ply and --out;
+<i>.smooth.pgm holds the mask (smooth.BITS), every record gains "smoothed" (changed pixels) and "density", the summary their
+total and mean.  With ground truth the record gains "smooth_epe": the EPE over the pixels that held a measurement before the
+step, before and after it.
 """
 import argparse
 import json
@@ -101,7 +109,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
-                lrc=None, flt=None, conf: Optional[float] = None) -> List[dict]:
+                lrc=None, flt=None, conf: Optional[float] = None, smooth=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -113,7 +121,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     surviving measurements and "metrics_filled" the filled pixels.
     conf = min_conf: the maps are those of engine.infer_conf (pixels below the threshold at 0); the record gains "conf", "mask"
     and "density", <i>.conf.pfm and <i>.mask.pgm are written.  With lrc as well: infer_conf unmasked, infer on the mirrored pair,
-    lr_check, conf_mask — two forwards — and "mask" is the OR of the two masks."""
+    lr_check, conf_mask — two forwards — and "mask" is the OR of the two masks.
+    smooth = (radius, sigma_luma, min_valid): the maps then pass through engine.smooth_raw, guided by the frame's left eye; the
+    record gains "smooth_mask", "smoothed" (changed pixels) and "density" (pixels > 0 after the step), <i>.smooth.pgm is written,
+    and with ground truth "smooth_epe" = {"before", "after", "valid_px"} over the pixels that held a measurement before it."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -157,6 +168,11 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             raw, fmask, counts = engine.filter_raw(raw, flt[0], flt[1], flt[2], disp=disp)
             rec.update(raw=raw, filter_mask=fmask, removed=int(counts[0][1]), filled=int(counts[0][2]),
                        density=float(counts[0][0]) / float(w * h))
+        if smooth is not None:
+            raw_in, disp_in = raw, disp.copy()
+            raw, smask, counts = engine.smooth_raw(raw, sbs, 0, 2 * w, smooth[0], smooth[1], smooth[2], disp=disp)
+            rec.update(raw=raw, smooth_mask=smask, smoothed=int(counts[0][1]) + int(counts[0][2]),
+                       density=float(counts[0][0]) / float(w * h))
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -171,6 +187,11 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
                 rec["metrics_filled"] = score(disp, gt, filled if gt_valid is None else (gt_valid & filled), float(engine.dmax))
                 valid = (fmask == 0) if gt_valid is None else (gt_valid & (fmask == 0))
             rec["metrics"] = score(disp, gt, valid, float(engine.dmax))
+            if smooth is not None:
+                held = (raw_in > 0) & (gt < float(engine.dmax))
+                if gt_valid is not None:
+                    held &= gt_valid
+                rec["smooth_epe"] = {"before": epe(disp_in, gt, held), "after": epe(disp, gt, held), "valid_px": int(held.sum())}
         if out_dir:
             raw.tofile(os.path.join(out_dir, f"{i}.raw.bin"))
             images.write_pfm(os.path.join(out_dir, f"{i}.disp.pfm"), disp)
@@ -183,6 +204,8 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
                 images.write_pfm(os.path.join(out_dir, f"{i}.conf.pfm"), cf)
             if flt is not None:
                 images.write_ppm(os.path.join(out_dir, f"{i}.filter.pgm"), fmask)
+            if smooth is not None:
+                images.write_ppm(os.path.join(out_dir, f"{i}.smooth.pgm"), smask)
         results.append(rec)
     return results
 
@@ -209,6 +232,10 @@ def main(argv=None) -> int:
                     help="fill row gaps of at most MAX_PX pixels with the smaller bounding disparity (after --speckle)")
     ap.add_argument("--conf", default=None, metavar="MIN",
                     help="drop pixels whose soft-argmin confidence (0..1) is below MIN (no second forward)")
+    ap.add_argument("--smooth", default=None, metavar="RADIUS[,SIGMA[,MIN_VALID]]",
+                    help="guided weighted median over a (2 RADIUS + 1)^2 window, RADIUS 1..3; SIGMA 0..255 is the luma scale of "
+                         "the weights (default 12, 0 = plain median); MIN_VALID > 0 also fills pixels without a measurement "
+                         "whose window holds that many (default 0); runs after every other step")
     args = ap.parse_args(argv)
     from . import api, pointcloud
     cam = None
@@ -253,12 +280,22 @@ def main(argv=None) -> int:
             if fmax < 1 or fmax > 2 ** 31 - 1:
                 ap.error("--fill takes MAX_PX, an integer >= 1")
         flt = (smax, sdiff, fmax)
+    smooth = None
+    if args.smooth is not None:
+        try:
+            v = [int(t) for t in args.smooth.split(",")]
+        except ValueError:
+            v = []
+        v += [12, 0][len(v) - 1:] if 1 <= len(v) <= 3 else []
+        if len(v) != 3 or not (1 <= v[0] <= 3 and 0 <= v[1] <= 255 and 0 <= v[2] <= (2 * v[0] + 1) ** 2):
+            ap.error("--smooth takes RADIUS[,SIGMA[,MIN_VALID]]: integers, 1..3, 0..255 and 0..(2 RADIUS + 1)^2")
+        smooth = tuple(v)
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
-                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf)
+                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -271,7 +308,12 @@ def main(argv=None) -> int:
     if flt is not None and recs:
         summary["removed"] = int(sum(r["removed"] for r in recs))
         summary["filled"] = int(sum(r["filled"] for r in recs))
-    if (lrc is not None or flt is not None or conf is not None) and recs:
+    if smooth is not None and recs:
+        summary["smoothed"] = int(sum(r["smoothed"] for r in recs))
+        if args.gt:
+            summary["smooth_epe_before"] = float(np.nanmean([r["smooth_epe"]["before"] for r in recs]))
+            summary["smooth_epe_after"] = float(np.nanmean([r["smooth_epe"]["after"] for r in recs]))
+    if (lrc is not None or flt is not None or conf is not None or smooth is not None) and recs:
         summary["density"] = float(np.mean([r["density"] for r in recs]))
     print(json.dumps(summary))
     return 0

@@ -538,6 +538,59 @@ enum { SN_FLT_INVALID_IN = 1, SN_FLT_SPECKLE = 16, SN_FLT_FILLED = 32 };   /* bi
 int sn_filter_raw(sn_handle *h, int n, const int32_t *raw, const sn_filter_params *p, int32_t *out_raw,
                   float *disp_inout, uint8_t *mask, uint32_t *counts, int mem, void *stream);
 
+/* ---- guided weighted-median smoothing of the int32 map: the edge-preserving smoother after check, filter and confidence -------
+ * sn_filter_raw fills every row on its own, which leaves streaks behind a foreground edge; isolated outliers of the soft-argmin
+ * pass the left-right check and are too well connected to be speckles; the refinement's sub-pixel noise roughens every surface
+ * of the point cloud.  A median removes all three but rounds corners and thin structures; a median WEIGHTED by the similarity
+ * of the left image's luma does not.  sn_smooth_raw computes it on the GPU, in integers. */
+typedef struct sn_smooth_params {
+  int radius;      /* 1, 2 or 3: the window is (2*radius+1)^2, clipped to the image (no padding)            */
+  int sigma_luma;  /* 0: plain median, guide ignored (may be NULL); 1..255: weight falls with |luma diff|  */
+  int min_valid;   /* 0: a pixel without a measurement stays without one; 1..(2*radius+1)^2: it takes the  */
+                   /* window's weighted median when at least this many window pixels hold a measurement    */
+} sn_smooth_params;
+enum { SN_SMOOTH_INVALID_IN = 1, SN_SMOOTH_CHANGED = 128 };   /* 128: the last free bit beside SN_LRC_*, SN_FLT_*, SN_CONF_LOW */
+enum { SN_GUIDE_NV12 = 0, SN_GUIDE_TENSOR = 1 };
+/* sn_smooth_raw: n maps raw [n][H][W] of the model's size, each on its own.  All per-pixel arithmetic is integer.
+ *   Luma Y(k, v, u), 0..255, of map k's left image:
+ *     SN_GUIDE_NV12: the luma byte of frame k, guide + k*F + v*guide_pitch + u, with the layout, the frame stride
+ *       F = guide_pitch*(H + ceil(H/2)) and guide_pitch exactly as sn_pointcloud_from_raw's nv12 / nv12_pitch (W for a plain
+ *       left image, 2W for FeedImg's side-by-side frame).  Only the luma rows are read.
+ *     SN_GUIDE_TENSOR: guide is the int8 model input [n][6][H][W] and Y = (uint8_t)guide[k][0][v][u] ^ 0x80; guide_pitch is
+ *       ignored.
+ *   Weight table, computed once on the host: T[j] = 1 for every j when sigma_luma == 0 (the guide is not read); otherwise, with
+ *     s = sigma_luma, T[j] = (256*s*s) / (s*s + j*j) in integer division for j = 0..255 — a Lorentzian, T[0] = 256, and it may
+ *     reach 0.
+ *   Per pixel p = (v, u): the PARTICIPANTS are the pixels q of the window around p that lie inside the image, have raw[q] > 0
+ *     and a weight w_q = T[|Y(q) - Y(p)|] > 0.  Wt = the sum of w_q over the participants.  The weighted median is
+ *       m = min{ raw[q] : 2 * (sum of w_q' over the participants q' with raw[q'] <= raw[q]) >= Wt }
+ *     — the LOWER weighted median: it depends on no traversal or tie order and is always the value of a participant.
+ *   Result:  raw[p] > 0: m (the centre takes part with weight T[0] > 0, so m exists).
+ *            raw[p] <= 0: m if min_valid > 0, at least min_valid pixels of the window have raw > 0 (counted regardless of
+ *            their weight) and Wt > 0; otherwise 0.
+ *   mask (nullable) [n][H][W] = SN_SMOOTH_INVALID_IN where raw <= 0, OR SN_SMOOTH_CHANGED where the result differs from
+ *     max(raw, 0): one of 0, 1, 128, 129; the result is > 0 exactly where mask is 0, 128 or 129.  128 is disjoint from the
+ *     SN_LRC_* bits (1, 2, 4, 8), the SN_FLT_* bits (16, 32) and SN_CONF_LOW (64): masks can be OR-ed.
+ *   out_raw (nullable) = the result; out_raw == raw is allowed (the call then reads a copy of the map in its scratch, never
+ *     what it has already overwritten), any other overlap between the buffers is SN_ERR_ARG, and the guide must not overlap an
+ *     output.
+ *   disp_inout (nullable) float [n][H][W]: where SN_SMOOTH_CHANGED is set, 0.0f if the result is 0, else (float)result * S with
+ *     S = (float)((double)out_scale * 192.0) (one rounded multiply); nothing else is touched — sn_filter_raw's rule.
+ *   counts (nullable) [n][3] = {pixels with result > 0, changed with raw > 0, changed with raw <= 0} per map (integer sums:
+ *     deterministic).  At least one of out_raw and mask is required.
+ * SN_ERR_ARG: n outside 1..max_batch, p or raw NULL, radius outside 1..3, sigma_luma outside 0..255, sigma_luma > 0 with guide
+ * NULL, an unknown guide_kind, SN_GUIDE_NV12 with guide_pitch < W or odd, min_valid outside 0..(2*radius+1)^2, neither out_raw
+ * nor mask, overlapping buffers.
+ * mem / stream as sn_filter_raw: a NULL stream is the smoother's own stream (never the inference stream); the call returns
+ * after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller stream only enqueue.  May run
+ * concurrently with sn_submit / sn_wait on the same handle: stream, scratch and staging are its own (created on first use,
+ * only ever grown, freed by sn_destroy), and calls on different streams are ordered on the scratch by an event.  The scratch
+ * (the copy an in-place call reads, 4 bytes per pixel) holds min(max_batch, 8) maps; a larger n is walked in slices of 8 maps
+ * on the stream.  Not covered: the asynchronous sn_submit* slots and the node. */
+int sn_smooth_raw(sn_handle *h, int n, const int32_t *raw, const void *guide, int guide_kind, int guide_pitch,
+                  const sn_smooth_params *p, int32_t *out_raw, float *disp_inout, uint8_t *mask, uint32_t *counts,
+                  int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
