@@ -79,7 +79,13 @@ class SnSmoothParams(C.Structure):
     _fields_ = [("radius", C.c_int), ("sigma_luma", C.c_int), ("min_valid", C.c_int)]
 
 
+class SnTemporalParams(C.Structure):
+    """sn_temporal_params (include/stereonet_hip.h): the temporal filter of disparity streams."""
+    _fields_ = [("alpha", C.c_int), ("delta_px", C.c_float), ("persist", C.c_int), ("luma_delta", C.c_int)]
+
+
 SN_FLT_INVALID_IN, SN_FLT_SPECKLE, SN_FLT_FILLED = 1, 16, 32
+SN_TMP_INVALID_IN, SN_TMP_BLENDED, SN_TMP_HELD, SN_TMP_MOVED, SN_TMP_JUMP = 1, 2, 4, 8, 16      # a mask plane of its own
 SN_SMOOTH_INVALID_IN, SN_SMOOTH_CHANGED = 1, 128
 SN_GUIDE_NV12, SN_GUIDE_TENSOR = 0, 1
 SN_CONF_KEPT, SN_CONF_INVALID_IN, SN_CONF_LOW = 0, 1, 64
@@ -169,6 +175,11 @@ def load_library(path: Optional[str] = None):
     lib.sn_infer_lrc.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnLrcParams), i32p, fp, i32p, u8p, vp, ip, vp]
     lib.sn_filter_raw.argtypes = [vp, ip, i32p, C.POINTER(SnFilterParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_smooth_raw.argtypes = [vp, ip, i32p, vp, ip, ip, C.POINTER(SnSmoothParams), i32p, fp, u8p, vp, ip, vp]
+    lib.sn_temporal_create.argtypes = [vp, ip, C.POINTER(SnTemporalParams), C.POINTER(vp)]
+    lib.sn_temporal_reset.argtypes = [vp, ip]
+    lib.sn_temporal_destroy.argtypes = [vp]
+    lib.sn_temporal_destroy.restype = None
+    lib.sn_temporal_push.argtypes = [vp, ip, vp, i32p, vp, ip, ip, i32p, fp, u8p, vp, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -182,7 +193,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -255,7 +266,9 @@ class StereoNetHIP:
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            self._lib.sn_destroy(self._h)
+            rc = self._lib.sn_destroy(self._h)
+            if rc:                            # refused (a live TemporalFilter): the handle stays valid, close the filter first
+                self._check(rc, "sn_destroy")
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -656,6 +669,12 @@ class StereoNetHIP:
                                             out_raw_ptr or None, disp_ptr or None, mask_ptr or None, counts_ptr or None,
                                             SN_MEM_DEVICE, stream or None), "sn_smooth_raw")
 
+    # -- temporal filter of disparity streams ----------------------------------------------------------------
+    def temporal_filter(self, streams: int = 1, alpha: int = 64, delta_px: float = 0.5, persist: int = 2,
+                        luma_delta: int = 0) -> "TemporalFilter":
+        """A TemporalFilter (sn_temporal) of `streams` independent states on this engine; close it before the engine."""
+        return TemporalFilter(self, streams, alpha, delta_px, persist, luma_delta)
+
     def synchronize(self):
         self._check(self._lib.sn_synchronize(self._h), "sn_synchronize")
 
@@ -943,3 +962,83 @@ class StereoNetMultiGPU:
             self.close()
         except Exception:
             pass
+
+
+class TemporalFilter:
+    """sn_temporal: the temporal filter of disparity streams, with its per-stream state on the GPU (temporal.reference is the
+    numpy twin).  A context object: the engine refuses to close while one of its filters is open."""
+
+    def __init__(self, engine: StereoNetHIP, streams: int = 1, alpha: int = 64, delta_px: float = 0.5, persist: int = 2,
+                 luma_delta: int = 0):
+        self._eng, self._lib, self._t = engine, engine._lib, C.c_void_p()
+        self.streams, self.params = int(streams), SnTemporalParams(int(alpha), delta_px, int(persist), int(luma_delta))
+        engine._check(self._lib.sn_temporal_create(engine._h, self.streams, C.byref(self.params), C.byref(self._t)),
+                      "sn_temporal_create")
+
+    def close(self):
+        if getattr(self, "_t", None) and self._t.value:
+            self._lib.sn_temporal_destroy(self._t)
+            self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self, stream: int = -1):
+        """Stream `stream` (-1: all) starts afresh at its next push."""
+        self._eng._check(self._lib.sn_temporal_reset(self._t, int(stream)), "sn_temporal_reset")
+
+    def _ids(self, stream_of, n: int):
+        if stream_of is None:
+            return None
+        ids = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        if ids.size != n:
+            raise StereoNetError(-1, "temporal push", f"{ids.size} stream ids for {n} maps")
+        return ids
+
+    def push(self, raw: np.ndarray, guide: Optional[np.ndarray] = None, guide_kind: int = SN_GUIDE_NV12, guide_pitch: int = 0,
+             stream_of=None, disp: Optional[np.ndarray] = None):
+        """sn_temporal_push on host buffers: int32 (H,W) or (n,H,W), map k the next frame of stream stream_of[k] (None: all
+        of stream 0, one clip) -> (out int32, mask uint8 (SN_TMP_*), counts uint32 (n,4) = {valid, blended, held, moved or
+        jumped} per map).  guide as smooth_raw's (None only with luma_delta = 0); `disp` (float32, the maps' shape) is
+        rewritten IN PLACE where the result differs from max(raw, 0)."""
+        eng = self._eng
+        r = eng._maps(raw, "temporal push")
+        dp = eng._disp_ptr(disp, r.shape, "temporal push")
+        n, out, mask, counts = eng._mask_outputs(r, 4)
+        ids = self._ids(stream_of, n)
+        g = None
+        w, h = eng.width, eng.height
+        if guide is not None:
+            if guide_kind == SN_GUIDE_TENSOR:
+                g = np.ascontiguousarray(guide, dtype=np.int8)
+                if g.shape not in ((6, h, w), (n, 6, h, w)) or g.size != n * 6 * h * w:
+                    raise StereoNetError(-1, "temporal push", f"guide shape {g.shape} != ([{n},] 6, {h}, {w})")
+            else:
+                g = np.ascontiguousarray(guide, dtype=np.uint8).reshape(-1)
+                guide_pitch = guide_pitch or w
+                need = (n - 1) * guide_pitch * (h + (h + 1) // 2) + guide_pitch * (h - 1) + w
+                if guide_pitch < w or g.size < need:      # the library cannot see how long a host buffer is
+                    raise StereoNetError(-1, "temporal push", f"guide of {g.size} bytes, {n} frames of pitch {guide_pitch} take {need}")
+        eng._check(self._lib.sn_temporal_push(self._t, n, _np_ptr(ids), r.ctypes.data, _np_ptr(g), guide_kind, guide_pitch,
+                                              out.ctypes.data, dp, mask.ctypes.data, counts.ctypes.data, SN_MEM_HOST, None),
+                   "sn_temporal_push")
+        return out, mask, counts
+
+    def push_device(self, n: int, raw_ptr: int, guide_ptr: int = 0, guide_kind: int = SN_GUIDE_NV12, guide_pitch: int = 0,
+                    stream_of=None, out_raw_ptr: int = 0, mask_ptr: int = 0, disp_ptr: int = 0, counts_ptr: int = 0,
+                    stream: int = 0):
+        """sn_temporal_push on device pointers (out_raw_ptr may equal raw_ptr; stream_of stays a host sequence); stream =
+        hipStream_t as int (0: the filter's own stream, and the call returns after completion)."""
+        ids = self._ids(stream_of, n)
+        self._eng._check(self._lib.sn_temporal_push(self._t, n, _np_ptr(ids), raw_ptr or None, guide_ptr or None, guide_kind,
+                                                    guide_pitch, out_raw_ptr or None, disp_ptr or None, mask_ptr or None,
+                                                    counts_ptr or None, SN_MEM_DEVICE, stream or None), "sn_temporal_push")

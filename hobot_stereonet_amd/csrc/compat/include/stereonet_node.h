@@ -39,7 +39,8 @@ struct StereonetNodeOutput : public hobot::dnn_node::DnnNodeOutput {
   // this implementation's own: set when the left-eye JPEG of this request is being encoded on a worker thread
   // (sp_left_nv12->jpeg is complete once it yields true); PostProcess waits for it
   std::shared_future<bool> jpeg_ready;
-  // kept only while the point cloud is on (STEREONET_POINTCLOUD): the frame whose left eye colours the cloud
+  // kept only while the point cloud is on (STEREONET_POINTCLOUD) or the temporal filter reads the luma (STEREONET_TEMPORAL
+  // with LUMA_DELTA > 0): the frame whose left eye colours the cloud and guides the filter
   hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame;
 };
 
@@ -49,6 +50,7 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
  public:
   StereonetNode(const std::string& node_name = "stereonet_node",
                 const rclcpp::NodeOptions& options = rclcpp::NodeOptions());
+  ~StereonetNode() override;
 
   // true once the model is loaded and the subscription exists (the harness checks it; the reference shuts
   // rclcpp down instead, which this node does as well)
@@ -84,6 +86,10 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // STEREONET_POINTCLOUD_Z=min,max (metres; max <= 0: no upper bound)
     int pointcloud_layout = -1;       // -1 off, else SN_PC_ORGANISED / SN_PC_COMPACT
     sn_camera camera{};
+    // this implementation's own: the temporal filter of the disparity stream (sn_temporal_push), applied to the int32 tensor
+    // in place before it is packed and before the cloud is built.  STEREONET_TEMPORAL=ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]
+    // (PERSIST defaults to 2, LUMA_DELTA to 0) turns it on; unset: off, nothing of it exists
+    sn_temporal_params temporal{};
   };
 
   void DeclareAndReadParameters();
@@ -91,6 +97,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame);   // the FeedImg role
   void ReadPointCloudSettings();
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
+  void ReadTemporalSettings();
+  void FilterTemporal(const StereonetNodeOutput& request, int32_t* raw);
 
   Settings cfg_;
   bool ready_ = false;
@@ -105,6 +113,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   rclcpp::Publisher<ai_msgs::msg::PerceptionTargets>::SharedPtr targets_out_;   // created for parity, never used
   rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pointcloud_out_;   // only while the cloud is on
   std::atomic<bool> cloud_uncoloured_logged_{false};
+  sn_temporal* temporal_ = nullptr;              // one stream; only while STEREONET_TEMPORAL is set and valid
+  bool temporal_unguided_logged_ = false;        // PostProcess only (one thread at a time)
 };
 
 }  // namespace stereonet

@@ -94,7 +94,15 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
   disparity_out_ = create_publisher<sensor_msgs::msg::Image>(cfg_.output_topic, 10);
   ReadPointCloudSettings();
   if (cfg_.pointcloud_layout >= 0) pointcloud_out_ = create_publisher<sensor_msgs::msg::PointCloud2>("/stereonet_pointcloud2", 10);
+  ReadTemporalSettings();
   ready_ = true;
+}
+
+StereonetNode::~StereonetNode() {
+  if (!temporal_) return;
+  WaitIdle();      // requests in flight still pass through PostProcess; the engine is destroyed after the filter (~DnnNode)
+  sn_temporal_destroy(temporal_);
+  temporal_ = nullptr;
 }
 
 void StereonetNode::DeclareAndReadParameters() {
@@ -152,6 +160,57 @@ void StereonetNode::ReadPointCloudSettings() {
   RCLCPP_WARN_STREAM(kLog, "point cloud: " << e << " on /stereonet_pointcloud2, fx " << c.fx << " fy " << c.fy << " cx " << c.cx
                                            << " cy " << c.cy << " baseline_mm " << c.baseline_mm << " step " << c.step
                                            << " z " << c.z_min_m << ".." << c.z_max_m);
+}
+
+// parsed and validated once here: a value sn_temporal_create would reject turns the filter off instead of failing every frame
+void StereonetNode::ReadTemporalSettings() {
+  const char* e = getenv("STEREONET_TEMPORAL");
+  if (!e || !*e) return;
+  sn_temporal_params& p = cfg_.temporal;
+  p = sn_temporal_params{0, 0.f, 2, 0};
+  int n2 = 0, n3 = 0, n4 = 0;      // characters used after 2, 3 and 4 fields: the whole value must be used
+  const int got = sscanf(e, "%d,%f%n,%d%n,%d%n", &p.alpha, &p.delta_px, &n2, &p.persist, &n3, &p.luma_delta, &n4);
+  const int used = got == 2 ? n2 : got == 3 ? n3 : got == 4 ? n4 : -1;
+  std::string bad;
+  if (used != (int)strlen(e))
+    bad = "is not ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]";
+  else if (p.alpha < 1 || p.alpha > 256 || !std::isfinite(p.delta_px) || p.delta_px < 0.f || p.persist < 0 || p.persist > 8 ||
+           p.luma_delta < 0 || p.luma_delta > 255)
+    bad = "needs ALPHA 1..256, DELTA_PX finite and >= 0, PERSIST 0..8, LUMA_DELTA 0..255";
+  else if (sn_temporal_create(net_->engine(), 1, &p, &temporal_) != SN_OK)
+    bad = std::string("was refused: ") + sn_last_error(net_->engine());
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, "STEREONET_TEMPORAL=" << e << " " << bad << ": no temporal filter");
+    temporal_ = nullptr;
+    return;
+  }
+  RCLCPP_WARN_STREAM(kLog, "temporal filter: alpha " << p.alpha << "/256, delta_px " << p.delta_px << ", persist " << p.persist
+                                                     << ", luma_delta " << p.luma_delta);
+}
+
+// The request's int32 tensor, filtered in place as the next frame of the node's one stream.  DnnNode::CompletionLoop calls
+// PostProcess from one thread in submission order, and the synchronous path calls it inline, so the pushes arrive in frame
+// order.  With LUMA_DELTA > 0 the guide is the request's side-by-side frame (NV12, pitch 2W).  A request without a frame of
+// the model's size (the offline feeder's) has no luma to compare: its map passes UNFILTERED and the stream is reset, so the
+// next guided frame starts afresh instead of being blended across the gap.
+void StereonetNode::FilterTemporal(const StereonetNodeOutput& request, int32_t* raw) {
+  const auto& f = request.frame;
+  const uint8_t* guide = nullptr;
+  if (cfg_.temporal.luma_delta > 0) {
+    const bool guided = f && (int)f->width == 2 * net_w_ && (int)f->height == net_h_ &&
+                        f->data.size() >= (size_t)2 * net_w_ * (net_h_ + (net_h_ + 1) / 2);
+    if (!guided) {
+      if (!temporal_unguided_logged_)
+        RCLCPP_WARN(kLog, "temporal filter: no side-by-side frame of the model's size for this request, map not filtered");
+      temporal_unguided_logged_ = true;
+      sn_temporal_reset(temporal_, 0);
+      return;
+    }
+    guide = f->data.data();
+  }
+  if (sn_temporal_push(temporal_, 1, nullptr, raw, guide, SN_GUIDE_NV12, 2 * net_w_, raw, nullptr, nullptr, nullptr, SN_MEM_HOST,
+                       nullptr) != SN_OK)
+    RCLCPP_ERROR(kLog, "temporal filter failed: %s", sn_last_error(net_->engine()));
 }
 
 // sensor_msgs/PointCloud2 of the request's map: x, y, z (+ rgb) FLOAT32 at 0 / 4 / 8 / 12, 16 bytes a point, the header of
@@ -250,7 +309,7 @@ void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSha
   request->msg_header = std::make_shared<std_msgs::msg::Header>();
   request->msg_header->frame_id = std::to_string(frame->index);
   request->msg_header->stamp = frame->time_stamp;
-  if (cfg_.pointcloud_layout >= 0) request->frame = frame;
+  if (cfg_.pointcloud_layout >= 0 || (temporal_ && cfg_.temporal.luma_delta > 0)) request->frame = frame;
 
   const auto t_pre = std::chrono::steady_clock::now();
   // STEREONET_INGEST=tensor keeps the reference's host steps (split both eyes, CvtNV12Data2Tensors, Run on the int8
@@ -412,6 +471,9 @@ int StereonetNode::PostProcess(const std::shared_ptr<hobot::dnn_node::DnnNodeOut
     rclcpp::shutdown();
     return -1;
   }
+  // ahead of the message and of the cloud: both see the filtered map
+  if (temporal_ && !request->output_tensors.empty())
+    FilterTemporal(*request, static_cast<int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
   if (cfg_.publish_output && request->sp_left_nv12 && !request->output_tensors.empty()) {
     // wire format consumed by the render node: sensor_msgs/Image, encoding "jpeg",
     // data = the raw int32 output tensor followed by the JPEG of the left eye, step = total length

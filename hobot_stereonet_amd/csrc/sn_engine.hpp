@@ -257,6 +257,24 @@ struct sn_handle {
     hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
     GrowBuf buf[kCount];
   } smo;
+  std::atomic<int> temporal_live{0};   // sn_temporal objects created on this handle and not yet destroyed: sn_destroy refuses
+};
+
+// sn_temporal_*: the one post-processing stage with state.  What the filter's and the smoother's structs hold per handle, this
+// object holds per filter — stream, event, mutex, host-mode staging — plus the state planes and the per-stream "fresh" flags.
+struct sn_temporal {
+  // host mode: map (filtered in place), guide, float map, mask, counts
+  enum { kRaw = 0, kGuide, kDisp, kMask, kCounts, kCount };
+  sn_handle* h = nullptr;
+  int streams = 0;
+  sn_temporal_params p{};
+  long long q = 0;                   // delta_px in units of raw
+  std::mutex mu;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev = nullptr;           // the last enqueue that used the state and the staging
+  GrowBuf buf[kCount];
+  void* state = nullptr;             // one allocation: P int32 [streams][H*W], then Hs and Yp uint8 [streams][H*W]
+  std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
 };
 
 namespace {

@@ -1,7 +1,7 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the pair-input staging, the per-call host staging and the overlap predicate — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter and smoother.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp and sn_smooth.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother and temporal filter.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp and sn_temporal.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -642,6 +642,154 @@ int sn_smooth_raw(sn_handle* h, int n, const int32_t* raw, const void* guide, in
   HIP_TRY(h, hipGetLastError());
   if (int e = s.download()) return e;
   HIP_TRY(h, hipEventRecord(f.ev, st));
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// ---- temporal filter of disparity streams (csrc/sn_temporal.hpp): an object with its own state, stream, event and mutex ------
+int sn_temporal_create(sn_handle* h, int streams, const sn_temporal_params* p, sn_temporal** out) {
+  if (!h) return SN_ERR_ARG;
+  if (!p || !out || streams < 1 || streams > h->max_batch || p->alpha < 1 || p->alpha > 256 || !std::isfinite(p->delta_px) ||
+      p->delta_px < 0.f || p->persist < 0 || p->persist > 8 || p->luma_delta < 0 || p->luma_delta > 255) {
+    set_err(h, "sn_temporal_create: bad arguments");
+    return SN_ERR_ARG;
+  }
+  const int rc = check_device(h);
+  if (rc) return rc;
+  std::unique_ptr<sn_temporal> t(new sn_temporal);
+  t->h = h;
+  t->streams = streams;
+  t->p = *p;
+  const float q = floorf(p->delta_px / (float)((double)kOutScale * kWireFactor));      // sn_filter_raw's dq
+  t->q = q >= 4294967296.f ? 4294967296ll : (long long)q;
+  t->fresh.assign(streams, 1);
+  if (hipMalloc(&t->state, (size_t)streams * h->H * h->W * 6) != hipSuccess) {
+    (void)hipGetLastError();
+    set_err(h, "sn_temporal_create: out of device memory");
+    return SN_ERR_NOMEM;
+  }
+  ++h->temporal_live;
+  *out = t.release();
+  return SN_OK;
+}
+
+int sn_temporal_reset(sn_temporal* t, int stream) {
+  if (!t) return SN_ERR_ARG;
+  if (stream < -1 || stream >= t->streams) {
+    set_err(t->h, "sn_temporal_reset: bad arguments");
+    return SN_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(t->mu);
+  if (stream < 0) std::fill(t->fresh.begin(), t->fresh.end(), (uint8_t)1);
+  else t->fresh[stream] = 1;
+  return SN_OK;
+}
+
+void sn_temporal_destroy(sn_temporal* t) {
+  if (!t) return;
+  (void)hipSetDevice(t->h->device);
+  if (t->stream) (void)hipStreamSynchronize(t->stream);
+  if (t->ev) {
+    (void)hipEventSynchronize(t->ev);      // a push that was only enqueued on a caller's stream
+    (void)hipEventDestroy(t->ev);
+  }
+  if (t->stream) (void)hipStreamDestroy(t->stream);
+  for (GrowBuf& b : t->buf) b.release();
+  (void)hipFree(t->state);
+  --t->h->temporal_live;
+  delete t;
+}
+
+int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t* raw, const void* guide, int guide_kind,
+                     int guide_pitch, int32_t* out_raw, float* disp_inout, uint8_t* mask, uint32_t* counts, int mem,
+                     void* stream) {
+  if (!t) return SN_ERR_ARG;
+  sn_handle* h = t->h;
+  const size_t HW = (size_t)h->H * h->W;
+  const bool nv12 = guide_kind == SN_GUIDE_NV12;
+  const bool luma = t->p.luma_delta > 0;      // luma_delta == 0: the guide is ignored altogether
+  bool ok = raw && (out_raw || mask) && n > 0 && n <= h->max_batch && !(luma && !guide) &&
+            (nv12 || guide_kind == SN_GUIDE_TENSOR) && !(nv12 && guide && (guide_pitch < h->W || (guide_pitch & 1)));
+  for (int k = 0; ok && stream_of && k < n; ++k) ok = stream_of[k] >= 0 && stream_of[k] < t->streams;
+  if (!ok) {
+    set_err(h, "sn_temporal_push: bad arguments");
+    return SN_ERR_ARG;
+  }
+  const size_t cnt = (size_t)n * HW;
+  const size_t frame = nv12 ? (size_t)guide_pitch * (h->H + (h->H + 1) / 2) : 6 * HW;      // as sn_smooth_raw
+  const size_t guide_bytes = !luma ? 0 : (n - 1) * frame + (nv12 ? (size_t)guide_pitch * (h->H - 1) + h->W : HW);
+  {      // out_raw == raw is the one overlap the kernel is written for
+    const Span r{raw, cnt * 4}, o{out_raw, cnt * 4}, d{disp_inout, cnt * 4}, m{mask, cnt}, k{counts, (size_t)n * 16};
+    const Span g{luma ? guide : nullptr, guide_bytes};
+    if ((out_raw != raw && overlap({r}, {o})) || overlap({r, o}, {d, m, k}) || overlap({d}, {m, k}) || overlap({m}, {k}) ||
+        overlap({g}, {o, d, m, k})) {
+      set_err(h, "sn_temporal_push: overlapping buffers (only out_raw == raw is allowed)");
+      return SN_ERR_ARG;
+    }
+  }
+  using T = sn_temporal;
+  std::lock_guard<std::mutex> lk(t->mu);
+  Call c;
+  const int rc = enter(h, "sn_temporal_push", mem, stream, &t->stream, &c);
+  if (rc) return rc;
+  if (!t->ev) HIP_TRY(h, hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
+  hipStream_t st = c.st;
+  HIP_TRY(h, hipStreamWaitEvent(st, t->ev, 0));      // the previous push (any stream) is done with the state and the staging
+  Staging s{h, "sn_temporal_push", st, c.host, t->buf};
+  const int32_t* draw = s.in(T::kRaw, raw, cnt * 4);
+  const uint8_t* dguide = luma ? s.in(T::kGuide, static_cast<const uint8_t*>(guide), guide_bytes) : nullptr;
+  int32_t* dout = s.alias(out_raw, s.staged<int32_t>(T::kRaw), cnt * 4);      // host mode: filtered in place
+  float* ddisp = s.inout(T::kDisp, disp_inout, cnt * 4);
+  uint8_t* dmask = s.out(T::kMask, mask, cnt);
+  uint32_t* dcounts = s.out(T::kCounts, counts, (size_t)n * 16);
+  if (s.rc) return s.rc;
+  int32_t* P = static_cast<int32_t*>(t->state);
+  uint8_t* Hs = reinterpret_cast<uint8_t*>(P + (size_t)t->streams * HW);
+  TmpArgs a{};
+  a.P = P, a.Hs = Hs, a.Yp = Hs + (size_t)t->streams * HW;
+  a.luma_frame = frame, a.luma_pitch = nv12 ? guide_pitch : h->W, a.luma_xor = nv12 ? 0u : 0x80u;
+  a.W = h->W, a.H = h->H, a.alpha = t->p.alpha, a.persist = t->p.persist, a.luma_delta = t->p.luma_delta, a.q = t->q;
+  a.S = (float)((double)kOutScale * kWireFactor);
+  if (dcounts) HIP_TRY(h, hipMemsetAsync(dcounts, 0, (size_t)n * 16, st));
+  // 16-byte map accesses, 4-byte luma and mask accesses: every address the kernel forms must be that aligned
+  const bool vec = (h->W & 3) == 0 && (((uintptr_t)draw | (uintptr_t)dout) & 15) == 0 && ((uintptr_t)dmask & 3) == 0 &&
+                   (!luma || (((uintptr_t)dguide | frame | (size_t)a.luma_pitch) & 3) == 0);
+  const unsigned chunks = (unsigned)((HW + (vec ? 1023 : 255)) / (vec ? 1024 : 256));
+  for (int k0 = 0; k0 < n; k0 += kTmpSlice) {      // the frame lists of kTmpSlice maps fit the kernel arguments
+    const int m = std::min(kTmpSlice, n - k0);
+    const size_t off = (size_t)k0 * HW;
+    a.raw = draw + off;
+    a.luma = dguide ? dguide + (size_t)k0 * frame : nullptr;
+    a.out_raw = dout ? dout + off : nullptr;
+    a.disp = ddisp ? ddisp + off : nullptr;
+    a.mask = dmask ? dmask + off : nullptr;
+    a.counts = dcounts ? dcounts + (size_t)k0 * 4 : nullptr;
+    int groups = 0, filled = 0;      // group the slice's maps by stream, in order of first appearance, each in the order of k
+    for (int k = 0; k < m; ++k) {
+      const int id = stream_of ? stream_of[k0 + k] : 0;
+      bool known = false;
+      for (int g = 0; g < groups && !known; ++g) known = a.stream[g] == id;
+      if (!known) a.stream[groups++] = id;
+    }
+    for (int g = 0; g < groups; ++g) {
+      a.first[g] = filled;
+      a.fresh[g] = t->fresh[a.stream[g]];
+      for (int k = 0; k < m; ++k)
+        if ((stream_of ? stream_of[k0 + k] : 0) == a.stream[g]) a.map[filled++] = k;
+    }
+    a.first[groups] = filled;
+    const dim3 grid(chunks, groups), block(256);
+    switch ((vec ? 2 : 0) + (luma ? 1 : 0)) {
+      case 0: hipLaunchKernelGGL((k_temporal<false, false>), grid, block, 0, st, a); break;
+      case 1: hipLaunchKernelGGL((k_temporal<false, true>), grid, block, 0, st, a); break;
+      case 2: hipLaunchKernelGGL((k_temporal<true, false>), grid, block, 0, st, a); break;
+      default: hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, st, a); break;
+    }
+    HIP_TRY(h, hipGetLastError());
+    for (int g = 0; g < groups; ++g) t->fresh[a.stream[g]] = 0;      // enqueued: the state now holds these frames
+  }
+  if (int e = s.download()) return e;
+  HIP_TRY(h, hipEventRecord(t->ev, st));
   if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }

@@ -5,7 +5,8 @@ D1) needed to score the output against dataset ground truth.
     python -m hobot_stereonet_amd.filelist --model m.snw --left left.list --right right.list \
         [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
         [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
-        [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]]
+        [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
+        [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -35,6 +36,14 @@ The guide is the side-by-side NV12 frame the harness holds anyway.  The smoothed
 <i>.smooth.pgm holds the mask (smooth.BITS), every record gains "smoothed" (changed pixels) and "density", the summary their
 total and mean.  With ground truth the record gains "smooth_epe": the EPE over the pixels that held a measurement before the
 step, before and after it.
+
+--temporal takes the list as ONE clip in list order and runs every map, after --smooth and everything before it, through a
+temporal filter (`sn_temporal_push`, one stream): a measurement within DELTA_PX of the pixel's filtered past is blended with it
+(weight ALPHA / 256 for the new one), a pixel without one keeps its last value while PERSIST of its last eight inputs held one
+(default 2, 0 = never), and with LUMA_DELTA > 0 (default 0) a luma change above it in the left eye stops both.  The filtered
+map feeds the metrics, --ply and --out; <i>.temporal.pgm holds the mask (temporal.BITS: a plane of its own), every record
+gains "blended", "held" and "density", the summary their totals and mean and "flicker_before" / "flicker_after" (mean frame to
+frame change in px over pixels measured in both frames).  With ground truth the record gains "temporal_epe", before and after.
 """
 import argparse
 import json
@@ -109,7 +118,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
-                lrc=None, flt=None, conf: Optional[float] = None, smooth=None) -> List[dict]:
+                lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -124,7 +133,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     lr_check, conf_mask — two forwards — and "mask" is the OR of the two masks.
     smooth = (radius, sigma_luma, min_valid): the maps then pass through engine.smooth_raw, guided by the frame's left eye; the
     record gains "smooth_mask", "smoothed" (changed pixels) and "density" (pixels > 0 after the step), <i>.smooth.pgm is written,
-    and with ground truth "smooth_epe" = {"before", "after", "valid_px"} over the pixels that held a measurement before it."""
+    and with ground truth "smooth_epe" = {"before", "after", "valid_px"} over the pixels that held a measurement before it.
+    temporal = (alpha, delta_px, persist, luma_delta): the list is one clip; the maps pass last through one api.TemporalFilter
+    that lives for the call; the record gains "temporal_in" (the map before the step), "temporal_mask", "blended", "held" and
+    "density", <i>.temporal.pgm is written, and with ground truth "temporal_epe" as "smooth_epe"."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -134,6 +146,17 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             os.makedirs(d, exist_ok=True)
     w, h = engine.width, engine.height
     results = []
+    tf = engine.temporal_filter(1, *temporal) if temporal is not None else None
+    try:
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results)
+    finally:
+        if tf is not None:
+            tf.close()
+    return results
+
+
+def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results):
+    w, h = engine.width, engine.height
     for i, (lp, rp) in enumerate(zip(left, right)):
         if log:
             log(f"Feed {i}/{len(left)}")
@@ -173,6 +196,11 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             raw, smask, counts = engine.smooth_raw(raw, sbs, 0, 2 * w, smooth[0], smooth[1], smooth[2], disp=disp)
             rec.update(raw=raw, smooth_mask=smask, smoothed=int(counts[0][1]) + int(counts[0][2]),
                        density=float(counts[0][0]) / float(w * h))
+        if tf is not None:
+            traw_in, tdisp_in = raw, disp.copy()
+            raw, tmask, counts = tf.push(raw, sbs, 0, 2 * w, disp=disp)
+            rec.update(raw=raw, temporal_in=traw_in, temporal_mask=tmask, blended=int(counts[0][1]), held=int(counts[0][2]),
+                       density=float(counts[0][0]) / float(w * h))
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -192,6 +220,11 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
                 if gt_valid is not None:
                     held &= gt_valid
                 rec["smooth_epe"] = {"before": epe(disp_in, gt, held), "after": epe(disp, gt, held), "valid_px": int(held.sum())}
+            if tf is not None:
+                held = (traw_in > 0) & (gt < float(engine.dmax))
+                if gt_valid is not None:
+                    held &= gt_valid
+                rec["temporal_epe"] = {"before": epe(tdisp_in, gt, held), "after": epe(disp, gt, held), "valid_px": int(held.sum())}
         if out_dir:
             raw.tofile(os.path.join(out_dir, f"{i}.raw.bin"))
             images.write_pfm(os.path.join(out_dir, f"{i}.disp.pfm"), disp)
@@ -206,8 +239,9 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
                 images.write_ppm(os.path.join(out_dir, f"{i}.filter.pgm"), fmask)
             if smooth is not None:
                 images.write_ppm(os.path.join(out_dir, f"{i}.smooth.pgm"), smask)
+            if tf is not None:
+                images.write_ppm(os.path.join(out_dir, f"{i}.temporal.pgm"), tmask)
         results.append(rec)
-    return results
 
 
 def main(argv=None) -> int:
@@ -236,6 +270,11 @@ def main(argv=None) -> int:
                     help="guided weighted median over a (2 RADIUS + 1)^2 window, RADIUS 1..3; SIGMA 0..255 is the luma scale of "
                          "the weights (default 12, 0 = plain median); MIN_VALID > 0 also fills pixels without a measurement "
                          "whose window holds that many (default 0); runs after every other step")
+    ap.add_argument("--temporal", default=None, metavar="ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]",
+                    help="temporal filter over the list as one clip, after every other step: ALPHA 1..256 is the weight of the "
+                         "new measurement in 1/256, DELTA_PX the largest change that is still blended, PERSIST 0..8 (default 2) "
+                         "how many of the last eight inputs must be valid to hold a value, LUMA_DELTA 0..255 (default 0 = off) "
+                         "the luma change that counts as motion")
     args = ap.parse_args(argv)
     from . import api, pointcloud
     cam = None
@@ -290,12 +329,23 @@ def main(argv=None) -> int:
         if len(v) != 3 or not (1 <= v[0] <= 3 and 0 <= v[1] <= 255 and 0 <= v[2] <= (2 * v[0] + 1) ** 2):
             ap.error("--smooth takes RADIUS[,SIGMA[,MIN_VALID]]: integers, 1..3, 0..255 and 0..(2 RADIUS + 1)^2")
         smooth = tuple(v)
+    temporal = None
+    if args.temporal is not None:
+        t = args.temporal.split(",")
+        try:
+            v = [int(t[0]), float(t[1])] + [int(x) for x in t[2:]]
+        except (ValueError, IndexError):
+            v = []
+        v += [2, 0][len(v) - 2:] if 2 <= len(v) <= 4 else []
+        if len(v) != 4 or not (1 <= v[0] <= 256 and np.isfinite(v[1]) and v[1] >= 0 and 0 <= v[2] <= 8 and 0 <= v[3] <= 255):
+            ap.error("--temporal takes ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]: 1..256, a finite difference >= 0, 0..8 and 0..255")
+        temporal = tuple(v)
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
-                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth)
+                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -313,7 +363,17 @@ def main(argv=None) -> int:
         if args.gt:
             summary["smooth_epe_before"] = float(np.nanmean([r["smooth_epe"]["before"] for r in recs]))
             summary["smooth_epe_after"] = float(np.nanmean([r["smooth_epe"]["after"] for r in recs]))
-    if (lrc is not None or flt is not None or conf is not None or smooth is not None) and recs:
+    if temporal is not None and recs:
+        from . import temporal as tmp
+        scale = float(tmp.wire_scale(eng.out_scale))
+        summary["blended"] = int(sum(r["blended"] for r in recs))
+        summary["held"] = int(sum(r["held"] for r in recs))
+        summary["flicker_before"] = tmp.flicker(np.stack([r["temporal_in"] for r in recs])) * scale
+        summary["flicker_after"] = tmp.flicker(np.stack([r["raw"] for r in recs])) * scale
+        if args.gt:
+            summary["temporal_epe_before"] = float(np.nanmean([r["temporal_epe"]["before"] for r in recs]))
+            summary["temporal_epe_after"] = float(np.nanmean([r["temporal_epe"]["after"] for r in recs]))
+    if (lrc is not None or flt is not None or conf is not None or smooth is not None or temporal is not None) and recs:
         summary["density"] = float(np.mean([r["density"] for r in recs]))
     print(json.dumps(summary))
     return 0

@@ -591,6 +591,72 @@ int sn_smooth_raw(sn_handle *h, int n, const int32_t *raw, const void *guide, in
                   const sn_smooth_params *p, int32_t *out_raw, float *disp_inout, uint8_t *mask, uint32_t *counts,
                   int mem, void *stream);
 
+/* ---- temporal filter of disparity STREAMS: the one stage of the chain that keeps state between calls --------------------------
+ * Every stage above treats a map on its own.  A learned matcher shows its noise over time: surfaces shimmer from frame to
+ * frame, and pixels that the check or the confidence mask reject flicker in and out.  sn_temporal blends a pixel with its own
+ * filtered past while it stays near it, holds the last value over short dropouts, and lets go at once where the left image's
+ * luma says that the scene moved.  Integer per pixel and bit-exact; the state lives on the GPU, one set per stream. */
+typedef struct sn_temporal_params {
+  int   alpha;       /* 1..256: the weight of the new measurement in 1/256; 256 = no blending                       */
+  float delta_px;    /* >= 0, finite: blend only while |new - last| <= this many pixels                             */
+  int   persist;     /* 0: never fill; 1..8: a pixel without a measurement keeps its last value while at least this */
+                     /* many of its last eight inputs held one                                                      */
+  int   luma_delta;  /* 0: the guide is not read (may be NULL); 1..255: a luma change above this counts as motion   */
+} sn_temporal_params;
+/* The eight bits of the chain's OR-able mask are all taken (SN_LRC_* 1 2 4 8, SN_FLT_* 16 32, SN_CONF_LOW 64,
+ * SN_SMOOTH_CHANGED 128), so the temporal mask is a PLANE OF ITS OWN with its own enum: it must not be OR-ed with the others. */
+enum { SN_TMP_INVALID_IN = 1, SN_TMP_BLENDED = 2, SN_TMP_HELD = 4, SN_TMP_MOVED = 8, SN_TMP_JUMP = 16 };
+typedef struct sn_temporal sn_temporal;
+/* With S = (float)((double)out_scale * 192.0) as for sn_filter_raw, q = (int64_t)floorf(delta_px / S), one fp32 division on
+ *   the host (a quotient of 2^32 or more is taken as 2^32), exactly as sn_filter_raw turns speckle_diff_px into dq.
+ * State per stream and pixel (6 bytes): P int32 >= 0, the last filtered value, 0 = none; Hs uint8, bit i = the input i + 1
+ *   frames ago held a measurement; Yp uint8, the last frame's luma.  A fresh or reset stream has P = 0, Hs = 0 and has seen no
+ *   frame (there is no previous luma).
+ * One frame of a stream, per pixel, with r = max(raw, 0) and y = the left image's luma Y(k, v, u) — guide, guide_kind and
+ *   guide_pitch exactly as sn_smooth_raw's (SN_GUIDE_NV12 with the frame stride and pitch rules of sn_pointcloud_from_raw,
+ *   SN_GUIDE_TENSOR); with luma_delta == 0 the guide is not read:
+ *     moved = luma_delta > 0 && the stream has seen a frame && |y - Yp| > luma_delta
+ *     r > 0:   P > 0 && !moved && |r - P| <= q (in 64 bits):
+ *                  out = (alpha*r + (256 - alpha)*P + 128) >> 8 in 64 bits (never 0: r, P >= 1), SN_TMP_BLENDED if out != r;
+ *              otherwise out = r, and where P > 0: SN_TMP_MOVED if moved, else SN_TMP_JUMP.
+ *              P' = out.
+ *     r == 0:  SN_TMP_INVALID_IN, and
+ *              persist > 0 && P > 0 && !moved && popcount(Hs) >= persist: out = P, SN_TMP_HELD, P' = P;
+ *              otherwise out = 0; P > 0 && moved: SN_TMP_MOVED and P' = 0; else P' = P.
+ *     then Hs' = ((Hs << 1) | (r > 0)) & 255, and Hs' == 0 sets P' = 0: a held value is never older than eight frames;
+ *     then Yp' = y.
+ *   The mask is one of 0, 1, 2, 5, 8, 9, 16; out > 0 exactly where it is 0, 2, 5, 8 or 16.
+ * sn_temporal_create: a filter of `streams` independent states (1 <= streams <= max_batch) on handle h, all fresh; the state
+ *   (6 * H * W * streams bytes), a stream, an event and the host-mode staging are the object's own.  SN_ERR_ARG: a NULL pointer,
+ *   streams out of range, alpha outside 1..256, delta_px negative or not finite, persist outside 0..8, luma_delta outside
+ *   0..255.  While a filter is alive sn_destroy(h) is REFUSED: it returns SN_ERR_BUSY and leaves the handle as it was — destroy
+ *   the handle's filters first.
+ * sn_temporal_reset: stream `stream` (-1: all) is fresh again.  A host-side flag that takes effect at the next push: no device
+ *   work, no memset, nothing to order.  SN_ERR_ARG: an id outside -1..streams-1.
+ * sn_temporal_push: n maps raw [n][H][W] (1 <= n <= max_batch); map k is the next frame of stream stream_of[k] (a host array
+ *   of n ids; NULL: every map belongs to stream 0, i.e. the call is one clip).  Maps with the same id are consecutive frames in
+ *   the order of k, and the result equals n single-map pushes in that order, bit for bit.
+ *   out_raw (nullable) = out; out_raw == raw is allowed (the kernel is pointwise: no copy), any other overlap between the
+ *     buffers is SN_ERR_ARG, and the guide must not overlap an output.
+ *   mask (nullable) [n][H][W] = the bits above.  At least one of out_raw and mask is required.
+ *   disp_inout (nullable) float [n][H][W]: rewritten exactly where out != r, as (float)out * S (one rounded multiply,
+ *     sn_filter_raw's rule; out > 0 there); nothing else is touched.
+ *   counts (nullable) [n][4] = {pixels with out > 0, with SN_TMP_BLENDED, with SN_TMP_HELD, with SN_TMP_MOVED or SN_TMP_JUMP}
+ *     per map (integer sums: deterministic).
+ *   SN_ERR_ARG (sn_last_error(h) names the call; nothing is launched and no state changes): n out of range, raw NULL, neither
+ *     out_raw nor mask, an id outside 0..streams-1, luma_delta > 0 with guide NULL, an unknown guide_kind, SN_GUIDE_NV12 with
+ *     guide_pitch < W or odd, overlapping buffers, a bad mem.
+ *   mem / stream as sn_filter_raw: a NULL stream is the filter's own stream (never the inference stream); the call returns
+ *   after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller stream only enqueue.  May run beside
+ *   sn_submit / sn_wait on the same handle, and calls are serialised by the object's mutex; pushes on different streams are
+ *   ordered on the state by an event.  One kernel launch per 64 maps of a call.  Not covered: the asynchronous sn_submit* slots. */
+int  sn_temporal_create(sn_handle *h, int streams, const sn_temporal_params *p, sn_temporal **out);
+int  sn_temporal_reset(sn_temporal *t, int stream);
+void sn_temporal_destroy(sn_temporal *t);
+int  sn_temporal_push(sn_temporal *t, int n, const int *stream_of, const int32_t *raw, const void *guide, int guide_kind,
+                      int guide_pitch, int32_t *out_raw, float *disp_inout, uint8_t *mask, uint32_t *counts, int mem,
+                      void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
