@@ -750,20 +750,31 @@ int auto_selfcheck(sn_handle* h, Workspace& ws, hipStream_t st, const int8_t* in
 }
 
 // A statistic of an earlier call that only enqueued its work (device buffers + caller stream): folded in once its copy has
-// landed (wait = false: only if it already has).
+// landed (wait = false: only if it already has; wait = true: after waiting for it).  The pending fields are read and
+// cleared under h->mu; the event is waited for outside it.
 int fold_pending(sn_handle* h, bool wait) {
   AutoCtl& a = h->actl;
-  if (!a.pending) return SN_OK;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!a.pending) return SN_OK;
+  }
   if (wait) {
     HIP_TRY(h, hipEventSynchronize(h->ev_stats));
   } else if (hipEventQuery(h->ev_stats) != hipSuccess) {
     (void)hipGetLastError();               // hipErrorNotReady: try again at the next call
     return SN_OK;
   }
-  a.pending = false;
+  int n, mode;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!a.pending) return SN_OK;
+    a.pending = false;
+    n = a.pending_n;
+    mode = a.pending_mode;
+  }
   double lvl[kMaxLevels], res = 0.0;
-  read_stats(h, h->ws, a.pending_n, lvl, &res);
-  fold_stats(h, lvl, res, a.pending_n, a.pending_mode);
+  read_stats(h, h->ws, n, lvl, &res);
+  fold_stats(h, lvl, res, n, mode);
   return SN_OK;
 }
 
@@ -772,13 +783,14 @@ int fold_pending(sn_handle* h, bool wait) {
 // towers have joined, and runs again after a repeat so that its outputs belong to the arithmetic that returned).  blocking: the entry point returns after completion — the statistic is folded in before it
 // does and, under SN_PREC_AUTO, a call that left the fp16 tower's envelope is REPEATED in SN_PREC_F16X3.  Not blocking
 // (work only enqueued on the caller's stream): the statistic is folded in by a later call; an AUTO handle that has not had
-// its self-check yet blocks once.
+// its self-check yet blocks once.  A blocking call WAITS for the statistic of an enqueue-only call before it (its own forward
+// overwrites the pinned words: left pending, they would later be read as that earlier call's and divided by its n).
 template <class Post>
 int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* ddisp, int32_t* draw, bool want_cost,
                 bool blocking, Post post, bool want_conf = false) {
   const bool is_auto = h->precision == SN_PREC_AUTO;
   AutoCtl& a = h->actl;
-  int rc = fold_pending(h, false);
+  int rc = fold_pending(h, blocking);
   if (rc) return rc;
   int mode, calibrated;
   {
@@ -792,6 +804,7 @@ int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* d
   count_call(h, n);
   if (!blocking && !check) {
     HIP_TRY(h, hipEventRecord(h->ev_stats, st));
+    std::lock_guard<std::mutex> lk(h->mu);
     a.pending = true;
     a.pending_n = n;
     a.pending_mode = mode;

@@ -91,7 +91,12 @@ enum {
                          /* for 8 calls.  Calls that only enqueue work (device buffers + a caller */
                          /* stream) cannot be repeated: the first such call of a handle blocks    */
                          /* for the self-check, later ones act on the statistic of the call        */
-                         /* before (sn_auto_* below is the state machine, pure functions).         */
+                         /* before (sn_auto_* below is the state machine, pure functions).  The    */
+                         /* rule and the bound are PER CALL: a batch is judged on the mean         */
+                         /* residual of its pairs and keeps the MEAN EPE of its pairs below 1e-3   */
+                         /* px; one hard pair among calm ones can stay in fp16 above it (measured  */
+                         /* worst pair: 1.03e-3 px in a call of 8 at a mean of 4.6e-4 px,          */
+                         /* profiles/auto_sequences.txt).  A per-pair statistic is future work.    */
 };
 
 typedef struct sn_config {
@@ -164,11 +169,13 @@ int sn_get_refine_stats(sn_handle *h, sn_refine_stats *out);
  * SN_PREC_F16X3 back repeats the call.
  *   limit: envelope_px (the shape class's envelope = the budget over the WORST error-per-pixel of the measured weight
  *          draws) until the self-check has measured THIS model's error per pixel of residual (epe_per_px); then
- *          min(SN_AUTO_ENVELOPE_CAP * envelope_px, SN_AUTO_BUDGET_PX / epe_per_px).
+ *          min(envelope_px, SN_AUTO_BUDGET_PX / epe_per_px).  The self-check only TIGHTENS the limit: it measures one pair,
+ *          the first the handle sees in SN_PREC_F16, and the error per pixel of residual depends on the frame (a handle
+ *          calibrated on a calm frame used to trust a later frame with 3 times its residual, and returned an fp16 map at
+ *          1.03e-3 px for it: tests/test_gpu_auto_sequences.py, profiles/auto_sequences.txt).
  *   F16 -> F16X3: residual > limit (at once).  F16X3 -> F16: SN_AUTO_CALM_CALLS consecutive calls with residual <
  *   SN_AUTO_REENTRY * limit. */
 #define SN_AUTO_BUDGET_PX 0.85e-3   /* of north_star's 1e-3 px: the rest is SN_PREC_F16X3's own distance to the oracle */
-#define SN_AUTO_ENVELOPE_CAP 4.0    /* a measured slope may widen the class envelope by at most this factor            */
 #define SN_AUTO_REENTRY 0.8
 #define SN_AUTO_CALM_CALLS 8
 typedef struct sn_auto_state {

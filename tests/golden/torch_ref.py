@@ -64,17 +64,20 @@ def soft_argmin(cost):                   # (1,dl,h,w) -> (1,h,w)
     return (p * d).sum(1)
 
 
-def refine(blob, disp_up, img, dmax, prefix="ref"):    # (1,1,hp,wp), (1,3,hp,wp)
+def refine(blob, disp_up, img, dmax, prefix="ref", moved=None):    # (1,1,hp,wp), (1,3,hp,wp)
+    """`moved`: a list that receives dmax * r of this level, BEFORE the relu (what the refinement statistic sums)"""
     dt = disp_up.dtype
     x = torch.cat([disp_up / dmax, img], 1)
     x = lrelu(F.conv2d(x, _t(blob, prefix + ".in.w", dt), _t(blob, prefix + ".in.b", dt), padding=1))
     for i, dil in enumerate(spec.REF_DILATIONS):
         x = res_block(blob, f"{prefix}.res{i}", x, dil)
     r = F.conv2d(x, _t(blob, prefix + ".out.w", dt), _t(blob, prefix + ".out.b", dt), padding=1)
+    if moved is not None:
+        moved.append((dmax * r)[0, 0].numpy().copy())
     return F.relu(disp_up + dmax * r)
 
 
-def refine_multi(blob, low, img, dmax, levels):
+def refine_multi(blob, low, img, dmax, levels, moved=None):
     """Hierarchical refinement (`multi`): level k = levels-1 .. 0 works at 1/2^k resolution on
     the x2 bilinear upsample (values x2) of the level below (the soft-argmin map for the coarsest level), the left image
     average-pooled by 2^k, its own tower weights and D / 2^k as the disparity normalisation."""
@@ -83,14 +86,16 @@ def refine_multi(blob, low, img, dmax, levels):
     for k in range(levels - 1, -1, -1):
         up = F.interpolate(d, scale_factor=2, mode="bilinear", align_corners=False) * 2.0
         img_k = F.avg_pool2d(img, 2 ** k) if k else img
-        d = refine(blob, up, img_k, dmax / 2 ** k, spec.ref_prefix(k))
+        d = refine(blob, up, img_k, dmax / 2 ** k, spec.ref_prefix(k), moved)
         per_level.append(d[0, 0].numpy().copy())
     return d, per_level
 
 
-def forward(blob, in6: np.ndarray, dmax: int, dtype=torch.float32):
+def forward(blob, in6: np.ndarray, dmax: int, dtype=torch.float32, moved=None):
     """in6 int8 (6,h,w) -> dict(disp (h,w), disp_low, cost, fl, fr, levels), every array of `dtype`: float32 (the
-    committed goldens), or float64 with the int8 input / 128 and the fp32 weights widened exactly and no fp32 step"""
+    committed goldens), or float64 with the int8 input / 128 and the fp32 weights widened exactly and no fp32 step.
+    `moved`: a list that receives D_k r_k of every refinement level before its relu, over the level's padded map, coarsest
+    level first (refine)"""
     _, h, w = in6.shape
     hp, wp = spec.ceil16(h), spec.ceil16(w)
     x = torch.zeros(1, 6, hp, wp, dtype=dtype)
@@ -107,9 +112,9 @@ def forward(blob, in6: np.ndarray, dmax: int, dtype=torch.float32):
         per_level = []
         if levels == 1:
             up = F.interpolate(low[:, None], scale_factor=16, mode="bilinear", align_corners=False) * 16.0
-            disp = refine(blob, up, x[:, :3], dmax)
+            disp = refine(blob, up, x[:, :3], dmax, moved=moved)
         else:
-            disp, per_level = refine_multi(blob, low, x[:, :3], dmax, levels)
+            disp, per_level = refine_multi(blob, low, x[:, :3], dmax, levels, moved)
     return {"levels": per_level, "disp": disp[0, 0, :h, :w].numpy().copy(), "disp_low": low[0].numpy().copy(),
             "cost": cost[0].numpy().copy(), "fl": fl[0].numpy().copy(), "fr": fr[0].numpy().copy()}
 
@@ -135,7 +140,7 @@ def torch_threads(n=None):
         torch.set_num_threads(before)
 
 
-def truth(blob, in6: np.ndarray, dmax: int):
+def truth(blob, in6: np.ndarray, dmax: int, moved=None):
     """The float64 ground truth of one input: forward() in float64 -> dict(disp, disp_low, cost, fl, fr, levels)."""
     with torch_threads():
-        return forward(blob, in6, dmax, torch.float64)
+        return forward(blob, in6, dmax, torch.float64, moved)

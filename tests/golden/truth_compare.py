@@ -285,3 +285,136 @@ def run_engine(path, prec, x, x_other, levels):
         again = read_stages(eng, levels)
     live = {s: not np.array_equal(stages[s], again[s]) for s in stages}
     return disp, raw, st, stages, live
+
+
+# ---- call sequences on ONE handle (tests/test_auto_sequences.py, tests/test_gpu_auto_sequences.py) ---------------------------
+# The frames a stream of calls is made of, at SHAPE_S: name -> the `kind` of domain_input (the three textures are seeds of
+# synth.model_input_i8).  Two seed-0 models, one per shape class of sn_auto_envelope_px, at the head gain at which the
+# committed call list makes the default precision switch, re-enter and switch again (SEQ_GAIN: chosen from {2, 4, 8} after
+# one run that printed limit_px, profiles/auto_sequences.txt).  What "calm" and "hard" mean is a premise that
+# tests/test_auto_sequences.py asserts on the truth's own residual, per model.
+SEQ_KINDS = {"zero": "zero", "tex4": 4, "tex5": 5, "tex6": 6, "noise": "noise", "checker": "checker", "max": "max", "step": "step",
+             "min": "min"}
+SEQ_LEVELS = {"single": 1, "multi": MULTI}
+SEQ_GAIN = {"single": 2.0, "multi": 2.0}
+SEQ_CALM = ("zero", "tex4", "tex5", "tex6")
+SEQ_HARD = ("max", "step", "min")
+# (a) calm x2, hard, hard, calm x9, hard, calm, noise, hard.  The first self-check sees `zero`, the frame with the smallest
+# residual; the ninth calm call is the first one after the re-entry and carries the second self-check, on another frame.
+SEQ_CALLS = ("zero", "tex4", "max", "step",
+             "tex5", "tex6", "zero", "tex4", "tex5", "tex6", "zero", "tex4", "tex5",
+             "min", "tex6", "noise", "max")
+# (b) one list, started at `zero`, at a texture and at `min`: whatever frame calibrates the handle, the hard frame with the
+# smallest residual (`min` or `step`, the one a widened limit lets through first) is the next but one at the latest
+SEQ_ROTATED = ("zero", "min", "tex4", "step", "checker", "max")
+SEQ_ROTATIONS = ("zero", "tex4", "min")
+_seq_cache = {}
+
+
+def seq_blob(model):
+    return weights.synthetic(0, SEQ_LEVELS[model], head_gain=SEQ_GAIN[model])
+
+
+def seq_input(frame):
+    return domain_input(*SHAPE_S, SEQ_KINDS[frame])
+
+
+def truth_residual(moved, h, w):
+    """`moved` of torch_ref.truth (D_k r_k before the relu, coarsest level first) -> (level_px[k] for k = 0 .., residual_px) as
+    sn_get_refine_stats defines them: level 0 over the h x w output map, a coarse level over its whole padded map, and
+    residual_px = sum_k 2^k level_px[k]"""
+    lv = [float(np.abs(m[:h, :w] if k == 0 else m).mean()) for k, m in enumerate(moved[::-1])]
+    return lv, float(sum(v * 2 ** k for k, v in enumerate(lv)))
+
+
+def seq_point(model, frame):
+    """-> (x, truth, level_px, residual_px) of a frame under a model, the truth computed once per process"""
+    key = (model, frame)
+    if key not in _seq_cache:
+        w, h, d = SHAPE_S
+        x, moved = seq_input(frame), []
+        t = torch_ref.truth(seq_blob(model), x, d, moved)
+        _seq_cache[key] = (x, t, *truth_residual(moved, h, w))
+    return _seq_cache[key]
+
+
+AUTO_FIELDS = ("residual_px", "precision_last", "reruns", "switches", "selfcheck_epe_px", "selfcheck_residual_px")
+
+
+def replay(stats_per_call, levels=1, pure=None):
+    """What a handle of the default precision reported after each of its calls (dicts of sn_get_refine_stats with at least
+    AUTO_FIELDS, in call order, from the first call of the handle on) against the pure state machine sn_auto_init /
+    sn_auto_observe / sn_auto_limit_px: -> [(call index, what the handle did that the state machine would not have done)].
+
+    The model of a blocking call (run_forward, include/stereonet_hip.h): it runs in the mode the state is in; a call that
+    runs in F16 on a handle that has had no self-check since it last entered F16 carries one (epe_per_px = selfcheck_epe_px /
+    selfcheck_residual_px from then on); the call's residual is observed; a call that ran in F16 and is answered with F16X3
+    is repeated, so its map (precision_last) is F16X3's and reruns grows by one.
+    Optional keys of a record: "observed_px" — the residual the state machine saw where that is not the one reported (a
+    repeated call reports the repeat's residual; its first run's is what was observed); "pairs" (default 1: the self-check
+    pair is then the whole call, and selfcheck_residual_px must be the observed residual); "running_px", "limit_px",
+    "precision_selected" — compared when present.  `pure`: the library (default api.load_library())."""
+    import ctypes as C
+    from hobot_stereonet_amd import api
+    lib = pure or api.load_library()
+    s = api.SnAutoState()
+    assert lib.sn_auto_init(C.byref(s), levels) == 0
+    calibrated, reruns, check = False, 0, (-1.0, -1.0)
+    bad = []
+    for i, r in enumerate(stats_per_call):
+        seen = r.get("observed_px", r["residual_px"])
+        start = s.mode
+        got_check = (r["selfcheck_epe_px"], r["selfcheck_residual_px"])
+        if start == api.PREC_F16 and not calibrated:
+            entered = s.switches > 0
+            if not (got_check[0] >= 0 and got_check[1] >= 0) or (r.get("pairs", 1) == 1 and abs(got_check[1] - seen) > 1e-9):
+                bad.append((i, ("re-entry to F16 without a new self-check" if entered else "first F16 call without a self-check")
+                            + f": self-check residual {got_check[1]!r}, this call's {seen!r}"))
+            s.epe_per_px = got_check[0] / got_check[1] if got_check[1] > 1e-6 else 0.0
+            calibrated = True
+        elif got_check != check:
+            bad.append((i, f"self-check values changed ({check} -> {got_check}) in a call that owes none"))
+        check = got_check
+        limit, calm = lib.sn_auto_limit_px(C.byref(s)), s.calm
+        after = lib.sn_auto_observe(C.byref(s), seen)
+        if start == api.PREC_F16X3 and after == api.PREC_F16:
+            calibrated = False
+        repeat = start == api.PREC_F16 and after == api.PREC_F16X3
+        reruns += int(repeat)
+        want_last = api.PREC_NAMES[api.PREC_F16X3 if repeat else start]
+        if r["precision_last"] != want_last:
+            if repeat:
+                bad.append((i, f"map returned in {r['precision_last']} although residual {seen:.4f} > limit {limit:.4f} demanded the repeat"))
+            elif start == api.PREC_F16X3:
+                bad.append((i, f"map returned in {r['precision_last']}: re-entry after {calm} calm calls, "
+                               f"the state machine is in f16x3 (residual {seen:.4f}, limit {limit:.4f})"))
+            else:
+                bad.append((i, f"map returned in {r['precision_last']}, the state machine ran f16 (residual {seen:.4f}, limit {limit:.4f})"))
+        if r["switches"] != s.switches:
+            bad.append((i, f"{'extra' if r['switches'] > s.switches else 'missing'} switch: handle {r['switches']}, state machine "
+                           f"{s.switches} (residual {seen:.4f}, limit {limit:.4f})"))
+        if r["reruns"] != reruns:
+            bad.append((i, f"reruns {r['reruns']}, state machine {reruns}"))
+        if "precision_selected" in r and r["precision_selected"] != api.PREC_NAMES[s.mode]:
+            bad.append((i, f"precision_selected {r['precision_selected']}, state machine {api.PREC_NAMES[s.mode]}"))
+        if "running_px" in r and abs(r["running_px"] - s.running_px) > 1e-9:
+            bad.append((i, f"running_px {r['running_px']!r}, state machine {s.running_px!r}"))
+        if "limit_px" in r and abs(r["limit_px"] - lib.sn_auto_limit_px(C.byref(s))) > 1e-9:
+            bad.append((i, f"limit_px {r['limit_px']!r}, state machine {lib.sn_auto_limit_px(C.byref(s))!r}"))
+    return bad
+
+
+def trajectory_is_live(stats_per_call):
+    """-> (switch with a repeat, re-entry to f16 after it, second switch after that) as call indices, None where missing"""
+    up = back = again = None
+    prev = {"switches": 0, "reruns": 0, "precision_last": "f16"}
+    for i, r in enumerate(stats_per_call):
+        rose = r["switches"] > prev["switches"]
+        if up is None and rose and r["reruns"] > prev["reruns"] and r["precision_last"] == "f16x3":
+            up = i
+        elif up is not None and back is None and r["precision_last"] == "f16":
+            back = i
+        elif back is not None and again is None and rose and r["precision_last"] == "f16x3":
+            again = i
+        prev = r
+    return up, back, again
