@@ -20,7 +20,9 @@ from . import build as _build
 SN_MEM_HOST, SN_MEM_DEVICE = 0, 1
 PREC_DEFAULT, PREC_F16X3, PREC_F16, PREC_FP32, PREC_AUTO = 0, 1, 2, 3, 4      # include/stereonet_hip.h; 0 selects PREC_AUTO
 PREC_NAMES = {PREC_F16X3: "f16x3", PREC_F16: "f16", PREC_FP32: "fp32", PREC_AUTO: "auto"}
-ABI_VERSION = 3
+ABI_VERSION = 4
+SN_ERR_RANGE = -8      # include/stereonet_hip.h: the maps were written by an arithmetic that left the range of fp16
+F16_MAX = 65504.0      # the largest value the fp16 modes can store between two layers
 STAGES = ("features", "aggregate", "refine", "refine_conv", "total", "dominant")
 
 
@@ -44,7 +46,7 @@ class SnRefineStats(C.Structure):
                 ("calls", C.c_uint64), ("pairs", C.c_uint64), ("switches", C.c_uint64), ("reruns", C.c_uint64),
                 ("level_px", C.c_double * 4), ("residual_px", C.c_double), ("running_px", C.c_double),
                 ("envelope_px", C.c_double), ("limit_px", C.c_double), ("selfcheck_epe_px", C.c_double),
-                ("selfcheck_residual_px", C.c_double)]
+                ("selfcheck_residual_px", C.c_double), ("nonfinite_px", C.c_uint64 * 4), ("nonfinite_low_px", C.c_uint64)]
 
 
 class SnAutoState(C.Structure):
@@ -97,6 +99,20 @@ class StereoNetError(RuntimeError):
     def __init__(self, code: int, where: str, detail: str = ""):
         self.code = code
         super().__init__(f"{where}: {error_string(code)} (code {code}){': ' + detail if detail else ''}")
+
+
+class StereoNetRangeError(StereoNetError):
+    """SN_ERR_RANGE: the call ran and its maps were written, by an arithmetic in which activations left the range of fp16
+    (65504) — they are not to be used; run such a model with precision=PREC_FP32.  nonfinite_px[k]: pixels of refinement level
+    k whose disparity was not finite before the head's relu; nonfinite_low_px: low-resolution pixels with a non-finite
+    matching cost; outputs: what the call would have returned (StereoNetHIP.infer and the calls built like it), for
+    diagnosis only."""
+
+    def __init__(self, where: str, detail: str, nonfinite_px, nonfinite_low_px):
+        super().__init__(SN_ERR_RANGE, where, detail)
+        self.nonfinite_px = list(nonfinite_px)
+        self.nonfinite_low_px = int(nonfinite_low_px)
+        self.outputs = None
 
 
 _lib = None
@@ -259,9 +275,15 @@ class StereoNetHIP:
         self.flops_per_pair = float(info.flops_per_pair)
 
     # -- plumbing -----------------------------------------------------------------------------
-    def _check(self, rc: int, where: str):
+    def _check(self, rc: int, where: str, outputs=None):
         if rc != 0:
             detail = self._lib.sn_last_error(self._h).decode() if self._h else ""
+            if rc == SN_ERR_RANGE:
+                st = SnRefineStats()
+                self._lib.sn_get_refine_stats(self._h, C.byref(st))
+                err = StereoNetRangeError(where, detail, [int(v) for v in st.nonfinite_px][:max(1, st.levels)], st.nonfinite_low_px)
+                err.outputs = outputs
+                raise err
             raise StereoNetError(rc, where, detail)
 
     def close(self):
@@ -289,8 +311,9 @@ class StereoNetHIP:
         which arithmetic an SN_PREC_AUTO handle is in."""
         st = SnRefineStats()
         self._check(self._lib.sn_get_refine_stats(self._h, C.byref(st)), "sn_get_refine_stats")
-        d = {k: getattr(st, k) for k, _ in SnRefineStats._fields_ if k != "level_px"}
+        d = {k: getattr(st, k) for k, _ in SnRefineStats._fields_ if k not in ("level_px", "nonfinite_px")}
         d["level_px"] = [float(v) for v in st.level_px][:max(1, st.levels)]
+        d["nonfinite_px"] = [int(v) for v in st.nonfinite_px][:max(1, st.levels)]
         for k in ("precision", "precision_selected", "precision_last"):
             d[k] = PREC_NAMES.get(d[k], str(d[k]))
         return d
@@ -313,11 +336,10 @@ class StereoNetHIP:
             raise StereoNetError(-1, "infer", f"input shape {x.shape} != (n,6,{self.height},{self.width})")
         disp = np.empty((n, self.height, self.width), np.float32) if want_disp else None
         raw = np.empty((n, self.height, self.width), np.int32) if want_raw else None
+        out = ((disp[0] if disp is not None else None), (raw[0] if raw is not None else None)) if single else (disp, raw)
         self._check(self._lib.sn_infer_batch(self._h, n, x.ctypes.data, _np_ptr(raw), _np_ptr(disp), SN_MEM_HOST, None),
-                    "sn_infer_batch")
-        if single:
-            return (disp[0] if disp is not None else None), (raw[0] if raw is not None else None)
-        return disp, raw
+                    "sn_infer_batch", out)
+        return out
 
     # -- Run (device pointers, e.g. torch tensors' data_ptr(); stream = hipStream_t as int) ------
     def infer_device(self, n: int, in_ptr: int, raw_ptr: int, disp_ptr: int, stream: int = 0):

@@ -12,6 +12,7 @@ constexpr int kRefDil[kNRefRes] = {1, 2, 4, 8, 1, 1};
 constexpr float kOutScale = 2.60443857769133e-6f;   // stereonet_node.cpp:282
 constexpr double kWireFactor = 16.0 * 12.0;         // parser.cpp:86
 constexpr double kAutoEnvelopeSingle = 1.0, kAutoEnvelopeMulti = 2.9;   // sn_auto_envelope_px
+constexpr double kAutoResidualCap = 1e30;     // what sn_auto_observe folds in for a residual that is NaN, negative or +inf
 constexpr int kMaxPieceEvents = 64;
 constexpr int kMaxTowerStreams = 2;
 
@@ -78,11 +79,18 @@ struct RefLayerF16 {        // fp16 tower layer: 18 MFMA A-fragments + fp32 bias
 struct HeadLayer {          // C -> 1 layers (VALU kernels)
   float* w = nullptr;       // device [32][taps]
   float bias = 0.f;
+  // ref*.out, fp16 modes (upload_head_split): the head kernels split w into a hi / lo pair of fp16 in registers, and fp16 has
+  // no normal numbers below 2^-14 — a head whose weights are small (a tower that works at large activations) would lose them
+  // there.  wsplit = w * 2^e with e chosen at load, biassplit = bias * 2^e, unscale = 2^-e: the kernels get (wsplit, biassplit,
+  // dmax * unscale), so that dmax * (bias + sum) is the same number with every power of two exact.  e = 0 (wsplit == w)
+  // unless the largest |w| is below 2^-12.
+  float* wsplit = nullptr;
+  float biassplit = 0.f, unscale = 1.f;
   uint4* pfrag = nullptr;   // agg.out only, fp16 modes: split A fragments of the taps-as-M contraction [2][hi|lo][64] (k_agg_x3s_dma HEADP)
 };
 
 constexpr int kMaxLevels = 4, kMultiLevels = 4;              // hierarchical refinement: 1/8, 1/4, 1/2, 1
-constexpr int kStatWords = 8;                                // refinement statistic: [level 0..3] sum |D r|, [4] self-check sum |a - b|
+constexpr int kStatWords = 8;                                // refinement statistic: [level 0..3] sum |D r|, [4] self-check sum |a - b|; each with its non-finite count in the same lines
 constexpr size_t kStatU64 = (size_t)kStatWords * kStatWordStride;   // each word = kStatSlots partial sums in separate 128-byte lines
 constexpr int kTileCtrStride = 8 * 16;                       // uints per tower launch (one 64-B line per XCD)
 constexpr size_t kTileCtrBytes = (size_t)2 * 6 * kTileCtrStride * sizeof(unsigned);   // 2 * kNRefRes launches
@@ -158,6 +166,13 @@ struct Slot {                // async request slot (sn_submit / sn_wait)
 
 // SN_PREC_AUTO (include/stereonet_hip.h): the handle starts in SN_PREC_F16 and moves to SN_PREC_F16X3 when the refinement
 // statistic leaves the envelope inside which the fp16 tower keeps EPE <= 1e-3 px, or when the self-check says so.
+// The range check of one call (SN_ERR_RANGE, sn_kernels.hpp above stat_commit_line): non-finite pixels per refinement level
+// and in the low-resolution branch's soft-argmin.
+struct RangeCount {
+  unsigned long long level[4] = {}, low = 0;
+  bool any() const { return (level[0] | level[1] | level[2] | level[3] | low) != 0; }
+};
+
 struct AutoCtl {
   sn_auto_state st{};
   bool calibrated = false;       // the self-check (one pair in both arithmetics) has run since the handle last entered F16
@@ -165,6 +180,7 @@ struct AutoCtl {
   int pending_mode = 0, pending_n = 0;
   double selfcheck_epe = -1.0, selfcheck_res = -1.0;
   double last_level[4] = {}, last_res = 0.0;
+  RangeCount last_range;         // the range check's counts of the same call
   int last_mode = 0;
   uint64_t calls = 0, pairs = 0, reruns = 0;
 };
@@ -311,7 +327,7 @@ struct DevScope {
   void adopt(const Down0F16& l) { track(l.wfrag); }
   void adopt(const Down01W& l) { track(l.wfrag); track(l.bias); }
   void adopt(const RefLayerF16& l) { track(l.wfrag); track(l.bias); }
-  void adopt(const HeadLayer& l) { track(l.w); track(l.pfrag); }
+  void adopt(const HeadLayer& l) { track(l.w); track(l.pfrag); if (l.wsplit != l.w) track(l.wsplit); }
   ~DevScope() {
     for (void* q : ptrs) (void)hipFree(q);
   }

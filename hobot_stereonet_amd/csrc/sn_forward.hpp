@@ -164,10 +164,11 @@ int launch_head_softargmin(sn_handle* h, Workspace& ws, hipStream_t st, const fl
   float* const cost_out = want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr;
   if (want_conf)
     hipLaunchKernelGGL((k_head_softargmin<16, true>), dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w,
-                       h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out, ws.conf_low + (size_t)p0 * hl * wl);
+                       h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out, ws.conf_low + (size_t)p0 * hl * wl,
+                       ws.stats + kStatNonfiniteLow);
   else
     hipLaunchKernelGGL(k_head_softargmin<16>, dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w, h->aout.bias, Dl,
-                       hl, wl, npix, disp_low, cost_out, nullptr);
+                       hl, wl, npix, disp_low, cost_out, nullptr, ws.stats + kStatNonfiniteLow);
   HIP_TRY(h, hipGetLastError());
   return SN_OK;
 }
@@ -271,10 +272,10 @@ int lowres_slots(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, con
       if (want_conf)
         hipLaunchKernelGGL((k_softargmin_p<16, true>), dim3((npix + 63) / 64), dim3(64 * Dl), 0, st, ws.vol[(kNAgg - 1) & 1],
                            h->aout.bias, Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl, cost_out,
-                           ws.conf_low + (size_t)p0 * hl * wl);
+                           ws.conf_low + (size_t)p0 * hl * wl, ws.stats + kStatNonfiniteLow);
       else
         hipLaunchKernelGGL(k_softargmin_p<16>, dim3((npix + 63) / 64), dim3(64 * Dl), 0, st, ws.vol[(kNAgg - 1) & 1], h->aout.bias,
-                           Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl, cost_out, nullptr);
+                           Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl, cost_out, nullptr, ws.stats + kStatNonfiniteLow);
       HIP_TRY(h, hipGetLastError());
       return SN_OK;
     }
@@ -434,7 +435,7 @@ int refine_level(sn_handle* h, Workspace& ws, hipStream_t st, const Tower& T, fl
         if (dom) HIP_TRY(h, hipEventRecord(h->ev_dom[2 * h->dom_pairs++ + 1], st));
       } else if (tail && i == kNRefRes - 1) {
         if (pe) HIP_TRY(h, hipEventRecord(h->ev[5], st));          // the plain tower launches end here
-        StreamHeadArgs ha{T.rout.w, src, od, orw, T.rout.bias, dnorm, inv_q, sh, sw, H, W, ups, stat};
+        StreamHeadArgs ha{T.rout.wsplit, src, od, orw, T.rout.biassplit, dnorm * T.rout.unscale, inv_q, sh, sw, H, W, ups, stat};
         HIP_TRY(h, ref_block_stream_tail(st, T.rres16[i][0], T.rres16[i][1], g, tcu, x16, c, h->dump, ha));
       } else {
         const bool dom = pe && h->fuse_mode == 4 && stream_block_supports(kRefDil[i]) && h->dom_pairs < 6;
@@ -446,8 +447,8 @@ int refine_level(sn_handle* h, Workspace& ws, hipStream_t st, const Tower& T, fl
     }
     if (!tail) {
       if (pe) HIP_TRY(h, hipEventRecord(h->ev[5], st));
-      HIP_TRY(h, launch_head_final_f16(st, x3, x16, lo_slots, g, T.rout.w, T.rout.bias, src, sh, sw, H, W, dnorm, inv_q, ups,
-                                       od, orw, c, stat));
+      HIP_TRY(h, launch_head_final_f16(st, x3, x16, lo_slots, g, T.rout.wsplit, T.rout.biassplit, src, sh, sw, H, W,
+                                       dnorm * T.rout.unscale, inv_q, ups, od, orw, c, stat));
     }
   }
   HIP_TRY(h, hipGetLastError());
@@ -668,21 +669,36 @@ __global__ __launch_bounds__(256) void k_abs_diff_sum(const float* __restrict__ 
 
 // mean |D_k r_k| per level from a workspace's pinned statistic of an n-pair call (valid once the stream that ran forward()
 // has been synchronised): level 0 writes the H x W output maps, a coarse level its whole padded map
-inline unsigned long long stat_word(const Workspace& ws, int word) {      // the word's partial sums (refine_stat_commit)
+// `at`: 0 = the sums, kStatNonfinite / kStatNonfiniteLow = the range check's counts in the same lines
+inline unsigned long long stat_word(const Workspace& ws, int word, int at = 0) {      // the word's partial sums (refine_stat_commit)
   unsigned long long sum = 0;
-  for (int s = 0; s < kStatSlots; ++s) sum += ws.stats_host[(size_t)word * kStatWordStride + (size_t)s * kStatLine];
+  for (int s = 0; s < kStatSlots; ++s) sum += ws.stats_host[(size_t)word * kStatWordStride + (size_t)s * kStatLine + at];
   return sum;
 }
-void read_stats(const sn_handle* h, const Workspace& ws, int n, double* level_px, double* residual_px) {
+// A non-zero count of the range check makes the residual +inf: whatever the sums say, the fp16 storage is not to be trusted
+// with this call (sn_auto_observe then leaves SN_PREC_F16).
+void read_stats(const sn_handle* h, const Workspace& ws, int n, double* level_px, double* residual_px, RangeCount* range) {
   double res = 0.0;
+  *range = RangeCount{};
   for (int lv = 0; lv < kMaxLevels; ++lv) {
     level_px[lv] = 0.0;
     if (lv >= h->levels || n <= 0) continue;
     const double px = lv == 0 ? (double)h->H * h->W : (double)h->tw[lv].Hk * h->tw[lv].Wk;
     level_px[lv] = (double)stat_word(ws, lv) / (double)kStatScale / (px * n);
     res += level_px[lv] * (double)(1 << lv);
+    range->level[lv] = stat_word(ws, lv, kStatNonfinite);
   }
-  *residual_px = res;
+  if (n > 0) range->low = stat_word(ws, 0, kStatNonfiniteLow);
+  *residual_px = range->any() ? (double)INFINITY : res;
+}
+// what a blocking call whose maps come from a flagged arithmetic returns instead of SN_OK
+int range_result(sn_handle* h, const RangeCount& r) {
+  if (!r.any()) return SN_OK;
+  char msg[256];
+  snprintf(msg, sizeof msg, "activations left the range of fp16 (65504): non-finite pixels per level %llu/%llu/%llu/%llu, low-resolution "
+           "%llu; the maps are not valid — use SN_PREC_FP32 for this model", r.level[0], r.level[1], r.level[2], r.level[3], r.low);
+  set_err(h, msg);
+  return SN_ERR_RANGE;
 }
 
 // every call is counted when it is issued (the statistic of an enqueue-only call may be superseded by the next call's before
@@ -695,18 +711,21 @@ void count_call(sn_handle* h, int n) {
 
 // Folds the statistic of one finished call (run in `mode`) into the handle; returns the arithmetic the handle is in
 // afterwards.  observe = false: a repeated call (its first run has been observed already).
-int fold_stats(sn_handle* h, const double* level_px, double residual_px, int n, int mode, bool observe = true) {
+int fold_stats(sn_handle* h, const double* level_px, double residual_px, const RangeCount& range, int n, int mode,
+               bool observe = true) {
   std::lock_guard<std::mutex> lk(h->mu);
   AutoCtl& a = h->actl;
   for (int lv = 0; lv < kMaxLevels; ++lv) a.last_level[lv] = level_px[lv];
   a.last_res = residual_px;
+  a.last_range = range;
   a.last_mode = mode;
   if (!observe) {
     ++a.reruns;
     return a.st.mode;
   }
   if (h->precision != SN_PREC_AUTO) {
-    a.st.running_px = a.st.running_px < 0.0 ? residual_px : 0.75 * a.st.running_px + 0.25 * residual_px;
+    const double r = residual_px <= kAutoResidualCap ? residual_px : kAutoResidualCap;     // as sn_auto_observe
+    a.st.running_px = a.st.running_px < 0.0 ? r : 0.75 * a.st.running_px + 0.25 * r;
     return h->precision;
   }
   const int before = a.st.mode;
@@ -726,7 +745,10 @@ int auto_selfcheck(sn_handle* h, Workspace& ws, hipStream_t st, const int8_t* in
   }
   const bool prof = h->profiling;
   h->profiling = false;                  // the stage events belong to the caller's own forward()
+  double lvl[kMaxLevels], res = 0.0;
+  RangeCount range_x3, range;
   int rc = forward(h, ws, st, 1, in6_pair, h->chk[1], nullptr, false, SN_PREC_F16X3);
+  if (!rc && hipStreamSynchronize(st) == hipSuccess) read_stats(h, ws, 1, lvl, &res, &range_x3);   // (the next forward clears the words)
   if (!rc) rc = forward(h, ws, st, 1, in6_pair, h->chk[0], nullptr, false, SN_PREC_F16);    // last: the intermediates sn_dbg_read sees
   h->profiling = prof;
   if (rc) return rc;
@@ -736,8 +758,10 @@ int auto_selfcheck(sn_handle* h, Workspace& ws, hipStream_t st, const int8_t* in
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(ws.stats_host, ws.stats, kStatU64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIP_TRY(h, hipStreamSynchronize(st));
-  double lvl[kMaxLevels], res = 0.0;
-  read_stats(h, ws, 1, lvl, &res);
+  read_stats(h, ws, 1, lvl, &res, &range);
+  // a pair that left the range of fp16 in either arithmetic measures nothing (its NaN pixels were clamped to 0 in both maps:
+  // their difference would read as an EPE of 0): the handle stays uncalibrated
+  if (range.any() || range_x3.any() || stat_word(ws, 4, kStatNonfinite) != 0) return SN_OK;
   const double epe = (double)stat_word(ws, 4) / (double)kStatScale / (double)HW;
   std::lock_guard<std::mutex> lk(h->mu);
   AutoCtl& a = h->actl;
@@ -773,8 +797,9 @@ int fold_pending(sn_handle* h, bool wait) {
     mode = a.pending_mode;
   }
   double lvl[kMaxLevels], res = 0.0;
-  read_stats(h, h->ws, n, lvl, &res);
-  fold_stats(h, lvl, res, n, mode);
+  RangeCount range;
+  read_stats(h, h->ws, n, lvl, &res, &range);
+  fold_stats(h, lvl, res, range, n, mode);
   return SN_OK;
 }
 
@@ -782,6 +807,7 @@ int fold_pending(sn_handle* h, bool wait) {
 // (device-to-host copies; sn_infer_conf: the confidence kernel, which reads ws.conf_low — want_conf — and the maps after the
 // towers have joined, and runs again after a repeat so that its outputs belong to the arithmetic that returned).  blocking: the entry point returns after completion — the statistic is folded in before it
 // does and, under SN_PREC_AUTO, a call that left the fp16 tower's envelope is REPEATED in SN_PREC_F16X3.  Not blocking
+// A blocking call whose returned maps come from an arithmetic that left the range of fp16 returns SN_ERR_RANGE (range_result).
 // (work only enqueued on the caller's stream): the statistic is folded in by a later call; an AUTO handle that has not had
 // its self-check yet blocks once.  A blocking call WAITS for the statistic of an enqueue-only call before it (its own forward
 // overwrites the pinned words: left pending, they would later be read as that earlier call's and divided by its n).
@@ -812,17 +838,20 @@ int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* d
   }
   HIP_TRY(h, hipStreamSynchronize(st));
   double lvl[kMaxLevels], res = 0.0;
-  read_stats(h, h->ws, n, lvl, &res);
-  if (check && (rc = auto_selfcheck(h, h->ws, st, din))) return rc;
-  const int next = fold_stats(h, lvl, res, n, mode);
+  RangeCount range;
+  read_stats(h, h->ws, n, lvl, &res, &range);
+  // (a flagged call owes no self-check: there is nothing to calibrate on, and the next F16 call of the handle, if any, has it)
+  if (check && !range.any() && (rc = auto_selfcheck(h, h->ws, st, din))) return rc;
+  const int next = fold_stats(h, lvl, res, range, n, mode);
   if (is_auto && mode == SN_PREC_F16 && next == SN_PREC_F16X3) {
     if ((rc = forward(h, h->ws, st, n, din, ddisp, draw, want_cost, SN_PREC_F16X3, want_conf))) return rc;
     if ((rc = post())) return rc;
     HIP_TRY(h, hipStreamSynchronize(st));
-    read_stats(h, h->ws, n, lvl, &res);
-    fold_stats(h, lvl, res, n, SN_PREC_F16X3, false);
+    read_stats(h, h->ws, n, lvl, &res, &range);
+    fold_stats(h, lvl, res, range, n, SN_PREC_F16X3, false);
   }
-  return collect_profile(h);
+  if ((rc = collect_profile(h))) return rc;
+  return blocking ? range_result(h, range) : SN_OK;      // the counts of the arithmetic whose maps the caller holds
 }
 
 }  // namespace

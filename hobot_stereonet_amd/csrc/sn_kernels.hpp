@@ -223,25 +223,64 @@ struct UpScale {
 constexpr float kStatScale = 1048576.0f;
 constexpr int kStatSlots = 16, kStatLine = 16;              // partial sums per word; 64-bit words per 128-byte line
 constexpr int kStatWordStride = kStatSlots * kStatLine;     // 64-bit words between two statistic words (levels)
-__device__ __forceinline__ void refine_stat_commit(unsigned long long* stat, float lane_sum) {
+// Range check (SN_ERR_RANGE, include/stereonet_hip.h): the fp16 modes store activations as fp16 (or a hi/lo fp16 pair), which
+// end at 65504; a model whose activations pass that leaves inf / NaN in the tensors, the heads' clamp `d > 0 ? d : 0` turns a
+// NaN into a finite 0 and a cost plane at +inf drops out of the soft-argmin without a trace.  So every head form counts the
+// pixels whose d is not finite BEFORE the clamp (and writes 0, the wire's "invalid", for them: the clamp alone lets +inf
+// through) and every soft-argmin form the pixels with a non-finite cost.  Finite pixels are bit-unchanged.  The counts
+// live in the 128-byte lines the sums already own: slot line + kStatNonfinite is the count that belongs to the sum at slot
+// line + 0, and line + kStatNonfiniteLow of statistic word 0 is the low-resolution branch's — the memset and the copy of the
+// statistic carry them along.  Same vector atomics, issued ONLY when a count is non-zero: a finite run adds none.
+constexpr int kStatNonfinite = 1, kStatNonfiniteLow = 2;
+__device__ __forceinline__ bool stat_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }      // false for inf and NaN
+// wave-wide sum of a per-lane count that is zero in all but broken runs: one ballot when it is
+__device__ __forceinline__ unsigned stat_wave_count(unsigned lane_count) {
+  if (__ballot(lane_count != 0) == 0) return 0u;            // uniform
+#pragma unroll
+  for (int off = 32; off; off >>= 1) lane_count += __shfl_xor(lane_count, off);
+  return lane_count;
+}
+// one lane: the sum (a non-finite one is NOT cast — NaN would become 0 — but counted) and the count, into one slot line
+__device__ __forceinline__ void stat_commit_line(unsigned long long* line, float sum, unsigned nonfinite) {
+  if (stat_finite(sum)) atomicAdd(line, (unsigned long long)(sum * kStatScale + 0.5f));
+  else ++nonfinite;
+  if (nonfinite) atomicAdd(line + kStatNonfinite, (unsigned long long)nonfinite);
+}
+__device__ __forceinline__ void refine_stat_commit(unsigned long long* stat, float lane_sum, unsigned lane_nonfinite = 0u) {
 #pragma unroll
   for (int off = 32; off; off >>= 1) lane_sum += __shfl_xor(lane_sum, off);
+  const unsigned nonfinite = stat_wave_count(lane_nonfinite);
   if (stat != nullptr && (threadIdx.x & 63) == 0)
-    atomicAdd(stat + (blockIdx.x % kStatSlots) * kStatLine, (unsigned long long)(lane_sum * kStatScale + 0.5f));
+    stat_commit_line(stat + (blockIdx.x % kStatSlots) * kStatLine, lane_sum, nonfinite);
 }
 // every thread of a (<= 512-thread) workgroup calls this: one atomic per workgroup
-__device__ __forceinline__ void refine_stat_commit_block(unsigned long long* stat, float lane_sum) {
+__device__ __forceinline__ void refine_stat_commit_block(unsigned long long* stat, float lane_sum, unsigned lane_nonfinite = 0u) {
   __shared__ float s_stat[8];
+  __shared__ unsigned s_nonfinite[8];
 #pragma unroll
   for (int off = 32; off; off >>= 1) lane_sum += __shfl_xor(lane_sum, off);
-  if ((threadIdx.x & 63) == 0) s_stat[threadIdx.x >> 6] = lane_sum;
+  const unsigned nonfinite = stat_wave_count(lane_nonfinite);
+  if ((threadIdx.x & 63) == 0) {
+    s_stat[threadIdx.x >> 6] = lane_sum;
+    s_nonfinite[threadIdx.x >> 6] = nonfinite;
+  }
   __syncthreads();
   if (stat != nullptr && threadIdx.x == 0) {
     float sum = 0.f;
-    for (unsigned w = 0; w < (blockDim.x + 63) / 64; ++w) sum += s_stat[w];
+    unsigned bad = 0u;
+    for (unsigned w = 0; w < (blockDim.x + 63) / 64; ++w) {
+      sum += s_stat[w];
+      bad += s_nonfinite[w];
+    }
     const unsigned wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    atomicAdd(stat + (wg % kStatSlots) * kStatLine, (unsigned long long)(sum * kStatScale + 0.5f));
+    stat_commit_line(stat + (wg % kStatSlots) * kStatLine, sum, bad);
   }
+}
+// soft-argmin forms: `bad` = this lane's pixel has a non-finite cost; nf = the low-resolution count's slot 0 (nullable)
+__device__ __forceinline__ void lowres_nonfinite_commit(unsigned long long* nf, bool bad) {
+  const unsigned long long b = __ballot(bad);
+  if (nf != nullptr && b != 0 && (threadIdx.x & 63) == 0)
+    atomicAdd(nf + (blockIdx.x % kStatSlots) * kStatLine, (unsigned long long)__popcll(b));
 }
 
 // bilinear upsample, align_corners=False (half-pixel centres, edge clamp), values x factor
@@ -1060,14 +1099,15 @@ __device__ __forceinline__ float softargmin_conf(const float (&cost)[DLMAX], int
 // ------------------------------------------------------------------------------------------
 constexpr int kSamWaves = 16;
 // WANT_CONF: also writes the confidence plane conf_out [n][H][W] (softargmin_conf); the default instantiation never
-// touches conf_out and is, instruction for instruction, the kernel it was before the parameter existed.
+// touches conf_out.  nf: the range check's low-resolution count (lowres_nonfinite_commit).
 template <int DLMAX, bool WANT_CONF = false>
 __global__ __launch_bounds__(64 * kSamWaves) void k_head_softargmin(const float* __restrict__ vol,   // [n][Dl][32][H][W]
                                                                     const float* __restrict__ w,     // [32][27] (ci, dz*9+ky*3+kx)
                                                                     float bias, int Dl, int H, int W, int npix_total,
                                                                     float* __restrict__ disp_low,    // [n][H][W]
                                                                     float* __restrict__ cost_out,    // nullable [n][Dl][H][W]
-                                                                    float* __restrict__ conf_out) {  // WANT_CONF: [n][H][W]
+                                                                    float* __restrict__ conf_out,    // WANT_CONF: [n][H][W]
+                                                                    unsigned long long* __restrict__ nf) {   // nullable: pixels with a non-finite cost
   __shared__ float s_part[kSamWaves][DLMAX][64];
   constexpr int CPW = kC / kSamWaves;           // channels per wave
   const int lane = threadIdx.x & 63;
@@ -1129,6 +1169,11 @@ __global__ __launch_bounds__(64 * kSamWaves) void k_head_softargmin(const float*
     cost[d] = c;
   }
   // soft-argmin over the Dl planes (max-subtracted), in registers
+  bool bad = false;                      // (+inf drops out of the softmax as a zero weight: finite, and wrong)
+#pragma unroll
+  for (int d = 0; d < DLMAX; ++d)
+    if (d < Dl) bad = bad || !stat_finite(cost[d]);
+  lowres_nonfinite_commit(nf, live && bad);
   float m = -cost[0];
 #pragma unroll
   for (int d = 1; d < DLMAX; ++d)
@@ -1166,7 +1211,8 @@ __global__ __launch_bounds__(64 * DLMAX) void k_softargmin_p(const float* __rest
                                                           float bias, int Dl, int H, int W, int npix_total,
                                                           float* __restrict__ disp_low,     // [n][H][W]
                                                           float* __restrict__ cost_out,     // nullable [n][Dl][H][W]
-                                                          float* __restrict__ conf_out) {   // WANT_CONF: [n][H][W]
+                                                          float* __restrict__ conf_out,     // WANT_CONF: [n][H][W]
+                                                          unsigned long long* __restrict__ nf) {   // nullable: pixels with a non-finite cost
   __shared__ float s_cost[DLMAX][64];
   const int lane = threadIdx.x & 63;
   const int d = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);        // this wave's plane (blockDim = 64 * Dl)
@@ -1202,6 +1248,11 @@ __global__ __launch_bounds__(64 * DLMAX) void k_softargmin_p(const float* __rest
   float cost[DLMAX];
 #pragma unroll
   for (int k = 0; k < DLMAX; ++k) cost[k] = k < Dl ? s_cost[k][lane] : 0.f;
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < DLMAX; ++k)
+    if (k < Dl) bad = bad || !stat_finite(cost[k]);
+  lowres_nonfinite_commit(nf, live && bad);
   float m = -cost[0];
 #pragma unroll
   for (int k = 1; k < DLMAX; ++k)
@@ -1243,6 +1294,7 @@ __global__ __launch_bounds__(256) void k_head_final(const float* __restrict__ xi
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int n = blockIdx.z;
   float moved = 0.f;
+  unsigned bad = 0u;
   if (x < W && y < H) {
   const size_t plane = (size_t)Hp * Wp;
   const float* src = xin + (size_t)n * kC * plane;
@@ -1265,12 +1317,13 @@ __global__ __launch_bounds__(256) void k_head_final(const float* __restrict__ xi
   const float up = upsample_map(disp_low + (size_t)n * hl * wl, hl, wl, y, x, ups);
   float d = up + dmax * acc;
   moved = fabsf(dmax * acc);
-  d = d > 0.f ? d : 0.f;
+  bad = stat_finite(d) ? 0u : 1u;
+  d = (d > 0.f && bad == 0u) ? d : 0.f;          // a counted pixel leaves as 0 = invalid: +inf would pass the relu
   const size_t o = ((size_t)n * H + y) * W + x;
   if (out_disp) out_disp[o] = d;
   if (out_raw) out_raw[o] = (int32_t)__float2int_rn(d * inv_q);
   }
-  refine_stat_commit_block(stat, moved);
+  refine_stat_commit_block(stat, moved, bad);
 }
 
 
@@ -2259,6 +2312,7 @@ __global__ __launch_bounds__(256) void k_head_final_f16(const uint4* __restrict_
   __syncthreads();
   const float* dl = disp_low + (size_t)n * hl * wl;
   float moved = 0.f;
+  unsigned bad = 0u;
   for (int p = tid; p < T::TH * T::TWO; p += 256) {
     const int oy = p / T::TWO, ox = p - oy * T::TWO;
     const int y = y0 + oy, x = x0 + ox;
@@ -2271,12 +2325,14 @@ __global__ __launch_bounds__(256) void k_head_final_f16(const uint4* __restrict_
     const float up = upsample_map(dl, hl, wl, y, x, ups);
     float d = up + dmax * acc;
     moved += fabsf(dmax * acc);
-    d = d > 0.f ? d : 0.f;
+    const bool fin = stat_finite(d);
+    bad += fin ? 0u : 1u;
+    d = (d > 0.f && fin) ? d : 0.f;              // a counted pixel leaves as 0 = invalid: +inf would pass the relu
     const size_t o = ((size_t)n * H + y) * W + x;
     if (out_disp) out_disp[o] = d;
     if (out_raw) out_raw[o] = (int32_t)__float2int_rn(d * inv_q);
   }
-  refine_stat_commit_block(stat, moved);
+  refine_stat_commit_block(stat, moved, bad);
 }
 
 // K8 in SN_PREC_FP32 on the matrix core: the same taps-as-M contraction on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32):
@@ -2347,6 +2403,7 @@ __global__ __launch_bounds__(256) void k_head_final_mfma32(const float* __restri
   __syncthreads();
   const float* dl = disp_low + (size_t)n * hl * wl;
   float moved = 0.f;
+  unsigned bad = 0u;
   for (int p = tid; p < T::TH * T::TWO; p += 256) {
     const int oy = p / T::TWO, ox = p - oy * T::TWO;
     const int y = y0 + oy, x = x0 + ox;
@@ -2359,12 +2416,14 @@ __global__ __launch_bounds__(256) void k_head_final_mfma32(const float* __restri
     const float up = upsample_map(dl, hl, wl, y, x, ups);
     float d = up + dmax * acc;
     moved += fabsf(dmax * acc);
-    d = d > 0.f ? d : 0.f;
+    const bool fin = stat_finite(d);
+    bad += fin ? 0u : 1u;
+    d = (d > 0.f && fin) ? d : 0.f;              // a counted pixel leaves as 0 = invalid: +inf would pass the relu
     const size_t o = ((size_t)n * H + y) * W + x;
     if (out_disp) out_disp[o] = d;
     if (out_raw) out_raw[o] = (int32_t)__float2int_rn(d * inv_q);
   }
-  refine_stat_commit_block(stat, moved);
+  refine_stat_commit_block(stat, moved, bad);
 }
 
 }  // namespace sn

@@ -240,7 +240,7 @@ struct StreamHeadArgs {
   float bias, dmax, inv_q;
   int hl, wl, H, W;        // H, W: size of the output maps (<= g.H, g.W)
   UpScale ups;
-  unsigned long long* stat = nullptr;   // nullable: sum of |D r| over the written pixels (refine_stat_commit)
+  unsigned long long* stat = nullptr;   // nullable: sum of |D r| over the written pixels, count of non-finite ones (refine_stat_commit)
 };
 
 template <int DIL, int TW, int R, int NXS, int NWR, bool HEAD = false>
@@ -360,6 +360,7 @@ __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per
     };
     int p4 = 0;                           // HEAD: (4 q) mod PROWS, the P ring position of slot q
     float moved = 0.f;                    // HEAD: this lane's sum of |D r| (refinement statistic)
+    unsigned bad = 0u;                    // HEAD: this lane's written pixels whose d was not finite before the clamp
     dm.step(0, 0, f0, f1, sc.hsub);
     dma_issue(dm, 0);
     dm.step(1, 0, f0, f1, sc.hsub);
@@ -415,9 +416,11 @@ __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per
             const float up = v * ha.ups.mul;
             float d = up + ha.dmax * acc;
             const float mv = fabsf(ha.dmax * acc);
-            d = d > 0.f ? d : 0.f;
+            const unsigned nf = stat_finite(d) ? 0u : 1u;
+            d = (d > 0.f && nf == 0u) ? d : 0.f;     // a counted pixel leaves as 0 = invalid: +inf would pass the relu
             if (lane >= 1 && lane <= T::OW && X < ha.W) {
               moved += mv;
+              bad += nf;
               const size_t oi = ((size_t)fin_img * ha.H + o) * ha.W + X;
               if (ha.out_disp) ha.out_disp[oi] = d;
               if (ha.out_raw) ha.out_raw[oi] = (int32_t)__float2int_rn(d * ha.inv_q);
@@ -512,7 +515,7 @@ __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per
       qt = qt + 1 == T::NTS ? 0 : qt + 1;
       p4 = p4 + R >= T::PROWS ? p4 + R - T::PROWS : p4 + R;
     }
-    if constexpr (HEAD) refine_stat_commit(ha.stat, moved);
+    if constexpr (HEAD) refine_stat_commit(ha.stat, moved, bad);
     SN_STAMP_WG(1);
   } else {
     // ============================ conv2 waves: conv2 + residual + stores ============================

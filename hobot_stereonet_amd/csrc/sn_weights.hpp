@@ -159,6 +159,31 @@ int upload_head(sn_handle* h, const HostLayer& l, HeadLayer* out) {   // [1][32]
   return to_device(h, l.w, (size_t)kC * l.taps, &out->w);
 }
 
+// ref*.out for the head kernels of the fp16 modes (HeadLayer::wsplit): the power of two that brings the largest |w| into
+// [1/2, 1) when it is below 2^-12, none otherwise (a model that is fine today computes what it did, bit for bit).  Measured
+// reason (tests/test_gpu_truth64_range.py, profiles/activation_range.txt): a tower gauged by 2^12 has head weights of 6e-8, one
+// fp16 subnormal step, and SN_PREC_F16X3 showed a coherent 3.8e-5 px offset there.
+int upload_head_split(sn_handle* h, const HostLayer& l, HeadLayer* out) {
+  int rc = upload_head(h, l, out);
+  if (rc) return rc;
+  const size_t n = (size_t)kC * l.taps;
+  float top = 0.f;
+  for (size_t i = 0; i < n; ++i) top = fabsf(l.w[i]) > top ? fabsf(l.w[i]) : top;
+  out->wsplit = out->w;
+  out->biassplit = out->bias;
+  out->unscale = 1.f;
+  if (!(top > 0.f) || !(top < 0x1p-12f) || !std::isfinite(top)) return SN_OK;
+  int e = 0;
+  (void)frexpf(top, &e);                 // top = m * 2^e, m in [1/2, 1)
+  const float up = ldexpf(1.f, -e);
+  if (!std::isfinite(out->bias * up) || !std::isfinite(up)) return SN_OK;     // (a bias that large next to weights that small: leave it)
+  std::vector<float> ws(n);
+  for (size_t i = 0; i < n; ++i) ws[i] = l.w[i] * up;
+  out->biassplit = out->bias * up;
+  out->unscale = ldexpf(1.f, e);
+  return to_device(h, ws.data(), n, &out->wsplit);
+}
+
 // agg.out as the A operand of P[tap][pixel] = sum_c w[c][tap] y[c][pixel] (k_agg_x3s_dma<false, true>): row m = tap
 // (27 of 32 rows), K-step kk = channels 16 kk .. 16 kk + 15, lane (m, g) holds channels 16 kk + 8 g + e; hi / lo split
 int upload_agg_head_frag(sn_handle* h, const HostLayer& l, HeadLayer* out) {

@@ -57,6 +57,7 @@ const char* sn_strerror(int code) {
     case SN_ERR_NOMEM: return "out of memory";
     case SN_ERR_BUSY: return "no free task slot";
     case SN_ERR_TICKET: return "unknown ticket";
+    case SN_ERR_RANGE: return "activations left the range of fp16 (65504): the maps are not valid; use SN_PREC_FP32 for this model";
     default: return "unknown error";
   }
 }
@@ -339,7 +340,7 @@ int sn_create_prio(const char* model_file, const sn_config* cfg, int stream_prio
         if (want_x3 && (rc = upload_ref_f16x3(h, hl_, &T.rres16x3[i][j]))) return fail(rc);
         if (want_f16 && (rc = upload_ref_f16(h, hl_, sw.w_round_sum_preserving, &T.rres16[i][j]))) return fail(rc);
       }
-    if ((rc = upload_head(h, bw.next(1, kC, 9), &T.rout))) return fail(rc);
+    if ((rc = upload_head_split(h, bw.next(1, kC, 9), &T.rout))) return fail(rc);
   }
   if (bw.off != blob.size()) return fail(SN_ERR_FORMAT);
 
@@ -385,6 +386,7 @@ int sn_destroy(sn_handle* h) {
         hipFree(l.wfrag);
         hipFree(l.bias);
       }
+    if (T.rout.wsplit != T.rout.w) hipFree(T.rout.wsplit);
     hipFree(T.rout.w);
   }
   hipFree(h->dump);
@@ -497,7 +499,8 @@ double sn_auto_limit_px(const sn_auto_state* s) {
 
 int sn_auto_observe(sn_auto_state* s, double residual_px) {
   if (!s) return SN_ERR_ARG;
-  if (!(residual_px >= 0.0)) residual_px = 1e30;       // NaN / negative: nothing the fp16 tower should be trusted with
+  // NaN / negative / +inf (a call the range check flagged): nothing the fp16 tower should be trusted with
+  if (!(residual_px >= 0.0) || residual_px > kAutoResidualCap) residual_px = kAutoResidualCap;
   s->running_px = s->running_px < 0.0 ? residual_px : 0.75 * s->running_px + 0.25 * residual_px;
   const double lim = sn_auto_limit_px(s);
   if (s->mode == SN_PREC_F16) {
@@ -543,6 +546,8 @@ int sn_get_refine_stats(sn_handle* h, sn_refine_stats* out) {
   out->limit_px = sn_auto_limit_px(&a.st);
   out->selfcheck_epe_px = a.selfcheck_epe;
   out->selfcheck_residual_px = a.selfcheck_res;
+  for (int lv = 0; lv < kMaxLevels; ++lv) out->nonfinite_px[lv] = a.last_range.level[lv];
+  out->nonfinite_low_px = a.last_range.low;
   return SN_OK;
 }
 
@@ -822,16 +827,17 @@ int sn_wait(sn_handle* h, uint64_t ticket, float* infer_ms) {
   hipSetDevice(h->device);
   HIP_TRY(h, hipEventSynchronize(s->ev1));
   const size_t HW = (size_t)h->H * h->W;
+  RangeCount range;          // of the arithmetic whose maps are handed over
   {
     // the request's refinement statistic; SN_PREC_AUTO: self-check on the first request, and a request that left the fp16
     // tower's envelope is repeated in SN_PREC_F16X3 on its own stream before its maps are handed over
     double lvl[kMaxLevels], res = 0.0;
-    read_stats(h, s->ws, 1, lvl, &res);
+    read_stats(h, s->ws, 1, lvl, &res, &range);
     const bool is_auto = h->precision == SN_PREC_AUTO;
     int rc = SN_OK;
-    if (is_auto && s->mode_run == SN_PREC_F16 && (rc = auto_selfcheck(h, s->ws, s->stream, s->ws.in6))) return rc;
+    if (is_auto && s->mode_run == SN_PREC_F16 && !range.any() && (rc = auto_selfcheck(h, s->ws, s->stream, s->ws.in6))) return rc;
     count_call(h, 1);
-    const int next = fold_stats(h, lvl, res, 1, s->mode_run);
+    const int next = fold_stats(h, lvl, res, range, 1, s->mode_run);
     if (is_auto && s->mode_run == SN_PREC_F16 && next == SN_PREC_F16X3) {
       if ((rc = forward(h, s->ws, s->stream, 1, s->ws.in6, s->user_disp ? s->ws.out_disp : nullptr,
                         s->user_raw ? s->ws.out_raw : nullptr, false, SN_PREC_F16X3)))
@@ -840,8 +846,8 @@ int sn_wait(sn_handle* h, uint64_t ticket, float* infer_ms) {
       if (s->user_disp) HIP_TRY(h, hipMemcpyAsync(s->pin_disp, s->ws.out_disp, 4 * HW, hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(h, hipEventRecord(s->ev1, s->stream));
       HIP_TRY(h, hipEventSynchronize(s->ev1));
-      read_stats(h, s->ws, 1, lvl, &res);
-      fold_stats(h, lvl, res, 1, SN_PREC_F16X3, false);
+      read_stats(h, s->ws, 1, lvl, &res, &range);
+      fold_stats(h, lvl, res, range, 1, SN_PREC_F16X3, false);
     }
   }
   if (s->user_raw) memcpy(s->user_raw, s->pin_raw, 4 * HW);
@@ -856,7 +862,7 @@ int sn_wait(sn_handle* h, uint64_t ticket, float* infer_ms) {
     s->ticket = 0;
   }
   h->cv.notify_one();
-  return SN_OK;
+  return range_result(h, range);         // SN_ERR_RANGE: the maps were copied and the ticket is consumed
 }
 
 int sn_synchronize(sn_handle* h) {

@@ -45,11 +45,12 @@ extern "C" {
 
 typedef struct sn_handle sn_handle;
 
-/* Version of this binary interface.  3 = SN_PREC_AUTO exists and is what 0 ("default") selects, sn_io_info ends in
+/* Version of this binary interface.  4 = SN_ERR_RANGE exists and sn_refine_stats ends in nonfinite_px / nonfinite_low_px;
+ * 3 = SN_PREC_AUTO exists and is what 0 ("default") selects, sn_io_info ends in
  * precision_selected, sn_get_refine_stats / sn_auto_* exist; 2 = the SN_PREC_* numbering below with 0 = SN_PREC_F16 and
  * exact fp32 = 3; version 1 (round 1) had 0 = exact fp32.  A caller built against an older header compares
  * SN_ABI_VERSION with sn_abi_version() at start-up instead of silently running in another arithmetic. */
-#define SN_ABI_VERSION 3
+#define SN_ABI_VERSION 4
 int sn_abi_version(void);
 
 enum {
@@ -60,8 +61,19 @@ enum {
   SN_ERR_DEVICE = -4,    /* HIP runtime error or no gfx950 device                     */
   SN_ERR_NOMEM = -5,
   SN_ERR_BUSY = -6,      /* sn_submit: no free task slot within the timeout           */
-  SN_ERR_TICKET = -7     /* sn_wait: unknown or already-consumed ticket               */
+  SN_ERR_TICKET = -7,    /* sn_wait: unknown or already-consumed ticket               */
+  SN_ERR_RANGE = -8      /* the maps were written, but the arithmetic that computed them left the range of fp16: see below */
 };
+/* SN_ERR_RANGE.  SN_PREC_F16 and SN_PREC_F16X3 (and so SN_PREC_AUTO) store the 32-channel activations between layers as fp16,
+ * or as a hi/lo pair of fp16 — the low-resolution branch in both modes alike.  fp16 ends at 65504: a model whose activations
+ * pass that (a trained, BN-folded checkpoint is under no obligation not to) leaves inf / NaN in those tensors, and the relu of
+ * the heads would hand back a finite map of zeros — "infinitely far" on the wire.  Every head kernel therefore counts the
+ * pixels whose disparity is not finite before its relu, every soft-argmin kernel the pixels with a non-finite cost
+ * (sn_refine_stats: nonfinite_px, nonfinite_low_px; nothing feeds back into the maps).  A non-zero count makes the call's
+ * residual_px +inf, which takes an SN_PREC_AUTO handle to SN_PREC_F16X3 (a blocking call is repeated there), and a blocking
+ * call — sn_wait included — whose returned maps come from an arithmetic with a non-zero count returns SN_ERR_RANGE instead of
+ * SN_OK: the outputs are written, and they are not to be used.  A call that only enqueues work shows the counts in
+ * sn_get_refine_stats once its statistic is folded in.  Use SN_PREC_FP32 for such a model. */
 
 enum { SN_MEM_HOST = 0, SN_MEM_DEVICE = 1 };
 
@@ -155,12 +167,16 @@ typedef struct sn_refine_stats {
   uint64_t switches;                /* SN_PREC_AUTO: changes of arithmetic                                            */
   uint64_t reruns;                  /* SN_PREC_AUTO: calls repeated in SN_PREC_F16X3 before they returned              */
   double level_px[4];               /* last call: mean |D_k r_k| of level k (0 = full resolution), level-k pixels      */
-  double residual_px;               /* last call: sum_k 2^k level_px[k] = full-resolution pixels the refinement adds   */
+  double residual_px;               /* last call: sum_k 2^k level_px[k] = full-resolution pixels the refinement adds;  */
+                                    /* +inf when a count below is non-zero                                            */
   double running_px;                /* exponential mean of residual_px over the calls (weight 1/4)                    */
   double envelope_px;               /* SN_PREC_F16 is trusted while residual_px stays below this (shape class)         */
   double limit_px;                  /* the threshold in force (sn_auto_limit_px)                                      */
   double selfcheck_epe_px;          /* mean |F16 - F16X3| of the self-check pair, < 0 = not measured                   */
   double selfcheck_residual_px;     /* residual_px of that pair                                                       */
+  uint64_t nonfinite_px[4];         /* last call: pixels of level k whose disparity was not finite before the head's relu */
+                                    /* (+ partial sums of |D_k r_k| that were not): SN_ERR_RANGE                          */
+  uint64_t nonfinite_low_px;        /* last call: low-resolution pixels with a non-finite matching cost                  */
 } sn_refine_stats;
 int sn_get_refine_stats(sn_handle *h, sn_refine_stats *out);
 

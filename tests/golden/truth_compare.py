@@ -278,13 +278,24 @@ def run_engine(path, prec, x, x_other, levels):
     input and the stages again — a stage that the second input does not change is not a live readout"""
     from hobot_stereonet_amd import api
     with api.StereoNetHIP(path, precision=prec) as eng:
-        disp, raw = eng.infer(x)
+        disp, raw, returned = infer_flagged(eng, x)
         st = eng.refine_stats()
+        st["returned"] = returned
         stages = read_stages(eng, levels)
-        eng.infer(x_other)
+        infer_flagged(eng, x_other)
         again = read_stages(eng, levels)
     live = {s: not np.array_equal(stages[s], again[s]) for s in stages}
     return disp, raw, st, stages, live
+
+
+def infer_flagged(eng, x):
+    """eng.infer(x) -> (disp, raw, "SN_OK"), or the maps a call that returned SN_ERR_RANGE wrote and "SN_ERR_RANGE" (the
+    st["returned"] of run_engine: the activation-range tests judge what such a call handed over)"""
+    from hobot_stereonet_amd import api
+    try:
+        return (*eng.infer(x), "SN_OK")
+    except api.StereoNetRangeError as e:
+        return (*e.outputs, "SN_ERR_RANGE")
 
 
 # ---- call sequences on ONE handle (tests/test_auto_sequences.py, tests/test_gpu_auto_sequences.py) ---------------------------
@@ -353,7 +364,9 @@ def replay(stats_per_call, levels=1, pure=None):
     Optional keys of a record: "observed_px" — the residual the state machine saw where that is not the one reported (a
     repeated call reports the repeat's residual; its first run's is what was observed); "pairs" (default 1: the self-check
     pair is then the whole call, and selfcheck_residual_px must be the observed residual); "running_px", "limit_px",
-    "precision_selected" — compared when present.  `pure`: the library (default api.load_library())."""
+    "precision_selected" — compared when present.  A call whose range check fired (SN_ERR_RANGE) reports residual_px = +inf:
+    it is observed like any other (the state machine leaves F16 at once), owes no self-check and never re-enters F16.
+    `pure`: the library (default api.load_library())."""
     import ctypes as C
     from hobot_stereonet_amd import api
     lib = pure or api.load_library()
@@ -365,7 +378,11 @@ def replay(stats_per_call, levels=1, pure=None):
         seen = r.get("observed_px", r["residual_px"])
         start = s.mode
         got_check = (r["selfcheck_epe_px"], r["selfcheck_residual_px"])
-        if start == api.PREC_F16 and not calibrated:
+        if start == api.PREC_F16 and not calibrated and np.isinf(seen):
+            # a call the range check flagged (residual +inf) owes no self-check: there is nothing to calibrate on
+            if got_check != check:
+                bad.append((i, f"self-check values changed ({check} -> {got_check}) on a call whose range check fired"))
+        elif start == api.PREC_F16 and not calibrated:
             entered = s.switches > 0
             if not (got_check[0] >= 0 and got_check[1] >= 0) or (r.get("pairs", 1) == 1 and abs(got_check[1] - seen) > 1e-9):
                 bad.append((i, ("re-entry to F16 without a new self-check" if entered else "first F16 call without a self-check")
@@ -418,3 +435,168 @@ def trajectory_is_live(stats_per_call):
             again = i
         prev = r
     return up, back, again
+
+
+# ---- the activation range (tests/test_truth64_range.py, tests/test_gpu_truth64_range.py) -------------------------------------
+# The network is positively homogeneous between its first layer and its head (leaky relu, zero padding, residual adds and the
+# cost volume's difference all commute with a positive scale), so scaling the first layer and every bias after it by s and the
+# head's weights by 1/s leaves the function unchanged — with s = 2^k bit for bit, in float64 and in fp32 alike.  One truth and
+# one Refs judge every point of the axis; what changes is where the values the fp16 modes STORE between two layers sit in the
+# fp16 format.
+F16_MAX = 65504.0            # the largest finite fp16
+F16_MIN_NORMAL = 2.0 ** -14
+SUB_CAP = 0.05               # in range: at most this share of a tensor's non-zero values below F16_MIN_NORMAL (a cap on the input)
+
+
+def _scale(out, table, name, gain):
+    off, shape = table[name]
+    out[off:off + int(np.prod(shape))] *= np.float32(gain)
+
+
+def gauge(blob, levels, tower=1.0, low=1.0, only_level=None):
+    """-> a copy of `blob` that computes the same function with its stored activations scaled: the refinement towers' by
+    `tower` (every level, or `only_level` alone), the low-resolution branch's by `low`.  Powers of two are exact."""
+    out, table = blob.copy(), spec.offsets(levels)
+    if tower != 1.0:
+        for lv in (range(levels) if only_level is None else [only_level]):
+            p = spec.ref_prefix(lv)
+            _scale(out, table, p + ".in.w", tower)
+            _scale(out, table, p + ".in.b", tower)
+            for i in range(spec.N_REF_RES):
+                for j in (1, 2):
+                    _scale(out, table, f"{p}.res{i}.{j}.b", tower)
+            _scale(out, table, p + ".out.w", 1.0 / tower)
+    if low != 1.0:
+        _scale(out, table, "feat.down0.w", low)
+        _scale(out, table, "feat.down0.b", low)
+        names = [f"feat.down{i}" for i in range(1, spec.N_DOWN)] + [f"feat.res{i}.{j}" for i in range(spec.N_FEAT_RES) for j in (1, 2)]
+        for n in names + ["feat.out"] + [f"agg.conv{i}" for i in range(spec.N_AGG)]:
+            _scale(out, table, n + ".b", low)
+        _scale(out, table, "agg.out.w", 1.0 / low)
+    return out
+
+
+def range_profile(blob, x, d):
+    """The float64 truth of (blob, x) with every 32-channel tensor of it looked at on the way: the outputs of torch_ref's
+    convolutions and leaky relus, its residual sums and its cost volume (the head outputs and the cost are fp32 in every
+    mode of the engine: not counted).  -> (truth, profile); profile["tower"], profile["low"] and profile["levels"][k] (the
+    tower of refinement level k) are (A_max, sub): the largest |v|, and the largest per-tensor share of non-zero values
+    below 2^-14."""
+    import contextlib
+    import torch
+    stats, where = {}, ["low"]
+
+    def see(t):
+        if t.dim() >= 4 and t.shape[1] == spec.C:
+            a = t.detach().abs()
+            nz = a > 0
+            n = int(nz.sum())
+            share = float(((a < F16_MIN_NORMAL) & nz).sum()) / n if n else 0.0
+            for key in where:
+                m, s = stats.get(key, (0.0, 0.0))
+                stats[key] = (max(m, float(a.max())), max(s, share))
+        return t
+
+    orig = {"conv2d": torch_ref.F.conv2d, "conv3d": torch_ref.F.conv3d, "lrelu": torch_ref.lrelu, "cost_volume": torch_ref.cost_volume,
+            "res_block": torch_ref.res_block, "refine": torch_ref.refine}
+
+    def res_block(blob_, prefix, t, dil):               # torch_ref.res_block with its residual sum in view
+        dt = t.dtype
+        u = torch_ref.lrelu(torch_ref.F.conv2d(t, torch_ref._t(blob_, prefix + ".1.w", dt), torch_ref._t(blob_, prefix + ".1.b", dt),
+                                               padding=dil, dilation=dil))
+        u = torch_ref.F.conv2d(u, torch_ref._t(blob_, prefix + ".2.w", dt), torch_ref._t(blob_, prefix + ".2.b", dt), padding=dil,
+                               dilation=dil)
+        return torch_ref.lrelu(see(t + u))
+
+    def refine(blob_, disp_up, img, dmax, prefix="ref", moved=None):
+        level = 0 if prefix == "ref" else int(prefix[3:])
+        where[:] = ["tower", ("levels", level)]
+        try:
+            return orig["refine"](blob_, disp_up, img, dmax, prefix, moved)
+        finally:
+            where[:] = ["low"]
+
+    @contextlib.contextmanager
+    def hooked():
+        torch_ref.F.conv2d = lambda *a, **k: see(orig["conv2d"](*a, **k))
+        torch_ref.F.conv3d = lambda *a, **k: see(orig["conv3d"](*a, **k))
+        torch_ref.lrelu = lambda t: see(orig["lrelu"](t))
+        torch_ref.cost_volume = lambda *a: see(orig["cost_volume"](*a))
+        torch_ref.res_block, torch_ref.refine = res_block, refine
+        try:
+            yield
+        finally:
+            torch_ref.F.conv2d, torch_ref.F.conv3d = orig["conv2d"], orig["conv3d"]
+            for k in ("lrelu", "cost_volume", "res_block", "refine"):
+                setattr(torch_ref, k, orig[k])
+    with hooked():
+        t = torch_ref.truth(blob, x, d)
+    prof = {"tower": stats["tower"], "low": stats["low"], "levels": {k[1]: v for k, v in stats.items() if isinstance(k, tuple)}}
+    return t, prof
+
+
+def range_class(a_max, sub):
+    """One branch's (A_max, sub) against the fp16 format alone -> "in range" (one binade of margin below 65504: the fp16
+    paths' stored values differ from the truth's by parts in a thousand, never by a factor of two; at most SUB_CAP of a
+    tensor below the normal range), "overflows" (one binade above), or "guard band" (anything between)"""
+    if a_max <= F16_MAX / 2 and sub <= SUB_CAP:
+        return "in range"
+    if a_max >= 2 * F16_MAX:
+        return "overflows"
+    return "guard band"
+
+
+def point_class(prof):
+    """-> the class of a grid point: overflows if a branch does, in range if both are, else guard band"""
+    c = {range_class(*prof["tower"]), range_class(*prof["low"])}
+    return "overflows" if "overflows" in c else ("in range" if c == {"in range"} else "guard band")
+
+
+# name: (levels, k_tower, k_low, only_level); all at SHAPE_S, weights seed 0, input seed 4.  "top" points sit at the largest k
+# of an axis that is in range (tests/test_truth64_range.py computes that they do).  The tower peaks at 6.2 where the
+# low-resolution branch peaks at 10.8, so 2^14 takes the low branch past 2 x 65504 and leaves the tower (1.0e5) in the guard
+# band, and 2^13 leaves both there: the tower axes carry k = 15 and the low axis k = 14 as well, so that every axis has two
+# points that overflow by the rule of range_class.
+RANGE_INPUT = 4
+RANGE_TOWER_K = (-8, -4, 4, 8, 12, 13, 14, 15, 16)
+RANGE_LOW_K = (-8, -4, 4, 8, 11, 12, 13, 14, 16)
+RANGE_TOWER_K_MULTI = (-4, 8, 12, 14, 15, 16)
+RANGE_LOW_K_MULTI = (-4, 8, 11, 14, 16)
+RANGE_TOP = {"tower": 12, "low": 11}
+RANGE = {"S-k0": (1, 0, 0, None), "M-k0": (MULTI, 0, 0, None)}
+for _k in RANGE_TOWER_K:
+    RANGE[f"S-tower{_k:+d}"] = (1, _k, 0, None)
+for _k in RANGE_LOW_K:
+    RANGE[f"S-low{_k:+d}"] = (1, 0, _k, None)
+RANGE["S-both-top"] = (1, RANGE_TOP["tower"], RANGE_TOP["low"], None)
+for _k in RANGE_TOWER_K_MULTI:
+    RANGE[f"M-tower{_k:+d}"] = (MULTI, _k, 0, None)
+for _k in RANGE_LOW_K_MULTI:
+    RANGE[f"M-low{_k:+d}"] = (MULTI, 0, _k, None)
+RANGE["M-level2+14"] = (MULTI, 14, 0, 2)       # one coarse tower alone: 4.8e4, guard band
+RANGE["M-level2+16"] = (MULTI, 16, 0, 2)       # ... and past the end of the format
+RANGE_BASE = {1: "S-k0", MULTI: "M-k0"}
+_range_cache, _range_refs = {}, {}
+
+
+def range_blob(name):
+    levels, kt, kl, only = RANGE[name]
+    return gauge(weights.synthetic(0, levels), levels, 2.0 ** kt, 2.0 ** kl, only)
+
+
+def range_point(name):
+    """-> (blob, truth, profile) of a grid point, computed once per process"""
+    if name not in _range_cache:
+        blob = range_blob(name)
+        _range_cache[name] = (blob, *range_profile(blob, domain_input(*SHAPE_S, RANGE_INPUT), SHAPE_S[2]))
+    return _range_cache[name]
+
+
+def range_refs(oracle, levels):
+    """ONE Refs per model, from the k = 0 blob: the truth and both fp32 checkers are bit-identical along the gauge
+    (tests/test_truth64_range.py), so it judges every point.  -> (x, x_other, Refs)"""
+    if levels not in _range_refs:
+        x = domain_input(*SHAPE_S, RANGE_INPUT)
+        x_other = np.random.default_rng(2).integers(-128, 128, x.shape, dtype=np.int8)
+        _range_refs[levels] = (x, x_other, Refs(oracle, range_blob(RANGE_BASE[levels]), x, SHAPE_S[2]))
+    return _range_refs[levels]

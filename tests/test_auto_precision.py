@@ -122,3 +122,56 @@ def test_struct_layouts_match_the_header():
     assert fields("sn_refine_stats") == [f for f, _ in api.SnRefineStats._fields_]
     assert fields("sn_io_info") == [f for f, _ in api.SnIoInfo._fields_]
     assert fields("sn_config") == [f for f, _ in api.SnConfig._fields_]
+
+
+# ---- the range check (SN_ERR_RANGE): a call whose fp16 storage overflowed reports residual_px = +inf ---------------------------
+def test_a_flagged_residual_leaves_f16_and_never_comes_back(lib):
+    inf = float("inf")
+    s = _state(lib)
+    assert lib.sn_auto_observe(C.byref(s), inf) == api.PREC_F16X3 and s.switches == 1
+    assert s.running_px == 1e30                               # folded in as the cap, so that the mean can come back
+    for _ in range(3 * CALM):
+        assert lib.sn_auto_observe(C.byref(s), inf) == api.PREC_F16X3
+    assert s.switches == 1 and s.calm == 0
+    # one flagged call among calm ones resets the count like any call outside the band
+    for _ in range(CALM - 1):
+        lib.sn_auto_observe(C.byref(s), 0.1)
+    assert lib.sn_auto_observe(C.byref(s), inf) == api.PREC_F16X3 and s.calm == 0
+    for i in range(CALM):
+        assert lib.sn_auto_observe(C.byref(s), 0.1) == (api.PREC_F16 if i == CALM - 1 else api.PREC_F16X3)
+    assert s.running_px < 1e30
+
+
+def test_the_range_error_is_declared_bound_and_distinct(lib):
+    assert re.search(r"SN_ERR_RANGE\s*=\s*-8", HEADER) and api.SN_ERR_RANGE == -8
+    assert "65504" in api.error_string(-8) and "SN_PREC_FP32" in api.error_string(-8)
+    assert "65504" in HEADER and "Use SN_PREC_FP32 for such a model" in HEADER
+    assert [f for f, _ in api.SnRefineStats._fields_][-2:] == ["nonfinite_px", "nonfinite_low_px"]
+    assert C.sizeof(api.SnRefineStats) == 4 * 4 + 4 * 8 + 4 * 8 + 6 * 8 + 4 * 8 + 8
+    e = api.StereoNetRangeError("sn_infer_batch", "detail", [0, 0, 7, 0], 3)
+    assert isinstance(e, api.StereoNetError) and e.code == api.SN_ERR_RANGE
+    assert e.nonfinite_px == [0, 0, 7, 0] and e.nonfinite_low_px == 3 and e.outputs is None and "65504" in str(e)
+    assert api.F16_MAX == 65504.0
+
+
+def _rec(residual, last, reruns, switches, check=(-1.0, -1.0), **extra):
+    return {"residual_px": residual, "precision_last": last, "reruns": reruns, "switches": switches,
+            "selfcheck_epe_px": check[0], "selfcheck_residual_px": check[1], **extra}
+
+
+def test_replay_accepts_a_flagged_call_and_only_what_the_state_machine_does(lib):
+    """truth_compare.replay on what a handle of the default precision reports when the range check fires"""
+    import truth_compare as tc
+    inf = float("inf")
+    # first call flagged in F16 (no self-check is owed), repeated in F16X3 and flagged there too; then the handle stays
+    flagged = [_rec(inf, "f16x3", 1, 1), _rec(inf, "f16x3", 1, 1), _rec(inf, "f16x3", 1, 1)]
+    assert tc.replay(flagged, pure=lib) == []
+    # the repeat is finite (only the fp16 tower overflowed): the record carries what was observed
+    assert tc.replay([_rec(0.5, "f16x3", 1, 1, observed_px=inf), _rec(0.5, "f16x3", 1, 1)], pure=lib) == []
+    # teeth: a flagged call that stayed in F16, one that was not repeated, one that calibrated on the flagged pair
+    assert tc.replay([_rec(inf, "f16", 0, 0)], pure=lib)
+    assert tc.replay([_rec(inf, "f16x3", 0, 1)], pure=lib)
+    assert tc.replay([_rec(inf, "f16x3", 1, 1, check=(0.0, 0.3))], pure=lib)
+    # a calm first call calibrates as before, a later flagged one switches at once
+    ok = [_rec(0.3, "f16", 0, 0, check=(1e-4, 0.3)), _rec(inf, "f16x3", 1, 1, check=(1e-4, 0.3))]
+    assert tc.replay(ok, pure=lib) == []

@@ -28,6 +28,7 @@ def test_header_symbols_are_exported():
 def test_strerror_and_codes():
     assert api.error_string(0) == "ok"
     assert "gfx950" in api.error_string(-4)
+    assert "65504" in api.error_string(-8)      # SN_ERR_RANGE
     assert api.error_string(-99) == "unknown error"
 
 

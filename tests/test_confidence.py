@@ -43,7 +43,7 @@ def test_header_and_binding_agree():
     decls = [d.split() for d in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";") if d.strip()]
     assert [(t, n) for t, n in decls] == [("float", "min_conf")]
     assert api.SnConfParams._fields_ == [("min_conf", C.c_float)] and C.sizeof(api.SnConfParams) == 4
-    assert int(re.search(r"#define\s+SN_ABI_VERSION\s+(\d+)", HEADER).group(1)) == api.ABI_VERSION == 3      # purely additive
+    assert int(re.search(r"#define\s+SN_ABI_VERSION\s+(\d+)", HEADER).group(1)) == api.ABI_VERSION == 4      # 4: SN_ERR_RANGE and the range counts of sn_refine_stats; these structs are as in 3
     lib = api.load_library()
     for sym in ("sn_infer_conf", "sn_conf_mask"):
         assert re.search(rf"\bint {sym}\(", HEADER) and hasattr(lib, sym)

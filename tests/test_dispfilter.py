@@ -238,7 +238,7 @@ def test_filter_binding_agrees_with_the_header():
     ctype = {"float": C.c_float, "int": C.c_int}
     assert [(name, ctype[t]) for t, name in decls] == list(api.SnFilterParams._fields_)
     assert C.sizeof(api.SnFilterParams) == 12
-    assert int(re.search(r"#define\s+SN_ABI_VERSION\s+(\d+)", HEADER).group(1)) == api.ABI_VERSION == 3      # purely additive
+    assert int(re.search(r"#define\s+SN_ABI_VERSION\s+(\d+)", HEADER).group(1)) == api.ABI_VERSION == 4      # 4: SN_ERR_RANGE and the range counts of sn_refine_stats; these structs are as in 3
     proto = re.search(r"\bint sn_filter_raw\((.*?)\);", HEADER, re.S).group(1)
     params = [" ".join(t.split()) for t in proto.split(",")]
     assert params == ["sn_handle *h", "int n", "const int32_t *raw", "const sn_filter_params *p", "int32_t *out_raw",

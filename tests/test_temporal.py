@@ -213,7 +213,7 @@ def test_temporal_binding_agrees_with_the_header():
     ctype = {"float": C.c_float, "int": C.c_int}
     assert [(name, ctype[t]) for t, name in decls] == list(api.SnTemporalParams._fields_)
     assert C.sizeof(api.SnTemporalParams) == 16 and temporal.Params._fields == tuple(n for n, _ in api.SnTemporalParams._fields_)
-    assert int(re.search(r"#define\s+SN_ABI_VERSION\s+(\d+)", HEADER).group(1)) == api.ABI_VERSION == 3      # purely additive
+    assert int(re.search(r"#define\s+SN_ABI_VERSION\s+(\d+)", HEADER).group(1)) == api.ABI_VERSION == 4      # 4: SN_ERR_RANGE and the range counts of sn_refine_stats; these structs are as in 3
     assert "typedef struct sn_temporal sn_temporal;" in HEADER
     lib = api.load_library()
     protos = {
