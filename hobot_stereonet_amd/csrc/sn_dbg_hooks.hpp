@@ -594,12 +594,12 @@ int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, co
   HIP_TRY(h, memset_now(dr, 0xff, nout * 4));
   const float inv_q = (float)(1.0 / (kWireFactor * (double)kOutScale));
   const UpScale us{1.0f / (float)ups, (float)ups};
+  const HeadArgs ha{hd.w, dlow, dd, dr, hd.bias, dnorm, inv_q, sh, sw, h_out, w_out, us};
   if (form == 1) {
-    StreamHeadArgs ha{hd.w, dlow, dd, dr, hd.bias, dnorm, inv_q, sh, sw, h_out, w_out, us};
     HIP_TRY(h, ref_block_stream_tail(h->stream, L1, L2, g, h->num_cu, da, n, h->dump, ha));
   } else {
     HIP_TRY(h, ref_block_stream(h->stream, L1, L2, g, h->num_cu, 1, da, db, n, h->dump));
-    HIP_TRY(h, launch_head_final_f16(h->stream, false, db, 0, g, hd.w, hd.bias, dlow, sh, sw, h_out, w_out, dnorm, inv_q, us, dd, dr, n));
+    HIP_TRY(h, launch_head_final_f16(h->stream, false, db, 0, g, n, ha));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   HIP_TRY(h, hipMemcpy(out_disp, dd, nout * 4, hipMemcpyDeviceToHost));

@@ -155,74 +155,79 @@ void free_ws(Workspace* ws) {
 }
 
 // ---- the forward pass on device buffers ------------------------------------------------------------
-// k_head_softargmin on the last aggregation volume `v` of pairs [p0, p0 + m) (SN_PREC_FP32, SN_HEAD_FOLD=0 and the plain
-// volumes): disp_low, and cost / conf_low on request
-int launch_head_softargmin(sn_handle* h, Workspace& ws, hipStream_t st, const float* v, int p0, int m, bool want_cost,
-                           bool want_conf) {
+// The soft-argmin of pairs [p0, p0 + m), every precision; the one place that names its kernels.  folded: v holds the
+// partial sums P of the last aggregation layer (SN_HEAD_FOLD on the zero-bordered volumes: k_softargmin_p), otherwise its
+// volume, which k_head_softargmin contracts first.  Writes disp_low, and cost / conf_low on request.
+int launch_softargmin(sn_handle* h, Workspace& ws, hipStream_t st, const float* v, bool folded, int p0, int m, bool want_cost,
+                      bool want_conf) {
   const int hl = h->hl, wl = h->wl, Dl = h->Dl, npix = m * hl * wl;
   float* const disp_low = ws.disp_low + (size_t)p0 * hl * wl;
   float* const cost_out = want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr;
-  if (want_conf)
-    hipLaunchKernelGGL((k_head_softargmin<16, true>), dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w,
-                       h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out, ws.conf_low + (size_t)p0 * hl * wl,
-                       ws.stats + kStatNonfiniteLow);
-  else
-    hipLaunchKernelGGL(k_head_softargmin<16>, dim3((npix + 63) / 64), dim3(64 * kSamWaves), 0, st, v, h->aout.w, h->aout.bias, Dl,
-                       hl, wl, npix, disp_low, cost_out, nullptr, ws.stats + kStatNonfiniteLow);
+  float* const conf_low = want_conf ? ws.conf_low + (size_t)p0 * hl * wl : nullptr;
+  unsigned long long* const nf = ws.stats + kStatNonfiniteLow;
+  const dim3 grid((npix + 63) / 64);
+  if (folded) {
+    const auto kern = want_conf ? k_softargmin_p<16, true> : k_softargmin_p<16, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * Dl), 0, st, v, h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out, conf_low, nf);
+  } else {
+    const auto kern = want_conf ? k_head_softargmin<16, true> : k_head_softargmin<16, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * kSamWaves), 0, st, v, h->aout.w, h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out,
+                       conf_low, nf);
+  }
   HIP_TRY(h, hipGetLastError());
   return SN_OK;
 }
 
-// Low-resolution branch for pairs [p0, p0+m): Siamese features -> cost volume -> 3-D aggregation ->
-// soft-argmin.  Intermediate buffers are piece-local; disp_low (and cost, conf_low) are indexed by p0.  want_conf: the
-// soft-argmin epilogue also writes the confidence plane conf_low (sn_infer_conf); the default path launches the kernels it
-// always did.
 // Low-resolution branch of the fp16 modes on split-slot activations (SlotIn): every layer's epilogue writes the
 // hi/lo fp16 pair its consumer's split-operand MFMAs read, the weights-stationary kernel stages them as plain
 // 16-byte copies.  Only the tensors other kernels read stay fp32 NCHW: the feature map (cost-volume loader, parity
-// hook) and the last aggregation volume (soft-argmin head).
-int lowres_slots(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, const int8_t* in6, bool want_cost,
-                 bool want_conf, bool prof) {
-  const int Hp = h->Hp, Wp = h->Wp, hl = h->hl, wl = h->wl, Dl = h->Dl;
-  const size_t HW = (size_t)h->H * h->W;
-  const int8_t* in = in6 + (size_t)p0 * 6 * HW;
-  const int ncu = h->num_cu, ni = 2 * m;
-  auto U4 = [](float* p) { return reinterpret_cast<const uint4*>(p); };
+// hook) and the last aggregation volume (soft-argmin head).  Three stages; each runs on the zero-bordered layout and its
+// LDS-DMA kernel where alloc_ws made the tensors, on the plain one otherwise.
+inline const uint4* as_slots(const float* p) { return reinterpret_cast<const uint4*>(p); }
+
+// down-convs: int8 input `in` of ni images -> ws.lowp[0] (zero-bordered feature layout) or ws.low[0]
+int lowres_down_slots(sn_handle* h, Workspace& ws, hipStream_t st, const int8_t* in, int ni) {
+  const int Hp = h->Hp, Wp = h->Wp, ncu = h->num_cu;
+  const int k_first = h->fold_down01 ? 1 : 0;       // folded: down-convs 0 and 1 as one 13x13 stride-4 conv straight from the int8 input (sn_down01.hpp)
   if (ws.downp[1] != nullptr) {       // zero-bordered tensors between the down-convs, LDS-DMA kernel
     SlotGeom gin[3];
     for (int i = 0; i < 3; ++i) gin[i] = down_in_geom(Hp >> (i + 2), Wp >> (i + 2));
-    if (h->fold_down01)      // down-convs 0 and 1 as one 13x13 stride-4 conv straight from the int8 input (sn_down01.hpp)
+    if (h->fold_down01)
       HIP_TRY(h, launch_down01(st, h->down01, in, h->H, h->W, ni, Hp / 4, Wp / 4, ws.downp[1], gin[1], ncu));
     else
       HIP_TRY(h, launch_down0_f16(st, h->down0, h->down[0].bias, in, h->H, h->W, ni, Hp / 2, Wp / 2,
                                   reinterpret_cast<float*>(ws.downp[0]), ncu, &gin[0]));
-    for (int i = h->fold_down01 ? 1 : 0; i < 3; ++i) {
+    for (int i = k_first; i < 3; ++i) {
       const int Ho = Hp >> (i + 2), Wo = Wp >> (i + 2);
       const SlotGeom plain{Ho, Wo, 0, 0};
-      const FeatPad fp = feat_pad(hl, wl);
+      const FeatPad fp = feat_pad(h->hl, h->wl);
       const SlotGeom bordered{fp.PH, fp.PW, 1, 1};           // the feature layers' zero-bordered layout (sn_feat_dma.hpp)
       void* const last = ws.lowp[0] ? (void*)ws.lowp[0] : (void*)ws.low[0];
       HIP_TRY(h, launch_down_dma(st, h->down[i + 1], ws.downp[i], ni, Ho, Wo, i < 2 ? (void*)ws.downp[i + 1] : last,
                                  i < 2 ? gin[i + 1] : (ws.lowp[0] ? bordered : plain), false, ncu));
     }
-  } else {
+    return SN_OK;
+  }
   if (h->fold_down01)
     HIP_TRY(h, launch_down01(st, h->down01, in, h->H, h->W, ni, Hp / 4, Wp / 4, reinterpret_cast<uint4*>(ws.down[1]),
                              SlotGeom{Hp / 4, Wp / 4, 0, 0}, ncu));
   else
     HIP_TRY(h, launch_down0_f16(st, h->down0, h->down[0].bias, in, h->H, h->W, ni, Hp / 2, Wp / 2, ws.down[0], ncu));
-  {
-    float* src[3] = {ws.down[0], ws.down[1], ws.down[2]};
-    float* dst[3] = {ws.down[1], ws.down[2], ws.low[0]};
-    for (int i = h->fold_down01 ? 1 : 0; i < 3; ++i) {
-      const int Hi = Hp >> (i + 1), Wi = Wp >> (i + 1);
-      if ((h->ablate_x >> (kAblDown + i)) & 1u) HIP_TRY(h, zero_lo_slots(st, src[i], ni, (size_t)Hi * Wi));
-      SlotIn ld{U4(src[i]), 0, Hi, Wi};
-      HIP_TRY(h, (launch_conv_x3s<5, 2, 32, 4, 32, 32, 1, true, SlotIn>(st, h->down[i + 1], ld, ni, Hi / 2, Wi / 2, dst[i],
-                                                                       nullptr, false, ncu)));
-    }
+  float* const src[3] = {ws.down[0], ws.down[1], ws.down[2]};
+  float* const dst[3] = {ws.down[1], ws.down[2], ws.low[0]};
+  for (int i = k_first; i < 3; ++i) {
+    const int Hi = Hp >> (i + 1), Wi = Wp >> (i + 1);
+    if ((h->ablate_x >> (kAblDown + i)) & 1u) HIP_TRY(h, zero_lo_slots(st, src[i], ni, (size_t)Hi * Wi));
+    SlotIn ld{as_slots(src[i]), 0, Hi, Wi};
+    HIP_TRY(h, (launch_conv_x3s<5, 2, 32, 4, 32, 32, 1, true, SlotIn>(st, h->down[i + 1], ld, ni, Hi / 2, Wi / 2, dst[i],
+                                                                     nullptr, false, ncu)));
   }
-  }
+  return SN_OK;
+}
+
+// feature tower: six residual blocks + the output conv on ni images -> ws.feat (fp32 NCHW)
+int lowres_features_slots(sn_handle* h, Workspace& ws, hipStream_t st, int ni) {
+  const int hl = h->hl, wl = h->wl, ncu = h->num_cu;
   if (ws.lowp[0] != nullptr && ws.downp[1] != nullptr) {     // zero-bordered (x, t), LDS-DMA kernel
     const FeatPad fp = feat_pad(hl, wl);
     uint4 *x = ws.lowp[0], *t = ws.lowp[1];
@@ -234,79 +239,72 @@ int lowres_slots(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, con
       HIP_TRY(h, (launch_feat_dma<true, true>(st, h->fres[i][1], t, fp, ni, x, x, true, ncu)));     // in-place residual
     }
     HIP_TRY(h, (launch_feat_dma<false, false>(st, h->fout, x, fp, ni, ws.feat, nullptr, false, ncu)));
-  } else {
-  float* x = ws.low[0];
-  float* t = ws.low[1];
+    return SN_OK;
+  }
+  float *const x = ws.low[0], *const t = ws.low[1];
+  const SlotIn lx{as_slots(x), 0, hl, wl}, lt{as_slots(t), 0, hl, wl};
   for (int i = 0; i < kNFeatRes; ++i) {
-    SlotIn lx{U4(x), 0, hl, wl}, lt{U4(t), 0, hl, wl};
     if ((h->ablate_x >> (kAblFeat + 2 * i)) & 1u) HIP_TRY(h, zero_lo_slots(st, x, ni, (size_t)hl * wl));
     HIP_TRY(h, (launch_conv_x3s<3, 1, 32, 8, 16, 16, 2, true, SlotIn>(st, h->fres[i][0], lx, ni, hl, wl, t, nullptr, true, ncu)));
     if ((h->ablate_x >> (kAblFeat + 2 * i + 1)) & 1u) HIP_TRY(h, zero_lo_slots(st, t, ni, (size_t)hl * wl));
     HIP_TRY(h, (launch_conv_x3s<3, 1, 32, 8, 16, 16, 2, true, SlotIn>(st, h->fres[i][1], lt, ni, hl, wl, x, x, true, ncu)));
   }
-  {
-    if ((h->ablate_x >> (kAblFeat + 12)) & 1u) HIP_TRY(h, zero_lo_slots(st, x, ni, (size_t)hl * wl));
-    SlotIn lx{U4(x), 0, hl, wl};
-    HIP_TRY(h, (launch_conv_x3s<3, 1, 32, 8, 16, 16, 1, false, SlotIn>(st, h->fout, lx, ni, hl, wl, ws.feat, nullptr, false, ncu)));
-  }
-  }
-  if (prof) HIP_TRY(h, hipEventRecord(h->ev[1], st));
-  // cost volume -> slots (vol[1]), then every aggregation layer reads slots: agg0 vol[1] -> vol[0], agg1 -> vol[1], ...
-  // (zero-bordered volumes volp[] and the LDS-DMA kernel by default; the last layer writes fp32 into vol[] either way)
-  if (ws.volp[0] != nullptr) {
+  if ((h->ablate_x >> (kAblFeat + 12)) & 1u) HIP_TRY(h, zero_lo_slots(st, x, ni, (size_t)hl * wl));
+  HIP_TRY(h, (launch_conv_x3s<3, 1, 32, 8, 16, 16, 1, false, SlotIn>(st, h->fout, lx, ni, hl, wl, ws.feat, nullptr, false, ncu)));
+  return SN_OK;
+}
+
+// cost volume -> slots (vol[1]), then every aggregation layer reads slots: agg0 vol[1] -> vol[0], agg1 -> vol[1], ...; the
+// last layer writes fp32 into ws.vol[(kNAgg - 1) & 1] either way.  *folded: what it wrote are the output conv's partial
+// sums P [m Dl][27][hl][wl] (the contraction rides on the last layer's epilogue), not the volume.
+int lowres_aggregate_slots(sn_handle* h, Workspace& ws, hipStream_t st, int m, bool* folded) {
+  const int hl = h->hl, wl = h->wl, Dl = h->Dl, ncu = h->num_cu;
+  const long total = (long)m * Dl * 4 * hl * wl;
+  *folded = false;
+  if (ws.volp[0] != nullptr) {        // zero-bordered volumes, LDS-DMA kernel
     const VolPad g = vol_pad(Dl, hl, wl);
-    const long total = (long)m * Dl * 4 * hl * wl;
     hipLaunchKernelGGL(k_cost_slots_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws.feat, ws.volp[1], g, m);
-    for (int i = 0; i < kNAgg; ++i) {
-      const uint4* src = ws.volp[(i + 1) & 1];
-      if (i + 1 < kNAgg)
-        HIP_TRY(h, launch_agg_dma<true>(st, h->agg[i], src, g, m, ws.volp[i & 1], true, ncu));
-      else if (switches().head_fold && h->aout.pfrag)     // the output conv's contraction rides on this layer's epilogue
-        HIP_TRY(h, (launch_agg_dma<false, true>(st, h->agg[i], src, g, m, ws.vol[i & 1], true, ncu, h->aout.pfrag)));
-      else
-        HIP_TRY(h, launch_agg_dma<false>(st, h->agg[i], src, g, m, ws.vol[i & 1], true, ncu));
-    }
-    if (switches().head_fold && h->aout.pfrag) {       // soft-argmin on the partial sums P [m Dl][27][hl][wl]
-      const int npix = m * hl * wl;
-      float* const cost_out = want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr;
-      if (want_conf)
-        hipLaunchKernelGGL((k_softargmin_p<16, true>), dim3((npix + 63) / 64), dim3(64 * Dl), 0, st, ws.vol[(kNAgg - 1) & 1],
-                           h->aout.bias, Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl, cost_out,
-                           ws.conf_low + (size_t)p0 * hl * wl, ws.stats + kStatNonfiniteLow);
-      else
-        hipLaunchKernelGGL(k_softargmin_p<16>, dim3((npix + 63) / 64), dim3(64 * Dl), 0, st, ws.vol[(kNAgg - 1) & 1], h->aout.bias,
-                           Dl, hl, wl, npix, ws.disp_low + (size_t)p0 * hl * wl, cost_out, nullptr, ws.stats + kStatNonfiniteLow);
-      HIP_TRY(h, hipGetLastError());
-      return SN_OK;
-    }
-  } else {
-  {
-    const long total = (long)m * Dl * 4 * hl * wl;
-    hipLaunchKernelGGL(k_cost_slots, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws.feat,
-                       reinterpret_cast<uint4*>(ws.vol[1]), Dl, hl, wl, m);
-    if ((h->ablate_x >> kAblAgg) & 1u) HIP_TRY(h, zero_lo_slots(st, ws.vol[1], m * Dl, (size_t)hl * wl));
-    SlotIn lc{U4(ws.vol[1]), Dl, hl, wl};
-    HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, true, SlotIn>(st, h->agg[0], lc, m * Dl, hl, wl, ws.vol[0], nullptr, true, ncu)));
+    for (int i = 0; i + 1 < kNAgg; ++i)
+      HIP_TRY(h, launch_agg_dma<true>(st, h->agg[i], ws.volp[(i + 1) & 1], g, m, ws.volp[i & 1], true, ncu));
+    const int i = kNAgg - 1;
+    *folded = switches().head_fold && h->aout.pfrag;
+    if (*folded)
+      HIP_TRY(h, (launch_agg_dma<false, true>(st, h->agg[i], ws.volp[(i + 1) & 1], g, m, ws.vol[i & 1], true, ncu, h->aout.pfrag)));
+    else
+      HIP_TRY(h, launch_agg_dma<false>(st, h->agg[i], ws.volp[(i + 1) & 1], g, m, ws.vol[i & 1], true, ncu));
+    return SN_OK;
   }
-  for (int i = 1; i < kNAgg; ++i) {
-    if ((h->ablate_x >> (kAblAgg + i)) & 1u) HIP_TRY(h, zero_lo_slots(st, ws.vol[(i - 1) & 1], m * Dl, (size_t)hl * wl));
-    SlotIn lv{U4(ws.vol[(i - 1) & 1]), Dl, hl, wl};
+  hipLaunchKernelGGL(k_cost_slots, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws.feat,
+                     reinterpret_cast<uint4*>(ws.vol[1]), Dl, hl, wl, m);
+  for (int i = 0; i < kNAgg; ++i) {
+    float* const src = ws.vol[(i + 1) & 1];
+    if ((h->ablate_x >> (kAblAgg + i)) & 1u) HIP_TRY(h, zero_lo_slots(st, src, m * Dl, (size_t)hl * wl));
+    SlotIn lv{as_slots(src), Dl, hl, wl};
     if (i + 1 < kNAgg)
       HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, true, SlotIn>(st, h->agg[i], lv, m * Dl, hl, wl, ws.vol[i & 1], nullptr, true, ncu)));
     else
       HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, false, SlotIn>(st, h->agg[i], lv, m * Dl, hl, wl, ws.vol[i & 1], nullptr, true, ncu)));
   }
-  }
-  const float* v = ws.vol[(kNAgg - 1) & 1];
-  return launch_head_softargmin(h, ws, st, v, p0, m, want_cost, want_conf);
+  return SN_OK;
 }
 
+// Low-resolution branch for pairs [p0, p0+m): Siamese features -> cost volume -> 3-D aggregation ->
+// soft-argmin.  Intermediate buffers are piece-local; disp_low (and cost, conf_low) are indexed by p0.  want_conf: the
+// soft-argmin epilogue also writes the confidence plane conf_low (sn_infer_conf).
 int lowres(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, const int8_t* in6, bool want_cost, bool want_conf,
            bool prof) {
   const int Hp = h->Hp, Wp = h->Wp, hl = h->hl, wl = h->wl, Dl = h->Dl;
   const size_t HW = (size_t)h->H * h->W;
   const int8_t* in = in6 + (size_t)p0 * 6 * HW;
-  if (h->precision != SN_PREC_FP32) return lowres_slots(h, ws, st, p0, m, in6, want_cost, want_conf, prof);
+  bool folded = false;
+  if (h->precision != SN_PREC_FP32) {
+    int rc;
+    if ((rc = lowres_down_slots(h, ws, st, in, 2 * m))) return rc;
+    if ((rc = lowres_features_slots(h, ws, st, 2 * m))) return rc;
+    if (prof) HIP_TRY(h, hipEventRecord(h->ev[1], st));
+    if ((rc = lowres_aggregate_slots(h, ws, st, m, &folded))) return rc;
+    return launch_softargmin(h, ws, st, ws.vol[(kNAgg - 1) & 1], folded, p0, m, want_cost, want_conf);
+  }
   // SN_PREC_FP32: every layer on the exact-fp32 MFMA, fp32 NCHW activations
   // --- Siamese feature tower: images = 2m (left, right interleaved), shared weights ---
   {
@@ -336,8 +334,7 @@ int lowres(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, const int
     LoadVol3D lv{ws.vol[(i - 1) & 1], Dl, hl, wl};
     HIP_TRY(h, (launch_conv<3, 1, 1, 8, 4, 32>(st, h->agg[i], lv, m * Dl, hl, wl, ws.vol[i & 1], nullptr, true)));
   }
-  const float* v = ws.vol[(kNAgg - 1) & 1];
-  return launch_head_softargmin(h, ws, st, v, p0, m, want_cost, want_conf);
+  return launch_softargmin(h, ws, st, ws.vol[(kNAgg - 1) & 1], folded, p0, m, want_cost, want_conf);
 }
 
 // Pieces of one forward(): [p0, p0 + m), ws.pb pairs each.  Rounds 1-4 started with a short piece (2-4 pairs: the towers
@@ -355,57 +352,66 @@ inline int first_piece(const sn_handle* h, const Workspace& ws, int n) {
   return m < n ? m : n;
 }
 
-// One refinement level of one tower chunk (c pairs) on stream `st`.
-//   T          the level's tower (weights + geometry); rx / rt (fp32) or rx16 / rt16 (fp16 modes) its activation pair
-//   src        [c][sh][sw] map the level starts from, upsampled by `ups` (x16: soft-argmin map, single-scale; x2: the
-//              level below, hierarchical)
-//   img_src    int8 model input of the chunk (pyr = false) or the level's float image pyramid [c][3][Hk][Wk]
-//   H, W       size of the level's output map (the image for level 0, the whole padded level otherwise)
-//   dnorm      D / 2^level: disparity normalisation at the tower input and residual scale at its output
-//   od / orw   float map and (level 0 only) wire map, both nullable
-//   cap        pairs the hi region of the activation buffers holds: the lo tensor of SN_PREC_F16X3 starts behind it (c <= cap)
-//   mode       SN_PREC_F16 / SN_PREC_F16X3 / SN_PREC_FP32: the arithmetic of this call (an SN_PREC_AUTO handle holds two)
-//   stat       the level's refinement statistic (sum of |D r|, refine_stat_commit)
-int refine_level(sn_handle* h, Workspace& ws, hipStream_t st, const Tower& T, float* rx, float* rt, uint4* rx16,
-                 uint4* rt16, const float* src, int sh, int sw, UpScale ups, const void* img_src, bool pyr, int H, int W,
-                 float dnorm, float* od, int32_t* orw, unsigned* chunk_ctr, int c, int cap, bool pe, int mode,
-                 unsigned long long* stat) {
-  const int ncu = h->num_cu;
+// One refinement level of one tower chunk: what refine_level runs, filled by refine_coarse and refine_chunk.
+struct RefineCall {
+  const Tower* T;             // the level's tower (weights + geometry)
+  float* const* ref;          // its activation pair ref[0], ref[1]: fp32 ...
+  uint4* const* ref16;        // ... or the fp16 modes
+  const float* src;           // [c][sh][sw] map the level starts from
+  int sh, sw;                 // its size
+  UpScale ups;                // its upsample: x16 (the soft-argmin map, single-scale) or x2 (the level below, hierarchical)
+  const void* img_src;        // int8 model input of the chunk (pyr = false) or the level's float image pyramid [c][3][Hk][Wk]
+  bool pyr;
+  int H, W;                   // size of the level's output map (the image for level 0, the whole padded level otherwise)
+  float dnorm;                // D / 2^level: disparity normalisation at the tower input and residual scale at its output
+  float* od;                  // float map and
+  int32_t* orw;               // (level 0 only) wire map, both nullable
+  unsigned* chunk_ctr;        // the chunk's tile-queue block (take_ctr_block)
+  int c;                      // pairs of this chunk
+  int cap;                    // pairs the hi region of the activation buffers holds: the lo tensor of SN_PREC_F16X3 starts behind it (c <= cap)
+  bool pe;                    // record the profiling events of the tower
+  int mode;                   // SN_PREC_F16 / SN_PREC_F16X3 / SN_PREC_FP32: the arithmetic of this call (an SN_PREC_AUTO handle holds two)
+  unsigned long long* stat;   // the level's refinement statistic (sum of |D r|, refine_stat_commit)
+};
+
+int refine_level(sn_handle* h, Workspace& ws, hipStream_t st, const RefineCall& a) {
+  const Tower& T = *a.T;
+  const int ncu = h->num_cu, c = a.c;
   const int tcu = ws.tower_cu > 0 ? ws.tower_cu : ncu;      // workgroups of the streamed tower launches
   const int Hk = T.Hk, Wk = T.Wk;
+  const bool pe = a.pe;
   // The wire factor is the reference's literal 16 * 12 for EVERY dmax (parser.cpp:86, stereonet_node.cpp:288,
   // publisher_member_function.py:75): the unmodified consumers recover pixels whatever D the model was built for.
   const float inv_q = (float)(1.0 / (kWireFactor * (double)kOutScale));
-  if (mode == SN_PREC_FP32) {
-    LoadRefineIn ld{src, reinterpret_cast<const int8_t*>(img_src), sh, sw, H, W, Hk, Wk, 1.0f / dnorm, ups,
-                    pyr ? reinterpret_cast<const float*>(img_src) : nullptr};
+  if (a.mode == SN_PREC_FP32) {
+    LoadRefineIn ld{a.src, reinterpret_cast<const int8_t*>(a.img_src), a.sh, a.sw, a.H, a.W, Hk, Wk, 1.0f / a.dnorm, a.ups,
+                    a.pyr ? reinterpret_cast<const float*>(a.img_src) : nullptr};
     if (Hk * Wk <= 64 * 128)
-      HIP_TRY(h, (launch_conv<3, 1, 1, 4, 4, 32>(st, T.rin, ld, c, Hk, Wk, rx, nullptr, true)));
+      HIP_TRY(h, (launch_conv<3, 1, 1, 4, 4, 32>(st, T.rin, ld, c, Hk, Wk, a.ref[0], nullptr, true)));
     else
-      HIP_TRY(h, (launch_conv<3, 1, 1, 4, 8, 64>(st, T.rin, ld, c, Hk, Wk, rx, nullptr, true)));
+      HIP_TRY(h, (launch_conv<3, 1, 1, 4, 8, 64>(st, T.rin, ld, c, Hk, Wk, a.ref[0], nullptr, true)));
     if (pe) HIP_TRY(h, hipEventRecord(h->ev[4], st));
     for (int i = 0; i < kNRefRes; ++i) {
-      HIP_TRY(h, conv3x3(st, T.rres[i][0], rx, c, Hk, Wk, kRefDil[i], rt, nullptr, true, ncu));
-      HIP_TRY(h, conv3x3(st, T.rres[i][1], rt, c, Hk, Wk, kRefDil[i], rx, rx, true, ncu));
+      HIP_TRY(h, conv3x3(st, T.rres[i][0], a.ref[0], c, Hk, Wk, kRefDil[i], a.ref[1], nullptr, true, ncu));
+      HIP_TRY(h, conv3x3(st, T.rres[i][1], a.ref[1], c, Hk, Wk, kRefDil[i], a.ref[0], a.ref[0], true, ncu));
     }
     if (pe) HIP_TRY(h, hipEventRecord(h->ev[5], st));
+    const HeadArgs ha{T.rout.w, a.src, a.od, a.orw, T.rout.bias, a.dnorm, inv_q, a.sh, a.sw, a.H, a.W, a.ups, a.stat};
     // head on the fp32 MFMA with the nine taps as M (k_head_final_mfma32); SN_HEAD_MFMA32=0 keeps the per-pixel kernel (A/B)
     if (switches().head_mfma32) {
       constexpr int TH = 14;               // 16-row P window: 32 segments, 8 per wave (TH = 6 measured the same 41 us without the statistic)
       using HT = HeadTile<TH>;
-      const int tiles_x = (W + HT::TWO - 1) / HT::TWO, tiles_y = (H + TH - 1) / TH;
-      hipLaunchKernelGGL(k_head_final_mfma32<TH>, dim3((unsigned)(tiles_x * tiles_y * c)), dim3(256), HT::LDS_BYTES, st, rx,
-                         T.rout.w, T.rout.bias, src, sh, sw, Hk, Wk, H, W, dnorm, inv_q, od, orw, tiles_x, tiles_y, ups, stat);
+      const int tiles_x = (a.W + HT::TWO - 1) / HT::TWO, tiles_y = (a.H + TH - 1) / TH;
+      hipLaunchKernelGGL(k_head_final_mfma32<TH>, dim3((unsigned)(tiles_x * tiles_y * c)), dim3(256), HT::LDS_BYTES, st, a.ref[0],
+                         Hk, Wk, tiles_x, tiles_y, ha);
     } else {
-      dim3 grid((W + 63) / 64, (H + 3) / 4, c);
-      hipLaunchKernelGGL(k_head_final, grid, dim3(256), 0, st, rx, T.rout.w, T.rout.bias, src, sh, sw, Hk, Wk, H, W, dnorm,
-                         inv_q, od, orw, ups, stat);
+      dim3 grid((a.W + 63) / 64, (a.H + 3) / 4, c);
+      hipLaunchKernelGGL(k_head_final, grid, dim3(256), 0, st, a.ref[0], Hk, Wk, ha);
     }
   } else {
     // fp16 tower: ref.in writes the NCHW8c fp16 tensor, the 12 C->C convs run on v_mfma_f32_32x32x16_f16, the head
     // reads fp16 and finishes in fp32
-    uint4* x16 = rx16;
-    uint4* t16 = rt16;
+    uint4 *x16 = a.ref16[0], *t16 = a.ref16[1];
     if (pe) h->dom_pairs = 0;
     // Consecutive launches of a tower walk their tiles in OPPOSITE directions (g.rev): a launch then starts on the part
     // of the tensor its predecessor wrote LAST — what a cache that is slightly too small for the chunk still holds —
@@ -418,15 +424,17 @@ int refine_level(sn_handle* h, Workspace& ws, hipStream_t st, const Tower& T, fl
     int launch_no = 0;
     auto flip = [&]() { g.rev = rev_env ? (launch_no++ & 1) : 0; };
     flip();
-    const bool x3 = mode == SN_PREC_F16X3;
-    const size_t lo_slots = ref16_slots(g, cap) + ref_slack(g);         // hi tensor -> lo tensor (F16X3); cap = pairs the buffers hold
-    HIP_TRY(h, launch_refin_f16(st, T.refin, T.rin.bias, src, img_src, pyr, sh, sw, H, W, 1.0f / dnorm, ups, g, c, x16, x3,
-                                lo_slots * 16, ncu));
+    const bool x3 = a.mode == SN_PREC_F16X3;
+    const size_t lo_slots = ref16_slots(g, a.cap) + ref_slack(g);         // hi tensor -> lo tensor (F16X3); cap = pairs the buffers hold
+    HIP_TRY(h, launch_refin_f16(st, T.refin, T.rin.bias, a.src, a.img_src, a.pyr, a.sh, a.sw, a.H, a.W, 1.0f / a.dnorm, a.ups, g,
+                                c, x16, x3, lo_slots * 16, ncu));
     if (pe) HIP_TRY(h, hipEventRecord(h->ev[4], st));
     flip();
+    const HeadArgs ha{T.rout.wsplit, a.src, a.od, a.orw, T.rout.biassplit, a.dnorm * T.rout.unscale, inv_q, a.sh, a.sw,
+                      a.H, a.W, a.ups, a.stat};
     // tail form: the streamed last block computes the head too (its output tensor is never written, no head launch)
     const bool last_streamed = h->fuse_mode == 4 && stream_block_supports(kRefDil[kNRefRes - 1]);
-    const bool tail = !x3 && last_streamed && h->tail_fuse && kRefDil[kNRefRes - 1] == 1 && ups.rs <= 0.5f;
+    const bool tail = !x3 && last_streamed && h->tail_fuse && kRefDil[kNRefRes - 1] == 1 && a.ups.rs <= 0.5f;
     for (int i = 0; i < kNRefRes; ++i) {
       if (x3) {
         const bool dom = pe && stream_x3_supports(kRefDil[i]) && h->dom_pairs < 6;
@@ -435,20 +443,18 @@ int refine_level(sn_handle* h, Workspace& ws, hipStream_t st, const Tower& T, fl
         if (dom) HIP_TRY(h, hipEventRecord(h->ev_dom[2 * h->dom_pairs++ + 1], st));
       } else if (tail && i == kNRefRes - 1) {
         if (pe) HIP_TRY(h, hipEventRecord(h->ev[5], st));          // the plain tower launches end here
-        StreamHeadArgs ha{T.rout.wsplit, src, od, orw, T.rout.biassplit, dnorm * T.rout.unscale, inv_q, sh, sw, H, W, ups, stat};
         HIP_TRY(h, ref_block_stream_tail(st, T.rres16[i][0], T.rres16[i][1], g, tcu, x16, c, h->dump, ha));
       } else {
         const bool dom = pe && h->fuse_mode == 4 && stream_block_supports(kRefDil[i]) && h->dom_pairs < 6;
         if (dom) HIP_TRY(h, hipEventRecord(h->ev_dom[2 * h->dom_pairs], st));
         HIP_TRY(h, ref_block_f16(st, T.rres16[i][0], T.rres16[i][1], g, tcu, kRefDil[i], &x16, &t16, c,
-                                 chunk_ctr + 2 * i * kTileCtrStride, h->fuse_mode, h->dump, rev_env));
+                                 a.chunk_ctr + 2 * i * kTileCtrStride, h->fuse_mode, h->dump, rev_env));
         if (dom) HIP_TRY(h, hipEventRecord(h->ev_dom[2 * h->dom_pairs++ + 1], st));
       }
     }
     if (!tail) {
       if (pe) HIP_TRY(h, hipEventRecord(h->ev[5], st));
-      HIP_TRY(h, launch_head_final_f16(st, x3, x16, lo_slots, g, T.rout.wsplit, T.rout.biassplit, src, sh, sw, H, W,
-                                       dnorm * T.rout.unscale, inv_q, ups, od, orw, c, stat));
+      HIP_TRY(h, launch_head_final_f16(st, x3, x16, lo_slots, g, c, ha));
     }
   }
   HIP_TRY(h, hipGetLastError());
@@ -502,14 +508,18 @@ int refine_coarse(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, co
     const int rbk = chunk_pairs(h, ws, mode, lv);
     for (int q = 0; q < m; q += rbk) {
       const int c = (m - q) < rbk ? (m - q) : rbk;
-      unsigned* ctr = nullptr;
-      int rc = take_ctr_block(h, ws, ctr_block, &ctr);
+      RefineCall a{};
+      int rc = take_ctr_block(h, ws, ctr_block, &a.chunk_ctr);
       if (rc) return rc;
-      rc = refine_level(h, ws, st, T, ws.ref_lv[lv][0], ws.ref_lv[lv][1], ws.ref16_lv[lv][0], ws.ref16_lv[lv][1],
-                                  src + (size_t)q * sh * sw, sh, sw, UpScale{0.5f, 2.0f}, ws.pyr[lv] + (size_t)q * 3 * HWk, true,
-                                  T.Hk, T.Wk, dnorm, ws.lvl_disp[lv] + (size_t)q * HWk, nullptr, ctr, c, ws.rbk[lv], false, mode,
-                                  ws.stats + (size_t)lv * kStatWordStride);
-      if (rc) return rc;
+      a.T = &T;
+      a.ref = ws.ref_lv[lv], a.ref16 = ws.ref16_lv[lv];
+      a.src = src + (size_t)q * sh * sw, a.sh = sh, a.sw = sw, a.ups = UpScale{0.5f, 2.0f};
+      a.img_src = ws.pyr[lv] + (size_t)q * 3 * HWk, a.pyr = true;
+      a.H = T.Hk, a.W = T.Wk, a.dnorm = dnorm;
+      a.od = ws.lvl_disp[lv] + (size_t)q * HWk;       // (no wire map, no profiling events below level 0)
+      a.c = c, a.cap = ws.rbk[lv], a.mode = mode;
+      a.stat = ws.stats + (size_t)lv * kStatWordStride;
+      if ((rc = refine_level(h, ws, st, a))) return rc;
     }
     src = ws.lvl_disp[lv];
     sh = T.Hk;
@@ -526,23 +536,25 @@ int refine_chunk(sn_handle* h, Workspace& ws, hipStream_t st, int sidx, int* ctr
                  const int8_t* in6, float* out_disp, int32_t* out_raw, bool pe, int mode) {
   const int hl = h->hl, wl = h->wl;
   const size_t HW = (size_t)h->H * h->W;
-  float* od = out_disp ? out_disp + (size_t)q0 * HW : nullptr;
-  int32_t* orw = out_raw ? out_raw + (size_t)q0 * HW : nullptr;
-  const int8_t* in_chunk = in6 + (size_t)q0 * 6 * HW;
-  unsigned* ctr = nullptr;
-  const int rc0 = take_ctr_block(h, ws, ctr_block, &ctr);
-  if (rc0) return rc0;
-  const float* src = ws.disp_low + (size_t)q0 * hl * wl;
-  int sh = hl, sw = wl;
-  UpScale ups{1.0f / 16.0f, 16.0f};
+  RefineCall a{};
+  if (const int rc = take_ctr_block(h, ws, ctr_block, &a.chunk_ctr)) return rc;
+  a.T = &h->tw[0];
+  a.ref = &ws.ref[2 * sidx], a.ref16 = &ws.ref16[2 * sidx];
   if (h->levels > 1) {
-    sh = h->tw[1].Hk;
-    sw = h->tw[1].Wk;
-    src = ws.lvl_disp[1] + (size_t)(q0 - p0) * sh * sw;
-    ups = UpScale{0.5f, 2.0f};
+    a.sh = h->tw[1].Hk, a.sw = h->tw[1].Wk;
+    a.src = ws.lvl_disp[1] + (size_t)(q0 - p0) * a.sh * a.sw;
+    a.ups = UpScale{0.5f, 2.0f};
+  } else {
+    a.sh = hl, a.sw = wl;
+    a.src = ws.disp_low + (size_t)q0 * hl * wl;
+    a.ups = UpScale{1.0f / 16.0f, 16.0f};
   }
-  return refine_level(h, ws, st, h->tw[0], ws.ref[2 * sidx], ws.ref[2 * sidx + 1], ws.ref16[2 * sidx], ws.ref16[2 * sidx + 1],
-                      src, sh, sw, ups, in_chunk, false, h->H, h->W, (float)h->D, od, orw, ctr, c, ws.rb, pe, mode, ws.stats);
+  a.img_src = in6 + (size_t)q0 * 6 * HW, a.pyr = false;
+  a.H = h->H, a.W = h->W, a.dnorm = (float)h->D;
+  a.od = out_disp ? out_disp + (size_t)q0 * HW : nullptr;
+  a.orw = out_raw ? out_raw + (size_t)q0 * HW : nullptr;
+  a.c = c, a.cap = ws.rb, a.pe = pe, a.mode = mode, a.stat = ws.stats;
+  return refine_level(h, ws, st, a);
 }
 
 // in6: device int8 [n][6][H][W]; out_disp / out_raw: device, nullable.
@@ -803,14 +815,38 @@ int fold_pending(sn_handle* h, bool wait) {
   return SN_OK;
 }
 
+// What a finished call owes the handle: n pairs from in6, run in `mode` on ws / st and synchronised.  Reads the statistic;
+// check (an SN_PREC_AUTO call in SN_PREC_F16): the self-check first, if the handle is uncalibrated and the call was not flagged
+// (a flagged call owes none: there is nothing to calibrate on, and the next F16 call of the handle, if any, has it); count: the
+// caller has not counted the call yet (sn_wait: a request counts once its self-check has passed); folds; and a call the fold
+// sends out of the fp16 tower's envelope is REPEATED: rerun() runs it again in SN_PREC_F16X3 with whatever the caller enqueues
+// behind it and returns once that has completed; its statistic is folded in without being observed a second time.
+// *range: the counts of the arithmetic whose maps the caller holds afterwards.
+template <class Rerun>
+int settle(sn_handle* h, Workspace& ws, hipStream_t st, int n, const int8_t* in6, int mode, bool check, bool count,
+           Rerun rerun, RangeCount* range) {
+  double lvl[kMaxLevels], res = 0.0;
+  int rc;
+  read_stats(h, ws, n, lvl, &res, range);
+  if (check && !range->any() && (rc = auto_selfcheck(h, ws, st, in6))) return rc;
+  if (count) count_call(h, n);
+  const int next = fold_stats(h, lvl, res, *range, n, mode);
+  if (h->precision == SN_PREC_AUTO && mode == SN_PREC_F16 && next == SN_PREC_F16X3) {
+    if ((rc = rerun())) return rc;
+    read_stats(h, ws, n, lvl, &res, range);
+    fold_stats(h, lvl, res, *range, n, SN_PREC_F16X3, false);
+  }
+  return SN_OK;
+}
+
 // forward() on the handle's own workspace for the synchronous entry points.  post() enqueues what follows the network
 // (device-to-host copies; sn_infer_conf: the confidence kernel, which reads ws.conf_low — want_conf — and the maps after the
-// towers have joined, and runs again after a repeat so that its outputs belong to the arithmetic that returned).  blocking: the entry point returns after completion — the statistic is folded in before it
-// does and, under SN_PREC_AUTO, a call that left the fp16 tower's envelope is REPEATED in SN_PREC_F16X3.  Not blocking
-// A blocking call whose returned maps come from an arithmetic that left the range of fp16 returns SN_ERR_RANGE (range_result).
-// (work only enqueued on the caller's stream): the statistic is folded in by a later call; an AUTO handle that has not had
-// its self-check yet blocks once.  A blocking call WAITS for the statistic of an enqueue-only call before it (its own forward
-// overwrites the pinned words: left pending, they would later be read as that earlier call's and divided by its n).
+// towers have joined, and runs again after a repeat so that its outputs belong to the arithmetic that returned).
+// blocking: the entry point returns after completion, so the call is settled before it does; maps that come from an
+// arithmetic that left the range of fp16 return SN_ERR_RANGE (range_result).  Not blocking (work only enqueued on the caller's
+// stream): the statistic is folded in by a later call; an AUTO handle that has not had its self-check yet blocks once.
+// A blocking call WAITS for the statistic of an enqueue-only call before it (its own forward overwrites the pinned words:
+// left pending, they would later be read as that earlier call's and divided by its n).
 template <class Post>
 int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* ddisp, int32_t* draw, bool want_cost,
                 bool blocking, Post post, bool want_conf = false) {
@@ -837,19 +873,15 @@ int run_forward(sn_handle* h, hipStream_t st, int n, const int8_t* din, float* d
     return SN_OK;
   }
   HIP_TRY(h, hipStreamSynchronize(st));
-  double lvl[kMaxLevels], res = 0.0;
   RangeCount range;
-  read_stats(h, h->ws, n, lvl, &res, &range);
-  // (a flagged call owes no self-check: there is nothing to calibrate on, and the next F16 call of the handle, if any, has it)
-  if (check && !range.any() && (rc = auto_selfcheck(h, h->ws, st, din))) return rc;
-  const int next = fold_stats(h, lvl, res, range, n, mode);
-  if (is_auto && mode == SN_PREC_F16 && next == SN_PREC_F16X3) {
-    if ((rc = forward(h, h->ws, st, n, din, ddisp, draw, want_cost, SN_PREC_F16X3, want_conf))) return rc;
-    if ((rc = post())) return rc;
+  auto rerun = [&]() -> int {
+    int r = forward(h, h->ws, st, n, din, ddisp, draw, want_cost, SN_PREC_F16X3, want_conf);
+    if (!r) r = post();
+    if (r) return r;
     HIP_TRY(h, hipStreamSynchronize(st));
-    read_stats(h, h->ws, n, lvl, &res, &range);
-    fold_stats(h, lvl, res, range, n, SN_PREC_F16X3, false);
-  }
+    return SN_OK;
+  };
+  if ((rc = settle(h, h->ws, st, n, din, mode, check, false, rerun, &range))) return rc;
   if ((rc = collect_profile(h))) return rc;
   return blocking ? range_result(h, range) : SN_OK;      // the counts of the arithmetic whose maps the caller holds
 }

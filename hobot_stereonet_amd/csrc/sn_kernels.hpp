@@ -208,6 +208,19 @@ struct UpScale {
   float rs, mul;            // 1 / factor, factor (the values are disparities in pixels of the finer grid)
 };
 
+// Arguments of the refinement head, every form: conv 3x3 32 -> 1 + `disp = relu(up + D r)` + wire quantisation (head_value /
+// head_store below).  The activation tensor, its geometry and the tile counts are the kernels' own parameters.
+struct HeadArgs {
+  const float* w;          // [32][9] fp32 head weights
+  const float* disp_low;   // [nimg][hl][wl] map the level starts from
+  float* out_disp;         // [nimg][H][W] (nullable)
+  int32_t* out_raw;        // [nimg][H][W] wire map (nullable)
+  float bias, dmax, inv_q;
+  int hl, wl, H, W;        // H, W: size of the output maps (<= the tensor's valid area)
+  UpScale ups;
+  unsigned long long* stat = nullptr;   // nullable: sum of |D r| over the written pixels, count of non-finite ones (refine_stat_commit)
+};
+
 // Refinement statistic (sn_get_refine_stats, SN_PREC_AUTO): every head form adds the |D r| of the pixels it writes — what the
 // refinement level moves the map by, in the level's pixels.  Per-lane partial sums meet in a wave reduction and leave as ONE
 // 64-bit fixed-point atomic per wave (units of 2^-20 px): integer addition does not depend on the order the waves arrive in,
@@ -296,6 +309,22 @@ __device__ __forceinline__ float upsample_map(const float* low, int hl, int wl, 
   const float v = hy * (hx * low[y0 * wl + x0] + lx * low[y0 * wl + x1]) +
                   ly * (hx * low[y1 * wl + x0] + lx * low[y1 * wl + x1]);
   return v * u.mul;
+}
+
+// The refinement head's output rule, every form: d = relu(up + D r) for the conv result r = acc; moved = |D r| (the
+// refinement statistic) and bad = 1 when d is not finite BEFORE the clamp (the range check); such a pixel leaves as 0 =
+// invalid: +inf would pass the relu.
+__device__ __forceinline__ float head_value(float up, float dmax, float acc, float& moved, unsigned& bad) {
+  const float d = up + dmax * acc;
+  moved = fabsf(dmax * acc);
+  const bool fin = stat_finite(d);
+  bad = fin ? 0u : 1u;
+  return (d > 0.f && fin) ? d : 0.f;
+}
+// ... and its two stores: the float map and the wire map raw = rint(d * inv_q), both nullable, at element o
+__device__ __forceinline__ void head_store(float* out_disp, int32_t* out_raw, size_t o, float d, float inv_q) {
+  if (out_disp) out_disp[o] = d;
+  if (out_raw) out_raw[o] = (int32_t)__float2int_rn(d * inv_q);
 }
 
 // Refinement input: channel 0 = upsampled disparity / D, channels 1..3 = left image planes — the int8 model input
@@ -1282,50 +1311,37 @@ __global__ __launch_bounds__(64 * DLMAX) void k_softargmin_p(const float* __rest
 //   multiplies raw by scale*16*12).  One thread per output pixel, lanes along x (coalesced).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_head_final(const float* __restrict__ xin,      // [n][32][Hp][Wp]
-                                                    const float* __restrict__ w,        // [32][9]
-                                                    float bias, const float* __restrict__ disp_low,
-                                                    int hl, int wl, int Hp, int Wp, int H, int W,
-                                                    float dmax, float inv_q,
-                                                    float* __restrict__ out_disp,       // nullable [n][H][W]
-                                                    int32_t* __restrict__ out_raw,      // nullable [n][H][W]
-                                                    UpScale ups,
-                                                    unsigned long long* __restrict__ stat) {   // nullable: sum |D r|
+                                                    int Hp, int Wp, HeadArgs ha) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int n = blockIdx.z;
   float moved = 0.f;
   unsigned bad = 0u;
-  if (x < W && y < H) {
-  const size_t plane = (size_t)Hp * Wp;
-  const float* src = xin + (size_t)n * kC * plane;
-  float acc = bias;
-  for (int ci = 0; ci < kC; ++ci) {
-    const float* p = src + (size_t)ci * plane;
-    const float* wc = w + ci * 9;
+  if (x < ha.W && y < ha.H) {
+    const size_t plane = (size_t)Hp * Wp;
+    const float* src = xin + (size_t)n * kC * plane;
+    float acc = ha.bias;
+    for (int ci = 0; ci < kC; ++ci) {
+      const float* p = src + (size_t)ci * plane;
+      const float* wc = ha.w + ci * 9;
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const int yy = y + ky - 1;
-      if ((unsigned)yy >= (unsigned)Hp) continue;
+      for (int ky = 0; ky < 3; ++ky) {
+        const int yy = y + ky - 1;
+        if ((unsigned)yy >= (unsigned)Hp) continue;
 #pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const int xx = x + kx - 1;
-        const float v = (unsigned)xx < (unsigned)Wp ? p[(size_t)yy * Wp + xx] : 0.f;
-        acc = fmaf(wc[ky * 3 + kx], v, acc);
+        for (int kx = 0; kx < 3; ++kx) {
+          const int xx = x + kx - 1;
+          const float v = (unsigned)xx < (unsigned)Wp ? p[(size_t)yy * Wp + xx] : 0.f;
+          acc = fmaf(wc[ky * 3 + kx], v, acc);
+        }
       }
     }
+    const float up = upsample_map(ha.disp_low + (size_t)n * ha.hl * ha.wl, ha.hl, ha.wl, y, x, ha.ups);
+    const float d = head_value(up, ha.dmax, acc, moved, bad);
+    head_store(ha.out_disp, ha.out_raw, ((size_t)n * ha.H + y) * ha.W + x, d, ha.inv_q);
   }
-  const float up = upsample_map(disp_low + (size_t)n * hl * wl, hl, wl, y, x, ups);
-  float d = up + dmax * acc;
-  moved = fabsf(dmax * acc);
-  bad = stat_finite(d) ? 0u : 1u;
-  d = (d > 0.f && bad == 0u) ? d : 0.f;          // a counted pixel leaves as 0 = invalid: +inf would pass the relu
-  const size_t o = ((size_t)n * H + y) * W + x;
-  if (out_disp) out_disp[o] = d;
-  if (out_raw) out_raw[o] = (int32_t)__float2int_rn(d * inv_q);
-  }
-  refine_stat_commit_block(stat, moved, bad);
+  refine_stat_commit_block(ha.stat, moved, bad);
 }
-
 
 // ==========================================================================================
 // fp16 refinement tower (SN_PREC_F16): the 12 C->C 3x3 (dilated) convolutions at full resolution.
@@ -2237,14 +2253,37 @@ struct HeadTile {
   static constexpr int LDS_BYTES = 9 * PLANE * 4;
 };
 
+// Epilogue of the taps-as-M heads, every thread of the 256-thread workgroup: the output pixels of the TH x 62 tile at
+// (y0, x0) of image n from the P window s_p [9][RP][CP] — bias + the nine shifted taps, the head's rule, both stores —
+// and the workgroup's share of the statistic.
+template <int TH>
+__device__ __forceinline__ void head_window_finish(const float* s_p, int n, int y0, int x0, const HeadArgs& ha) {
+  using T = HeadTile<TH>;
+  const float* dl = ha.disp_low + (size_t)n * ha.hl * ha.wl;
+  float moved = 0.f;
+  unsigned bad = 0u;
+  for (int p = threadIdx.x; p < T::TH * T::TWO; p += 256) {
+    const int oy = p / T::TWO, ox = p - oy * T::TWO;
+    const int y = y0 + oy, x = x0 + ox;
+    if (y >= ha.H || x >= ha.W) continue;
+    float acc = ha.bias;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) acc += s_p[(ky * 3 + kx) * T::PLANE + (oy + ky) * T::CP + ox + kx];
+    float mv;
+    unsigned nf;
+    const float d = head_value(upsample_map(dl, ha.hl, ha.wl, y, x, ha.ups), ha.dmax, acc, mv, nf);
+    moved += mv;
+    bad += nf;
+    head_store(ha.out_disp, ha.out_raw, ((size_t)n * ha.H + y) * ha.W + x, d, ha.inv_q);
+  }
+  refine_stat_commit_block(ha.stat, moved, bad);
+}
+
 template <bool SPLIT, int TH>
 __global__ __launch_bounds__(256) void k_head_final_f16(const uint4* __restrict__ xin, size_t lo_slots, RefGeom g,
-                                                        const float* __restrict__ w,      // [32][9]
-                                                        float bias, const float* __restrict__ disp_low, int hl,
-                                                        int wl, int H, int W, float dmax, float inv_q,
-                                                        float* __restrict__ out_disp, int32_t* __restrict__ out_raw,
-                                                        int tiles_x, int tiles_y, UpScale ups,
-                                                        unsigned long long* __restrict__ stat) {   // nullable: sum |D r|
+                                                        int tiles_x, int tiles_y, HeadArgs ha) {
   using T = HeadTile<TH>;
   extern __shared__ __attribute__((aligned(16))) float s_p[];           // [9][RP][CP]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -2278,7 +2317,7 @@ __global__ __launch_bounds__(256) void k_head_final_f16(const uint4* __restrict_
   for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float wv = j < 9 ? w[(16 * kk + 8 * gh + e) * 9 + j] : 0.f;
+      const float wv = j < 9 ? ha.w[(16 * kk + 8 * gh + e) * 9 + j] : 0.f;
       const _Float16 hi = (_Float16)wv;
       ah[kk][e] = hi;
       al[kk][e] = (_Float16)((wv - (float)hi) * kSplitScale);
@@ -2310,29 +2349,7 @@ __global__ __launch_bounds__(256) void k_head_final_f16(const uint4* __restrict_
     if (gh == 0) dst[8 * T::PLANE] = a0[4] + a1[4] * kSplitInv;
   }
   __syncthreads();
-  const float* dl = disp_low + (size_t)n * hl * wl;
-  float moved = 0.f;
-  unsigned bad = 0u;
-  for (int p = tid; p < T::TH * T::TWO; p += 256) {
-    const int oy = p / T::TWO, ox = p - oy * T::TWO;
-    const int y = y0 + oy, x = x0 + ox;
-    if (y >= H || x >= W) continue;
-    float acc = bias;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) acc += s_p[(ky * 3 + kx) * T::PLANE + (oy + ky) * T::CP + ox + kx];
-    const float up = upsample_map(dl, hl, wl, y, x, ups);
-    float d = up + dmax * acc;
-    moved += fabsf(dmax * acc);
-    const bool fin = stat_finite(d);
-    bad += fin ? 0u : 1u;
-    d = (d > 0.f && fin) ? d : 0.f;              // a counted pixel leaves as 0 = invalid: +inf would pass the relu
-    const size_t o = ((size_t)n * H + y) * W + x;
-    if (out_disp) out_disp[o] = d;
-    if (out_raw) out_raw[o] = (int32_t)__float2int_rn(d * inv_q);
-  }
-  refine_stat_commit_block(stat, moved, bad);
+  head_window_finish<TH>(s_p, n, y0, x0, ha);
 }
 
 // K8 in SN_PREC_FP32 on the matrix core: the same taps-as-M contraction on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32):
@@ -2344,12 +2361,7 @@ __global__ __launch_bounds__(256) void k_head_final_f16(const uint4* __restrict_
 // k_head_final (channels first, then the nine taps).
 template <int TH>
 __global__ __launch_bounds__(256) void k_head_final_mfma32(const float* __restrict__ xin,     // [n][32][Hp][Wp]
-                                                           const float* __restrict__ w,       // [32][9]
-                                                           float bias, const float* __restrict__ disp_low, int hl, int wl,
-                                                           int Hp, int Wp, int H, int W, float dmax, float inv_q,
-                                                           float* __restrict__ out_disp, int32_t* __restrict__ out_raw,
-                                                           int tiles_x, int tiles_y, UpScale ups,
-                                                           unsigned long long* __restrict__ stat) {   // nullable: sum |D r|
+                                                           int Hp, int Wp, int tiles_x, int tiles_y, HeadArgs ha) {
   using T = HeadTile<TH>;
   static_assert(T::NSEG % 4 == 0, "whole segments per wave");
   extern __shared__ __attribute__((aligned(16))) float s_p[];           // [9][RP][CP]
@@ -2367,7 +2379,7 @@ __global__ __launch_bounds__(256) void k_head_final_mfma32(const float* __restri
   // A operands: row i = tap (rows 9.. are zero), K-step kk <-> channels 2 kk, 2 kk + 1
   float a[16];
 #pragma unroll
-  for (int kk = 0; kk < 16; ++kk) a[kk] = j < 9 ? w[(2 * kk + kh) * 9 + j] : 0.f;
+  for (int kk = 0; kk < 16; ++kk) a[kk] = j < 9 ? ha.w[(2 * kk + kh) * 9 + j] : 0.f;
   constexpr int HALF = T::SPW > 4 ? (T::SPW + 1) / 2 : T::SPW;         // segments whose loads are in flight together
 #pragma unroll
   for (int s0 = 0; s0 < T::SPW; s0 += HALF) {
@@ -2401,29 +2413,7 @@ __global__ __launch_bounds__(256) void k_head_final_mfma32(const float* __restri
     }
   }
   __syncthreads();
-  const float* dl = disp_low + (size_t)n * hl * wl;
-  float moved = 0.f;
-  unsigned bad = 0u;
-  for (int p = tid; p < T::TH * T::TWO; p += 256) {
-    const int oy = p / T::TWO, ox = p - oy * T::TWO;
-    const int y = y0 + oy, x = x0 + ox;
-    if (y >= H || x >= W) continue;
-    float acc = bias;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) acc += s_p[(ky * 3 + kx) * T::PLANE + (oy + ky) * T::CP + ox + kx];
-    const float up = upsample_map(dl, hl, wl, y, x, ups);
-    float d = up + dmax * acc;
-    moved += fabsf(dmax * acc);
-    const bool fin = stat_finite(d);
-    bad += fin ? 0u : 1u;
-    d = (d > 0.f && fin) ? d : 0.f;              // a counted pixel leaves as 0 = invalid: +inf would pass the relu
-    const size_t o = ((size_t)n * H + y) * W + x;
-    if (out_disp) out_disp[o] = d;
-    if (out_raw) out_raw[o] = (int32_t)__float2int_rn(d * inv_q);
-  }
-  refine_stat_commit_block(stat, moved, bad);
+  head_window_finish<TH>(s_p, n, y0, x0, ha);
 }
 
 }  // namespace sn

@@ -416,7 +416,7 @@ hipError_t launch_ref_f16_v2(hipStream_t st, const RefLayerF16& L, const RefGeom
 // the flattened (image, row phase, strip, sub-row) sequence.  x and y must be different tensors.  dump: >= 1 KB scratch.
 template <class T>
 hipError_t launch_ref_block_stream(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu,
-                                   const uint4* x, uint4* y, int nimg, unsigned* dump, const StreamHeadArgs& ha = StreamHeadArgs{}) {
+                                   const uint4* x, uint4* y, int nimg, unsigned* dump, const HeadArgs& ha = HeadArgs{}) {
   constexpr int DIL = T::DIL;
   auto kern = k_ref_block_stream_f16<T::DIL, T::TW, T::R, T::NXS, T::NWR, T::HEAD>;
   if (dump == nullptr) return hipErrorInvalidValue;
@@ -443,7 +443,7 @@ hipError_t launch_ref_block_stream(hipStream_t st, const RefLayerF16& L1, const 
 // Last block of the tower + the refinement head in one launch (tail form): y never leaves the CU, the head's maps are the
 // only thing written.  Same arithmetic as the streamed block followed by k_head_final_f16 (bit-identical maps).
 hipError_t ref_block_stream_tail(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu,
-                                 const uint4* x, int nimg, unsigned* dump, const StreamHeadArgs& ha) {
+                                 const uint4* x, int nimg, unsigned* dump, const HeadArgs& ha) {
   return launch_ref_block_stream<StreamTileTail>(st, L1, L2, g, num_cu, x, nullptr, nimg, dump, ha);
 }
 
@@ -464,20 +464,17 @@ inline bool stream_block_supports(int dil) {
   return (dil == 1 || dil == 2 || dil == 4 || dil == 8) && dil <= switches().stream_dil;
 }
 
-hipError_t launch_head_final_f16(hipStream_t st, bool split, const uint4* x, size_t lo_slots, const RefGeom& g,
-                                 const float* w, float bias, const float* disp_low, int hl, int wl, int H, int W, float dmax,
-                                 float inv_q, UpScale ups, float* out_disp, int32_t* out_raw, int nimg,
-                                 unsigned long long* stat = nullptr) {
+// k_head_final_f16 on the tower's output tensor x (split: hi + lo tensor, lo_slots behind it) for nimg maps
+hipError_t launch_head_final_f16(hipStream_t st, bool split, const uint4* x, size_t lo_slots, const RefGeom& g, int nimg,
+                                 const HeadArgs& ha) {
   constexpr int TH = 16;
   using T = HeadTile<TH>;
-  const int tiles_x = (W + T::TWO - 1) / T::TWO, tiles_y = (H + TH - 1) / TH;
+  const int tiles_x = (ha.W + T::TWO - 1) / T::TWO, tiles_y = (ha.H + TH - 1) / TH;
   const dim3 grid((unsigned)(tiles_x * tiles_y * nimg));
   if (split)
-    hipLaunchKernelGGL((k_head_final_f16<true, TH>), grid, dim3(256), T::LDS_BYTES, st, x, lo_slots, g, w, bias, disp_low, hl,
-                       wl, H, W, dmax, inv_q, out_disp, out_raw, tiles_x, tiles_y, ups, stat);
+    hipLaunchKernelGGL((k_head_final_f16<true, TH>), grid, dim3(256), T::LDS_BYTES, st, x, lo_slots, g, tiles_x, tiles_y, ha);
   else
-    hipLaunchKernelGGL((k_head_final_f16<false, TH>), grid, dim3(256), T::LDS_BYTES, st, x, (size_t)0, g, w, bias, disp_low,
-                       hl, wl, H, W, dmax, inv_q, out_disp, out_raw, tiles_x, tiles_y, ups, stat);
+    hipLaunchKernelGGL((k_head_final_f16<false, TH>), grid, dim3(256), T::LDS_BYTES, st, x, (size_t)0, g, tiles_x, tiles_y, ha);
   return hipGetLastError();
 }
 

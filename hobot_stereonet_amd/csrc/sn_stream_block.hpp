@@ -230,24 +230,13 @@ __device__ __forceinline__ void glds4(unsigned lds_dst, unsigned voff, const voi
       : "memory");
 }
 
-// Arguments of the tail form (HEAD): the refinement head conv 3x3 32 -> 1 + `disp = relu(up + D r)` + wire quantisation,
-// exactly k_head_final_f16's arithmetic (same MFMA sequence for P, same order of the nine additions).
-struct StreamHeadArgs {
-  const float* w;          // [32][9] fp32 head weights
-  const float* disp_low;   // [nimg][hl][wl] map the level starts from
-  float* out_disp;         // [nimg][H][W] (nullable)
-  int32_t* out_raw;        // [nimg][H][W] wire map (nullable)
-  float bias, dmax, inv_q;
-  int hl, wl, H, W;        // H, W: size of the output maps (<= g.H, g.W)
-  UpScale ups;
-  unsigned long long* stat = nullptr;   // nullable: sum of |D r| over the written pixels, count of non-finite ones (refine_stat_commit)
-};
-
+// HEAD (tail form): the refinement head (HeadArgs) rides on the block, exactly k_head_final_f16's arithmetic (same MFMA
+// sequence for P, same order of the nine additions).
 template <int DIL, int TW, int R, int NXS, int NWR, bool HEAD = false>
 __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per_eu(NWR / 2, NWR / 2))) void k_ref_block_stream_f16(const uint4* __restrict__ xin, uint4* __restrict__ yout,
                                                                 const uint4* __restrict__ wfrag1, const float* __restrict__ bias1,
                                                                 const uint4* __restrict__ wfrag2, const float* __restrict__ bias2,
-                                                                RefGeom g, StreamSched sc, uint4* __restrict__ dump, StreamHeadArgs ha) {
+                                                                RefGeom g, StreamSched sc, uint4* __restrict__ dump, HeadArgs ha) {
   using T = StreamTile<DIL, TW, R, NXS, NWR, HEAD>;
   constexpr int HS = T::HS;
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
@@ -414,16 +403,13 @@ __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per
             const float* w0 = s_win + rw * 128;
             const float v = hy * (hx * w0[x0 - cb] + lx * w0[x1 - cb]) + ly * (hx * w0[64 + x0 - cb] + lx * w0[64 + x1 - cb]);
             const float up = v * ha.ups.mul;
-            float d = up + ha.dmax * acc;
-            const float mv = fabsf(ha.dmax * acc);
-            const unsigned nf = stat_finite(d) ? 0u : 1u;
-            d = (d > 0.f && nf == 0u) ? d : 0.f;     // a counted pixel leaves as 0 = invalid: +inf would pass the relu
+            float mv;
+            unsigned nf;
+            const float d = head_value(up, ha.dmax, acc, mv, nf);
             if (lane >= 1 && lane <= T::OW && X < ha.W) {
               moved += mv;
               bad += nf;
-              const size_t oi = ((size_t)fin_img * ha.H + o) * ha.W + X;
-              if (ha.out_disp) ha.out_disp[oi] = d;
-              if (ha.out_raw) ha.out_raw[oi] = (int32_t)__float2int_rn(d * ha.inv_q);
+              head_store(ha.out_disp, ha.out_raw, ((size_t)fin_img * ha.H + o) * ha.W + X, d, ha.inv_q);
             }
           }
         }

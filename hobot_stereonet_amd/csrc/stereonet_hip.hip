@@ -695,6 +695,22 @@ static int ensure_slots(sn_handle* h) {
   return SN_OK;
 }
 
+// Hands a busy slot back when it goes out of scope, unless disarmed: a slot left busy would make a later submit with
+// timeout -1 — what the node passes — block forever.  take_mu: the owner does not hold h->mu.
+struct SlotGuard {
+  sn_handle* h;
+  Slot* s;
+  bool take_mu;
+  bool armed = true;
+  ~SlotGuard() {
+    if (!armed) return;
+    if (take_mu) h->mu.lock();
+    s->ticket = 0;
+    if (take_mu) h->mu.unlock();
+    h->cv.notify_one();
+  }
+};
+
 // kind 0: `in` is the int8 model tensor (6*H*W bytes); kind 1: the raw 2W x H side-by-side NV12 frame of FeedImg
 // (3*H*W bytes: half the H2D traffic; split + chroma replication + ^0x80 run on the GPU in k_pre_nv12)
 static int submit_common(sn_handle* h, const void* in, int kind, int32_t* out_i32, float* out_disp, int timeout_ms,
@@ -722,18 +738,8 @@ static int submit_common(sn_handle* h, const void* in, int kind, int32_t* out_i3
   s->ticket = h->next_ticket++;
   s->user_raw = out_i32;
   s->user_disp = out_disp;
-  // Every error exit below must hand the slot back (a slot left busy would make a later submit with
-  // timeout -1 — what the node passes — block forever); *ticket is written on success only.
-  struct SlotGuard {
-    sn_handle* h;
-    Slot* s;
-    bool armed = true;
-    ~SlotGuard() {
-      if (!armed) return;
-      s->ticket = 0;            // h->mu is still held by the caller's unique_lock
-      h->cv.notify_one();
-    }
-  } guard{h, s};
+  // Every error exit below must hand the slot back; *ticket is written on success only.
+  SlotGuard guard{h, s, false};           // h->mu is held by lk
   memcpy(s->pin_in, in, (kind == 1 ? 3 : 6) * HW);   // the caller may release its buffer as soon as we return
   const int mask = (out_i32 ? 1 : 0) | (out_disp ? 2 : 0);
   // arithmetic of this request: an SN_PREC_AUTO handle's current one (sn_wait folds the request's statistic in and repeats
@@ -824,44 +830,30 @@ int sn_wait(sn_handle* h, uint64_t ticket, float* infer_ms) {
       if (c.ticket == ticket) s = &c;
   }
   if (!s) return SN_ERR_TICKET;
+  SlotGuard guard{h, s, true};       // every exit from here on consumes the ticket; an error exit writes no outputs
   hipSetDevice(h->device);
   HIP_TRY(h, hipEventSynchronize(s->ev1));
   const size_t HW = (size_t)h->H * h->W;
+  // the request's refinement statistic; SN_PREC_AUTO: self-check on the first request, and a request that left the fp16
+  // tower's envelope is repeated in SN_PREC_F16X3 on its own stream before its maps are handed over
+  auto rerun = [&]() -> int {
+    const int r = forward(h, s->ws, s->stream, 1, s->ws.in6, s->user_disp ? s->ws.out_disp : nullptr,
+                          s->user_raw ? s->ws.out_raw : nullptr, false, SN_PREC_F16X3);
+    if (r) return r;
+    if (s->user_raw) HIP_TRY(h, hipMemcpyAsync(s->pin_raw, s->ws.out_raw, 4 * HW, hipMemcpyDeviceToHost, s->stream));
+    if (s->user_disp) HIP_TRY(h, hipMemcpyAsync(s->pin_disp, s->ws.out_disp, 4 * HW, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(h, hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(h, hipEventSynchronize(s->ev1));
+    return SN_OK;
+  };
+  const bool check = h->precision == SN_PREC_AUTO && s->mode_run == SN_PREC_F16;
   RangeCount range;          // of the arithmetic whose maps are handed over
-  {
-    // the request's refinement statistic; SN_PREC_AUTO: self-check on the first request, and a request that left the fp16
-    // tower's envelope is repeated in SN_PREC_F16X3 on its own stream before its maps are handed over
-    double lvl[kMaxLevels], res = 0.0;
-    read_stats(h, s->ws, 1, lvl, &res, &range);
-    const bool is_auto = h->precision == SN_PREC_AUTO;
-    int rc = SN_OK;
-    if (is_auto && s->mode_run == SN_PREC_F16 && !range.any() && (rc = auto_selfcheck(h, s->ws, s->stream, s->ws.in6))) return rc;
-    count_call(h, 1);
-    const int next = fold_stats(h, lvl, res, range, 1, s->mode_run);
-    if (is_auto && s->mode_run == SN_PREC_F16 && next == SN_PREC_F16X3) {
-      if ((rc = forward(h, s->ws, s->stream, 1, s->ws.in6, s->user_disp ? s->ws.out_disp : nullptr,
-                        s->user_raw ? s->ws.out_raw : nullptr, false, SN_PREC_F16X3)))
-        return rc;
-      if (s->user_raw) HIP_TRY(h, hipMemcpyAsync(s->pin_raw, s->ws.out_raw, 4 * HW, hipMemcpyDeviceToHost, s->stream));
-      if (s->user_disp) HIP_TRY(h, hipMemcpyAsync(s->pin_disp, s->ws.out_disp, 4 * HW, hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(h, hipEventRecord(s->ev1, s->stream));
-      HIP_TRY(h, hipEventSynchronize(s->ev1));
-      read_stats(h, s->ws, 1, lvl, &res, &range);
-      fold_stats(h, lvl, res, range, 1, SN_PREC_F16X3, false);
-    }
-  }
+  if (const int rc = settle(h, s->ws, s->stream, 1, s->ws.in6, s->mode_run, check, true, rerun, &range)) return rc;
+  float ms = 0.f;
+  if (infer_ms) HIP_TRY(h, hipEventElapsedTime(&ms, s->ev0, s->ev1));      // the last exit that leaves the outputs unwritten
+  if (infer_ms) *infer_ms = ms;
   if (s->user_raw) memcpy(s->user_raw, s->pin_raw, 4 * HW);
   if (s->user_disp) memcpy(s->user_disp, s->pin_disp, 4 * HW);
-  if (infer_ms) {
-    float ms = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    *infer_ms = ms;
-  }
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    s->ticket = 0;
-  }
-  h->cv.notify_one();
   return range_result(h, range);         // SN_ERR_RANGE: the maps were copied and the ticket is consumed
 }
 

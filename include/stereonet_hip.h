@@ -232,7 +232,9 @@ int sn_preprocess_sbs_nv12_batch(sn_handle *h, int n, const uint8_t *sbs_nv12, i
 /* DnnNode::Run, asynchronous form (stereonet_node.cpp:812): host buffers only.  sn_submit copies
  * the input and returns at once with a ticket; up to task_num tickets are in flight;
  * timeout_ms < 0 waits for a free slot forever (the reference passes -1).  sn_wait blocks until the
- * ticket's pair is done, fills the host outputs given at submit, and reports the device time. */
+ * ticket's pair is done, fills the host outputs given at submit, and reports the device time.  Once sn_wait has found
+ * the ticket, every return consumes it and frees its slot; a return with a device error (not SN_ERR_RANGE, which hands the
+ * maps over) leaves the host outputs unwritten. */
 int sn_submit(sn_handle *h, const int8_t *in_nchw6_host, int32_t *out_i32_host, float *out_disp_host,
               int timeout_ms, uint64_t *ticket);
 /* The same with FeedImg's raw 2W x H side-by-side NV12 frame as the input (stereonet_node.cpp:705-738 + preprocess.cpp:
