@@ -86,6 +86,31 @@ class SnTemporalParams(C.Structure):
     _fields_ = [("alpha", C.c_int), ("delta_px", C.c_float), ("persist", C.c_int), ("luma_delta", C.c_int)]
 
 
+class SnEyeCalib(C.Structure):
+    """sn_eye_calib (include/stereonet_hip.h); rectify.Eye is the Python face of it."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("d", C.c_double * 5),
+                ("R", C.c_double * 9)]
+
+
+class SnStereoCalib(C.Structure):
+    """sn_stereo_calib (include/stereonet_hip.h); rectify.Calib is the Python face of it."""
+    _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("left", SnEyeCalib), ("right", SnEyeCalib), ("pfx", C.c_double),
+                ("pfy", C.c_double), ("pcx", C.c_double), ("pcy", C.c_double), ("baseline_mm", C.c_double)]
+
+
+class SnRectifyInfo(C.Structure):
+    _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
+                ("valid_right", C.c_uint32)]
+
+
+def stereo_calib(c) -> SnStereoCalib:
+    """rectify.Calib -> sn_stereo_calib"""
+    if isinstance(c, SnStereoCalib):
+        return c
+    eyes = [SnEyeCalib(e.fx, e.fy, e.cx, e.cy, (C.c_double * 5)(*e.d), (C.c_double * 9)(*e.R)) for e in (c.left, c.right)]
+    return SnStereoCalib(int(c.src_w), int(c.src_h), eyes[0], eyes[1], c.pfx, c.pfy, c.pcx, c.pcy, c.baseline_mm)
+
+
 SN_FLT_INVALID_IN, SN_FLT_SPECKLE, SN_FLT_FILLED = 1, 16, 32
 SN_TMP_INVALID_IN, SN_TMP_BLENDED, SN_TMP_HELD, SN_TMP_MOVED, SN_TMP_JUMP = 1, 2, 4, 8, 16      # a mask plane of its own
 SN_SMOOTH_INVALID_IN, SN_SMOOTH_CHANGED = 1, 128
@@ -196,6 +221,14 @@ def load_library(path: Optional[str] = None):
     lib.sn_temporal_destroy.argtypes = [vp]
     lib.sn_temporal_destroy.restype = None
     lib.sn_temporal_push.argtypes = [vp, ip, vp, i32p, vp, ip, ip, i32p, fp, u8p, vp, ip, vp]
+    lib.sn_rectify_build_map.argtypes = [C.POINTER(SnStereoCalib), ip, ip, ip, i32p]
+    lib.sn_rectify_create.argtypes = [vp, C.POINTER(SnStereoCalib), C.POINTER(vp)]
+    lib.sn_rectify_destroy.argtypes = [vp]
+    lib.sn_rectify_destroy.restype = None
+    lib.sn_rectify_get_info.argtypes = [vp, C.POINTER(SnRectifyInfo)]
+    lib.sn_rectify_get_camera.argtypes = [vp, C.POINTER(SnCamera)]
+    lib.sn_rectify_get_map.argtypes = [vp, ip, i32p]
+    lib.sn_rectify_nv12.argtypes = [vp, ip, u8p, u8p, ip, C.c_size_t, u8p, i8p, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -209,7 +242,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -239,6 +272,16 @@ def compose_down01(w0, b0, w1, b1):
     if rc:
         raise StereoNetError(rc, "sn_dbg_compose_down01")
     return weff, beff
+
+
+def rectify_build_map(calib, eye: int, w: int, h: int) -> np.ndarray:
+    """sn_rectify_build_map (host only, no device needed): Stage A of rectify.build_map by the library -> int32 (h, w, 2)."""
+    c = stereo_calib(calib)
+    out = np.empty((max(h, 0), max(w, 0), 2), np.int32)
+    rc = load_library().sn_rectify_build_map(C.byref(c), eye, w, h, out.ctypes.data)
+    if rc:
+        raise StereoNetError(rc, "sn_rectify_build_map")
+    return out
 
 
 def error_string(code: int) -> str:
@@ -697,6 +740,10 @@ class StereoNetHIP:
         """A TemporalFilter (sn_temporal) of `streams` independent states on this engine; close it before the engine."""
         return TemporalFilter(self, streams, alpha, delta_px, persist, luma_delta)
 
+    def rectifier(self, calib):
+        """A Rectifier (sn_rectify) for this engine's model size from a rectify.Calib; close it before the engine."""
+        return Rectifier(self, calib)
+
     def synchronize(self):
         self._check(self._lib.sn_synchronize(self._h), "sn_synchronize")
 
@@ -1064,3 +1111,82 @@ class TemporalFilter:
         self._eng._check(self._lib.sn_temporal_push(self._t, n, _np_ptr(ids), raw_ptr or None, guide_ptr or None, guide_kind,
                                                     guide_pitch, out_raw_ptr or None, disp_ptr or None, mask_ptr or None,
                                                     counts_ptr or None, SN_MEM_DEVICE, stream or None), "sn_temporal_push")
+
+
+class Rectifier:
+    """sn_rectify: raw NV12 pairs of the calibration's source size -> rectified side-by-side NV12 frames of the model's size
+    (and the int8 model tensor), on the GPU (rectify.reference is the numpy twin).  A context object: the engine refuses to
+    close while one of its rectifiers is open."""
+
+    def __init__(self, engine: StereoNetHIP, calib):
+        self._eng, self._lib, self._r = engine, engine._lib, C.c_void_p()
+        self.calib = stereo_calib(calib)
+        engine._check(self._lib.sn_rectify_create(engine._h, C.byref(self.calib), C.byref(self._r)), "sn_rectify_create")
+        self.src_w, self.src_h = self.calib.src_w, self.calib.src_h
+
+    def close(self):
+        if getattr(self, "_r", None) and self._r.value:
+            self._lib.sn_rectify_destroy(self._r)
+            self._r = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self) -> dict:
+        """{src_w, src_h, w, h, valid_left, valid_right}: valid_* = map entries with a source"""
+        i = SnRectifyInfo()
+        self._eng._check(self._lib.sn_rectify_get_info(self._r, C.byref(i)), "sn_rectify_get_info")
+        return {k: int(getattr(i, k)) for k, _ in SnRectifyInfo._fields_}
+
+    @property
+    def camera(self):
+        """pointcloud.Camera of the rectified left eye (sn_rectify_get_camera)"""
+        from . import pointcloud
+        c = SnCamera()
+        self._eng._check(self._lib.sn_rectify_get_camera(self._r, C.byref(c)), "sn_rectify_get_camera")
+        return pointcloud.Camera(fx=c.fx, fy=c.fy, cx=c.cx, cy=c.cy, baseline_mm=c.baseline_mm, z_min_m=c.z_min_m,
+                                 z_max_m=c.z_max_m, step=c.step)
+
+    def map(self, eye: int) -> np.ndarray:
+        """the device copy of an eye's map: int32 (H, W, 2)"""
+        out = np.empty((self._eng.height, self._eng.width, 2), np.int32)
+        self._eng._check(self._lib.sn_rectify_get_map(self._r, int(eye), out.ctypes.data), "sn_rectify_get_map")
+        return out
+
+    def rectify(self, left: np.ndarray, right: Optional[np.ndarray] = None, pitch: int = 0, n: int = 1, frame: int = 0,
+                want_sbs: bool = True, want_tensor: bool = False):
+        """sn_rectify_nv12 on host buffers.  left / right: uint8 buffers that start at pair 0's eye (right None: side-by-side
+        frames, the right eye src_w bytes into the left's rows); pitch (0: src_w, or 2 src_w side by side) and frame (0: pitch *
+        src_h * 3/2) are src_pitch and src_frame -> uint8 (n, H*3/2, 2W) and / or int8 (n, 6, H, W)."""
+        eng, sw, sh = self._eng, self.src_w, self.src_h
+        le = np.ascontiguousarray(left, dtype=np.uint8).reshape(-1)
+        pitch = pitch or (2 * sw if right is None else sw)
+        frame = frame or pitch * (sh + sh // 2)
+        span = (n - 1) * frame + (sh + sh // 2 - 1) * pitch + sw
+        re = le[sw:] if right is None else np.ascontiguousarray(right, dtype=np.uint8).reshape(-1)
+        if n < 1 or pitch < sw or le.size < span or re.size < span:      # the library cannot see how long a host buffer is
+            raise StereoNetError(-1, "rectify", f"{n} eyes of {sw}x{sh} at pitch {pitch} take {span} bytes, the buffers have "
+                                                f"{le.size} and {re.size}")
+        w, h = eng.width, eng.height
+        sbs = np.empty((n, h + h // 2, 2 * w), np.uint8) if want_sbs else None
+        ten = np.empty((n, 6, h, w), np.int8) if want_tensor else None
+        eng._check(self._lib.sn_rectify_nv12(self._r, n, le.ctypes.data, re.ctypes.data, pitch, frame, _np_ptr(sbs), _np_ptr(ten),
+                                             SN_MEM_HOST, None), "sn_rectify_nv12")
+        return (sbs, ten) if want_sbs and want_tensor else sbs if want_sbs else ten
+
+    def rectify_device(self, n: int, left_ptr: int, right_ptr: int, pitch: int, frame: int, sbs_ptr: int = 0, tensor_ptr: int = 0,
+                       stream: int = 0):
+        """sn_rectify_nv12 on device pointers; stream = hipStream_t as int (0: the rectifier's own stream, and the call returns
+        after completion)."""
+        self._eng._check(self._lib.sn_rectify_nv12(self._r, n, left_ptr or None, right_ptr or None, pitch, frame, sbs_ptr or None,
+                                                   tensor_ptr or None, SN_MEM_DEVICE, stream or None), "sn_rectify_nv12")

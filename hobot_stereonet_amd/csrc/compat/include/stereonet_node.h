@@ -90,6 +90,10 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // in place before it is packed and before the cloud is built.  STEREONET_TEMPORAL=ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]
     // (PERSIST defaults to 2, LUMA_DELTA to 0) turns it on; unset: off, nothing of it exists
     sn_temporal_params temporal{};
+    // this implementation's own: rectification of RAW frames ahead of everything else (sn_rectify_nv12).
+    // STEREONET_RECTIFY=<calibration file> (size, left.K / .D / .R, right.K / .D / .R, P, baseline_mm: one `key v v ...` per
+    // line, `#` comments) turns it on; unset: off, nothing of it exists
+    sn_stereo_calib calib{};
   };
 
   void DeclareAndReadParameters();
@@ -98,6 +102,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void ReadPointCloudSettings();
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
   void ReadTemporalSettings();
+  void ReadRectifySettings();
+  hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr RectifyFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr& raw);
   void FilterTemporal(const StereonetNodeOutput& request, int32_t* raw);
 
   Settings cfg_;
@@ -115,6 +121,7 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   std::atomic<bool> cloud_uncoloured_logged_{false};
   sn_temporal* temporal_ = nullptr;              // one stream; only while STEREONET_TEMPORAL is set and valid
   bool temporal_unguided_logged_ = false;        // PostProcess only (one thread at a time)
+  sn_rectify* rectify_ = nullptr;                // only while STEREONET_RECTIFY names a valid calibration
 };
 
 }  // namespace stereonet

@@ -21,7 +21,10 @@
 #include <fstream>
 #include <functional>
 #include <mutex>
+#include <sstream>
+#include <string>
 #include <thread>
+#include <vector>
 
 #include "image_io.h"
 #include "jpeg_nv12.h"
@@ -92,6 +95,7 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
       cfg_.image_topic, 10, [this](hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr m) { OnStereoFrame(m); });
   targets_out_ = create_publisher<ai_msgs::msg::PerceptionTargets>("/Stereonet_node_sample", 10);
   disparity_out_ = create_publisher<sensor_msgs::msg::Image>(cfg_.output_topic, 10);
+  ReadRectifySettings();      // before the point cloud: its camera defaults to the rectifier's
   ReadPointCloudSettings();
   if (cfg_.pointcloud_layout >= 0) pointcloud_out_ = create_publisher<sensor_msgs::msg::PointCloud2>("/stereonet_pointcloud2", 10);
   ReadTemporalSettings();
@@ -99,10 +103,12 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
 }
 
 StereonetNode::~StereonetNode() {
-  if (!temporal_) return;
+  if (!temporal_ && !rectify_) return;
   WaitIdle();      // requests in flight still pass through PostProcess; the engine is destroyed after the filter (~DnnNode)
-  sn_temporal_destroy(temporal_);
+  if (temporal_) sn_temporal_destroy(temporal_);
   temporal_ = nullptr;
+  if (rectify_) sn_rectify_destroy(rectify_);
+  rectify_ = nullptr;
 }
 
 void StereonetNode::DeclareAndReadParameters() {
@@ -137,6 +143,7 @@ void StereonetNode::ReadPointCloudSettings() {
   }
   sn_camera& c = cfg_.camera;
   c = sn_camera{527.1931762695312f, 527.1931762695312f, net_w_ / 2.0f, net_h_ / 2.0f, 119.89382172f, 0.f, 0.f, 1};
+  if (rectify_) sn_rectify_get_camera(rectify_, &c);      // the rectified left eye's; STEREONET_CAMERA still overrides it
   // checked once here: settings sn_pointcloud_from_raw would reject turn the cloud off instead of failing every frame
   std::string bad;
   char end = 0;
@@ -160,6 +167,109 @@ void StereonetNode::ReadPointCloudSettings() {
   RCLCPP_WARN_STREAM(kLog, "point cloud: " << e << " on /stereonet_pointcloud2, fx " << c.fx << " fy " << c.fy << " cx " << c.cx
                                            << " cy " << c.cy << " baseline_mm " << c.baseline_mm << " step " << c.step
                                            << " z " << c.z_min_m << ".." << c.z_max_m);
+}
+
+namespace {
+// rectify.load_calib's text form: one `key v v v...` per line, `#` comments, every key exactly once
+bool load_calib_file(const char* path, sn_stereo_calib* c, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct Key {
+    const char* name;
+    int count;
+    double* dst;
+  };
+  double size[2] = {0, 0}, kl[4] = {}, kr[4] = {}, proj[4] = {};
+  const Key keys[] = {{"size", 2, size},          {"left.K", 4, kl},           {"left.D", 5, c->left.d},
+                      {"left.R", 9, c->left.R},   {"right.K", 4, kr},          {"right.D", 5, c->right.d},
+                      {"right.R", 9, c->right.R}, {"P", 4, proj},              {"baseline_mm", 1, &c->baseline_mm}};
+  bool seen[9] = {};
+  std::string line;
+  for (int no = 1; std::getline(in, line); ++no) {
+    line = line.substr(0, line.find('#'));
+    std::istringstream ss(line);
+    std::string key;
+    if (!(ss >> key)) continue;
+    int k = 0;
+    while (k < 9 && key != keys[k].name) ++k;
+    std::vector<double> v;
+    for (std::string t; ss >> t;) {
+      char* end = nullptr;
+      v.push_back(strtod(t.c_str(), &end));
+      if (end == t.c_str() || *end) k = 9;
+    }
+    if (k == 9 || seen[k] || (int)v.size() != keys[k].count) {
+      *err = "line " + std::to_string(no) + " is not one of size, left.K/.D/.R, right.K/.D/.R, P, baseline_mm with its values";
+      return false;
+    }
+    seen[k] = true;
+    for (int i = 0; i < keys[k].count; ++i) keys[k].dst[i] = v[i];
+  }
+  for (int k = 0; k < 9; ++k)
+    if (!seen[k]) {
+      *err = std::string("has no `") + keys[k].name + "` line";
+      return false;
+    }
+  c->left.fx = kl[0], c->left.fy = kl[1], c->left.cx = kl[2], c->left.cy = kl[3];
+  c->right.fx = kr[0], c->right.fy = kr[1], c->right.cx = kr[2], c->right.cy = kr[3];
+  c->pfx = proj[0], c->pfy = proj[1], c->pcx = proj[2], c->pcy = proj[3];
+  c->src_w = (int)size[0];
+  c->src_h = (int)size[1];
+  if (c->src_w != size[0] || c->src_h != size[1]) {
+    *err = "size is not two integers";
+    return false;
+  }
+  return true;
+}
+}  // namespace
+
+// read and validated once here: a file sn_rectify_create would reject leaves the node as it is without the variable
+void StereonetNode::ReadRectifySettings() {
+  const char* e = getenv("STEREONET_RECTIFY");
+  if (!e || !*e) return;
+  std::string bad;
+  if (load_calib_file(e, &cfg_.calib, &bad) && sn_rectify_create(net_->engine(), &cfg_.calib, &rectify_) != SN_OK)
+    bad = std::string("was refused: ") + sn_last_error(net_->engine());
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, "STEREONET_RECTIFY=" << e << " " << bad << ": no rectification");
+    rectify_ = nullptr;
+    return;
+  }
+  sn_rectify_info info{};
+  sn_rectify_get_info(rectify_, &info);
+  RCLCPP_WARN_STREAM(kLog, "rectification: raw frames of " << 2 * info.src_w << "x" << info.src_h << " -> " << 2 * info.w << "x"
+                                                           << info.h << ", pixels with a source: left " << info.valid_left
+                                                           << ", right " << info.valid_right);
+}
+
+// The raw side-by-side frame (2 src_w x src_h) -> a message of the model's size that holds the rectified frame and the raw
+// one's index, stamp and encoding; everything downstream (ingest, the left-eye JPEG, the guide, the cloud's colour) then sees
+// the rectified frame, with which the depth is aligned.  nullptr: not a frame of the calibration's size, or the call failed.
+hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr StereonetNode::RectifyFrame(
+    const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr& raw) {
+  const int sw = cfg_.calib.src_w, sh = cfg_.calib.src_h;
+  if ((int)raw->height != sh || (int)raw->width != 2 * sw || raw->data.size() < (size_t)2 * sw * (sh + sh / 2)) {
+    RCLCPP_ERROR_STREAM(kLog, "recved img msg h: " << raw->height << ", w: " << raw->width
+                                                   << " is unmatch with the calibration's raw size " << 2 * sw << "x" << sh);
+    return nullptr;
+  }
+  auto out = std::make_shared<hbm_img_msgs::msg::HbmMsg1080P>();
+  out->index = raw->index;
+  out->time_stamp = raw->time_stamp;
+  out->encoding = raw->encoding;
+  out->height = net_h_;
+  out->width = 2 * net_w_;
+  out->data.resize((size_t)3 * net_w_ * net_h_);
+  out->data_size = (uint32_t)out->data.size();
+  if (sn_rectify_nv12(rectify_, 1, raw->data.data(), raw->data.data() + sw, 2 * sw, 0, out->data.data(), nullptr, SN_MEM_HOST,
+                      nullptr) != SN_OK) {
+    RCLCPP_ERROR(kLog, "rectification failed: %s", sn_last_error(net_->engine()));
+    return nullptr;
+  }
+  return out;
 }
 
 // parsed and validated once here: a value sn_temporal_create would reject turns the filter off instead of failing every frame
@@ -287,8 +397,9 @@ int StereonetNode::SetNodePara() {
   return 0;
 }
 
-void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame) {
-  if (!rclcpp::ok() || !frame) return;
+void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr received) {
+  if (!rclcpp::ok() || !received) return;
+  hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame = received;
 
   // accept only NV12 frames that hold both eyes side by side at the model's resolution
   const char* enc = reinterpret_cast<const char*>(frame->encoding.data());
@@ -296,6 +407,7 @@ void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSha
     RCLCPP_ERROR(kLog, "Only support nv12 img encoding!");
     return;
   }
+  if (rectify_ && !(frame = RectifyFrame(received))) return;
   if ((int)frame->height != net_h_ || (int)frame->width != 2 * net_w_) {
     RCLCPP_ERROR_STREAM(kLog, "recved img msg h: " << frame->height << ", w: " << frame->width
                                                    << " is unmatch with model_input_width: " << net_w_

@@ -274,6 +274,7 @@ struct sn_handle {
     GrowBuf buf[kCount];
   } smo;
   std::atomic<int> temporal_live{0};   // sn_temporal objects created on this handle and not yet destroyed: sn_destroy refuses
+  std::atomic<int> rectify_live{0};    // ... and sn_rectify objects
 };
 
 // sn_temporal_*: the one post-processing stage with state.  What the filter's and the smoother's structs hold per handle, this
@@ -291,6 +292,21 @@ struct sn_temporal {
   GrowBuf buf[kCount];
   void* state = nullptr;             // one allocation: P int32 [streams][H*W], then Hs and Yp uint8 [streams][H*W]
   std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
+};
+
+// sn_rectify_*: the head of the chain.  Per object, as the temporal filter: stream, event, mutex, staging — plus the two maps.
+struct sn_rectify {
+  // host mode: the eyes' source spans (one merged span for a side-by-side frame), the rectified frames (also the scratch of a
+  // call that wants the tensor alone), the tensors
+  enum { kLeft = 0, kRight, kSbs, kTensor, kCount };
+  sn_handle* h = nullptr;
+  sn_stereo_calib c{};
+  uint32_t valid[2] = {0, 0};
+  std::mutex mu;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev = nullptr;           // the last enqueue that used the scratch and the staging
+  GrowBuf buf[kCount];
+  int32_t* map = nullptr;            // device [2][H][W][2]
 };
 
 namespace {

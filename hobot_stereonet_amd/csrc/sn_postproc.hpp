@@ -1,7 +1,7 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the pair-input staging, the per-call host staging and the overlap predicate — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother and temporal filter.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp and sn_temporal.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter and rectifier.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp and sn_rectify.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -790,6 +790,158 @@ int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t*
   }
   if (int e = s.download()) return e;
   HIP_TRY(h, hipEventRecord(t->ev, st));
+  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
+  return SN_OK;
+}
+
+// ---- stereo rectification (csrc/sn_rectify.hpp): an object with its own maps, stream, event and mutex -------------------------
+int sn_rectify_build_map(const sn_stereo_calib* c, int eye, int w, int h_px, int32_t* map_xy) {
+  if (!rect_calib_ok(c) || !map_xy || (eye != 0 && eye != 1) || w < 1 || h_px < 1) return SN_ERR_ARG;
+  rectify_build_map(*c, eye, w, h_px, map_xy);
+  return SN_OK;
+}
+
+int sn_rectify_create(sn_handle* h, const sn_stereo_calib* c, sn_rectify** out) {
+  if (!h) return SN_ERR_ARG;
+  if (!out || !rect_calib_ok(c)) {
+    set_err(h, "sn_rectify_create: bad arguments");
+    return SN_ERR_ARG;
+  }
+  if ((h->W & 3) || (h->H & 1)) {
+    set_err(h, "sn_rectify_create: the model's width must be a multiple of 4 and its height even");
+    return SN_ERR_ARG;
+  }
+  const int rc = check_device(h);
+  if (rc) return rc;
+  const size_t words = (size_t)h->H * h->W * 2;
+  std::vector<int32_t> maps;
+  try {
+    maps.resize(2 * words);
+  } catch (const std::bad_alloc&) {
+    set_err(h, "sn_rectify_create: out of memory");
+    return SN_ERR_NOMEM;
+  }
+  std::unique_ptr<sn_rectify> r(new sn_rectify);
+  r->h = h;
+  r->c = *c;
+  for (int eye = 0; eye < 2; ++eye) r->valid[eye] = rectify_build_map(*c, eye, h->W, h->H, maps.data() + eye * words);
+  if (hipMalloc(&r->map, 2 * words * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    set_err(h, "sn_rectify_create: out of device memory");
+    return SN_ERR_NOMEM;
+  }
+  if (hipMemcpy(r->map, maps.data(), 2 * words * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(r->map);
+    set_err(h, "sn_rectify_create: the upload of the maps failed");
+    return SN_ERR_DEVICE;
+  }
+  ++h->rectify_live;
+  *out = r.release();
+  return SN_OK;
+}
+
+void sn_rectify_destroy(sn_rectify* r) {
+  if (!r) return;
+  (void)hipSetDevice(r->h->device);
+  if (r->stream) (void)hipStreamSynchronize(r->stream);
+  if (r->ev) {
+    (void)hipEventSynchronize(r->ev);      // a call that was only enqueued on a caller's stream
+    (void)hipEventDestroy(r->ev);
+  }
+  if (r->stream) (void)hipStreamDestroy(r->stream);
+  for (GrowBuf& b : r->buf) b.release();
+  (void)hipFree(r->map);
+  --r->h->rectify_live;
+  delete r;
+}
+
+int sn_rectify_get_info(const sn_rectify* r, sn_rectify_info* info) {
+  if (!r || !info) return SN_ERR_ARG;
+  *info = sn_rectify_info{r->c.src_w, r->c.src_h, r->h->W, r->h->H, r->valid[0], r->valid[1]};
+  return SN_OK;
+}
+
+int sn_rectify_get_camera(const sn_rectify* r, sn_camera* cam) {
+  if (!r || !cam) return SN_ERR_ARG;
+  *cam = sn_camera{(float)r->c.pfx, (float)r->c.pfy, (float)r->c.pcx, (float)r->c.pcy, (float)r->c.baseline_mm, 0.f, 0.f, 1};
+  return SN_OK;
+}
+
+int sn_rectify_get_map(sn_rectify* r, int eye, int32_t* map_xy_host) {
+  if (!r) return SN_ERR_ARG;
+  sn_handle* h = r->h;
+  if (!map_xy_host || (eye != 0 && eye != 1)) {
+    set_err(h, "sn_rectify_get_map: bad arguments");
+    return SN_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(r->mu);
+  const int rc = check_device(h);
+  if (rc) return rc;
+  const size_t words = (size_t)h->H * h->W * 2;
+  HIP_TRY(h, hipMemcpy(map_xy_host, r->map + eye * words, words * 4, hipMemcpyDeviceToHost));
+  return SN_OK;
+}
+
+int sn_rectify_nv12(sn_rectify* r, int n, const uint8_t* left, const uint8_t* right, int src_pitch, size_t src_frame,
+                    uint8_t* out_sbs_nv12, int8_t* out_nchw6, int mem, void* stream) {
+  if (!r) return SN_ERR_ARG;
+  sn_handle* h = r->h;
+  const int sw = r->c.src_w, sh = r->c.src_h, rows = sh + sh / 2;
+  if (!left || !right || (!out_sbs_nv12 && !out_nchw6) || n <= 0 || n > h->max_batch || src_pitch < sw ||
+      (size_t)src_pitch * rows > 0x7fffffffu) {
+    set_err(h, "sn_rectify_nv12: bad arguments");
+    return SN_ERR_ARG;
+  }
+  if (mem == SN_MEM_DEVICE && (((uintptr_t)out_sbs_nv12 | (uintptr_t)out_nchw6) & 3)) {
+    set_err(h, "sn_rectify_nv12: device outputs must be 4-byte aligned");
+    return SN_ERR_ARG;
+  }
+  const size_t HW = (size_t)h->H * h->W;
+  // an eye's span: from its first byte to the last byte of the last chroma row of pair n - 1
+  const size_t span = (size_t)(n - 1) * src_frame + (size_t)(rows - 1) * src_pitch + sw;
+  {
+    const Span l{left, span}, rr{right, span}, o{out_sbs_nv12, n * 3 * HW}, t{out_nchw6, n * 6 * HW};
+    if (overlap({l, rr}, {o, t}) || overlap({o}, {t})) {
+      set_err(h, "sn_rectify_nv12: overlapping buffers (an input and an output, or the two outputs)");
+      return SN_ERR_ARG;
+    }
+  }
+  using R = sn_rectify;
+  std::lock_guard<std::mutex> lk(r->mu);
+  Call c;
+  const int rc = enter(h, "sn_rectify_nv12", mem, stream, &r->stream, &c);
+  if (rc) return rc;
+  if (!r->ev) HIP_TRY(h, hipEventCreateWithFlags(&r->ev, hipEventDisableTiming));
+  hipStream_t st = c.st;
+  HIP_TRY(h, hipStreamWaitEvent(st, r->ev, 0));      // the previous call (any stream) is done with the scratch and the staging
+  Staging s{h, "sn_rectify_nv12", st, c.host, r->buf};
+  const uint8_t *dl = left, *dr = right;
+  if (c.host) {
+    // a side-by-side frame's eyes share their rows: one upload from the lower address, and both eyes keep their offsets
+    const uint8_t *lo = left < right ? left : right, *hi = left < right ? right : left;
+    if ((size_t)(hi - lo) < span) {
+      const uint8_t* d = s.in(R::kLeft, lo, (size_t)(hi - lo) + span);
+      dl = d ? d + (left - lo) : nullptr;
+      dr = d ? d + (right - lo) : nullptr;
+    } else {
+      dl = s.in(R::kLeft, left, span);
+      dr = s.in(R::kRight, right, span);
+    }
+  }
+  uint8_t* dsbs = s.out(R::kSbs, out_sbs_nv12, n * 3 * HW, out_nchw6 != nullptr);      // k_pre_nv12 reads the rectified frame
+  int8_t* dten = s.out(R::kTensor, out_nchw6, n * 6 * HW);
+  if (s.rc) return s.rc;
+  RectArgs a{{dl, dr}, r->map, dsbs, src_frame, src_pitch, sw, sh, h->W, h->H, n};
+  const int items = (h->H + h->H / 2) * (h->W / 4);
+  hipLaunchKernelGGL(k_rectify, dim3((items + 255) / 256, 2), dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  if (dten) {
+    const int e = sbs_to_tensors(h, st, n, dsbs, 2 * h->W, h->H, false, dten);
+    if (e) return e;
+  }
+  if (int e = s.download()) return e;
+  HIP_TRY(h, hipEventRecord(r->ev, st));
   if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
   return SN_OK;
 }

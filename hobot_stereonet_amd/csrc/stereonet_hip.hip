@@ -1,7 +1,7 @@
 // stereonet_hip.hip — the one translation unit of the engine of libstereonet_hip.so: the headers below, one concern each and
 // included in order, then the engine's own part of the public C ABI (include/stereonet_hip.h): create / destroy, io info,
 // SN_PREC_AUTO's state machine, infer, preprocess, submit / wait and the measurement hooks.  The entry points that follow the
-// network — depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter — and the host helpers they share with the ones
+// network — depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, rectifier — and the host helpers they share with the ones
 // here (entry preamble, NV12 launcher) are in sn_postproc.hpp.  DESIGN.md §6 has the source map.
 //
 // Replaces, for the StereoNet hot path, what the reference obtains from the closed dnn_node /
@@ -28,18 +28,19 @@
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
 #include "sn_switches.hpp"      // the SN_* environment switches
-#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp, sn_smooth.hpp, sn_temporal.hpp)
+#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_rectify.hpp)
 #include "sn_pointcloud.hpp"
 #include "sn_lrcheck.hpp"
 #include "sn_dispfilter.hpp"
 #include "sn_confidence.hpp"
 #include "sn_smooth.hpp"
 #include "sn_temporal.hpp"
+#include "sn_rectify.hpp"
 #include "sn_engine.hpp"        // handle, workspace and layer types, error and allocation helpers
 #include "sn_weights.hpp"       // .snw reader, weight packing and upload
 #include "sn_launch.hpp"        // kernel launchers and tensor geometry
 #include "sn_forward.hpp"       // workspace allocation, forward pass, refinement statistic, SN_PREC_AUTO
-#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter, smoother, temporal filter
+#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter, smoother, temporal filter, rectifier
 #include "sn_dbg_hooks.hpp"     // sn_dbg_* parity hooks
 
 // =====================================================================================================
@@ -354,6 +355,10 @@ int sn_destroy(sn_handle* h) {
   if (!h) return SN_ERR_ARG;
   if (h->temporal_live.load() > 0) {      // a live sn_temporal holds this handle: refused, nothing is freed
     set_err(h, "sn_destroy: the handle still has temporal filters (sn_temporal_destroy them first)");
+    return SN_ERR_BUSY;
+  }
+  if (h->rectify_live.load() > 0) {
+    set_err(h, "sn_destroy: the handle still has rectifiers (sn_rectify_destroy them first)");
     return SN_ERR_BUSY;
   }
   hipSetDevice(h->device);

@@ -6,7 +6,7 @@ D1) needed to score the output against dataset ground truth.
         [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
         [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
-        [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]]
+        [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -44,6 +44,12 @@ temporal filter (`sn_temporal_push`, one stream): a measurement within DELTA_PX 
 map feeds the metrics, --ply and --out; <i>.temporal.pgm holds the mask (temporal.BITS: a plane of its own), every record
 gains "blended", "held" and "density", the summary their totals and mean and "flicker_before" / "flicker_after" (mean frame to
 frame change in px over pixels measured in both frames).  With ground truth the record gains "temporal_epe", before and after.
+
+--rectify takes a calibration file (rectify.load_calib: size, left.K / .D / .R, right.K / .D / .R, P, baseline_mm).  The listed
+images are then RAW, of the calibration's source size: they are converted to NV12 as always, rectified on the GPU
+(`sn_rectify_nv12`) into the side-by-side frame of the model's size, and that frame feeds everything above unchanged.
+<i>.rect.ppm holds the rectified frame (both eyes, RGB), --ply takes its camera from the rectifier unless --camera is given,
+and the summary gains "valid_left" / "valid_right", the pixels of each eye that have a source.
 """
 import argparse
 import json
@@ -118,7 +124,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
-                lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None) -> List[dict]:
+                lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -136,7 +142,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     and with ground truth "smooth_epe" = {"before", "after", "valid_px"} over the pixels that held a measurement before it.
     temporal = (alpha, delta_px, persist, luma_delta): the list is one clip; the maps pass last through one api.TemporalFilter
     that lives for the call; the record gains "temporal_in" (the map before the step), "temporal_mask", "blended", "held" and
-    "density", <i>.temporal.pgm is written, and with ground truth "temporal_epe" as "smooth_epe"."""
+    "density", <i>.temporal.pgm is written, and with ground truth "temporal_epe" as "smooth_epe".
+    rectify = a rectify.Calib: the images are raw eyes of its source size; one api.Rectifier lives for the call and turns every
+    pair into the rectified side-by-side frame that feeds all of the above; the record gains "rect" (that frame), <i>.rect.ppm is
+    written, the record gains "valid_left" / "valid_right", and `camera` defaults to the rectifier's."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -147,26 +156,35 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     w, h = engine.width, engine.height
     results = []
     tf = engine.temporal_filter(1, *temporal) if temporal is not None else None
+    rect = None
     try:
-        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results)
+        if rectify is not None:
+            rect = engine.rectifier(rectify)
+            camera = camera or rect.camera
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect)
     finally:
+        if rect is not None:
+            rect.close()
         if tf is not None:
             tf.close()
     return results
 
 
-def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results):
+def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None):
     w, h = engine.width, engine.height
+    iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
+    valid = rect.info if rect is not None else None
     for i, (lp, rp) in enumerate(zip(left, right)):
         if log:
             log(f"Feed {i}/{len(left)}")
         eyes = []
         for p in (lp, rp):
             bgr = images.imread_bgr(p)
-            if bgr.shape[:2] != (h, w):
-                raise FileListError(f"BGRToNv12 Fail: {p} is {bgr.shape[1]}x{bgr.shape[0]}, model input is {w}x{h}")
+            if bgr.shape[:2] != (ih, iw):
+                raise FileListError(f"BGRToNv12 Fail: {p} is {bgr.shape[1]}x{bgr.shape[0]}, "
+                                    f"{'the calibration is for' if rect is not None else 'model input is'} {iw}x{ih}")
             eyes.append(images.bgr_to_nv12(bgr))
-        sbs = images.sbs_from_eyes(eyes[0], eyes[1], w, h)
+        sbs = images.sbs_from_eyes(eyes[0], eyes[1], w, h) if rect is None else rect.rectify(eyes[0], eyes[1])[0]
         cf = None
         if conf is not None and lrc is not None:
             disp, raw, cf = engine.infer_conf(sbs)
@@ -182,6 +200,8 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             disp, raw, mask, kept = engine.infer_lrc(sbs, lrc[0], lrc[1])
         masked = lrc is not None or conf is not None
         rec = {"frame_id": str(i), "left": lp, "right": rp, "raw": raw, "disp": disp}
+        if rect is not None:
+            rec.update(rect=sbs, valid_left=valid["valid_left"], valid_right=valid["valid_right"])
         if masked:
             rec["mask"] = mask
             rec["density"] = float(kept[0]) / float(w * h)
@@ -231,6 +251,9 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             from . import render
             _, depth = render.disparity_and_depth(raw.view(np.uint32))
             images.write_ppm(os.path.join(out_dir, f"{i}.depth.ppm"), render.colorize_depth(depth)[..., ::-1])
+            if rect is not None:
+                from . import rectify as rct
+                images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
             if masked:
                 images.write_ppm(os.path.join(out_dir, f"{i}.mask.pgm"), mask)      # 2-D: written as a P5 greymap
             if cf is not None:
@@ -275,6 +298,9 @@ def main(argv=None) -> int:
                          "new measurement in 1/256, DELTA_PX the largest change that is still blended, PERSIST 0..8 (default 2) "
                          "how many of the last eight inputs must be valid to hold a value, LUMA_DELTA 0..255 (default 0 = off) "
                          "the luma change that counts as motion")
+    ap.add_argument("--rectify", default=None, metavar="CALIB",
+                    help="calibration file (size, left.K/.D/.R, right.K/.D/.R, P, baseline_mm): the listed images are raw, of "
+                         "its source size, and are rectified on the GPU to the model's size before everything else")
     args = ap.parse_args(argv)
     from . import api, pointcloud
     cam = None
@@ -340,16 +366,27 @@ def main(argv=None) -> int:
         if len(v) != 4 or not (1 <= v[0] <= 256 and np.isfinite(v[1]) and v[1] >= 0 and 0 <= v[2] <= 8 and 0 <= v[3] <= 255):
             ap.error("--temporal takes ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]: 1..256, a finite difference >= 0, 0..8 and 0..255")
         temporal = tuple(v)
+    calib = None
+    if args.rectify is not None:
+        from . import rectify as rct
+        try:
+            calib = rct.load_calib(args.rectify)
+        except (OSError, ValueError) as e:
+            ap.error(f"--rectify takes a calibration file: {e}")
+        if not calib.ok():
+            ap.error("--rectify takes a calibration file: sizes even and 2..8192, every value finite, focal lengths and baseline > 0")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
-                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal)
+                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
     summary = {"frames": len(recs)}
+    if calib is not None and recs:
+        summary["valid_left"], summary["valid_right"] = recs[0]["valid_left"], recs[0]["valid_right"]
     if args.gt and recs:
         for k in ("epe", "bad1", "bad3", "d1"):
             summary[k] = float(np.nanmean([r["metrics"][k] for r in recs]))

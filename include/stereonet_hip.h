@@ -682,6 +682,90 @@ int  sn_temporal_push(sn_temporal *t, int n, const int *stream_of, const int32_t
                       int guide_pitch, int32_t *out_raw, float *disp_inout, uint8_t *mask, uint32_t *counts, int mem,
                       void *stream);
 
+/* ---- stereo rectification from the camera calibration: the head of the chain ----------------------------------------------------
+ * Every stage above assumes a RECTIFIED pair: undistorted, row-aligned and exactly the model's W x H.  sn_rectify makes one
+ * from raw NV12 frames of any source size and a calibration in the form a ROS CameraInfo pair or OpenCV's stereoRectify
+ * delivers: K, D (plumb-bob k1 k2 p1 p2 k3) and R per eye and the common rectified projection P.  It writes the side-by-side
+ * NV12 frame that sn_infer_sbs_nv12, sn_submit_nv12, sn_infer_lrc, the point cloud's colour and the guides take, optionally the
+ * int8 model tensor, and hands back the sn_camera of the rectified left eye. */
+typedef struct sn_eye_calib { double fx, fy, cx, cy; double d[5]; double R[9]; } sn_eye_calib;
+typedef struct sn_stereo_calib {
+  int src_w, src_h;                 /* one eye of the raw frame; both even, 2..8192                              */
+  sn_eye_calib left, right;
+  double pfx, pfy, pcx, pcy;        /* common rectified projection, in pixels of the model's W x H               */
+  double baseline_mm;               /* > 0; passed through to sn_camera                                          */
+} sn_stereo_calib;
+typedef struct sn_rectify sn_rectify;
+typedef struct sn_rectify_info { int src_w, src_h, w, h; uint32_t valid_left, valid_right; } sn_rectify_info;
+/* Two stages with an exact interface between them, so that every comparison with the numpy twin
+ * (hobot_stereonet_amd/rectify.py) is bit for bit.
+ *
+ * Stage A: the map.  Built once per calibration, on the host, in double.  For an eye with source intrinsics fx fy cx cy,
+ * distortion k1 k2 p1 p2 k3 = d[0..4], rectifying rotation R (row-major, source camera to rectified camera) and the common
+ * rectified projection pfx pfy pcx pcy, for every destination pixel (u, v), 0 <= u < W, 0 <= v < H, in exactly this order of
+ * operations, every step one rounded IEEE operation, no FMA (sw x sh = src_w x src_h):
+ *
+ *   x = ((double)u - pcx) / pfx;            y = ((double)v - pcy) / pfy
+ *   X = R[0]*x + R[3]*y + R[6];  Y = R[1]*x + R[4]*y + R[7];  Wc = R[2]*x + R[5]*y + R[8]     (R^T * [x y 1], left to right)
+ *   if !(Wc > 0): sentinel
+ *   a = X/Wc; b = Y/Wc; a2 = a*a; b2 = b*b; r2 = a2 + b2; ab2 = 2.0*(a*b)
+ *   rad = 1.0 + r2*(k1 + r2*(k2 + r2*k3))
+ *   xd = a*rad + (p1*ab2 + p2*(r2 + 2.0*a2));      yd = b*rad + (p1*(r2 + 2.0*b2) + p2*ab2)
+ *   us = fx*xd + cx;  vs = fy*yd + cy
+ *   if !(us > -1 && us < sw && vs > -1 && vs < sh): sentinel         (NaN fails the test: sentinel)
+ *   mx = (int32)floor(us*256.0 + 0.5);  my = (int32)floor(vs*256.0 + 0.5)
+ *
+ * The map is int32 [H][W][2] = (mx, my), in units of 1/256 source pixel.  Integer coordinates are pixel centres (OpenCV's
+ * convention).  The sentinel is (INT32_MIN, INT32_MIN).
+ *
+ * Stage B: the remap.  Per frame, on the GPU, in integers.  With B the border value (0 for luma, 128 for chroma) and a source
+ * plane of pw x ph samples:
+ *
+ *   sentinel            -> out = B
+ *   x0 = mx >> 8 (arithmetic), y0 = my >> 8, fx = mx & 255, fy = my & 255
+ *   p(i,j) = source sample at (x0+i, y0+j) if 0 <= x0+i < pw and 0 <= y0+j < ph, else B        (per tap)
+ *   out = ((256-fx)*(256-fy)*p(0,0) + fx*(256-fy)*p(1,0) + (256-fx)*fy*p(0,1) + fx*fy*p(1,1) + 32768) >> 16
+ *
+ * Luma: the formula at every (u, v) on the sw x sh luma plane.  Chroma: true NV12, interleaved UV rows, W/2 x H/2 samples; for
+ * chroma sample (cj, ci) take the luma map entry at (2cj, 2ci); if it is not the sentinel, (mx >> 1, my >> 1) is a Q8
+ * coordinate on the sw/2 x sh/2 chroma plane, and U and V are blended separately with the same weights.  The identity
+ * calibration gives mx = 256u, and the output equals the input byte for byte.
+ *
+ * sn_rectify_build_map: Stage A of eye `eye` (0 left, 1 right) for a w x h destination into map_xy [h][w][2].  Pure host: no
+ *   device and no handle.  SN_ERR_ARG: a NULL pointer, an eye other than 0 or 1, w or h < 1, src_w or src_h odd or outside
+ *   2..8192, a non-finite field, fx, fy (of either eye), pfx, pfy or baseline_mm <= 0.
+ * sn_rectify_create: a rectifier for handle h's model size W x H.  The same checks, and W % 4 != 0 or an odd H is SN_ERR_ARG
+ *   (sn_last_error(h) says so: the frames of such a model are not accepted by the side-by-side entry points either).  Both maps
+ *   are built on the host and uploaded (2 * H * W * 8 bytes); a stream, an event, a mutex and the staging are the object's own.
+ *   While a rectifier is alive sn_destroy(h) is REFUSED with SN_ERR_BUSY, as for sn_temporal.
+ * sn_rectify_get_info: the sizes and valid_left / valid_right, the number of map entries that are not the sentinel.
+ * sn_rectify_get_camera: {(float)pfx, (float)pfy, (float)pcx, (float)pcy, (float)baseline_mm, 0, 0, 1}.
+ * sn_rectify_get_map: downloads the device copy of an eye's map into map_xy_host [H][W][2] (the maps never change after create).
+ * sn_rectify_nv12: n raw pairs, 1 <= n <= max_batch.  Pair k's eyes are at left + k*src_frame and right + k*src_frame; each eye
+ *   is an NV12 image of luma pitch src_pitch: src_h luma rows, then src_h/2 interleaved chroma rows of the same pitch.  A
+ *   side-by-side camera frame is right = left + src_w with src_pitch >= 2*src_w; separate eyes are two buffers of pitch >=
+ *   src_w.  Source pointers need no alignment.  src_pitch * src_h * 3/2 must be below 2^31.
+ *   out_sbs_nv12 (nullable): [n] side-by-side frames of pitch 2W, 3*W*H bytes each.
+ *   out_nchw6 (nullable): [n][6][H][W], sn_preprocess_sbs_nv12_batch's tensor of the rectified frame, written on the same
+ *     stream (through the object's scratch when out_sbs_nv12 is NULL).  At least one of the two outputs is required;
+ *     device-mode outputs must be 4-byte aligned.
+ *   Overlap between any input span and any output span, or between the outputs, is SN_ERR_ARG.
+ *   SN_ERR_ARG (sn_last_error(h) names the call; nothing is launched): n out of range, an input NULL, both outputs NULL,
+ *     src_pitch < src_w, a frame too large, a misaligned device output, overlapping buffers, a bad mem.
+ *   mem / stream as sn_temporal_push: a NULL stream is the rectifier's own stream (never the inference stream); the call
+ *   returns after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller stream only enqueue.  May
+ *   run beside sn_submit / sn_wait on the same handle; calls are serialised by the object's mutex, and calls on different
+ *   streams are ordered on the scratch by an event.  One remap launch per call.  Not covered: the asynchronous sn_submit*
+ *   slots, fisheye and rational distortion models, a principal point per eye (one pcx for both). */
+int  sn_rectify_build_map(const sn_stereo_calib *c, int eye, int w, int h, int32_t *map_xy);
+int  sn_rectify_create(sn_handle *h, const sn_stereo_calib *c, sn_rectify **out);
+void sn_rectify_destroy(sn_rectify *r);
+int  sn_rectify_get_info(const sn_rectify *r, sn_rectify_info *info);
+int  sn_rectify_get_camera(const sn_rectify *r, sn_camera *cam);
+int  sn_rectify_get_map(sn_rectify *r, int eye, int32_t *map_xy_host);
+int  sn_rectify_nv12(sn_rectify *r, int n, const uint8_t *left, const uint8_t *right, int src_pitch, size_t src_frame,
+                     uint8_t *out_sbs_nv12, int8_t *out_nchw6, int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
