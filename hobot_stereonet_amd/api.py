@@ -472,6 +472,23 @@ class StereoNetHIP:
         n = self._count(r)
         return n, np.empty_like(r), np.empty(r.shape, np.uint8), np.zeros(n if per_map == 1 else (n, per_map), np.uint32)
 
+    def _guide(self, guide, guide_kind: int, guide_pitch: int, n: int, where: str):
+        """The optional luma guide of n maps, checked against the model's size -> (the array to pass or None, the pitch to pass)."""
+        if guide is None:
+            return None, guide_pitch
+        w, h = self.width, self.height
+        if guide_kind == SN_GUIDE_TENSOR:
+            g = np.ascontiguousarray(guide, dtype=np.int8)
+            if g.shape not in ((6, h, w), (n, 6, h, w)) or g.size != n * 6 * h * w:
+                raise StereoNetError(-1, where, f"guide shape {g.shape} != ([{n},] 6, {h}, {w})")
+            return g, guide_pitch
+        g = np.ascontiguousarray(guide, dtype=np.uint8).reshape(-1)
+        guide_pitch = guide_pitch or w
+        need = (n - 1) * guide_pitch * (h + (h + 1) // 2) + guide_pitch * (h - 1) + w
+        if guide_pitch < w or g.size < need:      # the library cannot see how long a host buffer is
+            raise StereoNetError(-1, where, f"guide of {g.size} bytes, {n} frames of pitch {guide_pitch} take {need}")
+        return g, guide_pitch
+
     def depth_from_raw(self, raw: np.ndarray, focal_px: float = 527.1931762695312, baseline_mm: float = 119.89382172,
                        want_disp: bool = False):
         """Parse()'s dequantisation + depth (parser.cpp:84-86) on the GPU: int32 (H,W) or (n,H,W) -> depth in metres
@@ -705,19 +722,7 @@ class StereoNetHIP:
         r = self._maps(raw, "smooth_raw")
         dp = self._disp_ptr(disp, r.shape, "smooth_raw")
         n, out, mask, counts = self._mask_outputs(r, 3)
-        g = None
-        w, h = self.width, self.height
-        if guide is not None:
-            if guide_kind == SN_GUIDE_TENSOR:
-                g = np.ascontiguousarray(guide, dtype=np.int8)
-                if g.shape not in ((6, h, w), (n, 6, h, w)) or g.size != n * 6 * h * w:
-                    raise StereoNetError(-1, "smooth_raw", f"guide shape {g.shape} != ([{n},] 6, {h}, {w})")
-            else:
-                g = np.ascontiguousarray(guide, dtype=np.uint8).reshape(-1)
-                guide_pitch = guide_pitch or w
-                need = (n - 1) * guide_pitch * (h + (h + 1) // 2) + guide_pitch * (h - 1) + w
-                if guide_pitch < w or g.size < need:      # the library cannot see how long a host buffer is
-                    raise StereoNetError(-1, "smooth_raw", f"guide of {g.size} bytes, {n} frames of pitch {guide_pitch} take {need}")
+        g, guide_pitch = self._guide(guide, guide_kind, guide_pitch, n, "smooth_raw")
         p = SnSmoothParams(int(radius), int(sigma_luma), int(min_valid))
         self._check(self._lib.sn_smooth_raw(self._h, n, r.ctypes.data, _np_ptr(g), guide_kind, guide_pitch, C.byref(p),
                                             out.ctypes.data, dp, mask.ctypes.data, counts.ctypes.data, SN_MEM_HOST, None),
@@ -1033,21 +1038,16 @@ class StereoNetMultiGPU:
             pass
 
 
-class TemporalFilter:
-    """sn_temporal: the temporal filter of disparity streams, with its per-stream state on the GPU (temporal.reference is the
-    numpy twin).  A context object: the engine refuses to close while one of its filters is open."""
-
-    def __init__(self, engine: StereoNetHIP, streams: int = 1, alpha: int = 64, delta_px: float = 0.5, persist: int = 2,
-                 luma_delta: int = 0):
-        self._eng, self._lib, self._t = engine, engine._lib, C.c_void_p()
-        self.streams, self.params = int(streams), SnTemporalParams(int(alpha), delta_px, int(persist), int(luma_delta))
-        engine._check(self._lib.sn_temporal_create(engine._h, self.streams, C.byref(self.params), C.byref(self._t)),
-                      "sn_temporal_create")
+class _Owned:
+    """The lifecycle of an object created on an engine: `_destroy` names the library's destroy function, `_handle` the
+    attribute that holds the object's handle.  close() is idempotent; the object is a context manager."""
+    _destroy = _handle = ""
 
     def close(self):
-        if getattr(self, "_t", None) and self._t.value:
-            self._lib.sn_temporal_destroy(self._t)
-            self._t = C.c_void_p()
+        p = getattr(self, self._handle, None)
+        if p:      # a c_void_p of NULL is false
+            getattr(self._lib, self._destroy)(p)
+            setattr(self, self._handle, C.c_void_p())
 
     def __del__(self):
         try:
@@ -1060,6 +1060,19 @@ class TemporalFilter:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class TemporalFilter(_Owned):
+    """sn_temporal: the temporal filter of disparity streams, with its per-stream state on the GPU (temporal.reference is the
+    numpy twin).  A context object: the engine refuses to close while one of its filters is open."""
+    _destroy, _handle = "sn_temporal_destroy", "_t"
+
+    def __init__(self, engine: StereoNetHIP, streams: int = 1, alpha: int = 64, delta_px: float = 0.5, persist: int = 2,
+                 luma_delta: int = 0):
+        self._eng, self._lib, self._t = engine, engine._lib, C.c_void_p()
+        self.streams, self.params = int(streams), SnTemporalParams(int(alpha), delta_px, int(persist), int(luma_delta))
+        engine._check(self._lib.sn_temporal_create(engine._h, self.streams, C.byref(self.params), C.byref(self._t)),
+                      "sn_temporal_create")
 
     def reset(self, stream: int = -1):
         """Stream `stream` (-1: all) starts afresh at its next push."""
@@ -1084,19 +1097,7 @@ class TemporalFilter:
         dp = eng._disp_ptr(disp, r.shape, "temporal push")
         n, out, mask, counts = eng._mask_outputs(r, 4)
         ids = self._ids(stream_of, n)
-        g = None
-        w, h = eng.width, eng.height
-        if guide is not None:
-            if guide_kind == SN_GUIDE_TENSOR:
-                g = np.ascontiguousarray(guide, dtype=np.int8)
-                if g.shape not in ((6, h, w), (n, 6, h, w)) or g.size != n * 6 * h * w:
-                    raise StereoNetError(-1, "temporal push", f"guide shape {g.shape} != ([{n},] 6, {h}, {w})")
-            else:
-                g = np.ascontiguousarray(guide, dtype=np.uint8).reshape(-1)
-                guide_pitch = guide_pitch or w
-                need = (n - 1) * guide_pitch * (h + (h + 1) // 2) + guide_pitch * (h - 1) + w
-                if guide_pitch < w or g.size < need:      # the library cannot see how long a host buffer is
-                    raise StereoNetError(-1, "temporal push", f"guide of {g.size} bytes, {n} frames of pitch {guide_pitch} take {need}")
+        g, guide_pitch = eng._guide(guide, guide_kind, guide_pitch, n, "temporal push")
         eng._check(self._lib.sn_temporal_push(self._t, n, _np_ptr(ids), r.ctypes.data, _np_ptr(g), guide_kind, guide_pitch,
                                               out.ctypes.data, dp, mask.ctypes.data, counts.ctypes.data, SN_MEM_HOST, None),
                    "sn_temporal_push")
@@ -1113,33 +1114,17 @@ class TemporalFilter:
                                                     counts_ptr or None, SN_MEM_DEVICE, stream or None), "sn_temporal_push")
 
 
-class Rectifier:
+class Rectifier(_Owned):
     """sn_rectify: raw NV12 pairs of the calibration's source size -> rectified side-by-side NV12 frames of the model's size
     (and the int8 model tensor), on the GPU (rectify.reference is the numpy twin).  A context object: the engine refuses to
     close while one of its rectifiers is open."""
+    _destroy, _handle = "sn_rectify_destroy", "_r"
 
     def __init__(self, engine: StereoNetHIP, calib):
         self._eng, self._lib, self._r = engine, engine._lib, C.c_void_p()
         self.calib = stereo_calib(calib)
         engine._check(self._lib.sn_rectify_create(engine._h, C.byref(self.calib), C.byref(self._r)), "sn_rectify_create")
         self.src_w, self.src_h = self.calib.src_w, self.calib.src_h
-
-    def close(self):
-        if getattr(self, "_r", None) and self._r.value:
-            self._lib.sn_rectify_destroy(self._r)
-            self._r = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     @property
     def info(self) -> dict:

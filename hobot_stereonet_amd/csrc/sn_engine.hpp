@@ -55,6 +55,27 @@ struct GrowBuf {
   }
 };
 
+// A lane: what a post-processing stage owns so that it may run beside sn_submit / sn_wait and on any stream of the caller's.
+// Slots names the buffers (an enum that ends in kCount).  Everything is created on first use; the call bracket that locks,
+// orders and stages a call on a lane is LaneCall (sn_postproc.hpp).
+template <class Slots>
+struct Lane : Slots {
+  std::mutex mu;
+  hipStream_t stream = nullptr;      // the stage's own stream: a call without a stream of the caller's runs here
+  hipEvent_t ev = nullptr;           // the last enqueue (on any stream) that used the buffers or the owner's state
+  GrowBuf buf[Slots::kCount];
+  void destroy() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (ev) {
+      (void)hipEventSynchronize(ev);      // a call that was only enqueued on a caller's stream
+      (void)hipEventDestroy(ev);
+    }
+    if (stream) (void)hipStreamDestroy(stream);
+    for (GrowBuf& b : buf) b.release();
+    stream = nullptr, ev = nullptr;
+  }
+};
+
 struct ConvLayer {
   uint4* wx3 = nullptr;    // device, split fp16 A-fragments [cin_pad/16][9][hi|lo][64 lanes] (fp16 modes, 3x3 layers)
   float* wpk = nullptr;    // device, packed [cin_pad][taps][32]
@@ -238,74 +259,62 @@ struct sn_handle {
   float stage_ms[SN_STAGE_COUNT] = {};
   mutable std::string err;
   mutable std::mutex err_mu;  // err is written by failing calls on any thread (sn_pointcloud_from_raw beside sn_wait)
-  // sn_pointcloud_from_raw: everything of its own (it may run beside sn_submit / sn_wait), created on its first call
-  struct PointCloud {
-    // compact form: valid samples per tile; host mode: raw, nv12, points, counts, and the pinned staging of raw and nv12
+  // The lanes of the handle's post-processing stages (Lane above): each may run beside sn_submit / sn_wait.
+  // sn_pointcloud_from_raw.  compact form: valid samples per tile; host mode: raw, nv12, points, counts, and the pinned staging
+  // of raw and nv12
+  struct PointCloudSlots {
     enum { kScratch = 0, kRaw, kNv12, kPoints, kCounts, kPinRaw, kPinNv12, kCount };
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
-    GrowBuf buf[kCount];
+  };
+  struct PointCloud : Lane<PointCloudSlots> {
     PointCloud() { buf[kPinRaw].pinned = buf[kPinNv12].pinned = true; }
   } pc;
-  // The staging of the calls that run on the inference stream (sn_mirror_pair_i8 / sn_lr_check / sn_infer_lrc / sn_infer_conf /
-  // sn_conf_mask): host-mode copies and the composites' intermediate maps.  No lock: calls on one handle must not overlap.
+  // sn_filter_raw.  label[slice][H][W] then size[slice][H][W]; host mode: map (filtered in place), float map, mask, counts
+  struct FilterSlots {
+    enum { kScratch = 0, kRaw, kDisp, kMask, kCounts, kCount };
+  };
+  using Filter = Lane<FilterSlots>;
+  Filter flt;
+  // sn_smooth_raw.  the copy of a slice that an in-place call reads; host mode: map, guide, result, float map, mask, counts
+  struct SmoothSlots {
+    enum { kScratch = 0, kRaw, kGuide, kOut, kDisp, kMask, kCounts, kCount };
+  };
+  using Smooth = Lane<SmoothSlots>;
+  Smooth smo;
+  // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
+  // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
+  // lock: calls on one handle must not overlap.
   struct InferStaging {
     // input tensor, mirrored tensor, left map (masked in place), second map, float map, right map, mask, kept, confidence
     enum { kIn = 0, kMirror, kLeft, kRight, kDisp, kRightOut, kMask, kKept, kConf, kCount };
     GrowBuf buf[kCount];
   } stage;
-  // sn_filter_raw: everything of its own as the point cloud has (it may run beside sn_submit / sn_wait), created on first use
-  struct Filter {
-    // label[slice][H][W] then size[slice][H][W]; host mode: map (filtered in place), float map, mask, counts
-    enum { kScratch = 0, kRaw, kDisp, kMask, kCounts, kCount };
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
-    GrowBuf buf[kCount];
-  } flt;
-  // sn_smooth_raw: everything of its own, as the filter has
-  struct Smooth {
-    // the copy of a slice that an in-place call reads; host mode: map, guide, result, float map, mask, counts
-    enum { kScratch = 0, kRaw, kGuide, kOut, kDisp, kMask, kCounts, kCount };
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;           // the last enqueue that used the scratch
-    GrowBuf buf[kCount];
-  } smo;
   std::atomic<int> temporal_live{0};   // sn_temporal objects created on this handle and not yet destroyed: sn_destroy refuses
   std::atomic<int> rectify_live{0};    // ... and sn_rectify objects
 };
 
-// sn_temporal_*: the one post-processing stage with state.  What the filter's and the smoother's structs hold per handle, this
-// object holds per filter — stream, event, mutex, host-mode staging — plus the state planes and the per-stream "fresh" flags.
-struct sn_temporal {
-  // host mode: map (filtered in place), guide, float map, mask, counts
+// sn_temporal_*: the one post-processing stage with state: a lane per filter, plus the state planes and the per-stream
+// "fresh" flags.  host mode: map (filtered in place), guide, float map, mask, counts
+struct sn_temporal_slots {
   enum { kRaw = 0, kGuide, kDisp, kMask, kCounts, kCount };
+};
+struct sn_temporal : Lane<sn_temporal_slots> {
   sn_handle* h = nullptr;
   int streams = 0;
   sn_temporal_params p{};
   long long q = 0;                   // delta_px in units of raw
-  std::mutex mu;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;           // the last enqueue that used the state and the staging
-  GrowBuf buf[kCount];
   void* state = nullptr;             // one allocation: P int32 [streams][H*W], then Hs and Yp uint8 [streams][H*W]
   std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
 };
 
-// sn_rectify_*: the head of the chain.  Per object, as the temporal filter: stream, event, mutex, staging — plus the two maps.
-struct sn_rectify {
-  // host mode: the eyes' source spans (one merged span for a side-by-side frame), the rectified frames (also the scratch of a
-  // call that wants the tensor alone), the tensors
+// sn_rectify_*: the head of the chain: a lane per object, plus the two maps.  host mode: the eyes' source spans (one merged
+// span for a side-by-side frame), the rectified frames (also the scratch of a call that wants the tensor alone), the tensors
+struct sn_rectify_slots {
   enum { kLeft = 0, kRight, kSbs, kTensor, kCount };
+};
+struct sn_rectify : Lane<sn_rectify_slots> {
   sn_handle* h = nullptr;
   sn_stereo_calib c{};
   uint32_t valid[2] = {0, 0};
-  std::mutex mu;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;           // the last enqueue that used the scratch and the staging
-  GrowBuf buf[kCount];
   int32_t* map = nullptr;            // device [2][H][W][2]
 };
 

@@ -1,5 +1,6 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
-// entry preamble, the k_pre_nv12 launcher, the pair-input staging, the per-call host staging and the overlap predicate — and
+// entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
+// call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
 // the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter and rectifier.  The kernels are in
 // sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp and sn_rectify.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
@@ -15,7 +16,7 @@ struct Call {
 };
 
 // What every entry point does after its own argument checks: `mem` is one of the two kinds, the handle's device is current,
-// and the call runs on `stream` or else on *own (h->stream; the point cloud's and the filter's are created on first use).
+// and the call runs on `stream` or else on *own (h->stream; a lane's is created on first use).
 int enter(sn_handle* h, const char* where, int mem, void* stream, hipStream_t* own, Call* c) {
   if (mem != SN_MEM_HOST && mem != SN_MEM_DEVICE) {
     set_err(h, std::string(where) + ": bad arguments");
@@ -44,6 +45,45 @@ bool overlap(std::initializer_list<Span> a, std::initializer_list<Span> b) {
       if (xl && yl && xl < yl + y.bytes && yl < xl + x.bytes) return true;
     }
   return false;
+}
+
+// The aliasing rule of the calls that mask a map (n maps of HW pixels): of raw, out_raw, disp, mask, counts (`per_map` words a
+// map) and the guide's span, only out_raw == raw may share a byte — the one overlap the kernels are written for.
+bool masked_map_overlap(size_t n, size_t HW, const int32_t* raw, const int32_t* out_raw, const float* disp, const uint8_t* mask,
+                        const uint32_t* counts, int per_map, Span guide = {nullptr, 0}) {
+  const Span r{raw, n * HW * 4}, o{out_raw, n * HW * 4}, d{disp, n * HW * 4}, m{mask, n * HW}, k{counts, n * per_map * 4};
+  return (out_raw != raw && overlap({r}, {o})) || overlap({r, o}, {d, m, k}) || overlap({d}, {m, k}) || overlap({m}, {k}) ||
+         overlap({guide}, {o, d, m, k});
+}
+
+// The luma guide of sn_smooth_raw / sn_temporal_push: n NV12 frames in rows of `guide_pitch` bytes, or n int8 model tensors.
+// used == false: the call ignores the guide altogether (it may be null, and its span is empty).
+struct GuideSpan {
+  bool ok;           // the argument test: a known kind, a guide where one is used, an NV12 pitch that is even and >= W
+  size_t frame;      // frame k of the guide starts at k * frame
+  Span span;         // what the call reads: the luma rows alone, so the last frame ends with the last of them
+  int pitch;         // of a luma row
+  uint32_t xor_;     // luma = byte ^ xor_: 0 (NV12) or 0x80 (the int8 model input)
+  GuideSpan(const sn_handle* h, int n, const void* guide, int kind, int guide_pitch, bool used) {
+    const bool nv12 = kind == SN_GUIDE_NV12;
+    const size_t HW = (size_t)h->H * h->W;
+    ok = !(used && !guide) && (nv12 || kind == SN_GUIDE_TENSOR) && !(nv12 && guide && (guide_pitch < h->W || (guide_pitch & 1)));
+    frame = nv12 ? (size_t)guide_pitch * (h->H + (h->H + 1) / 2) : 6 * HW;
+    span = used ? Span{guide, (n - 1) * frame + (nv12 ? (size_t)guide_pitch * (h->H - 1) + h->W : HW)} : Span{nullptr, 0};
+    pitch = nv12 ? guide_pitch : h->W;
+    xor_ = nv12 ? 0u : 0x80u;
+  }
+};
+
+// The args of the launch that starts at map k0: the per-map pointers of `all` moved on by k0 maps (a luma guide has its own stride)
+template <class A>
+void at_slice(A& a, const A& all, int k0, size_t HW, int counts_per_map) {
+  const size_t off = (size_t)k0 * HW;
+  a.raw = all.raw + off;
+  a.out_raw = all.out_raw ? all.out_raw + off : nullptr;
+  a.disp = all.disp ? all.disp + off : nullptr;
+  a.mask = all.mask ? all.mask + off : nullptr;
+  a.counts = all.counts ? all.counts + (size_t)k0 * counts_per_map : nullptr;
 }
 
 // ---- NV12 input ---------------------------------------------------------------------------------------------------------
@@ -104,7 +144,7 @@ struct Staging {
   T* scratch(int which, size_t bytes) {
     if (rc) return nullptr;
     if (slots[which].reserve(bytes) != hipSuccess) {
-      set_err(h, std::string(where) + ": out of device memory");
+      set_err(h, std::string(where) + (slots[which].pinned ? ": out of pinned host memory" : ": out of device memory"));
       rc = SN_ERR_NOMEM;
       return nullptr;
     }
@@ -115,6 +155,18 @@ struct Staging {
     if (!host) return user;
     T* d = scratch<T>(which, bytes);
     if (d && (rc = copy(d, user, bytes, hipMemcpyHostToDevice))) return nullptr;
+    return d;
+  }
+  // `in` by way of the pinned slot `pin`: the caller's pages may be pageable, and the call may run beside sn_submit / sn_wait.
+  // A host-mode call is blocking, so the one before it is done with the slot.
+  template <class T>
+  const T* in_pinned(int pin, int which, const T* user, size_t bytes) {
+    if (!host) return user;
+    void* p = scratch<void>(pin, bytes);
+    T* d = scratch<T>(which, bytes);
+    if (!d) return nullptr;
+    memcpy(p, user, bytes);
+    if ((rc = copy(d, p, bytes, hipMemcpyHostToDevice))) return nullptr;
     return d;
   }
   // a nullable output.  needed: the call itself reads it, so it has a device buffer even where the caller wants none
@@ -143,6 +195,49 @@ struct Staging {
   int download() {
     for (int i = 0; i < n_back; ++i)
       if (int e = copy(back[i].user, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost)) return e;
+    return SN_OK;
+  }
+};
+
+// ---- the call bracket ---------------------------------------------------------------------------------------------------
+// What every entry point opens after its argument checks and closes once.  Opening, on a lane: lock it, enter(), create its
+// event on first use, make the call's stream wait on the event, hand out the Staging `s`.  On the inference stream: enter() and
+// the Staging on the handle's InferStaging, no lock and no event (calls on one handle must not overlap).  A failure of the
+// opening sticks in s.rc, so an entry point names its buffers and tests s.rc once.  close(): the downloads, the record, the
+// sync of a blocking call.  An error exit returns before the record and writes no outputs.
+// The order is the same for every lane, and safe for each, because
+//   - the wait only enqueues, so nothing the host does after it (growing a buffer, the memcpy into a pinned slot) is held up,
+//     and everything the call enqueues after it follows the previous call's last use of the buffers, on whatever stream;
+//   - a buffer grows through GrowBuf::reserve, whose hipFree synchronises the device: no earlier call still uses the old one
+//     (a first allocation frees nothing, and has no earlier user);
+//   - the record follows the downloads, so the next call also waits for them; a call with downloads is a host-mode call, which
+//     is blocking and has finished them before it returns.
+struct Bracket {
+  Call c;
+  Staging s;
+  std::unique_lock<std::mutex> lk;
+  hipEvent_t ev = nullptr;
+
+  Bracket(sn_handle* h, const char* where, int mem, void* stream) : s{h, where, nullptr, false, h->stage.buf} {
+    s.rc = enter(h, where, mem, stream, &h->stream, &c);
+    s.st = c.st, s.host = c.host;
+  }
+  template <class L>
+  Bracket(sn_handle* h, const char* where, int mem, void* stream, L& lane) : s{h, where, nullptr, false, lane.buf}, lk(lane.mu) {
+    s.rc = open(mem, stream, lane.stream, lane.ev);
+    ev = lane.ev;
+  }
+  int open(int mem, void* stream, hipStream_t& own, hipEvent_t& lane_ev) {
+    if (int rc = enter(s.h, s.where, mem, stream, &own, &c)) return rc;
+    s.st = c.st, s.host = c.host;
+    if (!lane_ev) HIP_TRY(s.h, hipEventCreateWithFlags(&lane_ev, hipEventDisableTiming));
+    HIP_TRY(s.h, hipStreamWaitEvent(c.st, lane_ev, 0));
+    return SN_OK;
+  }
+  int close() {
+    if (int e = s.download()) return e;
+    if (ev) HIP_TRY(s.h, hipEventRecord(ev, c.st));
+    if (c.blocking) HIP_TRY(s.h, hipStreamSynchronize(c.st));
     return SN_OK;
   }
 };
@@ -226,42 +321,29 @@ int conf_launch(sn_handle* h, hipStream_t st, int n, bool low, const float* conf
 
 extern "C" {
 
-// ---- depth: Parse's dequantisation (k_depth_from_raw); per-call device buffers in host mode --------------------------------
+// ---- depth: Parse's dequantisation (k_depth_from_raw), on the inference stream; host mode stages in InferStaging's slots of
+// the left map (raw), the float map (depth) and the confidence (disp_px), so an allocation failure is SN_ERR_NOMEM ------------
 int sn_depth_from_raw(sn_handle* h, int n, const int32_t* raw, float focal_px, float baseline_mm, float* depth_m, float* disp_px,
                       int mem, void* stream) {
   if (!h || !raw || !depth_m || n <= 0 || n > h->max_batch) return SN_ERR_ARG;
-  Call c;
-  int rc = enter(h, "sn_depth_from_raw", mem, stream, &h->stream, &c);
-  if (rc) return rc;
+  Bracket b(h, "sn_depth_from_raw", mem, stream);
+  Staging& s = b.s;
+  using S = sn_handle::InferStaging;
   const size_t cnt = (size_t)n * h->H * h->W;
   const float fB = focal_px * baseline_mm;      // float product, as in the reference expression
-  const int32_t* draw = raw;
-  float *ddepth = depth_m, *ddisp = disp_px;
-  DevScope ds;
-  if (c.host) {
-    int32_t* a = nullptr;
-    float *b = nullptr, *d = nullptr;
-    HIP_TRY(h, ds.alloc(&a, cnt));
-    HIP_TRY(h, ds.alloc(&b, cnt));
-    if (disp_px) HIP_TRY(h, ds.alloc(&d, cnt));
-    HIP_TRY(h, hipMemcpyAsync(a, raw, cnt * 4, hipMemcpyHostToDevice, c.st));
-    draw = a;
-    ddepth = b;
-    ddisp = d;
-  }
+  const int32_t* draw = s.in(S::kLeft, raw, cnt * 4);
+  float* ddepth = s.out(S::kDisp, depth_m, cnt * 4);
+  float* ddisp = s.out(S::kConf, disp_px, cnt * 4);
+  if (s.rc) return s.rc;
   unsigned grid = (unsigned)((cnt + 255) / 256);
   if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(k_depth_from_raw, dim3(grid), dim3(256), 0, c.st, draw, cnt, kOutScale, fB, ddepth, ddisp);
+  hipLaunchKernelGGL(k_depth_from_raw, dim3(grid), dim3(256), 0, b.c.st, draw, cnt, kOutScale, fB, ddepth, ddisp);
   HIP_TRY(h, hipGetLastError());
-  if (c.host) {
-    HIP_TRY(h, hipMemcpyAsync(depth_m, ddepth, cnt * 4, hipMemcpyDeviceToHost, c.st));
-    if (disp_px) HIP_TRY(h, hipMemcpyAsync(disp_px, ddisp, cnt * 4, hipMemcpyDeviceToHost, c.st));
-    HIP_TRY(h, hipStreamSynchronize(c.st));
-  }
-  return SN_OK;
+  return b.close();
 }
 
-// ---- point cloud (csrc/sn_pointcloud.hpp): its own stream and mutex; host mode stages through pinned memory -----------------
+// ---- point cloud (csrc/sn_pointcloud.hpp): a lane of the handle's; host mode stages through pinned memory --------------------
+// An allocation failure is SN_ERR_NOMEM, as in every other stage.
 int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_t* nv12, int nv12_pitch, const sn_camera* cam,
                            int layout, float* points, uint32_t* counts, int mem, void* stream) {
   if (!h || !raw || !cam || !points || n <= 0 || n > h->max_batch || ((uintptr_t)points & 15) ||
@@ -272,48 +354,27 @@ int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_
     return SN_ERR_ARG;
   if (nv12 && (nv12_pitch < h->W || (nv12_pitch & 1))) return SN_ERR_ARG;
   using P = sn_handle::PointCloud;
-  auto& pc = h->pc;
-  std::lock_guard<std::mutex> lk(pc.mu);
-  Call c;
-  const int rc = enter(h, "sn_pointcloud_from_raw", mem, stream, &pc.stream, &c);
-  if (rc) return rc;
-  if (!pc.ev) HIP_TRY(h, hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming));
+  Bracket b(h, "sn_pointcloud_from_raw", mem, stream, h->pc);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
   const int W = h->W, H = h->H, step = cam->step;
   const int Wo = (W + step - 1) / step, Ho = (H + step - 1) / step;
   const int tiles = (Ho * Wo + kPcTile - 1) / kPcTile;
   const size_t raw_bytes = (size_t)n * H * W * 4, pts_bytes = (size_t)n * Ho * Wo * 16;
   const size_t frame = (size_t)nv12_pitch * (H + (H + 1) / 2);    // an odd height has ceil(H/2) chroma rows
-  hipStream_t st = c.st;
-  HIP_TRY(h, hipStreamWaitEvent(st, pc.ev, 0));      // the previous call (any stream) is done with the scratch
-  if (layout == SN_PC_COMPACT && (size_t)n * tiles * 4 > pc.buf[P::kScratch].cap) {
-    HIP_TRY(h, hipEventSynchronize(pc.ev));
-    HIP_TRY(h, pc.buf[P::kScratch].reserve((size_t)n * tiles * 4));
-  }
-  PcArgs a{raw, nv12, reinterpret_cast<float4*>(points), counts, static_cast<uint32_t*>(pc.buf[P::kScratch].p), frame, W, H, Wo,
-           Ho, step, nv12_pitch, tiles, kOutScale, cam->fx * cam->baseline_mm, cam->fx, cam->fy, cam->cx, cam->cy, cam->z_min_m,
-           cam->z_max_m, 0};
-  if (c.host) {
-    // through pinned memory: the caller's pages may be pageable, and the call may run beside sn_submit / sn_wait
-    auto upload = [&](int pin, int dev, const void* src, size_t bytes) -> int {
-      HIP_TRY(h, pc.buf[pin].reserve(bytes));
-      HIP_TRY(h, pc.buf[dev].reserve(bytes));
-      memcpy(pc.buf[pin].p, src, bytes);
-      HIP_TRY(h, hipMemcpyAsync(pc.buf[dev].p, pc.buf[pin].p, bytes, hipMemcpyHostToDevice, st));
-      return SN_OK;
-    };
-    HIP_TRY(h, pc.buf[P::kPoints].reserve(pts_bytes));
-    HIP_TRY(h, pc.buf[P::kCounts].reserve((size_t)n * 4));
-    if (int e = upload(P::kPinRaw, P::kRaw, raw, raw_bytes)) return e;
-    if (nv12) {
-      if (int e = upload(P::kPinNv12, P::kNv12, nv12, n * frame)) return e;
-      a.nv12 = static_cast<const uint8_t*>(pc.buf[P::kNv12].p);
-    }
-    a.raw = static_cast<const int32_t*>(pc.buf[P::kRaw].p);
-    a.pts = static_cast<float4*>(pc.buf[P::kPoints].p);
-    a.counts = counts ? static_cast<uint32_t*>(pc.buf[P::kCounts].p) : nullptr;
-  }
+  const bool compact = layout == SN_PC_COMPACT;
+  uint32_t* scratch = compact ? s.scratch<uint32_t>(P::kScratch, (size_t)n * tiles * 4) : s.staged<uint32_t>(P::kScratch);
+  const int32_t* draw = s.in_pinned(P::kPinRaw, P::kRaw, raw, raw_bytes);
+  const uint8_t* dnv12 = nv12 ? s.in_pinned(P::kPinNv12, P::kNv12, nv12, n * frame) : nullptr;
+  // compact, host mode: the counts say how much of every map to copy, so both are copied below and not by download()
+  const bool by_hand = compact && s.host;
+  float4* dpts = by_hand ? s.scratch<float4>(P::kPoints, pts_bytes) : s.out(P::kPoints, reinterpret_cast<float4*>(points), pts_bytes);
+  uint32_t* dcounts = by_hand ? s.scratch<uint32_t>(P::kCounts, (size_t)n * 4) : s.out(P::kCounts, counts, (size_t)n * 4);
+  if (s.rc) return s.rc;
+  PcArgs a{draw, dnv12, dpts, dcounts, scratch, frame, W, H, Wo, Ho, step, nv12_pitch, tiles, kOutScale,
+           cam->fx * cam->baseline_mm, cam->fx, cam->fy, cam->cx, cam->cy, cam->z_min_m, cam->z_max_m, 0};
   a.vec = step == 1 && (W & 3) == 0 && ((uintptr_t)a.raw & 15) == 0;
-  if (layout == SN_PC_ORGANISED) {
+  if (!compact) {
     if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, (size_t)n * 4, st));
     const int nseg = Ho * ((Wo + 255) / 256);            // 256-column row segments, one per wave and iteration
     const int per_map = std::max(1, std::min((nseg + 3) / 4, 2048 / n));
@@ -325,21 +386,16 @@ int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_
     else hipLaunchKernelGGL(k_pc_write<false>, dim3(tiles, n), dim3(256), 0, st, a);
   }
   HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipEventRecord(pc.ev, st));
-  if (c.host) {
-    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, a.counts, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (layout == SN_PC_ORGANISED) {
-      HIP_TRY(h, hipMemcpyAsync(points, a.pts, pts_bytes, hipMemcpyDeviceToHost, st));
-    } else {
-      HIP_TRY(h, hipStreamSynchronize(st));      // the counts say how much of every map to copy
-      for (int k = 0; k < n; ++k)
-        if (counts[k])
-          HIP_TRY(h, hipMemcpyAsync(points + (size_t)k * Ho * Wo * 4, a.pts + (size_t)k * Ho * Wo, (size_t)counts[k] * 16,
-                                    hipMemcpyDeviceToHost, st));
+  if (by_hand) {
+    if (int e = s.copy(counts, dcounts, (size_t)n * 4, hipMemcpyDeviceToHost)) return e;
+    HIP_TRY(h, hipStreamSynchronize(st));
+    for (int k = 0; k < n; ++k) {
+      const int e = counts[k] ? s.copy(points + (size_t)k * Ho * Wo * 4, dpts + (size_t)k * Ho * Wo, (size_t)counts[k] * 16,
+                                       hipMemcpyDeviceToHost) : SN_OK;
+      if (e) return e;
     }
   }
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
+  return b.close();
 }
 
 // ---- left-right consistency check (csrc/sn_lrcheck.hpp) --------------------------------------------------------------
@@ -350,18 +406,14 @@ int sn_mirror_pair_i8(sn_handle* h, int n, const int8_t* in, int8_t* out, int me
     set_err(h, "sn_mirror_pair_i8: bad arguments (in and out must not overlap)");
     return SN_ERR_ARG;
   }
-  Call c;
-  int rc = enter(h, "sn_mirror_pair_i8", mem, stream, &h->stream, &c);
-  if (rc) return rc;
+  Bracket b(h, "sn_mirror_pair_i8", mem, stream);
+  Staging& s = b.s;
   using S = sn_handle::InferStaging;
-  Staging s{h, "sn_mirror_pair_i8", c.st, c.host, h->stage.buf};
   const int8_t* din = s.in(S::kIn, in, bytes);
   int8_t* dout = s.out(S::kMirror, out, bytes);
   if (s.rc) return s.rc;
-  if ((rc = mirror_launch(h, c.st, n, din, dout))) return rc;
-  if ((rc = s.download())) return rc;
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
-  return SN_OK;
+  if (int rc = mirror_launch(h, b.c.st, n, din, dout)) return rc;
+  return b.close();
 }
 
 int sn_lr_check(sn_handle* h, int n, const int32_t* raw_left, const int32_t* raw_right, const sn_lrc_params* p,
@@ -371,11 +423,9 @@ int sn_lr_check(sn_handle* h, int n, const int32_t* raw_left, const int32_t* raw
     set_err(h, "sn_lr_check: bad arguments");
     return SN_ERR_ARG;
   }
-  Call c;
-  int rc = enter(h, "sn_lr_check", mem, stream, &h->stream, &c);
-  if (rc) return rc;
+  Bracket b(h, "sn_lr_check", mem, stream);
+  Staging& s = b.s;
   using S = sn_handle::InferStaging;
-  Staging s{h, "sn_lr_check", c.st, c.host, h->stage.buf};
   const size_t cnt = (size_t)n * h->H * h->W;
   const int32_t* dl = s.in(S::kLeft, raw_left, cnt * 4);
   const int32_t* dr = s.in(S::kRight, raw_right, cnt * 4);
@@ -384,10 +434,8 @@ int sn_lr_check(sn_handle* h, int n, const int32_t* raw_left, const int32_t* raw
   uint8_t* dmask = s.out(S::kMask, mask, cnt);
   uint32_t* dkept = s.out(S::kKept, kept, (size_t)n * 4);
   if (s.rc) return s.rc;
-  if ((rc = lrc_launch(h, c.st, n, dl, dr, p, dout, ddisp, dmask, dkept, nullptr))) return rc;
-  if ((rc = s.download())) return rc;
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
-  return SN_OK;
+  if (int rc = lrc_launch(h, b.c.st, n, dl, dr, p, dout, ddisp, dmask, dkept, nullptr)) return rc;
+  return b.close();
 }
 
 // L = forward(in), M = forward(mirror(in)), then the check of L against M in its mirrored storage: two run_forward calls, so
@@ -401,10 +449,10 @@ int sn_infer_lrc(sn_handle* h, int n, const void* in, int in_kind, int w2, int h
   }
   int rc = pair_input_check(h, "sn_infer_lrc", in, in_kind, w2, h_px, mem);
   if (rc) return rc;
-  Call c;
-  if ((rc = enter(h, "sn_infer_lrc", mem, stream, &h->stream, &c))) return rc;
+  Bracket b(h, "sn_infer_lrc", mem, stream);
+  Staging& s = b.s;
+  const Call& c = b.c;
   using S = sn_handle::InferStaging;
-  Staging s{h, "sn_infer_lrc", c.st, c.host, h->stage.buf};
   const size_t cnt = (size_t)n * h->H * h->W;
   int8_t* dmir = s.scratch<int8_t>(S::kMirror, cnt * 6);
   int32_t* dsecond = s.scratch<int32_t>(S::kRight, cnt * 4);
@@ -422,9 +470,7 @@ int sn_infer_lrc(sn_handle* h, int n, const void* in, int in_kind, int w2, int h
   sn_lrc_params q = *p;
   q.right_mirrored = 1;
   if ((rc = lrc_launch(h, c.st, n, dleft, dsecond, &q, dleft, ddisp, dmask, dkept, dright))) return rc;
-  if ((rc = s.download())) return rc;
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
-  return SN_OK;
+  return b.close();
 }
 
 // ---- confidence of the soft-argmin distribution and the mask on it (csrc/sn_confidence.hpp) ------------------------------------
@@ -439,10 +485,10 @@ int sn_infer_conf(sn_handle* h, int n, const void* in, int in_kind, int w2, int 
   }
   int rc = pair_input_check(h, "sn_infer_conf", in, in_kind, w2, h_px, mem);
   if (rc) return rc;
-  Call c;
-  if ((rc = enter(h, "sn_infer_conf", mem, stream, &h->stream, &c))) return rc;
+  Bracket b(h, "sn_infer_conf", mem, stream);      // opened only: the downloads are in `post`, the sync is run_forward's
+  Staging& s = b.s;
+  const Call& c = b.c;
   using S = sn_handle::InferStaging;
-  Staging s{h, "sn_infer_conf", c.st, c.host, h->stage.buf};
   const size_t cnt = (size_t)n * h->H * h->W;
   int32_t* draw = s.out(S::kLeft, out_i32, cnt * 4, p != nullptr);      // the mask rules read the map
   float* ddisp = s.out(S::kDisp, out_disp, cnt * 4);
@@ -471,11 +517,9 @@ int sn_conf_mask(sn_handle* h, int n, const int32_t* raw, const float* conf, con
     set_err(h, "sn_conf_mask: conf overlaps an output");
     return SN_ERR_ARG;
   }
-  Call c;
-  int rc = enter(h, "sn_conf_mask", mem, stream, &h->stream, &c);
-  if (rc) return rc;
+  Bracket b(h, "sn_conf_mask", mem, stream);
+  Staging& s = b.s;
   using S = sn_handle::InferStaging;
-  Staging s{h, "sn_conf_mask", c.st, c.host, h->stage.buf};
   const int32_t* draw = s.in(S::kLeft, raw, cnt * 4);
   const float* dconf = s.in(S::kConf, conf, cnt * 4);
   int32_t* dout = s.alias(out_raw, s.staged<int32_t>(S::kLeft), cnt * 4);      // host mode: masked in place
@@ -483,13 +527,11 @@ int sn_conf_mask(sn_handle* h, int n, const int32_t* raw, const float* conf, con
   uint8_t* dmask = s.out(S::kMask, mask, cnt);
   uint32_t* dkept = s.out(S::kKept, kept, (size_t)n * 4);
   if (s.rc) return s.rc;
-  if ((rc = conf_launch(h, c.st, n, false, dconf, draw, p, nullptr, dout, ddisp, dmask, dkept))) return rc;
-  if ((rc = s.download())) return rc;
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(c.st));
-  return SN_OK;
+  if (int rc = conf_launch(h, b.c.st, n, false, dconf, draw, p, nullptr, dout, ddisp, dmask, dkept)) return rc;
+  return b.close();
 }
 
-// ---- speckle removal and hole filling (csrc/sn_dispfilter.hpp): its own stream and mutex -----------------------------------------
+// ---- speckle removal and hole filling (csrc/sn_dispfilter.hpp): a lane of the handle's -----------------------------------------
 int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_params* p, int32_t* out_raw, float* disp_inout,
                   uint8_t* mask, uint32_t* counts, int mem, void* stream) {
   if (!h) return SN_ERR_ARG;
@@ -501,26 +543,16 @@ int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_param
     return SN_ERR_ARG;
   }
   const size_t cnt = (size_t)n * HW;
-  {      // out_raw == raw is the one overlap the kernels are written for
-    const Span r{raw, cnt * 4}, o{out_raw, cnt * 4}, d{disp_inout, cnt * 4}, m{mask, cnt}, k{counts, (size_t)n * 12};
-    if ((out_raw != raw && overlap({r}, {o})) || overlap({r, o}, {d, m, k}) || overlap({d}, {m, k}) || overlap({m}, {k})) {
-      set_err(h, "sn_filter_raw: overlapping buffers (only out_raw == raw is allowed)");
-      return SN_ERR_ARG;
-    }
+  if (masked_map_overlap(n, HW, raw, out_raw, disp_inout, mask, counts, 3)) {
+    set_err(h, "sn_filter_raw: overlapping buffers (only out_raw == raw is allowed)");
+    return SN_ERR_ARG;
   }
   using F = sn_handle::Filter;
-  auto& f = h->flt;
-  std::lock_guard<std::mutex> lk(f.mu);
-  Call c;
-  const int rc = enter(h, "sn_filter_raw", mem, stream, &f.stream, &c);
-  if (rc) return rc;
-  if (!f.ev) HIP_TRY(h, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
-  hipStream_t st = c.st;
-  Staging s{h, "sn_filter_raw", st, c.host, f.buf};
+  Bracket b(h, "sn_filter_raw", mem, stream, h->flt);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
   const int slice = std::min(h->max_batch, kFltSlice);
   uint32_t* scratch = p->speckle_max_px ? s.scratch<uint32_t>(F::kScratch, (size_t)slice * HW * 8) : s.staged<uint32_t>(F::kScratch);
-  if (s.rc) return s.rc;
-  HIP_TRY(h, hipStreamWaitEvent(st, f.ev, 0));      // the previous call (any stream) is done with the scratch and the staging
   const float S = (float)((double)kOutScale * kWireFactor);
   const float q = floorf(p->speckle_diff_px / S);
   const int32_t* draw = s.in(F::kRaw, raw, cnt * 4);
@@ -538,12 +570,7 @@ int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_param
   const int pairs = (a.tiles_x - 1) * h->H + (a.tiles_y - 1) * h->W;
   for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` maps: walk the batch on the stream
     const int m = std::min(slice, n - k0);
-    const size_t off = (size_t)k0 * HW;
-    a.raw = all.raw + off;
-    a.out_raw = all.out_raw ? all.out_raw + off : nullptr;
-    a.disp = all.disp ? all.disp + off : nullptr;
-    a.mask = all.mask ? all.mask + off : nullptr;
-    a.counts = all.counts ? all.counts + (size_t)k0 * 3 : nullptr;
+    at_slice(a, all, k0, HW, 3);
     if (a.max_px) {
       hipLaunchKernelGGL(k_flt_label, dim3(a.tiles_x * a.tiles_y, m), dim3(256), 0, st, a);
       if (pairs) hipLaunchKernelGGL(k_flt_seam, dim3((pairs + 255) / 256, m), dim3(256), 0, st, a);
@@ -554,62 +581,42 @@ int sn_filter_raw(sn_handle* h, int n, const int32_t* raw, const sn_filter_param
     else hipLaunchKernelGGL(k_flt_apply<false>, dim3(per_map, m), dim3(256), 0, st, a);
   }
   HIP_TRY(h, hipGetLastError());
-  if (int e = s.download()) return e;
-  HIP_TRY(h, hipEventRecord(f.ev, st));
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
+  return b.close();
 }
 
-// ---- guided weighted-median smoothing (csrc/sn_smooth.hpp): its own stream and mutex ------------------------------------------
+// ---- guided weighted-median smoothing (csrc/sn_smooth.hpp): a lane of the handle's ------------------------------------------
 int sn_smooth_raw(sn_handle* h, int n, const int32_t* raw, const void* guide, int guide_kind, int guide_pitch,
                   const sn_smooth_params* p, int32_t* out_raw, float* disp_inout, uint8_t* mask, uint32_t* counts, int mem,
                   void* stream) {
   if (!h) return SN_ERR_ARG;
   const size_t HW = (size_t)h->H * h->W;
-  const bool nv12 = guide_kind == SN_GUIDE_NV12;
+  const bool weighted = p && p->sigma_luma > 0;      // sigma_luma == 0: the guide is ignored altogether
+  const GuideSpan g(h, n, guide, guide_kind, guide_pitch, weighted);
   if (!raw || !p || (!out_raw && !mask) || n <= 0 || n > h->max_batch || p->radius < 1 || p->radius > 3 || p->sigma_luma < 0 ||
-      p->sigma_luma > 255 || (p->sigma_luma > 0 && !guide) || (!nv12 && guide_kind != SN_GUIDE_TENSOR) ||
-      (nv12 && guide && (guide_pitch < h->W || (guide_pitch & 1))) || p->min_valid < 0 ||
-      p->min_valid > (2 * p->radius + 1) * (2 * p->radius + 1)) {
+      p->sigma_luma > 255 || !g.ok || p->min_valid < 0 || p->min_valid > (2 * p->radius + 1) * (2 * p->radius + 1)) {
     set_err(h, "sn_smooth_raw: bad arguments");
     return SN_ERR_ARG;
   }
   const size_t cnt = (size_t)n * HW;
-  const bool weighted = p->sigma_luma > 0;      // sigma_luma == 0: the guide is ignored altogether
-  // frame k of the guide starts at k * frame; the call reads its luma rows alone, so the last frame ends with the last of them
-  const size_t frame = nv12 ? (size_t)guide_pitch * (h->H + (h->H + 1) / 2) : 6 * HW;
-  const size_t guide_bytes = !weighted ? 0 : (n - 1) * frame + (nv12 ? (size_t)guide_pitch * (h->H - 1) + h->W : HW);
-  {      // out_raw == raw is the one overlap the call is written for
-    const Span r{raw, cnt * 4}, o{out_raw, cnt * 4}, d{disp_inout, cnt * 4}, m{mask, cnt}, k{counts, (size_t)n * 12};
-    const Span g{weighted ? guide : nullptr, guide_bytes};
-    if ((out_raw != raw && overlap({r}, {o})) || overlap({r, o}, {d, m, k}) || overlap({d}, {m, k}) || overlap({m}, {k}) ||
-        overlap({g}, {o, d, m, k})) {
-      set_err(h, "sn_smooth_raw: overlapping buffers (only out_raw == raw is allowed)");
-      return SN_ERR_ARG;
-    }
+  if (masked_map_overlap(n, HW, raw, out_raw, disp_inout, mask, counts, 3, g.span)) {
+    set_err(h, "sn_smooth_raw: overlapping buffers (only out_raw == raw is allowed)");
+    return SN_ERR_ARG;
   }
   using M = sn_handle::Smooth;
-  auto& f = h->smo;
-  std::lock_guard<std::mutex> lk(f.mu);
-  Call c;
-  const int rc = enter(h, "sn_smooth_raw", mem, stream, &f.stream, &c);
-  if (rc) return rc;
-  if (!f.ev) HIP_TRY(h, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
-  hipStream_t st = c.st;
-  Staging s{h, "sn_smooth_raw", st, c.host, f.buf};
+  Bracket b(h, "sn_smooth_raw", mem, stream, h->smo);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
   const int slice = std::min(h->max_batch, kSmSlice);
-  const bool in_place = !c.host && out_raw == raw;      // the kernel reads its neighbours' pixels: it works on a copy
+  const bool in_place = !s.host && out_raw == raw;      // the kernel reads its neighbours' pixels: it works on a copy
   int32_t* scratch = in_place ? s.scratch<int32_t>(M::kScratch, (size_t)slice * HW * 4) : nullptr;
-  if (s.rc) return s.rc;
-  HIP_TRY(h, hipStreamWaitEvent(st, f.ev, 0));      // the previous call (any stream) is done with the scratch and the staging
   const int32_t* draw = s.in(M::kRaw, raw, cnt * 4);
-  const uint8_t* dguide = weighted ? s.in(M::kGuide, static_cast<const uint8_t*>(guide), guide_bytes) : nullptr;
+  const uint8_t* dguide = weighted ? s.in(M::kGuide, static_cast<const uint8_t*>(g.span.p), g.span.bytes) : nullptr;
   int32_t* dout = s.out(M::kOut, out_raw, cnt * 4);
   float* ddisp = s.inout(M::kDisp, disp_inout, cnt * 4);
   uint8_t* dmask = s.out(M::kMask, mask, cnt);
   uint32_t* dcounts = s.out(M::kCounts, counts, (size_t)n * 12);
   if (s.rc) return s.rc;
-  SmArgs a{draw, dguide, dout, ddisp, dmask, dcounts, frame, nv12 ? guide_pitch : h->W, nv12 ? 0u : 0x80u, h->W, h->H,
+  SmArgs a{draw, dguide, dout, ddisp, dmask, dcounts, g.frame, g.pitch, g.xor_, h->W, h->H,
            (h->W + kSmTW - 1) / kSmTW, p->min_valid, (float)((double)kOutScale * kWireFactor), {}};
   const long long ss = (long long)p->sigma_luma * p->sigma_luma;
   for (int j = 0; j < 256; ++j) a.table[j] = (uint16_t)(weighted ? (256 * ss) / (ss + (long long)j * j) : 1);
@@ -618,17 +625,12 @@ int sn_smooth_raw(sn_handle* h, int n, const int32_t* raw, const void* guide, in
   const int tiles = a.tiles_x * ((h->H + kSmTH - 1) / kSmTH);
   for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` maps: walk the batch on the stream
     const int m = std::min(slice, n - k0);
-    const size_t off = (size_t)k0 * HW;
-    a.raw = all.raw + off;
+    at_slice(a, all, k0, HW, 3);
+    a.luma = all.luma ? all.luma + (size_t)k0 * g.frame : nullptr;
     if (in_place) {
       HIP_TRY(h, hipMemcpyAsync(scratch, a.raw, (size_t)m * HW * 4, hipMemcpyDeviceToDevice, st));
       a.raw = scratch;
     }
-    a.luma = all.luma ? all.luma + (size_t)k0 * frame : nullptr;
-    a.out_raw = all.out_raw ? all.out_raw + off : nullptr;
-    a.disp = all.disp ? all.disp + off : nullptr;
-    a.mask = all.mask ? all.mask + off : nullptr;
-    a.counts = all.counts ? all.counts + (size_t)k0 * 3 : nullptr;
     const dim3 grid(tiles, m), block(256);
     switch (p->radius * 2 + (weighted ? 1 : 0)) {
       case 2: hipLaunchKernelGGL((k_smooth<1, false>), grid, block, 0, st, a); break;
@@ -640,13 +642,10 @@ int sn_smooth_raw(sn_handle* h, int n, const int32_t* raw, const void* guide, in
     }
   }
   HIP_TRY(h, hipGetLastError());
-  if (int e = s.download()) return e;
-  HIP_TRY(h, hipEventRecord(f.ev, st));
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
+  return b.close();
 }
 
-// ---- temporal filter of disparity streams (csrc/sn_temporal.hpp): an object with its own state, stream, event and mutex ------
+// ---- temporal filter of disparity streams (csrc/sn_temporal.hpp): an object with its own state and lane ------------------------
 int sn_temporal_create(sn_handle* h, int streams, const sn_temporal_params* p, sn_temporal** out) {
   if (!h) return SN_ERR_ARG;
   if (!p || !out || streams < 1 || streams > h->max_batch || p->alpha < 1 || p->alpha > 256 || !std::isfinite(p->delta_px) ||
@@ -688,13 +687,7 @@ int sn_temporal_reset(sn_temporal* t, int stream) {
 void sn_temporal_destroy(sn_temporal* t) {
   if (!t) return;
   (void)hipSetDevice(t->h->device);
-  if (t->stream) (void)hipStreamSynchronize(t->stream);
-  if (t->ev) {
-    (void)hipEventSynchronize(t->ev);      // a push that was only enqueued on a caller's stream
-    (void)hipEventDestroy(t->ev);
-  }
-  if (t->stream) (void)hipStreamDestroy(t->stream);
-  for (GrowBuf& b : t->buf) b.release();
+  t->destroy();
   (void)hipFree(t->state);
   --t->h->temporal_live;
   delete t;
@@ -706,38 +699,25 @@ int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t*
   if (!t) return SN_ERR_ARG;
   sn_handle* h = t->h;
   const size_t HW = (size_t)h->H * h->W;
-  const bool nv12 = guide_kind == SN_GUIDE_NV12;
   const bool luma = t->p.luma_delta > 0;      // luma_delta == 0: the guide is ignored altogether
-  bool ok = raw && (out_raw || mask) && n > 0 && n <= h->max_batch && !(luma && !guide) &&
-            (nv12 || guide_kind == SN_GUIDE_TENSOR) && !(nv12 && guide && (guide_pitch < h->W || (guide_pitch & 1)));
+  const GuideSpan g(h, n, guide, guide_kind, guide_pitch, luma);
+  bool ok = raw && (out_raw || mask) && n > 0 && n <= h->max_batch && g.ok;
   for (int k = 0; ok && stream_of && k < n; ++k) ok = stream_of[k] >= 0 && stream_of[k] < t->streams;
   if (!ok) {
     set_err(h, "sn_temporal_push: bad arguments");
     return SN_ERR_ARG;
   }
   const size_t cnt = (size_t)n * HW;
-  const size_t frame = nv12 ? (size_t)guide_pitch * (h->H + (h->H + 1) / 2) : 6 * HW;      // as sn_smooth_raw
-  const size_t guide_bytes = !luma ? 0 : (n - 1) * frame + (nv12 ? (size_t)guide_pitch * (h->H - 1) + h->W : HW);
-  {      // out_raw == raw is the one overlap the kernel is written for
-    const Span r{raw, cnt * 4}, o{out_raw, cnt * 4}, d{disp_inout, cnt * 4}, m{mask, cnt}, k{counts, (size_t)n * 16};
-    const Span g{luma ? guide : nullptr, guide_bytes};
-    if ((out_raw != raw && overlap({r}, {o})) || overlap({r, o}, {d, m, k}) || overlap({d}, {m, k}) || overlap({m}, {k}) ||
-        overlap({g}, {o, d, m, k})) {
-      set_err(h, "sn_temporal_push: overlapping buffers (only out_raw == raw is allowed)");
-      return SN_ERR_ARG;
-    }
+  if (masked_map_overlap(n, HW, raw, out_raw, disp_inout, mask, counts, 4, g.span)) {
+    set_err(h, "sn_temporal_push: overlapping buffers (only out_raw == raw is allowed)");
+    return SN_ERR_ARG;
   }
   using T = sn_temporal;
-  std::lock_guard<std::mutex> lk(t->mu);
-  Call c;
-  const int rc = enter(h, "sn_temporal_push", mem, stream, &t->stream, &c);
-  if (rc) return rc;
-  if (!t->ev) HIP_TRY(h, hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
-  hipStream_t st = c.st;
-  HIP_TRY(h, hipStreamWaitEvent(st, t->ev, 0));      // the previous push (any stream) is done with the state and the staging
-  Staging s{h, "sn_temporal_push", st, c.host, t->buf};
+  Bracket b(h, "sn_temporal_push", mem, stream, *t);      // the wait: the previous push (any stream) is done with the state too
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
   const int32_t* draw = s.in(T::kRaw, raw, cnt * 4);
-  const uint8_t* dguide = luma ? s.in(T::kGuide, static_cast<const uint8_t*>(guide), guide_bytes) : nullptr;
+  const uint8_t* dguide = luma ? s.in(T::kGuide, static_cast<const uint8_t*>(g.span.p), g.span.bytes) : nullptr;
   int32_t* dout = s.alias(out_raw, s.staged<int32_t>(T::kRaw), cnt * 4);      // host mode: filtered in place
   float* ddisp = s.inout(T::kDisp, disp_inout, cnt * 4);
   uint8_t* dmask = s.out(T::kMask, mask, cnt);
@@ -746,24 +726,21 @@ int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t*
   int32_t* P = static_cast<int32_t*>(t->state);
   uint8_t* Hs = reinterpret_cast<uint8_t*>(P + (size_t)t->streams * HW);
   TmpArgs a{};
+  a.raw = draw, a.luma = dguide, a.out_raw = dout, a.disp = ddisp, a.mask = dmask, a.counts = dcounts;
   a.P = P, a.Hs = Hs, a.Yp = Hs + (size_t)t->streams * HW;
-  a.luma_frame = frame, a.luma_pitch = nv12 ? guide_pitch : h->W, a.luma_xor = nv12 ? 0u : 0x80u;
+  a.luma_frame = g.frame, a.luma_pitch = g.pitch, a.luma_xor = g.xor_;
   a.W = h->W, a.H = h->H, a.alpha = t->p.alpha, a.persist = t->p.persist, a.luma_delta = t->p.luma_delta, a.q = t->q;
   a.S = (float)((double)kOutScale * kWireFactor);
   if (dcounts) HIP_TRY(h, hipMemsetAsync(dcounts, 0, (size_t)n * 16, st));
   // 16-byte map accesses, 4-byte luma and mask accesses: every address the kernel forms must be that aligned
   const bool vec = (h->W & 3) == 0 && (((uintptr_t)draw | (uintptr_t)dout) & 15) == 0 && ((uintptr_t)dmask & 3) == 0 &&
-                   (!luma || (((uintptr_t)dguide | frame | (size_t)a.luma_pitch) & 3) == 0);
+                   (!luma || (((uintptr_t)dguide | g.frame | (size_t)g.pitch) & 3) == 0);
   const unsigned chunks = (unsigned)((HW + (vec ? 1023 : 255)) / (vec ? 1024 : 256));
+  const TmpArgs all = a;
   for (int k0 = 0; k0 < n; k0 += kTmpSlice) {      // the frame lists of kTmpSlice maps fit the kernel arguments
     const int m = std::min(kTmpSlice, n - k0);
-    const size_t off = (size_t)k0 * HW;
-    a.raw = draw + off;
-    a.luma = dguide ? dguide + (size_t)k0 * frame : nullptr;
-    a.out_raw = dout ? dout + off : nullptr;
-    a.disp = ddisp ? ddisp + off : nullptr;
-    a.mask = dmask ? dmask + off : nullptr;
-    a.counts = dcounts ? dcounts + (size_t)k0 * 4 : nullptr;
+    at_slice(a, all, k0, HW, 4);
+    a.luma = all.luma ? all.luma + (size_t)k0 * g.frame : nullptr;
     int groups = 0, filled = 0;      // group the slice's maps by stream, in order of first appearance, each in the order of k
     for (int k = 0; k < m; ++k) {
       const int id = stream_of ? stream_of[k0 + k] : 0;
@@ -788,13 +765,10 @@ int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t*
     HIP_TRY(h, hipGetLastError());
     for (int g = 0; g < groups; ++g) t->fresh[a.stream[g]] = 0;      // enqueued: the state now holds these frames
   }
-  if (int e = s.download()) return e;
-  HIP_TRY(h, hipEventRecord(t->ev, st));
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
+  return b.close();
 }
 
-// ---- stereo rectification (csrc/sn_rectify.hpp): an object with its own maps, stream, event and mutex -------------------------
+// ---- stereo rectification (csrc/sn_rectify.hpp): an object with its own maps and lane -----------------------------------------
 int sn_rectify_build_map(const sn_stereo_calib* c, int eye, int w, int h_px, int32_t* map_xy) {
   if (!rect_calib_ok(c) || !map_xy || (eye != 0 && eye != 1) || w < 1 || h_px < 1) return SN_ERR_ARG;
   rectify_build_map(*c, eye, w, h_px, map_xy);
@@ -844,13 +818,7 @@ int sn_rectify_create(sn_handle* h, const sn_stereo_calib* c, sn_rectify** out) 
 void sn_rectify_destroy(sn_rectify* r) {
   if (!r) return;
   (void)hipSetDevice(r->h->device);
-  if (r->stream) (void)hipStreamSynchronize(r->stream);
-  if (r->ev) {
-    (void)hipEventSynchronize(r->ev);      // a call that was only enqueued on a caller's stream
-    (void)hipEventDestroy(r->ev);
-  }
-  if (r->stream) (void)hipStreamDestroy(r->stream);
-  for (GrowBuf& b : r->buf) b.release();
+  r->destroy();
   (void)hipFree(r->map);
   --r->h->rectify_live;
   delete r;
@@ -908,16 +876,11 @@ int sn_rectify_nv12(sn_rectify* r, int n, const uint8_t* left, const uint8_t* ri
     }
   }
   using R = sn_rectify;
-  std::lock_guard<std::mutex> lk(r->mu);
-  Call c;
-  const int rc = enter(h, "sn_rectify_nv12", mem, stream, &r->stream, &c);
-  if (rc) return rc;
-  if (!r->ev) HIP_TRY(h, hipEventCreateWithFlags(&r->ev, hipEventDisableTiming));
-  hipStream_t st = c.st;
-  HIP_TRY(h, hipStreamWaitEvent(st, r->ev, 0));      // the previous call (any stream) is done with the scratch and the staging
-  Staging s{h, "sn_rectify_nv12", st, c.host, r->buf};
+  Bracket b(h, "sn_rectify_nv12", mem, stream, *r);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
   const uint8_t *dl = left, *dr = right;
-  if (c.host) {
+  if (s.host) {
     // a side-by-side frame's eyes share their rows: one upload from the lower address, and both eyes keep their offsets
     const uint8_t *lo = left < right ? left : right, *hi = left < right ? right : left;
     if ((size_t)(hi - lo) < span) {
@@ -940,10 +903,7 @@ int sn_rectify_nv12(sn_rectify* r, int n, const uint8_t* left, const uint8_t* ri
     const int e = sbs_to_tensors(h, st, n, dsbs, 2 * h->W, h->H, false, dten);
     if (e) return e;
   }
-  if (int e = s.download()) return e;
-  HIP_TRY(h, hipEventRecord(r->ev, st));
-  if (c.blocking) HIP_TRY(h, hipStreamSynchronize(st));
-  return SN_OK;
+  return b.close();
 }
 
 }  // extern "C"

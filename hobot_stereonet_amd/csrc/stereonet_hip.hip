@@ -395,16 +395,10 @@ int sn_destroy(sn_handle* h) {
     hipFree(T.rout.w);
   }
   hipFree(h->dump);
-  for (GrowBuf& b : h->pc.buf) b.release();
+  h->pc.destroy();
+  h->flt.destroy();
+  h->smo.destroy();
   for (GrowBuf& b : h->stage.buf) b.release();
-  for (GrowBuf& b : h->flt.buf) b.release();
-  for (GrowBuf& b : h->smo.buf) b.release();
-  if (h->pc.ev) hipEventDestroy(h->pc.ev);
-  if (h->pc.stream) hipStreamDestroy(h->pc.stream);
-  if (h->flt.ev) hipEventDestroy(h->flt.ev);
-  if (h->flt.stream) hipStreamDestroy(h->flt.stream);
-  if (h->smo.ev) hipEventDestroy(h->smo.ev);
-  if (h->smo.stream) hipStreamDestroy(h->smo.stream);
   hipFree(h->aout.w);
   hipFree(h->aout.pfrag);
   for (auto p : h->chk) hipFree(p);

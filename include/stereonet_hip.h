@@ -418,7 +418,8 @@ enum { SN_PC_ORGANISED = 0, SN_PC_COMPACT = 1 };
  * mem / stream as sn_depth_from_raw, except that a NULL stream is the point cloud's own stream (never the inference
  * stream); the call returns after completion when mem is SN_MEM_HOST or stream is NULL.  SN_ERR_ARG: n outside
  * 1..max_batch, a required pointer NULL, points misaligned, fx or fy <= 0 or not finite, baseline_mm <= 0, step not 1/2/4,
- * unknown layout, nv12 with nv12_pitch < W or odd.
+ * unknown layout, nv12 with nv12_pitch < W or odd.  SN_ERR_NOMEM: the scratch or the staging could not be allocated (as
+ * in every other stage; earlier versions returned SN_ERR_DEVICE).
  * May run concurrently with sn_submit / sn_wait on the same handle: it has its own stream, scratch and staging (created
  * on first use, reused, freed by sn_destroy), and device-mode calls on different streams are ordered on that scratch by an
  * event. */

@@ -1,18 +1,21 @@
 """The host staging the post-processing entry points share (csrc/sn_postproc.hpp) on the MI355X: ONE handle's grow-only
-buffers used by different entry points in growing and shrinking order, inference interleaved with the stateless calls, and
-device mode followed by host mode.  Every result equals its numpy twin (or a fresh handle's result) bit for bit: a stale
+buffers — the inference stream's and every lane's, the temporal filter's and the rectifier's among them — used by different
+entry points in growing and shrinking order, inference interleaved with the other calls, and device mode followed by host mode.  Every result equals its numpy twin (or a fresh handle's result) bit for bit: a stale
 capacity, a slot shared by two meanings or a download of the previous call's size would show up as a wrong map.
 96x64 takes the vector paths, 33x47 (W % 4 != 0, odd height) the scalar ones."""
 import numpy as np
 import pytest
 
-from hobot_stereonet_amd import api, confidence, dispfilter, lrcheck, pointcloud, synth
+from hobot_stereonet_amd import api, confidence, dispfilter, lrcheck, pointcloud, rectify, smooth, synth, temporal
 
 SHAPES = [(96, 64), (33, 47)]
 DMAX = 48
 S = float(lrcheck.wire_scale())
 S32 = dispfilter.wire_scale()
 FLT = (6, 1.0, 16)               # speckle_max_px, speckle_diff_px, fill_max_px: both passes of the filter
+SMO = (2, 12, 3)                 # radius, sigma_luma, min_valid: the weighted median, with filling
+TMP = (64, 8.0, 2, 24)           # alpha, delta_px, persist, luma_delta: the guide is read
+SRC = (128, 80)                  # the rectifier's source size
 _cases = {}
 
 
@@ -39,6 +42,15 @@ def _maps(n, w, h, seed):
     return l, r
 
 
+def _depth(raw, out_scale):
+    """Parse's float / double mix, as tests/test_gpu_parity.py writes it -> (depth, disparity)"""
+    f, B = np.float32(527.1931762695312), np.float32(119.89382172)
+    dis = raw.astype(np.float32) * np.float32(out_scale)
+    with np.errstate(divide="ignore"):
+        depth = (np.float64(f * B) / (dis.astype(np.float64) * 16.0 * 12.0) / 1000.0).astype(np.float32)
+    return depth, dis * np.float32(16.0) * np.float32(12.0)
+
+
 def _case(w, h, out_scale):
     """Inputs and the twins' answers for one shape, computed once and shared by the tests (nothing here is written to)."""
     if (w, h) in _cases:
@@ -50,7 +62,18 @@ def _case(w, h, out_scale):
     disp0 = rng.integers(0, 2 ** 32, l.shape, dtype=np.uint32).view(np.float32)
     x = rng.integers(-128, 128, (3, 6, h, w), dtype=np.int8)
     cam = pointcloud.Camera()
-    c = {"l": l, "r": r, "conf": conf, "disp0": disp0, "x": x, "cam": cam,
+    # the guide: 3 NV12 frames whose pitch is not the width, noise in the chroma rows and beside the luma
+    pitch = w + (w & 1) + 2
+    nv = rng.integers(0, 256, (3, h + (h + 1) // 2, pitch), dtype=np.uint8)
+    luma = smooth.luma_from_nv12(nv, w, h, pitch, 3)
+    states = {}                      # the temporal twin's streams, carried from the first push to the second
+    c = {"l": l, "r": r, "conf": conf, "disp0": disp0, "x": x, "cam": cam, "nv": nv, "pitch": pitch,
+         "sm3": smooth.reference(l, luma, *SMO, out_scale=out_scale),
+         "sm1": smooth.reference(r[:1], None, 1, 0, 0, out_scale=out_scale),
+         "dep3": _depth(l, out_scale),
+         "dep1": _depth(r[1:2], out_scale),
+         "tmp3": temporal.reference(l, luma, TMP, [0, 1, 0], states, out_scale),
+         "tmp1": temporal.reference(r[:1], luma[:1], TMP, [0], states, out_scale),
          "lrc1": lrcheck.reference(l[:1], r[:1], 1.0, 0.0, False, out_scale),
          "lrc3": lrcheck.reference(l, r, 0.5, 0.02, False, out_scale),
          "conf3": confidence.mask(l, conf, 0.5),
@@ -60,6 +83,14 @@ def _case(w, h, out_scale):
          "pc3": pointcloud.reference(l, cam, pointcloud.ORGANISED, None, 0, out_scale),
          "mir3": lrcheck.mirror_pair(x),
          "mir1": lrcheck.mirror_pair(x[1:2])}
+    if w % 4 == 0 and h % 2 == 0:      # what the rectifier asks of the model's size
+        sw, sh = SRC
+        calib = rectify.synthetic_rig(sw, sh, w, h, sw + w)
+        eyes = rng.integers(0, 256, (2, 2, sh + sh // 2, sw), dtype=np.uint8)        # [eye][pair]
+        sbs = rng.integers(0, 256, (sh + sh // 2, 2 * sw), dtype=np.uint8)           # one side-by-side frame
+        rect2 = rectify.reference(calib, w, h, eyes[0], eyes[1], n=2)
+        c.update(calib=calib, eyes=eyes, sbs=sbs, rect2=rect2, rect2t=rectify.tensor_from_sbs(rect2),
+                 rect1=rectify.reference(calib, w, h, sbs))
     for a in c.values():
         for b in (a if isinstance(a, tuple) else (a,)):
             if isinstance(b, np.ndarray):
@@ -75,9 +106,11 @@ def _same3(got, want, tag):
 
 
 def _steps(c):
-    """The stateless host-mode calls, in the order that grows and shrinks the shared buffers: each runs on `eng` and compares
-    with the twin."""
-    l, r, conf, disp0, x, cam = (c[k] for k in ("l", "r", "conf", "disp0", "x", "cam"))
+    """The host-mode calls, in the order that grows and shrinks every lane's buffers beside the others': each runs on `eng`
+    and compares with the twin.  The temporal filter and the rectifier are opened on `eng` by their first step and closed by
+    their second."""
+    l, r, conf, disp0, x, cam, nv, pitch = (c[k] for k in ("l", "r", "conf", "disp0", "x", "cam", "nv", "pitch"))
+    live = {}
 
     def lr_check_1(eng):
         _same3(eng.lr_check(l[:1], r[:1]), c["lrc1"], "lr_check n=1")
@@ -117,8 +150,47 @@ def _steps(c):
     def mirror_pair_1(eng):
         assert np.array_equal(eng.mirror_pair(x[1:2]), c["mir1"]), "mirror_pair n=1"
 
-    return [lr_check_1, conf_mask_3, filter_raw_3, lr_check_3, pointcloud_compact_2, pointcloud_organised_3, conf_mask_1,
-            mirror_pair_3, mirror_pair_1]
+    def smooth_raw_3(eng):
+        disp = disp0.copy()
+        _same3(eng.smooth_raw(l, nv, api.SN_GUIDE_NV12, pitch, *SMO, disp=disp), c["sm3"], "smooth_raw n=3")
+        out, mask, _ = c["sm3"]
+        assert np.array_equal(_bits(disp), _bits(smooth.expected_disp(disp0, out, mask, eng.out_scale))), "smooth_raw n=3: disp"
+
+    def smooth_raw_1(eng):
+        _same3(eng.smooth_raw(r[:1], None, radius=1, sigma_luma=0), c["sm1"], "smooth_raw n=1")
+
+    def depth_from_raw_3(eng):
+        depth, disp = eng.depth_from_raw(l, want_disp=True)
+        assert np.array_equal(_bits(depth), _bits(c["dep3"][0])) and np.array_equal(_bits(disp), _bits(c["dep3"][1])), \
+            "depth_from_raw n=3"
+
+    def depth_from_raw_1(eng):
+        assert np.array_equal(_bits(eng.depth_from_raw(r[1:2])), _bits(c["dep1"][0])), "depth_from_raw n=1"
+
+    def temporal_push_3(eng):
+        live["tf"] = eng.temporal_filter(2, *TMP)
+        disp = disp0.copy()
+        _same3(live["tf"].push(l, nv, api.SN_GUIDE_NV12, pitch, [0, 1, 0], disp), c["tmp3"], "temporal push n=3")
+        assert np.array_equal(_bits(disp), _bits(temporal.expected_disp(disp0, l, c["tmp3"][0], eng.out_scale))), \
+            "temporal push n=3: disp"
+
+    def temporal_push_1(eng):
+        with live.pop("tf") as tf:
+            _same3(tf.push(r[:1], nv[:1], api.SN_GUIDE_NV12, pitch), c["tmp1"], "temporal push n=1")
+
+    def rectify_2(eng):
+        live["rect"] = eng.rectifier(c["calib"])
+        sbs, ten = live["rect"].rectify(c["eyes"][0], c["eyes"][1], n=2, want_tensor=True)
+        assert np.array_equal(sbs, c["rect2"]) and np.array_equal(ten, c["rect2t"]), "rectify n=2"
+
+    def rectify_1(eng):
+        with live.pop("rect") as rect:
+            assert np.array_equal(rect.rectify(c["sbs"]), c["rect1"]), "rectify n=1"
+
+    steps = [lr_check_1, conf_mask_3, filter_raw_3, lr_check_3, smooth_raw_3, temporal_push_3, pointcloud_compact_2,
+             depth_from_raw_3, rectify_2, pointcloud_organised_3, smooth_raw_1, conf_mask_1, temporal_push_1, depth_from_raw_1,
+             mirror_pair_3, rectify_1, mirror_pair_1]
+    return [s for s in steps if "calib" in c or s not in (rectify_2, rectify_1)]
 
 
 @pytest.mark.gpu
