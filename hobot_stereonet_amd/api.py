@@ -98,6 +98,11 @@ class SnStereoCalib(C.Structure):
                 ("pfy", C.c_double), ("pcx", C.c_double), ("pcy", C.c_double), ("baseline_mm", C.c_double)]
 
 
+class SnJpegParams(C.Structure):
+    """sn_jpeg_params (include/stereonet_hip.h)"""
+    _fields_ = [("quality", C.c_int), ("rows_per_slice", C.c_int)]
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -229,6 +234,10 @@ def load_library(path: Optional[str] = None):
     lib.sn_rectify_get_camera.argtypes = [vp, C.POINTER(SnCamera)]
     lib.sn_rectify_get_map.argtypes = [vp, ip, i32p]
     lib.sn_rectify_nv12.argtypes = [vp, ip, u8p, u8p, ip, C.c_size_t, u8p, i8p, ip, vp]
+    lib.sn_jpeg_bound.argtypes = [ip, ip]
+    lib.sn_jpeg_bound.restype = C.c_size_t
+    lib.sn_jpeg_encode_nv12.argtypes = [vp, ip, u8p, ip, ip, ip, C.c_size_t, C.POINTER(SnJpegParams), u8p, C.c_size_t, vp, ip, vp]
+    lib.sn_dbg_jpeg_dct.argtypes = [vp, u8p, ip, ip, ip, fp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -242,7 +251,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -282,6 +291,11 @@ def rectify_build_map(calib, eye: int, w: int, h: int) -> np.ndarray:
     if rc:
         raise StereoNetError(rc, "sn_rectify_build_map")
     return out
+
+
+def jpeg_bound(w: int, h: int) -> int:
+    """sn_jpeg_bound (host only): a capacity no JPEG stream of a w x h image can exceed; 0 for a size the encoder does not take"""
+    return int(load_library().sn_jpeg_bound(w, h))
 
 
 def error_string(code: int) -> str:
@@ -748,6 +762,44 @@ class StereoNetHIP:
     def rectifier(self, calib):
         """A Rectifier (sn_rectify) for this engine's model size from a rectify.Calib; close it before the engine."""
         return Rectifier(self, calib)
+
+    def jpeg_encode_nv12(self, nv12: np.ndarray, w: int, h: int, pitch: int = 0, n: int = 1, frame: int = 0, quality: int = 95,
+                         rows_per_slice: int = 1, out_stride: int = 0, raw: bool = False):
+        """sn_jpeg_encode_nv12 on a host buffer that starts at image 0 (jpeg.encode_nv12 is the numpy twin): n NV12 images of
+        w x h at luma pitch `pitch` (0: w), image k at byte k * frame (0: pitch * h * 3/2).  out_stride 0: sn_jpeg_bound(w, h).
+        -> list of n bytes objects, None where a stream did not fit out_stride; raw: (uint8 (n, out_stride), uint32 (n,))."""
+        src = np.ascontiguousarray(nv12, np.uint8).reshape(-1)
+        pitch = pitch or w
+        frame = frame or pitch * (h + h // 2)
+        span = (n - 1) * frame + (h + h // 2 - 1) * pitch + w
+        if n < 1 or src.size < span:
+            raise StereoNetError(-1, "jpeg_encode_nv12", f"{n} images of {w}x{h} at pitch {pitch} take {span} bytes, the buffer has {src.size}")
+        out_stride = out_stride or jpeg_bound(w, h)
+        out = np.empty((n, out_stride), np.uint8)
+        sizes = np.zeros(n, np.uint32)
+        prm = SnJpegParams(quality, rows_per_slice)
+        self._check(self._lib.sn_jpeg_encode_nv12(self._h, n, src.ctypes.data, w, h, pitch, frame, C.byref(prm), out.ctypes.data,
+                                                  out_stride, sizes.ctypes.data, SN_MEM_HOST, None), "sn_jpeg_encode_nv12")
+        if raw:
+            return out, sizes
+        return [out[k, :sizes[k]].tobytes() if sizes[k] else None for k in range(n)]
+
+    def jpeg_encode_nv12_device(self, n: int, nv12_ptr: int, w: int, h: int, pitch: int, frame: int, quality: int,
+                                rows_per_slice: int, out_ptr: int, out_stride: int, sizes_ptr: int, stream: int = 0):
+        """sn_jpeg_encode_nv12 on device pointers; stream = hipStream_t as int (0: the encoder's own stream, and the call returns
+        after completion)."""
+        prm = SnJpegParams(quality, rows_per_slice)
+        self._check(self._lib.sn_jpeg_encode_nv12(self._h, n, nv12_ptr or None, w, h, pitch, frame, C.byref(prm), out_ptr or None,
+                                                  out_stride, sizes_ptr or None, SN_MEM_DEVICE, stream or None), "sn_jpeg_encode_nv12")
+
+    def dbg_jpeg_dct(self, nv12: np.ndarray, w: int, h: int, pitch: int = 0) -> np.ndarray:
+        """sn_dbg_jpeg_dct: the fp32 coefficients of the encoder's transform before quantisation -> float32 (blocks, 64)"""
+        src = np.ascontiguousarray(nv12, np.uint8).reshape(-1)
+        pitch = pitch or w
+        out = np.empty((((w + 15) // 16) * ((h + 15) // 16) * 6, 64), np.float32)
+        assert src.size >= (h + h // 2 - 1) * pitch + w
+        self._check(self._lib.sn_dbg_jpeg_dct(self._h, src.ctypes.data, w, h, pitch, out.ctypes.data), "sn_dbg_jpeg_dct")
+        return out
 
     def synchronize(self):
         self._check(self._lib.sn_synchronize(self._h), "sn_synchronize")

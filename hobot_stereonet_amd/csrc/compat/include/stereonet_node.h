@@ -78,6 +78,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     int jpeg_threads = 0;             // 0 = hardware threads / 4, clamped to 2..32; STEREONET_JPEG_THREADS overrides
     int jpeg_slices = 8;              // restart-interval slices per frame, encoded in parallel (1 = one scan, no RSTm);
                                       // STEREONET_JPEG_SLICES overrides
+    bool jpeg_gpu = false;            // STEREONET_JPEG=gpu: the encoder task is one sn_jpeg_encode_nv12 call per frame instead of
+                                      // jpeg_slices host tasks; the stream is the same bytes (default: host)
     int feed_start_pause_ms = 1000;   // the reference waits for the viewer before / between offline frames
     int feed_frame_pause_ms = 300;    // (stereonet_node.cpp:890,974); STEREONET_FEED_PAUSE_MS overrides both
     // this implementation's own: sensor_msgs/PointCloud2 on /stereonet_pointcloud2 (sn_pointcloud_from_raw).

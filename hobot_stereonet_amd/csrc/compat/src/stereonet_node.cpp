@@ -89,7 +89,9 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
     }
     jpeg_pool_ = std::make_shared<JpegPool>(n);
     if (const char* e = getenv("STEREONET_JPEG_SLICES")) cfg_.jpeg_slices = atoi(e);
-    RCLCPP_WARN_STREAM(kLog, "left-eye JPEG encoder threads: " << n << ", slices per frame: " << cfg_.jpeg_slices);
+    if (const char* e = getenv("STEREONET_JPEG")) cfg_.jpeg_gpu = !strcmp(e, "gpu");
+    RCLCPP_WARN_STREAM(kLog, "left-eye JPEG encoder threads: " << n << ", slices per frame: " << cfg_.jpeg_slices
+                                 << ", encoder: " << (cfg_.jpeg_gpu ? "gpu" : "host"));
   }
   frames_in_ = create_subscription<hbm_img_msgs::msg::HbmMsg1080P>(
       cfg_.image_topic, 10, [this](hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr m) { OnStereoFrame(m); });
@@ -397,6 +399,35 @@ int StereonetNode::SetNodePara() {
   return 0;
 }
 
+namespace {
+// STEREONET_JPEG=gpu: the frame's stream by ONE pool task that calls sn_jpeg_encode_nv12 (host mode: the call stages the frame
+// and blocks the pool thread, not FeedImg), with the rows_per_slice of SubmitSlicedJpeg, so the bytes are those of the host
+// encoder.  A failed call or a stream that did not fit completes the future with false: the jpeg_bad path of PostProcess.
+std::shared_future<bool> SubmitGpuJpeg(JpegPool& pool, sn_handle* engine, std::shared_ptr<const void> keep_alive, const uint8_t* nv12,
+                                       int w, int h, int pitch, int quality, int slices, std::shared_ptr<BinDataType> out) {
+  const int rows = JpegMcuRows(h);
+  int nsl = slices < 1 ? 1 : slices;
+  if (nsl > rows) nsl = rows;
+  const int per = (rows + nsl - 1) / nsl;
+  nsl = (rows + per - 1) / per;
+  auto done = std::make_shared<std::promise<bool>>();
+  std::shared_future<bool> fut = done->get_future().share();
+  pool.Post([engine, keep_alive, nv12, out, done, w, h, pitch, quality, per, nsl] {
+    static thread_local std::vector<uint8_t> stream;      // sn_jpeg_bound bytes, once per thread: no 9 MB vector per frame
+    const size_t cap = sn_jpeg_bound(w, h);
+    if (stream.size() < cap) stream.resize(cap);
+    const sn_jpeg_params p{quality, nsl > 1 ? per : 0};
+    uint32_t size = 0;
+    const int rc = sn_jpeg_encode_nv12(engine, 1, nv12, w, h, pitch, 0, &p, stream.data(), stream.size(), &size, SN_MEM_HOST, nullptr);
+    const bool ok = rc == SN_OK && size != 0;
+    if (ok) out->jpeg.assign(stream.begin(), stream.begin() + size);
+    else out->jpeg.clear();
+    done->set_value(ok);
+  });
+  return fut;
+}
+}  // namespace
+
 void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr received) {
   if (!rclcpp::ok() || !received) return;
   hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame = received;
@@ -455,7 +486,10 @@ void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSha
     request->sp_left_nv12 = left;
     const int quality = cfg_.jpeg_quality;
     const auto tq = std::chrono::steady_clock::now();
-    request->jpeg_ready = SubmitSlicedJpeg(*jpeg_pool_, frame, frame->data.data(), w, h, pitch, quality, cfg_.jpeg_slices, left);
+    request->jpeg_ready = cfg_.jpeg_gpu ? SubmitGpuJpeg(*jpeg_pool_, net_->engine(), frame, frame->data.data(), w, h, pitch, quality,
+                                                        cfg_.jpeg_slices, left)
+                                        : SubmitSlicedJpeg(*jpeg_pool_, frame, frame->data.data(), w, h, pitch, quality,
+                                                           cfg_.jpeg_slices, left);
     g_stats.add(1, tq);
   }
   request->preprocess_time_ms = elapsed_ms(t_pre);

@@ -11,6 +11,8 @@
 #include <mutex>
 #include <vector>
 
+#include <sys/resource.h>
+
 #include "parser.h"
 #include "stereonet_node.h"
 
@@ -21,6 +23,7 @@ using hobot::stereonet::StereonetNode;
 // harness plays the camera (one executor thread publishing side-by-side NV12 frames back to back; publish() returns when
 // FeedImg has queued the request, and blocks while all task slots are busy) and a subscriber of the output topic.  Prints
 // one JSON line.  STEREONET_PUB_OUTPUT=0 measures the node without the wire message (no JPEG, nothing published).
+// cpu_ms_per_frame is the process's user + system time (getrusage) over the measured frames: what the encoder costs the host.
 static int bench_main(int argc, char** argv) {
   if (argc < 7) {
     fprintf(stderr, "usage: %s --bench model sbs.bin w h nframes\n", argv[0]);
@@ -84,16 +87,25 @@ static int bench_main(int argc, char** argv) {
     }
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   };
+  auto cpu_seconds = [] {
+    rusage u{};
+    getrusage(RUSAGE_SELF, &u);
+    return (double)(u.ru_utime.tv_sec + u.ru_stime.tv_sec) + 1e-6 * (double)(u.ru_utime.tv_usec + u.ru_stime.tv_usec);
+  };
   if (run(8) < 0) return 4;                      // warm-up: first use of every task slot, graph capture
+  const double cpu0 = cpu_seconds();
   const double dt = run(nframes);
+  const double cpu = cpu_seconds() - cpu0;
   if (dt < 0) {
     fprintf(stderr, "timeout\n");
     return 4;
   }
   printf("{\"node_bench\": true, \"frames\": %d, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"ms_per_frame\": %.4f, "
-         "\"publish\": %s, \"width\": %d, \"height\": %d, \"payload_bytes_per_frame\": %ld, \"jpeg_threads\": \"%s\"}\n",
+         "\"publish\": %s, \"width\": %d, \"height\": %d, \"payload_bytes_per_frame\": %ld, \"jpeg_threads\": \"%s\", \"jpeg\": \"%s\", \"cpu_seconds\": %.4f, "
+         "\"cpu_ms_per_frame\": %.4f}\n",
          nframes, dt, nframes / dt, dt / nframes * 1e3, pub_on ? "true" : "false", w, h, pub_on && received ? bytes / received : 0,
-         getenv("STEREONET_JPEG_THREADS") ? getenv("STEREONET_JPEG_THREADS") : "auto");
+         getenv("STEREONET_JPEG_THREADS") ? getenv("STEREONET_JPEG_THREADS") : "auto",
+         getenv("STEREONET_JPEG") ? getenv("STEREONET_JPEG") : "host", cpu, cpu / nframes * 1e3);
   node.reset();
   rclcpp::shutdown();
   return 0;

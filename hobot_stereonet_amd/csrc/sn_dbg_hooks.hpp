@@ -607,6 +607,30 @@ int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, co
   return SN_OK;
 }
 
+// The fp32 coefficients of k_jpeg_dct before quantisation for one host NV12 image: out [blocks][64], coefficient (v, u) of a
+// block at u * 8 + v (the layout the host encoder's two passes leave)
+int sn_dbg_jpeg_dct(sn_handle* h, const uint8_t* nv12, int w, int h_px, int pitch, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !nv12 || !out || !jpg_size_ok(w, h_px) || pitch < w) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const size_t span = (size_t)(h_px + h_px / 2 - 1) * pitch + w;
+  const size_t blocks = (size_t)((w + 15) / 16) * jpg_mcu_rows(h_px) * 6;
+  JpgPlan plan;
+  jpg_make_plan(w, h_px, 50, 0, &plan);
+  uint8_t* din = nullptr;
+  int16_t* dcoef = nullptr;
+  float* ddct = nullptr;
+  HIP_TRY(h, ds.alloc(&din, span));
+  HIP_TRY(h, ds.alloc(&dcoef, blocks * 64));
+  HIP_TRY(h, ds.alloc(&ddct, blocks * 64));
+  HIP_TRY(h, hipMemcpy(din, nv12, span, hipMemcpyHostToDevice));
+  if ((rc = jpeg_launch(h, h->stream, plan, 1, din, pitch, 0, 0, dcoef, nullptr, nullptr, nullptr, 0, nullptr, ddct))) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(out, ddct, blocks * 64 * 4, hipMemcpyDeviceToHost));
+  return SN_OK;
+}
+
 __global__ __launch_bounds__(256) void k_copy_limited(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t n16) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }

@@ -280,6 +280,14 @@ struct sn_handle {
   };
   using Smooth = Lane<SmoothSlots>;
   Smooth smo;
+  // sn_jpeg_encode_nv12.  the coefficients, the slices' stuffed bytes and their lengths of one batch slice; host mode: the
+  // images, the streams of one batch slice, the sizes.  plan: the tables and the header of the last (w, h, quality, restart)
+  struct JpegSlots {
+    enum { kCoef = 0, kBytes, kLens, kIn, kOut, kSizes, kCount };
+  };
+  struct Jpeg : Lane<JpegSlots> {
+    sn::JpgPlan plan;
+  } jpg;
   // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
   // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
   // lock: calls on one handle must not overlap.

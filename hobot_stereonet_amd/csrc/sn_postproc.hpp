@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter and rectifier.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp and sn_rectify.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder and rectifier.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp and sn_rectify.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -313,6 +313,29 @@ int conf_launch(sn_handle* h, hipStream_t st, int n, bool low, const float* conf
   const dim3 grid((unsigned)std::max(1, std::min(blocks, 1024 / n)), (unsigned)n);
   if (low) hipLaunchKernelGGL(k_conf_apply<true>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_conf_apply<false>, grid, dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+// The three launches for m frames on device pointers: dct == nullptr except for the debug hook
+int jpeg_launch(sn_handle* h, hipStream_t st, const JpgPlan& plan, int m, const uint8_t* nv12, int pitch, size_t frame,
+                int rows_per_slice, int16_t* coef, uint8_t* bytes, uint32_t* lens, uint8_t* out, size_t out_stride, uint32_t* sizes,
+                float* dct = nullptr) {
+  const int w = plan.w, hp = plan.h, mw = (w + 15) / 16, rows = jpg_mcu_rows(hp), blocks = mw * rows * 6;
+  JpgDctArgs d{nv12, coef, dct, frame, pitch, w, hp, mw, blocks, {}, {}};
+  memcpy(d.rl, plan.rl, sizeof d.rl);
+  memcpy(d.rc, plan.rc, sizeof d.rc);
+  hipLaunchKernelGGL(k_jpeg_dct, dim3((blocks + 255) / 256, m), dim3(256), 0, st, d);
+  if (out) {
+    const int per = plan.restart ? plan.restart * 6 : blocks, nslices = plan.restart ? (rows + rows_per_slice - 1) / rows_per_slice : 1;
+    const size_t cap = (size_t)per * (2 * kJpgBlockBytes) + 16;
+    JpgEntArgs e{coef, bytes, lens, cap, blocks, per, nslices, {}};
+    memcpy(e.huff, plan.huff, sizeof e.huff);
+    hipLaunchKernelGGL(k_jpeg_entropy, dim3(nslices, m), dim3(kJpgT), 0, st, e);
+    JpgAsmArgs a{bytes, lens, out, sizes, out_stride, cap, nslices, plan.hdr_len, {}};
+    memcpy(a.hdr, plan.hdr, sizeof a.hdr);
+    hipLaunchKernelGGL(k_jpeg_assemble, dim3(nslices, m), dim3(256), 0, st, a);
+  }
   HIP_TRY(h, hipGetLastError());
   return SN_OK;
 }
@@ -764,6 +787,65 @@ int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t*
     }
     HIP_TRY(h, hipGetLastError());
     for (int g = 0; g < groups; ++g) t->fresh[a.stream[g]] = 0;      // enqueued: the state now holds these frames
+  }
+  return b.close();
+}
+
+// ---- JPEG of NV12 images (csrc/sn_jpeg.hpp): a lane of the handle's -------------------------------------------------------------
+size_t sn_jpeg_bound(int w, int h_px) { return jpg_bound(w, h_px); }
+
+int sn_jpeg_encode_nv12(sn_handle* h, int n, const uint8_t* nv12, int w, int h_px, int pitch, size_t frame, const sn_jpeg_params* p,
+                        uint8_t* out, size_t out_stride, uint32_t* sizes, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto bad = [&](const char* why) {
+    set_err(h, std::string("sn_jpeg_encode_nv12: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!nv12 || !p || !out || !sizes || n <= 0 || n > h->max_batch) return bad("bad arguments");
+  if (!jpg_size_ok(w, h_px)) return bad("the width and the height must be even and within 2..65535");
+  if (pitch < w) return bad("pitch < w");
+  const long long restart = jpg_restart_mcus(w, h_px, p->rows_per_slice);
+  if (restart > 65535) return bad("more than 65535 MCUs per restart interval");
+  const size_t bound = jpg_bound(w, h_px);
+  if (bound > 0xffffffffu) return bad("the image is too large: a stream could exceed 2^32 bytes");
+  const size_t span = (size_t)(n - 1) * frame + (size_t)(h_px + h_px / 2 - 1) * pitch + w;
+  {
+    const Span in{nv12, span}, o{out, n * out_stride}, z{sizes, (size_t)n * 4};
+    if (overlap({in}, {o, z}) || overlap({o}, {z})) return bad("overlapping buffers");
+  }
+  using J = sn_handle::JpegSlots;
+  Bracket b(h, "sn_jpeg_encode_nv12", mem, stream, h->jpg);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  if (s.rc) return s.rc;
+  JpgPlan& plan = h->jpg.plan;
+  jpg_make_plan(w, h_px, p->quality, (int)restart, &plan);
+  const int mw = (w + 15) / 16, rows = jpg_mcu_rows(h_px), blocks = mw * rows * 6;
+  const int per = restart ? (int)restart * 6 : blocks, nslices = restart ? (rows + p->rows_per_slice - 1) / p->rows_per_slice : 1;
+  const int slice = std::min(h->max_batch, kJpgSlice);
+  int16_t* coef = s.scratch<int16_t>(J::kCoef, (size_t)slice * blocks * 128);
+  uint8_t* bytes = s.scratch<uint8_t>(J::kBytes, (size_t)slice * nslices * ((size_t)per * (2 * kJpgBlockBytes) + 16));
+  uint32_t* lens = s.scratch<uint32_t>(J::kLens, (size_t)slice * nslices * 4);
+  const uint8_t* din = s.in(J::kIn, nv12, span);
+  // host mode: the streams of one batch slice are staged at a stride no stream needs more than, and copied back by their sizes
+  const size_t dstride = s.host ? std::min(out_stride, bound) : out_stride;
+  uint8_t* dout = s.host ? s.scratch<uint8_t>(J::kOut, (size_t)slice * dstride + 16) : out;
+  uint32_t* dsizes = s.host ? s.scratch<uint32_t>(J::kSizes, (size_t)n * 4) : sizes;
+  if (s.rc) return s.rc;
+  for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` frames: walk the batch on the stream
+    const int m = std::min(slice, n - k0);
+    if (int rc = jpeg_launch(h, st, plan, m, din + (size_t)k0 * frame, pitch, frame, p->rows_per_slice, coef, bytes, lens,
+                             s.host ? dout : dout + (size_t)k0 * out_stride, dstride, dsizes + k0))
+      return rc;
+    if (s.host) {
+      if (int e = s.copy(sizes + k0, dsizes + k0, (size_t)m * 4, hipMemcpyDeviceToHost)) return e;
+      HIP_TRY(h, hipStreamSynchronize(st));
+      for (int k = 0; k < m; ++k)
+        if (sizes[k0 + k])
+          if (int e = s.copy(out + (size_t)(k0 + k) * out_stride, dout + (size_t)k * dstride, sizes[k0 + k], hipMemcpyDeviceToHost))
+            return e;
+      HIP_TRY(h, hipStreamSynchronize(st));      // the next slice rewrites the staged streams
+    }
   }
   return b.close();
 }

@@ -6,7 +6,7 @@ D1) needed to score the output against dataset ground truth.
         [--gt gt.list] [--out out_dir] [--precision auto|f16|f16x3|fp32] \
         [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
-        [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt]
+        [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -50,6 +50,10 @@ images are then RAW, of the calibration's source size: they are converted to NV1
 (`sn_rectify_nv12`) into the side-by-side frame of the model's size, and that frame feeds everything above unchanged.
 <i>.rect.ppm holds the rectified frame (both eyes, RGB), --ply takes its camera from the rectifier unless --camera is given,
 and the summary gains "valid_left" / "valid_right", the pixels of each eye that have a source.
+
+--jpeg Q[,ROWS] encodes the left eye of every frame (the rectified one with --rectify) on the GPU (`sn_jpeg_encode_nv12`,
+quality Q, restart intervals of ROWS MCU rows, default 1; 0 = a single scan) and writes <i>.left.jpg into --out: the node's
+left-eye picture, byte for byte the host encoder's stream.  Every record gains "jpeg_bytes".
 """
 import argparse
 import json
@@ -124,7 +128,8 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 # ---- the feeder ---------------------------------------------------------------------------------------------
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
-                lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None) -> List[dict]:
+                lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
+                jpeg=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -145,7 +150,9 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     "density", <i>.temporal.pgm is written, and with ground truth "temporal_epe" as "smooth_epe".
     rectify = a rectify.Calib: the images are raw eyes of its source size; one api.Rectifier lives for the call and turns every
     pair into the rectified side-by-side frame that feeds all of the above; the record gains "rect" (that frame), <i>.rect.ppm is
-    written, the record gains "valid_left" / "valid_right", and `camera` defaults to the rectifier's."""
+    written, the record gains "valid_left" / "valid_right", and `camera` defaults to the rectifier's.
+    jpeg = (quality, rows_per_slice): the record gains "jpeg" (the left eye's stream from engine.jpeg_encode_nv12) and
+    "jpeg_bytes", and <i>.left.jpg is written."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -161,7 +168,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
         if rectify is not None:
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
-        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect)
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg)
     finally:
         if rect is not None:
             rect.close()
@@ -170,7 +177,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     return results
 
 
-def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None):
+def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -202,6 +209,9 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
         rec = {"frame_id": str(i), "left": lp, "right": rp, "raw": raw, "disp": disp}
         if rect is not None:
             rec.update(rect=sbs, valid_left=valid["valid_left"], valid_right=valid["valid_right"])
+        if jpeg is not None:      # the left half of the side-by-side frame, read in place at pitch 2w
+            rec["jpeg"] = engine.jpeg_encode_nv12(sbs, w, h, 2 * w, quality=jpeg[0], rows_per_slice=jpeg[1])[0]
+            rec["jpeg_bytes"] = len(rec["jpeg"])
         if masked:
             rec["mask"] = mask
             rec["density"] = float(kept[0]) / float(w * h)
@@ -251,6 +261,9 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             from . import render
             _, depth = render.disparity_and_depth(raw.view(np.uint32))
             images.write_ppm(os.path.join(out_dir, f"{i}.depth.ppm"), render.colorize_depth(depth)[..., ::-1])
+            if jpeg is not None:
+                with open(os.path.join(out_dir, f"{i}.left.jpg"), "wb") as f:
+                    f.write(rec["jpeg"])
             if rect is not None:
                 from . import rectify as rct
                 images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
@@ -298,6 +311,9 @@ def main(argv=None) -> int:
                          "new measurement in 1/256, DELTA_PX the largest change that is still blended, PERSIST 0..8 (default 2) "
                          "how many of the last eight inputs must be valid to hold a value, LUMA_DELTA 0..255 (default 0 = off) "
                          "the luma change that counts as motion")
+    ap.add_argument("--jpeg", default=None, metavar="Q[,ROWS]",
+                    help="write <i>.left.jpg, the left eye encoded on the GPU at quality Q with restart intervals of ROWS MCU rows "
+                         "(default 1; 0 = a single scan); needs --out")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
                     help="calibration file (size, left.K/.D/.R, right.K/.D/.R, P, baseline_mm): the listed images are raw, of "
                          "its source size, and are rectified on the GPU to the model's size before everything else")
@@ -375,18 +391,30 @@ def main(argv=None) -> int:
             ap.error(f"--rectify takes a calibration file: {e}")
         if not calib.ok():
             ap.error("--rectify takes a calibration file: sizes even and 2..8192, every value finite, focal lengths and baseline > 0")
+    jpg = None
+    if args.jpeg is not None:
+        try:
+            parts = [int(v) for v in args.jpeg.split(",")]
+            jpg = (parts[0], parts[1] if len(parts) > 1 else 1)
+            if len(parts) > 2 or not args.out:
+                raise ValueError
+        except ValueError:
+            ap.error("--jpeg takes Q[,ROWS] (integers) and needs --out")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
-                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib)
+                               ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
+                               jpeg=jpg)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
     summary = {"frames": len(recs)}
     if calib is not None and recs:
         summary["valid_left"], summary["valid_right"] = recs[0]["valid_left"], recs[0]["valid_right"]
+    if jpg is not None and recs:
+        summary["jpeg_bytes"] = int(sum(r["jpeg_bytes"] for r in recs))
     if args.gt and recs:
         for k in ("epe", "bad1", "bad3", "d1"):
             summary[k] = float(np.nanmean([r["metrics"][k] for r in recs]))

@@ -767,6 +767,59 @@ int  sn_rectify_get_map(sn_rectify *r, int eye, int32_t *map_xy_host);
 int  sn_rectify_nv12(sn_rectify *r, int n, const uint8_t *left, const uint8_t *right, int src_pitch, size_t src_frame,
                      uint8_t *out_sbs_nv12, int8_t *out_nchw6, int mem, void *stream);
 
+/* ---- baseline JPEG of NV12 images: the left-eye picture of the node's message, on the GPU ----------------------------------------
+ * For every frame sn_jpeg_encode_nv12 produces exactly the bytes of the host encoder EncodeNv12ToJpegSliced(nv12, w, h, pitch,
+ * quality, rows_per_slice) of csrc/compat/src/jpeg_nv12.cpp.  No tolerance: the same bytes.  hobot_stereonet_amd/jpeg.py is the
+ * numpy twin.  The contract:
+ *
+ *   Header: SOI, APP0 (JFIF 1.1), two DQT, SOF0 (8 bit; Y 2x2, Cb and Cr 1x1), four DHT with the ITU T.81 Annex K tables, DRI
+ *     only when sliced, SOS: 623 bytes, 629 with DRI.
+ *   Quality: clamped to 1..100; sf = quality < 50 ? 5000 / quality : 200 - 2 * quality; q = clamp((base * sf + 50) / 100, 1, 255).
+ *   Samples: NV12 is the YCbCr 4:2:0 that the stream stores: (float)byte - 128.  MCUs of 16x16 pixels in raster order, blocks
+ *     Y0 Y1 Y2 Y3 Cb Cr.  A block cut by the right or bottom edge replicates the last column or row of its plane; the chroma
+ *     planes are w/2 x h/2 samples, read interleaved from the rows behind the luma rows.
+ *   Transform: the AAN forward DCT in fp32, every operation rounded once, NO fused multiply-add, in this order: the 8-point pass
+ *     down the columns, transpose, the same pass again (so coefficient (v, u) ends at [u][v]).  One pass, on d[0..7]:
+ *       t0 = d0 + d7; t7 = d0 - d7; t1 = d1 + d6; t6 = d1 - d6; t2 = d2 + d5; t5 = d2 - d5; t3 = d3 + d4; t4 = d3 - d4
+ *       e0 = t0 + t3; e3 = t0 - t3; e1 = t1 + t2; e2 = t1 - t2;  d0 = e0 + e1; d4 = e0 - e1
+ *       z1 = (e2 + e3) * 0.707106781f;  d2 = e3 + z1; d6 = e3 - z1
+ *       o0 = t4 + t5; o1 = t5 + t6; o2 = t6 + t7;  z5 = (o0 - o2) * 0.382683433f
+ *       z2 = 0.541196100f * o0 + z5;  z4 = 1.306562965f * o2 + z5;  z3 = o1 * 0.707106781f
+ *       z11 = t7 + z3; z13 = t7 - z3;  d5 = z13 + z2; d3 = z13 - z2; d1 = z11 + z4; d7 = z11 - z4
+ *   Quantisation: lrintf(coefficient * recip), ties to even, recip = (float)(1.0 / (q * aan[u] * aan[v] * 8.0)) with
+ *     aan = {1, 1.387039845, 1.306562965, 1.175875602, 1, 0.785694958, 0.541196100, 0.275899379}.
+ *   Entropy coding: one DC predictor per component, reset at every slice; AC run / size symbols in zigzag order, ZRL (0xF0) for
+ *     runs over 15, EOB unless coefficient 63 is non-zero.
+ *   Slices: rows_per_slice MCU rows form a restart interval (DRI = rows_per_slice * ceil(w / 16) MCUs).  A slice ends with its
+ *     last partial byte padded with ones; a zero byte is stuffed after every 0xFF.  FF D0+(k mod 8) follows slice k, FF D9 the
+ *     last.  rows_per_slice <= 0 or >= ceil(h / 16): a single scan without DRI.
+ *
+ * sn_jpeg_bound: a capacity no stream of a w x h image can exceed (the header, 416 bytes per 8x8 block, the markers); 0 for a
+ *   size the encoder does not take.  Pure host.
+ * sn_jpeg_encode_nv12: n images (1 <= n <= max_batch) of w x h pixels, image k at nv12 + k * frame: h luma rows of `pitch`
+ *   bytes, the h/2 chroma rows behind them at nv12 + h * pitch.  w and h are arguments, not the model's; any address and any
+ *   pitch >= w: odd addresses, the left half of a side-by-side frame (pitch = 2w), what sn_rectify_nv12 wrote.
+ *   Stream k goes to out + k * out_stride and its length to sizes[k].  A stream that does not fit out_stride gives sizes[k] = 0
+ *   (no valid stream is shorter than its header) and not one byte of it is stored; the other frames of the call are
+ *   unaffected, and the call returns SN_OK.  Nothing is ever written at or beyond out + (k + 1) * out_stride.
+ *   SN_ERR_ARG (sn_last_error(h) says why; nothing is launched or written): a NULL pointer, n out of range, w or h odd or
+ *     outside 2..65535, pitch < w, more than 65535 MCUs in a restart interval, an image so large that sn_jpeg_bound exceeds
+ *     2^32 - 1, the images overlapping out or sizes, a bad mem.  SN_ERR_NOMEM: the scratch could not be allocated.
+ *   mem / stream as sn_filter_raw: a lane of the handle's with a stream, an event and grow-only scratch of its own (never the
+ *   inference stream); the call returns after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller
+ *   stream only enqueue.  May run beside sn_submit / sn_wait and beside the other stages; calls are serialised by the lane's
+ *   mutex.  The batch is walked eight frames at a time, so the scratch (128 bytes per block for the coefficients, 416 for the
+ *   slices) does not grow with n.  Parallelism is n x slices: a single-scan stream is one sequential chain per frame, correct
+ *   but slow; use rows_per_slice = 1 where the consumer accepts restart markers.  Not covered: the asynchronous sn_submit*
+ *   slots, optimised Huffman tables, progressive or 4:4:4 streams, a decoder.
+ * sn_dbg_jpeg_dct: the fp32 coefficients BEFORE quantisation of one host image, out [blocks][64] in coding order, coefficient
+ *   (v, u) of a block at u * 8 + v: a contracted or reordered transform shows in the last bit of almost every value. */
+typedef struct sn_jpeg_params { int quality; int rows_per_slice; } sn_jpeg_params;
+size_t sn_jpeg_bound(int w, int h_px);
+int  sn_jpeg_encode_nv12(sn_handle *h, int n, const uint8_t *nv12, int w, int h_px, int pitch, size_t frame,
+                         const sn_jpeg_params *p, uint8_t *out, size_t out_stride, uint32_t *sizes, int mem, void *stream);
+int  sn_dbg_jpeg_dct(sn_handle *h, const uint8_t *nv12, int w, int h_px, int pitch, float *out);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
