@@ -103,6 +103,22 @@ class SnJpegParams(C.Structure):
     _fields_ = [("quality", C.c_int), ("rows_per_slice", C.c_int)]
 
 
+class SnRenderParams(C.Structure):
+    """sn_render_params (include/stereonet_hip.h); render.RenderParams is the Python face of it.  All zero: the reference's
+    render node."""
+    _fields_ = [("scale", C.c_double), ("focal_px", C.c_double), ("baseline_mm", C.c_double), ("alpha", C.c_double),
+                ("layout", C.c_int), ("colormap", C.c_int), ("true_colours", C.c_int), ("invalid_black", C.c_int)]
+
+
+def render_params(p=None) -> SnRenderParams:
+    """render.RenderParams (or None: the reference's render node) -> sn_render_params"""
+    if isinstance(p, SnRenderParams):
+        return p
+    if p is None:
+        return SnRenderParams()
+    return SnRenderParams(p.scale, p.focal_px, p.baseline_mm, p.alpha, p.layout, p.colormap, p.true_colours, p.invalid_black)
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -238,6 +254,9 @@ def load_library(path: Optional[str] = None):
     lib.sn_jpeg_bound.restype = C.c_size_t
     lib.sn_jpeg_encode_nv12.argtypes = [vp, ip, u8p, ip, ip, ip, C.c_size_t, C.POINTER(SnJpegParams), u8p, C.c_size_t, vp, ip, vp]
     lib.sn_dbg_jpeg_dct.argtypes = [vp, u8p, ip, ip, ip, fp]
+    lib.sn_render_tables.argtypes = [C.POINTER(SnRenderParams), u8p, u8p]
+    lib.sn_render.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnRenderParams), ip, u8p, ip, C.c_size_t, ip, vp]
+    lib.sn_render_jpeg.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnRenderParams), C.POINTER(SnJpegParams), u8p, C.c_size_t, vp, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -251,7 +270,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -296,6 +315,17 @@ def rectify_build_map(calib, eye: int, w: int, h: int) -> np.ndarray:
 def jpeg_bound(w: int, h: int) -> int:
     """sn_jpeg_bound (host only): a capacity no JPEG stream of a w x h image can exceed; 0 for a size the encoder does not take"""
     return int(load_library().sn_jpeg_bound(w, h))
+
+
+def render_tables(params=None):
+    """sn_render_tables (host only): -> (rgb, ycc) uint8 (257, 3), the canvas bytes of every colour index and their YCbCr;
+    render.render_tables is the numpy twin."""
+    prm = render_params(params)
+    rgb, ycc = np.empty((257, 3), np.uint8), np.empty((257, 3), np.uint8)
+    rc = load_library().sn_render_tables(C.byref(prm), rgb.ctypes.data, ycc.ctypes.data)
+    if rc:
+        raise StereoNetError(rc, "sn_render_tables")
+    return rgb, ycc
 
 
 def error_string(code: int) -> str:
@@ -791,6 +821,68 @@ class StereoNetHIP:
         prm = SnJpegParams(quality, rows_per_slice)
         self._check(self._lib.sn_jpeg_encode_nv12(self._h, n, nv12_ptr or None, w, h, pitch, frame, C.byref(prm), out_ptr or None,
                                                   out_stride, sizes_ptr or None, SN_MEM_DEVICE, stream or None), "sn_jpeg_encode_nv12")
+
+    # -- the depth view: colour-mapped depth under the left eye ------------------------------------------------
+    def _render_inputs(self, raw, left_nv12, left_pitch: int, prm: "SnRenderParams", where: str):
+        r = self._maps(raw, where) if np.asarray(raw).dtype != np.uint32 else self._maps(np.asarray(raw).view(np.int32), where)
+        n = self._count(r)
+        left = None
+        if prm.layout == 0:
+            left_pitch = left_pitch or self.width
+            rows = self.height + (self.height + 1) // 2
+            need = (n - 1) * left_pitch * rows + (rows - 1) * left_pitch + ((self.width + 1) & ~1)
+            left = np.ascontiguousarray(left_nv12, np.uint8).reshape(-1) if left_nv12 is not None else None
+            if left is None or left_pitch < self.width or left.size < need:
+                raise StereoNetError(-1, where, f"{n} left eyes of {self.width}x{self.height} at pitch {left_pitch} take {need} bytes")
+        return r, n, left, left_pitch
+
+    def render(self, raw: np.ndarray, left_nv12: Optional[np.ndarray] = None, left_pitch: int = 0, params=None, fmt: int = 0):
+        """sn_render on host buffers (render.canvas is the numpy twin): int32 (H,W) or (n,H,W) and, for the stacked layout, n
+        left eyes as NV12 at luma pitch left_pitch (0: W; 2W: the side-by-side frames in place) -> uint8 (n, Hc, W, 3) for
+        render.RGB8, (n, Hc * 3 / 2, W) for render.NV12; leading n dropped for a 2-D raw."""
+        prm = render_params(params)
+        r, n, left, left_pitch = self._render_inputs(raw, left_nv12, left_pitch, prm, "render")
+        hc = self.height * (2 if prm.layout == 0 else 1)
+        shape = (n, hc + hc // 2, self.width) if fmt == 1 else (n, hc, self.width, 3)
+        out = np.empty(shape, np.uint8)
+        pitch = self.width * (1 if fmt == 1 else 3)
+        self._check(self._lib.sn_render(self._h, n, r.ctypes.data, _np_ptr(left), left_pitch, C.byref(prm), fmt, out.ctypes.data,
+                                        pitch, shape[1] * pitch, SN_MEM_HOST, None), "sn_render")
+        return out[0] if r.ndim == 2 else out
+
+    def render_device(self, n: int, raw_ptr: int, left_ptr: int, left_pitch: int, params, fmt: int, out_ptr: int, out_pitch: int,
+                      out_frame: int, stream: int = 0):
+        """sn_render on device pointers; stream = hipStream_t as int (0: the stage's own stream, and the call returns after
+        completion)."""
+        prm = render_params(params)
+        self._check(self._lib.sn_render(self._h, n, raw_ptr or None, left_ptr or None, left_pitch, C.byref(prm), fmt, out_ptr or None,
+                                        out_pitch, out_frame, SN_MEM_DEVICE, stream or None), "sn_render")
+
+    def render_jpeg(self, raw: np.ndarray, left_nv12: Optional[np.ndarray] = None, left_pitch: int = 0, params=None,
+                    quality: int = 95, rows_per_slice: int = 1, out_stride: int = 0, raw_out: bool = False):
+        """sn_render_jpeg on host buffers (render.canvas_jpeg is the numpy twin): the JPEG of every NV12 canvas -> list of n bytes
+        objects, None where a stream did not fit out_stride (0: sn_jpeg_bound of the canvas); raw_out: (uint8 (n, out_stride),
+        uint32 (n,))."""
+        prm = render_params(params)
+        r, n, left, left_pitch = self._render_inputs(raw, left_nv12, left_pitch, prm, "render_jpeg")
+        out_stride = out_stride or jpeg_bound(self.width, self.height * (2 if prm.layout == 0 else 1)) or 1
+        out = np.empty((n, out_stride), np.uint8)
+        sizes = np.zeros(n, np.uint32)
+        jp = SnJpegParams(quality, rows_per_slice)
+        self._check(self._lib.sn_render_jpeg(self._h, n, r.ctypes.data, _np_ptr(left), left_pitch, C.byref(prm), C.byref(jp),
+                                             out.ctypes.data, out_stride, sizes.ctypes.data, SN_MEM_HOST, None), "sn_render_jpeg")
+        if raw_out:
+            return out, sizes
+        return [out[k, :sizes[k]].tobytes() if sizes[k] else None for k in range(n)]
+
+    def render_jpeg_device(self, n: int, raw_ptr: int, left_ptr: int, left_pitch: int, params, quality: int, rows_per_slice: int,
+                           out_ptr: int, out_stride: int, sizes_ptr: int, stream: int = 0):
+        """sn_render_jpeg on device pointers; stream as in render_device."""
+        prm = render_params(params)
+        jp = SnJpegParams(quality, rows_per_slice)
+        self._check(self._lib.sn_render_jpeg(self._h, n, raw_ptr or None, left_ptr or None, left_pitch, C.byref(prm), C.byref(jp),
+                                             out_ptr or None, out_stride, sizes_ptr or None, SN_MEM_DEVICE, stream or None),
+                    "sn_render_jpeg")
 
     def dbg_jpeg_dct(self, nv12: np.ndarray, w: int, h: int, pitch: int = 0) -> np.ndarray:
         """sn_dbg_jpeg_dct: the fp32 coefficients of the encoder's transform before quantisation -> float32 (blocks, 64)"""

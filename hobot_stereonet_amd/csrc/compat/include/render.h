@@ -33,5 +33,21 @@ bool RenderDepth(const uint8_t* payload, size_t len, int w, int h, const RenderC
 // reference's PIL round trip) -> 2h x w x 3 RGB
 void StackJoint(const uint8_t* left_rgb, const uint8_t* color_bgr, int w, int h, std::vector<uint8_t>& joint_rgb);
 
+
+// ---- the host twin of the GPU stage "render" (sn_render, include/stereonet_hip.h): the same canvas from the map and the left
+// eye as NV12, byte for byte.  RenderParams is sn_render_params field for field (0 = the reference's value).
+struct RenderParams {
+  double scale = 0, focal_px = 0, baseline_mm = 0, alpha = 0;
+  int layout = 0, colormap = 0, true_colours = 0, invalid_black = 0;
+};
+enum { kRenderStack = 0, kRenderDepth = 1, kRenderRgb8 = 0, kRenderNv12 = 1, kCmapJet = 0, kCmapGrey = 1 };
+// rgb / ycc (either nullable): 257 x 3 bytes, entry 256 = "no measurement".  false: an unknown colour map
+bool RenderTables(const RenderParams& p, uint8_t* rgb, uint8_t* ycc);
+// One canvas of w x (layout == stack ? 2h : h) pixels at out, rows of out_pitch bytes: RGB8, or NV12 (luma rows, then chroma
+// rows; w and h even).  left_nv12: h luma rows of left_pitch bytes and the chroma rows behind them (not read without the
+// stack).  Bytes beyond a row's 3w (w) are not written.  false: arguments the contract refuses.
+bool RenderCanvas(const int32_t* raw, const uint8_t* left_nv12, int left_pitch, int w, int h, const RenderParams& p, int format,
+                  uint8_t* out, int out_pitch);
+
 }  // namespace stereonet
 }  // namespace hobot

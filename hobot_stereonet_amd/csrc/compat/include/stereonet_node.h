@@ -39,8 +39,9 @@ struct StereonetNodeOutput : public hobot::dnn_node::DnnNodeOutput {
   // this implementation's own: set when the left-eye JPEG of this request is being encoded on a worker thread
   // (sp_left_nv12->jpeg is complete once it yields true); PostProcess waits for it
   std::shared_future<bool> jpeg_ready;
-  // kept only while the point cloud is on (STEREONET_POINTCLOUD) or the temporal filter reads the luma (STEREONET_TEMPORAL
-  // with LUMA_DELTA > 0): the frame whose left eye colours the cloud and guides the filter
+  // kept only while the point cloud is on (STEREONET_POINTCLOUD), the temporal filter reads the luma (STEREONET_TEMPORAL
+  // with LUMA_DELTA > 0) or the depth view is on (STEREONET_RENDER): the frame whose left eye colours the cloud, guides the
+  // filter and tops the view
   hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame;
 };
 
@@ -96,6 +97,13 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // STEREONET_RECTIFY=<calibration file> (size, left.K / .D / .R, right.K / .D / .R, P, baseline_mm: one `key v v ...` per
     // line, `#` comments) turns it on; unset: off, nothing of it exists
     sn_stereo_calib calib{};
+    // this implementation's own: the reference render node's picture (colour-mapped depth under the left eye) as
+    // sensor_msgs/Image "jpeg" on /image_jpeg, one sn_render_jpeg call per frame on the map after the temporal filter.
+    // STEREONET_RENDER=Q[,ROWS] (JPEG quality, MCU rows per restart interval; ROWS defaults to 1) turns it on, with
+    // STEREONET_RENDER_TRUE=1 (the colour map's own colours) and STEREONET_RENDER_INVALID_BLACK=1; unset: off, nothing of it exists
+    bool render = false;
+    sn_render_params render_params{};
+    sn_jpeg_params render_jpeg{95, 1};
   };
 
   void DeclareAndReadParameters();
@@ -107,6 +115,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void ReadRectifySettings();
   hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr RectifyFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr& raw);
   void FilterTemporal(const StereonetNodeOutput& request, int32_t* raw);
+  void ReadRenderSettings();
+  void PublishRender(const StereonetNodeOutput& request, const int32_t* raw);
 
   Settings cfg_;
   bool ready_ = false;
@@ -123,6 +133,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   std::atomic<bool> cloud_uncoloured_logged_{false};
   sn_temporal* temporal_ = nullptr;              // one stream; only while STEREONET_TEMPORAL is set and valid
   bool temporal_unguided_logged_ = false;        // PostProcess only (one thread at a time)
+  rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr render_out_;   // only while STEREONET_RENDER is set and valid
+  std::atomic<bool> render_no_frame_logged_{false};
   sn_rectify* rectify_ = nullptr;                // only while STEREONET_RECTIFY names a valid calibration
 };
 

@@ -99,6 +99,8 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
   disparity_out_ = create_publisher<sensor_msgs::msg::Image>(cfg_.output_topic, 10);
   ReadRectifySettings();      // before the point cloud: its camera defaults to the rectifier's
   ReadPointCloudSettings();
+  ReadRenderSettings();
+  if (cfg_.render) render_out_ = create_publisher<sensor_msgs::msg::Image>("/image_jpeg", 10);
   if (cfg_.pointcloud_layout >= 0) pointcloud_out_ = create_publisher<sensor_msgs::msg::PointCloud2>("/stereonet_pointcloud2", 10);
   ReadTemporalSettings();
   ready_ = true;
@@ -325,6 +327,63 @@ void StereonetNode::FilterTemporal(const StereonetNodeOutput& request, int32_t* 
     RCLCPP_ERROR(kLog, "temporal filter failed: %s", sn_last_error(net_->engine()));
 }
 
+// parsed and validated once here: a value sn_render_jpeg would refuse leaves the node as it is without the variable
+void StereonetNode::ReadRenderSettings() {
+  const char* e = getenv("STEREONET_RENDER");
+  if (!e || !*e) return;
+  sn_jpeg_params& jp = cfg_.render_jpeg;
+  jp = sn_jpeg_params{95, 1};
+  int n1 = 0, n2 = 0;      // characters used after 1 and 2 fields: the whole value must be used
+  const int got = sscanf(e, "%d%n,%d%n", &jp.quality, &n1, &jp.rows_per_slice, &n2);
+  const int used = got == 1 ? n1 : got == 2 ? n2 : -1;
+  std::string bad;
+  if (used != (int)strlen(e)) bad = "is not Q[,ROWS]";
+  else if (jp.quality < 1 || jp.quality > 100 || jp.rows_per_slice < 0) bad = "needs Q 1..100 and ROWS >= 0";
+  else if (((net_w_ | net_h_) & 1) || sn_jpeg_bound(net_w_, 2 * net_h_) == 0) bad = "needs a model of even width and height";
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, "STEREONET_RENDER=" << e << " " << bad << ": no depth view");
+    return;
+  }
+  auto flag = [](const char* name) { return getenv(name) != nullptr && atoi(getenv(name)) == 1; };
+  cfg_.render_params = sn_render_params{};      // the reference's render node
+  cfg_.render_params.true_colours = flag("STEREONET_RENDER_TRUE");
+  cfg_.render_params.invalid_black = flag("STEREONET_RENDER_INVALID_BLACK");
+  cfg_.render = true;
+  RCLCPP_WARN_STREAM(kLog, "depth view on /image_jpeg: quality " << jp.quality << ", rows per slice " << jp.rows_per_slice
+                                                                 << ", true colours " << cfg_.render_params.true_colours
+                                                                 << ", invalid black " << cfg_.render_params.invalid_black);
+}
+
+// sensor_msgs/Image on /image_jpeg as the reference render node's cv2_to_imgmsg forms it: encoding "jpeg", width W, height 2H,
+// step = the data's length; data = the JPEG of the request's left eye (the rectified one where the node rectifies) over its
+// colour-mapped map, by one sn_render_jpeg call.  A request without a side-by-side frame of the model's size (the offline
+// feeder's) has no left eye in NV12: nothing is published for it.
+void StereonetNode::PublishRender(const StereonetNodeOutput& request, const int32_t* raw) {
+  const auto& f = request.frame;
+  if (!(f && (int)f->width == 2 * net_w_ && (int)f->height == net_h_ &&
+        f->data.size() >= (size_t)2 * net_w_ * (net_h_ + (net_h_ + 1) / 2))) {
+    if (!render_no_frame_logged_.exchange(true))
+      RCLCPP_WARN(kLog, "depth view: no side-by-side frame of the model's size for this request, nothing published");
+    return;
+  }
+  sensor_msgs::msg::Image msg;
+  msg.header = *request.msg_header;
+  msg.width = net_w_;
+  msg.height = 2 * net_h_;
+  msg.encoding = "jpeg";
+  msg.data.resize(sn_jpeg_bound(net_w_, 2 * net_h_));
+  uint32_t size = 0;
+  const int rc = sn_render_jpeg(net_->engine(), 1, raw, f->data.data(), 2 * net_w_, &cfg_.render_params, &cfg_.render_jpeg,
+                                msg.data.data(), msg.data.size(), &size, SN_MEM_HOST, nullptr);
+  if (rc != SN_OK || size == 0) {
+    RCLCPP_ERROR(kLog, "depth view failed: %s", rc != SN_OK ? sn_last_error(net_->engine()) : "the stream did not fit");
+    return;
+  }
+  msg.data.resize(size);
+  msg.step = size;
+  render_out_->publish(std::move(msg));
+}
+
 // sensor_msgs/PointCloud2 of the request's map: x, y, z (+ rgb) FLOAT32 at 0 / 4 / 8 / 12, 16 bytes a point, the header of
 // the disparity message; organised = the sampled image grid with NaN for invalid samples, compact = one row of valid points
 void StereonetNode::PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw) {
@@ -452,7 +511,7 @@ void StereonetNode::OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSha
   request->msg_header = std::make_shared<std_msgs::msg::Header>();
   request->msg_header->frame_id = std::to_string(frame->index);
   request->msg_header->stamp = frame->time_stamp;
-  if (cfg_.pointcloud_layout >= 0 || (temporal_ && cfg_.temporal.luma_delta > 0)) request->frame = frame;
+  if (cfg_.pointcloud_layout >= 0 || (temporal_ && cfg_.temporal.luma_delta > 0) || cfg_.render) request->frame = frame;
 
   const auto t_pre = std::chrono::steady_clock::now();
   // STEREONET_INGEST=tensor keeps the reference's host steps (split both eyes, CvtNV12Data2Tensors, Run on the int8
@@ -620,6 +679,9 @@ int StereonetNode::PostProcess(const std::shared_ptr<hobot::dnn_node::DnnNodeOut
   // ahead of the message and of the cloud: both see the filtered map
   if (temporal_ && !request->output_tensors.empty())
     FilterTemporal(*request, static_cast<int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
+  // the view of the filtered map, ahead of the message it belongs to: whoever has the message has the view as well
+  if (render_out_ && !request->output_tensors.empty())
+    PublishRender(*request, static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
   if (cfg_.publish_output && request->sp_left_nv12 && !request->output_tensors.empty()) {
     // wire format consumed by the render node: sensor_msgs/Image, encoding "jpeg",
     // data = the raw int32 output tensor followed by the JPEG of the left eye, step = total length

@@ -27,6 +27,24 @@ int snhost_render(const unsigned char* payload, long len, int w, int h, double* 
 
 void snhost_jet_lut(unsigned char* out) { memcpy(out, hobot::stereonet::JetLutBGR(), 768); }
 
+// the host twin of sn_render_tables: dp = {scale, focal_px, baseline_mm, alpha}, ip = {layout, colormap, true_colours, invalid_black}
+int snhost_render_tables(const double* dp, const int* ip, unsigned char* rgb, unsigned char* ycc) {
+  const hobot::stereonet::RenderParams p{dp[0], dp[1], dp[2], dp[3], ip[0], ip[1], ip[2], ip[3]};
+  return hobot::stereonet::RenderTables(p, rgb, ycc) ? 0 : -1;
+}
+
+// the host twin of sn_render: n canvases, frame k at out + k * out_frame, the left eyes by sn_render's frame rule
+int snhost_render_canvas(int n, const int32_t* raw, const unsigned char* left_nv12, int left_pitch, int w, int h, const double* dp,
+                         const int* ip, int format, unsigned char* out, int out_pitch, long out_frame) {
+  const hobot::stereonet::RenderParams p{dp[0], dp[1], dp[2], dp[3], ip[0], ip[1], ip[2], ip[3]};
+  const size_t left_frame = (size_t)left_pitch * (h + (h + 1) / 2);
+  for (int k = 0; k < n; ++k)
+    if (!hobot::stereonet::RenderCanvas(raw + (size_t)k * w * h, left_nv12 ? left_nv12 + k * left_frame : nullptr, left_pitch, w, h, p,
+                                        format, out + (size_t)k * out_frame, out_pitch))
+      return -1;
+  return 0;
+}
+
 void snhost_yuv420_to_yuv444(const unsigned char* in, unsigned char* out, int w, int h) {
   hobot::stereonet::Tools::YUV420TOYUV444(in, out, w, h);
 }

@@ -288,6 +288,14 @@ struct sn_handle {
   struct Jpeg : Lane<JpegSlots> {
     sn::JpgPlan plan;
   } jpg;
+  // sn_render / sn_render_jpeg.  host mode: the maps, the left eyes, the canvases at their minimal pitch; sn_render_jpeg: the
+  // NV12 canvases of one batch slice, then the encoder's scratch and staging as in JpegSlots, and a plan of its own
+  struct RenderSlots {
+    enum { kRaw = 0, kLeft, kOut, kCanvas, kCoef, kBytes, kLens, kJpegOut, kSizes, kCount };
+  };
+  struct Render : Lane<RenderSlots> {
+    sn::JpgPlan plan;
+  } rnd;
   // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
   // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
   // lock: calls on one handle must not overlap.

@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder and rectifier.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp and sn_rectify.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier and render.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp and sn_render.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -336,6 +336,111 @@ int jpeg_launch(sn_handle* h, hipStream_t st, const JpgPlan& plan, int m, const 
     memcpy(a.hdr, plan.hdr, sizeof a.hdr);
     hipLaunchKernelGGL(k_jpeg_assemble, dim3(nslices, m), dim3(256), 0, st, a);
   }
+  HIP_TRY(h, hipGetLastError());
+  return SN_OK;
+}
+
+// The encoder's walk over the n frames of a call on an open bracket, shared by sn_jpeg_encode_nv12 and sn_render_jpeg: the
+// scratch of one batch slice in the lane's slots `id`, then per slice `source(k0, m, &src)` (the slice's first frame, after
+// enqueuing whatever makes it), the three launches and, in host mode, the copy of every stream by its size.
+struct JpgSlotIds {
+  int coef, bytes, lens, out, sizes;
+};
+
+template <class Source>
+int jpeg_walk(sn_handle* h, Staging& s, hipStream_t st, JpgPlan& plan, const JpgSlotIds& id, int n, int w, int h_px, int pitch,
+              size_t frame, const sn_jpeg_params* p, int restart, uint8_t* out, size_t out_stride, uint32_t* sizes, Source source) {
+  jpg_make_plan(w, h_px, p->quality, restart, &plan);
+  const size_t bound = jpg_bound(w, h_px);
+  const int mw = (w + 15) / 16, rows = jpg_mcu_rows(h_px), blocks = mw * rows * 6;
+  const int per = restart ? restart * 6 : blocks, nslices = restart ? (rows + p->rows_per_slice - 1) / p->rows_per_slice : 1;
+  const int slice = std::min(h->max_batch, kJpgSlice);
+  int16_t* coef = s.scratch<int16_t>(id.coef, (size_t)slice * blocks * 128);
+  uint8_t* bytes = s.scratch<uint8_t>(id.bytes, (size_t)slice * nslices * ((size_t)per * (2 * kJpgBlockBytes) + 16));
+  uint32_t* lens = s.scratch<uint32_t>(id.lens, (size_t)slice * nslices * 4);
+  // host mode: the streams of one batch slice are staged at a stride no stream needs more than, and copied back by their sizes
+  const size_t dstride = s.host ? std::min(out_stride, bound) : out_stride;
+  uint8_t* dout = s.host ? s.scratch<uint8_t>(id.out, (size_t)slice * dstride + 16) : out;
+  uint32_t* dsizes = s.host ? s.scratch<uint32_t>(id.sizes, (size_t)n * 4) : sizes;
+  if (s.rc) return s.rc;
+  for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` frames: walk the batch on the stream
+    const int m = std::min(slice, n - k0);
+    const uint8_t* src = nullptr;
+    if (int rc = source(k0, m, &src)) return rc;
+    if (int rc = jpeg_launch(h, st, plan, m, src, pitch, frame, p->rows_per_slice, coef, bytes, lens,
+                             s.host ? dout : dout + (size_t)k0 * out_stride, dstride, dsizes + k0))
+      return rc;
+    if (s.host) {
+      if (int e = s.copy(sizes + k0, dsizes + k0, (size_t)m * 4, hipMemcpyDeviceToHost)) return e;
+      HIP_TRY(h, hipStreamSynchronize(st));
+      for (int k = 0; k < m; ++k)
+        if (sizes[k0 + k])
+          if (int e = s.copy(out + (size_t)(k0 + k) * out_stride, dout + (size_t)k * dstride, sizes[k0 + k], hipMemcpyDeviceToHost))
+            return e;
+      HIP_TRY(h, hipStreamSynchronize(st));      // the next slice rewrites the staged streams
+    }
+  }
+  return SN_OK;
+}
+
+// sn_render / sn_render_jpeg: the checked arguments of a call
+struct RenderCall {
+  sn_render_params p;      // the zero fields replaced by the reference's values
+  bool nv12, stack;
+  int Hc, rows, row_bytes;      // canvas rows (NV12: luma and chroma), the bytes the call writes in each
+  size_t raw_bytes, left_frame, left_span;
+};
+
+// nullptr, or why the arguments are refused
+const char* render_check(const sn_handle* h, int n, const int32_t* raw, const uint8_t* left, int left_pitch, const sn_render_params* p,
+                         int format, RenderCall* c) {
+  if (!raw || !p) return "a NULL pointer";
+  if (n <= 0 || n > h->max_batch) return "n outside 1..max_batch";
+  if (p->layout != SN_RENDER_STACK && p->layout != SN_RENDER_DEPTH) return "unknown layout";
+  if (format != SN_RENDER_RGB8 && format != SN_RENDER_NV12) return "unknown format";
+  if (p->colormap != SN_CMAP_JET && p->colormap != SN_CMAP_GREY) return "unknown colour map";
+  for (double v : {p->scale, p->focal_px, p->baseline_mm})
+    if (!std::isfinite(v) || v < 0) return "scale, focal_px and baseline_mm must be finite and not negative";
+  if (!std::isfinite(p->alpha)) return "alpha must be finite";
+  c->p = *p;
+  if (c->p.scale == 0) c->p.scale = 0.00000260443857769133;
+  if (c->p.focal_px == 0) c->p.focal_px = 527.1931762695312;
+  if (c->p.baseline_mm == 0) c->p.baseline_mm = 119.89382172;
+  if (c->p.alpha == 0) c->p.alpha = 9.0;
+  c->nv12 = format == SN_RENDER_NV12;
+  c->stack = p->layout == SN_RENDER_STACK;
+  if (c->stack && !left) return "SN_RENDER_STACK needs left_nv12";
+  if (c->stack && (left_pitch < h->W || (left_pitch & 1))) return "left_pitch must be even and >= W";
+  if (c->nv12 && ((h->W | h->H) & 1)) return "SN_RENDER_NV12 needs an even width and height";
+  c->Hc = c->stack ? 2 * h->H : h->H;
+  c->rows = c->nv12 ? c->Hc + c->Hc / 2 : c->Hc;
+  c->row_bytes = c->nv12 ? h->W : 3 * h->W;
+  c->raw_bytes = (size_t)n * h->H * h->W * 4;
+  const int left_rows = h->H + (h->H + 1) / 2;      // an odd height has ceil(H/2) chroma rows
+  c->left_frame = c->stack ? (size_t)left_pitch * left_rows : 0;
+  c->left_span = c->stack ? (n - 1) * c->left_frame + (size_t)(left_rows - 1) * left_pitch + ((h->W + 1) & ~1) : 0;
+  return nullptr;
+}
+
+// one launch: n canvases at device pointers
+int render_launch(sn_handle* h, hipStream_t st, int n, const RenderCall& c, const int32_t* raw, const uint8_t* left, int left_pitch,
+                  uint8_t* out, int out_pitch, size_t out_frame) {
+  RenderArgs a{};
+  a.raw = raw, a.left = c.stack ? left : nullptr, a.out = out;
+  a.left_frame = c.left_frame, a.out_frame = out_frame;
+  a.scale = c.p.scale, a.fB = c.p.focal_px * c.p.baseline_mm, a.alpha = c.p.alpha;
+  a.W = h->W, a.H = h->H, a.left_pitch = left_pitch, a.out_pitch = out_pitch;
+  a.stack = c.stack, a.invalid_black = c.p.invalid_black != 0;
+  a.vec_raw = (h->W & 3) == 0 && ((uintptr_t)raw & 15) == 0;
+  a.word_left = c.stack && (((uintptr_t)left | (size_t)left_pitch | c.left_frame) & 3) == 0;
+  a.word_out = (((uintptr_t)out | (size_t)out_pitch | out_frame) & 3) == 0;
+  uint8_t tab[kRenderEntries * 3];
+  render_tables(&c.p, c.nv12 ? nullptr : tab, c.nv12 ? tab : nullptr);
+  for (int i = 0; i < kRenderEntries; ++i) a.tab[i] = tab[3 * i] | (uint32_t)tab[3 * i + 1] << 8 | (uint32_t)tab[3 * i + 2] << 16;
+  const int items = ((h->W + 3) / 4) * ((h->H + 1) / 2);
+  const dim3 grid((items + 255) / 256, n);
+  if (c.nv12) hipLaunchKernelGGL(k_render<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_render<false>, grid, dim3(256), 0, st, a);
   HIP_TRY(h, hipGetLastError());
   return SN_OK;
 }
@@ -816,37 +921,93 @@ int sn_jpeg_encode_nv12(sn_handle* h, int n, const uint8_t* nv12, int w, int h_p
   using J = sn_handle::JpegSlots;
   Bracket b(h, "sn_jpeg_encode_nv12", mem, stream, h->jpg);
   Staging& s = b.s;
-  hipStream_t st = b.c.st;
-  if (s.rc) return s.rc;
-  JpgPlan& plan = h->jpg.plan;
-  jpg_make_plan(w, h_px, p->quality, (int)restart, &plan);
-  const int mw = (w + 15) / 16, rows = jpg_mcu_rows(h_px), blocks = mw * rows * 6;
-  const int per = restart ? (int)restart * 6 : blocks, nslices = restart ? (rows + p->rows_per_slice - 1) / p->rows_per_slice : 1;
-  const int slice = std::min(h->max_batch, kJpgSlice);
-  int16_t* coef = s.scratch<int16_t>(J::kCoef, (size_t)slice * blocks * 128);
-  uint8_t* bytes = s.scratch<uint8_t>(J::kBytes, (size_t)slice * nslices * ((size_t)per * (2 * kJpgBlockBytes) + 16));
-  uint32_t* lens = s.scratch<uint32_t>(J::kLens, (size_t)slice * nslices * 4);
   const uint8_t* din = s.in(J::kIn, nv12, span);
-  // host mode: the streams of one batch slice are staged at a stride no stream needs more than, and copied back by their sizes
-  const size_t dstride = s.host ? std::min(out_stride, bound) : out_stride;
-  uint8_t* dout = s.host ? s.scratch<uint8_t>(J::kOut, (size_t)slice * dstride + 16) : out;
-  uint32_t* dsizes = s.host ? s.scratch<uint32_t>(J::kSizes, (size_t)n * 4) : sizes;
   if (s.rc) return s.rc;
-  for (int k0 = 0; k0 < n; k0 += slice) {      // the scratch holds `slice` frames: walk the batch on the stream
-    const int m = std::min(slice, n - k0);
-    if (int rc = jpeg_launch(h, st, plan, m, din + (size_t)k0 * frame, pitch, frame, p->rows_per_slice, coef, bytes, lens,
-                             s.host ? dout : dout + (size_t)k0 * out_stride, dstride, dsizes + k0))
-      return rc;
-    if (s.host) {
-      if (int e = s.copy(sizes + k0, dsizes + k0, (size_t)m * 4, hipMemcpyDeviceToHost)) return e;
-      HIP_TRY(h, hipStreamSynchronize(st));
-      for (int k = 0; k < m; ++k)
-        if (sizes[k0 + k])
-          if (int e = s.copy(out + (size_t)(k0 + k) * out_stride, dout + (size_t)k * dstride, sizes[k0 + k], hipMemcpyDeviceToHost))
-            return e;
-      HIP_TRY(h, hipStreamSynchronize(st));      // the next slice rewrites the staged streams
-    }
+  auto source = [&](int k0, int, const uint8_t** src) {
+    *src = din + (size_t)k0 * frame;
+    return SN_OK;
+  };
+  if (int rc = jpeg_walk(h, s, b.c.st, h->jpg.plan, JpgSlotIds{J::kCoef, J::kBytes, J::kLens, J::kOut, J::kSizes}, n, w, h_px, pitch,
+                         frame, p, (int)restart, out, out_stride, sizes, source))
+    return rc;
+  return b.close();
+}
+
+// ---- the depth view (csrc/sn_render.hpp): a lane of the handle's ------------------------------------------------------------------
+int sn_render_tables(const sn_render_params* p, uint8_t* rgb, uint8_t* ycc) {
+  return render_tables(p, rgb, ycc) ? SN_OK : SN_ERR_ARG;
+}
+
+int sn_render(sn_handle* h, int n, const int32_t* raw, const uint8_t* left_nv12, int left_pitch, const sn_render_params* p, int format,
+              uint8_t* out, int out_pitch, size_t out_frame, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto bad = [&](const char* why) {
+    set_err(h, std::string("sn_render: ") + why);
+    return SN_ERR_ARG;
+  };
+  RenderCall c;
+  if (const char* why = render_check(h, n, raw, left_nv12, left_pitch, p, format, &c)) return bad(why);
+  if (!out) return bad("a NULL pointer");
+  if (out_pitch < c.row_bytes) return bad("out_pitch is smaller than a row of the canvas");
+  const size_t canvas = (size_t)(c.rows - 1) * out_pitch + c.row_bytes;
+  if (out_frame < canvas) return bad("out_frame is smaller than a canvas");
+  if (overlap({{out, (n - 1) * out_frame + canvas}}, {{raw, c.raw_bytes}, {c.stack ? left_nv12 : nullptr, c.left_span}}))
+    return bad("out overlaps an input");
+  using R = sn_handle::RenderSlots;
+  Bracket b(h, "sn_render", mem, stream, h->rnd);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  const int32_t* draw = s.in(R::kRaw, raw, c.raw_bytes);
+  const uint8_t* dleft = c.stack ? s.in(R::kLeft, left_nv12, c.left_span) : nullptr;
+  // host mode: the canvases are staged at their minimal pitch and copied back row by row, so the caller's padding stays untouched
+  const size_t tight = (size_t)c.rows * c.row_bytes;
+  uint8_t* dout = s.host ? s.scratch<uint8_t>(R::kOut, n * tight) : out;
+  if (s.rc) return s.rc;
+  if (int rc = render_launch(h, st, n, c, draw, dleft, left_pitch, dout, s.host ? c.row_bytes : out_pitch, s.host ? tight : out_frame))
+    return rc;
+  for (int k = 0; s.host && k < n; ++k)
+    HIP_TRY(h, hipMemcpy2DAsync(out + k * out_frame, out_pitch, dout + k * tight, c.row_bytes, c.row_bytes, c.rows,
+                                hipMemcpyDeviceToHost, st));
+  return b.close();
+}
+
+int sn_render_jpeg(sn_handle* h, int n, const int32_t* raw, const uint8_t* left_nv12, int left_pitch, const sn_render_params* p,
+                   const sn_jpeg_params* jp, uint8_t* out, size_t out_stride, uint32_t* sizes, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto bad = [&](const char* why) {
+    set_err(h, std::string("sn_render_jpeg: ") + why);
+    return SN_ERR_ARG;
+  };
+  RenderCall c;
+  if (const char* why = render_check(h, n, raw, left_nv12, left_pitch, p, SN_RENDER_NV12, &c)) return bad(why);
+  if (!jp || !out || !sizes) return bad("a NULL pointer");
+  const int W = h->W;
+  if (!jpg_size_ok(W, c.Hc)) return bad("the canvas must be within 2..65535 pixels a side");
+  const long long restart = jpg_restart_mcus(W, c.Hc, jp->rows_per_slice);
+  if (restart > 65535) return bad("more than 65535 MCUs per restart interval");
+  if (jpg_bound(W, c.Hc) > 0xffffffffu) return bad("the canvas is too large: a stream could exceed 2^32 bytes");
+  {
+    const Span o{out, n * out_stride}, z{sizes, (size_t)n * 4};
+    if (overlap({o}, {{raw, c.raw_bytes}, {c.stack ? left_nv12 : nullptr, c.left_span}, z}) ||
+        overlap({z}, {{raw, c.raw_bytes}, {c.stack ? left_nv12 : nullptr, c.left_span}}))
+      return bad("out or sizes overlaps another buffer");
   }
+  using R = sn_handle::RenderSlots;
+  Bracket b(h, "sn_render_jpeg", mem, stream, h->rnd);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  const size_t HW = (size_t)h->H * W, frame = (size_t)c.rows * W;      // the canvas at pitch W
+  const int32_t* draw = s.in(R::kRaw, raw, c.raw_bytes);
+  const uint8_t* dleft = c.stack ? s.in(R::kLeft, left_nv12, c.left_span) : nullptr;
+  uint8_t* canvas = s.scratch<uint8_t>(R::kCanvas, std::min(h->max_batch, kJpgSlice) * frame);
+  if (s.rc) return s.rc;
+  auto source = [&](int k0, int m, const uint8_t** src) {
+    *src = canvas;
+    return render_launch(h, st, m, c, draw + k0 * HW, dleft ? dleft + k0 * c.left_frame : nullptr, left_pitch, canvas, W, frame);
+  };
+  if (int rc = jpeg_walk(h, s, st, h->rnd.plan, JpgSlotIds{R::kCoef, R::kBytes, R::kLens, R::kJpegOut, R::kSizes}, n, W, c.Hc, W,
+                         frame, jp, (int)restart, out, out_stride, sizes, source))
+    return rc;
   return b.close();
 }
 

@@ -7,6 +7,7 @@ D1) needed to score the output against dataset ground truth.
         [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
+        [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -54,6 +55,13 @@ and the summary gains "valid_left" / "valid_right", the pixels of each eye that 
 --jpeg Q[,ROWS] encodes the left eye of every frame (the rectified one with --rectify) on the GPU (`sn_jpeg_encode_nv12`,
 quality Q, restart intervals of ROWS MCU rows, default 1; 0 = a single scan) and writes <i>.left.jpg into --out: the node's
 left-eye picture, byte for byte the host encoder's stream.  Every record gains "jpeg_bytes".
+
+--render jpeg[,Q[,ROWS]] | ppm writes the reference render node's picture of every frame into --out, made on the GPU from the
+FINAL map of the chain and the frame's left eye: the left eye on top, the colour-mapped depth below.  jpeg: <i>.render.jpg by
+`sn_render_jpeg` (quality Q, default 95; restart intervals of ROWS MCU rows, default 1); ppm: <i>.render.ppm, the RGB8 canvas of
+`sn_render`.  The default is the reference's published picture (its colour map with red and blue swapped, raw == 0 painted like
+the farthest depth); --render-true-colours keeps the colour map's own colours, --render-invalid-black paints pixels without a
+measurement (raw == 0, what the masks above leave) black.  Every record gains "render_bytes".
 """
 import argparse
 import json
@@ -129,7 +137,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None) -> List[dict]:
+                jpeg=None, view=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -152,7 +160,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     pair into the rectified side-by-side frame that feeds all of the above; the record gains "rect" (that frame), <i>.rect.ppm is
     written, the record gains "valid_left" / "valid_right", and `camera` defaults to the rectifier's.
     jpeg = (quality, rows_per_slice): the record gains "jpeg" (the left eye's stream from engine.jpeg_encode_nv12) and
-    "jpeg_bytes", and <i>.left.jpg is written."""
+    "jpeg_bytes", and <i>.left.jpg is written.
+    view = ("jpeg", quality, rows_per_slice, render.RenderParams) or ("ppm", render.RenderParams): the record gains "render" (the
+    stream of engine.render_jpeg, or the RGB8 canvas of engine.render, of the final map under the left eye) and "render_bytes",
+    and <i>.render.jpg / <i>.render.ppm is written."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -168,7 +179,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
         if rectify is not None:
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
-        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg)
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view)
     finally:
         if rect is not None:
             rect.close()
@@ -177,7 +188,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     return results
 
 
-def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None):
+def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -231,6 +242,13 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             raw, tmask, counts = tf.push(raw, sbs, 0, 2 * w, disp=disp)
             rec.update(raw=raw, temporal_in=traw_in, temporal_mask=tmask, blended=int(counts[0][1]), held=int(counts[0][2]),
                        density=float(counts[0][0]) / float(w * h))
+        if view is not None:      # the final map; the left half of the side-by-side frame, read in place at pitch 2w
+            if view[0] == "jpeg":
+                rec["render"] = engine.render_jpeg(raw, sbs, 2 * w, view[3], quality=view[1], rows_per_slice=view[2])[0]
+                rec["render_bytes"] = len(rec["render"])
+            else:
+                rec["render"] = engine.render(raw, sbs, 2 * w, view[1])
+                rec["render_bytes"] = int(rec["render"].size)
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -264,6 +282,11 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             if jpeg is not None:
                 with open(os.path.join(out_dir, f"{i}.left.jpg"), "wb") as f:
                     f.write(rec["jpeg"])
+            if view is not None and view[0] == "jpeg":
+                with open(os.path.join(out_dir, f"{i}.render.jpg"), "wb") as f:
+                    f.write(rec["render"])
+            elif view is not None:
+                images.write_ppm(os.path.join(out_dir, f"{i}.render.ppm"), rec["render"])
             if rect is not None:
                 from . import rectify as rct
                 images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
@@ -314,6 +337,11 @@ def main(argv=None) -> int:
     ap.add_argument("--jpeg", default=None, metavar="Q[,ROWS]",
                     help="write <i>.left.jpg, the left eye encoded on the GPU at quality Q with restart intervals of ROWS MCU rows "
                          "(default 1; 0 = a single scan); needs --out")
+    ap.add_argument("--render", default=None, metavar="jpeg[,Q[,ROWS]]|ppm",
+                    help="write <i>.render.jpg (quality Q, default 95; restart intervals of ROWS MCU rows, default 1) or "
+                         "<i>.render.ppm: the left eye over the colour-mapped depth of the final map, made on the GPU; needs --out")
+    ap.add_argument("--render-true-colours", action="store_true", help="--render: the colour map's own colours, not the reference's R/B swap")
+    ap.add_argument("--render-invalid-black", action="store_true", help="--render: pixels without a measurement (raw == 0) are black")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
                     help="calibration file (size, left.K/.D/.R, right.K/.D/.R, P, baseline_mm): the listed images are raw, of "
                          "its source size, and are rectified on the GPU to the model's size before everything else")
@@ -400,13 +428,30 @@ def main(argv=None) -> int:
                 raise ValueError
         except ValueError:
             ap.error("--jpeg takes Q[,ROWS] (integers) and needs --out")
+    rnd = None
+    if args.render is not None:
+        from . import render as rnd_mod
+        prm = rnd_mod.RenderParams(true_colours=int(args.render_true_colours), invalid_black=int(args.render_invalid_black))
+        t = args.render.split(",")
+        try:
+            v = [int(x) for x in t[1:]]
+            if t[0] == "jpeg" and len(v) <= 2 and args.out:
+                rnd = ("jpeg", v[0] if v else 95, v[1] if len(v) > 1 else 1, prm)
+            elif t[0] == "ppm" and not v and args.out:
+                rnd = ("ppm", prm)
+            else:
+                raise ValueError
+        except ValueError:
+            ap.error("--render takes jpeg[,Q[,ROWS]] (integers) or ppm, and needs --out")
+    elif args.render_true_colours or args.render_invalid_black:
+        ap.error("--render-true-colours and --render-invalid-black need --render")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg)
+                               jpeg=jpg, view=rnd)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -415,6 +460,8 @@ def main(argv=None) -> int:
         summary["valid_left"], summary["valid_right"] = recs[0]["valid_left"], recs[0]["valid_right"]
     if jpg is not None and recs:
         summary["jpeg_bytes"] = int(sum(r["jpeg_bytes"] for r in recs))
+    if rnd is not None and recs:
+        summary["render_bytes"] = int(sum(r["render_bytes"] for r in recs))
     if args.gt and recs:
         for k in ("epe", "bad1", "bad3", "d1"):
             summary[k] = float(np.nanmean([r["metrics"][k] for r in recs]))

@@ -820,6 +820,81 @@ int  sn_jpeg_encode_nv12(sn_handle *h, int n, const uint8_t *nv12, int w, int h_
                          const sn_jpeg_params *p, uint8_t *out, size_t out_stride, uint32_t *sizes, int mem, void *stream);
 int  sn_dbg_jpeg_dct(sn_handle *h, const uint8_t *nv12, int w, int h_px, int pitch, float *out);
 
+/* ---- the depth view: colour-mapped depth under the left eye, the picture of the reference's render node -------------------------
+ * The reference's render node (MinimalPublisher.listener_callback) turns the int32 map into metric depth, applies
+ * convertScaleAbs(alpha = 9) and COLORMAP_JET, stacks the result under the left image and publishes it as a JPEG.  sn_render
+ * makes that canvas from the map and the left eye in device memory, sn_render_jpeg its JPEG.  No tolerance: the numpy twin
+ * (hobot_stereonet_amd/render.py: canvas, canvas_jpeg), the host C++ twin (compat/src/render.cpp: RenderCanvas) and the kernel
+ * give the same bytes.  Making the JET table or the final bytes match OpenCV's is not claimed (parity unpinned: no cv2 to diff).
+ *
+ * Colour index of a pixel with map word raw, viewed as uint32 as the reference does, in IEEE double, left to right, every
+ * operation rounded once (the order of RenderDepth):
+ *
+ *   d   = (double)raw * scale * 16.0 * 12.0
+ *   z   = focal_px * baseline_mm / d / 1000.0          (raw == 0 -> +inf)
+ *   a   = fabs(z * alpha)
+ *   idx = isnan(a) ? 0 : (rint(a) >= 255 ? 255 : (int)rint(a))          (ties to even)
+ *
+ * A field of scale, focal_px, baseline_mm, alpha that is 0 takes the reference's value (0.00000260443857769133,
+ * 527.1931762695312, 119.89382172, 9); all of sn_render_params zero is the reference's render node.
+ *
+ * Tables (sn_render_tables, pure host): rgb[257][3] and ycc[257][3], entry 256 = "no measurement".
+ *   colour map entry i (0..255) as (B, G, R): SN_CMAP_JET = round(255 * clip(1.5 - |4 * i/255 - {1, 2, 3}|, 0, 1)), exactly
+ *     JetLutBGR() / render.jet_lut(); SN_CMAP_GREY = (i, i, i).
+ *   rgb[i] = the three canvas bytes of index i, in the canvas's R, G, B positions: with true_colours == 0 (the reference's
+ *     published picture) the map's (B, G, R) stored as if they were (R, G, B), so rgb[0..255] is the JET table as it stands;
+ *     with true_colours != 0 the map's (R, G, B).  rgb[256] is black; it is used for raw == 0 when invalid_black != 0
+ *     (the post-processing masks say "no measurement" with raw == 0); otherwise raw == 0 takes idx = 255 as the formula gives.
+ *   ycc[i] from the canvas (R, G, B) = rgb[i], JFIF full-range BT.601 in libjpeg's fixed point (>> arithmetic, no clamp needed):
+ *     Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *     Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16
+ *     Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16
+ *
+ * Canvas.  layout SN_RENDER_STACK: the left eye on top, the colour map below, Hc = 2H; SN_RENDER_DEPTH: the colour map only,
+ *   Hc = H, left_nv12 may be NULL.  The left eye: frame k at left_nv12 + k * left_pitch * (H + ceil(H/2)), H luma rows of
+ *   left_pitch bytes and the chroma rows behind them — sn_pointcloud_from_raw's rule: W for a plain left image, 2W for the left
+ *   half of a side-by-side frame in place, any even value >= W.
+ *   format SN_RENDER_RGB8: frame k at out + k * out_frame, Hc rows of out_pitch >= 3W bytes, pixel = R, G, B.  The left eye is
+ *     converted with the integer formula sn_pointcloud_from_raw documents; the colour half is rgb[idx].  In reference mode the
+ *     colour half equals RenderDepth's color_bgr and the whole equals StackJoint, byte for byte.  Any W and H.
+ *   format SN_RENDER_NV12: Hc luma rows of out_pitch >= W bytes, then Hc/2 chroma rows, as sn_jpeg_encode_nv12 reads them.
+ *     The left eye's luma and chroma rows are copied as they are.  Colour half: Y = ycc[idx][0] per pixel; per 2x2 block
+ *     Cb = (sum of the four pixels' ycc[.][1] + 2) >> 2, Cr likewise.  W and H must be even.
+ *   Bytes between W (3W) and out_pitch are not written; out may be at any address.
+ *
+ * sn_render_tables: the two tables for p's colormap and true_colours; rgb and ycc may each be NULL.  SN_ERR_ARG: p NULL or an
+ *   unknown colour map.
+ * sn_render: n maps (1 <= n <= max_batch) raw [n][H][W] -> n canvases.  One kernel launch per call.
+ * sn_render_jpeg: exactly the bytes and sizes of sn_jpeg_encode_nv12(w = W, h = Hc, pitch = W, jp) on the SN_RENDER_NV12
+ *   canvas of sn_render at pitch W: stream k at out + k * out_stride, its length in sizes[k]; a stream that does not fit gives
+ *   sizes[k] = 0 and nothing of it is stored, the other frames are unaffected and the call returns SN_OK.  The canvas lives
+ *   in the stage's scratch (eight frames of it) and never crosses to the host.
+ * SN_ERR_ARG (sn_last_error(h) says why; nothing is launched or written): n out of range, a required pointer NULL (left_nv12
+ *   with SN_RENDER_STACK), an unknown layout, format or colour map, scale, focal_px or baseline_mm negative or not finite, alpha
+ *   not finite, left_pitch odd or < W, out_pitch too small, out_frame smaller than a canvas ((rows - 1) * out_pitch + the
+ *   bytes of a row), odd W or H with SN_RENDER_NV12 or sn_render_jpeg (and what sn_jpeg_encode_nv12 refuses for W x Hc), out
+ *   overlapping raw, left_nv12 or sizes, a bad mem.  SN_ERR_NOMEM: the scratch or the staging could not be allocated.
+ * mem / stream as sn_filter_raw: a lane of the handle's with a stream, an event and grow-only scratch of its own (never the
+ *   inference stream), freed by sn_destroy; the call returns after completion when mem is SN_MEM_HOST or stream is NULL; device
+ *   buffers + a caller stream only enqueue.  May run beside sn_submit / sn_wait and beside the other stages; calls are
+ *   serialised by the lane's mutex.  Not covered: the asynchronous sn_submit* slots, colour maps other than the two, a
+ *   horizontal stack. */
+#define SN_RENDER_STACK 0
+#define SN_RENDER_DEPTH 1
+#define SN_RENDER_RGB8  0
+#define SN_RENDER_NV12  1
+#define SN_CMAP_JET     0
+#define SN_CMAP_GREY    1
+typedef struct sn_render_params {
+  double scale, focal_px, baseline_mm, alpha;   /* 0 = the reference's 0.00000260443857769133 / 527.1931762695312 / 119.89382172 / 9 */
+  int layout, colormap, true_colours, invalid_black;
+} sn_render_params;                             /* all zero = the reference's render node */
+int  sn_render_tables(const sn_render_params *p, uint8_t *rgb /*257*3*/, uint8_t *ycc /*257*3*/);   /* pure host */
+int  sn_render(sn_handle *h, int n, const int32_t *raw, const uint8_t *left_nv12, int left_pitch, const sn_render_params *p,
+               int format, uint8_t *out, int out_pitch, size_t out_frame, int mem, void *stream);
+int  sn_render_jpeg(sn_handle *h, int n, const int32_t *raw, const uint8_t *left_nv12, int left_pitch, const sn_render_params *p,
+                    const sn_jpeg_params *jp, uint8_t *out, size_t out_stride, uint32_t *sizes, int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
