@@ -119,6 +119,23 @@ def render_params(p=None) -> SnRenderParams:
     return SnRenderParams(p.scale, p.focal_px, p.baseline_mm, p.alpha, p.layout, p.colormap, p.true_colours, p.invalid_black)
 
 
+class SnObstacleParams(C.Structure):
+    """sn_obstacle_params (include/stereonet_hip.h); obstacles.ObstacleParams is the Python face of it."""
+    _fields_ = [("base_from_cam", C.c_float * 12), ("x_min_m", C.c_float), ("y_min_m", C.c_float), ("cell_m", C.c_float),
+                ("gw", C.c_int), ("gh", C.c_int), ("z_floor_m", C.c_float), ("z_lo_m", C.c_float), ("z_hi_m", C.c_float),
+                ("min_obstacle_hits", C.c_int), ("min_ground_hits", C.c_int), ("beams", C.c_int), ("angle_min_rad", C.c_float),
+                ("angle_increment_rad", C.c_float), ("range_min_m", C.c_float), ("range_max_m", C.c_float)]
+
+
+def obstacle_params(p) -> SnObstacleParams:
+    """obstacles.ObstacleParams -> sn_obstacle_params"""
+    if isinstance(p, SnObstacleParams):
+        return p
+    return SnObstacleParams((C.c_float * 12)(*p.base_from_cam), p.x_min_m, p.y_min_m, p.cell_m, p.gw, p.gh, p.z_floor_m, p.z_lo_m,
+                            p.z_hi_m, p.min_obstacle_hits, p.min_ground_hits, p.beams, p.angle_min_rad, p.angle_increment_rad,
+                            p.range_min_m, p.range_max_m)
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -257,6 +274,8 @@ def load_library(path: Optional[str] = None):
     lib.sn_render_tables.argtypes = [C.POINTER(SnRenderParams), u8p, u8p]
     lib.sn_render.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnRenderParams), ip, u8p, ip, C.c_size_t, ip, vp]
     lib.sn_render_jpeg.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnRenderParams), C.POINTER(SnJpegParams), u8p, C.c_size_t, vp, ip, vp]
+    lib.sn_obstacle_beam_edges.argtypes = [C.POINTER(SnObstacleParams), fp]
+    lib.sn_obstacles_from_raw.argtypes = [vp, ip, i32p, C.POINTER(SnCamera), C.POINTER(SnObstacleParams), vp, vp, i32p, fp, vp, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -270,7 +289,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -326,6 +345,17 @@ def render_tables(params=None):
     if rc:
         raise StereoNetError(rc, "sn_render_tables")
     return rgb, ycc
+
+
+def beam_edges(params) -> np.ndarray:
+    """sn_obstacle_beam_edges (host only): float32 (beams + 1,), the tangents that bound the beams of the scan;
+    obstacles.beam_edges is the numpy twin (the two may differ by an ulp: two implementations of a double tan)."""
+    prm = obstacle_params(params)
+    edges = np.empty(max(prm.beams, 0) + 1, np.float32)
+    rc = load_library().sn_obstacle_beam_edges(C.byref(prm), edges.ctypes.data)
+    if rc:
+        raise StereoNetError(rc, "sn_obstacle_beam_edges")
+    return edges
 
 
 def error_string(code: int) -> str:
@@ -586,6 +616,39 @@ class StereoNetHIP:
         self._check(self._lib.sn_pointcloud_from_raw(self._h, n, raw_ptr, nv12_ptr or None, nv12_pitch, C.byref(c), layout,
                                                      points_ptr, counts_ptr or None, SN_MEM_DEVICE, stream or None),
                     "sn_pointcloud_from_raw")
+
+    # -- obstacle grid and laser scan ------------------------------------------------------------------
+    def obstacles(self, raw: np.ndarray, cam, params, grid: bool = True, scan: bool = True):
+        """sn_obstacles_from_raw on host buffers: int32 (H,W) or (n,H,W) -> (occ int8 (n, gh, gw), hits uint32 (n, gh, gw, 2),
+        height_mm int32 (n, gh, gw), ranges float32 (n, beams), stats uint32 (n, 4)), leading n dropped for a 2-D raw;
+        obstacles.reference is the numpy twin.  cam: pointcloud.Camera (None: as pointcloud()); params:
+        obstacles.ObstacleParams.  Without a grid (gw = gh = 0, or grid=False) the grid outputs are empty, without a scan
+        (beams = 0, or scan=False) ranges is."""
+        r = self._maps(raw, "obstacles")
+        n = self._count(r)
+        c, prm = self._camera(cam), obstacle_params(params)
+        gw, gh = (max(prm.gw, 0), max(prm.gh, 0)) if grid else (0, 0)
+        beams = max(prm.beams, 0) if scan else 0
+        occ, hits = np.empty((n, gh, gw), np.int8), np.empty((n, gh, gw, 2), np.uint32)
+        height, ranges, stats = np.empty((n, gh, gw), np.int32), np.empty((n, beams), np.float32), np.zeros((n, 4), np.uint32)
+        g = gw * gh > 0
+        self._check(self._lib.sn_obstacles_from_raw(self._h, n, r.ctypes.data, C.byref(c), C.byref(prm), _np_ptr(occ if g else None),
+                                                    _np_ptr(hits if g else None), _np_ptr(height if g else None),
+                                                    _np_ptr(ranges if beams else None), _np_ptr(stats if g else None), SN_MEM_HOST, None),
+                    "sn_obstacles_from_raw")
+        out = (occ, hits, height, ranges, stats)
+        return tuple(a[0] for a in out) if r.ndim == 2 else out
+
+    beam_edges = staticmethod(beam_edges)      # sn_obstacle_beam_edges needs no engine; here beside the calls that use its table
+
+    def obstacles_device(self, n: int, raw_ptr: int, cam, params, occ_ptr: int = 0, hits_ptr: int = 0, height_ptr: int = 0,
+                         ranges_ptr: int = 0, stats_ptr: int = 0, stream: int = 0):
+        """sn_obstacles_from_raw on device pointers (0: that output is not wanted); stream = hipStream_t as int (0: the stage's
+        own stream, and the call returns after completion)."""
+        c, prm = self._camera(cam), obstacle_params(params)
+        self._check(self._lib.sn_obstacles_from_raw(self._h, n, raw_ptr, C.byref(c), C.byref(prm), occ_ptr or None, hits_ptr or None,
+                                                    height_ptr or None, ranges_ptr or None, stats_ptr or None, SN_MEM_DEVICE,
+                                                    stream or None), "sn_obstacles_from_raw")
 
     # -- left-right consistency check -----------------------------------------------------------------
     def mirror_pair(self, in6: np.ndarray) -> np.ndarray:

@@ -19,7 +19,9 @@
 #include <vector>
 
 #include "rclcpp/rclcpp.hpp"
+#include "nav_msgs/msg/occupancy_grid.hpp"
 #include "sensor_msgs/msg/image.hpp"
+#include "sensor_msgs/msg/laser_scan.hpp"
 #include "sensor_msgs/msg/point_cloud2.hpp"
 #include "ai_msgs/msg/perception_targets.hpp"
 #include "hbm_img_msgs/msg/hbm_msg1080_p.hpp"
@@ -104,12 +106,23 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     bool render = false;
     sn_render_params render_params{};
     sn_jpeg_params render_jpeg{95, 1};
+    // this implementation's own: where the robot cannot drive (sn_obstacles_from_raw), from the map the point cloud gets:
+    // nav_msgs/OccupancyGrid on /stereonet_obstacle_grid and sensor_msgs/LaserScan on /stereonet_scan, whichever of the two
+    // the file configures.  STEREONET_OBSTACLES=<parameter file> (obstacles.save_params' `key value` lines, `frame` = the frame
+    // id, default base_link) turns it on, with the point cloud's camera (STEREONET_CAMERA, STEREONET_POINTCLOUD_STEP / _Z or the
+    // rectifier's); unset: off, nothing of it exists
+    bool obstacles = false;
+    sn_obstacle_params obstacle_params{};
+    std::string obstacle_frame = "base_link";
   };
 
   void DeclareAndReadParameters();
   void LogModelIo();
   void OnStereoFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr frame);   // the FeedImg role
+  bool ReadCamera(std::string* bad);
   void ReadPointCloudSettings();
+  void ReadObstacleSettings();
+  void PublishObstacles(const StereonetNodeOutput& request, const int32_t* raw);
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
   void ReadTemporalSettings();
   void ReadRectifySettings();
@@ -131,6 +144,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   rclcpp::Publisher<ai_msgs::msg::PerceptionTargets>::SharedPtr targets_out_;   // created for parity, never used
   rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pointcloud_out_;   // only while the cloud is on
   std::atomic<bool> cloud_uncoloured_logged_{false};
+  rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr obstacle_grid_out_;   // only while STEREONET_OBSTACLES configures a grid
+  rclcpp::Publisher<sensor_msgs::msg::LaserScan>::SharedPtr obstacle_scan_out_;    // ... a scan
   sn_temporal* temporal_ = nullptr;              // one stream; only while STEREONET_TEMPORAL is set and valid
   bool temporal_unguided_logged_ = false;        // PostProcess only (one thread at a time)
   rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr render_out_;   // only while STEREONET_RENDER is set and valid

@@ -102,6 +102,11 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
   ReadRenderSettings();
   if (cfg_.render) render_out_ = create_publisher<sensor_msgs::msg::Image>("/image_jpeg", 10);
   if (cfg_.pointcloud_layout >= 0) pointcloud_out_ = create_publisher<sensor_msgs::msg::PointCloud2>("/stereonet_pointcloud2", 10);
+  ReadObstacleSettings();
+  if (cfg_.obstacles && cfg_.obstacle_params.gw)
+    obstacle_grid_out_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/stereonet_obstacle_grid", 10);
+  if (cfg_.obstacles && cfg_.obstacle_params.beams)
+    obstacle_scan_out_ = create_publisher<sensor_msgs::msg::LaserScan>("/stereonet_scan", 10);
   ReadTemporalSettings();
   ready_ = true;
 }
@@ -134,22 +139,14 @@ void StereonetNode::DeclareAndReadParameters() {
                                               << "\n ros_img_topic_name: " << cfg_.output_topic);
 }
 
-void StereonetNode::ReadPointCloudSettings() {
-  const char* e = getenv("STEREONET_POINTCLOUD");
-  if (!e || !*e) return;
-  if (!strcmp(e, "organised")) {
-    cfg_.pointcloud_layout = SN_PC_ORGANISED;
-  } else if (!strcmp(e, "compact")) {
-    cfg_.pointcloud_layout = SN_PC_COMPACT;
-  } else {
-    RCLCPP_ERROR_STREAM(kLog, "STEREONET_POINTCLOUD=" << e << " is neither organised nor compact: no point cloud");
-    return;
-  }
+// cfg_.camera of the point cloud and the obstacle stage: the reference's intrinsics or the rectifier's, then STEREONET_CAMERA,
+// STEREONET_POINTCLOUD_STEP and STEREONET_POINTCLOUD_Z.  false: *bad says which setting sn_pointcloud_from_raw would reject
+bool StereonetNode::ReadCamera(std::string* bad_out) {
+  std::string& bad = *bad_out;
   sn_camera& c = cfg_.camera;
   c = sn_camera{527.1931762695312f, 527.1931762695312f, net_w_ / 2.0f, net_h_ / 2.0f, 119.89382172f, 0.f, 0.f, 1};
   if (rectify_) sn_rectify_get_camera(rectify_, &c);      // the rectified left eye's; STEREONET_CAMERA still overrides it
-  // checked once here: settings sn_pointcloud_from_raw would reject turn the cloud off instead of failing every frame
-  std::string bad;
+  // checked once here: settings sn_pointcloud_from_raw would reject turn the stage off instead of failing every frame
   char end = 0;
   if (const char* v = getenv("STEREONET_CAMERA"))
     if (sscanf(v, "%f,%f,%f,%f,%f%c", &c.fx, &c.fy, &c.cx, &c.cy, &c.baseline_mm, &end) != 5)
@@ -163,11 +160,28 @@ void StereonetNode::ReadPointCloudSettings() {
                        std::isfinite(c.cx) && std::isfinite(c.cy)))
     bad = "STEREONET_CAMERA: fx, fy and baseline_mm must be positive and every value finite";
   if (bad.empty() && c.step != 1 && c.step != 2 && c.step != 4) bad = "STEREONET_POINTCLOUD_STEP must be 1, 2 or 4";
+  return bad.empty();
+}
+
+void StereonetNode::ReadPointCloudSettings() {
+  const char* e = getenv("STEREONET_POINTCLOUD");
+  if (!e || !*e) return;
+  if (!strcmp(e, "organised")) {
+    cfg_.pointcloud_layout = SN_PC_ORGANISED;
+  } else if (!strcmp(e, "compact")) {
+    cfg_.pointcloud_layout = SN_PC_COMPACT;
+  } else {
+    RCLCPP_ERROR_STREAM(kLog, "STEREONET_POINTCLOUD=" << e << " is neither organised nor compact: no point cloud");
+    return;
+  }
+  std::string bad;
+  ReadCamera(&bad);
   if (!bad.empty()) {
     RCLCPP_ERROR_STREAM(kLog, bad << ": no point cloud");
     cfg_.pointcloud_layout = -1;
     return;
   }
+  const sn_camera& c = cfg_.camera;
   RCLCPP_WARN_STREAM(kLog, "point cloud: " << e << " on /stereonet_pointcloud2, fx " << c.fx << " fy " << c.fy << " cx " << c.cx
                                            << " cy " << c.cy << " baseline_mm " << c.baseline_mm << " step " << c.step
                                            << " z " << c.z_min_m << ".." << c.z_max_m);
@@ -428,6 +442,147 @@ void StereonetNode::PublishPointCloud(const StereonetNodeOutput& request, const 
   }
   msg.row_step = 16 * msg.width;
   pointcloud_out_->publish(std::move(msg));
+}
+
+namespace {
+// obstacles.load_params' text form: one `key value...` per line, `#` comments, a key at most once; a key that is missing
+// keeps `p`'s value
+bool load_obstacle_file(const char* path, sn_obstacle_params* p, std::string* frame, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct FloatKey {
+    const char* name;
+    float* v;
+  } floats[] = {{"x_min_m", &p->x_min_m}, {"y_min_m", &p->y_min_m}, {"cell_m", &p->cell_m}, {"z_floor_m", &p->z_floor_m},
+                {"z_lo_m", &p->z_lo_m}, {"z_hi_m", &p->z_hi_m}, {"angle_min_rad", &p->angle_min_rad},
+                {"angle_increment_rad", &p->angle_increment_rad}, {"range_min_m", &p->range_min_m}, {"range_max_m", &p->range_max_m}};
+  struct IntKey {
+    const char* name;
+    int* v;
+  } ints[] = {{"gw", &p->gw}, {"gh", &p->gh}, {"min_obstacle_hits", &p->min_obstacle_hits}, {"min_ground_hits", &p->min_ground_hits},
+              {"beams", &p->beams}};
+  std::vector<std::string> seen;
+  std::string text;
+  for (int no = 1; std::getline(in, text); ++no) {
+    std::istringstream words(text.substr(0, text.find('#')));
+    std::string key, w;
+    if (!(words >> key)) continue;
+    std::vector<std::string> vals;
+    while (words >> w) vals.push_back(w);
+    const std::string at = "line " + std::to_string(no) + ": ";
+    for (const std::string& k : seen)
+      if (k == key) {
+        *err = at + key + " twice";
+        return false;
+      }
+    seen.push_back(key);
+    auto number = [&](const std::string& t, double* out) {
+      char* end = nullptr;
+      *out = strtod(t.c_str(), &end);
+      return end != t.c_str() && !*end;
+    };
+    bool known = false, ok = true;
+    double d = 0;
+    if (key == "frame") {
+      known = true, ok = vals.size() == 1;
+      if (ok) *frame = vals[0];
+    } else if (key == "base_from_cam") {
+      known = true, ok = vals.size() == 12;
+      for (int i = 0; ok && i < 12; ++i) {
+        ok = number(vals[i], &d);
+        p->base_from_cam[i] = (float)d;
+      }
+    }
+    for (const FloatKey& f : floats)
+      if (key == f.name) {
+        known = true, ok = vals.size() == 1 && number(vals[0], &d);
+        *f.v = (float)d;
+      }
+    for (const IntKey& f : ints)
+      if (key == f.name) {
+        known = true, ok = vals.size() == 1 && number(vals[0], &d) && d == (double)(int)d;
+        *f.v = (int)d;
+      }
+    if (!known || !ok) {
+      *err = at + (known ? "wrong values for " : "unknown key ") + key;
+      return false;
+    }
+  }
+  return true;
+}
+}  // namespace
+
+void StereonetNode::ReadObstacleSettings() {
+  const char* e = getenv("STEREONET_OBSTACLES");
+  if (!e || !*e) return;
+  // obstacles.ObstacleParams' defaults: a 10 m x 10 m grid of 0.1 m cells ahead of a level camera, no scan
+  sn_obstacle_params& p = cfg_.obstacle_params;
+  p = sn_obstacle_params{};
+  p.y_min_m = -5.f, p.cell_m = 0.1f, p.gw = p.gh = 100;
+  p.z_floor_m = -0.15f, p.z_lo_m = 0.1f, p.z_hi_m = 1.5f, p.min_obstacle_hits = p.min_ground_hits = 3;
+  std::string bad;
+  if (!load_obstacle_file(e, &p, &cfg_.obstacle_frame, &bad)) bad = std::string("STEREONET_OBSTACLES=") + e + ": " + bad;
+  if (bad.empty() && cfg_.pointcloud_layout < 0) ReadCamera(&bad);      // the point cloud's camera, read once
+  // checked once here, on empty buffers: what sn_obstacles_from_raw would refuse turns the stage off instead of failing every frame
+  std::vector<float> edges(p.beams > 0 && p.beams <= 4096 ? p.beams + 1 : 0);
+  if (bad.empty() && !p.gw && !p.beams) bad = "neither a grid (gw, gh) nor a scan (beams)";
+  if (bad.empty() && p.beams && (edges.empty() || sn_obstacle_beam_edges(&p, edges.data()) != SN_OK))
+    bad = "the sector must have 1..4096 beams inside (-pi/2, pi/2)";
+  if (bad.empty()) {
+    std::vector<int32_t> none((size_t)net_w_ * net_h_, 0);
+    std::vector<uint32_t> hits((size_t)p.gw * p.gh * 2);
+    std::vector<float> ranges(p.beams);
+    if (sn_obstacles_from_raw(net_->engine(), 1, none.data(), &cfg_.camera, &p, nullptr, p.gw ? hits.data() : nullptr, nullptr,
+                              p.beams ? ranges.data() : nullptr, nullptr, SN_MEM_HOST, nullptr) != SN_OK)
+      bad = sn_last_error(net_->engine());
+  }
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no obstacle grid and no scan");
+    return;
+  }
+  cfg_.obstacles = true;
+  RCLCPP_WARN_STREAM(kLog, "obstacles: frame " << cfg_.obstacle_frame << ", grid " << p.gw << " x " << p.gh << " cells of " << p.cell_m
+                                               << " m on /stereonet_obstacle_grid, " << p.beams << " beams on /stereonet_scan");
+}
+
+// nav_msgs/OccupancyGrid and sensor_msgs/LaserScan of the request's map: one sn_obstacles_from_raw call, the stamp of the
+// disparity message, the frame of the parameter file
+void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const int32_t* raw) {
+  const sn_obstacle_params& p = cfg_.obstacle_params;
+  nav_msgs::msg::OccupancyGrid grid;
+  sensor_msgs::msg::LaserScan scan;
+  grid.data.resize((size_t)p.gw * p.gh);
+  scan.ranges.resize(p.beams);
+  const int rc = sn_obstacles_from_raw(net_->engine(), 1, raw, &cfg_.camera, &p, p.gw ? grid.data.data() : nullptr, nullptr, nullptr,
+                                       p.beams ? scan.ranges.data() : nullptr, nullptr, SN_MEM_HOST, nullptr);
+  if (rc != SN_OK) {
+    RCLCPP_ERROR(kLog, "obstacles failed: %s", sn_last_error(net_->engine()));
+    return;
+  }
+  if (obstacle_grid_out_) {
+    grid.header.stamp = request.msg_header->stamp;
+    grid.header.frame_id = cfg_.obstacle_frame;
+    grid.info.map_load_time = request.msg_header->stamp;
+    grid.info.resolution = p.cell_m;
+    grid.info.width = p.gw;
+    grid.info.height = p.gh;
+    grid.info.origin.position.x = p.x_min_m;
+    grid.info.origin.position.y = p.y_min_m;
+    obstacle_grid_out_->publish(std::move(grid));
+  }
+  if (obstacle_scan_out_) {
+    scan.header.stamp = request.msg_header->stamp;
+    scan.header.frame_id = cfg_.obstacle_frame;
+    scan.angle_min = p.angle_min_rad + 0.5f * p.angle_increment_rad;      // beam i looks along the middle of its sector
+    scan.angle_increment = p.angle_increment_rad;
+    scan.angle_max = scan.angle_min + (float)(p.beams - 1) * p.angle_increment_rad;
+    scan.range_min = p.range_min_m;
+    scan.range_max = p.range_max_m;
+    obstacle_scan_out_->publish(std::move(scan));
+  }
 }
 
 void StereonetNode::LogModelIo() {
@@ -710,6 +865,8 @@ int StereonetNode::PostProcess(const std::shared_ptr<hobot::dnn_node::DnnNodeOut
   }
   if (pointcloud_out_ && !request->output_tensors.empty())
     PublishPointCloud(*request, static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
+  if (cfg_.obstacles && !request->output_tensors.empty())
+    PublishObstacles(*request, static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
   const auto& st = node_output->rt_stat;
   if (st && st->fps_updated)
     RCLCPP_WARN(kLog,

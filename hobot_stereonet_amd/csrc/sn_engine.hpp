@@ -231,6 +231,7 @@ struct sn_handle {
 #else
   static constexpr unsigned ablate_x = 0;      // the shipping library has no ablation code: every test of it folds away
 #endif
+  bool obstacle_rle = true;  // sn_obstacles_from_raw accumulates run-length per lane; SN_OBSTACLE_RLE=0: one set of atomics per point
   bool tail_fuse = true;     // the streamed last block carries the head (tail form); SN_TAIL_FUSE=0: block + k_head_final_f16
   int fuse_mode = 4;         // SN_FUSE: 4 = streaming fused blocks (default), 0 = two launches per block
   unsigned* dump = nullptr;  // 2 KB device scratch: where lanes without an output pixel store (fused head)
@@ -296,6 +297,16 @@ struct sn_handle {
   struct Render : Lane<RenderSlots> {
     sn::JpgPlan plan;
   } rnd;
+  // sn_obstacles_from_raw.  the beam edges of the last sector (device); host mode: the maps (and their pinned staging), then
+  // occ, hits, height_mm, ranges, stats; device mode: hits where the caller wants occ or stats without them
+  struct ObstacleSlots {
+    enum { kEdges = 0, kRaw, kPinRaw, kOcc, kHits, kHeight, kRanges, kStats, kCount };
+  };
+  struct Obstacles : Lane<ObstacleSlots> {
+    Obstacles() { buf[kPinRaw].pinned = true; }
+    int beams = 0;                     // the sector whose edges are in buf[kEdges]: 0 = none
+    float angle_min = 0.f, angle_increment = 0.f;
+  } obs;
   // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
   // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
   // lock: calls on one handle must not overlap.

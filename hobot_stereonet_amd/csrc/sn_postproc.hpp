@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier and render.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp and sn_render.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render and obstacles.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp and sn_obstacles.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -266,6 +266,30 @@ const int8_t* pair_input(Staging& s, int n, const void* in, int in_kind, int w2,
 }
 
 // ---- kernel launches (device pointers) ---------------------------------------------------------------------------------
+// the camera test of sn_pointcloud_from_raw and sn_obstacles_from_raw
+bool camera_ok(const sn_camera* cam) {
+  return cam && cam->fx > 0.f && std::isfinite(cam->fx) && cam->fy > 0.f && std::isfinite(cam->fy) && cam->baseline_mm > 0.f &&
+         (cam->step == 1 || cam->step == 2 || cam->step == 4);
+}
+
+// nullptr, or why sn_obstacles_from_raw refuses the parameters (the sector of a scan is ob_beam_edges' test)
+const char* obstacle_params_check(const sn_obstacle_params* p) {
+  if (!p) return "a NULL pointer";
+  for (float v : p->base_from_cam)
+    if (!std::isfinite(v)) return "base_from_cam must be finite";
+  for (float v : {p->x_min_m, p->y_min_m, p->cell_m, p->z_floor_m, p->z_lo_m, p->z_hi_m, p->angle_min_rad, p->angle_increment_rad,
+                  p->range_min_m, p->range_max_m})
+    if (!std::isfinite(v)) return "every parameter must be finite";
+  if (!(p->cell_m > 0.f)) return "cell_m must be positive";
+  if (p->gw < 0 || p->gh < 0 || p->gw > kObMaxCells || p->gh > kObMaxCells || (p->gw == 0) != (p->gh == 0))
+    return "gw and gh must be 1..4096, or both 0";
+  if (p->beams < 0 || p->beams > kObMaxBeams) return "beams must be 0..4096";
+  if (p->z_floor_m > p->z_lo_m || p->z_lo_m > p->z_hi_m) return "z_floor_m <= z_lo_m <= z_hi_m is required";
+  if (p->min_obstacle_hits < 0 || p->min_ground_hits < 0) return "the hit thresholds must not be negative";
+  if (p->range_min_m < 0.f || p->range_max_m < p->range_min_m) return "0 <= range_min_m <= range_max_m is required";
+  return nullptr;
+}
+
 bool lrc_params_ok(const sn_lrc_params* p) {
   return p && std::isfinite(p->tau_px) && std::isfinite(p->tau_rel) && p->tau_px >= 0.f && p->tau_rel >= 0.f;
 }
@@ -477,9 +501,7 @@ int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_
   if (!h || !raw || !cam || !points || n <= 0 || n > h->max_batch || ((uintptr_t)points & 15) ||
       (layout != SN_PC_ORGANISED && layout != SN_PC_COMPACT) || (layout == SN_PC_COMPACT && !counts))
     return SN_ERR_ARG;
-  if (!(cam->fx > 0.f) || !std::isfinite(cam->fx) || !(cam->fy > 0.f) || !std::isfinite(cam->fy) ||
-      !(cam->baseline_mm > 0.f) || (cam->step != 1 && cam->step != 2 && cam->step != 4))
-    return SN_ERR_ARG;
+  if (!camera_ok(cam)) return SN_ERR_ARG;
   if (nv12 && (nv12_pitch < h->W || (nv12_pitch & 1))) return SN_ERR_ARG;
   using P = sn_handle::PointCloud;
   Bracket b(h, "sn_pointcloud_from_raw", mem, stream, h->pc);
@@ -523,6 +545,104 @@ int sn_pointcloud_from_raw(sn_handle* h, int n, const int32_t* raw, const uint8_
       if (e) return e;
     }
   }
+  return b.close();
+}
+
+// ---- obstacle grid and laser scan (csrc/sn_obstacles.hpp): a lane of the handle's; host mode stages the maps through pinned
+// memory as the point cloud does ------------------------------------------------------------------------------------------------
+int sn_obstacle_beam_edges(const sn_obstacle_params* p, float* edges) {
+  return p && edges && ob_beam_edges(p->beams, p->angle_min_rad, p->angle_increment_rad, edges) ? SN_OK : SN_ERR_ARG;
+}
+
+int sn_obstacles_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_camera* cam, const sn_obstacle_params* p, int8_t* occ,
+                          uint32_t* hits, int32_t* height_mm, float* ranges, uint32_t* stats, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_obstacles_from_raw: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!raw) return refuse("a NULL pointer");
+  if (n <= 0 || n > h->max_batch) return refuse("n outside 1..max_batch");
+  if (!camera_ok(cam)) return refuse("a camera sn_pointcloud_from_raw refuses");
+  if (const char* why = obstacle_params_check(p)) return refuse(why);
+  if (!occ && !hits && !height_mm && !ranges) return refuse("one of occ, hits, height_mm and ranges is needed");
+  if ((occ || hits || height_mm || stats) && !p->gw) return refuse("occ, hits, height_mm and stats need a grid (gw, gh > 0)");
+  if (ranges && !p->beams) return refuse("ranges needs beams > 0");
+  std::vector<float> edges;
+  if (ranges) {
+    edges.resize(p->beams + 1);
+    if (!ob_beam_edges(p->beams, p->angle_min_rad, p->angle_increment_rad, edges.data()))
+      return refuse("the sector must lie inside (-pi/2, pi/2) with strictly increasing edges");
+  }
+  const int W = h->W, H = h->H, step = cam->step;
+  const int Wo = (W + step - 1) / step, Ho = (H + step - 1) / step;
+  const size_t cells = (size_t)p->gw * p->gh, raw_bytes = (size_t)n * H * W * 4;
+  const size_t occ_bytes = n * cells, hits_bytes = n * cells * 8, height_bytes = n * cells * 4, ranges_bytes = (size_t)n * p->beams * 4,
+               stats_bytes = (size_t)n * 16;
+  {
+    const Span in{raw, raw_bytes};
+    const Span out[5] = {{occ, occ_bytes}, {hits, hits_bytes}, {height_mm, height_bytes}, {ranges, ranges_bytes}, {stats, stats_bytes}};
+    for (int i = 0; i < 5; ++i) {
+      if (overlap({in}, {out[i]})) return refuse("overlapping buffers");
+      for (int j = i + 1; j < 5; ++j)
+        if (overlap({out[i]}, {out[j]})) return refuse("overlapping buffers");
+    }
+  }
+  using O = sn_handle::Obstacles;
+  O& lane = h->obs;
+  Bracket b(h, "sn_obstacles_from_raw", mem, stream, lane);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  const bool grid = occ || hits || height_mm || stats;
+  const int32_t* draw = s.in_pinned(O::kPinRaw, O::kRaw, raw, raw_bytes);
+  int8_t* docc = s.out(O::kOcc, occ, occ_bytes);
+  uint32_t* dhits = s.out(O::kHits, hits, hits_bytes, grid);      // every grid output comes from the counts
+  int32_t* dheight = s.out(O::kHeight, height_mm, height_bytes);
+  uint32_t* dranges = s.out(O::kRanges, reinterpret_cast<uint32_t*>(ranges), ranges_bytes);
+  uint32_t* dstats = s.out(O::kStats, stats, stats_bytes);
+  const bool same_sector = ranges && lane.beams == p->beams && lane.angle_min == p->angle_min_rad &&
+                           lane.angle_increment == p->angle_increment_rad;
+  float* dedges = ranges ? s.scratch<float>(O::kEdges, (size_t)(kObMaxBeams + 1) * 4) : nullptr;
+  if (s.rc) return s.rc;
+  if (ranges && !same_sector) {      // a new sector is rare: its table is uploaded behind the lane's earlier calls and waited for
+    lane.beams = 0;
+    HIP_TRY(h, hipMemcpyAsync(dedges, edges.data(), edges.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    lane.beams = p->beams, lane.angle_min = p->angle_min_rad, lane.angle_increment = p->angle_increment_rad;
+  }
+  ObArgs a{};
+  a.pc.raw = draw;
+  a.pc.W = W, a.pc.H = H, a.pc.Wo = Wo, a.pc.Ho = Ho, a.pc.step = step;
+  a.pc.scale = kOutScale, a.pc.fB = cam->fx * cam->baseline_mm, a.pc.fx = cam->fx, a.pc.fy = cam->fy, a.pc.cx = cam->cx, a.pc.cy = cam->cy;
+  a.pc.zmin = cam->z_min_m, a.pc.zmax = cam->z_max_m;
+  a.edges = dedges, a.hits = dhits, a.height = dheight, a.ranges = dranges;
+  bool level = true;
+  for (float v : p->base_from_cam) level = level && v == 0.f;
+  const float level_mount[12] = {0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0};
+  memcpy(a.m, level ? level_mount : p->base_from_cam, sizeof a.m);
+  a.x_min = p->x_min_m, a.y_min = p->y_min_m, a.cell = p->cell_m, a.z_floor = p->z_floor_m, a.z_lo = p->z_lo_m, a.z_hi = p->z_hi_m;
+  a.r_min = p->range_min_m, a.r_max = p->range_max_m;
+  a.gw = p->gw, a.gh = p->gh, a.beams = ranges ? p->beams : 0;
+  // a workgroup is 256 columns of a chunk of rows: about 2048 workgroups a call, and runs of at least 16 rows
+  const int cblocks = (Wo + 255) / 256;
+  a.chunks = std::max(1, std::min((2048 + cblocks * n - 1) / (cblocks * n), (Ho + 15) / 16));
+  a.rows = (Ho + a.chunks - 1) / a.chunks;
+  a.chunks = (Ho + a.rows - 1) / a.rows;
+  {
+    const ObFillArgs f{dhits, dstats, dheight, dranges, dhits ? n * cells * 2 : 0, dstats ? (size_t)n * 4 : 0, dheight ? n * cells : 0,
+                       dranges ? (size_t)n * p->beams : 0};
+    const size_t words = f.n_hits + f.n_stats + f.n_height + f.n_ranges;
+    hipLaunchKernelGGL(k_ob_fill, dim3((unsigned)std::min<size_t>((words + 255) / 256, 2048)), dim3(256), 0, st, f);
+  }
+  const dim3 acc_grid(cblocks * a.chunks, n);
+  if (h->obstacle_rle) hipLaunchKernelGGL(k_ob_accumulate<true>, acc_grid, dim3(256), dranges ? (2 * a.beams + 1) * 4 : 0, st, a);
+  else hipLaunchKernelGGL(k_ob_accumulate<false>, acc_grid, dim3(256), dranges ? (a.beams + 1) * 4 : 0, st, a);
+  if (docc || dstats) {
+    ObClassArgs c{dhits, docc, dstats, (int)cells, p->min_obstacle_hits, p->min_ground_hits};
+    const int per_map = (int)std::max<size_t>(1, std::min<size_t>((cells + 255) / 256, 1024 / n));
+    hipLaunchKernelGGL(k_ob_classify, dim3(per_map, n), dim3(256), 0, st, c);
+  }
+  HIP_TRY(h, hipGetLastError());
   return b.close();
 }
 

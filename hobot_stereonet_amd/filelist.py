@@ -7,7 +7,8 @@ D1) needed to score the output against dataset ground truth.
         [--ply DIR [--camera fx,fy,cx,cy,baseline_mm]] [--lrc TAU_PX[,TAU_REL]] \
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
-        [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]]
+        [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]] \
+        [--obstacles PARAMS_FILE]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -62,6 +63,12 @@ FINAL map of the chain and the frame's left eye: the left eye on top, the colour
 `sn_render`.  The default is the reference's published picture (its colour map with red and blue swapped, raw == 0 painted like
 the farthest depth); --render-true-colours keeps the colour map's own colours, --render-invalid-black paints pixels without a
 measurement (raw == 0, what the masks above leave) black.  Every record gains "render_bytes".
+
+--obstacles PARAMS_FILE (obstacles.save_params' `key value` lines) reduces the FINAL map of the chain on the GPU
+(`sn_obstacles_from_raw`) to where a robot cannot drive, with --camera or the rectifier's camera as --ply: <i>.grid.pgm, the
+occupancy grid seen from above with forward up (0 occupied, 128 unknown, 255 free), and <i>.scan.txt, one `angle range` line per
+beam of the laser scan, are written into --out; the summary gains per pair "occupied" and "free" (cells) and "nearest_m" (the
+smallest range, null without a return).
 """
 import argparse
 import json
@@ -137,7 +144,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None, view=None) -> List[dict]:
+                jpeg=None, view=None, obstacle=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -163,7 +170,9 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     "jpeg_bytes", and <i>.left.jpg is written.
     view = ("jpeg", quality, rows_per_slice, render.RenderParams) or ("ppm", render.RenderParams): the record gains "render" (the
     stream of engine.render_jpeg, or the RGB8 canvas of engine.render, of the final map under the left eye) and "render_bytes",
-    and <i>.render.jpg / <i>.render.ppm is written."""
+    and <i>.render.jpg / <i>.render.ppm is written.
+    obstacle = an obstacles.ObstacleParams: the record gains "occ", "ranges" and "obstacle_stats" (engine.obstacles of the final
+    map, `camera` as for the cloud), "occupied", "free" and "nearest_m"; <i>.grid.pgm and <i>.scan.txt are written."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -179,7 +188,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
         if rectify is not None:
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
-        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view)
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle)
     finally:
         if rect is not None:
             rect.close()
@@ -188,7 +197,8 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     return results
 
 
-def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None):
+def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None,
+          obstacle=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -249,6 +259,11 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             else:
                 rec["render"] = engine.render(raw, sbs, 2 * w, view[1])
                 rec["render_bytes"] = int(rec["render"].size)
+        if obstacle is not None:      # the final map
+            occ, _, _, ranges, stats = engine.obstacles(raw, camera, obstacle)
+            near = float(ranges.min()) if ranges.size else float("inf")
+            rec.update(occ=occ, ranges=ranges, obstacle_stats=stats, occupied=int(stats[2]), free=int(stats[3]),
+                       nearest_m=near if np.isfinite(near) else None)
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -287,6 +302,12 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
                     f.write(rec["render"])
             elif view is not None:
                 images.write_ppm(os.path.join(out_dir, f"{i}.render.ppm"), rec["render"])
+            if obstacle is not None:
+                from . import obstacles as obs
+                if obstacle.gw:
+                    obs.write_pgm(os.path.join(out_dir, f"{i}.grid.pgm"), obs.grid_image(rec["occ"]))
+                if obstacle.beams:
+                    obs.write_scan(os.path.join(out_dir, f"{i}.scan.txt"), obstacle, rec["ranges"])
             if rect is not None:
                 from . import rectify as rct
                 images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
@@ -340,6 +361,9 @@ def main(argv=None) -> int:
     ap.add_argument("--render", default=None, metavar="jpeg[,Q[,ROWS]]|ppm",
                     help="write <i>.render.jpg (quality Q, default 95; restart intervals of ROWS MCU rows, default 1) or "
                          "<i>.render.ppm: the left eye over the colour-mapped depth of the final map, made on the GPU; needs --out")
+    ap.add_argument("--obstacles", default=None, metavar="PARAMS_FILE",
+                    help="write <i>.grid.pgm and <i>.scan.txt: the obstacle grid and the laser scan of the final map, made on the GPU "
+                         "with --camera or the rectifier's camera; needs --out")
     ap.add_argument("--render-true-colours", action="store_true", help="--render: the colour map's own colours, not the reference's R/B swap")
     ap.add_argument("--render-invalid-black", action="store_true", help="--render: pixels without a measurement (raw == 0) are black")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
@@ -445,13 +469,25 @@ def main(argv=None) -> int:
             ap.error("--render takes jpeg[,Q[,ROWS]] (integers) or ppm, and needs --out")
     elif args.render_true_colours or args.render_invalid_black:
         ap.error("--render-true-colours and --render-invalid-black need --render")
+    obstacle = None
+    if args.obstacles is not None:
+        from . import obstacles as obs
+        try:
+            obstacle = obs.load_params(args.obstacles)
+            why = obs.check(obstacle) or (None if args.out else "needs --out")
+            if obstacle.beams:
+                obs.beam_edges(obstacle)
+            if why:
+                raise ValueError(why)
+        except (OSError, ValueError) as e:
+            ap.error(f"--obstacles {args.obstacles}: {e}")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg, view=rnd)
+                               jpeg=jpg, view=rnd, obstacle=obstacle)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -462,6 +498,9 @@ def main(argv=None) -> int:
         summary["jpeg_bytes"] = int(sum(r["jpeg_bytes"] for r in recs))
     if rnd is not None and recs:
         summary["render_bytes"] = int(sum(r["render_bytes"] for r in recs))
+    if obstacle is not None and recs:
+        for k in ("occupied", "free", "nearest_m"):
+            summary[k] = [r[k] for r in recs]
     if args.gt and recs:
         for k in ("epe", "bad1", "bad3", "d1"):
             summary[k] = float(np.nanmean([r["metrics"][k] for r in recs]))

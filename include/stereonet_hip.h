@@ -895,6 +895,59 @@ int  sn_render(sn_handle *h, int n, const int32_t *raw, const uint8_t *left_nv12
 int  sn_render_jpeg(sn_handle *h, int n, const int32_t *raw, const uint8_t *left_nv12, int left_pitch, const sn_render_params *p,
                     const sn_jpeg_params *jp, uint8_t *out, size_t out_stride, uint32_t *sizes, int mem, void *stream);
 
+/* ---- bird's-eye obstacle grid and laser scan from the int32 map (csrc/sn_obstacles.hpp; hobot_stereonet_amd/obstacles.py is
+ * the numpy twin, byte for byte) ------------------------------------------------------------------------------------------
+ * What a robot needs of the point cloud: where it cannot drive.  A nav_msgs/OccupancyGrid and a sensor_msgs/LaserScan per map,
+ * reduced on the device: the call reads the 4 bytes a pixel sn_pointcloud_from_raw reads and writes a few thousand numbers.
+ *
+ * Points.  The samples are sn_pointcloud_from_raw's: (u, v) = (j*step, i*step) of map k; Z, X, Y and valid exactly as there
+ *   (the same device functions), cam's z_min_m / z_max_m / step honoured.  The base frame (x forward, y left, z up) in fp32,
+ *   left to right, every operation rounded (no FMA), m = base_from_cam:
+ *     xb = ((m0*X + m1*Y) + m2*Z) + m3,   yb likewise from m4..m7,   zb likewise from m8..m11
+ *   Class from zb: ground z_floor_m <= zb <= z_lo_m; obstacle z_lo_m < zb <= z_hi_m; anything else (overhead, below the floor,
+ *   NaN) counts nowhere.
+ * Grid.  qx = floorf((xb - x_min_m) / cell_m), qy likewise from yb and y_min_m; the point is in the grid when
+ *   qx >= 0 && qx < (float)gw && qy >= 0 && qy < (float)gh (tested in float before the conversion to int); cell = qy*gw + qx.
+ *   hits      [n][gh][gw][2] = {obstacle points, ground points} of the cell
+ *   height_mm [n][gh][gw]    = the maximum over the cell's obstacle points of (int)floorf(zb * 1000.f) (saturated to int32),
+ *                              INT32_MIN without one
+ *   occ       [n][gh][gw]    = 100 when obstacle hits >= min_obstacle_hits, else 0 when ground hits >= min_ground_hits, else -1
+ *   stats     [n][4]         = {obstacle points in the grid, ground points in the grid, occupied cells, free cells}
+ * Scan.  sn_obstacle_beam_edges: edges[i] = (float)tan((double)angle_min_rad + (double)i * (double)angle_increment_rad),
+ *   i = 0..beams; SN_ERR_ARG unless 1 <= beams <= 4096, every angle lies inside (-pi/2, pi/2) and the edges increase strictly.
+ *   An obstacle-class point contributes, whether or not the grid holds it, when xb > 0, t = yb / xb has
+ *   edges[0] <= t < edges[beams], and r = sqrtf(xb*xb + yb*yb) (two rounded products, one rounded sum) has
+ *   range_min_m <= r <= range_max_m.  Its beam is the number of edges <= t, minus 1 (a binary search on the table).
+ *   ranges [n][beams] = the minimum r per beam, +inf (bits 0x7f800000) without a return.
+ * Every accumulator is an integer (a positive float orders as its bits), so the outputs do not depend on the order in which
+ * the points arrive.
+ *
+ * Every output is nullable; a call needs occ, hits, height_mm or ranges.  The grid outputs (occ, hits, height_mm, stats)
+ * require gw, gh > 0, ranges requires beams > 0.  SN_ERR_ARG (sn_last_error(h) says why; nothing is launched or written):
+ * n outside 1..max_batch, raw / cam / p NULL, a camera sn_pointcloud_from_raw would refuse, a float of p that is not finite,
+ * cell_m <= 0, gw or gh negative or > 4096 or only one of them 0, beams negative or > 4096, z_floor_m > z_lo_m or
+ * z_lo_m > z_hi_m, a negative hit threshold, range_min_m < 0 or range_max_m < range_min_m, a sector sn_obstacle_beam_edges
+ * refuses (beams > 0), overlapping buffers, a bad mem.  Whether R is a rotation is not checked.
+ * mem / stream / blocking and SN_ERR_NOMEM as sn_pointcloud_from_raw: a lane of the handle's with a stream, an event and
+ * grow-only buffers of its own, freed by sn_destroy; may run beside sn_submit / sn_wait and beside the other stages.
+ * Not covered: the asynchronous sn_submit* slots, beams beyond +-90 degrees, ray clearing of the cells in front of an obstacle,
+ * negative obstacles (below z_floor_m), hit thresholds that fall with range. */
+typedef struct sn_obstacle_params {
+  float base_from_cam[12];          /* row-major 3x4 [R|t], metres: p_base = R p_cam + t.  Camera frame as the point cloud's
+                                       (X right, Y down, Z forward); base frame x forward, y left, z up.  All twelve zero =
+                                       the level forward mount R = [[0,0,1],[-1,0,0],[0,-1,0]], t = 0 */
+  float x_min_m, y_min_m, cell_m;   /* cell (ix, iy) covers [x_min + ix*cell, +cell) x [y_min + iy*cell, +cell) */
+  int   gw, gh;                     /* cells along x and y; data index iy*gw + ix (nav_msgs/OccupancyGrid); 0,0 = no grid */
+  float z_floor_m, z_lo_m, z_hi_m;  /* ground: z_floor <= zb <= z_lo; obstacle: z_lo < zb <= z_hi; else ignored */
+  int   min_obstacle_hits, min_ground_hits;
+  int   beams;                      /* 0 = no scan */
+  float angle_min_rad, angle_increment_rad, range_min_m, range_max_m;
+} sn_obstacle_params;
+int sn_obstacle_beam_edges(const sn_obstacle_params *p, float *edges /* beams + 1 */);      /* pure host, no device */
+int sn_obstacles_from_raw(sn_handle *h, int n, const int32_t *raw, const sn_camera *cam, const sn_obstacle_params *p,
+                          int8_t *occ, uint32_t *hits, int32_t *height_mm, float *ranges, uint32_t *stats,
+                          int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
