@@ -136,6 +136,27 @@ def obstacle_params(p) -> SnObstacleParams:
                             p.range_min_m, p.range_max_m)
 
 
+class SnGroundParams(C.Structure):
+    """sn_ground_params (include/stereonet_hip.h); ground.GroundParams is the Python face of it."""
+    _fields_ = [("base_from_cam", C.c_float * 12), ("roi_x", C.c_int), ("roi_y", C.c_int), ("roi_w", C.c_int), ("roi_h", C.c_int),
+                ("hypotheses", C.c_int), ("seed", C.c_uint32), ("min_area", C.c_int), ("min_inliers", C.c_int), ("refits", C.c_int),
+                ("tol_px", C.c_float), ("max_tilt_rad", C.c_float), ("height_min_m", C.c_float), ("height_max_m", C.c_float)]
+
+
+class SnGround(C.Structure):
+    """sn_ground (include/stereonet_hip.h); ground.RECORD is the numpy dtype of it."""
+    _fields_ = [("flags", C.c_uint32), ("usable", C.c_uint32), ("inliers", C.c_uint32), ("winner", C.c_int32), ("survivors", C.c_uint32),
+                ("reserved", C.c_uint32), ("plane_q16", C.c_int64 * 3), ("plane_cam", C.c_float * 4), ("base_from_cam", C.c_float * 12)]
+
+
+def ground_params(p) -> SnGroundParams:
+    """ground.GroundParams -> sn_ground_params"""
+    if isinstance(p, SnGroundParams):
+        return p
+    return SnGroundParams((C.c_float * 12)(*p.base_from_cam), p.roi_x, p.roi_y, p.roi_w, p.roi_h, p.hypotheses, p.seed, p.min_area,
+                          p.min_inliers, p.refits, p.tol_px, p.max_tilt_rad, p.height_min_m, p.height_max_m)
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -276,6 +297,10 @@ def load_library(path: Optional[str] = None):
     lib.sn_render_jpeg.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnRenderParams), C.POINTER(SnJpegParams), u8p, C.c_size_t, vp, ip, vp]
     lib.sn_obstacle_beam_edges.argtypes = [C.POINTER(SnObstacleParams), fp]
     lib.sn_obstacles_from_raw.argtypes = [vp, ip, i32p, C.POINTER(SnCamera), C.POINTER(SnObstacleParams), vp, vp, i32p, fp, vp, ip, vp]
+    lib.sn_obstacles_from_raw_mounts.argtypes = [vp, ip, i32p, C.POINTER(SnCamera), C.POINTER(SnObstacleParams), fp, ip, vp, vp, i32p, fp, vp,
+                                                 ip, vp]
+    lib.sn_ground_gate.argtypes = [C.POINTER(SnCamera), C.POINTER(SnGroundParams), ip, ip, vp]
+    lib.sn_ground_from_raw.argtypes = [vp, ip, i32p, C.POINTER(SnCamera), C.POINTER(SnGroundParams), vp, u8p, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -289,7 +314,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -356,6 +381,22 @@ def beam_edges(params) -> np.ndarray:
     if rc:
         raise StereoNetError(rc, "sn_obstacle_beam_edges")
     return edges
+
+
+def _sn_camera(cam, w: int, h: int) -> "SnCamera":
+    c = cam.resolved(w, h)
+    return SnCamera(c.fx, c.fy, c.cx, c.cy, c.baseline_mm, c.z_min_m, c.z_max_m, c.step)
+
+
+def ground_gate(cam, params, w: int, h: int) -> np.ndarray:
+    """sn_ground_gate (host only): int64 (6,), the Q16 bounds on the plane's a, b and c that a hypothesis must meet;
+    ground.gate is the numpy twin (the two may differ by one: two implementations of a double cos and sin)."""
+    c, prm = _sn_camera(cam, w, h), ground_params(params)
+    gate = np.empty(6, np.int64)
+    rc = load_library().sn_ground_gate(C.byref(c), C.byref(prm), w, h, gate.ctypes.data)
+    if rc:
+        raise StereoNetError(rc, "sn_ground_gate")
+    return gate
 
 
 def error_string(code: int) -> str:
@@ -618,12 +659,13 @@ class StereoNetHIP:
                     "sn_pointcloud_from_raw")
 
     # -- obstacle grid and laser scan ------------------------------------------------------------------
-    def obstacles(self, raw: np.ndarray, cam, params, grid: bool = True, scan: bool = True):
+    def obstacles(self, raw: np.ndarray, cam, params, grid: bool = True, scan: bool = True, mounts=None):
         """sn_obstacles_from_raw on host buffers: int32 (H,W) or (n,H,W) -> (occ int8 (n, gh, gw), hits uint32 (n, gh, gw, 2),
         height_mm int32 (n, gh, gw), ranges float32 (n, beams), stats uint32 (n, 4)), leading n dropped for a 2-D raw;
         obstacles.reference is the numpy twin.  cam: pointcloud.Camera (None: as pointcloud()); params:
         obstacles.ObstacleParams.  Without a grid (gw = gh = 0, or grid=False) the grid outputs are empty, without a scan
-        (beams = 0, or scan=False) ranges is."""
+        (beams = 0, or scan=False) ranges is.  mounts: float32 (n, 12), one base_from_cam per map (sn_obstacles_from_raw_mounts:
+        params.base_from_cam is then ignored), e.g. ground()'s records' base_from_cam."""
         r = self._maps(raw, "obstacles")
         n = self._count(r)
         c, prm = self._camera(cam), obstacle_params(params)
@@ -632,23 +674,63 @@ class StereoNetHIP:
         occ, hits = np.empty((n, gh, gw), np.int8), np.empty((n, gh, gw, 2), np.uint32)
         height, ranges, stats = np.empty((n, gh, gw), np.int32), np.empty((n, beams), np.float32), np.zeros((n, 4), np.uint32)
         g = gw * gh > 0
-        self._check(self._lib.sn_obstacles_from_raw(self._h, n, r.ctypes.data, C.byref(c), C.byref(prm), _np_ptr(occ if g else None),
-                                                    _np_ptr(hits if g else None), _np_ptr(height if g else None),
-                                                    _np_ptr(ranges if beams else None), _np_ptr(stats if g else None), SN_MEM_HOST, None),
-                    "sn_obstacles_from_raw")
+        outs = (_np_ptr(occ if g else None), _np_ptr(hits if g else None), _np_ptr(height if g else None),
+                _np_ptr(ranges if beams else None), _np_ptr(stats if g else None), SN_MEM_HOST, None)
+        if mounts is None:
+            self._check(self._lib.sn_obstacles_from_raw(self._h, n, r.ctypes.data, C.byref(c), C.byref(prm), *outs), "sn_obstacles_from_raw")
+        else:
+            m = np.ascontiguousarray(mounts, np.float32)
+            if m.size != n * 12:
+                raise StereoNetError(-1, "obstacles", f"mounts of shape {m.shape} for {n} maps: (n, 12) is needed")
+            self._check(self._lib.sn_obstacles_from_raw_mounts(self._h, n, r.ctypes.data, C.byref(c), C.byref(prm), m.ctypes.data, 12, *outs),
+                        "sn_obstacles_from_raw_mounts")
         out = (occ, hits, height, ranges, stats)
         return tuple(a[0] for a in out) if r.ndim == 2 else out
 
     beam_edges = staticmethod(beam_edges)      # sn_obstacle_beam_edges needs no engine; here beside the calls that use its table
 
     def obstacles_device(self, n: int, raw_ptr: int, cam, params, occ_ptr: int = 0, hits_ptr: int = 0, height_ptr: int = 0,
-                         ranges_ptr: int = 0, stats_ptr: int = 0, stream: int = 0):
+                         ranges_ptr: int = 0, stats_ptr: int = 0, stream: int = 0, mounts_ptr: int = 0, mount_stride: int = 12):
         """sn_obstacles_from_raw on device pointers (0: that output is not wanted); stream = hipStream_t as int (0: the stage's
-        own stream, and the call returns after completion)."""
+        own stream, and the call returns after completion).  mounts_ptr: sn_obstacles_from_raw_mounts, map k's mount at
+        mounts_ptr + 4 * k * mount_stride (ground_device's records: their address + 64, ground.RECORD_FLOATS)."""
         c, prm = self._camera(cam), obstacle_params(params)
+        if mounts_ptr:
+            self._check(self._lib.sn_obstacles_from_raw_mounts(self._h, n, raw_ptr, C.byref(c), C.byref(prm), mounts_ptr, mount_stride,
+                                                               occ_ptr or None, hits_ptr or None, height_ptr or None, ranges_ptr or None,
+                                                               stats_ptr or None, SN_MEM_DEVICE, stream or None),
+                        "sn_obstacles_from_raw_mounts")
+            return
         self._check(self._lib.sn_obstacles_from_raw(self._h, n, raw_ptr, C.byref(c), C.byref(prm), occ_ptr or None, hits_ptr or None,
                                                     height_ptr or None, ranges_ptr or None, stats_ptr or None, SN_MEM_DEVICE,
                                                     stream or None), "sn_obstacles_from_raw")
+
+    # -- ground plane -----------------------------------------------------------------------------------
+    def ground(self, raw: np.ndarray, cam, params, labels: bool = True):
+        """sn_ground_from_raw on host buffers: int32 (H,W) or (n,H,W) -> (records ground.RECORD (n,), labels uint8 (n, H, W) or
+        None), leading n dropped for a 2-D raw; ground.reference is the numpy twin.  cam: pointcloud.Camera (None: as
+        pointcloud()); params: ground.GroundParams.  ground.angles(rec["base_from_cam"]) gives pitch and roll."""
+        from . import ground as gr
+        r = self._maps(raw, "ground")
+        n = self._count(r)
+        c, prm = self._camera(cam), ground_params(params)
+        rec = np.zeros(n, gr.RECORD)
+        lab = np.empty((n, self.height, self.width), np.uint8) if labels else None
+        self._check(self._lib.sn_ground_from_raw(self._h, n, r.ctypes.data, C.byref(c), C.byref(prm), rec.ctypes.data, _np_ptr(lab),
+                                                 SN_MEM_HOST, None), "sn_ground_from_raw")
+        return (rec[0], lab[0] if labels else None) if r.ndim == 2 else (rec, lab)
+
+    def ground_gate(self, cam, params) -> np.ndarray:
+        """sn_ground_gate for this engine's map size (needs no device)"""
+        from . import pointcloud
+        return ground_gate(cam or pointcloud.Camera(), params, self.width, self.height)
+
+    def ground_device(self, n: int, raw_ptr: int, cam, params, ground_ptr: int = 0, labels_ptr: int = 0, stream: int = 0):
+        """sn_ground_from_raw on device pointers (0: that output is not wanted); stream = hipStream_t as int (0: the stage's own
+        stream, and the call returns after completion)."""
+        c, prm = self._camera(cam), ground_params(params)
+        self._check(self._lib.sn_ground_from_raw(self._h, n, raw_ptr, C.byref(c), C.byref(prm), ground_ptr or None, labels_ptr or None,
+                                                 SN_MEM_DEVICE, stream or None), "sn_ground_from_raw")
 
     # -- left-right consistency check -----------------------------------------------------------------
     def mirror_pair(self, in6: np.ndarray) -> np.ndarray:

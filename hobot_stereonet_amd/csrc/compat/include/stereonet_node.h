@@ -114,6 +114,13 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     bool obstacles = false;
     sn_obstacle_params obstacle_params{};
     std::string obstacle_frame = "base_link";
+    // this implementation's own: the ground plane of every frame's map (sn_ground_from_raw) ahead of the obstacle stage, which
+    // then classifies with the frame's mount (sn_obstacles_from_raw_mounts) instead of the obstacle file's base_from_cam.
+    // STEREONET_GROUND=<parameter file> (ground.save_params' `key value` lines) turns it on, with the camera of the point cloud
+    // and the obstacle stage; height and tilt are logged when they change by more than the file's log_delta; unset: off
+    bool ground = false;
+    sn_ground_params ground_params{};
+    float ground_log_delta = 0.02f;
   };
 
   void DeclareAndReadParameters();
@@ -122,7 +129,9 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   bool ReadCamera(std::string* bad);
   void ReadPointCloudSettings();
   void ReadObstacleSettings();
-  void PublishObstacles(const StereonetNodeOutput& request, const int32_t* raw);
+  void PublishObstacles(const StereonetNodeOutput& request, const int32_t* raw, const float* mount);
+  void ReadGroundSettings();
+  bool FitGround(const int32_t* raw, sn_ground* out);
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
   void ReadTemporalSettings();
   void ReadRectifySettings();
@@ -146,6 +155,7 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   std::atomic<bool> cloud_uncoloured_logged_{false};
   rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr obstacle_grid_out_;   // only while STEREONET_OBSTACLES configures a grid
   rclcpp::Publisher<sensor_msgs::msg::LaserScan>::SharedPtr obstacle_scan_out_;    // ... a scan
+  float ground_logged_[3] = {-1.f, 0.f, 0.f};     // height, pitch, roll of the last log line; PostProcess only
   sn_temporal* temporal_ = nullptr;              // one stream; only while STEREONET_TEMPORAL is set and valid
   bool temporal_unguided_logged_ = false;        // PostProcess only (one thread at a time)
   rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr render_out_;   // only while STEREONET_RENDER is set and valid

@@ -103,6 +103,7 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
   if (cfg_.render) render_out_ = create_publisher<sensor_msgs::msg::Image>("/image_jpeg", 10);
   if (cfg_.pointcloud_layout >= 0) pointcloud_out_ = create_publisher<sensor_msgs::msg::PointCloud2>("/stereonet_pointcloud2", 10);
   ReadObstacleSettings();
+  ReadGroundSettings();
   if (cfg_.obstacles && cfg_.obstacle_params.gw)
     obstacle_grid_out_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/stereonet_obstacle_grid", 10);
   if (cfg_.obstacles && cfg_.obstacle_params.beams)
@@ -550,14 +551,18 @@ void StereonetNode::ReadObstacleSettings() {
 
 // nav_msgs/OccupancyGrid and sensor_msgs/LaserScan of the request's map: one sn_obstacles_from_raw call, the stamp of the
 // disparity message, the frame of the parameter file
-void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const int32_t* raw) {
+void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const int32_t* raw, const float* mount) {
   const sn_obstacle_params& p = cfg_.obstacle_params;
   nav_msgs::msg::OccupancyGrid grid;
   sensor_msgs::msg::LaserScan scan;
   grid.data.resize((size_t)p.gw * p.gh);
   scan.ranges.resize(p.beams);
-  const int rc = sn_obstacles_from_raw(net_->engine(), 1, raw, &cfg_.camera, &p, p.gw ? grid.data.data() : nullptr, nullptr, nullptr,
-                                       p.beams ? scan.ranges.data() : nullptr, nullptr, SN_MEM_HOST, nullptr);
+  int8_t* occ = p.gw ? grid.data.data() : nullptr;
+  float* ranges = p.beams ? scan.ranges.data() : nullptr;
+  const int rc = mount ? sn_obstacles_from_raw_mounts(net_->engine(), 1, raw, &cfg_.camera, &p, mount, 12, occ, nullptr, nullptr, ranges,
+                                                      nullptr, SN_MEM_HOST, nullptr)      // the frame's mount, from FitGround
+                       : sn_obstacles_from_raw(net_->engine(), 1, raw, &cfg_.camera, &p, occ, nullptr, nullptr, ranges, nullptr,
+                                               SN_MEM_HOST, nullptr);
   if (rc != SN_OK) {
     RCLCPP_ERROR(kLog, "obstacles failed: %s", sn_last_error(net_->engine()));
     return;
@@ -583,6 +588,120 @@ void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const i
     scan.range_max = p.range_max_m;
     obstacle_scan_out_->publish(std::move(scan));
   }
+}
+
+namespace {
+// ground.load_params' text form, as load_obstacle_file
+bool load_ground_file(const char* path, sn_ground_params* p, float* log_delta, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct FloatKey {
+    const char* name;
+    float* v;
+  } floats[] = {{"tol_px", &p->tol_px}, {"max_tilt_rad", &p->max_tilt_rad}, {"height_min_m", &p->height_min_m},
+                {"height_max_m", &p->height_max_m}, {"log_delta", log_delta}};
+  struct IntKey {
+    const char* name;
+    int* v;
+  } ints[] = {{"roi_x", &p->roi_x}, {"roi_y", &p->roi_y}, {"roi_w", &p->roi_w}, {"roi_h", &p->roi_h}, {"hypotheses", &p->hypotheses},
+              {"min_area", &p->min_area}, {"min_inliers", &p->min_inliers}, {"refits", &p->refits}};
+  std::vector<std::string> seen;
+  std::string text;
+  for (int no = 1; std::getline(in, text); ++no) {
+    std::istringstream words(text.substr(0, text.find('#')));
+    std::string key, w;
+    if (!(words >> key)) continue;
+    std::vector<std::string> vals;
+    while (words >> w) vals.push_back(w);
+    const std::string at = "line " + std::to_string(no) + ": ";
+    for (const std::string& k : seen)
+      if (k == key) {
+        *err = at + key + " twice";
+        return false;
+      }
+    seen.push_back(key);
+    auto number = [&](const std::string& t, double* out) {
+      char* end = nullptr;
+      *out = strtod(t.c_str(), &end);
+      return end != t.c_str() && !*end;
+    };
+    bool known = false, ok = true;
+    double d = 0;
+    if (key == "base_from_cam") {
+      known = true, ok = vals.size() == 12;
+      for (int i = 0; ok && i < 12; ++i) {
+        ok = number(vals[i], &d);
+        p->base_from_cam[i] = (float)d;
+      }
+    } else if (key == "seed") {
+      known = true, ok = vals.size() == 1 && number(vals[0], &d) && d >= 0 && d <= 4294967295.0 && d == (double)(uint32_t)d;
+      p->seed = (uint32_t)d;
+    }
+    for (const FloatKey& f : floats)
+      if (key == f.name) {
+        known = true, ok = vals.size() == 1 && number(vals[0], &d);
+        *f.v = (float)d;
+      }
+    for (const IntKey& f : ints)
+      if (key == f.name) {
+        known = true, ok = vals.size() == 1 && number(vals[0], &d) && d >= -2147483648.0 && d <= 2147483647.0 && d == (double)(int)d;
+        *f.v = (int)d;
+      }
+    if (!known || !ok) {
+      *err = at + (known ? "wrong values for " : "unknown key ") + key;
+      return false;
+    }
+  }
+  return true;
+}
+}  // namespace
+
+void StereonetNode::ReadGroundSettings() {
+  const char* e = getenv("STEREONET_GROUND");
+  if (!e || !*e) return;
+  // ground.GroundParams' defaults: the lower half of the image, 256 hypotheses, two refits, a level prior
+  sn_ground_params& p = cfg_.ground_params;
+  p = sn_ground_params{};
+  p.hypotheses = 256, p.seed = 1, p.min_area = 64, p.min_inliers = 100, p.refits = 2;
+  p.tol_px = 0.1f, p.max_tilt_rad = 0.5f, p.height_min_m = 0.1f, p.height_max_m = 3.0f;
+  std::string bad;
+  if (!load_ground_file(e, &p, &cfg_.ground_log_delta, &bad)) bad = std::string("STEREONET_GROUND=") + e + ": " + bad;
+  if (bad.empty() && cfg_.pointcloud_layout < 0 && !cfg_.obstacles) ReadCamera(&bad);      // the point cloud's camera, read once
+  // checked once here, on an empty map: what sn_ground_from_raw would refuse turns the stage off instead of failing every frame
+  if (bad.empty()) {
+    std::vector<int32_t> none((size_t)net_w_ * net_h_, 0);
+    sn_ground g;
+    if (sn_ground_from_raw(net_->engine(), 1, none.data(), &cfg_.camera, &p, &g, nullptr, SN_MEM_HOST, nullptr) != SN_OK)
+      bad = sn_last_error(net_->engine());
+  }
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no ground plane" << (cfg_.obstacles ? ", the obstacle stage keeps its file's mount" : ""));
+    return;
+  }
+  cfg_.ground = true;
+  RCLCPP_WARN_STREAM(kLog, "ground: " << p.hypotheses << " hypotheses, " << p.refits << " refits, tol " << p.tol_px << " px"
+                                      << (cfg_.obstacles ? ", the obstacle stage takes every frame's mount" : ""));
+}
+
+// the frame's ground plane; logs height and tilt when either moved by more than log_delta since the last line
+bool StereonetNode::FitGround(const int32_t* raw, sn_ground* g) {
+  if (sn_ground_from_raw(net_->engine(), 1, raw, &cfg_.camera, &cfg_.ground_params, g, nullptr, SN_MEM_HOST, nullptr) != SN_OK) {
+    RCLCPP_ERROR(kLog, "ground failed: %s", sn_last_error(net_->engine()));
+    return false;
+  }
+  const float* m = g->base_from_cam;
+  const float hgt = m[11], pitch = std::asin(std::max(-1.f, std::min(1.f, -m[10]))), roll = std::asin(std::max(-1.f, std::min(1.f, -m[8])));
+  const float d = cfg_.ground_log_delta;
+  if (ground_logged_[0] < 0.f || std::fabs(hgt - ground_logged_[0]) > d || std::fabs(pitch - ground_logged_[1]) > d ||
+      std::fabs(roll - ground_logged_[2]) > d) {
+    RCLCPP_WARN(kLog, "ground: %s, height %.3f m, pitch %.4f rad, roll %.4f rad, %u inliers of %u",
+                (g->flags & SN_GROUND_FOUND) ? "found" : "not found (the prior mount)", hgt, pitch, roll, g->inliers, g->usable);
+    ground_logged_[0] = hgt, ground_logged_[1] = pitch, ground_logged_[2] = roll;
+  }
+  return true;
 }
 
 void StereonetNode::LogModelIo() {
@@ -865,8 +984,12 @@ int StereonetNode::PostProcess(const std::shared_ptr<hobot::dnn_node::DnnNodeOut
   }
   if (pointcloud_out_ && !request->output_tensors.empty())
     PublishPointCloud(*request, static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
-  if (cfg_.obstacles && !request->output_tensors.empty())
-    PublishObstacles(*request, static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
+  if ((cfg_.obstacles || cfg_.ground) && !request->output_tensors.empty()) {
+    const int32_t* raw = static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr);
+    sn_ground g;
+    const bool fitted = cfg_.ground && FitGround(raw, &g);
+    if (cfg_.obstacles) PublishObstacles(*request, raw, fitted ? g.base_from_cam : nullptr);
+  }
   const auto& st = node_output->rt_stat;
   if (st && st->fps_updated)
     RCLCPP_WARN(kLog,

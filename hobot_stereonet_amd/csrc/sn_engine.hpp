@@ -299,14 +299,23 @@ struct sn_handle {
   } rnd;
   // sn_obstacles_from_raw.  the beam edges of the last sector (device); host mode: the maps (and their pinned staging), then
   // occ, hits, height_mm, ranges, stats; device mode: hits where the caller wants occ or stats without them
+  // sn_obstacles_from_raw_mounts, host mode: the mounts, packed twelve a map
   struct ObstacleSlots {
-    enum { kEdges = 0, kRaw, kPinRaw, kOcc, kHits, kHeight, kRanges, kStats, kCount };
+    enum { kEdges = 0, kRaw, kPinRaw, kOcc, kHits, kHeight, kRanges, kStats, kMounts, kCount };
   };
   struct Obstacles : Lane<ObstacleSlots> {
     Obstacles() { buf[kPinRaw].pinned = true; }
     int beams = 0;                     // the sector whose edges are in buf[kEdges]: 0 = none
     float angle_min = 0.f, angle_increment = 0.f;
   } obs;
+  // sn_ground_from_raw.  the hypotheses, their counts and the moments (one allocation each), the per-map state; host mode: the
+  // maps (and their pinned staging), the records, the labels; device mode: the records where the caller wants labels alone
+  struct GroundSlots {
+    enum { kHyp = 0, kCounts, kAcc, kState, kRaw, kPinRaw, kGround, kLabels, kCount };
+  };
+  struct Ground : Lane<GroundSlots> {
+    Ground() { buf[kPinRaw].pinned = true; }
+  } gnd;
   // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
   // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
   // lock: calls on one handle must not overlap.

@@ -12,6 +12,7 @@
 //                     of a wave that leave their cells at the same row, and what the lanes hold at the end of the walk, are
 //                     summed over the wave's runs of equal cells first (ob_wave_flush): one set of atomics per run.
 //                     The ranges row is accumulated in LDS and flushed once per workgroup, finite entries only.
+//                     MOUNTS (sn_obstacles_from_raw_mounts): a second instantiation reads the map's mount from memory.
 //                     Plain form (SN_OBSTACLE_RLE=0): the same arithmetic, one set of global atomics per point.
 //   k_ob_classify     a pass over the cells: occ from the two counts and the thresholds, stats from block sums, one integer
 //                     atomic per workgroup and statistic (as k_pc_organised's count).
@@ -37,6 +38,8 @@ struct ObArgs {
   int32_t* height;        // [n][gh][gw], nullable
   uint32_t* ranges;       // [n][beams] as bits, or nullptr: no scan
   float m[12];
+  const float* mounts;    // MOUNTS: map k's mount is the twelve floats at mounts + k * mount_stride, and m is not used
+  int mount_stride;
   float x_min, y_min, cell, z_floor, z_lo, z_hi, r_min, r_max;
   int gw, gh, beams;
   int chunks, rows;       // row chunks per column block, output rows per chunk
@@ -141,13 +144,19 @@ __device__ __forceinline__ void ob_wave_flush(int cur, uint32_t n_ob, uint32_t n
 }
 
 // grid (column blocks * chunks, n), 256 lanes = 256 output columns; dynamic LDS: (beams + 1) floats [+ beams words, RLE]
-template <bool RLE>
+template <bool RLE, bool MOUNTS>
 __global__ __launch_bounds__(256) void k_ob_accumulate(ObArgs a) {
   extern __shared__ __align__(16) uint32_t ob_lds[];
   const bool grid = a.hits != nullptr, scan = a.ranges != nullptr;
   float* edges = reinterpret_cast<float*>(ob_lds);
   uint32_t* lds_near = ob_lds + a.beams + 1;      // RLE: this workgroup's copy of the ranges row
   const int k = blockIdx.y;
+  float own[12];      // MOUNTS: the map's mount, the same for every lane
+  if (MOUNTS) {
+#pragma unroll
+    for (int e = 0; e < 12; ++e) own[e] = a.mounts[(size_t)k * a.mount_stride + e];
+  }
+  const float* m = MOUNTS ? own : a.m;
   uint32_t* g_ranges = scan ? a.ranges + (size_t)k * a.beams : nullptr;
   if (scan) {
     for (int b = threadIdx.x; b <= a.beams; b += 256) edges[b] = a.edges[b];
@@ -195,10 +204,10 @@ __global__ __launch_bounds__(256) void k_ob_accumulate(ObArgs a) {
       int c = -1;
       if (pc_valid(r[e], z, a.pc)) {
         const float4 p = pc_point<false>(a.pc, nullptr, u, (ib + e) * a.pc.step, z);
-        zb = ob_row(a.m + 8, p.x, p.y, p.z);
+        zb = ob_row(m + 8, p.x, p.y, p.z);
         ground = a.z_floor <= zb && zb <= a.z_lo, obstacle = a.z_lo < zb && zb <= a.z_hi;
         if (ground || obstacle) {
-          xb = ob_row(a.m, p.x, p.y, p.z), yb = ob_row(a.m + 4, p.x, p.y, p.z);
+          xb = ob_row(m, p.x, p.y, p.z), yb = ob_row(m + 4, p.x, p.y, p.z);
           if (grid) c = ob_cell(a, xb, yb);
         }
       }

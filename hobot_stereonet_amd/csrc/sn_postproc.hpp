@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render and obstacles.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp and sn_obstacles.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles and ground plane.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp and sn_ground.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -554,14 +554,23 @@ int sn_obstacle_beam_edges(const sn_obstacle_params* p, float* edges) {
   return p && edges && ob_beam_edges(p->beams, p->angle_min_rad, p->angle_increment_rad, edges) ? SN_OK : SN_ERR_ARG;
 }
 
-int sn_obstacles_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_camera* cam, const sn_obstacle_params* p, int8_t* occ,
-                          uint32_t* hits, int32_t* height_mm, float* ranges, uint32_t* stats, int mem, void* stream) {
+namespace {
+// both entry points.  mounts: nullptr (p->base_from_cam is the mount of every map), or a mount per map
+int obstacles_call(sn_handle* h, const char* where, int n, const int32_t* raw, const sn_camera* cam, const sn_obstacle_params* p_in,
+                   const float* mounts, int mount_stride, int8_t* occ, uint32_t* hits, int32_t* height_mm, float* ranges, uint32_t* stats,
+                   int mem, void* stream) {
   if (!h) return SN_ERR_ARG;
   auto refuse = [&](const char* why) {
-    set_err(h, std::string("sn_obstacles_from_raw: ") + why);
+    set_err(h, std::string(where) + ": " + why);
     return SN_ERR_ARG;
   };
-  if (!raw) return refuse("a NULL pointer");
+  if (!raw || !p_in) return refuse("a NULL pointer");
+  sn_obstacle_params with_mounts;
+  if (mounts) {      // p->base_from_cam is ignored
+    with_mounts = *p_in;
+    for (float& v : with_mounts.base_from_cam) v = 0.f;
+  }
+  const sn_obstacle_params* p = mounts ? &with_mounts : p_in;
   if (n <= 0 || n > h->max_batch) return refuse("n outside 1..max_batch");
   if (!camera_ok(cam)) return refuse("a camera sn_pointcloud_from_raw refuses");
   if (const char* why = obstacle_params_check(p)) return refuse(why);
@@ -579,18 +588,19 @@ int sn_obstacles_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_came
   const size_t cells = (size_t)p->gw * p->gh, raw_bytes = (size_t)n * H * W * 4;
   const size_t occ_bytes = n * cells, hits_bytes = n * cells * 8, height_bytes = n * cells * 4, ranges_bytes = (size_t)n * p->beams * 4,
                stats_bytes = (size_t)n * 16;
+  const size_t mounts_bytes = mounts ? ((size_t)(n - 1) * mount_stride + 12) * 4 : 0;
   {
     const Span in{raw, raw_bytes};
     const Span out[5] = {{occ, occ_bytes}, {hits, hits_bytes}, {height_mm, height_bytes}, {ranges, ranges_bytes}, {stats, stats_bytes}};
     for (int i = 0; i < 5; ++i) {
-      if (overlap({in}, {out[i]})) return refuse("overlapping buffers");
+      if (overlap({in, Span{mounts, mounts_bytes}}, {out[i]})) return refuse("overlapping buffers");
       for (int j = i + 1; j < 5; ++j)
         if (overlap({out[i]}, {out[j]})) return refuse("overlapping buffers");
     }
   }
   using O = sn_handle::Obstacles;
   O& lane = h->obs;
-  Bracket b(h, "sn_obstacles_from_raw", mem, stream, lane);
+  Bracket b(h, where, mem, stream, lane);
   Staging& s = b.s;
   hipStream_t st = b.c.st;
   const bool grid = occ || hits || height_mm || stats;
@@ -600,6 +610,13 @@ int sn_obstacles_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_came
   int32_t* dheight = s.out(O::kHeight, height_mm, height_bytes);
   uint32_t* dranges = s.out(O::kRanges, reinterpret_cast<uint32_t*>(ranges), ranges_bytes);
   uint32_t* dstats = s.out(O::kStats, stats, stats_bytes);
+  std::vector<float> packed;      // host mode: the mounts, twelve a map (the call is blocking, so it outlives the copy)
+  const float* dmounts = mounts;
+  if (mounts && s.host) {
+    packed.resize((size_t)n * 12);
+    for (int k = 0; k < n; ++k) memcpy(&packed[(size_t)k * 12], mounts + (size_t)k * mount_stride, 48);
+    dmounts = s.in(O::kMounts, packed.data(), packed.size() * 4);
+  }
   const bool same_sector = ranges && lane.beams == p->beams && lane.angle_min == p->angle_min_rad &&
                            lane.angle_increment == p->angle_increment_rad;
   float* dedges = ranges ? s.scratch<float>(O::kEdges, (size_t)(kObMaxBeams + 1) * 4) : nullptr;
@@ -620,6 +637,7 @@ int sn_obstacles_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_came
   for (float v : p->base_from_cam) level = level && v == 0.f;
   const float level_mount[12] = {0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0};
   memcpy(a.m, level ? level_mount : p->base_from_cam, sizeof a.m);
+  a.mounts = dmounts, a.mount_stride = mounts && s.host ? 12 : mount_stride;
   a.x_min = p->x_min_m, a.y_min = p->y_min_m, a.cell = p->cell_m, a.z_floor = p->z_floor_m, a.z_lo = p->z_lo_m, a.z_hi = p->z_hi_m;
   a.r_min = p->range_min_m, a.r_max = p->range_max_m;
   a.gw = p->gw, a.gh = p->gh, a.beams = ranges ? p->beams : 0;
@@ -635,12 +653,128 @@ int sn_obstacles_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_came
     hipLaunchKernelGGL(k_ob_fill, dim3((unsigned)std::min<size_t>((words + 255) / 256, 2048)), dim3(256), 0, st, f);
   }
   const dim3 acc_grid(cblocks * a.chunks, n);
-  if (h->obstacle_rle) hipLaunchKernelGGL(k_ob_accumulate<true>, acc_grid, dim3(256), dranges ? (2 * a.beams + 1) * 4 : 0, st, a);
-  else hipLaunchKernelGGL(k_ob_accumulate<false>, acc_grid, dim3(256), dranges ? (a.beams + 1) * 4 : 0, st, a);
+  const size_t lds = dranges ? ((h->obstacle_rle ? 2 : 1) * a.beams + 1) * 4 : 0;
+  if (h->obstacle_rle && mounts) hipLaunchKernelGGL((k_ob_accumulate<true, true>), acc_grid, dim3(256), lds, st, a);
+  else if (h->obstacle_rle) hipLaunchKernelGGL((k_ob_accumulate<true, false>), acc_grid, dim3(256), lds, st, a);
+  else if (mounts) hipLaunchKernelGGL((k_ob_accumulate<false, true>), acc_grid, dim3(256), lds, st, a);
+  else hipLaunchKernelGGL((k_ob_accumulate<false, false>), acc_grid, dim3(256), lds, st, a);
   if (docc || dstats) {
     ObClassArgs c{dhits, docc, dstats, (int)cells, p->min_obstacle_hits, p->min_ground_hits};
     const int per_map = (int)std::max<size_t>(1, std::min<size_t>((cells + 255) / 256, 1024 / n));
     hipLaunchKernelGGL(k_ob_classify, dim3(per_map, n), dim3(256), 0, st, c);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return b.close();
+}
+}  // namespace
+
+int sn_obstacles_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_camera* cam, const sn_obstacle_params* p, int8_t* occ,
+                          uint32_t* hits, int32_t* height_mm, float* ranges, uint32_t* stats, int mem, void* stream) {
+  return obstacles_call(h, "sn_obstacles_from_raw", n, raw, cam, p, nullptr, 0, occ, hits, height_mm, ranges, stats, mem, stream);
+}
+
+int sn_obstacles_from_raw_mounts(sn_handle* h, int n, const int32_t* raw, const sn_camera* cam, const sn_obstacle_params* p,
+                                 const float* mounts, int mount_stride, int8_t* occ, uint32_t* hits, int32_t* height_mm, float* ranges,
+                                 uint32_t* stats, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  if (!mounts || ((uintptr_t)mounts & 3) || mount_stride < 12) {
+    set_err(h, "sn_obstacles_from_raw_mounts: mounts must be a 4-byte aligned pointer with mount_stride >= 12");
+    return SN_ERR_ARG;
+  }
+  return obstacles_call(h, "sn_obstacles_from_raw_mounts", n, raw, cam, p, mounts, mount_stride, occ, hits, height_mm, ranges, stats,
+                        mem, stream);
+}
+
+// ---- ground plane (csrc/sn_ground.hpp): a lane of the handle's, staged as the obstacle stage ---------------------------------
+namespace {
+// nullptr, or why sn_ground_from_raw refuses the parameters (the region apart: gr_roi says)
+const char* ground_params_check(const sn_camera* cam, const sn_ground_params* p, int64_t* tol) {
+  if (!p) return "a NULL pointer";
+  if (!camera_ok(cam) || !std::isfinite(cam->cx) || !std::isfinite(cam->cy)) return "a camera sn_pointcloud_from_raw refuses, or cx, cy not finite";
+  for (float v : p->base_from_cam)
+    if (!std::isfinite(v)) return "base_from_cam must be finite";
+  for (float v : {p->tol_px, p->max_tilt_rad, p->height_min_m, p->height_max_m})
+    if (!std::isfinite(v)) return "every parameter must be finite";
+  if (p->hypotheses < 1 || p->hypotheses > kGrMaxHyp) return "hypotheses must be 1..1024";
+  if (p->refits < 0 || p->refits > kGrMaxRefits) return "refits must be 0..4";
+  if (p->min_area < 0 || p->min_inliers < 0) return "min_area and min_inliers must not be negative";
+  if (p->tol_px < 0.f) return "tol_px must not be negative";
+  const float q = floorf(p->tol_px / gr_scale(kOutScale));      // sn_temporal's rule
+  if (!(q <= (float)kGrMaxRaw)) return "tol_px is too large (tol_raw <= 2^24)";
+  *tol = (int64_t)q;
+  if (p->max_tilt_rad < 0.f || p->max_tilt_rad > 1.5f) return "max_tilt_rad must lie in [0, 1.5]";
+  if (!(p->height_min_m > 0.f) || p->height_max_m < p->height_min_m) return "0 < height_min_m <= height_max_m is required";
+  return nullptr;
+}
+}  // namespace
+
+int sn_ground_gate(const sn_camera* cam, const sn_ground_params* p, int W, int H, int64_t gate[6]) {
+  int64_t tol;
+  GrRoi roi;
+  if (!gate || W < 1 || H < 1 || W > 8192 || H > 8192 || ground_params_check(cam, p, &tol) || gr_roi(p, W, H, cam->step, &roi))
+    return SN_ERR_ARG;
+  gr_gate(cam, p, roi, kOutScale, gate);
+  return SN_OK;
+}
+
+int sn_ground_from_raw(sn_handle* h, int n, const int32_t* raw, const sn_camera* cam, const sn_ground_params* p, sn_ground* ground,
+                       uint8_t* labels, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_ground_from_raw: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!raw || !cam) return refuse("a NULL pointer");
+  if (n <= 0 || n > h->max_batch) return refuse("n outside 1..max_batch");
+  GrArgs a{};
+  if (const char* why = ground_params_check(cam, p, &a.tol)) return refuse(why);
+  const int W = h->W, H = h->H;
+  if (W > 8192 || H > 8192) return refuse("maps beyond 8192 x 8192");
+  if (const char* why = gr_roi(p, W, H, cam->step, &a.roi)) return refuse(why);
+  if (!ground && !labels) return refuse("one of ground and labels is needed");
+  if ((uintptr_t)ground & 7) return refuse("ground must be 8-byte aligned");
+  const size_t HW = (size_t)H * W, raw_bytes = n * HW * 4, ground_bytes = (size_t)n * sizeof(sn_ground), label_bytes = n * HW;
+  if (overlap({{raw, raw_bytes}}, {{ground, ground_bytes}, {labels, label_bytes}}) || overlap({{ground, ground_bytes}}, {{labels, label_bytes}}))
+    return refuse("overlapping buffers");
+  using G = sn_handle::Ground;
+  G& lane = h->gnd;
+  Bracket b(h, "sn_ground_from_raw", mem, stream, lane);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  const int K = p->hypotheses;
+  a.acc_words = 1 + 9 * (p->refits + 1);
+  a.raw = s.in_pinned(G::kPinRaw, G::kRaw, raw, raw_bytes);
+  a.out = s.out(G::kGround, ground, ground_bytes, true);      // the label pass reads the records
+  a.labels = s.out(G::kLabels, labels, label_bytes);
+  a.hyp = s.scratch<GrHyp>(G::kHyp, (size_t)n * K * sizeof(GrHyp));
+  a.counts = s.scratch<uint32_t>(G::kCounts, (size_t)n * K * 4);
+  a.acc = s.scratch<unsigned long long>(G::kAcc, (size_t)n * a.acc_words * 8);
+  a.state = s.scratch<GrState>(G::kState, (size_t)n * sizeof(GrState));
+  if (s.rc) return s.rc;
+  a.W = W, a.H = H, a.step = cam->step, a.n = n;
+  a.K = K, a.min_area = p->min_area, a.min_inliers = p->min_inliers, a.refits = p->refits, a.seed = p->seed;
+  gr_gate(cam, p, a.roi, kOutScale, a.gate);
+  gr_prior(p, a.m);
+  a.fx = cam->fx, a.fy = cam->fy, a.cx = cam->cx, a.cy = cam->cy, a.baseline_mm = cam->baseline_mm, a.S = gr_scale(kOutScale);
+  {
+    const GrFillArgs f{a.counts, a.acc, (size_t)n * K, (size_t)n * a.acc_words};
+    hipLaunchKernelGGL(k_gr_fill, dim3((unsigned)std::min<size_t>((f.n_counts + f.n_acc + 255) / 256, 2048)), dim3(256), 0, st, f);
+  }
+  a.rows = gr_rows(a.roi, K, n);
+  const int tiles_x = (a.roi.Ws + 255) / 256;
+  const dim3 tiles(tiles_x * ((a.roi.Hs + a.rows - 1) / a.rows), n), tiles8(tiles_x * ((a.roi.Hs + kGrRows - 1) / kGrRows), n), per_map((n + 63) / 64);
+  hipLaunchKernelGGL(k_gr_hyp, dim3((K + 255) / 256, n), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_gr_score, tiles, dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_gr_select, dim3(n), dim3(256), 0, st, a);
+  for (int round = 0; round <= p->refits; ++round) {
+    hipLaunchKernelGGL(k_gr_moments, tiles8, dim3(256), 0, st, a, round);
+    if (round < p->refits) hipLaunchKernelGGL(k_gr_solve, per_map, dim3(64), 0, st, a, round);
+  }
+  hipLaunchKernelGGL(k_gr_finish, per_map, dim3(64), 0, st, a);
+  if (a.labels) {
+    const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((HW / 4 + 255) / 256, 2048 / n + 1)), n);
+    if (!((uintptr_t)a.raw & 15) && !((uintptr_t)a.labels & 3) && HW % 4 == 0) hipLaunchKernelGGL(k_gr_labels<true>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_gr_labels<false>, grid, dim3(256), 0, st, a);
   }
   HIP_TRY(h, hipGetLastError());
   return b.close();

@@ -8,7 +8,7 @@ D1) needed to score the output against dataset ground truth.
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
         [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]] \
-        [--obstacles PARAMS_FILE]
+        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -69,6 +69,12 @@ measurement (raw == 0, what the masks above leave) black.  Every record gains "r
 occupancy grid seen from above with forward up (0 occupied, 128 unknown, 255 free), and <i>.scan.txt, one `angle range` line per
 beam of the laser scan, are written into --out; the summary gains per pair "occupied" and "free" (cells) and "nearest_m" (the
 smallest range, null without a return).
+
+--ground PARAMS_FILE (ground.save_params' `key value` lines) fits the ground plane of the FINAL map on the GPU
+(`sn_ground_from_raw`), camera as above: <i>.ground.txt (the record: flags, counts, the plane, the mount, pitch and roll) and
+<i>.ground.pgm (the labels: no measurement 0, no plane 48, above 96, below 160, ground 255) are written into --out; the summary gains
+per pair "ground_found", "height_m", "pitch_deg", "roll_deg" and "inliers".  With --obstacles the grid and the scan use the mount
+the fit hands back (the file's own prior where no plane was found) instead of the obstacle file's base_from_cam.
 """
 import argparse
 import json
@@ -144,7 +150,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None, view=None, obstacle=None) -> List[dict]:
+                jpeg=None, view=None, obstacle=None, ground=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -172,7 +178,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     stream of engine.render_jpeg, or the RGB8 canvas of engine.render, of the final map under the left eye) and "render_bytes",
     and <i>.render.jpg / <i>.render.ppm is written.
     obstacle = an obstacles.ObstacleParams: the record gains "occ", "ranges" and "obstacle_stats" (engine.obstacles of the final
-    map, `camera` as for the cloud), "occupied", "free" and "nearest_m"; <i>.grid.pgm and <i>.scan.txt are written."""
+    map, `camera` as for the cloud), "occupied", "free" and "nearest_m"; <i>.grid.pgm and <i>.scan.txt are written.
+    ground = a ground.GroundParams: the record gains "ground" (the record of engine.ground of the final map) and "ground_labels",
+    "ground_found", "height_m", "pitch_deg", "roll_deg" and "inliers"; <i>.ground.txt and <i>.ground.pgm are written, and the
+    obstacle stage takes the record's mount."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -188,7 +197,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
         if rectify is not None:
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
-        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle)
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground)
     finally:
         if rect is not None:
             rect.close()
@@ -198,7 +207,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
 
 
 def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None,
-          obstacle=None):
+          obstacle=None, ground=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -259,8 +268,17 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             else:
                 rec["render"] = engine.render(raw, sbs, 2 * w, view[1])
                 rec["render_bytes"] = int(rec["render"].size)
+        mounts = None
+        if ground is not None:        # the final map
+            import math
+            from . import ground as gnd
+            grec, glab = engine.ground(raw, camera, ground)
+            pitch, roll = gnd.angles(grec["base_from_cam"])
+            rec.update(ground=grec, ground_labels=glab, ground_found=bool(grec["flags"] & gnd.FOUND), height_m=float(grec["plane_cam"][3]),
+                       pitch_deg=math.degrees(pitch), roll_deg=math.degrees(roll), inliers=int(grec["inliers"]))
+            mounts = grec["base_from_cam"].reshape(1, 12)
         if obstacle is not None:      # the final map
-            occ, _, _, ranges, stats = engine.obstacles(raw, camera, obstacle)
+            occ, _, _, ranges, stats = engine.obstacles(raw, camera, obstacle, mounts=mounts)
             near = float(ranges.min()) if ranges.size else float("inf")
             rec.update(occ=occ, ranges=ranges, obstacle_stats=stats, occupied=int(stats[2]), free=int(stats[3]),
                        nearest_m=near if np.isfinite(near) else None)
@@ -302,6 +320,11 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
                     f.write(rec["render"])
             elif view is not None:
                 images.write_ppm(os.path.join(out_dir, f"{i}.render.ppm"), rec["render"])
+            if ground is not None:
+                from . import ground as gnd
+                from . import obstacles as obs
+                gnd.write_record(os.path.join(out_dir, f"{i}.ground.txt"), rec["ground"])
+                obs.write_pgm(os.path.join(out_dir, f"{i}.ground.pgm"), gnd.labels_image(rec["ground_labels"]))
             if obstacle is not None:
                 from . import obstacles as obs
                 if obstacle.gw:
@@ -364,6 +387,10 @@ def main(argv=None) -> int:
     ap.add_argument("--obstacles", default=None, metavar="PARAMS_FILE",
                     help="write <i>.grid.pgm and <i>.scan.txt: the obstacle grid and the laser scan of the final map, made on the GPU "
                          "with --camera or the rectifier's camera; needs --out")
+    ap.add_argument("--ground", default=None, metavar="PARAMS_FILE",
+                    help="write <i>.ground.txt and <i>.ground.pgm: the ground plane of the final map, the mount it implies and the "
+                         "per-pixel labels, made on the GPU with --camera or the rectifier's camera; --obstacles then uses that mount; "
+                         "needs --out")
     ap.add_argument("--render-true-colours", action="store_true", help="--render: the colour map's own colours, not the reference's R/B swap")
     ap.add_argument("--render-invalid-black", action="store_true", help="--render: pixels without a measurement (raw == 0) are black")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
@@ -481,13 +508,23 @@ def main(argv=None) -> int:
                 raise ValueError(why)
         except (OSError, ValueError) as e:
             ap.error(f"--obstacles {args.obstacles}: {e}")
+    gparams = None
+    if args.ground is not None:
+        from . import ground as gnd
+        try:
+            gparams = gnd.load_params(args.ground)
+            why = gnd.check(gparams) or (None if args.out else "needs --out")
+            if why:
+                raise ValueError(why)
+        except (OSError, ValueError) as e:
+            ap.error(f"--ground {args.ground}: {e}")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg, view=rnd, obstacle=obstacle)
+                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -500,6 +537,9 @@ def main(argv=None) -> int:
         summary["render_bytes"] = int(sum(r["render_bytes"] for r in recs))
     if obstacle is not None and recs:
         for k in ("occupied", "free", "nearest_m"):
+            summary[k] = [r[k] for r in recs]
+    if gparams is not None and recs:
+        for k in ("ground_found", "height_m", "pitch_deg", "roll_deg", "inliers"):
             summary[k] = [r[k] for r in recs]
     if args.gt and recs:
         for k in ("epe", "bad1", "bad3", "d1"):

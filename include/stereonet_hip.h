@@ -948,6 +948,123 @@ int sn_obstacles_from_raw(sn_handle *h, int n, const int32_t *raw, const sn_came
                           int8_t *occ, uint32_t *hits, int32_t *height_mm, float *ranges, uint32_t *stats,
                           int mem, void *stream);
 
+/* sn_obstacles_from_raw with one mount per map: map k's base_from_cam is the twelve floats at mounts + k * mount_stride
+ * (mount_stride >= 12, in floats; host or device memory per `mem`, like every other buffer of the call), used as they are (no
+ * all-zero rule), and p->base_from_cam is ignored (it need not be finite).  With &ground[0].base_from_cam[0] and
+ * sizeof(sn_ground) / 4 the mounts of sn_ground_from_raw are read where that call left them: on one stream, fit -> grid needs no
+ * host round trip.  Everything else, the arithmetic included, is sn_obstacles_from_raw's; a mount that is not finite classifies
+ * nothing (NaN counts nowhere).  SN_ERR_ARG also for mounts NULL or misaligned (4 bytes), mount_stride < 12, and mounts that
+ * overlap an output. */
+int sn_obstacles_from_raw_mounts(sn_handle *h, int n, const int32_t *raw, const sn_camera *cam, const sn_obstacle_params *p,
+                                 const float *mounts, int mount_stride, int8_t *occ, uint32_t *hits, int32_t *height_mm,
+                                 float *ranges, uint32_t *stats, int mem, void *stream);
+
+/* ---- the ground plane of the int32 map, and the mount it implies (csrc/sn_ground.hpp; hobot_stereonet_amd/ground.py is the
+ * numpy twin, byte for byte) --------------------------------------------------------------------------------------------------
+ * sn_obstacles_from_raw classifies by height in a base frame that the caller measured once.  This stage measures it per frame
+ * from what nearly every map shows: the floor.  For a rectified pinhole pair a plane in space is a plane in (u, v, raw),
+ * raw = a*u + b*v + c, so every decision below is taken on integers and the outputs do not depend on the order of arrival.
+ *
+ * Samples.  The region of interest is roi_x, roi_y, roi_w, roi_h in pixels (all four 0: the lower half at full width, y = H/2,
+ *   h = H - H/2).  Its samples are the pixels (u, v) = (j*step, i*step), step = cam->step, with roi_x <= u < roi_x + roi_w and
+ *   roi_y <= v < roi_y + roi_h: Ws columns from j0 = ceil(roi_x/step), Hs rows from i0 = ceil(roi_y/step), Ns = Ws*Hs, sample
+ *   index s = si*Ws + sj.  (u0, v0) = (roi_x + roi_w/2, roi_y + roi_h/2) (integer division) is the centre the plane's c refers
+ *   to.  A sample is usable when 0 < r <= 2^24 (8 388 px of disparity).  cam's z_min_m / z_max_m are not used.
+ *   Bounds, W, H <= 8192: |du|, |dv| <= 8191 < 2^13 and |dr| < 2^24, so |C| <= 2 * 2^26 = 2^27 and r <= 2^24 fit in 32 bits,
+ *   |A|, |B| <= 2^38, |D| and every residual A*u + B*v + C*r - D stay below 2^54, tol_raw*C <= 2^51; in Q16, |aq|, |bq| <= 2^34
+ *   and |cq| <= 2^41 (enforced), so aq*du + bq*dv + cq < 2^49 and r*65536 <= 2^40; the moments are taken of du = u - u0,
+ *   dv = v - v0 (|du|, |dv| <= 4097) over Ns <= 2^26 samples, the largest, sum du*r, below 2^26 * 4097 * 2^24 < 2^63.
+ * Hypotheses.  K = hypotheses, 1..1024.  mix(seed, i): x = seed + i*0x9E3779B9; x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15;
+ *   x *= 0x846CA68B; x ^= x >> 16 (all uint32).  Hypothesis i takes the samples s_j = mix(seed, 3*i + j) % Ns, j = 0, 1, 2, the
+ *   same for every map of the call.  With d1 = P1 - P0, d2 = P2 - P0 in (u, v, r): A = d1v*d2r - d1r*d2v, B = d1r*d2u - d1u*d2r,
+ *   C = d1u*d2v - d1v*d2u; all three negated when C < 0; D = A*u_0 + B*v_0 + C*r_0.  The hypothesis is dead when a sample is not
+ *   usable, when C < max(min_area, 1), or when it lies outside the gate:
+ *     gate[0]*C <= -A*65536 <= gate[1]*C,  gate[2]*C <= -B*65536 <= gate[3]*C,
+ *     gate[4]*C <= (D - A*u0 - B*v0)*65536 <= gate[5]*C     (this last pair needs 70 bits: 128-bit integers)
+ * Gate.  sn_ground_gate (pure host, no device) turns the prior mount m = base_from_cam (all twelve zero: the level forward
+ *   mount), max_tilt_rad and the two heights into Q16 bounds on a = -A/C, b = -B/C and c, the plane's value at (u0, v0).  In
+ *   double, S = (double)(float)((double)out_scale * 192.0), Bm = (double)baseline_mm / 1000.0, x0 = (m0, m1, m2),
+ *   y0 = (m4, m5, m6), n0 = -(m8, m9, m10); for alpha and beta in {0, -max_tilt_rad, +max_tilt_rad} (alpha outer) and
+ *   h in {height_min_m, height_max_m} (innermost):
+ *     n = cos(beta)*(cos(alpha)*n0 + sin(alpha)*y0) + sin(beta)*x0,  g = Bm / (h*S),
+ *     a = g*n_x,  b = g*n_y*fx/fy,  cp = g*n_z*fx,  c = (cp + a*(u0 - cx)) + b*(v0 - cy)
+ *   gate[0], gate[1] = floor(min a*65536), ceil(max a*65536) over the eighteen planes, gate[2..3] likewise from b, gate[4..5]
+ *   from c; the first four clamped to +-2^34, the last two to +-2^41.  A wall is often the largest plane in view: for a level
+ *   prior the gate keeps b well above 0, which a fronto-parallel wall (a = b = 0) is not.  The device never calls a
+ *   transcendental function; a twin is fed the library's gate, as it is fed the library's beam table.
+ * Score.  tol_raw = (int64)floorf(tol_px / S) with S = (float)((double)out_scale * 192.0), sn_temporal's rule; it must not
+ *   exceed 2^24.  A usable sample is an inlier of a live hypothesis when |A*u + B*v + C*r - D| <= tol_raw*C.  The winner is the
+ *   live hypothesis with the highest count, ties to the lowest index.  Its plane in Q16, q(x) = (int64)floor(x*65536 + 0.5) with
+ *   x a correctly rounded double quotient: aq = q(-A / C), bq = q(-B / C), cq = q((D - A*u0 - B*v0) / C).
+ * Refit, `refits` (0..4) times.  A usable sample is an inlier of a Q16 plane when
+ *     |r*65536 - (aq*(u - u0) + bq*(v - v0) + cq)| <= tol_raw*65536.
+ *   Over the inliers, with du = u - u0, dv = v - v0, nine int64 moments: N, Su, Sv, Sr, Suu, Suv, Svv, Sur, Svr.  Each is
+ *   converted to double (round to nearest), then, in double, every operation rounded, no FMA:
+ *     mu = Su/N, mv = Sv/N, mr = Sr/N,
+ *     suu = Suu - Su*mu, suv = Suv - Su*mv, svv = Svv - Sv*mv, sur = Sur - Su*mr, svr = Svr - Sv*mr,
+ *     det = suu*svv - suv*suv,  a = (sur*svv - svr*suv)/det,  b = (svr*suu - sur*suv)/det,  c = (mr - a*mu) - b*mv
+ *   and (aq, bq, cq) = (q(a), q(b), q(c)).  The system is singular when N < 3, when det > 0 does not hold, or when |a*65536| or
+ *   |b*65536| exceeds 2^34 or |c*65536| exceeds 2^41 (NaN included): the previous plane stays, no further refit is made, and
+ *   SN_GROUND_SINGULAR is set (a note, not a failure).  `inliers` is the count under the final plane.
+ * Result.  SN_GROUND_NO_HYPOTHESIS: no hypothesis is live (winner = -1, plane_q16 = 0, inliers = 0).  Else
+ *   SN_GROUND_FEW_INLIERS: inliers < min_inliers.  Else SN_GROUND_GATED: the final plane is outside the gate (the six bounds
+ *   on aq, bq, cq as integers) or the geometry below fails.  Else SN_GROUND_FOUND.  Without SN_GROUND_FOUND, plane_cam is
+ *   (-m8, -m9, -m10, m11) and base_from_cam the prior mount (the level mount written out where the prior is all zero), so what
+ *   follows stays defined.
+ * Geometry, in double, every operation rounded, no FMA, only + - * / and sqrt; then rounded to float:
+ *     a = aq/65536, b = bq/65536, c = cq/65536,  cp = (c + a*(cx - u0)) + b*(cy - v0),
+ *     w = (a, (b*fy)/fx, cp/fx),  len = sqrt((w0*w0 + w1*w1) + w2*w2)   (0 or not finite: gated),
+ *     height = (baseline_mm/1000) / (S*len),  the downward normal n = w/len,  plane_cam = (n, height)
+ *   The mount keeps the prior's heading and horizontal offset and replaces tilt and height: z = -n,
+ *   d = (x0_0*z_0 + x0_1*z_1) + x0_2*z_2, x' = x0 - d*z, |x'| = sqrt((x'_0^2 + x'_1^2) + x'_2^2) (below 1e-3: gated),
+ *   x = x'/|x'|, y = z cross x = (z1*x2 - z2*x1, z2*x0 - z0*x2, z0*x1 - z1*x0), base_from_cam = rows (x, m3), (y, m7),
+ *   (z, height).  A level camera 0.5 m above a level floor gives back the level mount with t_z = 0.5.
+ *   The integer outputs (flags, counts, plane_q16, labels) are exact on every input.  The float outputs are the same bits
+ *   as the twin's wherever double division and sqrt are correctly rounded on both sides, which they are on gfx950 and in numpy.
+ * Labels (nullable), uint8 [n][H][W], every pixel of the map, not only the region or the step grid: SN_GROUND_LABEL_NONE where
+ *   the pixel is not usable; else SN_GROUND_LABEL_NO_PLANE without SN_GROUND_FOUND; else, with
+ *   e = r*65536 - (aq*(u - u0) + bq*(v - v0) + cq): GROUND when |e| <= tol_raw*65536, ABOVE when e is larger (nearer than the
+ *   floor: something stands there), BELOW when smaller (a hole, a step down).
+ *
+ * ground (nullable) [n]; one of ground and labels is needed.  SN_ERR_ARG (sn_last_error(h) says why; nothing is launched or
+ * written): n outside 1..max_batch, raw / cam / p NULL, a camera sn_pointcloud_from_raw refuses or whose cx, cy are not finite,
+ * a float of p that is not finite, hypotheses outside 1..1024, refits outside 0..4, min_area or min_inliers negative, tol_px
+ * negative or tol_raw > 2^24, max_tilt_rad outside [0, 1.5], height_min_m <= 0 or height_max_m < height_min_m, a region that
+ * leaves the image or holds fewer than three samples, W or H above 8192, ground misaligned (8 bytes), overlapping buffers, a bad
+ * mem.  mem / stream / blocking and SN_ERR_NOMEM as sn_obstacles_from_raw: a lane of the handle's with a stream, an event and
+ * grow-only buffers of its own, freed by sn_destroy; may run beside sn_submit / sn_wait and beside the other stages.
+ * Not covered: the asynchronous sn_submit* slots, smoothing the plane over time, publishing the mount as a transform, more
+ * than one plane (a ramp ahead), uneven ground, yaw and the horizontal offset (which a plane cannot give). */
+enum { SN_GROUND_FOUND = 1, SN_GROUND_NO_HYPOTHESIS = 2, SN_GROUND_FEW_INLIERS = 4, SN_GROUND_GATED = 8, SN_GROUND_SINGULAR = 16 };
+enum { SN_GROUND_LABEL_NONE = 0, SN_GROUND_LABEL_GROUND = 1, SN_GROUND_LABEL_ABOVE = 2, SN_GROUND_LABEL_BELOW = 3,
+       SN_GROUND_LABEL_NO_PLANE = 4 };
+typedef struct sn_ground_params {
+  float base_from_cam[12];          /* the prior mount, as sn_obstacle_params' (all twelve zero: the level forward mount) */
+  int   roi_x, roi_y, roi_w, roi_h; /* pixels; all four 0: the lower half of the image at full width */
+  int   hypotheses;                 /* K, 1..1024 */
+  uint32_t seed;
+  int   min_area;                   /* a hypothesis needs C (twice its triangle's area, in pixels^2) >= max(min_area, 1) */
+  int   min_inliers;
+  int   refits;                     /* 0..4 */
+  float tol_px;                     /* inlier band, pixels of disparity */
+  float max_tilt_rad;               /* the gate: tilt about the prior's x and y axes */
+  float height_min_m, height_max_m; /* the gate: camera height above the plane */
+} sn_ground_params;
+typedef struct sn_ground {
+  uint32_t flags;                   /* SN_GROUND_* */
+  uint32_t usable;                  /* usable samples of the region */
+  uint32_t inliers;                 /* under the final plane */
+  int32_t  winner;                  /* index of the winning hypothesis, -1 without one */
+  uint32_t survivors;               /* live hypotheses */
+  uint32_t reserved;                /* 0 */
+  int64_t  plane_q16[3];            /* aq, bq, cq: raw*65536 = aq*(u - u0) + bq*(v - v0) + cq */
+  float    plane_cam[4];            /* the downward unit normal in the camera frame, and the height in metres */
+  float    base_from_cam[12];       /* the mount: sn_obstacles_from_raw_mounts reads it here */
+} sn_ground;
+int sn_ground_gate(const sn_camera *cam, const sn_ground_params *p, int W, int H, int64_t gate[6]);      /* pure host, no device */
+int sn_ground_from_raw(sn_handle *h, int n, const int32_t *raw, const sn_camera *cam, const sn_ground_params *p,
+                       sn_ground *ground, uint8_t *labels, int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
