@@ -267,6 +267,13 @@ def load_library(path: Optional[str] = None):
     lib.sn_dbg_ref_block_f16x3.argtypes = [vp, fp, ip, ip, fp, fp, fp, fp, ip, ip, fp]
     lib.sn_dbg_ref_tail_f16.argtypes = [vp, ip, fp, ip, ip, fp, fp, fp, fp, fp, C.c_float, fp, ip, C.c_float, ip, ip, ip, fp, i32p]
     lib.sn_dbg_read.argtypes = [vp, C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_size_t)]
+    u64p = C.POINTER(C.c_uint64)
+    lib.sn_dbg_cost_volume.argtypes = [vp, fp, ip, ip, ip, ip, ip, fp]
+    lib.sn_dbg_agg_first_f32.argtypes = [vp, fp, ip, ip, ip, ip, fp, fp, fp]
+    lib.sn_dbg_softargmin.argtypes = [vp, ip, ip, ip, ip, ip, ip, C.c_float, fp, fp, fp, fp, fp, u64p]
+    lib.sn_dbg_agg_tail.argtypes = [vp, fp, ip, ip, ip, ip, fp, fp, fp, C.c_float, ip, ip, fp, fp, fp, u64p, fp]
+    lib.sn_dbg_head.argtypes = [vp, ip, fp, ip, ip, fp, C.c_float, fp, ip, C.c_float, ip, ip, ip, fp, i32p, C.POINTER(C.c_double), u64p]
+    lib.sn_dbg_img_pool2.argtypes = [vp, i8p, ip, ip, ip, ip, fp]
     lib.sn_dbg_copy_limited.argtypes = [vp, vp, C.c_size_t, ip, vp]
     lib.sn_depth_from_raw.argtypes = [vp, ip, i32p, C.c_float, C.c_float, fp, fp, ip, vp]
     lib.sn_pointcloud_from_raw.argtypes = [vp, ip, i32p, u8p, ip, C.POINTER(SnCamera), ip, fp, vp, ip, vp]
@@ -314,7 +321,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -1186,6 +1193,94 @@ class StereoNetHIP:
                                                   a[6].ctypes.data, ups, float(dnorm), h_out, w_out, form, disp.ctypes.data,
                                                   raw.ctypes.data), "sn_dbg_ref_tail_f16")
         return disp, raw
+
+    # mid-stage hooks: every output sits between guard bands and starts as the 0xff pattern (include/stereonet_hip.h)
+    def dbg_cost_volume(self, feat, dl, form):
+        """feat float32 (2n, 32, hl, wl), left / right interleaved -> cost volume (n, dl, 32, hl, wl) read back from split slots;
+        form 0 = k_cost_slots, 1 = k_cost_slots_pad (zero-bordered volume; the hook checks the borders)"""
+        f = np.ascontiguousarray(feat, np.float32)
+        n2, c, hl, wl = f.shape
+        assert c == 32 and n2 % 2 == 0
+        out = np.empty((n2 // 2, dl, 32, hl, wl), np.float32)
+        self._check(self._lib.sn_dbg_cost_volume(self._h, f.ctypes.data, n2 // 2, dl, hl, wl, form, out.ctypes.data),
+                    "sn_dbg_cost_volume")
+        return out
+
+    def dbg_agg_first_f32(self, feat, dl, wt, bias):
+        """the fp32 first aggregation layer with the cost-volume loader -> (n, 32, dl, hl, wl)"""
+        f, wt, bias = (np.ascontiguousarray(a, np.float32) for a in (feat, wt, bias))
+        n2, c, hl, wl = f.shape
+        assert c == 32 and n2 % 2 == 0 and wt.size == 32 * 32 * 27 and bias.size == 32
+        out = np.empty((n2 // 2, dl, 32, hl, wl), np.float32)
+        self._check(self._lib.sn_dbg_agg_first_f32(self._h, f.ctypes.data, n2 // 2, dl, hl, wl, wt.ctypes.data, bias.ctypes.data,
+                                                   out.ctypes.data), "sn_dbg_agg_first_f32")
+        return np.ascontiguousarray(out.transpose(0, 2, 1, 3, 4))
+
+    def dbg_softargmin(self, v, bias, w=None, want_conf=False):
+        """w given: k_head_softargmin on the volume v (n, dl, 32, hl, wl) with w (32, 27); w None: k_softargmin_p on the partial
+        sums v (n, dl, 27, hl, wl).  -> dict cost (n, dl, hl, wl), disp_low, conf_low (n, hl, wl; the 0xff pattern = NaN
+        without want_conf), nonfinite"""
+        v = np.ascontiguousarray(v, np.float32)
+        n, dl, c, hl, wl = v.shape
+        assert c == (27 if w is None else 32)
+        wa = None if w is None else np.ascontiguousarray(w, np.float32).reshape(32, 27)
+        cost = np.empty((n, dl, hl, wl), np.float32)
+        disp = np.empty((n, hl, wl), np.float32)
+        conf = np.empty((n, hl, wl), np.float32)
+        nf = C.c_uint64()
+        self._check(self._lib.sn_dbg_softargmin(self._h, n, dl, hl, wl, 1 if w is None else 0, int(want_conf), float(bias),
+                                                v.ctypes.data, _np_ptr(wa), cost.ctypes.data, disp.ctypes.data, conf.ctypes.data,
+                                                C.byref(nf)), "sn_dbg_softargmin")
+        return {"cost": cost, "disp_low": disp, "conf_low": conf, "nonfinite": int(nf.value)}
+
+    def dbg_agg_tail(self, vol, wt, bias, out_w, out_b, form, want_conf=False):
+        """Last aggregation layer (fp32 output) + soft-argmin on vol (n, 32, dl, hl, wl); form 0 = plain slots (k_conv_x3s +
+        k_head_softargmin), 1 = zero-bordered (k_agg_x3s_dma + k_head_softargmin), 2 = partial sums P (k_agg_x3s_dma HEADP +
+        k_softargmin_p).  -> dict as dbg_softargmin plus layer_vol (n, 32, dl, hl, wl) for forms 0 and 1"""
+        vol, wt, bias, ow = (np.ascontiguousarray(a, np.float32) for a in (vol, wt, bias, out_w))
+        n, c, dl, hl, wl = vol.shape
+        assert c == 32 and wt.size == 32 * 32 * 27 and bias.size == 32 and ow.size == 32 * 27
+        cost = np.empty((n, dl, hl, wl), np.float32)
+        disp = np.empty((n, hl, wl), np.float32)
+        conf = np.empty((n, hl, wl), np.float32)
+        lv = np.empty((n, dl, 32, hl, wl), np.float32) if form != 2 else None
+        nf = C.c_uint64()
+        self._check(self._lib.sn_dbg_agg_tail(self._h, vol.ctypes.data, n, dl, hl, wl, wt.ctypes.data, bias.ctypes.data,
+                                              ow.ctypes.data, float(out_b), form, int(want_conf), cost.ctypes.data,
+                                              disp.ctypes.data, conf.ctypes.data, C.byref(nf), _np_ptr(lv)), "sn_dbg_agg_tail")
+        return {"cost": cost, "disp_low": disp, "conf_low": conf, "nonfinite": int(nf.value),
+                "layer_vol": None if lv is None else np.ascontiguousarray(lv.transpose(0, 2, 1, 3, 4))}
+
+    def dbg_head(self, x, head_w, head_b, low, ups, dnorm, h_out, w_out, form):
+        """The refinement head alone on x float32 (n, 32, hk, wk), low (n, hk/ups, wk/ups); form 0 = k_head_final, 1 =
+        k_head_final_mfma32 (fp32 engine), 2 = k_head_final_f16<true> on the hi / lo tensor (fp16-mode engine).
+        -> dict disp float32, raw int32 (n, h_out, w_out), mean_abs_dr, nonfinite"""
+        x, hw, low = (np.ascontiguousarray(a, np.float32) for a in (x, head_w, low))
+        n, c, hk, wk = x.shape
+        assert c == 32 and hw.size == 32 * 9 and low.shape == (n, hk // ups, wk // ups)
+        disp = np.empty((n, h_out, w_out), np.float32)
+        raw = np.empty((n, h_out, w_out), np.int32)
+        mean, nf = C.c_double(), C.c_uint64()
+        self._check(self._lib.sn_dbg_head(self._h, n, x.ctypes.data, hk, wk, hw.ctypes.data, float(head_b), low.ctypes.data, ups,
+                                          float(dnorm), h_out, w_out, form, disp.ctypes.data, raw.ctypes.data, C.byref(mean),
+                                          C.byref(nf)), "sn_dbg_head")
+        return {"disp": disp, "raw": raw, "mean_abs_dr": float(mean.value), "nonfinite": int(nf.value)}
+
+    def dbg_img_pool2(self, in6, levels):
+        """in6 int8 (n, 6, h, w) -> [level 1, ..., level levels-1], level k float32 (n, 3, hp >> k, wp >> k): the image pyramid of
+        the hierarchical refinement through both k_img_pool2 instantiations, chained as the forward pass chains them"""
+        a = np.ascontiguousarray(in6, np.int8)
+        n, c, h, w = a.shape
+        assert c == 6 and 2 <= levels <= 4
+        hp, wp = (h + 15) // 16 * 16, (w + 15) // 16 * 16
+        shapes = [(n, 3, hp >> k, wp >> k) for k in range(1, levels)]
+        flat = np.empty(sum(int(np.prod(s)) for s in shapes), np.float32)
+        self._check(self._lib.sn_dbg_img_pool2(self._h, a.ctypes.data, n, h, w, levels, flat.ctypes.data), "sn_dbg_img_pool2")
+        out, at = [], 0
+        for s in shapes:
+            out.append(flat[at:at + int(np.prod(s))].reshape(s).copy())
+            at += int(np.prod(s))
+        return out
 
     def stream_priority_high(self) -> bool:
         """True when the engine's pipeline streams were created with the device's highest priority (SN_STREAM_PRIORITY=1,

@@ -1,6 +1,7 @@
 // sn_dbg_hooks.hpp — the sn_dbg_* entry points (parity hooks: one kernel or block on caller-supplied tensors, as the
 // pipeline launches it) and the host-side marshalling they share: split-slot tensors, their zero-bordered grids
-// (PaddedSlots) and the fp16 tower layout (RefHost).  Part of the single translation unit stereonet_hip.hip.
+// (PaddedSlots), the fp16 tower layout (RefHost) and the guarded outputs of the mid-stage hooks (Guarded, HookStat).  Part of
+// the single translation unit stereonet_hip.hip.
 #pragma once
 
 namespace {
@@ -41,15 +42,19 @@ hipError_t from_dev(V& v, const void* dev) {
 
 // Host image of split-slot (block, part) planes inside a zero-bordered grid (FeatPad, SlotGeom, VolPad): `nplanes` planes
 // of g.PH x g.PW slots with the H x W image at (g.py, g.px), and `lead` all-zero planes in front of and behind them
-// (VolPad: one disparity plane = 8).  The plain counterpart is [nplanes][H][W] slots (host_to_slots).
+// (VolPad: one disparity plane = 8).  group > 0: the planes come in groups of `group` (VolPad: the 8 Dl planes of one pair)
+// with `lead` zero planes in front of the first group and behind EVERY group, so two neighbours share one run of zero
+// planes.  The plain counterpart is [nplanes][H][W] slots (host_to_slots).
 struct PaddedSlots {
   SlotGeom g;
   int H, W;
-  size_t nplanes, lead;
+  size_t nplanes, lead, group;
   std::vector<_Float16> v;
-  PaddedSlots(const SlotGeom& g_, int H_, int W_, size_t nplanes_, size_t lead_ = 0)
-      : g(g_), H(H_), W(W_), nplanes(nplanes_), lead(lead_), v((nplanes_ + 2 * lead_) * g_.PH * g_.PW * 8, (_Float16)0.f) {}
-  size_t row(size_t plane, int y) const { return (((plane + lead) * g.PH + y + g.py) * g.PW + g.px) * 8; }
+  PaddedSlots(const SlotGeom& g_, int H_, int W_, size_t nplanes_, size_t lead_ = 0, size_t group_ = 0)
+      : g(g_), H(H_), W(W_), nplanes(nplanes_), lead(lead_), group(group_ ? group_ : (nplanes_ ? nplanes_ : 1)),
+        v((lead_ + (nplanes_ + group - 1) / group * (group + lead_)) * g_.PH * g_.PW * 8, (_Float16)0.f) {}
+  size_t padded_plane(size_t plane) const { return lead + plane / group * (group + lead) + plane % group; }
+  size_t row(size_t plane, int y) const { return ((padded_plane(plane) * g.PH + y + g.py) * g.PW + g.px) * 8; }
   void put(const std::vector<_Float16>& plain) {
     for (size_t p = 0; p < nplanes; ++p)
       for (int y = 0; y < H; ++y) memcpy(&v[row(p, y)], &plain[((p * H + y) * W) * 8], (size_t)W * 16);
@@ -62,8 +67,8 @@ struct PaddedSlots {
     const size_t phw = (size_t)g.PH * g.PW;
     for (size_t i = 0; i < v.size(); ++i) {
       const size_t sl = i / 8, p = sl / phw, y = (sl % phw) / g.PW, x = sl % g.PW;
-      const bool inside = p >= lead && p < lead + nplanes && y >= (size_t)g.py && y < (size_t)H + g.py && x >= (size_t)g.px &&
-                          x < (size_t)W + g.px;
+      const bool inside = p >= lead && (p - lead) % (group + lead) < group && y >= (size_t)g.py && y < (size_t)H + g.py &&
+                          x >= (size_t)g.px && x < (size_t)W + g.px;
       if (!inside && (float)v[i] != 0.f) return false;
     }
     return true;
@@ -124,6 +129,74 @@ hipError_t alloc_ref16(DevScope& ds, const RefGeom& g, size_t tensor_and_slack_s
   const hipError_t e = alloc_ref16(g, tensor_and_slack_slots, &raw, base);
   ds.track(raw);
   return e;
+}
+
+// A device output of a mid-stage hook between two guard bands of kGuardBytes known bytes (kGuardByte), owned by ds.  The
+// payload starts as the 0xff pattern (fp32 NaN, int32 -1, fp16 NaN): an element the kernel does not write shows.
+constexpr size_t kGuardBytes = 4096;
+constexpr int kGuardByte = 0xa5;
+template <class T>
+struct Guarded {
+  char* raw = nullptr;
+  size_t bytes = 0;
+  T* p() const { return reinterpret_cast<T*>(raw + kGuardBytes); }
+  hipError_t alloc(DevScope& ds, size_t count) {
+    bytes = (count * sizeof(T) + 15) / 16 * 16;
+    hipError_t e = ds.alloc(&raw, bytes + 2 * kGuardBytes);
+    if (e == hipSuccess) e = hipMemset(raw, kGuardByte, bytes + 2 * kGuardBytes);
+    if (e == hipSuccess) e = memset_now(raw + kGuardBytes, 0xff, bytes);
+    return e;
+  }
+  // *ok: both bands still hold kGuardByte
+  hipError_t intact(bool* ok) const {
+    std::vector<unsigned char> band(2 * kGuardBytes);
+    hipError_t e = hipMemcpy(band.data(), raw, kGuardBytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(band.data() + kGuardBytes, raw + kGuardBytes + bytes, kGuardBytes, hipMemcpyDeviceToHost);
+    *ok = e == hipSuccess;
+    for (unsigned char b : band) *ok = *ok && b == (unsigned char)kGuardByte;
+    return e;
+  }
+};
+#define SN_GUARD_CHECK(h, buf, what)                                                \
+  do {                                                                              \
+    bool ok_ = false;                                                               \
+    HIP_TRY(h, (buf).intact(&ok_));                                                 \
+    if (!ok_) {                                                                     \
+      set_err(h, std::string(what) + " wrote outside its output (guard band)");     \
+      return SN_ERR_DEVICE;                                                         \
+    }                                                                               \
+  } while (0)
+
+// One statistic word of a hook's own (the layout refine_stat_commit / lowres_nonfinite_commit write): zeroed, owned by ds
+struct HookStat {
+  unsigned long long* dev = nullptr;
+  hipError_t alloc(DevScope& ds) {
+    const hipError_t e = ds.alloc(&dev, (size_t)kStatWordStride);
+    return e != hipSuccess ? e : memset_now(dev, 0, kStatWordStride * sizeof(unsigned long long));
+  }
+  // the sum over the slots of the 64-bit word `at` of every line (0 = the |D r| sum, kStatNonfinite, kStatNonfiniteLow)
+  hipError_t read(int at, unsigned long long* out) const {
+    std::vector<unsigned long long> v(kStatWordStride);
+    const hipError_t e = from_dev(v, dev);
+    *out = 0;
+    for (int s = 0; s < kStatSlots; ++s) *out += v[(size_t)s * kStatLine + at];
+    return e;
+  }
+};
+
+// caller volume [n][32][Dl][hl][wl] (PyTorch) -> device order [n Dl][32][hl][wl]
+void vol_to_device_order(const float* in, int n, int Dl, size_t plane, std::vector<float>& out) {
+  out.resize((size_t)n * Dl * kC * plane);
+  for (int i = 0; i < n; ++i)
+    for (int ci = 0; ci < kC; ++ci)
+      for (int z = 0; z < Dl; ++z)
+        memcpy(&out[(((size_t)i * Dl + z) * kC + ci) * plane], &in[(((size_t)i * kC + ci) * Dl + z) * plane], plane * 4);
+}
+
+// the padded volume image (VolPad) of n pairs of Dl planes: 8 (block, part) planes per disparity plane, one zero disparity
+// plane in front of every pair's planes and one behind the last
+PaddedSlots vol_padded(const VolPad& g, int n) {
+  return PaddedSlots(SlotGeom{g.PH, g.PW, 1, 1}, g.H, g.W, (size_t)n * g.Dl * 8, 8, (size_t)g.Dl * 8);
 }
 
 }  // namespace
@@ -604,6 +677,272 @@ int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, co
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   HIP_TRY(h, hipMemcpy(out_disp, dd, nout * 4, hipMemcpyDeviceToHost));
   HIP_TRY(h, hipMemcpy(out_raw, dr, nout * 4, hipMemcpyDeviceToHost));
+  return SN_OK;
+}
+
+// ---- mid-stage hooks: cost volume, aggregation tail, soft-argmin, refinement heads, image pyramid -------------------
+// Each runs the kernel through the launch code of the forward pass on caller tensors; every device output sits between
+// guard bands (Guarded) and starts as the 0xff pattern, padded layouts are checked with PaddedSlots::outside_is_zero.
+int sn_dbg_cost_volume(sn_handle* h, const float* feat, int n, int Dl, int hl, int wl, int form, float* out) {
+  DevScope ds;
+  if (!h || !feat || !out || n <= 0 || Dl <= 0 || hl <= 0 || wl <= 0 || (form != 0 && form != 1)) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const size_t plane = (size_t)hl * wl, nfeat = (size_t)2 * n * kC * plane;
+  float* dfeat = nullptr;
+  HIP_TRY(h, ds.alloc(&dfeat, nfeat));
+  HIP_TRY(h, hipMemcpy(dfeat, feat, nfeat * 4, hipMemcpyHostToDevice));
+  std::vector<_Float16> hs((size_t)n * Dl * 8 * plane * 8);
+  Guarded<uint4> dvol;
+  if (form == 0) {
+    HIP_TRY(h, dvol.alloc(ds, hs.size() / 8));
+    HIP_TRY(h, launch_cost_slots(h->stream, dfeat, dvol.p(), Dl, hl, wl, n));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, from_dev(hs, dvol.p()));
+  } else {
+    const VolPad g = vol_pad(Dl, hl, wl);
+    PaddedSlots pv = vol_padded(g, n);
+    memset(hs.data(), 0xff, hs.size() * 2);
+    pv.put(hs);                                  // 0xff inside the images, zeros everywhere else
+    HIP_TRY(h, dvol.alloc(ds, pv.v.size() / 8));
+    HIP_TRY(h, to_dev(dvol.p(), pv.v));
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, launch_cost_slots_pad(h->stream, dfeat, dvol.p(), g, n));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, from_dev(pv.v, dvol.p()));
+    pv.get(hs);
+    if (!pv.outside_is_zero()) {
+      set_err(h, "k_cost_slots_pad wrote outside the image");
+      return SN_ERR_DEVICE;
+    }
+  }
+  SN_GUARD_CHECK(h, dvol, form == 0 ? "k_cost_slots" : "k_cost_slots_pad");
+  host_from_slots(hs, n * Dl, hl, wl, out);
+  return SN_OK;
+}
+
+int sn_dbg_agg_first_f32(sn_handle* h, const float* feat, int n, int Dl, int hl, int wl, const float* wt, const float* bias,
+                         float* out) {
+  DevScope ds;
+  if (!h || !feat || !wt || !bias || !out || n <= 0 || Dl <= 0 || hl <= 0 || wl <= 0) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  ConvLayer L;
+  rc = upload_conv3d(h, HostLayer{wt, bias, kC, kC, 27}, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  const size_t plane = (size_t)hl * wl, nfeat = (size_t)2 * n * kC * plane, nout = (size_t)n * Dl * kC * plane;
+  float* dfeat = nullptr;
+  Guarded<float> dout;
+  HIP_TRY(h, ds.alloc(&dfeat, nfeat));
+  HIP_TRY(h, dout.alloc(ds, nout));
+  HIP_TRY(h, hipMemcpy(dfeat, feat, nfeat * 4, hipMemcpyHostToDevice));
+  LoadCostVol ld{dfeat, Dl, hl, wl};
+  HIP_TRY(h, (launch_conv<3, 1, 1, 8, 4, 32>(h->stream, L, ld, n * Dl, hl, wl, dout.p(), nullptr, true)));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(out, dout.p(), nout * 4, hipMemcpyDeviceToHost));
+  SN_GUARD_CHECK(h, dout, "the fp32 first aggregation layer");
+  return SN_OK;
+}
+
+int sn_dbg_softargmin(sn_handle* h, int n, int Dl, int hl, int wl, int form, int want_conf, float bias, const float* v,
+                      const float* w, float* cost, float* disp_low, float* conf_low, unsigned long long* nonfinite) {
+  DevScope ds;
+  if (!h || !v || !cost || !disp_low || !nonfinite || n <= 0 || Dl <= 0 || Dl > 16 || hl <= 0 || wl <= 0) return SN_ERR_ARG;
+  if ((form != 0 && form != 1) || (form == 0 && !w) || (want_conf && !conf_low)) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const size_t plane = (size_t)hl * wl, npix = (size_t)n * plane, nv = npix * Dl * (form == 0 ? kC : 27);
+  float *dv = nullptr, *dw = nullptr;
+  Guarded<float> dcost, ddisp, dconf;
+  HookStat st;
+  HIP_TRY(h, ds.alloc(&dv, nv));
+  HIP_TRY(h, hipMemcpy(dv, v, nv * 4, hipMemcpyHostToDevice));
+  if (form == 0) {
+    HIP_TRY(h, ds.alloc(&dw, (size_t)kC * 27));
+    HIP_TRY(h, hipMemcpy(dw, w, (size_t)kC * 27 * 4, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(h, dcost.alloc(ds, npix * Dl));
+  HIP_TRY(h, ddisp.alloc(ds, npix));
+  HIP_TRY(h, dconf.alloc(ds, npix));
+  HIP_TRY(h, st.alloc(ds));
+  HIP_TRY(h, launch_softargmin_kernels(h->stream, dv, form == 1, dw, bias, Dl, hl, wl, (int)npix, ddisp.p(), dcost.p(),
+                                       want_conf ? dconf.p() : nullptr, st.dev + kStatNonfiniteLow));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(cost, dcost.p(), npix * Dl * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(disp_low, ddisp.p(), npix * 4, hipMemcpyDeviceToHost));
+  if (conf_low) HIP_TRY(h, hipMemcpy(conf_low, dconf.p(), npix * 4, hipMemcpyDeviceToHost));     // !want_conf: still the 0xff pattern
+  HIP_TRY(h, st.read(kStatNonfiniteLow, nonfinite));
+  const char* const name = form == 1 ? "k_softargmin_p" : "k_head_softargmin";
+  SN_GUARD_CHECK(h, dcost, name);
+  SN_GUARD_CHECK(h, ddisp, name);
+  SN_GUARD_CHECK(h, dconf, name);
+  return SN_OK;
+}
+
+int sn_dbg_agg_tail(sn_handle* h, const float* vol, int n, int Dl, int hl, int wl, const float* wt, const float* bias,
+                    const float* out_w, float out_b, int form, int want_conf, float* cost, float* disp_low, float* conf_low,
+                    unsigned long long* nonfinite, float* layer_vol) {
+  DevScope ds;
+  if (!h || !vol || !wt || !bias || !out_w || !cost || !disp_low || !nonfinite || n <= 0 || Dl <= 0 || Dl > 16 || hl <= 0 ||
+      wl <= 0 || form < 0 || form > 2 || (want_conf && !conf_low) || (form == 2 && layer_vol))
+    return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  ConvLayer L;
+  HeadLayer hd;
+  rc = upload_conv3d(h, HostLayer{wt, bias, kC, kC, 27}, &L);
+  if (!rc) rc = upload_x3(h, 96, [&](int co, int c, int tap) { return wt[(((size_t)co * kC + (c & 31)) * 3 + (c >> 5)) * 9 + tap]; }, &L);
+  if (!rc) rc = upload_head(h, HostLayer{out_w, &out_b, 1, kC, 27}, &hd);
+  if (!rc && form == 2) rc = upload_agg_head_frag(h, HostLayer{out_w, &out_b, 1, kC, 27}, &hd);
+  ds.adopt(L);
+  ds.adopt(hd);
+  if (rc) return rc;
+  const size_t plane = (size_t)hl * wl, npix = (size_t)n * plane;
+  const size_t nmid = npix * Dl * (form == 2 ? 27 : kC);       // the layer's fp32 output: volume, or the partial sums P
+  std::vector<float> tmp;
+  vol_to_device_order(vol, n, Dl, plane, tmp);
+  std::vector<_Float16> hs;
+  host_to_slots(tmp.data(), n * Dl, hl, wl, hs);
+  uint4* din = nullptr;
+  Guarded<float> dmid, dcost, ddisp, dconf;
+  HookStat st;
+  HIP_TRY(h, dmid.alloc(ds, nmid));
+  HIP_TRY(h, dcost.alloc(ds, npix * Dl));
+  HIP_TRY(h, ddisp.alloc(ds, npix));
+  HIP_TRY(h, dconf.alloc(ds, npix));
+  HIP_TRY(h, st.alloc(ds));
+  if (form == 0) {
+    HIP_TRY(h, ds.alloc(&din, hs.size() / 8));
+    HIP_TRY(h, to_dev(din, hs));
+    HIP_TRY(h, hipDeviceSynchronize());
+    SlotIn ls{din, Dl, hl, wl};
+    HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, false, SlotIn>(h->stream, L, ls, n * Dl, hl, wl, dmid.p(), nullptr, true, h->num_cu)));
+  } else {
+    const VolPad g = vol_pad(Dl, hl, wl);
+    PaddedSlots pin = vol_padded(g, n);
+    pin.put(hs);
+    HIP_TRY(h, ds.alloc(&din, pin.v.size() / 8));
+    HIP_TRY(h, to_dev(din, pin.v));
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (form == 1)
+      HIP_TRY(h, launch_agg_dma<false>(h->stream, L, din, g, n, dmid.p(), true, h->num_cu));
+    else
+      HIP_TRY(h, (launch_agg_dma<false, true>(h->stream, L, din, g, n, dmid.p(), true, h->num_cu, hd.pfrag)));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, from_dev(pin.v, din));
+    if (!pin.outside_is_zero()) {      // the padded volume is this layer's input only: its borders still hold the zeros
+      set_err(h, "k_agg_x3s_dma (fp32 output) wrote into the padded input volume");
+      return SN_ERR_DEVICE;
+    }
+  }
+  HIP_TRY(h, launch_softargmin_kernels(h->stream, dmid.p(), form == 2, hd.w, hd.bias, Dl, hl, wl, (int)npix, ddisp.p(), dcost.p(),
+                                       want_conf ? dconf.p() : nullptr, st.dev + kStatNonfiniteLow));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(cost, dcost.p(), npix * Dl * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(disp_low, ddisp.p(), npix * 4, hipMemcpyDeviceToHost));
+  if (conf_low) HIP_TRY(h, hipMemcpy(conf_low, dconf.p(), npix * 4, hipMemcpyDeviceToHost));
+  if (layer_vol) HIP_TRY(h, hipMemcpy(layer_vol, dmid.p(), nmid * 4, hipMemcpyDeviceToHost));      // [n Dl][32][hl][wl]
+  HIP_TRY(h, st.read(kStatNonfiniteLow, nonfinite));
+  SN_GUARD_CHECK(h, dmid, form == 0 ? "k_conv_x3s (fp32 output)" : "k_agg_x3s_dma (fp32 output)");
+  SN_GUARD_CHECK(h, dcost, "the soft-argmin");
+  SN_GUARD_CHECK(h, ddisp, "the soft-argmin");
+  SN_GUARD_CHECK(h, dconf, "the soft-argmin");
+  return SN_OK;
+}
+
+int sn_dbg_head(sn_handle* h, int n, const float* x, int hk, int wk, const float* head_w, float head_b, const float* low, int ups,
+                float dnorm, int h_out, int w_out, int form, float* out_disp, int32_t* out_raw, double* mean_abs_dr,
+                unsigned long long* nonfinite) {
+  DevScope ds;
+  if (!h || !x || !head_w || !low || !out_disp || !out_raw || !mean_abs_dr || !nonfinite) return SN_ERR_ARG;
+  if (n <= 0 || hk <= 0 || wk <= 0 || h_out <= 0 || w_out <= 0 || h_out > hk || w_out > wk || (ups != 16 && ups != 2) ||
+      hk % ups || wk % ups || form < 0 || form > 2 || !(dnorm > 0.f))
+    return SN_ERR_ARG;
+  if (form != 2 && h->precision != SN_PREC_FP32) {
+    set_err(h, "sn_dbg_head forms 0 and 1 need an engine created with SN_PREC_FP32");
+    return SN_ERR_ARG;
+  }
+  if (form == 2 && h->precision == SN_PREC_FP32) {
+    set_err(h, "sn_dbg_head form 2 needs an engine created in an fp16 mode");
+    return SN_ERR_ARG;
+  }
+  int rc = check_device(h);
+  if (rc) return rc;
+  HeadLayer hd;
+  rc = form == 2 ? upload_head_split(h, HostLayer{head_w, &head_b, 1, kC, 9}, &hd) : upload_head(h, HostLayer{head_w, &head_b, 1, kC, 9}, &hd);
+  ds.adopt(hd);
+  if (rc) return rc;
+  const int sh = hk / ups, sw = wk / ups;
+  const size_t nlow = (size_t)n * sh * sw, nout = (size_t)n * h_out * w_out;
+  float* dlow = nullptr;
+  Guarded<float> dd;
+  Guarded<int32_t> dr;
+  HookStat st;
+  HIP_TRY(h, ds.alloc(&dlow, nlow));
+  HIP_TRY(h, dd.alloc(ds, nout));
+  HIP_TRY(h, dr.alloc(ds, nout));
+  HIP_TRY(h, st.alloc(ds));
+  HIP_TRY(h, hipMemcpy(dlow, low, nlow * 4, hipMemcpyHostToDevice));
+  const float inv_q = (float)(1.0 / (kWireFactor * (double)kOutScale));
+  const UpScale us{1.0f / (float)ups, (float)ups};
+  if (form == 2) {        // the split head of SN_PREC_F16X3 on the hi / lo tower tensor, as refine_level launches it
+    const RefGeom g = make_ref_geom(hk, wk);
+    if ((2 * (ref16_slots(g, n) + ref_slack(g)) + ref_front(g)) * 16 >= ((size_t)1 << 32)) return SN_ERR_ARG;
+    RefHost t(g, n, hk, wk, true, true);      // [hi | slack | lo | slack]
+    t.pack(x, true);
+    uint4* da = nullptr;
+    HIP_TRY(h, alloc_ref16(ds, g, t.slots(), &da));
+    HIP_TRY(h, to_dev(da, t.v));
+    HIP_TRY(h, hipDeviceSynchronize());
+    const HeadArgs ha{hd.wsplit, dlow, dd.p(), dr.p(), hd.biassplit, dnorm * hd.unscale, inv_q, sh, sw, h_out, w_out, us, st.dev};
+    HIP_TRY(h, launch_head_final_f16(h->stream, true, da, t.lo_slots, g, n, ha));
+  } else {
+    const size_t nx = (size_t)n * kC * hk * wk;
+    float* dx = nullptr;
+    HIP_TRY(h, ds.alloc(&dx, nx));
+    HIP_TRY(h, hipMemcpy(dx, x, nx * 4, hipMemcpyHostToDevice));
+    const HeadArgs ha{hd.w, dlow, dd.p(), dr.p(), hd.bias, dnorm, inv_q, sh, sw, h_out, w_out, us, st.dev};
+    HIP_TRY(h, launch_head_final_f32(h->stream, form == 1, dx, hk, wk, n, ha));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(out_disp, dd.p(), nout * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(out_raw, dr.p(), nout * 4, hipMemcpyDeviceToHost));
+  unsigned long long sum = 0;
+  HIP_TRY(h, st.read(0, &sum));
+  HIP_TRY(h, st.read(kStatNonfinite, nonfinite));
+  *mean_abs_dr = (double)sum / (double)kStatScale / (double)nout;
+  const char* const name = form == 0 ? "k_head_final" : form == 1 ? "k_head_final_mfma32" : "k_head_final_f16<true>";
+  SN_GUARD_CHECK(h, dd, name);
+  SN_GUARD_CHECK(h, dr, name);
+  return SN_OK;
+}
+
+int sn_dbg_img_pool2(sn_handle* h, const int8_t* in6, int n, int h_px, int w, int levels, float* out) {
+  DevScope ds;
+  if (!h || !in6 || !out || n <= 0 || h_px <= 0 || w <= 0 || levels < 2 || levels > kMaxLevels) return SN_ERR_ARG;
+  int rc = check_device(h);
+  if (rc) return rc;
+  const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16;
+  const size_t nin = (size_t)n * 6 * h_px * w;
+  int8_t* din = nullptr;
+  HIP_TRY(h, ds.alloc(&din, nin));
+  HIP_TRY(h, hipMemcpy(din, in6, nin, hipMemcpyHostToDevice));
+  Guarded<float> lvl[kMaxLevels];
+  for (int lv = 1; lv < levels; ++lv) HIP_TRY(h, lvl[lv].alloc(ds, (size_t)n * 3 * (Hp >> lv) * (Wp >> lv)));
+  for (int lv = 1; lv < levels; ++lv) {       // chained as refine_coarse chains them
+    if (lv == 1)
+      HIP_TRY(h, launch_img_pool2(h->stream, true, din, h_px, w, Hp >> lv, Wp >> lv, lvl[lv].p(), n));
+    else
+      HIP_TRY(h, launch_img_pool2(h->stream, false, lvl[lv - 1].p(), 0, 0, Hp >> lv, Wp >> lv, lvl[lv].p(), n));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int lv = 1; lv < levels; ++lv) {
+    const size_t cnt = (size_t)n * 3 * (Hp >> lv) * (Wp >> lv);
+    HIP_TRY(h, hipMemcpy(out, lvl[lv].p(), cnt * 4, hipMemcpyDeviceToHost));
+    out += cnt;
+    SN_GUARD_CHECK(h, lvl[lv], "k_img_pool2");
+  }
   return SN_OK;
 }
 

@@ -155,26 +155,34 @@ void free_ws(Workspace* ws) {
 }
 
 // ---- the forward pass on device buffers ------------------------------------------------------------
-// The soft-argmin of pairs [p0, p0 + m), every precision; the one place that names its kernels.  folded: v holds the
-// partial sums P of the last aggregation layer (SN_HEAD_FOLD on the zero-bordered volumes: k_softargmin_p), otherwise its
-// volume, which k_head_softargmin contracts first.  Writes disp_low, and cost / conf_low on request.
+// The soft-argmin of npix = (pairs) hl wl pixels on caller buffers, every precision; the one place that names its kernels.
+// folded: v holds the partial sums P of the last aggregation layer (k_softargmin_p; w unused), otherwise its volume, which
+// k_head_softargmin contracts with w [32][27] first.  cost_out / conf_low nullable; nf: the range check's count (nullable).
+hipError_t launch_softargmin_kernels(hipStream_t st, const float* v, bool folded, const float* w, float bias, int Dl, int hl,
+                                     int wl, int npix, float* disp_low, float* cost_out, float* conf_low, unsigned long long* nf) {
+  const bool want_conf = conf_low != nullptr;
+  const dim3 grid((npix + 63) / 64);
+  if (folded) {
+    const auto kern = want_conf ? k_softargmin_p<16, true> : k_softargmin_p<16, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * Dl), 0, st, v, bias, Dl, hl, wl, npix, disp_low, cost_out, conf_low, nf);
+  } else {
+    const auto kern = want_conf ? k_head_softargmin<16, true> : k_head_softargmin<16, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * kSamWaves), 0, st, v, w, bias, Dl, hl, wl, npix, disp_low, cost_out, conf_low, nf);
+  }
+  return hipGetLastError();
+}
+
+// The soft-argmin of pairs [p0, p0 + m) on the workspace's buffers (launch_softargmin_kernels, above, names the kernels).  folded: v
+// holds the partial sums P of the last aggregation layer (SN_HEAD_FOLD on the zero-bordered volumes), otherwise its volume.
+// Writes disp_low, and cost / conf_low on request.
 int launch_softargmin(sn_handle* h, Workspace& ws, hipStream_t st, const float* v, bool folded, int p0, int m, bool want_cost,
                       bool want_conf) {
   const int hl = h->hl, wl = h->wl, Dl = h->Dl, npix = m * hl * wl;
   float* const disp_low = ws.disp_low + (size_t)p0 * hl * wl;
   float* const cost_out = want_cost ? ws.cost + (size_t)p0 * Dl * hl * wl : nullptr;
   float* const conf_low = want_conf ? ws.conf_low + (size_t)p0 * hl * wl : nullptr;
-  unsigned long long* const nf = ws.stats + kStatNonfiniteLow;
-  const dim3 grid((npix + 63) / 64);
-  if (folded) {
-    const auto kern = want_conf ? k_softargmin_p<16, true> : k_softargmin_p<16, false>;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * Dl), 0, st, v, h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out, conf_low, nf);
-  } else {
-    const auto kern = want_conf ? k_head_softargmin<16, true> : k_head_softargmin<16, false>;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * kSamWaves), 0, st, v, h->aout.w, h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out,
-                       conf_low, nf);
-  }
-  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, launch_softargmin_kernels(st, v, folded, h->aout.w, h->aout.bias, Dl, hl, wl, npix, disp_low, cost_out, conf_low,
+                                       ws.stats + kStatNonfiniteLow));
   return SN_OK;
 }
 
@@ -259,11 +267,10 @@ int lowres_features_slots(sn_handle* h, Workspace& ws, hipStream_t st, int ni) {
 // sums P [m Dl][27][hl][wl] (the contraction rides on the last layer's epilogue), not the volume.
 int lowres_aggregate_slots(sn_handle* h, Workspace& ws, hipStream_t st, int m, bool* folded) {
   const int hl = h->hl, wl = h->wl, Dl = h->Dl, ncu = h->num_cu;
-  const long total = (long)m * Dl * 4 * hl * wl;
   *folded = false;
   if (ws.volp[0] != nullptr) {        // zero-bordered volumes, LDS-DMA kernel
     const VolPad g = vol_pad(Dl, hl, wl);
-    hipLaunchKernelGGL(k_cost_slots_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws.feat, ws.volp[1], g, m);
+    HIP_TRY(h, launch_cost_slots_pad(st, ws.feat, ws.volp[1], g, m));
     for (int i = 0; i + 1 < kNAgg; ++i)
       HIP_TRY(h, launch_agg_dma<true>(st, h->agg[i], ws.volp[(i + 1) & 1], g, m, ws.volp[i & 1], true, ncu));
     const int i = kNAgg - 1;
@@ -274,8 +281,7 @@ int lowres_aggregate_slots(sn_handle* h, Workspace& ws, hipStream_t st, int m, b
       HIP_TRY(h, launch_agg_dma<false>(st, h->agg[i], ws.volp[(i + 1) & 1], g, m, ws.vol[i & 1], true, ncu));
     return SN_OK;
   }
-  hipLaunchKernelGGL(k_cost_slots, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws.feat,
-                     reinterpret_cast<uint4*>(ws.vol[1]), Dl, hl, wl, m);
+  HIP_TRY(h, launch_cost_slots(st, ws.feat, reinterpret_cast<uint4*>(ws.vol[1]), Dl, hl, wl, m));
   for (int i = 0; i < kNAgg; ++i) {
     float* const src = ws.vol[(i + 1) & 1];
     if ((h->ablate_x >> (kAblAgg + i)) & 1u) HIP_TRY(h, zero_lo_slots(st, src, m * Dl, (size_t)hl * wl));
@@ -398,16 +404,7 @@ int refine_level(sn_handle* h, Workspace& ws, hipStream_t st, const RefineCall& 
     if (pe) HIP_TRY(h, hipEventRecord(h->ev[5], st));
     const HeadArgs ha{T.rout.w, a.src, a.od, a.orw, T.rout.bias, a.dnorm, inv_q, a.sh, a.sw, a.H, a.W, a.ups, a.stat};
     // head on the fp32 MFMA with the nine taps as M (k_head_final_mfma32); SN_HEAD_MFMA32=0 keeps the per-pixel kernel (A/B)
-    if (switches().head_mfma32) {
-      constexpr int TH = 14;               // 16-row P window: 32 segments, 8 per wave (TH = 6 measured the same 41 us without the statistic)
-      using HT = HeadTile<TH>;
-      const int tiles_x = (a.W + HT::TWO - 1) / HT::TWO, tiles_y = (a.H + TH - 1) / TH;
-      hipLaunchKernelGGL(k_head_final_mfma32<TH>, dim3((unsigned)(tiles_x * tiles_y * c)), dim3(256), HT::LDS_BYTES, st, a.ref[0],
-                         Hk, Wk, tiles_x, tiles_y, ha);
-    } else {
-      dim3 grid((a.W + 63) / 64, (a.H + 3) / 4, c);
-      hipLaunchKernelGGL(k_head_final, grid, dim3(256), 0, st, a.ref[0], Hk, Wk, ha);
-    }
+    HIP_TRY(h, launch_head_final_f32(st, switches().head_mfma32, a.ref[0], Hk, Wk, c, ha));
   } else {
     // fp16 tower: ref.in writes the NCHW8c fp16 tensor, the 12 C->C convs run on v_mfma_f32_32x32x16_f16, the head
     // reads fp16 and finishes in fp32
@@ -489,16 +486,11 @@ int refine_coarse(sn_handle* h, Workspace& ws, hipStream_t st, int p0, int m, co
   const int8_t* in_piece = in6 + (size_t)p0 * 6 * HW;
   for (int lv = 1; lv < h->levels; ++lv) {       // level 1 from the int8 input, the others from the level above
     const Tower& T = h->tw[lv];
-    const long total = (long)m * 3 * T.Hk * T.Wk;
-    const dim3 grid((unsigned)((total + 255) / 256));
     if (lv == 1)
-      hipLaunchKernelGGL(k_img_pool2<true>, grid, dim3(256), 0, st, (const void*)in_piece, h->H, h->W, T.Hk, T.Wk,
-                         ws.pyr[lv], total);
+      HIP_TRY(h, launch_img_pool2(st, true, in_piece, h->H, h->W, T.Hk, T.Wk, ws.pyr[lv], m));
     else
-      hipLaunchKernelGGL(k_img_pool2<false>, grid, dim3(256), 0, st, (const void*)ws.pyr[lv - 1], 0, 0, T.Hk, T.Wk,
-                         ws.pyr[lv], total);
+      HIP_TRY(h, launch_img_pool2(st, false, ws.pyr[lv - 1], 0, 0, T.Hk, T.Wk, ws.pyr[lv], m));
   }
-  HIP_TRY(h, hipGetLastError());
   const float* src = ws.disp_low + (size_t)p0 * h->hl * h->wl;
   int sh = h->hl, sw = h->wl;
   for (int lv = h->levels - 1; lv >= 1; --lv) {

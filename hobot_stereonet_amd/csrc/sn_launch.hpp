@@ -478,6 +478,46 @@ hipError_t launch_head_final_f16(hipStream_t st, bool split, const uint4* x, siz
   return hipGetLastError();
 }
 
+// The SN_PREC_FP32 head on x fp32 [nimg][32][Hk][Wk]: the fp32 MFMA with the nine taps as M (k_head_final_mfma32), or the
+// per-pixel kernel (SN_HEAD_MFMA32=0, A/B).  Geometry-free: refine_level and the parity hook sn_dbg_head both launch through it.
+hipError_t launch_head_final_f32(hipStream_t st, bool mfma32, const float* x, int Hk, int Wk, int nimg, const HeadArgs& ha) {
+  if (mfma32) {
+    constexpr int TH = 14;               // 16-row P window: 32 segments, 8 per wave (TH = 6 measured the same 41 us without the statistic)
+    using HT = HeadTile<TH>;
+    const int tiles_x = (ha.W + HT::TWO - 1) / HT::TWO, tiles_y = (ha.H + TH - 1) / TH;
+    hipLaunchKernelGGL(k_head_final_mfma32<TH>, dim3((unsigned)(tiles_x * tiles_y * nimg)), dim3(256), HT::LDS_BYTES, st, x,
+                       Hk, Wk, tiles_x, tiles_y, ha);
+  } else {
+    dim3 grid((ha.W + 63) / 64, (ha.H + 3) / 4, nimg);
+    hipLaunchKernelGGL(k_head_final, grid, dim3(256), 0, st, x, Hk, Wk, ha);
+  }
+  return hipGetLastError();
+}
+
+// The cost volume of m pairs from feat fp32 [2m][32][hl][wl], in split slots: the plain layout, or the zero-bordered one
+hipError_t launch_cost_slots(hipStream_t st, const float* feat, uint4* vol, int Dl, int hl, int wl, int m) {
+  const long total = (long)m * Dl * 4 * hl * wl;
+  hipLaunchKernelGGL(k_cost_slots, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, vol, Dl, hl, wl, m);
+  return hipGetLastError();
+}
+hipError_t launch_cost_slots_pad(hipStream_t st, const float* feat, uint4* volp, const VolPad& g, int m) {
+  const long total = (long)m * g.Dl * 4 * g.H * g.W;
+  hipLaunchKernelGGL(k_cost_slots_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, volp, g, m);
+  return hipGetLastError();
+}
+
+// One level of the hierarchical refinement's image pyramid for nimg images: 2x2 average pooling of the left eye into
+// out [nimg][3][Ho][Wo].  first: src = the int8 model input [nimg][6][H][W]; otherwise the float level above (H, W unused).
+hipError_t launch_img_pool2(hipStream_t st, bool first, const void* src, int H, int W, int Ho, int Wo, float* out, int nimg) {
+  const long total = (long)nimg * 3 * Ho * Wo;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (first)
+    hipLaunchKernelGGL(k_img_pool2<true>, grid, dim3(256), 0, st, src, H, W, Ho, Wo, out, total);
+  else
+    hipLaunchKernelGGL(k_img_pool2<false>, grid, dim3(256), 0, st, src, 0, 0, Ho, Wo, out, total);
+  return hipGetLastError();
+}
+
 // Tile width of a dilation-1 / -2 launch.  The persistent grid (two workgroups per CU) works through the tiles in
 // rounds and the launch lasts ceil(tiles / workgroups) rounds: 1280x720, two pairs = 3600 8x64 tiles on 512
 // workgroups = 7.03 -> 8 rounds, 12 % of the launch spent on 16 leftover tiles.  8x32 tiles cost ~3 % more per pixel

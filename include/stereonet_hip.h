@@ -373,6 +373,41 @@ int sn_dbg_ref_block_f16x3(sn_handle *h, const float *in, int h_px, int w, const
 int sn_dbg_ref_tail_f16(sn_handle *h, int n, const float *in, int hk, int wk, const float *w1, const float *b1,
                         const float *w2, const float *b2, const float *head_w, float head_b, const float *low, int ups,
                         float dnorm, int h_out, int w_out, int form, float *out_disp, int32_t *out_raw);
+/* Mid-stage hooks: the kernels between the feature tower and the output maps, one at a time, on caller tensors and through the
+ * launch code of the forward pass.  Every device output lies between guard bands of known bytes and starts as the 0xff pattern
+ * (fp32 NaN / int32 -1: an element the kernel does not write shows); a changed band or a non-zero border of a padded layout
+ * returns SN_ERR_DEVICE with a message.  n = pairs (images for the heads), Dl <= 16 planes, hl x wl the low-resolution map.
+ *
+ * sn_dbg_cost_volume: feat [2n][32][hl][wl] (left, right interleaved) -> out [n][Dl][32][hl][wl], the split-slot cost volume
+ * read back as hi + lo / 2048.  form 0 = k_cost_slots (plain layout), 1 = k_cost_slots_pad (zero-bordered volume of n pairs). */
+int sn_dbg_cost_volume(sn_handle *h, const float *feat, int n, int Dl, int hl, int wl, int form, float *out);
+/* the SN_PREC_FP32 first aggregation layer with the cost volume in its loader (LoadCostVol), LeakyReLU on:
+ * wt [32][32][3][3][3], out [n][Dl][32][hl][wl] */
+int sn_dbg_agg_first_f32(sn_handle *h, const float *feat, int n, int Dl, int hl, int wl, const float *wt, const float *bias,
+                         float *out);
+/* the soft-argmin alone.  form 0 = k_head_softargmin on v = a volume [n][Dl][32][hl][wl] with w [32][27] (ci, dz*9+ky*3+kx);
+ * form 1 = k_softargmin_p on v = partial sums P [n][Dl][27][hl][wl] (w unused).  -> cost [n][Dl][hl][wl], disp_low [n][hl][wl],
+ * conf_low [n][hl][wl] (written when want_conf; nullable otherwise, left as the 0xff pattern) and the count of pixels with a
+ * non-finite cost. */
+int sn_dbg_softargmin(sn_handle *h, int n, int Dl, int hl, int wl, int form, int want_conf, float bias, const float *v,
+                      const float *w, float *cost, float *disp_low, float *conf_low, unsigned long long *nonfinite);
+/* the LAST aggregation layer (fp32 output, LeakyReLU) of the fp16 modes followed by the soft-argmin, n pairs in one volume:
+ * vol [n][32][Dl][hl][wl], wt [32][32][3][3][3], out_w [32][27].  form 0 = plain slots, k_conv_x3s (fp32 output) +
+ * k_head_softargmin; 1 = zero-bordered slots, k_agg_x3s_dma<false> + k_head_softargmin; 2 = k_agg_x3s_dma<false, true>
+ * (partial sums P) + k_softargmin_p.  layer_vol (nullable; forms 0 and 1 only): the layer's volume [n][Dl][32][hl][wl]. */
+int sn_dbg_agg_tail(sn_handle *h, const float *vol, int n, int Dl, int hl, int wl, const float *wt, const float *bias,
+                    const float *out_w, float out_b, int form, int want_conf, float *cost, float *disp_low, float *conf_low,
+                    unsigned long long *nonfinite, float *layer_vol);
+/* the refinement head alone on x [n][32][hk][wk] (the tower's output), arguments as sn_dbg_ref_tail_f16.  form 0 = k_head_final,
+ * 1 = k_head_final_mfma32 (both need an SN_PREC_FP32 engine), 2 = the split head of SN_PREC_F16X3 on the hi / lo tensor (needs an
+ * engine in an fp16 mode); SN_ERR_ARG with a message otherwise.  -> out_disp / out_raw [n][h_out][w_out], the mean |D r| per
+ * written pixel (the refinement statistic) and the count of non-finite pixels. */
+int sn_dbg_head(sn_handle *h, int n, const float *x, int hk, int wk, const float *head_w, float head_b, const float *low, int ups,
+                float dnorm, int h_out, int w_out, int form, float *out_disp, int32_t *out_raw, double *mean_abs_dr,
+                unsigned long long *nonfinite);
+/* the image pyramid of the hierarchical refinement: in6 int8 [n][6][h][w] -> the float levels 1 .. levels - 1 one after the
+ * other, level k [n][3][hp >> k][wp >> k] (hp / wp = ceil16), level 1 from the int8 input, the others from the level above */
+int sn_dbg_img_pool2(sn_handle *h, const int8_t *in6, int n, int h_px, int w, int levels, float *out);
 /* intermediates of the most recent batch-1 inference: "feat_l" / "feat_r" [32][hl][wl],
  * "cost" [Dl][hl][wl], "disp_low" [hl][wl], and for a hierarchical model "level1" .. "level3" (the map of that
  * refinement level, [Hp/2^k][Wp/2^k]); returns the element count in *n (dst may be NULL to query).
