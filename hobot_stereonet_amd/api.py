@@ -267,6 +267,16 @@ def load_library(path: Optional[str] = None):
     lib.sn_dbg_ref_block_f16x3.argtypes = [vp, fp, ip, ip, fp, fp, fp, fp, ip, ip, fp]
     lib.sn_dbg_ref_tail_f16.argtypes = [vp, ip, fp, ip, ip, fp, fp, fp, fp, fp, C.c_float, fp, ip, C.c_float, ip, ip, ip, fp, i32p]
     lib.sn_dbg_read.argtypes = [vp, C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.sn_dbg_set_grid_cus.argtypes = [vp, ip]
+    lib.sn_dbg_last_launch.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+    lib.sn_dbg_conv2d_n.argtypes = [vp, ip] + lib.sn_dbg_conv2d.argtypes[1:]
+    lib.sn_dbg_down0_n.argtypes = [vp, ip] + lib.sn_dbg_down0.argtypes[1:]
+    lib.sn_dbg_down01_n.argtypes = [vp, ip] + lib.sn_dbg_down01.argtypes[1:]
+    lib.sn_dbg_refin_n.argtypes = [vp, ip] + lib.sn_dbg_refin.argtypes[1:]
+    lib.sn_dbg_ref_conv_f16_n.argtypes = [vp, ip] + lib.sn_dbg_ref_conv_f16.argtypes[1:]
+    lib.sn_dbg_ref_conv_f16x3_n.argtypes = [vp, ip] + lib.sn_dbg_ref_conv_f16x3.argtypes[1:]
+    lib.sn_dbg_ref_block_f16_n.argtypes = [vp, ip] + lib.sn_dbg_ref_block_f16.argtypes[1:]
+    lib.sn_dbg_ref_block_f16x3_n.argtypes = [vp, ip] + lib.sn_dbg_ref_block_f16x3.argtypes[1:]
     u64p = C.POINTER(C.c_uint64)
     lib.sn_dbg_cost_volume.argtypes = [vp, fp, ip, ip, ip, ip, ip, fp]
     lib.sn_dbg_agg_first_f32.argtypes = [vp, fp, ip, ip, ip, ip, fp, fp, fp]
@@ -321,7 +331,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -1067,60 +1077,82 @@ class StereoNetHIP:
                 "bytes_per_launch": by.value}
 
     # -- parity hooks --------------------------------------------------------------------------------
+    def dbg_set_grid_cus(self, cus: int = 0):
+        """sn_dbg_set_grid_cus: the CU count the parity hooks (and only they) size their persistent grids with; 0 = the
+        device's.  Hooks whose launcher builds its grid in bands of 8 refuse a value that is no multiple of 8."""
+        self._check(self._lib.sn_dbg_set_grid_cus(self._h, int(cus)), "sn_dbg_set_grid_cus")
+
+    def dbg_last_launch(self):
+        """-> (workgroups, work units) of the last hook call's last persistent launch: tiles, half tiles for
+        k_ref_conv_f32, flat rows for the streamed blocks"""
+        wgs, units = C.c_int(0), C.c_int(0)
+        self._check(self._lib.sn_dbg_last_launch(self._h, C.byref(wgs), C.byref(units)), "sn_dbg_last_launch")
+        return wgs.value, units.value
+
+    @staticmethod
+    def _batch(x, dtype=np.float32):
+        """(c, h, w) or (n, c, h, w) -> contiguous (n, c, h, w) and whether the caller passed one image without the batch axis"""
+        x = np.ascontiguousarray(x, dtype)
+        return (x[None], True) if x.ndim == 3 else (x, False)
+
     def dbg_conv2d(self, x, wt, bias, k, stride=1, dil=1, lrelu=False, residual=None, x3=False, slots=False, tower32=False, dma=False):
-        """dma (with x3 and slots): the kernel of the zero-bordered tensors — k_down_x3s_dma (5x5 stride 2) or
-        k_feat_x3s_dma (3x3, also with a residual); the hook also checks that the borders stay zero"""
-        x = np.ascontiguousarray(x, np.float32)
+        """x (cin, h, w) or (n, cin, h, w): n images in one launch.  dma (with x3 and slots): the kernel of the zero-bordered
+        tensors — k_down_x3s_dma (5x5 stride 2) or k_feat_x3s_dma (3x3, also with a residual); the hook also checks that the
+        borders stay zero"""
+        x, one = self._batch(x)
         wt = np.ascontiguousarray(wt, np.float32)
         bias = np.ascontiguousarray(bias, np.float32)
-        cin, h, w = x.shape
+        n, cin, h, w = x.shape
         ho, wo = (h, w) if stride == 1 else (h // 2, w // 2)
-        out = np.empty((32, ho, wo), np.float32)
+        out = np.empty((n, 32, ho, wo), np.float32)
         res = np.ascontiguousarray(residual, np.float32) if residual is not None else None
-        self._check(self._lib.sn_dbg_conv2d(self._h, x.ctypes.data, cin, h, w, wt.ctypes.data, bias.ctypes.data, k,
-                                            stride, dil, int(lrelu) | (2 if x3 else 0) | (4 if slots else 0) | (8 if tower32 else 0) | (16 if dma else 0), _np_ptr(res),
-                                            out.ctypes.data),
+        assert res is None or res.size == out.size
+        self._check(self._lib.sn_dbg_conv2d_n(self._h, n, x.ctypes.data, cin, h, w, wt.ctypes.data, bias.ctypes.data, k,
+                                              stride, dil, int(lrelu) | (2 if x3 else 0) | (4 if slots else 0) | (8 if tower32 else 0) | (16 if dma else 0), _np_ptr(res),
+                                              out.ctypes.data),
                     "sn_dbg_conv2d")
-        return out
+        return out[0] if one else out
 
     def dbg_down0(self, in6, wt, bias, tc=32):
-        """in6 int8 (6,h,w) -> float32 (2, 32, ho, wo): first down-conv of both eyes on the fp16 MFMA."""
-        x = np.ascontiguousarray(in6, np.int8)
+        """in6 int8 (6,h,w) -> float32 (2, 32, ho, wo): first down-conv of both eyes on the fp16 MFMA; in6 (n,6,h,w): n pairs
+        in one launch -> (2n, 32, ho, wo)."""
+        x, _ = self._batch(in6, np.int8)
         wt = np.ascontiguousarray(wt, np.float32)
         bias = np.ascontiguousarray(bias, np.float32)
-        _, h, w = x.shape
+        n, _, h, w = x.shape
         ho, wo = (h + 15) // 16 * 8, (w + 15) // 16 * 8
-        out = np.empty((2, 32, ho, wo), np.float32)
-        self._check(self._lib.sn_dbg_down0(self._h, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, tc,
-                                           out.ctypes.data), "sn_dbg_down0")
+        out = np.empty((2 * n, 32, ho, wo), np.float32)
+        self._check(self._lib.sn_dbg_down0_n(self._h, n, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, tc,
+                                             out.ctypes.data), "sn_dbg_down0")
         return out
 
     def dbg_down01(self, in6, w0, b0, w1, b1):
         """in6 int8 (6,h,w) -> float32 (2, 32, ho, wo), ho/wo = ceil16/4: the first two down-convs of both eyes as the
-        folded 13x13 stride-4 convolution (k_down01_f16 + k_down01_border)."""
-        x = np.ascontiguousarray(in6, np.int8)
+        folded 13x13 stride-4 convolution (k_down01_f16 + k_down01_border); in6 (n,6,h,w): n pairs in one launch -> (2n, ...)."""
+        x, _ = self._batch(in6, np.int8)
         w0, b0, w1, b1 = (np.ascontiguousarray(a, np.float32) for a in (w0, b0, w1, b1))
         assert w0.shape == (32, 3, 5, 5) and w1.shape == (32, 32, 5, 5) and b0.shape == (32,) and b1.shape == (32,)
-        _, h, w = x.shape
+        n, _, h, w = x.shape
         ho, wo = (h + 15) // 16 * 4, (w + 15) // 16 * 4
-        out = np.empty((2, 32, ho, wo), np.float32)
-        self._check(self._lib.sn_dbg_down01(self._h, x.ctypes.data, h, w, w0.ctypes.data, b0.ctypes.data, w1.ctypes.data,
-                                            b1.ctypes.data, out.ctypes.data), "sn_dbg_down01")
+        out = np.empty((2 * n, 32, ho, wo), np.float32)
+        self._check(self._lib.sn_dbg_down01_n(self._h, n, x.ctypes.data, h, w, w0.ctypes.data, b0.ctypes.data, w1.ctypes.data,
+                                              b1.ctypes.data, out.ctypes.data), "sn_dbg_down01")
         return out
 
     def dbg_refin(self, disp_low, in6, dmax, wt, bias, split=False):
-        """disp_low float32 (hp/16, wp/16), in6 int8 (6,h,w) -> float32 (32, hp, wp): refinement input conv."""
-        x = np.ascontiguousarray(in6, np.int8)
+        """disp_low float32 (hp/16, wp/16), in6 int8 (6,h,w) -> float32 (32, hp, wp): refinement input conv; with a leading
+        batch axis on both, n images in one launch."""
+        x, one = self._batch(in6, np.int8)
         dl = np.ascontiguousarray(disp_low, np.float32)
         wt = np.ascontiguousarray(wt, np.float32)
         bias = np.ascontiguousarray(bias, np.float32)
-        _, h, w = x.shape
+        n, _, h, w = x.shape
         hp, wp = (h + 15) // 16 * 16, (w + 15) // 16 * 16
-        assert dl.shape == (hp // 16, wp // 16)
-        out = np.empty((32, hp, wp), np.float32)
-        self._check(self._lib.sn_dbg_refin(self._h, dl.ctypes.data, x.ctypes.data, h, w, dmax, wt.ctypes.data,
-                                           bias.ctypes.data, int(split), out.ctypes.data), "sn_dbg_refin")
-        return out
+        assert dl.shape == ((hp // 16, wp // 16) if one else (n, hp // 16, wp // 16))
+        out = np.empty((n, 32, hp, wp), np.float32)
+        self._check(self._lib.sn_dbg_refin_n(self._h, n, dl.ctypes.data, x.ctypes.data, h, w, dmax, wt.ctypes.data,
+                                             bias.ctypes.data, int(split), out.ctypes.data), "sn_dbg_refin")
+        return out[0] if one else out
 
     def dbg_conv3d(self, x, wt, bias, lrelu=False, x3=False, slots=False, dma=False):
         """dma: the aggregation kernel on zero-bordered volumes (k_agg_x3s_dma; needs x3 and slots); the hook also checks that
@@ -1136,49 +1168,54 @@ class StereoNetHIP:
         return out
 
     def dbg_ref_conv_f16(self, x, wt, bias, dil=1, lrelu=False, residual=None, tile_w=0):
-        """tile_w: 0 = the width the engine would choose for this launch, 64 / 32 = force that variant (dilation 1, 2)"""
-        x = np.ascontiguousarray(x, np.float32)
+        """x (32, h, w) or (n, 32, h, w): n images in one launch.  tile_w: 0 = the width the engine would choose for this
+        launch, 64 / 32 = force that variant (dilation 1, 2)"""
+        x, one = self._batch(x)
         wt = np.ascontiguousarray(wt, np.float32)
         bias = np.ascontiguousarray(bias, np.float32)
-        _, h, w = x.shape
-        out = np.empty((32, h, w), np.float32)
+        n, _, h, w = x.shape
+        out = np.empty((n, 32, h, w), np.float32)
         res = np.ascontiguousarray(residual, np.float32) if residual is not None else None
+        assert res is None or res.size == out.size
         flags = int(bool(lrelu)) | (2 if tile_w == 64 else 4 if tile_w == 32 else 0)
-        self._check(self._lib.sn_dbg_ref_conv_f16(self._h, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, dil,
-                                                  flags, _np_ptr(res), out.ctypes.data), "sn_dbg_ref_conv_f16")
-        return out
+        self._check(self._lib.sn_dbg_ref_conv_f16_n(self._h, n, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, dil,
+                                                    flags, _np_ptr(res), out.ctypes.data), "sn_dbg_ref_conv_f16")
+        return out[0] if one else out
 
     def dbg_ref_conv_f16x3(self, x, wt, bias, dil=1, lrelu=False, residual=None):
-        x = np.ascontiguousarray(x, np.float32)
+        x, one = self._batch(x)
         wt = np.ascontiguousarray(wt, np.float32)
         bias = np.ascontiguousarray(bias, np.float32)
-        _, h, w = x.shape
-        out = np.empty((32, h, w), np.float32)
+        n, _, h, w = x.shape
+        out = np.empty((n, 32, h, w), np.float32)
         res = np.ascontiguousarray(residual, np.float32) if residual is not None else None
-        self._check(self._lib.sn_dbg_ref_conv_f16x3(self._h, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, dil,
-                                                    int(lrelu), _np_ptr(res), out.ctypes.data), "sn_dbg_ref_conv_f16x3")
-        return out
+        assert res is None or res.size == out.size
+        self._check(self._lib.sn_dbg_ref_conv_f16x3_n(self._h, n, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, dil,
+                                                      int(lrelu), _np_ptr(res), out.ctypes.data), "sn_dbg_ref_conv_f16x3")
+        return out[0] if one else out
 
     def dbg_ref_block_f16(self, x, w1, b1, w2, b2, dil=1, fused=0):
         """fused: 0 = two conv launches, 2 = row-streaming fused kernel (every dilation: 1, 2, 4, 8)"""
         dil = dil | (fused << 8)
-        a = [np.ascontiguousarray(v, np.float32) for v in (x, w1, b1, w2, b2)]
-        _, h, w = a[0].shape
-        out = np.empty((32, h, w), np.float32)
-        self._check(self._lib.sn_dbg_ref_block_f16(self._h, a[0].ctypes.data, h, w, a[1].ctypes.data, a[2].ctypes.data,
-                                                   a[3].ctypes.data, a[4].ctypes.data, dil, out.ctypes.data),
+        a = [np.ascontiguousarray(v, np.float32) for v in (w1, b1, w2, b2)]
+        x, one = self._batch(x)
+        n, _, h, w = x.shape
+        out = np.empty((n, 32, h, w), np.float32)
+        self._check(self._lib.sn_dbg_ref_block_f16_n(self._h, n, x.ctypes.data, h, w, a[0].ctypes.data, a[1].ctypes.data,
+                                                     a[2].ctypes.data, a[3].ctypes.data, dil, out.ctypes.data),
                     "sn_dbg_ref_block_f16")
-        return out
+        return out[0] if one else out
 
     def dbg_ref_block_f16x3(self, x, w1, b1, w2, b2, dil=1, streamed=False):
         """the same block on split operands (SN_PREC_F16X3): two k_ref_conv_f16x3 launches, or the row-streaming fused kernel"""
-        a = [np.ascontiguousarray(v, np.float32) for v in (x, w1, b1, w2, b2)]
-        _, h, w = a[0].shape
-        out = np.empty((32, h, w), np.float32)
-        self._check(self._lib.sn_dbg_ref_block_f16x3(self._h, a[0].ctypes.data, h, w, a[1].ctypes.data, a[2].ctypes.data,
-                                                     a[3].ctypes.data, a[4].ctypes.data, dil, int(streamed), out.ctypes.data),
+        a = [np.ascontiguousarray(v, np.float32) for v in (w1, b1, w2, b2)]
+        x, one = self._batch(x)
+        n, _, h, w = x.shape
+        out = np.empty((n, 32, h, w), np.float32)
+        self._check(self._lib.sn_dbg_ref_block_f16x3_n(self._h, n, x.ctypes.data, h, w, a[0].ctypes.data, a[1].ctypes.data,
+                                                       a[2].ctypes.data, a[3].ctypes.data, dil, int(streamed), out.ctypes.data),
                     "sn_dbg_ref_block_f16x3")
-        return out
+        return out[0] if one else out
 
     def dbg_ref_tail_f16(self, x, w1, b1, w2, b2, head_w, head_b, low, ups, dnorm, h_out, w_out, form):
         """Last residual block + refinement head on x float32 (n, 32, hk, wk); low (n, hk/ups, wk/ups); form 0 = streamed

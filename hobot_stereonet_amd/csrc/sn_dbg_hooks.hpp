@@ -1,6 +1,7 @@
 // sn_dbg_hooks.hpp — the sn_dbg_* entry points (parity hooks: one kernel or block on caller-supplied tensors, as the
 // pipeline launches it) and the host-side marshalling they share: split-slot tensors, their zero-bordered grids
-// (PaddedSlots), the fp16 tower layout (RefHost) and the guarded outputs of the mid-stage hooks (Guarded, HookStat).  Part of
+// (PaddedSlots), the fp16 tower layout (RefHost) and its device allocation with front rows and slack (RefDev), the guarded
+// outputs of the mid-stage hooks (Guarded, HookStat), and the grid cap of the hooks (sn_dbg_set_grid_cus, dbg_cus).  Part of
 // the single translation unit stereonet_hip.hip.
 #pragma once
 
@@ -110,15 +111,27 @@ struct RefHost {
             dst[(((size_t)i * kC + c) * h + y) * w + x] = f;
           }
   }
-  bool border_is_zero(int parts) const {      // the zero border of the hi (and lo) tensor survived a kernel
+  // the 0xff pattern (fp16 NaN) in the valid area of the first `parts` tensors, zeros everywhere else: what an output
+  // tensor holds before the launch, so that an element the kernel does not write shows
+  void prefill(int parts) {
+    v.assign(v.size(), (_Float16)0.f);
     for (int part = 0; part < parts; ++part)
       for (int plane = 0; plane < 4 * n; ++plane)
-        for (int y = 0; y < g.Hs; ++y)
-          for (int x = 0; x < g.Ws; ++x) {
-            if (y >= kRefPad && y < kRefPad + h && x >= kRefPad && x < kRefPad + w) continue;
-            for (int e = 0; e < 8; ++e)
-              if ((float)v[part * lo_slots * 8 + (((size_t)plane * g.Hs + y) * g.Ws + x) * 8 + e] != 0.f) return false;
-          }
+        for (int y = 0; y < h; ++y)
+          memset(&v[part * lo_slots * 8 + (((size_t)plane * g.Hs + y + kRefPad) * g.Ws + kRefPad) * 8], 0xff, (size_t)w * 16);
+  }
+  // everything but the valid area of the first `parts` tensors is still zero after a kernel: the border of all n images,
+  // the slack behind each part, and a lo part the kernel was not asked to write
+  bool outside_is_zero(int parts) const {
+    const size_t tensor = ref16_slots(g, n), hw = (size_t)g.Hs * g.Ws;
+    for (size_t s = 0; s < slots(); ++s) {
+      const size_t part = s / lo_slots, t = s % lo_slots, y = t % hw / g.Ws, x = t % g.Ws;
+      if ((int)part < parts && t < tensor && y >= (size_t)kRefPad && y < (size_t)kRefPad + h && x >= (size_t)kRefPad &&
+          x < (size_t)kRefPad + w)
+        continue;
+      for (int e = 0; e < 8; ++e)
+        if ((float)v[s * 8 + e] != 0.f) return false;
+    }
     return true;
   }
 };
@@ -130,6 +143,46 @@ hipError_t alloc_ref16(DevScope& ds, const RefGeom& g, size_t tensor_and_slack_s
   ds.track(raw);
   return e;
 }
+
+// A device fp16 tower tensor as the pipeline allocates it, [front | tensor | slack] (alloc_ref16), owned by ds; t is its host
+// image (built with slack).
+struct RefDev {
+  uint4* base = nullptr;      // the tensor: what the kernels are handed
+  size_t front = 0;
+  hipError_t alloc(DevScope& ds, const RefHost& t) {
+    front = ref_front(t.g);
+    return alloc_ref16(ds, t.g, t.slots(), &base);
+  }
+  // reads the tensor into t; *ok: the front rows, the border of every image and the slack still hold their zeros
+  hipError_t get(RefHost& t, int parts, bool* ok) const {
+    std::vector<_Float16> f(front * 8);
+    hipError_t e = from_dev(f, base - front);
+    if (e == hipSuccess) e = from_dev(t.v, base);
+    *ok = e == hipSuccess && t.outside_is_zero(parts);
+    for (const _Float16 x : f) *ok = *ok && (float)x == 0.f;
+    return e;
+  }
+};
+#define SN_REF_GET(h, dev, t, parts, what)                                                     \
+  do {                                                                                         \
+    bool ok_ = false;                                                                          \
+    HIP_TRY(h, (dev).get(t, parts, &ok_));                                                     \
+    if (!ok_) {                                                                                \
+      set_err(h, std::string(what) + " wrote outside the valid area (border, front rows or slack)"); \
+      return SN_ERR_DEVICE;                                                                    \
+    }                                                                                          \
+  } while (0)
+
+// The CU count a parity hook sizes its grid with: sn_dbg_set_grid_cus, or the device's.  banded: the launcher builds its grid
+// in XCD bands of 8, so a cap that is no multiple of 8 is refused (launch_down01 would launch nothing).
+int dbg_cus(const sn_handle* h) { return h->dbg_grid_cus > 0 ? h->dbg_grid_cus : h->num_cu; }
+#define SN_DBG_BANDED(h)                                                            \
+  do {                                                                              \
+    if (h->dbg_grid_cus % 8) {                                                      \
+      set_err(h, "this hook's launcher builds its grid in bands of 8: sn_dbg_set_grid_cus needs a multiple of 8"); \
+      return SN_ERR_ARG;                                                            \
+    }                                                                               \
+  } while (0)
 
 // A device output of a mid-stage hook between two guard bands of kGuardBytes known bytes (kGuardByte), owned by ds.  The
 // payload starts as the 0xff pattern (fp32 NaN, int32 -1, fp16 NaN): an element the kernel does not write shows.
@@ -204,10 +257,23 @@ PaddedSlots vol_padded(const VolPad& g, int n) {
 extern "C" {
 
 // ---- parity hooks ----------------------------------------------------------------------------------------
-int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const float* wt, const float* bias,
-                  int k, int stride, int dil, int lrelu, const float* residual, float* out) {
+int sn_dbg_set_grid_cus(sn_handle* h, int cus) {
+  if (!h || cus < 0 || cus > h->num_cu) return SN_ERR_ARG;
+  h->dbg_grid_cus = cus;
+  return SN_OK;
+}
+
+int sn_dbg_last_launch(sn_handle* h, int* wgs, int* units) {
+  if (!h || !wgs || !units) return SN_ERR_ARG;
+  *wgs = h->dbg_launch.wgs;
+  *units = h->dbg_launch.units;
+  return SN_OK;
+}
+
+int sn_dbg_conv2d_n(sn_handle* h, int n, const float* in, int cin, int h_px, int w, const float* wt, const float* bias,
+                    int k, int stride, int dil, int lrelu, const float* residual, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !wt || !bias || !out || cin <= 0 || cin > kC) return SN_ERR_ARG;
+  if (!h || !in || !wt || !bias || !out || cin <= 0 || cin > kC || n <= 0) return SN_ERR_ARG;
   if (!((k == 3 && stride == 1) || (k == 5 && stride == 2 && dil == 1))) return SN_ERR_ARG;
   int rc = check_device(h);
   if (rc) return rc;
@@ -220,6 +286,10 @@ int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const
   lrelu &= 1;
   if (x3 != slots || (x3 && !(cin == kC && dil == 1))) return SN_ERR_ARG;     // the split-operand kernel reads slots
   if (dma && !(slots && (k == 3 || !residual))) return SN_ERR_ARG;
+  if (slots) SN_DBG_BANDED(h);
+  const int ncu = dbg_cus(h);
+  LaunchInfo* const li = &h->dbg_launch;
+  *li = LaunchInfo{};
   ConvLayer L;
   rc = upload_conv2d(h, HostLayer{wt, bias, kC, cin, taps}, slots ? 8 : (k == 5 || cin <= 4) ? 4 : 8, &L);
   if (!rc && slots)
@@ -228,16 +298,17 @@ int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const
   if (rc) return rc;
   hipStream_t st = h->stream;
   if (slots) {          // split-slot tensors in and out through the weights-stationary kernel (fp16 modes' low-res path)
-    std::vector<_Float16> hin, hres, hout((size_t)8 * Ho * Wo * 8);
-    host_to_slots(in, 1, h_px, w, hin);
-    if (residual) host_to_slots(residual, 1, Ho, Wo, hres);
+    std::vector<_Float16> hin, hres, hout((size_t)n * 8 * Ho * Wo * 8);
+    host_to_slots(in, n, h_px, w, hin);
+    if (residual) host_to_slots(residual, n, Ho, Wo, hres);
+    else memset(hout.data(), 0xff, hout.size() * 2);      // an output that is not also an input starts as the 0xff pattern
     if (dma) {      // zero-bordered tensors: k_feat_x3s_dma (3x3; input, output and residual in FeatPad) or k_down_x3s_dma
       const FeatPad fp = feat_pad(h_px, w);
       // (5x5 stride 2: an output grid with a border of its own, 3 pixels of slack)
-      PaddedSlots pin(k == 3 ? SlotGeom{fp.PH, fp.PW, 1, 1} : down_in_geom(Ho, Wo), h_px, w, 8);
-      PaddedSlots pout(k == 3 ? pin.g : SlotGeom{Ho + 5, Wo + 7, 2, 3}, Ho, Wo, 8);
+      PaddedSlots pin(k == 3 ? SlotGeom{fp.PH, fp.PW, 1, 1} : down_in_geom(Ho, Wo), h_px, w, (size_t)n * 8);
+      PaddedSlots pout(k == 3 ? pin.g : SlotGeom{Ho + 5, Wo + 7, 2, 3}, Ho, Wo, (size_t)n * 8);
       pin.put(hin);
-      if (residual) pout.put(hres);
+      pout.put(residual ? hres : hout);
       uint4 *pdin = nullptr, *pdout = nullptr;
       HIP_TRY(h, ds.alloc(&pdin, pin.v.size() / 8));
       HIP_TRY(h, ds.alloc(&pdout, pout.v.size() / 8));
@@ -245,11 +316,11 @@ int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const
       HIP_TRY(h, to_dev(pdout, pout.v));
       HIP_TRY(h, hipDeviceSynchronize());
       if (k == 5)
-        HIP_TRY(h, launch_down_dma(st, L, pdin, 1, Ho, Wo, pdout, pout.g, lrelu != 0, h->num_cu));
+        HIP_TRY(h, launch_down_dma(st, L, pdin, n, Ho, Wo, pdout, pout.g, lrelu != 0, ncu, li));
       else if (residual)
-        HIP_TRY(h, (launch_feat_dma<true, true>(st, L, pdin, fp, 1, pdout, pdout, lrelu != 0, h->num_cu)));     // in place, as the pipeline
+        HIP_TRY(h, (launch_feat_dma<true, true>(st, L, pdin, fp, n, pdout, pdout, lrelu != 0, ncu, li)));     // in place, as the pipeline
       else
-        HIP_TRY(h, (launch_feat_dma<true, false>(st, L, pdin, fp, 1, pdout, nullptr, lrelu != 0, h->num_cu)));
+        HIP_TRY(h, (launch_feat_dma<true, false>(st, L, pdin, fp, n, pdout, nullptr, lrelu != 0, ncu, li)));
       HIP_TRY(h, hipStreamSynchronize(st));
       HIP_TRY(h, from_dev(pout.v, pdout));
       pout.get(hout);
@@ -258,54 +329,65 @@ int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const
         return SN_ERR_DEVICE;
       }
     } else {
-      uint4 *din = nullptr, *dout = nullptr;
+      uint4* din = nullptr;
+      Guarded<uint4> dout;
       HIP_TRY(h, ds.alloc(&din, hin.size() / 8));
-      HIP_TRY(h, ds.alloc(&dout, hout.size() / 8));
+      HIP_TRY(h, dout.alloc(ds, hout.size() / 8));
       HIP_TRY(h, to_dev(din, hin));
-      if (residual) HIP_TRY(h, to_dev(dout, hres));
-      const float* dres = residual ? reinterpret_cast<const float*>(dout) : nullptr;
+      if (residual) HIP_TRY(h, to_dev(dout.p(), hres));
+      HIP_TRY(h, hipDeviceSynchronize());
+      const float* dres = residual ? reinterpret_cast<const float*>(dout.p()) : nullptr;
       SlotIn ls{din, 0, h_px, w};
-      HIP_TRY(h, k == 5 ? (launch_conv_x3s<5, 2, 32, 4, 32, 32, 1, true, SlotIn>(st, L, ls, 1, Ho, Wo, reinterpret_cast<float*>(dout), dres, lrelu != 0, h->num_cu))
-                        : (launch_conv_x3s<3, 1, 32, 8, 16, 16, 2, true, SlotIn>(st, L, ls, 1, Ho, Wo, reinterpret_cast<float*>(dout), dres, lrelu != 0, h->num_cu)));
+      HIP_TRY(h, k == 5 ? (launch_conv_x3s<5, 2, 32, 4, 32, 32, 1, true, SlotIn>(st, L, ls, n, Ho, Wo, reinterpret_cast<float*>(dout.p()), dres, lrelu != 0, ncu, li))
+                        : (launch_conv_x3s<3, 1, 32, 8, 16, 16, 2, true, SlotIn>(st, L, ls, n, Ho, Wo, reinterpret_cast<float*>(dout.p()), dres, lrelu != 0, ncu, li)));
       HIP_TRY(h, hipStreamSynchronize(st));
-      HIP_TRY(h, from_dev(hout, dout));
+      HIP_TRY(h, from_dev(hout, dout.p()));
+      SN_GUARD_CHECK(h, dout, "k_conv_x3s");
     }
-    host_from_slots(hout, 1, Ho, Wo, out);
+    host_from_slots(hout, n, Ho, Wo, out);
     return SN_OK;
   }
-  float *din = nullptr, *dout = nullptr;
-  const size_t nin = (size_t)cin * h_px * w, nout = (size_t)kC * Ho * Wo;
+  float* din = nullptr;
+  Guarded<float> dout;          // starts as the 0xff pattern
+  const size_t nin = (size_t)n * cin * h_px * w, nout = (size_t)n * kC * Ho * Wo;
   HIP_TRY(h, ds.alloc(&din, nin));
-  HIP_TRY(h, ds.alloc(&dout, nout));
+  HIP_TRY(h, dout.alloc(ds, nout));
   HIP_TRY(h, hipMemcpy(din, in, nin * 4, hipMemcpyHostToDevice));
   const float* dres = nullptr;
   if (residual) {   // in-place form, as the pipeline uses it
-    HIP_TRY(h, hipMemcpy(dout, residual, nout * 4, hipMemcpyHostToDevice));
-    dres = dout;
+    HIP_TRY(h, hipMemcpy(dout.p(), residual, nout * 4, hipMemcpyHostToDevice));
+    dres = dout.p();
   }
+  HIP_TRY(h, hipDeviceSynchronize());
   LoadF32 ld{din, cin, h_px, w};
   hipError_t e;
   if (k == 5) {
-    e = (Ho * Wo <= 64 * 128) ? launch_conv<5, 2, 1, 4, 4, 32>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0)
-                              : launch_conv<5, 2, 1, 4, 8, 64>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0);
+    e = (Ho * Wo <= 64 * 128) ? launch_conv<5, 2, 1, 4, 4, 32>(st, L, ld, n, Ho, Wo, dout.p(), dres, lrelu != 0)
+                              : launch_conv<5, 2, 1, 4, 8, 64>(st, L, ld, n, Ho, Wo, dout.p(), dres, lrelu != 0);
   } else if (cin <= 4) {
     if (dil != 1) return SN_ERR_ARG;
-    e = (Ho * Wo <= 64 * 128) ? launch_conv<3, 1, 1, 4, 4, 32>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0)
-                              : launch_conv<3, 1, 1, 4, 8, 64>(st, L, ld, 1, Ho, Wo, dout, dres, lrelu != 0);
+    e = (Ho * Wo <= 64 * 128) ? launch_conv<3, 1, 1, 4, 4, 32>(st, L, ld, n, Ho, Wo, dout.p(), dres, lrelu != 0)
+                              : launch_conv<3, 1, 1, 4, 8, 64>(st, L, ld, n, Ho, Wo, dout.p(), dres, lrelu != 0);
   } else {
     if (tower32 && ((w & 3) != 0 || cin != kC)) return SN_ERR_ARG;
-    e = conv3x3(st, L, din, 1, h_px, w, dil, dout, dres, lrelu != 0, tower32 ? h->num_cu : 0);
+    e = conv3x3(st, L, din, n, h_px, w, dil, dout.p(), dres, lrelu != 0, tower32 ? ncu : 0, li);
   }
   HIP_TRY(h, e);
   HIP_TRY(h, hipStreamSynchronize(st));
-  HIP_TRY(h, hipMemcpy(out, dout, nout * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(out, dout.p(), nout * 4, hipMemcpyDeviceToHost));
+  SN_GUARD_CHECK(h, dout, "the fp32 convolution");
   return SN_OK;
 }
 
-int sn_dbg_down0(sn_handle* h, const int8_t* in6, int h_px, int w, const float* wt, const float* bias, int tc,
-                 float* out) {
+int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const float* wt, const float* bias,
+                  int k, int stride, int dil, int lrelu, const float* residual, float* out) {
+  return sn_dbg_conv2d_n(h, 1, in, cin, h_px, w, wt, bias, k, stride, dil, lrelu, residual, out);
+}
+
+int sn_dbg_down0_n(sn_handle* h, int n, const int8_t* in6, int h_px, int w, const float* wt, const float* bias, int tc,
+                   float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in6 || !wt || !bias || !out || h_px <= 0 || w <= 0 || tc != 32) return SN_ERR_ARG;
+  if (!h || !in6 || !wt || !bias || !out || h_px <= 0 || w <= 0 || tc != 32 || n <= 0) return SN_ERR_ARG;
   int rc = check_device(h);
   if (rc) return rc;
   const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16, Ho = Hp / 2, Wo = Wp / 2;
@@ -315,18 +397,24 @@ int sn_dbg_down0(sn_handle* h, const int8_t* in6, int h_px, int w, const float* 
   if (rc) return rc;
   int8_t* din = nullptr;
   float *dout = nullptr, *dbias = nullptr;
-  const size_t nin = (size_t)6 * h_px * w, nout = (size_t)2 * kC * Ho * Wo;     // split slots: same bytes as fp32
+  const size_t nin = (size_t)n * 6 * h_px * w, nout = (size_t)n * 2 * kC * Ho * Wo;     // split slots: same bytes as fp32
   HIP_TRY(h, ds.alloc(&din, nin));
   HIP_TRY(h, ds.alloc(&dout, nout));
   HIP_TRY(h, ds.alloc(&dbias, kC));
   HIP_TRY(h, hipMemcpy(din, in6, nin, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(dbias, bias, kC * 4, hipMemcpyHostToDevice));
-  HIP_TRY(h, launch_down0_f16(h->stream, L, dbias, din, h_px, w, 2, Ho, Wo, dout, h->num_cu));   // the pipeline's kernel
+  HIP_TRY(h, memset_now(dout, 0xff, nout * 4));       // an element the kernel does not write reads back as NaN
+  HIP_TRY(h, launch_down0_f16(h->stream, L, dbias, din, h_px, w, 2 * n, Ho, Wo, dout, dbg_cus(h), nullptr, &h->dbg_launch));   // the pipeline's kernel
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   std::vector<_Float16> hs(nout * 2);
   HIP_TRY(h, from_dev(hs, dout));
-  host_from_slots(hs, 2, Ho, Wo, out);
+  host_from_slots(hs, 2 * n, Ho, Wo, out);
   return SN_OK;
+}
+
+int sn_dbg_down0(sn_handle* h, const int8_t* in6, int h_px, int w, const float* wt, const float* bias, int tc,
+                 float* out) {
+  return sn_dbg_down0_n(h, 1, in6, h_px, w, wt, bias, tc, out);
 }
 
 int sn_dbg_round_kernels_f16(const float* w, int nkernels, float* out) {
@@ -348,10 +436,11 @@ int sn_dbg_compose_down01(const float* w0, const float* b0, const float* w1, con
   return SN_OK;
 }
 
-int sn_dbg_down01(sn_handle* h, const int8_t* in6, int h_px, int w, const float* w0, const float* b0, const float* w1,
-                  const float* b1, float* out) {
+int sn_dbg_down01_n(sn_handle* h, int n, const int8_t* in6, int h_px, int w, const float* w0, const float* b0, const float* w1,
+                    const float* b1, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in6 || !w0 || !b0 || !w1 || !b1 || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  if (!h || !in6 || !w0 || !b0 || !w1 || !b1 || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
+  SN_DBG_BANDED(h);
   int rc = check_device(h);
   if (rc) return rc;
   const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16, Ho = Hp / 4, Wo = Wp / 4;
@@ -361,51 +450,62 @@ int sn_dbg_down01(sn_handle* h, const int8_t* in6, int h_px, int w, const float*
   if (rc) return rc;
   int8_t* din = nullptr;
   uint4* dout = nullptr;
-  const size_t nin = (size_t)6 * h_px * w, nout = (size_t)2 * kC * Ho * Wo;     // split slots: same bytes as fp32
+  const size_t nin = (size_t)n * 6 * h_px * w, nout = (size_t)n * 2 * kC * Ho * Wo;     // split slots: same bytes as fp32
   HIP_TRY(h, ds.alloc(&din, nin));
   HIP_TRY(h, ds.alloc(&dout, nout / 4));
   HIP_TRY(h, hipMemcpy(din, in6, nin, hipMemcpyHostToDevice));
-  HIP_TRY(h, launch_down01(h->stream, L, din, h_px, w, 2, Ho, Wo, dout, SlotGeom{Ho, Wo, 0, 0}, h->num_cu));   // the pipeline's kernels
+  HIP_TRY(h, memset_now(dout, 0xff, nout * 4));       // an element neither kernel writes reads back as NaN
+  HIP_TRY(h, launch_down01(h->stream, L, din, h_px, w, 2 * n, Ho, Wo, dout, SlotGeom{Ho, Wo, 0, 0}, dbg_cus(h), &h->dbg_launch));   // the pipeline's kernels
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   std::vector<_Float16> hs(nout * 2);
   HIP_TRY(h, from_dev(hs, dout));
-  host_from_slots(hs, 2, Ho, Wo, out);
+  host_from_slots(hs, 2 * n, Ho, Wo, out);
   return SN_OK;
 }
 
-int sn_dbg_refin(sn_handle* h, const float* disp_low, const int8_t* in6, int h_px, int w, int dmax, const float* wt,
-                 const float* bias, int split, float* out) {
+int sn_dbg_down01(sn_handle* h, const int8_t* in6, int h_px, int w, const float* w0, const float* b0, const float* w1,
+                  const float* b1, float* out) {
+  return sn_dbg_down01_n(h, 1, in6, h_px, w, w0, b0, w1, b1, out);
+}
+
+int sn_dbg_refin_n(sn_handle* h, int n, const float* disp_low, const int8_t* in6, int h_px, int w, int dmax, const float* wt,
+                   const float* bias, int split, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !disp_low || !in6 || !wt || !bias || !out || h_px <= 0 || w <= 0 || dmax <= 0) return SN_ERR_ARG;
+  if (!h || !disp_low || !in6 || !wt || !bias || !out || h_px <= 0 || w <= 0 || dmax <= 0 || n <= 0) return SN_ERR_ARG;
   int rc = check_device(h);
   if (rc) return rc;
   const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16, hl = Hp / 16, wl = Wp / 16;
-  RefHost t(make_ref_geom(Hp, Wp), 1, Hp, Wp, true, true);      // [hi | slack | lo | slack] whatever `split` says
+  RefHost t(make_ref_geom(Hp, Wp), n, Hp, Wp, true, true);      // [hi | slack | lo | slack] whatever `split` says
   Down0F16 L;
   rc = upload_refin_f16(h, HostLayer{wt, bias, kC, 4, 9}, &L);
   ds.adopt(L);
   if (rc) return rc;
   float *ddl = nullptr, *dbias = nullptr;
   int8_t* din = nullptr;
-  uint4* dout = nullptr;
-  HIP_TRY(h, ds.alloc(&ddl, (size_t)hl * wl));
+  RefDev dout;
+  const int parts = split ? 2 : 1;
+  HIP_TRY(h, ds.alloc(&ddl, (size_t)n * hl * wl));
   HIP_TRY(h, ds.alloc(&dbias, kC));
-  HIP_TRY(h, ds.alloc(&din, (size_t)6 * h_px * w));
-  HIP_TRY(h, ds.alloc(&dout, t.slots()));
-  HIP_TRY(h, hipMemcpy(ddl, disp_low, (size_t)hl * wl * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, ds.alloc(&din, (size_t)n * 6 * h_px * w));
+  HIP_TRY(h, dout.alloc(ds, t));
+  HIP_TRY(h, hipMemcpy(ddl, disp_low, (size_t)n * hl * wl * 4, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(dbias, bias, kC * 4, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(din, in6, (size_t)6 * h_px * w, hipMemcpyHostToDevice));
-  HIP_TRY(h, memset_now(dout, 0, t.slots() * 16));
+  HIP_TRY(h, hipMemcpy(din, in6, (size_t)n * 6 * h_px * w, hipMemcpyHostToDevice));
+  t.prefill(parts);
+  HIP_TRY(h, to_dev(dout.base, t.v));
+  HIP_TRY(h, hipDeviceSynchronize());
   HIP_TRY(h, launch_refin_f16(h->stream, L, dbias, ddl, din, false, hl, wl, h_px, w, 1.0f / (float)dmax,
-                              UpScale{1.0f / 16.0f, 16.0f}, t.g, 1, dout, split != 0, t.lo_slots * 16, h->num_cu));
+                              UpScale{1.0f / 16.0f, 16.0f}, t.g, n, dout.base, split != 0, t.lo_slots * 16, dbg_cus(h),
+                              &h->dbg_launch));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, from_dev(t.v, dout));
+  SN_REF_GET(h, dout, t, parts, "ref.in");
   t.unpack(out, split != 0);
-  if (!t.border_is_zero(1)) {
-    set_err(h, "ref.in wrote into the zero border");
-    return SN_ERR_DEVICE;
-  }
   return SN_OK;
+}
+
+int sn_dbg_refin(sn_handle* h, const float* disp_low, const int8_t* in6, int h_px, int w, int dmax, const float* wt,
+                 const float* bias, int split, float* out) {
+  return sn_dbg_refin_n(h, 1, disp_low, in6, h_px, w, dmax, wt, bias, split, out);
 }
 
 int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const float* wt, const float* bias,
@@ -417,6 +517,8 @@ int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const f
   const bool x3 = (lrelu & 2) != 0, slots = (lrelu & 4) != 0, dma = (lrelu & 8) != 0;   // dma: zero-bordered volumes
   lrelu &= 1;
   if (slots != x3 || (dma && !slots)) return SN_ERR_ARG;        // the split-operand kernels read split-slot volumes
+  if (slots) SN_DBG_BANDED(h);
+  h->dbg_launch = LaunchInfo{};
   ConvLayer L;
   rc = upload_conv3d(h, HostLayer{wt, bias, kC, kC, 27}, &L);
   if (!rc && x3)
@@ -439,12 +541,15 @@ int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const f
       const VolPad g = vol_pad(d, h_px, w);
       PaddedSlots pin(SlotGeom{g.PH, g.PW, 1, 1}, h_px, w, (size_t)d * 8, 8), pout = pin;
       pin.put(hs);
+      memset(ho.data(), 0xff, ho.size() * 2);
+      pout.put(ho);                                // 0xff inside the images, zeros everywhere else
       uint4 *pdin = nullptr, *pdout = nullptr;
       HIP_TRY(h, ds.alloc(&pdin, pin.v.size() / 8));
       HIP_TRY(h, ds.alloc(&pdout, pout.v.size() / 8));
       HIP_TRY(h, to_dev(pdin, pin.v));
-      HIP_TRY(h, memset_now(pdout, 0, pout.v.size() * 2));
-      HIP_TRY(h, launch_agg_dma<true>(h->stream, L, pdin, g, 1, pdout, lrelu != 0, h->num_cu));
+      HIP_TRY(h, to_dev(pdout, pout.v));
+      HIP_TRY(h, hipDeviceSynchronize());
+      HIP_TRY(h, launch_agg_dma<true>(h->stream, L, pdin, g, 1, pdout, lrelu != 0, dbg_cus(h), nullptr, &h->dbg_launch));
       HIP_TRY(h, hipStreamSynchronize(h->stream));
       HIP_TRY(h, from_dev(pout.v, pdout));
       pout.get(ho);
@@ -455,7 +560,8 @@ int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const f
     } else {
       HIP_TRY(h, to_dev(din, hs));
       SlotIn ls{reinterpret_cast<const uint4*>(din), d, h_px, w};
-      HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, true, SlotIn>(h->stream, L, ls, d, h_px, w, dout, nullptr, lrelu != 0, h->num_cu)));
+      HIP_TRY(h, memset_now(dout, 0xff, n * 4));
+      HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, true, SlotIn>(h->stream, L, ls, d, h_px, w, dout, nullptr, lrelu != 0, dbg_cus(h), &h->dbg_launch)));
       HIP_TRY(h, hipStreamSynchronize(h->stream));
       HIP_TRY(h, from_dev(ho, dout));
     }
@@ -473,29 +579,27 @@ int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const f
   return SN_OK;
 }
 
-int sn_dbg_ref_conv_f16(sn_handle* h, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
-                        int lrelu, const float* residual, float* out) {
+int sn_dbg_ref_conv_f16_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
+                          int lrelu, const float* residual, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
   if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
+  SN_DBG_BANDED(h);
   int rc = check_device(h);
   if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, false, false);
+  RefHost t(make_ref_geom(h_px, w), n, h_px, w, false, true);
   RefLayerF16 L;
   rc = upload_ref_f16(h, HostLayer{wt, bias, kC, kC, 9}, switches_at_create().w_round_sum_preserving, &L);
   ds.adopt(L);
   if (rc) return rc;
-  uint4 *din = nullptr, *dout = nullptr;
-  HIP_TRY(h, ds.alloc(&din, t.slots()));
-  HIP_TRY(h, ds.alloc(&dout, t.slots()));
+  RefDev din, dout;
+  HIP_TRY(h, din.alloc(ds, t));
+  HIP_TRY(h, dout.alloc(ds, t));
   t.pack(in, false);
-  HIP_TRY(h, to_dev(din, t.v));
-  if (residual) {
-    t.pack(residual, false);
-    HIP_TRY(h, to_dev(dout, t.v));
-  } else {
-    HIP_TRY(h, memset_now(dout, 0, t.slots() * 16));
-  }
+  HIP_TRY(h, to_dev(din.base, t.v));
+  if (residual) t.pack(residual, false);      // added in place, as the pipeline does
+  else t.prefill(1);
+  HIP_TRY(h, to_dev(dout.base, t.v));
   unsigned* ctr = h->ws.tile_ctr;
   if (!ctr) {
     set_err(h, "sn_dbg_ref_conv_f16 needs an engine created in an fp16 mode");
@@ -503,88 +607,98 @@ int sn_dbg_ref_conv_f16(sn_handle* h, const float* in, int h_px, int w, const fl
   }
   HIP_TRY(h, hipMemsetAsync(ctr, 0, kTileCtrBytes, h->stream));
   // lrelu bits 1 / 2: force the 8x64 / 8x32 tile variant of the dilation-1 / -2 kernels (default: chosen per launch)
-  HIP_TRY(h, ref_conv_f16(h->stream, L, t.g, h->num_cu, dil, din, dout, residual ? dout : nullptr, 1, (lrelu & 1) != 0, ctr,
-                          (lrelu & 2) ? 64 : (lrelu & 4) ? 32 : 0));
+  HIP_TRY(h, ref_conv_f16(h->stream, L, t.g, dbg_cus(h), dil, din.base, dout.base, residual ? dout.base : nullptr, n, (lrelu & 1) != 0,
+                          ctr, (lrelu & 2) ? 64 : (lrelu & 4) ? 32 : 0, &h->dbg_launch));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, from_dev(t.v, dout));
+  SN_REF_GET(h, dout, t, 1, "the fp16 conv");      // the kernel never writes outside the valid area
   t.unpack(out, false);
-  if (!t.border_is_zero(1)) {      // the kernel never writes outside the valid area
-    set_err(h, "fp16 conv wrote into the zero border");
-    return SN_ERR_DEVICE;
-  }
+  return SN_OK;
+}
+
+int sn_dbg_ref_conv_f16(sn_handle* h, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
+                        int lrelu, const float* residual, float* out) {
+  return sn_dbg_ref_conv_f16_n(h, 1, in, h_px, w, wt, bias, dil, lrelu, residual, out);
+}
+
+int sn_dbg_ref_conv_f16x3_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
+                            int lrelu, const float* residual, float* out) {
+  DevScope ds;      // frees every tracked device buffer on every return path
+  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
+  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
+  SN_DBG_BANDED(h);
+  int rc = check_device(h);
+  if (rc) return rc;
+  RefHost t(make_ref_geom(h_px, w), n, h_px, w, true, true);      // [hi | slack | lo | slack]
+  RefLayerF16 L;
+  rc = upload_ref_f16x3(h, HostLayer{wt, bias, kC, kC, 9}, &L);
+  ds.adopt(L);
+  if (rc) return rc;
+  RefDev din, dout;
+  HIP_TRY(h, din.alloc(ds, t));
+  HIP_TRY(h, dout.alloc(ds, t));
+  t.pack(in, true);
+  HIP_TRY(h, to_dev(din.base, t.v));
+  if (residual) t.pack(residual, true);
+  else t.prefill(2);
+  HIP_TRY(h, to_dev(dout.base, t.v));
+  HIP_TRY(h, hipDeviceSynchronize());
+  HIP_TRY(h, ref_conv_f16x3(h->stream, L, t.g, dbg_cus(h), dil, din.base, dout.base, residual ? dout.base : nullptr, t.lo_slots, n,
+                            lrelu != 0, &h->dbg_launch));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  SN_REF_GET(h, dout, t, 2, "the f16x3 conv");
+  t.unpack(out, true);
   return SN_OK;
 }
 
 int sn_dbg_ref_conv_f16x3(sn_handle* h, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
                           int lrelu, const float* residual, float* out) {
-  DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
-  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
-  int rc = check_device(h);
-  if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, true, true);      // [hi | slack | lo | slack]
-  RefLayerF16 L;
-  rc = upload_ref_f16x3(h, HostLayer{wt, bias, kC, kC, 9}, &L);
-  ds.adopt(L);
-  if (rc) return rc;
-  uint4 *din = nullptr, *dout = nullptr;
-  HIP_TRY(h, ds.alloc(&din, t.slots()));
-  HIP_TRY(h, ds.alloc(&dout, t.slots()));
-  t.pack(in, true);
-  HIP_TRY(h, to_dev(din, t.v));
-  if (residual) {
-    t.pack(residual, true);
-    HIP_TRY(h, to_dev(dout, t.v));
-  } else {
-    HIP_TRY(h, memset_now(dout, 0, t.slots() * 16));
-  }
-  HIP_TRY(h, ref_conv_f16x3(h->stream, L, t.g, h->num_cu, dil, din, dout, residual ? dout : nullptr, t.lo_slots, 1, lrelu != 0));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, from_dev(t.v, dout));
-  t.unpack(out, true);
-  if (!t.border_is_zero(2)) {
-    set_err(h, "f16x3 conv wrote into the zero border");
-    return SN_ERR_DEVICE;
-  }
-  return SN_OK;
+  return sn_dbg_ref_conv_f16x3_n(h, 1, in, h_px, w, wt, bias, dil, lrelu, residual, out);
 }
 
-int sn_dbg_ref_block_f16x3(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1, const float* w2,
-                           const float* b2, int dil, int form, float* out) {
+int sn_dbg_ref_block_f16x3_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* w1, const float* b1,
+                             const float* w2, const float* b2, int dil, int form, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
   if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
   if (form != 0 && form != 1) return SN_ERR_ARG;            // 0 = two k_ref_conv_f16x3 launches, 1 = the streamed block
   if (form == 1 && !stream_x3_supports(dil)) return SN_ERR_ARG;
+  if (form == 0) SN_DBG_BANDED(h);
   int rc = check_device(h);
   if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, true, true);      // [hi | slack | lo | slack]
+  RefHost t(make_ref_geom(h_px, w), n, h_px, w, true, true);      // [hi | slack | lo | slack]
   RefLayerF16 L1, L2;
   rc = upload_ref_f16x3(h, HostLayer{w1, b1, kC, kC, 9}, &L1);
   if (!rc) rc = upload_ref_f16x3(h, HostLayer{w2, b2, kC, kC, 9}, &L2);
   ds.adopt(L1);
   ds.adopt(L2);
   if (rc) return rc;
-  uint4 *cur = nullptr, *oth = nullptr;
-  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots(), &cur));
-  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots(), &oth));
+  RefDev a, b;
+  HIP_TRY(h, a.alloc(ds, t));
+  HIP_TRY(h, b.alloc(ds, t));
+  t.prefill(2);       // the other tensor (the streamed block's output, the two launches' intermediate) is never an input first
+  HIP_TRY(h, to_dev(b.base, t.v));
   t.pack(in, true);
-  HIP_TRY(h, to_dev(cur, t.v));
-  HIP_TRY(h, ref_block_f16x3(h->stream, L1, L2, t.g, h->num_cu, dil, &cur, &oth, t.lo_slots, 1, form == 1));
+  HIP_TRY(h, to_dev(a.base, t.v));
+  HIP_TRY(h, hipDeviceSynchronize());
+  uint4 *cur = a.base, *oth = b.base;
+  HIP_TRY(h, ref_block_f16x3(h->stream, L1, L2, t.g, dbg_cus(h), dil, &cur, &oth, t.lo_slots, n, form == 1, &h->dbg_launch));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, from_dev(t.v, cur));
+  RefHost u = t;
+  SN_REF_GET(h, (cur == a.base ? b : a), u, 2, "the f16x3 residual block (its other tensor)");
+  SN_REF_GET(h, (cur == a.base ? a : b), t, 2, "the f16x3 residual block");
   t.unpack(out, true);
-  if (!t.border_is_zero(2)) {
-    set_err(h, "f16x3 residual block wrote into the zero border");
-    return SN_ERR_DEVICE;
-  }
   return SN_OK;
 }
 
-int sn_dbg_ref_block_f16(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1,
-                         const float* w2, const float* b2, int dil, float* out) {
+int sn_dbg_ref_block_f16x3(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1, const float* w2,
+                           const float* b2, int dil, int form, float* out) {
+  return sn_dbg_ref_block_f16x3_n(h, 1, in, h_px, w, w1, b1, w2, b2, dil, form, out);
+}
+
+int sn_dbg_ref_block_f16_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* w1, const float* b1,
+                           const float* w2, const float* b2, int dil, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0) return SN_ERR_ARG;
+  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
   // tests: bits 8.. select the form: 0 = two launches, 2 = row-streaming fused kernel (1 was the tile-fused kernel of round 2)
   const int form = dil >> 8;
   if (form != 0 && form != 2) return SN_ERR_ARG;
@@ -592,9 +706,10 @@ int sn_dbg_ref_block_f16(sn_handle* h, const float* in, int h_px, int w, const f
   dil &= 0xff;
   if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
   if (fuse_mode == 4 && !stream_block_supports(dil)) return SN_ERR_ARG;
+  if (form == 0) SN_DBG_BANDED(h);
   int rc = check_device(h);
   if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), 1, h_px, w, false, false);
+  RefHost t(make_ref_geom(h_px, w), n, h_px, w, false, true);
   const bool sp = switches_at_create().w_round_sum_preserving;
   RefLayerF16 L1, L2;
   rc = upload_ref_f16(h, HostLayer{w1, b1, kC, kC, 9}, sp, &L1);
@@ -602,25 +717,32 @@ int sn_dbg_ref_block_f16(sn_handle* h, const float* in, int h_px, int w, const f
   ds.adopt(L1);
   ds.adopt(L2);
   if (rc) return rc;
-  uint4 *cur = nullptr, *oth = nullptr;
-  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots() + ref_slack(t.g), &cur));
-  HIP_TRY(h, alloc_ref16(ds, t.g, t.slots() + ref_slack(t.g), &oth));
+  RefDev a, b;
+  HIP_TRY(h, a.alloc(ds, t));
+  HIP_TRY(h, b.alloc(ds, t));
+  t.prefill(1);       // the other tensor (the streamed block's output, the two launches' intermediate) is never an input first
+  HIP_TRY(h, to_dev(b.base, t.v));
   t.pack(in, false);
-  HIP_TRY(h, to_dev(cur, t.v));
+  HIP_TRY(h, to_dev(a.base, t.v));
   if (!h->ws.tile_ctr) {
     set_err(h, "sn_dbg_ref_block_f16 needs an engine created in an fp16 mode");
     return SN_ERR_ARG;
   }
   HIP_TRY(h, hipMemsetAsync(h->ws.tile_ctr, 0, kTileCtrBytes, h->stream));
-  HIP_TRY(h, ref_block_f16(h->stream, L1, L2, t.g, h->num_cu, dil, &cur, &oth, 1, h->ws.tile_ctr, fuse_mode, h->dump));
+  uint4 *cur = a.base, *oth = b.base;
+  HIP_TRY(h, ref_block_f16(h->stream, L1, L2, t.g, dbg_cus(h), dil, &cur, &oth, n, h->ws.tile_ctr, fuse_mode, h->dump, false,
+                           &h->dbg_launch));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, from_dev(t.v, cur));
+  RefHost u = t;
+  SN_REF_GET(h, (cur == a.base ? b : a), u, 1, "the fp16 residual block (its other tensor)");
+  SN_REF_GET(h, (cur == a.base ? a : b), t, 1, "the fp16 residual block");
   t.unpack(out, false);
-  if (!t.border_is_zero(1)) {      // the zero border of the result tensor
-    set_err(h, "fp16 residual block wrote into the zero border");
-    return SN_ERR_DEVICE;
-  }
   return SN_OK;
+}
+
+int sn_dbg_ref_block_f16(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1,
+                         const float* w2, const float* b2, int dil, float* out) {
+  return sn_dbg_ref_block_f16_n(h, 1, in, h_px, w, w1, b1, w2, b2, dil, out);
 }
 
 int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, const float* w1, const float* b1, const float* w2,
@@ -639,8 +761,7 @@ int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, co
   if (rc) return rc;
   const RefGeom g = make_ref_geom(hk, wk);
   if ((ref16_slots(g, n) + ref_slack(g) + ref_front(g)) * 16 >= ((size_t)1 << 32)) return SN_ERR_ARG;      // 32-bit byte offsets inside a tensor
-  RefHost t(g, n, hk, wk, false, false);
-  t.pack(in, false);
+  RefHost t(g, n, hk, wk, false, true);
   const bool sp = switches_at_create().w_round_sum_preserving;
   RefLayerF16 L1, L2;
   HeadLayer hd;
@@ -651,10 +772,14 @@ int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, co
   ds.adopt(L2);
   ds.adopt(hd);
   if (rc) return rc;
-  uint4 *da = nullptr, *db = nullptr;
-  HIP_TRY(h, alloc_ref16(ds, g, t.slots() + ref_slack(g), &da));
-  HIP_TRY(h, alloc_ref16(ds, g, t.slots() + ref_slack(g), &db));
-  HIP_TRY(h, to_dev(da, t.v));
+  RefDev ta, tb;
+  HIP_TRY(h, ta.alloc(ds, t));
+  HIP_TRY(h, tb.alloc(ds, t));
+  t.prefill(1);        // y: written by form 0 only
+  HIP_TRY(h, to_dev(tb.base, t.v));
+  t.pack(in, false);
+  HIP_TRY(h, to_dev(ta.base, t.v));
+  uint4 *const da = ta.base, *const db = tb.base;
   const int sh = hk / ups, sw = wk / ups;
   const size_t nlow = (size_t)n * sh * sw, nout = (size_t)n * h_out * w_out;
   float *dlow = nullptr, *dd = nullptr;
@@ -669,14 +794,16 @@ int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, co
   const UpScale us{1.0f / (float)ups, (float)ups};
   const HeadArgs ha{hd.w, dlow, dd, dr, hd.bias, dnorm, inv_q, sh, sw, h_out, w_out, us};
   if (form == 1) {
-    HIP_TRY(h, ref_block_stream_tail(h->stream, L1, L2, g, h->num_cu, da, n, h->dump, ha));
+    HIP_TRY(h, ref_block_stream_tail(h->stream, L1, L2, g, dbg_cus(h), da, n, h->dump, ha, &h->dbg_launch));
   } else {
-    HIP_TRY(h, ref_block_stream(h->stream, L1, L2, g, h->num_cu, 1, da, db, n, h->dump));
+    HIP_TRY(h, ref_block_stream(h->stream, L1, L2, g, dbg_cus(h), 1, da, db, n, h->dump, &h->dbg_launch));
     HIP_TRY(h, launch_head_final_f16(h->stream, false, db, 0, g, n, ha));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   HIP_TRY(h, hipMemcpy(out_disp, dd, nout * 4, hipMemcpyDeviceToHost));
   HIP_TRY(h, hipMemcpy(out_raw, dr, nout * 4, hipMemcpyDeviceToHost));
+  SN_REF_GET(h, ta, t, 1, "the tail (its input tensor)");
+  SN_REF_GET(h, tb, t, 1, form == 1 ? "the tail form (the tensor it must not write)" : "the streamed block in front of the head");
   return SN_OK;
 }
 
@@ -787,6 +914,7 @@ int sn_dbg_agg_tail(sn_handle* h, const float* vol, int n, int Dl, int hl, int w
   if (!h || !vol || !wt || !bias || !out_w || !cost || !disp_low || !nonfinite || n <= 0 || Dl <= 0 || Dl > 16 || hl <= 0 ||
       wl <= 0 || form < 0 || form > 2 || (want_conf && !conf_low) || (form == 2 && layer_vol))
     return SN_ERR_ARG;
+  SN_DBG_BANDED(h);
   int rc = check_device(h);
   if (rc) return rc;
   ConvLayer L;
@@ -817,7 +945,7 @@ int sn_dbg_agg_tail(sn_handle* h, const float* vol, int n, int Dl, int hl, int w
     HIP_TRY(h, to_dev(din, hs));
     HIP_TRY(h, hipDeviceSynchronize());
     SlotIn ls{din, Dl, hl, wl};
-    HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, false, SlotIn>(h->stream, L, ls, n * Dl, hl, wl, dmid.p(), nullptr, true, h->num_cu)));
+    HIP_TRY(h, (launch_conv_x3s<3, 1, 96, 8, 16, 16, 1, false, SlotIn>(h->stream, L, ls, n * Dl, hl, wl, dmid.p(), nullptr, true, dbg_cus(h))));
   } else {
     const VolPad g = vol_pad(Dl, hl, wl);
     PaddedSlots pin = vol_padded(g, n);
@@ -826,9 +954,9 @@ int sn_dbg_agg_tail(sn_handle* h, const float* vol, int n, int Dl, int hl, int w
     HIP_TRY(h, to_dev(din, pin.v));
     HIP_TRY(h, hipDeviceSynchronize());
     if (form == 1)
-      HIP_TRY(h, launch_agg_dma<false>(h->stream, L, din, g, n, dmid.p(), true, h->num_cu));
+      HIP_TRY(h, launch_agg_dma<false>(h->stream, L, din, g, n, dmid.p(), true, dbg_cus(h)));
     else
-      HIP_TRY(h, (launch_agg_dma<false, true>(h->stream, L, din, g, n, dmid.p(), true, h->num_cu, hd.pfrag)));
+      HIP_TRY(h, (launch_agg_dma<false, true>(h->stream, L, din, g, n, dmid.p(), true, dbg_cus(h), hd.pfrag)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, from_dev(pin.v, din));
     if (!pin.outside_is_zero()) {      // the padded volume is this layer's input only: its borders still hold the zeros

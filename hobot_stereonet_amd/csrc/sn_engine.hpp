@@ -206,6 +206,12 @@ struct AutoCtl {
   uint64_t calls = 0, pairs = 0, reruns = 0;
 };
 
+// What a persistent launcher launched: workgroups and work units (tiles; half tiles for k_ref_conv_f32; flat rows for the
+// streamed blocks).  Optional out-parameter of the launchers (sn_launch.hpp), read by the parity hooks only.
+struct LaunchInfo {
+  int wgs = 0, units = 0;
+};
+
 }  // namespace
 
 struct sn_handle {
@@ -247,6 +253,10 @@ struct sn_handle {
   int levels = 1;
   Tower tw[kMaxLevels];
   int num_cu = 256;
+  // parity hooks only (sn_dbg_set_grid_cus, sn_dbg_last_launch): the CU count the sn_dbg_* hooks size their grids with
+  // (0 = num_cu) and what the last swept launch reported.  The forward pass reads neither.
+  int dbg_grid_cus = 0;
+  LaunchInfo dbg_launch;
   Workspace ws;
   std::vector<Slot> slots;
   std::mutex mu;

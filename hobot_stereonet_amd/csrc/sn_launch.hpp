@@ -45,6 +45,11 @@ inline ConvArgs make_conv_args(const ConvLayer& L, const void* w, void* out, con
   return a;
 }
 
+// the launchers' optional report (LaunchInfo, sn_engine.hpp)
+inline void report(LaunchInfo* li, int wgs, int units) {
+  if (li) *li = LaunchInfo{wgs, units};
+}
+
 // Persistent grid of at most `cap` workgroups over `total` tiles, a multiple of 8: one band of tiles per XCD.
 inline int xcd_band_grid(int cap, int total) {
   const int need = (total + 7) / 8 * 8;
@@ -55,13 +60,15 @@ inline int xcd_band_grid(int cap, int total) {
 template <int TW>
 hipError_t launch_refin_f16_tw(hipStream_t st, const Down0F16& L, const float* bias, const float* disp_low,
                                const void* img_src, bool pyr, int hl, int wl, int H, int W, float inv_d, UpScale ups,
-                               RefGeom g, int nimg, uint4* out, bool split, size_t lo_off_bytes, int num_cu) {
+                               RefGeom g, int nimg, uint4* out, bool split, size_t lo_off_bytes, int num_cu,
+                               LaunchInfo* li = nullptr) {
   using T = RefInTile<TW>;
   g.tiles_x = (g.W + TW - 1) / TW;
   g.tiles_y = (g.H + T::TH - 1) / T::TH;
   const int total = g.tiles_x * g.tiles_y * nimg;
   int blocks = 2 * num_cu;
   if (blocks > total) blocks = total;
+  report(li, blocks, total);
   const int al4 = !pyr && (W % 4 == 0) && (reinterpret_cast<uintptr_t>(img_src) % 4 == 0);
 #define SN_REFIN(S, P)                                                                                             \
   hipLaunchKernelGGL((k_refin_f16<S, P, TW>), dim3(blocks), dim3(256), T::LDS_BYTES, st, disp_low, img_src, hl, wl, H, \
@@ -78,19 +85,22 @@ hipError_t launch_refin_f16_tw(hipStream_t st, const Down0F16& L, const float* b
 // against 41.5 us per two pairs at 1280x720 — only 100 of the 256 threads have a staging unit then.)
 hipError_t launch_refin_f16(hipStream_t st, const Down0F16& L, const float* bias, const float* disp_low,
                             const void* img_src, bool pyr, int hl, int wl, int H, int W, float inv_d, UpScale ups,
-                            const RefGeom& g, int nimg, uint4* out, bool split, size_t lo_off_bytes, int num_cu) {
+                            const RefGeom& g, int nimg, uint4* out, bool split, size_t lo_off_bytes, int num_cu,
+                            LaunchInfo* li = nullptr) {
   return launch_refin_f16_tw<64>(st, L, bias, disp_low, img_src, pyr, hl, wl, H, W, inv_d, ups, g, nimg, out, split,
-                                 lo_off_bytes, num_cu);
+                                 lo_off_bytes, num_cu, li);
 }
 
 hipError_t launch_down0_f16(hipStream_t st, const Down0F16& L, const float* bias, const int8_t* in6, int H, int W,
-                            int nimg, int Ho, int Wo, float* out, int num_cu, const SlotGeom* og = nullptr) {
+                            int nimg, int Ho, int Wo, float* out, int num_cu, const SlotGeom* og = nullptr,
+                            LaunchInfo* li = nullptr) {
   constexpr int TC = 32;
   using T = Down0Tile<TC>;
   const int tiles_x = (Wo + TC - 1) / TC, tiles_y = (Ho + T::TR - 1) / T::TR;
   const int total = tiles_x * tiles_y * nimg;
   int blocks = 2 * num_cu;                        // register budget: two workgroups per CU
   if (blocks > total) blocks = total;
+  report(li, blocks, total);
   const int al4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(in6) % 4 == 0);
   hipLaunchKernelGGL((k_down0_f16<TC>), dim3(blocks), dim3(256), T::LDS_BYTES, st, in6, H, W, L.wfrag, bias, out, Ho, Wo,
                      tiles_x, tiles_y, nimg, 0, al4, og ? og->PH : Ho, og ? og->PW : Wo, og ? og->py : 0, og ? og->px : 0);
@@ -101,7 +111,7 @@ hipError_t launch_down0_f16(hipStream_t st, const Down0F16& L, const float* bias
 // (W4: dword loads at any byte address — the int8 planes need no alignment, only W % 4 decides which instance runs)
 template <bool W4>
 hipError_t launch_down01_w(hipStream_t st, const Down01W& L, const int8_t* in6, int H, int W, int nimg, int Ho, int Wo,
-                           uint4* out, const SlotGeom& og, int num_cu) {
+                           uint4* out, const SlotGeom& og, int num_cu, LaunchInfo* li = nullptr) {
   using T = Down01;
   hipError_t e = ensure_lds_attr(k_down01_f16<W4>, T::LDS_BYTES);
   if (e != hipSuccess) return e;
@@ -109,6 +119,7 @@ hipError_t launch_down01_w(hipStream_t st, const Down01W& L, const int8_t* in6, 
   const int total = tiles_x * tiles_y * nimg;
   int blocks = num_cu / 8 * 8;                    // one workgroup per CU (register budget), whole XCD bands
   while (blocks > 8 && blocks / 8 > (total + 7) / 8) blocks -= 8;
+  report(li, blocks, total);
   hipLaunchKernelGGL(k_down01_f16<W4>, dim3(blocks), dim3(256), T::LDS_BYTES, st, in6, H, W,
                      L.wfrag + (size_t)T::INNER * T::NK * 2 * 64, L.bias + T::INNER * kC, out, Ho, Wo, tiles_x, tiles_y, nimg,
                      og.PH, og.PW, og.py, og.px);
@@ -118,19 +129,19 @@ hipError_t launch_down01_w(hipStream_t st, const Down01W& L, const int8_t* in6, 
   return hipGetLastError();
 }
 hipError_t launch_down01(hipStream_t st, const Down01W& L, const int8_t* in6, int H, int W, int nimg, int Ho, int Wo,
-                         uint4* out, const SlotGeom& og, int num_cu) {
-  return (W % 4) == 0 ? launch_down01_w<true>(st, L, in6, H, W, nimg, Ho, Wo, out, og, num_cu)
-                      : launch_down01_w<false>(st, L, in6, H, W, nimg, Ho, Wo, out, og, num_cu);
+                         uint4* out, const SlotGeom& og, int num_cu, LaunchInfo* li = nullptr) {
+  return (W % 4) == 0 ? launch_down01_w<true>(st, L, in6, H, W, nimg, Ho, Wo, out, og, num_cu, li)
+                      : launch_down01_w<false>(st, L, in6, H, W, nimg, Ho, Wo, out, og, num_cu, li);
 }
 
 // weights-stationary split-operand conv on split-slot tensors: persistent grid of MINB workgroups per CU
 template <int KS, int STRIDE, int VCH, int TR, int TC, int SEGW, int MINB, bool OUTSLOT, class Loader, bool HASRES = false>
 hipError_t launch_conv_x3s(hipStream_t st, const ConvLayer& L, const Loader& ld, int nimg, int Ho, int Wo, float* out,
-                           const float* res, bool lrelu, int num_cu) {
+                           const float* res, bool lrelu, int num_cu, LaunchInfo* li = nullptr) {
   using T = X3sTile<KS, STRIDE, VCH, TR, TC, SEGW>;
   const ConvArgs a = make_conv_args(L, L.wx3, out, res, nimg, Ho, Wo, 1, KS / 2, lrelu, TR, TC);
   if (res != nullptr && !HASRES)      // residual layers use their own instantiation (16 more registers)
-    return launch_conv_x3s<KS, STRIDE, VCH, TR, TC, SEGW, MINB, OUTSLOT, Loader, true>(st, L, ld, nimg, Ho, Wo, out, res, lrelu, num_cu);
+    return launch_conv_x3s<KS, STRIDE, VCH, TR, TC, SEGW, MINB, OUTSLOT, Loader, true>(st, L, ld, nimg, Ho, Wo, out, res, lrelu, num_cu, li);
   auto kern = k_conv_x3s<KS, STRIDE, VCH, TR, TC, SEGW, MINB, OUTSLOT, HASRES, Loader>;
   static_assert(T::LDS_BYTES <= 160 * 1024, "x3s tile does not fit the LDS");
   if (T::LDS_BYTES > 64 * 1024) {
@@ -138,6 +149,7 @@ hipError_t launch_conv_x3s(hipStream_t st, const ConvLayer& L, const Loader& ld,
     if (e != hipSuccess) return e;
   }
   const int blocks = xcd_band_grid(num_cu * MINB, a.tiles_x * a.tiles_y * nimg);
+  report(li, blocks, a.tiles_x * a.tiles_y * nimg);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), T::LDS_BYTES, st, a, ld);
   return hipGetLastError();
 }
@@ -176,13 +188,14 @@ VolPad vol_pad(int Dl, int hl, int wl) { return VolPad{Dl, hl, wl, VolPad::ph(hl
 // sums P [npairs Dl][27][H][W] instead of the activated volume (k_agg_x3s_dma HEADP)
 template <bool OUTSLOT, bool HEADP = false>
 hipError_t launch_agg_dma(hipStream_t st, const ConvLayer& L, const uint4* vin, const VolPad& g, int npairs, void* out,
-                          bool lrelu, int num_cu, const uint4* head_frag = nullptr) {
+                          bool lrelu, int num_cu, const uint4* head_frag = nullptr, LaunchInfo* li = nullptr) {
   if (HEADP != (head_frag != nullptr)) return hipErrorInvalidValue;
   const ConvArgs a = make_conv_args(L, L.wx3, out, head_frag, npairs * g.Dl, g.H, g.W, 1, 1, lrelu, 8, 16);
   auto kern = k_agg_x3s_dma<OUTSLOT, HEADP>;
   hipError_t e = ensure_lds_attr(kern, (int)AggDma::LDS_BYTES);
   if (e != hipSuccess) return e;
   const int blocks = xcd_band_grid(num_cu, a.tiles_x * a.tiles_y * a.nimg);
+  report(li, blocks, a.tiles_x * a.tiles_y * a.nimg);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), AggDma::LDS_BYTES, st, a, vin, g);
   return hipGetLastError();
 }
@@ -193,12 +206,13 @@ FeatPad feat_pad(int H, int W) { return FeatPad{H, W, FeatPad::ph(H), FeatPad::p
 // out / res: FeatPad tensors (OUTSLOT) or fp32 NCHW.
 template <bool OUTSLOT, bool HASRES>
 hipError_t launch_feat_dma(hipStream_t st, const ConvLayer& L, const uint4* vin, const FeatPad& g, int nimg, void* out,
-                           const void* res, bool lrelu, int num_cu) {
+                           const void* res, bool lrelu, int num_cu, LaunchInfo* li = nullptr) {
   const ConvArgs a = make_conv_args(L, L.wx3, out, res, nimg, g.H, g.W, 1, 1, lrelu, 8, 16);
   auto kern = k_feat_x3s_dma<OUTSLOT, HASRES>;
   hipError_t e = ensure_lds_attr(kern, (int)FeatDma::LDS_BYTES);
   if (e != hipSuccess) return e;
   const int blocks = xcd_band_grid(2 * num_cu, a.tiles_x * a.tiles_y * a.nimg);
+  report(li, blocks, a.tiles_x * a.tiles_y * a.nimg);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), FeatDma::LDS_BYTES, st, a, vin, g);
   return hipGetLastError();
 }
@@ -208,11 +222,12 @@ SlotGeom down_in_geom(int Ho, int Wo) { return SlotGeom{DownDma::ph(Ho), DownDma
 
 // 5x5 stride-2 32->32 down-conv on a zero-bordered split-slot input (sn_agg_dma.hpp); go = the output tensor's grid
 hipError_t launch_down_dma(hipStream_t st, const ConvLayer& L, const uint4* vin, int nimg, int Ho, int Wo, void* out,
-                           const SlotGeom& go, bool lrelu, int num_cu) {
+                           const SlotGeom& go, bool lrelu, int num_cu, LaunchInfo* li = nullptr) {
   const ConvArgs a = make_conv_args(L, L.wx3, out, nullptr, nimg, Ho, Wo, 1, 2, lrelu, DownDma::TR, DownDma::TC);
   hipError_t e = ensure_lds_attr(k_down_x3s_dma, (int)DownDma::LDS_BYTES);
   if (e != hipSuccess) return e;
   const int blocks = xcd_band_grid(num_cu, a.tiles_x * a.tiles_y * nimg);
+  report(li, blocks, a.tiles_x * a.tiles_y * nimg);
   hipLaunchKernelGGL(k_down_x3s_dma, dim3(blocks), dim3(256), DownDma::LDS_BYTES, st, a, vin, down_in_geom(Ho, Wo), go);
   return hipGetLastError();
 }
@@ -251,7 +266,7 @@ hipError_t conv3x3_d(hipStream_t st, const ConvLayer& L, const float* in, int ni
 // Tower layers of SN_PREC_FP32 (plain fp32 NCHW, 32 -> 32, 3x3 dilated): the weights-stationary kernel of sn_tower_f32.hpp.
 template <int DIL, int CPH, int NW = 8>
 hipError_t launch_ref_conv_f32(hipStream_t st, const ConvLayer& L, const float* in, int nimg, int H, int W, float* out,
-                               const float* res, bool lrelu, int num_cu) {
+                               const float* res, bool lrelu, int num_cu, LaunchInfo* li = nullptr) {
   using T = F32Tile<DIL, CPH, 64, NW>;
   auto kern = res ? k_ref_conv_f32<DIL, CPH, true, NW> : k_ref_conv_f32<DIL, CPH, false, NW>;
   if (T::LDS_BYTES > 64 * 1024 - 1024) {
@@ -266,21 +281,22 @@ hipError_t launch_ref_conv_f32(hipStream_t st, const ConvLayer& L, const float* 
   const int grid_env = switches().f32_grid;          // probe: workgroups per launch
   if (grid_env > 0) grid = grid_env < 2 * total ? grid_env : 2 * total;
   if (grid < 1) grid = 1;
+  report(li, grid, 2 * total);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), T::LDS_BYTES, st, in, out, res, L.wpk, L.bias, nimg, H, W, lrelu ? 1 : 0);
   return hipGetLastError();
 }
 
 hipError_t conv3x3(hipStream_t st, const ConvLayer& L, const float* in, int nimg, int H, int W, int dil,
-                   float* out, const float* res, bool lrelu, int tower_cu = 0) {
+                   float* out, const float* res, bool lrelu, int tower_cu = 0, LaunchInfo* li = nullptr) {
   // (the 16-byte staging wants rows that start 16-byte aligned: W % 4 == 0 — every level-0 geometry, not every coarse
   // level of a hierarchical model)
   if (tower_cu > 0 && L.cin == kC && L.cin_pad == kC && (W & 3) == 0 && switches().f32_tower) {      // SN_F32_TOWER=0 keeps the generic kernel (A/B)
     switch (dil) {
-      case 1: return launch_ref_conv_f32<1, 8>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu);
-      case 2: return launch_ref_conv_f32<2, 8>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu);
-      case 4: return launch_ref_conv_f32<4, 4, 16>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu);
+      case 1: return launch_ref_conv_f32<1, 8>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu, li);
+      case 2: return launch_ref_conv_f32<2, 8>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu, li);
+      case 4: return launch_ref_conv_f32<4, 4, 16>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu, li);
       // dilation 4 / 8: sixteen rows per tile (1024 threads) — 16 / 24 halo rows per 8 would be 2 - 3x the staging of the tile itself
-      case 8: return launch_ref_conv_f32<8, 4, 16>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu);
+      case 8: return launch_ref_conv_f32<8, 4, 16>(st, L, in, nimg, H, W, out, res, lrelu, tower_cu, li);
       default: return hipErrorInvalidValue;
     }
   }
@@ -355,7 +371,7 @@ hipError_t alloc_ref16(const RefGeom& g, size_t tensor_and_slack_slots, uint4** 
 
 template <int DIL, int TW, int NBUF>
 hipError_t launch_ref_f16x3(hipStream_t st, const RefLayerF16& L, const RefGeom& g, int num_cu, const uint4* in,
-                            uint4* out, const uint4* res, size_t lo_slots, int nimg, bool lrelu) {
+                            uint4* out, const uint4* res, size_t lo_slots, int nimg, bool lrelu, LaunchInfo* li = nullptr) {
   using T = RefTile2<DIL, TW>;
   constexpr int lds_bytes = NBUF * 2 * T::BUF * 16;
   auto kern = res ? k_ref_conv_f16x3<DIL, TW, NBUF, true> : k_ref_conv_f16x3<DIL, TW, NBUF, false>;
@@ -370,25 +386,26 @@ hipError_t launch_ref_f16x3(hipStream_t st, const RefLayerF16& L, const RefGeom&
   if (cap < 1) cap = 1;
   const int rounds = (band + cap - 1) / cap;
   const int nlb = (band + rounds - 1) / rounds;
+  report(li, nlb * 8, total);
   hipLaunchKernelGGL(kern, dim3(nlb * 8), dim3(256), lds_bytes, st, in, out, res, lo_slots, L.wfrag, L.bias, gt, nimg,
                      lrelu ? 1 : 0);
   return hipGetLastError();
 }
 
 hipError_t ref_conv_f16x3(hipStream_t st, const RefLayerF16& L, const RefGeom& g, int num_cu, int dil, const uint4* in,
-                          uint4* out, const uint4* res, size_t lo_slots, int nimg, bool lrelu) {
+                          uint4* out, const uint4* res, size_t lo_slots, int nimg, bool lrelu, LaunchInfo* li = nullptr) {
   switch (dil) {
-    case 1: return launch_ref_f16x3<1, 64, 3>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu);
-    case 2: return launch_ref_f16x3<2, 64, 3>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu);
-    case 4: return launch_ref_f16x3<4, 32, 3>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu);
-    case 8: return launch_ref_f16x3<8, 32, 2>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu);
+    case 1: return launch_ref_f16x3<1, 64, 3>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu, li);
+    case 2: return launch_ref_f16x3<2, 64, 3>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu, li);
+    case 4: return launch_ref_f16x3<4, 32, 3>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu, li);
+    case 8: return launch_ref_f16x3<8, 32, 2>(st, L, g, num_cu, in, out, res, lo_slots, nimg, lrelu, li);
     default: return hipErrorInvalidValue;
   }
 }
 
 template <int DIL, int TW, int NB = 3>
 hipError_t launch_ref_f16_v2(hipStream_t st, const RefLayerF16& L, const RefGeom& g, int num_cu, const uint4* in,
-                             uint4* out, const uint4* res, int nimg, bool lrelu, unsigned* tile_ctr) {
+                             uint4* out, const uint4* res, int nimg, bool lrelu, unsigned* tile_ctr, LaunchInfo* li = nullptr) {
   using T = RefTile2<DIL, TW, 8, NB>;
   // tile_ctr: the launch's tile queue (8 zeroed counters, 64 B apart)
   auto kern = res ? k_ref_conv_f16_v2<DIL, TW, true, 8, 2, NB> : k_ref_conv_f16_v2<DIL, TW, false, 8, 2, NB>;
@@ -407,6 +424,7 @@ hipError_t launch_ref_f16_v2(hipStream_t st, const RefLayerF16& L, const RefGeom
   int cap = num_cu * 2 / 8;
   if (cap < 1) cap = 1;
   const int nlb = cap < band ? cap : band;
+  report(li, nlb * 8, total);
   hipLaunchKernelGGL(kern, dim3(nlb * 8), dim3(256), T::LDS_BYTES, st, in, out, res, L.wfrag, L.bias, gt, nimg,
                      lrelu ? 1 : 0, tile_ctr);
   return hipGetLastError();
@@ -416,7 +434,8 @@ hipError_t launch_ref_f16_v2(hipStream_t st, const RefLayerF16& L, const RefGeom
 // the flattened (image, row phase, strip, sub-row) sequence.  x and y must be different tensors.  dump: >= 1 KB scratch.
 template <class T>
 hipError_t launch_ref_block_stream(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu,
-                                   const uint4* x, uint4* y, int nimg, unsigned* dump, const HeadArgs& ha = HeadArgs{}) {
+                                   const uint4* x, uint4* y, int nimg, unsigned* dump, const HeadArgs& ha = HeadArgs{},
+                                   LaunchInfo* li = nullptr) {
   constexpr int DIL = T::DIL;
   auto kern = k_ref_block_stream_f16<T::DIL, T::TW, T::R, T::NXS, T::NWR, T::HEAD>;
   if (dump == nullptr) return hipErrorInvalidValue;
@@ -435,6 +454,7 @@ hipError_t launch_ref_block_stream(hipStream_t st, const RefLayerF16& L1, const 
   if (nwg < 1) nwg = 1;
   sc.rows_per_wg = (sc.total_rows + nwg - 1) / nwg;
   const int grid = (sc.total_rows + sc.rows_per_wg - 1) / sc.rows_per_wg;
+  report(li, grid, sc.total_rows);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), T::LDS_BYTES, st, x, y, L1.wfrag, L1.bias, L2.wfrag, L2.bias, g, sc,
                      reinterpret_cast<uint4*>(dump), ha);
   return hipGetLastError();
@@ -443,19 +463,19 @@ hipError_t launch_ref_block_stream(hipStream_t st, const RefLayerF16& L1, const 
 // Last block of the tower + the refinement head in one launch (tail form): y never leaves the CU, the head's maps are the
 // only thing written.  Same arithmetic as the streamed block followed by k_head_final_f16 (bit-identical maps).
 hipError_t ref_block_stream_tail(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu,
-                                 const uint4* x, int nimg, unsigned* dump, const HeadArgs& ha) {
-  return launch_ref_block_stream<StreamTileTail>(st, L1, L2, g, num_cu, x, nullptr, nimg, dump, ha);
+                                 const uint4* x, int nimg, unsigned* dump, const HeadArgs& ha, LaunchInfo* li = nullptr) {
+  return launch_ref_block_stream<StreamTileTail>(st, L1, L2, g, num_cu, x, nullptr, nimg, dump, ha, li);
 }
 
 // Strip shapes: 64 columns x 4 rows per step for dilation 1 / 2 (62 / 60 of 64 columns are outputs); 128 columns x 2 rows
 // for dilation 4 / 8, where a 64-wide strip would keep only 56 / 48 of its columns (120 / 112 of 128 here).
 hipError_t ref_block_stream(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu, int dil,
-                            const uint4* x, uint4* y, int nimg, unsigned* dump) {
+                            const uint4* x, uint4* y, int nimg, unsigned* dump, LaunchInfo* li = nullptr) {
   switch (dil) {
-    case 1: return launch_ref_block_stream<StreamTile1>(st, L1, L2, g, num_cu, x, y, nimg, dump);
-    case 2: return launch_ref_block_stream<StreamTile2>(st, L1, L2, g, num_cu, x, y, nimg, dump);
-    case 4: return launch_ref_block_stream<StreamTile4>(st, L1, L2, g, num_cu, x, y, nimg, dump);
-    case 8: return launch_ref_block_stream<StreamTile8>(st, L1, L2, g, num_cu, x, y, nimg, dump);
+    case 1: return launch_ref_block_stream<StreamTile1>(st, L1, L2, g, num_cu, x, y, nimg, dump, HeadArgs{}, li);
+    case 2: return launch_ref_block_stream<StreamTile2>(st, L1, L2, g, num_cu, x, y, nimg, dump, HeadArgs{}, li);
+    case 4: return launch_ref_block_stream<StreamTile4>(st, L1, L2, g, num_cu, x, y, nimg, dump, HeadArgs{}, li);
+    case 8: return launch_ref_block_stream<StreamTile8>(st, L1, L2, g, num_cu, x, y, nimg, dump, HeadArgs{}, li);
     default: return hipErrorInvalidValue;
   }
 }
@@ -534,16 +554,17 @@ inline int tower_tile_width(const RefGeom& g, int nimg, int num_cu, int force_tw
 }
 
 hipError_t ref_conv_f16(hipStream_t st, const RefLayerF16& L, const RefGeom& g, int num_cu, int dil, const uint4* in,
-                        uint4* out, const uint4* res, int nimg, bool lrelu, unsigned* tile_ctr, int force_tw = 0) {
+                        uint4* out, const uint4* res, int nimg, bool lrelu, unsigned* tile_ctr, int force_tw = 0,
+                        LaunchInfo* li = nullptr) {
   if (dil <= 2 && tower_tile_width(g, nimg, num_cu, force_tw) == 32) {
-    if (dil == 1) return launch_ref_f16_v2<1, 32>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr);
-    if (dil == 2) return launch_ref_f16_v2<2, 32>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr);
+    if (dil == 1) return launch_ref_f16_v2<1, 32>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr, li);
+    if (dil == 2) return launch_ref_f16_v2<2, 32>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr, li);
   }
   switch (dil) {
-    case 1: return launch_ref_f16_v2<1, 64>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr);
-    case 2: return launch_ref_f16_v2<2, 64>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr);
-    case 4: return launch_ref_f16_v2<4, 32>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr);      // 61 KB ring
-    case 8: return launch_ref_f16_v2<8, 32, 2>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr);   // 74 KB, two buffers
+    case 1: return launch_ref_f16_v2<1, 64>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr, li);
+    case 2: return launch_ref_f16_v2<2, 64>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr, li);
+    case 4: return launch_ref_f16_v2<4, 32>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr, li);      // 61 KB ring
+    case 8: return launch_ref_f16_v2<8, 32, 2>(st, L, g, num_cu, in, out, res, nimg, lrelu, tile_ctr, li);   // 74 KB, two buffers
     default: return hipErrorInvalidValue;
   }
 }
@@ -552,11 +573,11 @@ hipError_t ref_conv_f16(hipStream_t st, const RefLayerF16& L, const RefGeom& g, 
 // block's two tile queues (kTileCtrStride apart).
 hipError_t ref_block_f16(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu,
                          int dil, uint4** cur, uint4** oth, int nimg, unsigned* tile_ctr, int fuse_mode, unsigned* dump,
-                         bool alt = false) {
+                         bool alt = false, LaunchInfo* li = nullptr) {
   hipError_t e = hipErrorInvalidValue;
   bool fused = false;
   if (fuse_mode == 4 && stream_block_supports(dil)) {
-    e = ref_block_stream(st, L1, L2, g, num_cu, dil, *cur, *oth, nimg, dump);
+    e = ref_block_stream(st, L1, L2, g, num_cu, dil, *cur, *oth, nimg, dump, li);
     fused = true;
   }
   if (fused) {
@@ -569,7 +590,7 @@ hipError_t ref_block_f16(hipStream_t st, const RefLayerF16& L1, const RefLayerF1
   if (e != hipSuccess) return e;
   RefGeom g2 = g;
   if (alt) g2.rev ^= 1;                  // the second conv walks the tiles the other way round (refine_level)
-  return ref_conv_f16(st, L2, g2, num_cu, dil, *oth, *cur, *cur, nimg, true, tile_ctr + kTileCtrStride);   // in-place residual
+  return ref_conv_f16(st, L2, g2, num_cu, dil, *oth, *cur, *cur, nimg, true, tile_ctr + kTileCtrStride, 0, li);   // in-place residual
 }
 
 // Fused residual block on split operands, row-streaming form (sn_stream_block_x3.hpp): every dilation.  x and y are
@@ -579,7 +600,7 @@ inline bool stream_x3_supports(int dil) {
 }
 template <int DIL, int NWR = 2>
 hipError_t launch_ref_block_stream_x3(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu,
-                                      const uint4* x, uint4* y, size_t lo_slots, int nimg) {
+                                      const uint4* x, uint4* y, size_t lo_slots, int nimg, LaunchInfo* li = nullptr) {
   using T = StreamTileX3<DIL, 64, 2, 5, NWR>;
   static_assert(T::ROWS_ABOVE <= kStreamRowsAbove && T::ROWS_BELOW <= kStreamRowsBelow, "inside the zero rows the tensors are allocated with");
   auto kern = k_ref_block_stream_x3<T::DIL, T::TW, T::R, T::NXS, T::NWR>;
@@ -594,27 +615,28 @@ hipError_t launch_ref_block_stream_x3(hipStream_t st, const RefLayerF16& L1, con
   if (nwg < 1) nwg = 1;
   sc.rows_per_wg = (sc.total_rows + nwg - 1) / nwg;
   const int grid = (sc.total_rows + sc.rows_per_wg - 1) / sc.rows_per_wg;
+  report(li, grid, sc.total_rows);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * T::NWR), T::LDS_BYTES, st, x, y, lo_slots * 16, L1.wfrag, L1.bias, L2.wfrag,
                      L2.bias, g, sc);
   return hipGetLastError();
 }
 // One residual block of the split tower on `*cur` (input and, on return, output); `*oth` is scratch.
 hipError_t ref_block_f16x3(hipStream_t st, const RefLayerF16& L1, const RefLayerF16& L2, const RefGeom& g, int num_cu, int dil,
-                           uint4** cur, uint4** oth, size_t lo_slots, int nimg, bool stream = true) {
+                           uint4** cur, uint4** oth, size_t lo_slots, int nimg, bool stream = true, LaunchInfo* li = nullptr) {
   if (stream && stream_x3_supports(dil)) {
     hipError_t e = hipErrorInvalidValue;
     // waves per role: 4 (default) = two waves per SIMD, one of each role, so that one role's epilogue / DMA issue sits beside the
     // other's MFMAs (256 registers per wave: 20 bytes of scratch at dilation 1 / 2); SN_X3_NWR=2 = one wave per SIMD (A/B)
     const int nwr = switches().x3_nwr;
     if (nwr == 4) {
-      if (dil == 1) e = launch_ref_block_stream_x3<1, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
-      else if (dil == 2) e = launch_ref_block_stream_x3<2, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
-      else if (dil == 4) e = launch_ref_block_stream_x3<4, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
-      else e = launch_ref_block_stream_x3<8, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
-    } else if (dil == 1) e = launch_ref_block_stream_x3<1>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
-    else if (dil == 2) e = launch_ref_block_stream_x3<2>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
-    else if (dil == 4) e = launch_ref_block_stream_x3<4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
-    else e = launch_ref_block_stream_x3<8>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg);
+      if (dil == 1) e = launch_ref_block_stream_x3<1, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
+      else if (dil == 2) e = launch_ref_block_stream_x3<2, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
+      else if (dil == 4) e = launch_ref_block_stream_x3<4, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
+      else e = launch_ref_block_stream_x3<8, 4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
+    } else if (dil == 1) e = launch_ref_block_stream_x3<1>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
+    else if (dil == 2) e = launch_ref_block_stream_x3<2>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
+    else if (dil == 4) e = launch_ref_block_stream_x3<4>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
+    else e = launch_ref_block_stream_x3<8>(st, L1, L2, g, num_cu, *cur, *oth, lo_slots, nimg, li);
     uint4* t = *cur;
     *cur = *oth;
     *oth = t;
@@ -622,7 +644,7 @@ hipError_t ref_block_f16x3(hipStream_t st, const RefLayerF16& L1, const RefLayer
   }
   hipError_t e = ref_conv_f16x3(st, L1, g, num_cu, dil, *cur, *oth, nullptr, lo_slots, nimg, true);
   if (e != hipSuccess) return e;
-  return ref_conv_f16x3(st, L2, g, num_cu, dil, *oth, *cur, *cur, lo_slots, nimg, true);      // in-place residual
+  return ref_conv_f16x3(st, L2, g, num_cu, dil, *oth, *cur, *cur, lo_slots, nimg, true, li);      // in-place residual
 }
 
 }  // namespace

@@ -316,6 +316,40 @@ int sn_get_dominant_kernel(sn_handle *h, char *name, size_t name_cap, int *launc
 int sn_dbg_conv2d(sn_handle *h, const float *in, int cin, int h_px, int w, const float *wt,
                   const float *bias, int k, int stride, int dil, int lrelu, const float *residual,
                   float *out);
+/* The grid of the parity hooks.  Every hot kernel is persistent: its launcher sizes the grid from the CU count, and a
+ * workgroup walks several tiles (or a share of the streamed blocks' flat rows).  sn_dbg_set_grid_cus makes the sn_dbg_* hooks
+ * (and nothing else: the forward pass never reads it) hand their launchers `cus` in place of the device's CU count, so that a
+ * small tensor runs the tile loops, queue and share boundaries a full-size one does.  cus = 1 .. the device's CU count, 0
+ * restores the default; SN_ERR_ARG otherwise.  A hook whose launcher builds its grid in XCD bands of 8 (the split-slot
+ * convolutions, sn_dbg_conv3d's slot forms, sn_dbg_agg_tail, sn_dbg_down01, sn_dbg_ref_conv_f16 / _f16x3 and the two-launch
+ * forms of the blocks) returns SN_ERR_ARG with a message while the value is no multiple of 8.
+ * sn_dbg_last_launch: workgroups and work units (tiles; half tiles for k_ref_conv_f32; flat rows for the streamed blocks) of
+ * the last launch of the last hook call that went through a persistent launcher (0, 0 for one that did not). */
+int sn_dbg_set_grid_cus(sn_handle *h, int cus);
+int sn_dbg_last_launch(sn_handle *h, int *wgs, int *units);
+/* The _n forms of the one-image hooks: n images in ONE launch, as the pipeline batches them (in / residual / out
+ * [n][32][h][w]; sn_dbg_refin_n: disp_low [n][hp/16][wp/16], in6 [n][6][h][w]); the one-image forms are n = 1.
+ * The tower hooks (sn_dbg_refin, sn_dbg_ref_conv_*, sn_dbg_ref_block_*) allocate their tensors as the pipeline does
+ * ([front rows | tensor | slack]); an output tensor that is not also an input (everything except the in-place residual) starts
+ * with the 0xff pattern (fp16 NaN) in its valid area, and after the launch the zero border of all n images, the front rows and
+ * the slack are read back: SN_ERR_DEVICE with a message if any of them changed. */
+int sn_dbg_conv2d_n(sn_handle *h, int n, const float *in, int cin, int h_px, int w, const float *wt,
+                    const float *bias, int k, int stride, int dil, int lrelu, const float *residual,
+                    float *out);
+int sn_dbg_down0_n(sn_handle *h, int n, const int8_t *in6, int h_px, int w, const float *wt, const float *bias, int tc,
+                   float *out);       /* in6 [n][6][h][w] -> out [2n][32][ho][wo] */
+int sn_dbg_down01_n(sn_handle *h, int n, const int8_t *in6, int h_px, int w, const float *w0, const float *b0,
+                    const float *w1, const float *b1, float *out);
+int sn_dbg_refin_n(sn_handle *h, int n, const float *disp_low, const int8_t *in6, int h_px, int w, int dmax,
+                   const float *wt, const float *bias, int split, float *out);
+int sn_dbg_ref_conv_f16_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *wt, const float *bias,
+                          int dil, int lrelu, const float *residual, float *out);
+int sn_dbg_ref_conv_f16x3_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *wt, const float *bias,
+                            int dil, int lrelu, const float *residual, float *out);
+int sn_dbg_ref_block_f16_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *w1, const float *b1,
+                           const float *w2, const float *b2, int dil, float *out);
+int sn_dbg_ref_block_f16x3_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *w1, const float *b1,
+                             const float *w2, const float *b2, int dil, int form, float *out);
 /* the first down-conv (3->32, 5x5, stride 2, no activation) of both eyes through the fp16-MFMA kernel of the fp16
  * modes: in6 int8 [6][h][w] (model input), wt [32][3][5][5], out [2][32][ho][wo] with ho/wo = ceil16(h|w)/2;
  * tc = 32 or 64 selects the tile width */
