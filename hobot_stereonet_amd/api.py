@@ -157,6 +157,19 @@ def ground_params(p) -> SnGroundParams:
                           p.min_inliers, p.refits, p.tol_px, p.max_tilt_rad, p.height_min_m, p.height_max_m)
 
 
+class SnCostmapParams(C.Structure):
+    """sn_costmap_params (include/stereonet_hip.h); costmap.CostmapParams is the Python face of it."""
+    _fields_ = [("mw", C.c_int), ("mh", C.c_int), ("l_hit", C.c_int), ("l_miss", C.c_int), ("l_min", C.c_int), ("l_max", C.c_int),
+                ("clear_margin_m", C.c_float), ("clear_min_m", C.c_float), ("clear_max_m", C.c_float)]
+
+
+def costmap_params(p) -> SnCostmapParams:
+    """costmap.CostmapParams -> sn_costmap_params"""
+    if isinstance(p, SnCostmapParams):
+        return p
+    return SnCostmapParams(p.mw, p.mh, p.l_hit, p.l_miss, p.l_min, p.l_max, p.clear_margin_m, p.clear_min_m, p.clear_max_m)
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -318,6 +331,12 @@ def load_library(path: Optional[str] = None):
                                                  ip, vp]
     lib.sn_ground_gate.argtypes = [C.POINTER(SnCamera), C.POINTER(SnGroundParams), ip, ip, vp]
     lib.sn_ground_from_raw.argtypes = [vp, ip, i32p, C.POINTER(SnCamera), C.POINTER(SnGroundParams), vp, u8p, ip, vp]
+    lib.sn_costmap_create.argtypes = [vp, ip, C.POINTER(SnObstacleParams), C.POINTER(SnCostmapParams), C.POINTER(vp)]
+    lib.sn_costmap_reset.argtypes = [vp, ip]
+    lib.sn_costmap_destroy.argtypes = [vp]
+    lib.sn_costmap_destroy.restype = None
+    lib.sn_costmap_pose_q.argtypes = [vp, vp, i32p]
+    lib.sn_costmap_push.argtypes = [vp, ip, vp, vp, i8p, fp, i8p, vp, vp, i32p, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -331,7 +350,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -414,6 +433,27 @@ def ground_gate(cam, params, w: int, h: int) -> np.ndarray:
     if rc:
         raise StereoNetError(rc, "sn_ground_gate")
     return gate
+
+
+def costmap_pose_q(params, obstacle, poses) -> np.ndarray:
+    """sn_costmap_pose_q (host only: a costmap without an engine serves it): poses (x, y, yaw) or (n, 3) -> int32 (6,) or
+    (n, 6) = {tx, ty, cq, sq, ox, oy}; costmap.pose_q is the Python twin (the two may differ by one unit in cq and sq: two
+    implementations of a double cos and sin)."""
+    lib, c = load_library(), C.c_void_p()
+    prm, op = costmap_params(params), obstacle_params(obstacle)
+    rc = lib.sn_costmap_create(None, 1, C.byref(op), C.byref(prm), C.byref(c))
+    if rc:
+        raise StereoNetError(rc, "sn_costmap_create")
+    try:
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        q = np.empty((ps.shape[0], 6), np.int32)
+        for k in range(ps.shape[0]):
+            rc = lib.sn_costmap_pose_q(c, ps[k].ctypes.data, q[k].ctypes.data)
+            if rc:
+                raise StereoNetError(rc, "sn_costmap_pose_q", f"pose {k}: {ps[k].tolist()}")
+    finally:
+        lib.sn_costmap_destroy(c)
+    return q[0] if np.ndim(poses) == 1 else q
 
 
 def error_string(code: int) -> str:
@@ -950,6 +990,11 @@ class StereoNetHIP:
                         luma_delta: int = 0) -> "TemporalFilter":
         """A TemporalFilter (sn_temporal) of `streams` independent states on this engine; close it before the engine."""
         return TemporalFilter(self, streams, alpha, delta_px, persist, luma_delta)
+
+    def costmap(self, obstacle, params, streams: int = 1) -> "Costmap":
+        """A Costmap (sn_costmap) of `streams` rolling log-odds maps on this engine, fed by obstacles() under `obstacle`
+        (obstacles.ObstacleParams); params: costmap.CostmapParams.  Close it before the engine."""
+        return Costmap(self, obstacle, params, streams)
 
     def rectifier(self, calib):
         """A Rectifier (sn_rectify) for this engine's model size from a rectify.Calib; close it before the engine."""
@@ -1533,6 +1578,71 @@ class TemporalFilter(_Owned):
         self._eng._check(self._lib.sn_temporal_push(self._t, n, _np_ptr(ids), raw_ptr or None, guide_ptr or None, guide_kind,
                                                     guide_pitch, out_raw_ptr or None, disp_ptr or None, mask_ptr or None,
                                                     counts_ptr or None, SN_MEM_DEVICE, stream or None), "sn_temporal_push")
+
+
+class Costmap(_Owned):
+    """sn_costmap: a rolling log-odds costmap with ray clearing per stream, its state on the GPU (costmap.Reference is the numpy
+    twin).  A context object: the engine refuses to close while one of its costmaps is open."""
+    _destroy, _handle = "sn_costmap_destroy", "_c"
+
+    def __init__(self, engine: StereoNetHIP, obstacle, params, streams: int = 1):
+        self._eng, self._lib, self._c = engine, engine._lib, C.c_void_p()
+        self.streams, self.params, self.obstacle = int(streams), costmap_params(params), obstacle_params(obstacle)
+        engine._check(self._lib.sn_costmap_create(engine._h, self.streams, C.byref(self.obstacle), C.byref(self.params), C.byref(self._c)),
+                      "sn_costmap_create")
+
+    def reset(self, stream: int = -1):
+        """Stream `stream` (-1: all) starts afresh at its next push."""
+        self._eng._check(self._lib.sn_costmap_reset(self._c, int(stream)), "sn_costmap_reset")
+
+    def pose_q(self, poses) -> np.ndarray:
+        """sn_costmap_pose_q: (x, y, yaw) or (n, 3) -> int32 (6,) or (n, 6)"""
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        q = np.empty((ps.shape[0], 6), np.int32)
+        for k in range(ps.shape[0]):
+            self._eng._check(self._lib.sn_costmap_pose_q(self._c, ps[k].ctypes.data, q[k].ctypes.data), "sn_costmap_pose_q")
+        return q[0] if np.ndim(poses) == 1 else q
+
+    def _poses(self, poses, stream_of, n: int):
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        if ps.size != 3 * n:
+            raise StereoNetError(-1, "costmap push", f"{ps.size} pose numbers for {n} maps: (n, 3) is needed")
+        ids = None if stream_of is None else np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        if ids is not None and ids.size != n:
+            raise StereoNetError(-1, "costmap push", f"{ids.size} stream ids for {n} maps")
+        return ps, ids
+
+    def push(self, poses, occ: Optional[np.ndarray] = None, ranges: Optional[np.ndarray] = None, stream_of=None,
+             want=(True, True, True)):
+        """sn_costmap_push on host buffers: poses (n, 3) = x, y, yaw; occ int8 (n, gh, gw) and ranges float32 (n, beams) as
+        obstacles() returns them (either may be None); map k the next frame of stream stream_of[k] (None: all of stream 0, one
+        clip) -> (grid int8 (n, mh, mw), logodds int16 (n, mh, mw), stats uint32 (n, 4) = {known, occupied, hit, cleared} per
+        map, q int32 (n, 6)); `want` drops grid, logodds or stats (None in their place)."""
+        n = int(np.size(poses)) // 3
+        ps, ids = self._poses(poses, stream_of, n)
+        o = None if occ is None else np.ascontiguousarray(occ, np.int8)
+        r = None if ranges is None else np.ascontiguousarray(ranges, np.float32)
+        cells, beams, (mh, mw) = self.obstacle.gw * self.obstacle.gh, self.obstacle.beams, (self.params.mh, self.params.mw)
+        if (o is not None and o.size != n * cells) or (r is not None and r.size != n * beams):
+            raise StereoNetError(-1, "costmap push", f"occ and ranges must hold {n} x {cells} cells and {n} x {beams} beams")
+        grid = np.empty((n, mh, mw), np.int8) if want[0] else None
+        logodds = np.empty((n, mh, mw), np.int16) if want[1] else None
+        stats = np.zeros((n, 4), np.uint32) if want[2] else None
+        q = np.zeros((n, 6), np.int32)
+        self._eng._check(self._lib.sn_costmap_push(self._c, n, _np_ptr(ids), ps.ctypes.data, _np_ptr(o), _np_ptr(r), _np_ptr(grid),
+                                                   _np_ptr(logodds), _np_ptr(stats), q.ctypes.data, SN_MEM_HOST, None), "sn_costmap_push")
+        return grid, logodds, stats, q
+
+    def push_device(self, n: int, poses, occ_ptr: int = 0, ranges_ptr: int = 0, stream_of=None, grid_ptr: int = 0, logodds_ptr: int = 0,
+                    stats_ptr: int = 0, stream: int = 0) -> np.ndarray:
+        """sn_costmap_push on device pointers (0: absent / not wanted; poses and stream_of stay host sequences); stream =
+        hipStream_t as int (0: the costmap's own stream, and the call returns after completion) -> q int32 (n, 6)."""
+        ps, ids = self._poses(poses, stream_of, n)
+        q = np.zeros((n, 6), np.int32)
+        self._eng._check(self._lib.sn_costmap_push(self._c, n, _np_ptr(ids), ps.ctypes.data, occ_ptr or None, ranges_ptr or None,
+                                                   grid_ptr or None, logodds_ptr or None, stats_ptr or None, q.ctypes.data, SN_MEM_DEVICE,
+                                                   stream or None), "sn_costmap_push")
+        return q
 
 
 class Rectifier(_Owned):

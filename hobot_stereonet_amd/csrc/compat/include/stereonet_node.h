@@ -18,6 +18,8 @@
 #include <string>
 #include <vector>
 
+#include <mutex>
+
 #include "rclcpp/rclcpp.hpp"
 #include "nav_msgs/msg/occupancy_grid.hpp"
 #include "sensor_msgs/msg/image.hpp"
@@ -65,6 +67,10 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   // length mismatch, or an image that is not the model's size ends the run with rclcpp::shutdown(), as the
   // reference does.  Returns the number of frames that went through PostProcess.
   int RunImglistFeedInfer(std::string left_img_list, std::string right_img_list);
+
+  // this implementation's own: the robot's planar pose in the costmap's fixed frame (metres, radians), taken by every frame
+  // processed after the call (STEREONET_COSTMAP).  Thread-safe; the default is the origin.
+  void SetBasePose(double x, double y, double yaw);
 
  protected:
   int SetNodePara() override;
@@ -121,6 +127,12 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     bool ground = false;
     sn_ground_params ground_params{};
     float ground_log_delta = 0.02f;
+    // this implementation's own: a rolling log-odds costmap with ray clearing (sn_costmap_push) over the obstacle stage's grid and
+    // scan, at the pose of SetBasePose: nav_msgs/OccupancyGrid on /stereonet_costmap, published after the obstacle topics.
+    // STEREONET_COSTMAP=<parameter file> (costmap.save_params' `key value` lines, `frame` = the fixed frame's id, default odom)
+    // turns it on and requires STEREONET_OBSTACLES; unset: off, nothing of it exists
+    sn_costmap_params costmap_params{};
+    std::string costmap_frame = "odom";
   };
 
   void DeclareAndReadParameters();
@@ -131,6 +143,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void ReadObstacleSettings();
   void PublishObstacles(const StereonetNodeOutput& request, const int32_t* raw, const float* mount);
   void ReadGroundSettings();
+  void ReadCostmapSettings();
+  void PublishCostmap(const StereonetNodeOutput& request, const int8_t* occ, const float* ranges);
   bool FitGround(const int32_t* raw, sn_ground* out);
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
   void ReadTemporalSettings();
@@ -160,6 +174,10 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   bool temporal_unguided_logged_ = false;        // PostProcess only (one thread at a time)
   rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr render_out_;   // only while STEREONET_RENDER is set and valid
   std::atomic<bool> render_no_frame_logged_{false};
+  sn_costmap* costmap_ = nullptr;                // one stream; only while STEREONET_COSTMAP is set and valid
+  rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr costmap_out_;
+  std::mutex base_pose_mu_;
+  double base_pose_[3] = {0.0, 0.0, 0.0};        // x, y, yaw of SetBasePose
   sn_rectify* rectify_ = nullptr;                // only while STEREONET_RECTIFY names a valid calibration
 };
 

@@ -108,13 +108,16 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
     obstacle_grid_out_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/stereonet_obstacle_grid", 10);
   if (cfg_.obstacles && cfg_.obstacle_params.beams)
     obstacle_scan_out_ = create_publisher<sensor_msgs::msg::LaserScan>("/stereonet_scan", 10);
+  ReadCostmapSettings();
   ReadTemporalSettings();
   ready_ = true;
 }
 
 StereonetNode::~StereonetNode() {
-  if (!temporal_ && !rectify_) return;
+  if (!temporal_ && !rectify_ && !costmap_) return;
   WaitIdle();      // requests in flight still pass through PostProcess; the engine is destroyed after the filter (~DnnNode)
+  if (costmap_) sn_costmap_destroy(costmap_);
+  costmap_ = nullptr;
   if (temporal_) sn_temporal_destroy(temporal_);
   temporal_ = nullptr;
   if (rectify_) sn_rectify_destroy(rectify_);
@@ -567,6 +570,13 @@ void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const i
     RCLCPP_ERROR(kLog, "obstacles failed: %s", sn_last_error(net_->engine()));
     return;
   }
+  // the costmap reads the frame's grid and scan after the messages that own them have left
+  std::vector<int8_t> occ_kept;
+  std::vector<float> ranges_kept;
+  if (costmap_) {
+    occ_kept = grid.data;
+    ranges_kept = scan.ranges;
+  }
   if (obstacle_grid_out_) {
     grid.header.stamp = request.msg_header->stamp;
     grid.header.frame_id = cfg_.obstacle_frame;
@@ -588,6 +598,119 @@ void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const i
     scan.range_max = p.range_max_m;
     obstacle_scan_out_->publish(std::move(scan));
   }
+  if (costmap_) PublishCostmap(request, p.gw ? occ_kept.data() : nullptr, p.beams ? ranges_kept.data() : nullptr);
+}
+
+namespace {
+// costmap.load_params' text form, as load_obstacle_file
+bool load_costmap_file(const char* path, sn_costmap_params* p, std::string* frame, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct FloatKey {
+    const char* name;
+    float* v;
+  } floats[] = {{"clear_margin_m", &p->clear_margin_m}, {"clear_min_m", &p->clear_min_m}, {"clear_max_m", &p->clear_max_m}};
+  struct IntKey {
+    const char* name;
+    int* v;
+  } ints[] = {{"mw", &p->mw}, {"mh", &p->mh}, {"l_hit", &p->l_hit}, {"l_miss", &p->l_miss}, {"l_min", &p->l_min}, {"l_max", &p->l_max}};
+  std::vector<std::string> seen;
+  std::string text;
+  for (int no = 1; std::getline(in, text); ++no) {
+    std::istringstream words(text.substr(0, text.find('#')));
+    std::string key, w;
+    if (!(words >> key)) continue;
+    std::vector<std::string> vals;
+    while (words >> w) vals.push_back(w);
+    const std::string at = "line " + std::to_string(no) + ": ";
+    for (const std::string& k : seen)
+      if (k == key) {
+        *err = at + key + " twice";
+        return false;
+      }
+    seen.push_back(key);
+    char* end = nullptr;
+    const double d = vals.size() == 1 ? strtod(vals[0].c_str(), &end) : 0.0;
+    const bool number = vals.size() == 1 && end != vals[0].c_str() && !*end;
+    bool known = false, ok = true;
+    if (key == "frame") {
+      known = true, ok = vals.size() == 1;
+      if (ok) *frame = vals[0];
+    }
+    for (const FloatKey& f : floats)
+      if (key == f.name) {
+        known = true, ok = number;
+        *f.v = (float)d;
+      }
+    for (const IntKey& f : ints)
+      if (key == f.name) {
+        known = true, ok = number && d == (double)(int)d;
+        *f.v = (int)d;
+      }
+    if (!known || !ok) {
+      *err = at + (known ? "wrong values for " : "unknown key ") + key;
+      return false;
+    }
+  }
+  return true;
+}
+}  // namespace
+
+// parsed and validated once here: what sn_costmap_create would refuse turns the stage off instead of failing every frame
+void StereonetNode::ReadCostmapSettings() {
+  const char* e = getenv("STEREONET_COSTMAP");
+  if (!e || !*e) return;
+  // costmap.CostmapParams' defaults: a 200 x 200 window, five hits to the upper clamp and five misses to the lower
+  sn_costmap_params& p = cfg_.costmap_params;
+  p = sn_costmap_params{200, 200, 85, 40, -200, 350, 0.1f, 0.f, 0.f};
+  std::string bad;
+  if (!cfg_.obstacles) bad = std::string("STEREONET_COSTMAP=") + e + " requires STEREONET_OBSTACLES";
+  else if (!load_costmap_file(e, &p, &cfg_.costmap_frame, &bad)) bad = std::string("STEREONET_COSTMAP=") + e + ": " + bad;
+  else if (sn_costmap_create(net_->engine(), 1, &cfg_.obstacle_params, &p, &costmap_) != SN_OK) bad = sn_last_error(net_->engine());
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no costmap");
+    costmap_ = nullptr;
+    return;
+  }
+  costmap_out_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/stereonet_costmap", 10);
+  RCLCPP_WARN_STREAM(kLog, "costmap: frame " << cfg_.costmap_frame << ", window " << p.mw << " x " << p.mh << " cells of "
+                                             << cfg_.obstacle_params.cell_m << " m on /stereonet_costmap, hit " << p.l_hit << ", miss "
+                                             << p.l_miss << ", clamps " << p.l_min << " .. " << p.l_max);
+}
+
+void StereonetNode::SetBasePose(double x, double y, double yaw) {
+  std::lock_guard<std::mutex> lk(base_pose_mu_);
+  base_pose_[0] = x, base_pose_[1] = y, base_pose_[2] = yaw;
+}
+
+// nav_msgs/OccupancyGrid of the rolling map after this frame: one sn_costmap_push call at the pose of SetBasePose, the stamp of
+// the disparity message, the origin of the window from the quantised pose
+void StereonetNode::PublishCostmap(const StereonetNodeOutput& request, const int8_t* occ, const float* ranges) {
+  const sn_costmap_params& p = cfg_.costmap_params;
+  double pose[3];
+  {
+    std::lock_guard<std::mutex> lk(base_pose_mu_);
+    memcpy(pose, base_pose_, sizeof(pose));
+  }
+  nav_msgs::msg::OccupancyGrid map;
+  map.data.resize((size_t)p.mw * p.mh);
+  int32_t q[6];
+  if (sn_costmap_push(costmap_, 1, nullptr, pose, occ, ranges, map.data.data(), nullptr, nullptr, q, SN_MEM_HOST, nullptr) != SN_OK) {
+    RCLCPP_ERROR(kLog, "costmap failed: %s", sn_last_error(net_->engine()));
+    return;
+  }
+  map.header.stamp = request.msg_header->stamp;
+  map.header.frame_id = cfg_.costmap_frame;
+  map.info.map_load_time = request.msg_header->stamp;
+  map.info.resolution = cfg_.obstacle_params.cell_m;
+  map.info.width = p.mw;
+  map.info.height = p.mh;
+  map.info.origin.position.x = (double)q[4] * (double)cfg_.obstacle_params.cell_m;
+  map.info.origin.position.y = (double)q[5] * (double)cfg_.obstacle_params.cell_m;
+  costmap_out_->publish(std::move(map));
 }
 
 namespace {

@@ -336,6 +336,7 @@ struct sn_handle {
   } stage;
   std::atomic<int> temporal_live{0};   // sn_temporal objects created on this handle and not yet destroyed: sn_destroy refuses
   std::atomic<int> rectify_live{0};    // ... and sn_rectify objects
+  std::atomic<int> costmap_live{0};    // ... and sn_costmap objects
 };
 
 // sn_temporal_*: the one post-processing stage with state: a lane per filter, plus the state planes and the per-stream
@@ -350,6 +351,24 @@ struct sn_temporal : Lane<sn_temporal_slots> {
   long long q = 0;                   // delta_px in units of raw
   void* state = nullptr;             // one allocation: P int32 [streams][H*W], then Hs and Yp uint8 [streams][H*W]
   std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
+};
+
+// sn_costmap_*: the tail of the chain, with state as sn_temporal: a lane per object, plus the int16 maps, the beam table and
+// per stream the "fresh" flag and the last origin.  host mode: occ, ranges, grid, logodds, stats
+struct sn_costmap_slots {
+  enum { kOcc = 0, kRanges, kGrid, kLog, kStats, kCount };
+};
+struct sn_costmap : Lane<sn_costmap_slots> {
+  sn_handle* h = nullptr;            // nullptr: a host-only object that serves sn_costmap_pose_q alone
+  int streams = 0;
+  sn_costmap_params p{};
+  int gw = 0, gh = 0, beams = 0;
+  double k256 = 0.0;
+  long long gx0 = 0, gy0 = 0, margin = 0, rmin = 0, cmax = 0;
+  int16_t* state = nullptr;          // device [streams][mh][mw]
+  float* edges = nullptr;            // device [beams + 1]
+  std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
+  std::vector<int> ox, oy;           // per stream: the origin of its last frame
 };
 
 // sn_rectify_*: the head of the chain: a lane per object, plus the two maps.  host mode: the eyes' source spans (one merged

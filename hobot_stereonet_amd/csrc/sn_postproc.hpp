@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles and ground plane.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp and sn_ground.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane and costmap.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp and sn_costmap.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -1399,6 +1399,188 @@ int sn_rectify_nv12(sn_rectify* r, int n, const uint8_t* left, const uint8_t* ri
   if (dten) {
     const int e = sbs_to_tensors(h, st, n, dsbs, 2 * h->W, h->H, false, dten);
     if (e) return e;
+  }
+  return b.close();
+}
+
+// ---- rolling log-odds costmap (csrc/sn_costmap.hpp): an object with its own state and lane ----------------------------------------
+namespace {
+// llrint(v) for a finite v, values beyond +-lim taken as +-lim
+long long cm_llrint_sat(double v, double lim) { return v >= lim ? (long long)lim : (v <= -lim ? -(long long)lim : std::llrint(v)); }
+
+// the contract's q of one pose; false where sn_costmap_pose_q refuses it
+bool cm_pose_q(const sn_costmap* c, const double* pose, int32_t* q) {
+  const double x = pose[0], y = pose[1], yaw = pose[2], lim = 1073741824.0;
+  if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(yaw)) return false;
+  const double fx = x * c->k256, fy = y * c->k256;
+  if (!(std::fabs(fx) <= lim) || !(std::fabs(fy) <= lim)) return false;
+  const long long tx = std::llrint(fx), ty = std::llrint(fy);
+  q[0] = (int32_t)tx, q[1] = (int32_t)ty;
+  q[2] = (int32_t)std::llrint(std::cos(yaw) * lim), q[3] = (int32_t)std::llrint(std::sin(yaw) * lim);
+  q[4] = (int32_t)((tx >> 8) - c->p.mw / 2), q[5] = (int32_t)((ty >> 8) - c->p.mh / 2);
+  return true;
+}
+}  // namespace
+
+int sn_costmap_create(sn_handle* h, int streams, const sn_obstacle_params* op, const sn_costmap_params* p, sn_costmap** out) {
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_costmap_create: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!op || !p || !out) return refuse("a NULL pointer");
+  if (streams < 1 || (h && streams > h->max_batch)) return refuse("streams must be 1..max_batch");
+  if (p->mw < 1 || p->mh < 1 || p->mw > kCmMaxWindow || p->mh > kCmMaxWindow) return refuse("mw and mh must be 1..4096");
+  if (p->l_hit < 1 || p->l_hit > 32767 || p->l_miss < 1 || p->l_miss > 32767) return refuse("l_hit and l_miss must be 1..32767");
+  if (!(p->l_min >= -32767 && p->l_min < 0 && p->l_max > 0 && p->l_max <= 32767)) return refuse("-32767 <= l_min < 0 < l_max <= 32767 is required");
+  for (float v : {p->clear_margin_m, p->clear_min_m, p->clear_max_m, op->cell_m, op->x_min_m, op->y_min_m})
+    if (!std::isfinite(v)) return refuse("every parameter must be finite");
+  if (p->clear_margin_m < 0.f || p->clear_min_m < 0.f || p->clear_max_m < 0.f) return refuse("the clear_* distances must not be negative");
+  if (!(op->cell_m > 0.f)) return refuse("cell_m must be positive");
+  if (op->gw < 0 || op->gh < 0 || op->gw > kObMaxCells || op->gh > kObMaxCells || (op->gw == 0) != (op->gh == 0))
+    return refuse("gw and gh must be 1..4096, or both 0");
+  if (op->beams < 0 || op->beams > kObMaxBeams) return refuse("beams must be 0..4096");
+  if (op->gw == 0 && op->beams == 0) return refuse("neither a grid nor a scan");
+  std::vector<float> edges(op->beams + 1);
+  if (op->beams > 0 && !ob_beam_edges(op->beams, op->angle_min_rad, op->angle_increment_rad, edges.data()))
+    return refuse("the scan's sector must lie inside (-pi/2, pi/2) with increasing edges");
+  std::unique_ptr<sn_costmap> c(new sn_costmap);
+  c->h = h, c->streams = streams, c->p = *p;
+  c->gw = op->gw, c->gh = op->gh, c->beams = op->beams;
+  c->k256 = 256.0 / (double)op->cell_m;
+  const double far = 1099511627776.0, cap = 2147483648.0;      // 2^40, 2^31
+  c->gx0 = cm_llrint_sat((double)op->x_min_m / (double)op->cell_m * 256.0, far);
+  c->gy0 = cm_llrint_sat((double)op->y_min_m / (double)op->cell_m * 256.0, far);
+  c->margin = cm_llrint_sat((double)p->clear_margin_m * c->k256, cap);
+  c->rmin = cm_llrint_sat((double)p->clear_min_m * c->k256, cap);
+  c->cmax = cm_llrint_sat((double)p->clear_max_m * c->k256, cap);
+  c->fresh.assign(streams, 1);
+  c->ox.assign(streams, 0), c->oy.assign(streams, 0);
+  if (h) {      // without a handle: a host-only object for sn_costmap_pose_q
+    const int rc = check_device(h);
+    if (rc) return rc;
+    const size_t bytes = (size_t)streams * p->mw * p->mh * 2;
+    if (hipMalloc(reinterpret_cast<void**>(&c->state), bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->edges), edges.size() * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(c->state);
+      set_err(h, "sn_costmap_create: out of device memory");
+      return SN_ERR_NOMEM;
+    }
+    if (hipMemcpy(c->edges, edges.data(), edges.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(c->state);
+      (void)hipFree(c->edges);
+      set_err(h, "sn_costmap_create: the upload of the beam table failed");
+      return SN_ERR_DEVICE;
+    }
+    ++h->costmap_live;
+  }
+  *out = c.release();
+  return SN_OK;
+}
+
+int sn_costmap_reset(sn_costmap* c, int stream) {
+  if (!c) return SN_ERR_ARG;
+  if (stream < -1 || stream >= c->streams) {
+    set_err(c->h, "sn_costmap_reset: bad arguments");
+    return SN_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (stream < 0) std::fill(c->fresh.begin(), c->fresh.end(), (uint8_t)1);
+  else c->fresh[stream] = 1;
+  return SN_OK;
+}
+
+void sn_costmap_destroy(sn_costmap* c) {
+  if (!c) return;
+  if (c->h) {
+    (void)hipSetDevice(c->h->device);
+    c->destroy();
+    (void)hipFree(c->state);
+    (void)hipFree(c->edges);
+    --c->h->costmap_live;
+  }
+  delete c;
+}
+
+int sn_costmap_pose_q(const sn_costmap* c, const double pose[3], int32_t q[6]) {
+  return c && pose && q && cm_pose_q(c, pose, q) ? SN_OK : SN_ERR_ARG;
+}
+
+int sn_costmap_push(sn_costmap* c, int n, const int* stream_of, const double* poses, const int8_t* occ, const float* ranges,
+                    int8_t* grid, int16_t* logodds, uint32_t* stats, int32_t* pose_q_out, int mem, void* stream) {
+  if (!c || !c->h) return SN_ERR_ARG;
+  sn_handle* h = c->h;
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_costmap_push: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (n <= 0 || n > h->max_batch || !poses) return refuse("bad arguments");
+  if (c->gw == 0) occ = nullptr;
+  if (c->beams == 0) ranges = nullptr;
+  if (!occ && !ranges) return refuse("neither occ nor ranges");
+  if (!grid && !logodds && !stats) return refuse("no output");
+  for (int k = 0; stream_of && k < n; ++k)
+    if (stream_of[k] < 0 || stream_of[k] >= c->streams) return refuse("a stream id out of range");
+  if (((uintptr_t)logodds & 1) || ((uintptr_t)stats & 3) || ((uintptr_t)ranges & 3)) return refuse("a misaligned buffer");
+  std::vector<int32_t> q((size_t)n * 6);
+  for (int k = 0; k < n; ++k)
+    if (!cm_pose_q(c, poses + 3 * k, q.data() + 6 * k)) return refuse("a pose that is not finite or too far from the origin");
+  const size_t cells = (size_t)c->p.mw * c->p.mh, ocells = (size_t)c->gw * c->gh;
+  {
+    const Span i0{occ, n * ocells}, i1{ranges, (size_t)n * c->beams * 4}, o0{grid, n * cells}, o1{logodds, n * cells * 2},
+        o2{stats, (size_t)n * 16};
+    if (overlap({i0, i1}, {o0, o1, o2}) || overlap({o0}, {o1, o2}) || overlap({o1}, {o2})) return refuse("overlapping buffers");
+  }
+  using T = sn_costmap;
+  Bracket b(h, "sn_costmap_push", mem, stream, *c);      // the wait: the previous push (any stream) is done with the state too
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  const int8_t* docc = occ ? s.in(T::kOcc, occ, n * ocells) : nullptr;
+  const float* dranges = ranges ? s.in(T::kRanges, ranges, (size_t)n * c->beams * 4) : nullptr;
+  int8_t* dgrid = s.out(T::kGrid, grid, n * cells);
+  int16_t* dlog = s.out(T::kLog, logodds, n * cells * 2);
+  uint32_t* dstats = s.out(T::kStats, stats, (size_t)n * 16);
+  if (s.rc) return s.rc;
+  if (pose_q_out) memcpy(pose_q_out, q.data(), q.size() * 4);
+  CmArgs a{};
+  a.edges = c->edges, a.L = c->state, a.k256 = c->k256;
+  a.gx0 = c->gx0, a.gy0 = c->gy0, a.margin = c->margin, a.rmin = c->rmin, a.cmax = c->cmax;
+  a.mw = c->p.mw, a.mh = c->p.mh, a.gw = c->gw, a.gh = c->gh, a.beams = c->beams;
+  a.l_hit = c->p.l_hit, a.l_miss = c->p.l_miss, a.l_min = c->p.l_min, a.l_max = c->p.l_max;
+  if (dstats) HIP_TRY(h, hipMemsetAsync(dstats, 0, (size_t)n * 16, st));
+  const unsigned chunks = (unsigned)((cells + 255) / 256);
+  const size_t lds = dranges ? (size_t)(3 * c->beams + 1) * 4 : 0;      // E, and Rb twice
+  for (int k0 = 0; k0 < n; k0 += kCmSlice) {      // the frame lists and the poses of kCmSlice maps fit the kernel arguments
+    const int m = std::min(kCmSlice, n - k0);
+    a.occ = docc ? docc + k0 * ocells : nullptr;
+    a.ranges = dranges ? dranges + (size_t)k0 * c->beams : nullptr;
+    a.grid = dgrid ? dgrid + k0 * cells : nullptr;
+    a.logodds = dlog ? dlog + k0 * cells : nullptr;
+    a.stats = dstats ? dstats + (size_t)k0 * 4 : nullptr;
+    memcpy(a.q, q.data() + (size_t)k0 * 6, (size_t)m * 24);
+    int groups = 0, filled = 0;      // group the slice's maps by stream, in order of first appearance, each in the order of k
+    for (int k = 0; k < m; ++k) {
+      const int id = stream_of ? stream_of[k0 + k] : 0;
+      bool known = false;
+      for (int g = 0; g < groups && !known; ++g) known = a.stream[g] == id;
+      if (!known) a.stream[groups++] = id;
+    }
+    int last[kCmSlice];      // per group: its last map of the slice
+    for (int g = 0; g < groups; ++g) {
+      const int id = a.stream[g];
+      a.first[g] = filled;
+      a.fresh[g] = c->fresh[id], a.pox[g] = c->ox[id], a.poy[g] = c->oy[id];
+      for (int k = 0; k < m; ++k)
+        if ((stream_of ? stream_of[k0 + k] : 0) == id) a.map[filled++] = k, last[g] = k;
+    }
+    a.first[groups] = filled;
+    hipLaunchKernelGGL(k_costmap, dim3(chunks, groups), dim3(256), lds, st, a);
+    HIP_TRY(h, hipGetLastError());
+    for (int g = 0; g < groups; ++g) {      // enqueued: the state now holds these frames
+      const int id = a.stream[g];
+      c->fresh[id] = 0, c->ox[id] = a.q[last[g]][4], c->oy[id] = a.q[last[g]][5];
+    }
   }
   return b.close();
 }

@@ -8,7 +8,7 @@ D1) needed to score the output against dataset ground truth.
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
         [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]] \
-        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE]
+        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -75,6 +75,12 @@ smallest range, null without a return).
 <i>.ground.pgm (the labels: no measurement 0, no plane 48, above 96, below 160, ground 255) are written into --out; the summary gains
 per pair "ground_found", "height_m", "pitch_deg", "roll_deg" and "inliers".  With --obstacles the grid and the scan use the mount
 the fit hands back (the file's own prior where no plane was found) instead of the obstacle file's base_from_cam.
+
+--costmap PARAMS_FILE[,POSES_FILE] (costmap.save_params' `key value` lines; needs --obstacles) treats the list as ONE clip and
+accumulates every frame's grid and scan on the GPU (`sn_costmap_push`) into a rolling log-odds map with ray clearing that
+travels with the robot.  POSES_FILE holds one `x y yaw` line per pair (metres and radians in the map's fixed frame); without
+it every pair stands at the origin.  <i>.costmap.pgm (0 occupied .. 255 free, 128 unknown, world x up) is written into --out;
+the summary gains "costmap": per pair "known", "occupied" (cells with positive log-odds), "hit" and "cleared" (cells this frame).
 """
 import argparse
 import json
@@ -150,7 +156,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None, view=None, obstacle=None, ground=None) -> List[dict]:
+                jpeg=None, view=None, obstacle=None, ground=None, costmap=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -181,7 +187,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     map, `camera` as for the cloud), "occupied", "free" and "nearest_m"; <i>.grid.pgm and <i>.scan.txt are written.
     ground = a ground.GroundParams: the record gains "ground" (the record of engine.ground of the final map) and "ground_labels",
     "ground_found", "height_m", "pitch_deg", "roll_deg" and "inliers"; <i>.ground.txt and <i>.ground.pgm are written, and the
-    obstacle stage takes the record's mount."""
+    obstacle stage takes the record's mount.
+    costmap = (costmap.CostmapParams, poses (n, 3) or None), with `obstacle`: the list is one clip; one api.Costmap lives for the
+    call and takes every frame's "occ" and "ranges" at the frame's pose (None: the origin); the record gains "costmap" (the int8
+    grid), "costmap_q" and "costmap_stats" = {"known", "occupied", "hit", "cleared"}, and <i>.costmap.pgm is written."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -192,13 +201,22 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     w, h = engine.width, engine.height
     results = []
     tf = engine.temporal_filter(1, *temporal) if temporal is not None else None
-    rect = None
+    rect = cm = None
+    if costmap is not None:
+        if obstacle is None:
+            raise FileListError("the costmap needs the obstacle stage")
+        if costmap[1] is not None and len(costmap[1]) != len(left):
+            raise FileListError(f"Poses size error! left_imgs.size: {len(left)}, poses.size: {len(costmap[1])}")
     try:
+        if costmap is not None:
+            cm = (engine.costmap(obstacle, costmap[0]), costmap[1])
         if rectify is not None:
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
-        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground)
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground, cm)
     finally:
+        if cm is not None:
+            cm[0].close()
         if rect is not None:
             rect.close()
         if tf is not None:
@@ -207,7 +225,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
 
 
 def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None,
-          obstacle=None, ground=None):
+          obstacle=None, ground=None, cm=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -282,6 +300,11 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             near = float(ranges.min()) if ranges.size else float("inf")
             rec.update(occ=occ, ranges=ranges, obstacle_stats=stats, occupied=int(stats[2]), free=int(stats[3]),
                        nearest_m=near if np.isfinite(near) else None)
+        if cm is not None:            # the clip's map after this frame
+            pose = np.zeros(3) if cm[1] is None else np.asarray(cm[1][i], np.float64)
+            grid, _, cstats, q = cm[0].push(pose, occ if obstacle.gw else None, ranges if obstacle.beams else None, want=(True, False, True))
+            rec.update(costmap=grid[0], costmap_q=q[0],
+                       costmap_stats=dict(zip(("known", "occupied", "hit", "cleared"), (int(v) for v in cstats[0]))))
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -331,6 +354,9 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
                     obs.write_pgm(os.path.join(out_dir, f"{i}.grid.pgm"), obs.grid_image(rec["occ"]))
                 if obstacle.beams:
                     obs.write_scan(os.path.join(out_dir, f"{i}.scan.txt"), obstacle, rec["ranges"])
+            if cm is not None:
+                from . import costmap as cmap
+                cmap.write_pgm(os.path.join(out_dir, f"{i}.costmap.pgm"), rec["costmap"])
             if rect is not None:
                 from . import rectify as rct
                 images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
@@ -391,6 +417,9 @@ def main(argv=None) -> int:
                     help="write <i>.ground.txt and <i>.ground.pgm: the ground plane of the final map, the mount it implies and the "
                          "per-pixel labels, made on the GPU with --camera or the rectifier's camera; --obstacles then uses that mount; "
                          "needs --out")
+    ap.add_argument("--costmap", default=None, metavar="PARAMS_FILE[,POSES_FILE]",
+                    help="write <i>.costmap.pgm: the list is one clip whose grids and scans accumulate on the GPU into a rolling "
+                         "log-odds map with ray clearing; POSES_FILE: one `x y yaw` line per pair (default: the origin); needs --obstacles")
     ap.add_argument("--render-true-colours", action="store_true", help="--render: the colour map's own colours, not the reference's R/B swap")
     ap.add_argument("--render-invalid-black", action="store_true", help="--render: pixels without a measurement (raw == 0) are black")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
@@ -518,13 +547,32 @@ def main(argv=None) -> int:
                 raise ValueError(why)
         except (OSError, ValueError) as e:
             ap.error(f"--ground {args.ground}: {e}")
+    cmap = None
+    if args.costmap is not None:
+        from . import costmap as cmod
+        if obstacle is None:
+            ap.error("--costmap needs --obstacles")
+        try:
+            files = args.costmap.split(",")
+            if len(files) > 2:
+                raise ValueError("takes PARAMS_FILE[,POSES_FILE]")
+            cparams = cmod.load_params(files[0])
+            why = cmod.check(cparams, obstacle)
+            if why:
+                raise ValueError(why)
+            cposes = cmod.load_poses(files[1]) if len(files) == 2 else None
+            for pose in (cposes if cposes is not None else []):
+                cmod.pose_q(cparams, obstacle, pose)
+            cmap = (cparams, cposes)
+        except (OSError, ValueError) as e:
+            ap.error(f"--costmap {args.costmap}: {e}")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams)
+                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -538,6 +586,8 @@ def main(argv=None) -> int:
     if obstacle is not None and recs:
         for k in ("occupied", "free", "nearest_m"):
             summary[k] = [r[k] for r in recs]
+    if cmap is not None and recs:
+        summary["costmap"] = {k: [r["costmap_stats"][k] for r in recs] for k in ("known", "occupied", "hit", "cleared")}
     if gparams is not None and recs:
         for k in ("ground_found", "height_m", "pitch_deg", "roll_deg", "inliers"):
             summary[k] = [r[k] for r in recs]

@@ -1134,6 +1134,92 @@ int sn_ground_gate(const sn_camera *cam, const sn_ground_params *p, int W, int H
 int sn_ground_from_raw(sn_handle *h, int n, const int32_t *raw, const sn_camera *cam, const sn_ground_params *p,
                        sn_ground *ground, uint8_t *labels, int mem, void *stream);
 
+/* ---- rolling log-odds costmap with ray clearing, one map per STREAM (csrc/sn_costmap.hpp; hobot_stereonet_amd/costmap.py is
+ * the numpy twin, byte for byte) --------------------------------------------------------------------------------------------------
+ * sn_obstacles_from_raw answers for one frame: a cell is free only where enough ground points landed in it, and the answer is
+ * forgotten at the next frame.  sn_costmap accumulates the grid and the scan over time as log-odds in a window that travels
+ * with the robot (costmap_2d's rolling window with an inverse sensor model), and clears the cells a beam crossed in front of
+ * its return.  It takes occ and ranges where the obstacle stage left them, and the robot's planar pose per frame.  Everything
+ * below the pose quantisation is integer apart from two single rounded double multiplies, so no tolerance appears anywhere.
+ *
+ * `op` is the block the caller gives the obstacle stage: cell_m, gw, gh, x_min_m, y_min_m describe the base-frame grid that
+ *   occ is in, beams, the angles and sn_obstacle_beam_edges describe ranges; the base frame is that stage's (x forward, y left).
+ *   The map's cells are cell_m wide as well.
+ * Units.  A "sub" is 1/256 of a cell.  Host quantities, in double, computed once (or per pose) and passed to the kernel as
+ *   integers, the one double k256 apart:
+ *     k256 = 256.0 / (double)cell_m,   gx0 = llrint((double)x_min_m / (double)cell_m * 256.0), gy0 likewise from y_min_m
+ *       (beyond +-2^40 taken as +-2^40: no cell reaches that far),
+ *     margin = llrint((double)clear_margin_m * k256), rmin and cmax likewise from clear_min_m and clear_max_m (above 2^31
+ *       taken as 2^31: r2 below stays under 2^42),
+ *   sn_costmap_pose_q (pure host, no device): q = {tx, ty, cq, sq, ox, oy} with tx = llrint(x * k256), ty likewise,
+ *     cq = llrint(cos(yaw) * 2^30), sq = llrint(sin(yaw) * 2^30), ox = (tx >> 8) - mw/2, oy = (ty >> 8) - mh/2 (>> arithmetic,
+ *     / integer division).  SN_ERR_ARG for a pose that is not finite or has |x| * k256 or |y| * k256 above 2^30.  Two
+ *     implementations of a double cos may differ by an ulp: a twin is fed the library's q, as it is fed the library's beam table.
+ * State per stream: int16 L[mh][mw], -32768 = unknown.  The map is a torus: world cell (cx, cy) lives in slot
+ *   (cx mod mw, cy mod mh) (floor modulo); after a frame with origin (ox, oy), slot (i, j) holds the world cell
+ *   cx = ox + ((i - ox) mod mw), cy = oy + ((j - oy) mod mh).  A fresh or reset stream is all unknown and has no previous origin.
+ * One frame of a stream, per slot, in this order:
+ *   1. Scroll.  Where the stream has a previous origin and the slot's world cell under it differs from the one under the new
+ *      origin, L = unknown (a jump of more than a window clears everything; nothing is copied).
+ *   2. The cell's centre in the base frame, in int64, >> arithmetic:
+ *        dx = cx*256 + 128 - tx, dy = cy*256 + 128 - ty,
+ *        bx = (cq*dx + sq*dy + 2^29) >> 30,   by = (-sq*dx + cq*dy + 2^29) >> 30
+ *   3. Grid observation.  qx = (bx - gx0) >> 8, qy = (by - gy0) >> 8; o = occ[qy][qx] inside 0..gw-1 x 0..gh-1, else -1.
+ *   4. Ray, only when bx > 0.  With E[i] = (double)edges[i], the cell is in the sector when E[0]*(double)bx <= (double)by and
+ *      not E[beams]*(double)bx <= (double)by; its beam b is (the number of i with E[i]*(double)bx <= (double)by) - 1 (each
+ *      comparison one rounded double product, monotone in i: a binary search).
+ *        Rb = ranges[b] finite and > 0 ? min((int64)floor((double)ranges[b] * k256), 2^31 - 1) : -1   (no return: clears nothing)
+ *        C = Rb - margin,  r2 = bx*bx + by*by,
+ *        ray = Rb >= 0 && C > 0 && r2 < C*C && r2 >= rmin*rmin && (cmax == 0 || r2 <= cmax*cmax)
+ *   5. Log-odds, with L0 = (L unknown ? 0 : L):  o == 100: L = min(L0 + l_hit, l_max), a hit;  otherwise, o == 0 || ray:
+ *      L = max(L0 - l_miss, l_min), cleared;  otherwise L stays.
+ * Outputs, unrolled in nav_msgs/OccupancyGrid order: element [cy - oy][cx - ox] of map k.
+ *   grid    int8  [n][mh][mw] = -1 for unknown, else ((L - l_min)*100 + (l_max - l_min)/2) / (l_max - l_min)
+ *   logodds int16 [n][mh][mw] = L
+ *   stats   [n][4] = {known cells, cells with L > 0, hits this frame, cleared this frame}
+ *   At least one of the three is required.  pose_q_out (nullable, HOST, [n][6]) receives the q of every map.
+ * sn_costmap_create: `streams` independent maps (1 <= streams <= max_batch) on handle h, all fresh; the state
+ *   (2 * mh * mw * streams bytes), the beam table, a stream, an event and the host-mode staging are the object's own.
+ *   h == NULL makes a host-only object (any streams >= 1) that serves sn_costmap_pose_q alone and touches no device;
+ *   sn_costmap_push on it is SN_ERR_ARG.
+ *   SN_ERR_ARG: a NULL pointer, streams out of range, mw or mh outside 1..4096, l_hit or l_miss outside 1..32767, not
+ *   -32767 <= l_min < 0 < l_max <= 32767, a negative clear_*, a float of p or cell_m, x_min_m, y_min_m that is not finite,
+ *   cell_m <= 0, gw or gh negative or > 4096 or only one of them 0, beams negative or > 4096, a sector sn_obstacle_beam_edges
+ *   refuses (beams > 0), neither a grid nor a scan.  While a costmap is alive sn_destroy(h) is REFUSED with SN_ERR_BUSY, as for
+ *   sn_temporal.
+ * sn_costmap_reset: stream `stream` (-1: all) is fresh again.  A host-side flag that takes effect at the next push.
+ *   SN_ERR_ARG: an id outside -1..streams-1.
+ * sn_costmap_push: n maps (1 <= n <= max_batch); map k is the next frame of stream stream_of[k] (a host array; NULL: all of
+ *   stream 0, one clip) at pose poses[k] = {x, y, yaw} (metres, radians; always HOST memory).  Maps with the same id are
+ *   consecutive frames in the order of k, and a push of n maps equals n single pushes in that order, bit for bit.
+ *   occ [n][gh][gw] and ranges [n][beams] as sn_obstacles_from_raw wrote them.  Either may be absent (occ NULL or gw == 0;
+ *   ranges NULL or beams == 0), but not both.
+ *   SN_ERR_ARG (sn_last_error(h) names the call; nothing is launched or written and no state changes): n out of range, poses
+ *     NULL, a pose sn_costmap_pose_q refuses, neither occ nor ranges usable, no output, an id outside 0..streams-1, logodds
+ *     misaligned (2 bytes), stats or ranges misaligned (4 bytes), overlapping buffers, a bad mem.
+ *   mem / stream as sn_temporal_push: a NULL stream is the costmap's own stream (never the inference stream); the call
+ *   returns after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller stream only enqueue, so
+ *   ground -> obstacles -> costmap run on one stream without a host round trip.  May run beside sn_submit / sn_wait and the
+ *   other stages; calls are serialised by the object's mutex.  One kernel launch per 64 maps of a call.
+ * Not covered: the asynchronous sn_submit* slots, inflation, decay of unobserved cells, 3-D voxels, clearing along beams
+ * without a return, poses with roll or pitch. */
+typedef struct sn_costmap_params {
+  int   mw, mh;                      /* window in cells, 1..4096 each */
+  int   l_hit, l_miss;               /* 1..32767 */
+  int   l_min, l_max;                /* -32767 <= l_min < 0 < l_max <= 32767 */
+  float clear_margin_m;              /* >= 0: a ray clears only up to this far in front of its return */
+  float clear_min_m, clear_max_m;    /* >= 0; clear_max_m == 0: no cap */
+} sn_costmap_params;
+typedef struct sn_costmap sn_costmap;
+int  sn_costmap_create(sn_handle *h, int streams, const sn_obstacle_params *op, const sn_costmap_params *p, sn_costmap **out);
+int  sn_costmap_reset(sn_costmap *c, int stream);
+void sn_costmap_destroy(sn_costmap *c);
+int  sn_costmap_pose_q(const sn_costmap *c, const double pose[3] /* x, y, yaw */, int32_t q[6]);   /* pure host */
+int  sn_costmap_push(sn_costmap *c, int n, const int *stream_of, const double *poses /* host [n][3] */,
+                     const int8_t *occ /* [n][gh][gw] */, const float *ranges /* [n][beams] */,
+                     int8_t *grid /* [n][mh][mw] */, int16_t *logodds /* [n][mh][mw] */, uint32_t *stats /* [n][4] */,
+                     int32_t *pose_q_out /* host [n][6], nullable */, int mem, void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
