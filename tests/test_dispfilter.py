@@ -1,6 +1,6 @@
 """Speckle removal and hole filling as the numpy twin (hobot_stereonet_amd/dispfilter.py) — no GPU.  The twin against
-implementations written here from the contract in include/stereonet_hip.h (a flood fill, a per-pixel scalar fill loop,
-scipy.ndimage.label), known answers at every boundary of the contract, and the agreement of the Python binding with the header."""
+implementations written from the contract in include/stereonet_hip.h (the flood fill and the per-pixel scalar fill loop of
+tests/golden/plain_refs.py, scipy.ndimage.label), known answers at every boundary of the contract, and the agreement of the Python binding with the header."""
 import ctypes as C
 import os
 import re
@@ -10,6 +10,7 @@ import pytest
 
 from hobot_stereonet_amd import api, dispfilter
 from hobot_stereonet_amd.dispfilter import FILLED, INVALID_IN, SPECKLE
+from plain_refs import filter_independent as _independent
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "stereonet_hip.h")).read()
@@ -22,65 +23,6 @@ def _px(dq):
     d = (dq + 0.5) * S
     assert dispfilter.diff_units(d) == dq
     return d
-
-
-def _flood_speckles(raw, dq, max_px):
-    """The contract's stage 1 by flood fill, Python integers throughout -> (M, removed)."""
-    H, W = raw.shape
-    seen = np.zeros((H, W), bool)
-    M = np.where(raw > 0, raw, 0).astype(np.int32)
-    removed = np.zeros((H, W), bool)
-    for y in range(H):
-        for x in range(W):
-            if raw[y, x] <= 0 or seen[y, x]:
-                continue
-            stack, comp = [(y, x)], []
-            seen[y, x] = True
-            while stack:
-                a, b = stack.pop()
-                comp.append((a, b))
-                for c, d in ((a + 1, b), (a - 1, b), (a, b + 1), (a, b - 1)):
-                    if 0 <= c < H and 0 <= d < W and not seen[c, d] and raw[c, d] > 0 and \
-                            abs(int(raw[a, b]) - int(raw[c, d])) <= dq:
-                        seen[c, d] = True
-                        stack.append((c, d))
-            if len(comp) <= max_px:
-                for a, b in comp:
-                    M[a, b] = 0
-                    removed[a, b] = True
-    return M, removed
-
-
-def _scalar_fill(M, fill_max):
-    """The contract's stage 2, one pixel at a time -> (out, filled)."""
-    H, W = M.shape
-    out = M.copy()
-    filled = np.zeros((H, W), bool)
-    for v in range(H):
-        for u in range(W):
-            if M[v, u] > 0:
-                continue
-            ul = next((x for x in range(u - 1, -1, -1) if M[v, x] > 0), None)
-            ur = next((x for x in range(u + 1, W) if M[v, x] > 0), None)
-            if ul is None and ur is None:
-                continue
-            gap = (W if ur is None else ur) - (-1 if ul is None else ul) - 1
-            if gap <= fill_max:
-                out[v, u] = M[v, ur] if ul is None else (M[v, ul] if ur is None else min(M[v, ul], M[v, ur]))
-                filled[v, u] = True
-    return out, filled
-
-
-def _independent(raw, max_px, dq, fill_max):
-    M = np.where(raw > 0, raw, 0).astype(np.int32)
-    mask = np.where(raw <= 0, INVALID_IN, 0).astype(np.uint8)
-    if max_px:
-        M, removed = _flood_speckles(raw, dq, max_px)
-        mask[removed] = SPECKLE
-    if fill_max:
-        M, filled = _scalar_fill(M, fill_max)
-        mask[filled] |= FILLED
-    return M, mask
 
 
 def test_twin_equals_flood_fill_and_scalar_fill_on_random_maps():

@@ -1,6 +1,6 @@
 """The left-right consistency check as its numpy twin (hobot_stereonet_amd/lrcheck.py) — no GPU.  Analytic occlusion scenes
 (everything the right eye cannot see is rejected, and little else), mirrored storage, reason priority and corner values against
-a per-pixel scalar transcription of the contract in include/stereonet_hip.h, the eye-swapping mirror, and the agreement of the
+a per-pixel scalar transcription of the contract in include/stereonet_hip.h (tests/golden/plain_refs.py), the eye-swapping mirror, and the agreement of the
 Python binding with the header."""
 import ctypes as C
 import os
@@ -11,6 +11,7 @@ import pytest
 
 from hobot_stereonet_amd import api, lrcheck
 from hobot_stereonet_amd.lrcheck import INCONSISTENT, INVALID_IN, KEPT, NO_PARTNER, OUT_OF_VIEW
+from plain_refs import lrcheck_scalar as _scalar_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "stereonet_hip.h")).read()
@@ -20,44 +21,6 @@ f32 = np.float32
 
 def _to_raw(d):
     return np.rint(np.asarray(d, np.float64) / np.float64(S)).astype(np.int32)
-
-
-def _scalar_reference(L, R, tau_px, tau_rel, mirrored):
-    """The contract, one pixel at a time, every operation a float32 scalar operation."""
-    L = np.asarray(L, np.int32)
-    R = np.asarray(R, np.int32)
-    H, W = L.shape
-    mask = np.zeros((H, W), np.uint8)
-    for v in range(H):
-        for u in range(W):
-            def Rx(x):
-                return int(R[v, W - 1 - x] if mirrored else R[v, x])
-            rl = int(L[v, u])
-            if rl <= 0:
-                mask[v, u] = INVALID_IN
-                continue
-            d = f32(rl) * S
-            xr = f32(u) - d
-            if xr < 0:
-                mask[v, u] = OUT_OF_VIEW
-                continue
-            x0 = int(np.floor(xr))
-            t = xr - f32(x0)
-            x1 = min(x0 + 1, W - 1)
-            r0, r1 = Rx(x0), Rx(x1)
-            d0, d1 = f32(r0) * S, f32(r1) * S
-            if r0 <= 0 and r1 <= 0:
-                mask[v, u] = NO_PARTNER
-                continue
-            if r0 <= 0:
-                dr = d1
-            elif r1 <= 0:
-                dr = d0
-            else:
-                dr = d0 + t * (d1 - d0)
-            if not (abs(d - dr) <= f32(tau_px) + f32(tau_rel) * d):
-                mask[v, u] = INCONSISTENT
-    return np.where(mask == KEPT, L, 0).astype(np.int32), mask, np.uint32((mask == KEPT).sum())
 
 
 # (W, d0, d1, a, b) -> occluded pixels, out-of-view pixels, further rejected columns per row

@@ -1,5 +1,5 @@
 """Obstacle grid and laser scan from the int32 map (sn_obstacles_from_raw, hobot_stereonet_amd/obstacles.py) without a GPU: the
-numpy twin against an independent scalar loop written from the header's text, the beam table of the library against the
+numpy twin against an independent scalar loop written from the header's text (tests/golden/plain_refs.py), the beam table of the library against the
 twin's, the struct in the header against its ctypes mirror, a known answer (a ground plane and a wall), and the parameter file."""
 import ctypes as C
 import math
@@ -9,68 +9,14 @@ import re
 import numpy as np
 import pytest
 
-from hobot_stereonet_amd import api, obstacles, spec
+from hobot_stereonet_amd import api, obstacles
 from hobot_stereonet_amd.obstacles import ObstacleParams
 from hobot_stereonet_amd.pointcloud import Camera
+from plain_refs import obstacles_scalar_loop as _scalar_loop
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 f32 = np.float32
 INT32_MIN = -(1 << 31)
-
-
-def _scalar_loop(raw, cam, p, edges):
-    """sn_obstacles_from_raw's contract one point at a time, np.float32 scalars, every operation rounded on its own."""
-    n, H, W = raw.shape
-    s = cam.step
-    Ho, Wo = -(-H // s), -(-W // s)
-    m = [f32(v) for v in p.base_from_cam]
-    if not any(float(v) != 0.0 for v in m):
-        m = [f32(v) for v in (0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0)]
-    fx, fy, cx, cy = f32(cam.fx), f32(cam.fy), f32(cam.cx), f32(cam.cy)
-    fB = fx * f32(cam.baseline_mm)
-    zmin, zmax = f32(cam.z_min_m), f32(cam.z_max_m)
-    gw, gh = p.gw, p.gh
-    hits = np.zeros((n, gh, gw, 2), np.uint32)
-    height = np.full((n, gh, gw), INT32_MIN, np.int64)
-    ranges = np.full((n, p.beams), np.inf, f32)
-    for k in range(n):
-        for i in range(Ho):
-            for j in range(Wo):
-                u, v = j * s, i * s
-                r = int(raw[k, v, u])
-                if r <= 0:
-                    continue
-                dis = f32(r) * f32(spec.OUT_SCALE)
-                Z = f32(np.float64(fB) / (np.float64(dis) * 16.0 * 12.0) / 1000.0)
-                if not (zmin <= Z and (zmax <= 0 or Z <= zmax)):
-                    continue
-                X = f32(f32(f32(u) - cx) * Z) / fx
-                Y = f32(f32(f32(v) - cy) * Z) / fy
-                xb, yb, zb = (f32(f32(f32(m[4 * q] * X) + f32(m[4 * q + 1] * Y)) + f32(m[4 * q + 2] * Z)) + m[4 * q + 3] for q in range(3))
-                ground = f32(p.z_floor_m) <= zb <= f32(p.z_lo_m)
-                obstacle = f32(p.z_lo_m) < zb <= f32(p.z_hi_m)
-                if not (ground or obstacle):
-                    continue
-                if gw:
-                    qx = f32(math.floor(f32(xb - f32(p.x_min_m)) / f32(p.cell_m)))
-                    qy = f32(math.floor(f32(yb - f32(p.y_min_m)) / f32(p.cell_m)))
-                    if 0 <= qx < f32(gw) and 0 <= qy < f32(gh):
-                        hits[k, int(qy), int(qx), 0 if obstacle else 1] += 1
-                        if obstacle:
-                            height[k, int(qy), int(qx)] = max(height[k, int(qy), int(qx)], math.floor(f32(zb * f32(1000.0))))
-                if p.beams and obstacle and xb > 0:
-                    t = yb / xb
-                    if edges[0] <= t < edges[p.beams]:
-                        rr = f32(np.sqrt(f32(f32(xb * xb) + f32(yb * yb))))
-                        if f32(p.range_min_m) <= rr <= f32(p.range_max_m):
-                            beam = sum(1 for e in edges if e <= t) - 1
-                            ranges[k, beam] = min(ranges[k, beam], rr)
-    occ = np.full((n, gh, gw), -1, np.int8)
-    occ[hits[..., 1] >= p.min_ground_hits] = 0
-    occ[hits[..., 0] >= p.min_obstacle_hits] = 100
-    stats = np.stack([hits[..., 0].sum(axis=(1, 2)), hits[..., 1].sum(axis=(1, 2)), (occ == 100).sum(axis=(1, 2)), (occ == 0).sum(axis=(1, 2))],
-                     axis=1).astype(np.uint32) if gw else np.zeros((n, 4), np.uint32)
-    return occ, hits, height.astype(np.int32), ranges, stats
 
 
 def _maps_24x16(seed):

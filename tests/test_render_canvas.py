@@ -3,17 +3,15 @@ the numpy twin (hobot_stereonet_amd/render.py) against the reference-mode twin (
 (RenderCanvas) and against the host JPEG encoder; then what the picture is worth beside PIL's own encoder.
 
 No tolerance appears except in the picture-quality test: the contract is the same bytes."""
-import ctypes as C
-import functools
 import io
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from hobot_stereonet_amd import jpeg, render, synth
+from plain_refs import host_canvas as _host_canvas, hostlib as _hostlib, render_params_arrays as _params_arrays
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 COMPAT = os.path.join(ROOT, "hobot_stereonet_amd", "csrc", "compat")
@@ -23,28 +21,6 @@ QUALITY_FILE = os.path.join(ROOT, "profiles", "render_canvas_quality.txt")
 # the three frames below; measured first, then fixed here with the 10 % the issue allows on top.
 MEASURED_QUALITY_RATIO = 1.0356
 QUALITY_MARGIN = 0.10
-
-
-@functools.lru_cache(maxsize=None)
-def _hostlib():
-    san = os.environ.get("SN_SANITIZE") == "1"       # scripts/run_sanitized.sh: the ASan + UBSan build of the mirror
-    from hobot_stereonet_amd import build
-    build.build()
-    subprocess.check_call(["make", "-C", COMPAT, "-s"] + (["asan"] if san else []))
-    import torch  # noqa: F401  (before anything that links HIP: one HIP runtime per process, see api.load_library)
-    lib = C.CDLL(os.path.join(COMPAT, "build", "asan" if san else "", "libhobot_stereonet_node.so"))
-    vp, ci = C.c_void_p, C.c_int
-    lib.snhost_render.argtypes = [vp, C.c_long, ci, ci, vp, vp, vp, vp, vp]
-    lib.snhost_render_tables.argtypes = [vp, vp, vp, vp]
-    lib.snhost_render_canvas.argtypes = [ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, ci, C.c_long]
-    lib.snhost_jpeg_nv12_sliced.restype = C.c_long
-    lib.snhost_jpeg_nv12_sliced.argtypes = [vp, ci, ci, ci, ci, ci, vp, C.c_long]
-    return lib
-
-
-def _params_arrays(p):
-    return (np.array([p.scale, p.focal_px, p.baseline_mm, p.alpha], np.float64),
-            np.array([p.layout, p.colormap, p.true_colours, p.invalid_black], np.int32))
 
 
 def _content(n, h, w, seed):
@@ -134,22 +110,6 @@ def test_reference_mode_equals_stack_joint():
     got = render.canvas(raw, left, w, render.RenderParams(), render.RGB8)[0]
     assert np.array_equal(got, joint) and np.array_equal(got[h:], color)
     assert np.array_equal(render.canvas(raw, None, 0, render.RenderParams(layout=render.DEPTH), render.RGB8)[0], color)
-
-
-def _host_canvas(n, raw, left, pitch, w, h, p, fmt, pad):
-    lib = _hostlib()
-    hc = h * (2 if p.layout == render.STACK else 1)
-    rows = hc + hc // 2 if fmt == render.NV12 else hc
-    row_bytes = w if fmt == render.NV12 else 3 * w
-    out_pitch = row_bytes + pad
-    out = np.full((n, rows, out_pitch), 0x5a, np.uint8)
-    dp, ip = _params_arrays(p)
-    rc = lib.snhost_render_canvas(n, raw.ctypes.data, left.ctypes.data if left is not None else None, pitch, w, h, dp.ctypes.data,
-                                  ip.ctypes.data, fmt, out.ctypes.data, out_pitch, rows * out_pitch)
-    assert rc == 0
-    assert np.all(out[:, :, row_bytes:] == 0x5a), "the pitch padding is not written"
-    body = out[:, :, :row_bytes]
-    return body.reshape(n, hc, w, 3) if fmt == render.RGB8 else body
 
 
 FLAGS = list(itertools.product((render.RGB8, render.NV12), (render.STACK, render.DEPTH), (render.CMAP_JET, render.CMAP_GREY), (0, 1), (0, 1)))

@@ -1,43 +1,12 @@
 """The numpy twin of sn_smooth_raw (hobot_stereonet_amd/smooth.py) against a per-pixel loop written straight from the header
-text, hand-computed answers, the weight table, and the invariants of mask and counts.  No GPU."""
+text (tests/golden/plain_refs.py), hand-computed answers, the weight table, and the invariants of mask and counts.  No GPU."""
 import numpy as np
 import pytest
 
 from hobot_stereonet_amd import smooth
+from plain_refs import smooth_brute as brute
 
 IMAX, IMIN = 2 ** 31 - 1, -2 ** 31
-
-
-def brute(raw, luma, radius, sigma, min_valid):
-    """include/stereonet_hip.h, sn_smooth_raw, word for word: collect the participants, sort, scan."""
-    H, W = raw.shape
-    s = sigma
-    T = [1] * 256 if s == 0 else [(256 * s * s) // (s * s + j * j) for j in range(256)]
-    out = np.zeros((H, W), np.int32)
-    mask = np.zeros((H, W), np.uint8)
-    for v in range(H):
-        for u in range(W):
-            part, measured = [], 0
-            for y in range(max(0, v - radius), min(H, v + radius + 1)):
-                for x in range(max(0, u - radius), min(W, u + radius + 1)):
-                    if raw[y, x] > 0:
-                        measured += 1
-                        wq = T[abs(int(luma[y, x]) - int(luma[v, u]))] if s else 1
-                        if wq > 0:
-                            part.append((int(raw[y, x]), wq))
-            wt = sum(wq for _, wq in part)
-            m = None
-            for val in sorted({val for val, _ in part}):
-                if 2 * sum(wq for v2, wq in part if v2 <= val) >= wt:
-                    m = val
-                    break
-            if raw[v, u] > 0:
-                res = m
-            else:
-                res = m if (min_valid > 0 and measured >= min_valid and wt > 0) else 0
-            out[v, u] = res
-            mask[v, u] = (1 if raw[v, u] <= 0 else 0) | (128 if res != max(int(raw[v, u]), 0) else 0)
-    return out, mask
 
 
 def random_map(rng, w=24, h=16):

@@ -1,5 +1,5 @@
 """The temporal filter's numpy twin (hobot_stereonet_amd/temporal.py) against a per-pixel Python loop written from the header
-text of sn_temporal_push, hand-computed pixel histories, the mask values the test clip must produce (the condition that keeps
+text of sn_temporal_push (tests/golden/plain_refs.py), hand-computed pixel histories, the mask values the test clip must produce (the condition that keeps
 the GPU comparison from passing on an idle filter), interleaved streams, what the filter buys on the clip's static part, and
 the binding against the header.  No GPU."""
 import ctypes as C
@@ -13,6 +13,7 @@ import pytest
 
 from hobot_stereonet_amd import api, dispfilter, temporal
 from hobot_stereonet_amd.temporal import BLENDED, HELD, INVALID_IN, JUMP, MOVED
+from plain_refs import temporal_loop as _loop
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 COMPAT = os.path.join(ROOT, "hobot_stereonet_amd", "csrc", "compat")
@@ -22,45 +23,6 @@ S = float(temporal.wire_scale())
 # (alpha, q, persist, luma_delta) with q = delta_px in raw units, and the mask values the clip must produce for each
 SETTINGS = {(64, 1000, 2, 24): {0, 1, 2, 5, 8, 9, 16}, (256, 0, 1, 0): {0, 1, 5, 16},
             (128, 400, 0, 24): {0, 1, 2, 8, 9, 16}, (64, 1000, 8, 0): {0, 1, 2, 5, 16}}
-
-
-def _loop(raw, luma, alpha, q, persist, luma_delta):
-    """The contract, one pixel and one frame at a time, in Python integers (nothing can overflow)."""
-    T, H, W = raw.shape
-    out, mask = np.zeros(raw.shape, np.int64), np.zeros(raw.shape, np.uint8)
-    for v, u in itertools.product(range(H), range(W)):
-        P, Hs, Yp = 0, 0, None
-        for t in range(T):
-            r, y = max(int(raw[t, v, u]), 0), int(luma[t, v, u])
-            moved = luma_delta > 0 and Yp is not None and abs(y - Yp) > luma_delta
-            bits = 0
-            if r > 0:
-                if P > 0 and not moved and abs(r - P) <= q:
-                    o = (alpha * r + (256 - alpha) * P + 128) >> 8
-                    assert o >= 1
-                    bits = BLENDED if o != r else 0
-                else:
-                    o = r
-                    if P > 0:
-                        bits = MOVED if moved else JUMP
-                P = o
-            else:
-                bits = INVALID_IN
-                if persist > 0 and P > 0 and not moved and bin(Hs).count("1") >= persist:
-                    o = P
-                    bits |= HELD
-                else:
-                    o = 0
-                    if P > 0 and moved:
-                        bits |= MOVED
-                        P = 0
-            Hs = ((Hs << 1) | (r > 0)) & 255
-            if Hs == 0:
-                P = 0
-            Yp = y
-            out[t, v, u], mask[t, v, u] = o, bits
-    assert out.min() >= 0 and out.max() <= IMAX
-    return out.astype(np.int32), mask
 
 
 def _corner_clip(seed):
