@@ -170,6 +170,19 @@ def costmap_params(p) -> SnCostmapParams:
     return SnCostmapParams(p.mw, p.mh, p.l_hit, p.l_miss, p.l_min, p.l_max, p.clear_margin_m, p.clear_min_m, p.clear_max_m)
 
 
+class SnInflateParams(C.Structure):
+    """sn_inflate_params (include/stereonet_hip.h); inflate.InflateParams is the Python face of it."""
+    _fields_ = [("cell_m", C.c_float), ("inscribed_radius_m", C.c_float), ("inflation_radius_m", C.c_float), ("cost_scaling", C.c_float),
+                ("lethal_min", C.c_int), ("flags", C.c_int)]
+
+
+def inflate_params(p) -> SnInflateParams:
+    """inflate.InflateParams -> sn_inflate_params"""
+    if isinstance(p, SnInflateParams):
+        return p
+    return SnInflateParams(p.cell_m, p.inscribed_radius_m, p.inflation_radius_m, p.cost_scaling, p.lethal_min, p.flags)
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -337,6 +350,8 @@ def load_library(path: Optional[str] = None):
     lib.sn_costmap_destroy.restype = None
     lib.sn_costmap_pose_q.argtypes = [vp, vp, i32p]
     lib.sn_costmap_push.argtypes = [vp, ip, vp, vp, i8p, fp, i8p, vp, vp, i32p, ip, vp]
+    lib.sn_inflate_table.argtypes = [C.POINTER(SnInflateParams), u8p, C.POINTER(C.c_int)]
+    lib.sn_inflate_grid.argtypes = [vp, ip, i8p, ip, ip, C.POINTER(SnInflateParams), u8p, i8p, vp, vp, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -350,7 +365,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_inflate_table", "sn_inflate_grid", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -454,6 +469,20 @@ def costmap_pose_q(params, obstacle, poses) -> np.ndarray:
     finally:
         lib.sn_costmap_destroy(c)
     return q[0] if np.ndim(poses) == 1 else q
+
+
+def inflate_table(params) -> np.ndarray:
+    """sn_inflate_table (host only): uint8 (R*R + 1,), the cost of every squared distance in cells up to the inflation radius;
+    inflate.table is the Python twin (an entry of the fall-off may differ by one: two implementations of a double exp)."""
+    lib, prm, R = load_library(), inflate_params(params), C.c_int(0)
+    rc = lib.sn_inflate_table(C.byref(prm), None, C.byref(R))
+    if rc:
+        raise StereoNetError(rc, "sn_inflate_table")
+    T = np.empty(R.value * R.value + 1, np.uint8)
+    rc = lib.sn_inflate_table(C.byref(prm), T.ctypes.data, None)
+    if rc:
+        raise StereoNetError(rc, "sn_inflate_table")
+    return T
 
 
 def error_string(code: int) -> str:
@@ -761,6 +790,30 @@ class StereoNetHIP:
         self._check(self._lib.sn_obstacles_from_raw(self._h, n, raw_ptr, C.byref(c), C.byref(prm), occ_ptr or None, hits_ptr or None,
                                                     height_ptr or None, ranges_ptr or None, stats_ptr or None, SN_MEM_DEVICE,
                                                     stream or None), "sn_obstacles_from_raw")
+
+    # -- inflation by the robot's radius ------------------------------------------------------------------
+    def inflate(self, occ: np.ndarray, params, want=(True, True, True, True)):
+        """sn_inflate_grid on host buffers: occ int8 (gh, gw) or (n, gh, gw), as obstacles() or Costmap.push() give it ->
+        (cost uint8, grid int8, dist2 uint16 (each (n, gh, gw)), stats uint32 (n, 5)), None where `want` says an output is not
+        asked for, leading n dropped for a 2-D occ; inflate.reference is the numpy twin.  params: inflate.InflateParams."""
+        o = np.ascontiguousarray(occ, np.int8)
+        if o.ndim not in (2, 3):
+            raise StereoNetError(-1, "inflate", f"occ of shape {o.shape}: (gh, gw) or (n, gh, gw) is needed")
+        n, (gh, gw) = (1 if o.ndim == 2 else o.shape[0]), o.shape[-2:]
+        prm = inflate_params(params)
+        shapes = ((n, gh, gw), (n, gh, gw), (n, gh, gw), (n, 5))
+        outs = [np.zeros(s, d) if w else None for s, d, w in zip(shapes, (np.uint8, np.int8, np.uint16, np.uint32), want)]
+        self._check(self._lib.sn_inflate_grid(self._h, n, o.ctypes.data, gw, gh, C.byref(prm), *[_np_ptr(a) for a in outs], SN_MEM_HOST, None),
+                    "sn_inflate_grid")
+        return tuple(a if a is None or o.ndim == 3 else a[0] for a in outs)
+
+    def inflate_device(self, n: int, occ_ptr: int, gw: int, gh: int, params, cost_ptr: int = 0, grid_ptr: int = 0, dist2_ptr: int = 0,
+                       stats_ptr: int = 0, stream: int = 0):
+        """sn_inflate_grid on device pointers (0: that output is not wanted); stream = hipStream_t as int (0: the stage's own
+        stream, and the call returns after completion)."""
+        prm = inflate_params(params)
+        self._check(self._lib.sn_inflate_grid(self._h, n, occ_ptr or None, gw, gh, C.byref(prm), cost_ptr or None, grid_ptr or None,
+                                              dist2_ptr or None, stats_ptr or None, SN_MEM_DEVICE, stream or None), "sn_inflate_grid")
 
     # -- ground plane -----------------------------------------------------------------------------------
     def ground(self, raw: np.ndarray, cam, params, labels: bool = True):

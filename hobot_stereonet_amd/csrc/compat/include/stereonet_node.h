@@ -133,6 +133,13 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // turns it on and requires STEREONET_OBSTACLES; unset: off, nothing of it exists
     sn_costmap_params costmap_params{};
     std::string costmap_frame = "odom";
+    // this implementation's own: inflation by the robot's radius (sn_inflate_grid) of the grid a planner reads: nav_msgs/
+    // OccupancyGrid on /stereonet_inflated_grid with the header and info of its source, published right after it: the costmap's
+    // grid when the costmap is on, else the obstacle grid.  STEREONET_INFLATE=<parameter file> (inflate.save_params' `key value`
+    // lines; cell_m is the source grid's, whatever the file says) turns it on and requires STEREONET_OBSTACLES with a grid;
+    // unset: off, nothing of it exists
+    bool inflate = false;
+    sn_inflate_params inflate_params{};
   };
 
   void DeclareAndReadParameters();
@@ -145,6 +152,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void ReadGroundSettings();
   void ReadCostmapSettings();
   void PublishCostmap(const StereonetNodeOutput& request, const int8_t* occ, const float* ranges);
+  void ReadInflateSettings();
+  void PublishInflated(const nav_msgs::msg::OccupancyGrid& src);
   bool FitGround(const int32_t* raw, sn_ground* out);
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
   void ReadTemporalSettings();
@@ -176,6 +185,7 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   std::atomic<bool> render_no_frame_logged_{false};
   sn_costmap* costmap_ = nullptr;                // one stream; only while STEREONET_COSTMAP is set and valid
   rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr costmap_out_;
+  rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr inflated_out_;      // only while STEREONET_INFLATE is set and valid
   std::mutex base_pose_mu_;
   double base_pose_[3] = {0.0, 0.0, 0.0};        // x, y, yaw of SetBasePose
   sn_rectify* rectify_ = nullptr;                // only while STEREONET_RECTIFY names a valid calibration

@@ -109,6 +109,7 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
   if (cfg_.obstacles && cfg_.obstacle_params.beams)
     obstacle_scan_out_ = create_publisher<sensor_msgs::msg::LaserScan>("/stereonet_scan", 10);
   ReadCostmapSettings();
+  ReadInflateSettings();
   ReadTemporalSettings();
   ready_ = true;
 }
@@ -570,7 +571,8 @@ void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const i
     RCLCPP_ERROR(kLog, "obstacles failed: %s", sn_last_error(net_->engine()));
     return;
   }
-  // the costmap reads the frame's grid and scan after the messages that own them have left
+  // the costmap and the inflation read the frame's grid and scan after the messages that own them have left
+  nav_msgs::msg::OccupancyGrid inflate_src;
   std::vector<int8_t> occ_kept;
   std::vector<float> ranges_kept;
   if (costmap_) {
@@ -586,7 +588,9 @@ void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const i
     grid.info.height = p.gh;
     grid.info.origin.position.x = p.x_min_m;
     grid.info.origin.position.y = p.y_min_m;
+    if (cfg_.inflate && !costmap_) inflate_src = grid;      // the inflated grid follows this one
     obstacle_grid_out_->publish(std::move(grid));
+    if (cfg_.inflate && !costmap_) PublishInflated(inflate_src);
   }
   if (obstacle_scan_out_) {
     scan.header.stamp = request.msg_header->stamp;
@@ -710,7 +714,106 @@ void StereonetNode::PublishCostmap(const StereonetNodeOutput& request, const int
   map.info.height = p.mh;
   map.info.origin.position.x = (double)q[4] * (double)cfg_.obstacle_params.cell_m;
   map.info.origin.position.y = (double)q[5] * (double)cfg_.obstacle_params.cell_m;
+  nav_msgs::msg::OccupancyGrid inflate_src;
+  if (cfg_.inflate) inflate_src = map;      // the inflated grid follows this one
   costmap_out_->publish(std::move(map));
+  if (cfg_.inflate) PublishInflated(inflate_src);
+}
+
+namespace {
+// inflate.load_params' text form, as load_costmap_file
+bool load_inflate_file(const char* path, sn_inflate_params* p, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct FloatKey {
+    const char* name;
+    float* v;
+  } floats[] = {{"cell_m", &p->cell_m}, {"inscribed_radius_m", &p->inscribed_radius_m}, {"inflation_radius_m", &p->inflation_radius_m},
+                {"cost_scaling", &p->cost_scaling}};
+  struct IntKey {
+    const char* name;
+    int* v;
+  } ints[] = {{"lethal_min", &p->lethal_min}, {"flags", &p->flags}};
+  std::vector<std::string> seen;
+  std::string text;
+  for (int no = 1; std::getline(in, text); ++no) {
+    std::istringstream words(text.substr(0, text.find('#')));
+    std::string key, w;
+    if (!(words >> key)) continue;
+    std::vector<std::string> vals;
+    while (words >> w) vals.push_back(w);
+    const std::string at = "line " + std::to_string(no) + ": ";
+    for (const std::string& k : seen)
+      if (k == key) {
+        *err = at + key + " twice";
+        return false;
+      }
+    seen.push_back(key);
+    char* end = nullptr;
+    const double d = vals.size() == 1 ? strtod(vals[0].c_str(), &end) : 0.0;
+    const bool number = vals.size() == 1 && end != vals[0].c_str() && !*end;
+    bool known = false, ok = true;
+    for (const FloatKey& f : floats)
+      if (key == f.name) {
+        known = true, ok = number;
+        *f.v = (float)d;
+      }
+    for (const IntKey& f : ints)
+      if (key == f.name) {
+        known = true, ok = number && d >= -1e9 && d <= 1e9 && d == (double)(int)d;      // the range first: the cast of a larger double is undefined
+        if (ok) *f.v = (int)d;
+      }
+    if (!known || !ok) {
+      *err = at + (known ? "wrong values for " : "unknown key ") + key;
+      return false;
+    }
+  }
+  return true;
+}
+}  // namespace
+
+// parsed and validated once here: what sn_inflate_grid would refuse turns the stage off instead of failing every frame
+void StereonetNode::ReadInflateSettings() {
+  const char* e = getenv("STEREONET_INFLATE");
+  if (!e || !*e) return;
+  // inflate.InflateParams' defaults; the cell is that of the grid the stage follows, whatever the file says
+  sn_inflate_params& p = cfg_.inflate_params;
+  p = sn_inflate_params{0.05f, 0.2f, 0.4f, 10.f, 100, 0};
+  std::string bad;
+  int R = 0;
+  if (!cfg_.obstacles || !cfg_.obstacle_params.gw) bad = std::string("STEREONET_INFLATE=") + e + " requires STEREONET_OBSTACLES with a grid";
+  else if (!load_inflate_file(e, &p, &bad)) bad = std::string("STEREONET_INFLATE=") + e + ": " + bad;
+  else {
+    p.cell_m = cfg_.obstacle_params.cell_m;
+    if (sn_inflate_table(&p, nullptr, &R) != SN_OK) bad = std::string("STEREONET_INFLATE=") + e + ": parameters sn_inflate_table refuses";
+  }
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no inflated grid");
+    return;
+  }
+  cfg_.inflate = true;
+  inflated_out_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/stereonet_inflated_grid", 10);
+  RCLCPP_WARN_STREAM(kLog, "inflation: " << (costmap_ ? "/stereonet_costmap" : "/stereonet_obstacle_grid") << " on /stereonet_inflated_grid, inscribed "
+                                         << p.inscribed_radius_m << " m, out to " << p.inflation_radius_m << " m (" << R << " cells), scaling "
+                                         << p.cost_scaling << ", lethal from " << p.lethal_min);
+}
+
+// nav_msgs/OccupancyGrid of the costs after inflation: one sn_inflate_grid call on the grid just published, whose header and
+// info it takes
+void StereonetNode::PublishInflated(const nav_msgs::msg::OccupancyGrid& src) {
+  nav_msgs::msg::OccupancyGrid out;
+  out.header = src.header;
+  out.info = src.info;
+  out.data.resize(src.data.size());
+  if (sn_inflate_grid(net_->engine(), 1, src.data.data(), (int)src.info.width, (int)src.info.height, &cfg_.inflate_params, nullptr,
+                      out.data.data(), nullptr, nullptr, SN_MEM_HOST, nullptr) != SN_OK) {
+    RCLCPP_ERROR(kLog, "inflation failed: %s", sn_last_error(net_->engine()));
+    return;
+  }
+  inflated_out_->publish(std::move(out));
 }
 
 namespace {

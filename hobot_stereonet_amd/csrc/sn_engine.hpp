@@ -238,6 +238,7 @@ struct sn_handle {
   static constexpr unsigned ablate_x = 0;      // the shipping library has no ablation code: every test of it folds away
 #endif
   bool obstacle_rle = true;  // sn_obstacles_from_raw accumulates run-length per lane; SN_OBSTACLE_RLE=0: one set of atomics per point
+  int inflate_waves = 0;     // SN_INFLATE_WAVES: 4 or 16 waves per workgroup of k_inflate whatever the call's size; 0: by size (in_waves)
   bool tail_fuse = true;     // the streamed last block carries the head (tail form); SN_TAIL_FUSE=0: block + k_head_final_f16
   int fuse_mode = 4;         // SN_FUSE: 4 = streaming fused blocks (default), 0 = two launches per block
   unsigned* dump = nullptr;  // 2 KB device scratch: where lanes without an output pixel store (fused head)
@@ -326,6 +327,14 @@ struct sn_handle {
   struct Ground : Lane<GroundSlots> {
     Ground() { buf[kPinRaw].pinned = true; }
   } gnd;
+  // sn_inflate_grid.  the cost table of the last parameter block (device); host mode: occ, cost, grid, dist2, stats
+  struct InflateSlots {
+    enum { kTable = 0, kOcc, kCost, kGrid, kDist2, kStats, kCount };
+  };
+  struct Inflate : Lane<InflateSlots> {
+    bool cached = false;               // buf[kTable] holds the table of `key`
+    sn_inflate_params key{};
+  } inf;
   // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
   // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
   // lock: calls on one handle must not overlap.

@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane and costmap.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp and sn_costmap.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane, costmap and inflation.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp and sn_inflate.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -1582,6 +1582,78 @@ int sn_costmap_push(sn_costmap* c, int n, const int* stream_of, const double* po
       c->fresh[id] = 0, c->ox[id] = a.q[last[g]][4], c->oy[id] = a.q[last[g]][5];
     }
   }
+  return b.close();
+}
+
+// ---- inflation by the robot's radius (csrc/sn_inflate.hpp): a lane of the handle's; the cost table of the last parameter block
+// stays on the device, as the obstacle lane keeps its beam edges ------------------------------------------------------------------
+int sn_inflate_table(const sn_inflate_params* p, uint8_t* table, int* R) {
+  int r = 0;
+  if (in_params_check(p, &r)) return SN_ERR_ARG;
+  std::vector<uint8_t> T((size_t)r * r + 1);
+  if (!in_table(p, r, T.data())) return SN_ERR_ARG;
+  if (table) memcpy(table, T.data(), T.size());
+  if (R) *R = r;
+  return SN_OK;
+}
+
+int sn_inflate_grid(sn_handle* h, int n, const int8_t* occ, int gw, int gh, const sn_inflate_params* p, uint8_t* cost, int8_t* grid,
+                    uint16_t* dist2, uint32_t* stats, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_inflate_grid: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!p || !occ) return refuse("a NULL pointer");
+  if (n <= 0 || n > h->max_batch) return refuse("n outside 1..max_batch");
+  if (gw < 1 || gh < 1 || gw > kInMaxCells || gh > kInMaxCells) return refuse("gw and gh must be 1..4096");
+  int R = 0;
+  if (const char* why = in_params_check(p, &R)) return refuse(why);
+  if (!cost && !grid && !dist2 && !stats) return refuse("one of cost, grid, dist2 and stats is needed");
+  if (((uintptr_t)dist2 & 1) || ((uintptr_t)stats & 3)) return refuse("a misaligned buffer");
+  const size_t cells = (size_t)gw * gh, map_bytes = n * cells, stats_bytes = (size_t)n * 20;
+  {
+    const Span in{occ, map_bytes};
+    const Span out[4] = {{cost, map_bytes}, {grid, map_bytes}, {dist2, map_bytes * 2}, {stats, stats_bytes}};
+    for (int i = 0; i < 4; ++i) {
+      if (overlap({in}, {out[i]})) return refuse("overlapping buffers");
+      for (int j = i + 1; j < 4; ++j)
+        if (overlap({out[i]}, {out[j]})) return refuse("overlapping buffers");
+    }
+  }
+  using I = sn_handle::Inflate;
+  I& lane = h->inf;
+  Bracket b(h, "sn_inflate_grid", mem, stream, lane);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  InArgs a{};
+  a.occ = s.in(I::kOcc, occ, map_bytes);
+  a.cost = s.out(I::kCost, cost, map_bytes);
+  a.grid = s.out(I::kGrid, grid, map_bytes);
+  a.dist2 = s.out(I::kDist2, dist2, map_bytes * 2);
+  a.stats = s.out(I::kStats, stats, stats_bytes);
+  uint8_t* dtable = s.scratch<uint8_t>(I::kTable, (size_t)kInMaxR * kInMaxR + 1);
+  if (s.rc) return s.rc;
+  // The key is tested first, under the lane's lock: a call with the block of the one before builds no table and uploads none.
+  // A new block is rare: its table is built here (still nothing launched or written), uploaded behind the lane's earlier calls
+  // and waited for.
+  if (!lane.cached || memcmp(&lane.key, p, sizeof *p)) {
+    std::vector<uint8_t> T((size_t)R * R + 1);
+    if (!in_table(p, R, T.data())) return refuse("the cost table increases with the distance");
+    lane.cached = false;
+    HIP_TRY(h, hipMemcpyAsync(dtable, T.data(), T.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    lane.key = *p, lane.cached = true;
+  }
+  a.table = dtable;
+  a.gw = gw, a.gh = gh, a.R = R, a.lethal_min = p->lethal_min, a.flags = p->flags;
+  a.tiles_x = (gw + kInTileW - 1) / kInTileW;
+  const unsigned tiles = (unsigned)(a.tiles_x * ((gh + kInTileH - 1) / kInTileH));
+  if (a.stats) HIP_TRY(h, hipMemsetAsync(a.stats, 0, stats_bytes, st));
+  const bool wide = in_waves((long long)tiles * n, h->num_cu, h->inflate_waves) == 16;
+  if (wide) hipLaunchKernelGGL(k_inflate<16>, dim3(tiles, n), dim3(1024), 0, st, a);
+  else hipLaunchKernelGGL(k_inflate<4>, dim3(tiles, n), dim3(256), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
   return b.close();
 }
 

@@ -54,6 +54,7 @@ struct Switches {
   bool no_graph = false;                   // SN_NO_GRAPH | unset | create | presence: no hipGraph replay in the async slots
   bool tail_fuse = true;                   // SN_TAIL_FUSE | 1 | create | 0: last streamed block + k_head_final_f16 instead of the tail form
   bool obstacle_rle = true;                // SN_OBSTACLE_RLE | 1 | create | 0: sn_obstacles_from_raw sends one set of atomics per point instead of one per run of a lane
+  int inflate_waves = 0;                   // SN_INFLATE_WAVES | 0 | create | 4 or 16: waves per workgroup of k_inflate whatever the call's size (0: 16 while all its workgroups are resident at once, else 4)
   int mgpu_gather = 0;                     // SN_MGPU_GATHER | unset | create | peer (1) or rccl (2): forces the exchange of sn_mgpu_*
   bool mgpu_allow_dup = false;             // SN_MGPU_ALLOW_DUP | 0 | create | 1: several shards may name one device (tests)
   // Diagnostic build only (-DSN_DIAGNOSTICS=1); the shipping library never reads them and both masks stay 0.  Any
@@ -136,6 +137,7 @@ inline void read_switches(Switches* s, bool process_scope) {
   s->no_graph = present("SN_NO_GRAPH");
   s->tail_fuse = on_unless_zero("SN_TAIL_FUSE");
   s->obstacle_rle = on_unless_zero("SN_OBSTACLE_RLE");
+  s->inflate_waves = int_or("SN_INFLATE_WAVES", 0);
   s->mgpu_gather = equals("SN_MGPU_GATHER", "peer") ? 1 : equals("SN_MGPU_GATHER", "rccl") ? 2 : 0;
   s->mgpu_allow_dup = int_or("SN_MGPU_ALLOW_DUP", 0) == 1;
   s->ablate_w = ablate_mask("SN_ABLATE_W");

@@ -28,7 +28,7 @@
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
 #include "sn_switches.hpp"      // the SN_* environment switches
-#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_rectify.hpp, sn_jpeg.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp)
+#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_rectify.hpp, sn_jpeg.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_inflate.hpp)
 #include "sn_pointcloud.hpp"
 #include "sn_lrcheck.hpp"
 #include "sn_dispfilter.hpp"
@@ -41,11 +41,12 @@
 #include "sn_obstacles.hpp"
 #include "sn_ground.hpp"
 #include "sn_costmap.hpp"
+#include "sn_inflate.hpp"
 #include "sn_engine.hpp"        // handle, workspace and layer types, error and allocation helpers
 #include "sn_weights.hpp"       // .snw reader, weight packing and upload
 #include "sn_launch.hpp"        // kernel launchers and tensor geometry
 #include "sn_forward.hpp"       // workspace allocation, forward pass, refinement statistic, SN_PREC_AUTO
-#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter, smoother, temporal filter, rectifier, JPEG encoder, render, obstacles, ground, costmap
+#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter, smoother, temporal filter, rectifier, JPEG encoder, render, obstacles, ground, costmap, inflation
 #include "sn_dbg_hooks.hpp"     // sn_dbg_* parity hooks
 
 // =====================================================================================================
@@ -284,6 +285,7 @@ int sn_create_prio(const char* model_file, const sn_config* cfg, int stream_prio
   h->fuse_mode = sw.fuse;
   h->tail_fuse = sw.tail_fuse;
   h->obstacle_rle = sw.obstacle_rle;
+  h->inflate_waves = sw.inflate_waves;
   if (hipMalloc(reinterpret_cast<void**>(&h->dump), 4096) != hipSuccess) return fail(SN_ERR_NOMEM);
 
   BlobWalker bw{blob.data()};
@@ -412,6 +414,7 @@ int sn_destroy(sn_handle* h) {
   h->rnd.destroy();
   h->obs.destroy();
   h->gnd.destroy();
+  h->inf.destroy();
   for (GrowBuf& b : h->stage.buf) b.release();
   hipFree(h->aout.w);
   hipFree(h->aout.pfrag);

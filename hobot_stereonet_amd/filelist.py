@@ -8,7 +8,7 @@ D1) needed to score the output against dataset ground truth.
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
         [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]] \
-        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]]
+        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]] [--inflate PARAMS_FILE]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -81,6 +81,12 @@ accumulates every frame's grid and scan on the GPU (`sn_costmap_push`) into a ro
 travels with the robot.  POSES_FILE holds one `x y yaw` line per pair (metres and radians in the map's fixed frame); without
 it every pair stands at the origin.  <i>.costmap.pgm (0 occupied .. 255 free, 128 unknown, world x up) is written into --out;
 the summary gains "costmap": per pair "known", "occupied" (cells with positive log-odds), "hit" and "cleared" (cells this frame).
+
+--inflate PARAMS_FILE (inflate.save_params' `key value` lines; needs --obstacles with a grid) charges every cell for its distance
+to the nearest obstacle on the GPU (`sn_inflate_grid`): of the costmap's grid with --costmap, else of the obstacle grid, with
+cell_m taken from the obstacle file.  <i>.inflated.pgm (the cost bytes: 254 lethal, 253 inscribed, 1..252 the fall-off, 0 free,
+255 unknown; row y of the grid is row y of the picture) is written into --out; the summary gains "inflate": per pair "lethal",
+"inscribed", "inflated", "free" and "unknown".
 """
 import argparse
 import json
@@ -156,7 +162,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None, view=None, obstacle=None, ground=None, costmap=None) -> List[dict]:
+                jpeg=None, view=None, obstacle=None, ground=None, costmap=None, inflation=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -190,7 +196,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     obstacle stage takes the record's mount.
     costmap = (costmap.CostmapParams, poses (n, 3) or None), with `obstacle`: the list is one clip; one api.Costmap lives for the
     call and takes every frame's "occ" and "ranges" at the frame's pose (None: the origin); the record gains "costmap" (the int8
-    grid), "costmap_q" and "costmap_stats" = {"known", "occupied", "hit", "cleared"}, and <i>.costmap.pgm is written."""
+    grid), "costmap_q" and "costmap_stats" = {"known", "occupied", "hit", "cleared"}, and <i>.costmap.pgm is written.
+    inflation = an inflate.InflateParams whose cell_m is the obstacle grid's, with `obstacle` (gw > 0): engine.inflate of the
+    costmap's grid (with `costmap`) or else of "occ"; the record gains "inflated" (the uint8 cost) and "inflate_stats" =
+    {"lethal", "inscribed", "inflated", "free", "unknown"}, and <i>.inflated.pgm is written."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -207,13 +216,16 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             raise FileListError("the costmap needs the obstacle stage")
         if costmap[1] is not None and len(costmap[1]) != len(left):
             raise FileListError(f"Poses size error! left_imgs.size: {len(left)}, poses.size: {len(costmap[1])}")
+    if inflation is not None and (obstacle is None or not obstacle.gw):
+        raise FileListError("the inflation needs the obstacle stage's grid")
     try:
         if costmap is not None:
             cm = (engine.costmap(obstacle, costmap[0]), costmap[1])
         if rectify is not None:
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
-        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground, cm)
+        _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground, cm,
+              inflation)
     finally:
         if cm is not None:
             cm[0].close()
@@ -225,7 +237,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
 
 
 def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None,
-          obstacle=None, ground=None, cm=None):
+          obstacle=None, ground=None, cm=None, inflation=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -305,6 +317,10 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             grid, _, cstats, q = cm[0].push(pose, occ if obstacle.gw else None, ranges if obstacle.beams else None, want=(True, False, True))
             rec.update(costmap=grid[0], costmap_q=q[0],
                        costmap_stats=dict(zip(("known", "occupied", "hit", "cleared"), (int(v) for v in cstats[0]))))
+        if inflation is not None:     # of the clip's map, or else of this frame's grid
+            from . import inflate as infl
+            cost, _, _, istats = engine.inflate(rec["costmap"] if cm is not None else occ, inflation, want=(True, False, False, True))
+            rec.update(inflated=cost, inflate_stats=dict(zip(infl.STATS, (int(v) for v in istats))))
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -357,6 +373,9 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             if cm is not None:
                 from . import costmap as cmap
                 cmap.write_pgm(os.path.join(out_dir, f"{i}.costmap.pgm"), rec["costmap"])
+            if inflation is not None:
+                from . import inflate as infl
+                infl.write_pgm(os.path.join(out_dir, f"{i}.inflated.pgm"), rec["inflated"])
             if rect is not None:
                 from . import rectify as rct
                 images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
@@ -420,6 +439,9 @@ def main(argv=None) -> int:
     ap.add_argument("--costmap", default=None, metavar="PARAMS_FILE[,POSES_FILE]",
                     help="write <i>.costmap.pgm: the list is one clip whose grids and scans accumulate on the GPU into a rolling "
                          "log-odds map with ray clearing; POSES_FILE: one `x y yaw` line per pair (default: the origin); needs --obstacles")
+    ap.add_argument("--inflate", default=None, metavar="PARAMS_FILE",
+                    help="write <i>.inflated.pgm: the cost of every cell after inflation by the robot's radius on the GPU, of the "
+                         "costmap's grid with --costmap, else of the obstacle grid; needs --obstacles with a grid")
     ap.add_argument("--render-true-colours", action="store_true", help="--render: the colour map's own colours, not the reference's R/B swap")
     ap.add_argument("--render-invalid-black", action="store_true", help="--render: pixels without a measurement (raw == 0) are black")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
@@ -566,13 +588,27 @@ def main(argv=None) -> int:
             cmap = (cparams, cposes)
         except (OSError, ValueError) as e:
             ap.error(f"--costmap {args.costmap}: {e}")
+    inflation = None
+    if args.inflate is not None:
+        import dataclasses
+        from . import inflate as imod
+        if obstacle is None or not obstacle.gw:
+            ap.error("--inflate needs --obstacles with a grid")
+        try:
+            inflation = dataclasses.replace(imod.load_params(args.inflate), cell_m=obstacle.cell_m)
+            why = imod.check(inflation)
+            if why:
+                raise ValueError(why)
+            imod.table(inflation)
+        except (OSError, ValueError) as e:
+            ap.error(f"--inflate {args.inflate}: {e}")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap)
+                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap, inflation=inflation)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -588,6 +624,9 @@ def main(argv=None) -> int:
             summary[k] = [r[k] for r in recs]
     if cmap is not None and recs:
         summary["costmap"] = {k: [r["costmap_stats"][k] for r in recs] for k in ("known", "occupied", "hit", "cleared")}
+    if inflation is not None and recs:
+        from . import inflate as imod
+        summary["inflate"] = {k: [r["inflate_stats"][k] for r in recs] for k in imod.STATS}
     if gparams is not None and recs:
         for k in ("ground_found", "height_m", "pitch_deg", "roll_deg", "inliers"):
             summary[k] = [r[k] for r in recs]

@@ -1201,8 +1201,8 @@ int sn_ground_from_raw(sn_handle *h, int n, const int32_t *raw, const sn_camera 
  *   returns after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller stream only enqueue, so
  *   ground -> obstacles -> costmap run on one stream without a host round trip.  May run beside sn_submit / sn_wait and the
  *   other stages; calls are serialised by the object's mutex.  One kernel launch per 64 maps of a call.
- * Not covered: the asynchronous sn_submit* slots, inflation, decay of unobserved cells, 3-D voxels, clearing along beams
- * without a return, poses with roll or pitch. */
+ * Not covered: the asynchronous sn_submit* slots, decay of unobserved cells, 3-D voxels, clearing along beams without a
+ * return, poses with roll or pitch.  (Inflation by the robot's radius is sn_inflate_grid below.) */
 typedef struct sn_costmap_params {
   int   mw, mh;                      /* window in cells, 1..4096 each */
   int   l_hit, l_miss;               /* 1..32767 */
@@ -1219,6 +1219,67 @@ int  sn_costmap_push(sn_costmap *c, int n, const int *stream_of, const double *p
                      const int8_t *occ /* [n][gh][gw] */, const float *ranges /* [n][beams] */,
                      int8_t *grid /* [n][mh][mw] */, int16_t *logodds /* [n][mh][mw] */, uint32_t *stats /* [n][4] */,
                      int32_t *pose_q_out /* host [n][6], nullable */, int mem, void *stream);
+
+/* ---- inflation of occupancy grids by the robot's radius (csrc/sn_inflate.hpp; hobot_stereonet_amd/inflate.py is the numpy
+ * twin, byte for byte) -----------------------------------------------------------------------------------------------------------
+ * A planner treats the robot as a point, so every cell is first charged for how close it lies to an obstacle: lethal at the
+ * obstacle, "inscribed" within the robot's inner radius, an exponential fall-off out to the inflation radius (the inflation
+ * layer of a navigation stack, directly above the rolling window).  sn_inflate_grid does that for n OccupancyGrid payloads as
+ * sn_obstacles_from_raw (occ) and sn_costmap_push (grid) write them: -1 unknown, 0..100 known.  The stage is stateless and
+ * integer below one host-built table, so no tolerance appears anywhere.  The distance is the EXACT Euclidean distance to the
+ * nearest obstacle cell (a bounded distance transform), not the wavefront approximation of costmap_2d, whose cells inherit
+ * the obstacle of the neighbour that reached them first.
+ *
+ * The host table (sn_inflate_table: pure host, no device), in double, in this order of operations:
+ *   R = (int)ceil((double)inflation_radius_m / (double)cell_m); R above SN_INFLATE_MAX_R is refused.
+ *   T[0] = 254.  For d2 = 1..R*R:  dist = sqrt((double)d2) * (double)cell_m;
+ *     dist <= (double)inscribed_radius_m: T[d2] = 253;   dist > (double)inflation_radius_m: T[d2] = 0;   otherwise
+ *     T[d2] = (uint8_t)(252.0 * exp(-(double)cost_scaling * (dist - (double)inscribed_radius_m))), truncated.
+ *   T does not increase with d2: the library asserts so after building the table and refuses the parameters otherwise.
+ *   Two implementations of a double exp may differ by an ulp, so an entry may differ by one between them: a twin is fed the
+ *   library's table, as it is fed the beam table and the costmap's q.
+ *   *R (nullable) receives R, table (nullable) its R*R + 1 bytes: call it once for R, then with a table of that size.
+ *   SN_ERR_ARG: p NULL, cell_m not finite or <= 0, inscribed_radius_m not finite or negative, inflation_radius_m not finite or
+ *   below inscribed_radius_m, cost_scaling not finite or negative, R above 64, lethal_min outside 1..100, flags with bits
+ *   other than SN_INFLATE_UNKNOWN, a table that increases.
+ * Per cell (x, y) of map k, all integer:
+ *   cell (x', y') is an obstacle when occ[k][y'][x'] >= lethal_min (the input is read as trinary: unknown, free, obstacle);
+ *   d2 = min (x - x')^2 + (y - y')^2 over the obstacles of the same map; there are no obstacles outside the grid;
+ *   c  = d2 <= R*R ? T[d2] : 0;
+ *   cost: a known cell (occ >= 0) costs c; an unknown cell costs c when (flags & SN_INFLATE_UNKNOWN ? c > 0 : c >= 253)
+ *     and 255 otherwise.
+ * Outputs, each [n][gh][gw], each nullable, at least one required:
+ *   cost  uint8
+ *   grid  int8, the usual publisher translation of cost: 0 -> 0, 253 -> 99, 254 -> 100, 255 -> -1, otherwise
+ *         1 + 97 * (cost - 1) / 251 (integer division)
+ *   dist2 uint16: d2 where d2 <= R*R, else 0xFFFF
+ *   stats uint32 [n][5] = {cells at 254, at 253, at 1..252, at 0, at 255}; they sum to gw * gh.
+ * sn_inflate_grid: SN_ERR_ARG is decided before anything is launched or written (sn_last_error(h) names the call): a NULL h, p
+ *   or occ, n outside 1..max_batch, gw or gh outside 1..4096, any parameter sn_inflate_table refuses, no output, dist2
+ *   misaligned (2 bytes), stats misaligned (4 bytes), any output overlapping occ or another output (a cell reads a halo of R
+ *   cells around it, so the call cannot work in place), a bad mem.
+ *   mem / stream as sn_obstacles_from_raw: the stage has its own lane on the handle; a NULL stream is the lane's own (never the
+ *   inference stream); the call returns after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller
+ *   stream only enqueue, so obstacles -> costmap -> inflate run on one stream without a host round trip.  May run beside
+ *   sn_submit / sn_wait and the other stages; calls are serialised by the lane's mutex.  One kernel launch per call.
+ *   The table of the last parameter block stays on the device: a call with the same block uploads nothing, one with
+ *   another block uploads its table behind the lane's earlier calls and waits for the upload.
+ * Not covered: the asynchronous sn_submit* slots, non-circular footprints, per-cell own costs (a known cell below lethal_min
+ * counts as free whatever its value), a cost that depends on heading. */
+#define SN_INFLATE_MAX_R   64
+#define SN_INFLATE_UNKNOWN 1     /* flags: an unknown cell takes any cost > 0 (otherwise only costs >= 253) */
+typedef struct sn_inflate_params {
+  float cell_m;               /* > 0, finite: the grid's cell */
+  float inscribed_radius_m;   /* >= 0 */
+  float inflation_radius_m;   /* >= inscribed_radius_m */
+  float cost_scaling;         /* >= 0, finite */
+  int   lethal_min;           /* 1..100: a cell with occ >= lethal_min is an obstacle */
+  int   flags;                /* SN_INFLATE_UNKNOWN or 0 */
+} sn_inflate_params;
+int sn_inflate_table(const sn_inflate_params *p, uint8_t *table /* [R*R+1], nullable */, int *R);   /* pure host, no device */
+int sn_inflate_grid(sn_handle *h, int n, const int8_t *occ /* [n][gh][gw] */, int gw, int gh, const sn_inflate_params *p,
+                    uint8_t *cost, int8_t *grid, uint16_t *dist2 /* each [n][gh][gw] */, uint32_t *stats /* [n][5] */,
+                    int mem, void *stream);
 
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
