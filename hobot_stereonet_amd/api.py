@@ -183,6 +183,19 @@ def inflate_params(p) -> SnInflateParams:
     return SnInflateParams(p.cell_m, p.inscribed_radius_m, p.inflation_radius_m, p.cost_scaling, p.lethal_min, p.flags)
 
 
+class SnNavParams(C.Structure):
+    """sn_nav_params (include/stereonet_hip.h); navfn.NavParams is the Python face of it."""
+    _fields_ = [("neutral", C.c_int), ("lethal_cost", C.c_int), ("unknown_cost", C.c_int), ("flags", C.c_int), ("max_rounds", C.c_int),
+                ("max_path", C.c_int)]
+
+
+def nav_params(p) -> SnNavParams:
+    """navfn.NavParams -> sn_nav_params"""
+    if isinstance(p, SnNavParams):
+        return p
+    return SnNavParams(p.neutral, p.lethal_cost, p.unknown_cost, p.flags, p.max_rounds, p.max_path)
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -352,6 +365,7 @@ def load_library(path: Optional[str] = None):
     lib.sn_costmap_push.argtypes = [vp, ip, vp, vp, i8p, fp, i8p, vp, vp, i32p, ip, vp]
     lib.sn_inflate_table.argtypes = [C.POINTER(SnInflateParams), u8p, C.POINTER(C.c_int)]
     lib.sn_inflate_grid.argtypes = [vp, ip, i8p, ip, ip, C.POINTER(SnInflateParams), u8p, i8p, vp, vp, ip, vp]
+    lib.sn_navfn.argtypes = [vp, ip, u8p, ip, ip, i32p, i32p, C.POINTER(SnNavParams), vp, i32p, vp, C.POINTER(C.c_int), ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -365,7 +379,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_inflate_table", "sn_inflate_grid", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -814,6 +828,36 @@ class StereoNetHIP:
         prm = inflate_params(params)
         self._check(self._lib.sn_inflate_grid(self._h, n, occ_ptr or None, gw, gh, C.byref(prm), cost_ptr or None, grid_ptr or None,
                                               dist2_ptr or None, stats_ptr or None, SN_MEM_DEVICE, stream or None), "sn_inflate_grid")
+
+    # -- navigation function and path ---------------------------------------------------------------------
+    def navfn(self, cost: np.ndarray, goals, starts, params, want=(True, True, True)):
+        """sn_navfn on host buffers: cost uint8 (gh, gw) or (n, gh, gw) as inflate() gives it, goals (n, 2) and starts (n, 2) or
+        None as {x, y} in cells -> (potential uint32 (n, gh, gw), path int32 (n, max_path, 2) with -1 past the path's length,
+        stats uint32 (n, 5), rounds: how many rounds did work), None where `want` says an output is not asked for, leading n
+        dropped for a 2-D cost; navfn.reference is the twin.  params: navfn.NavParams."""
+        c = np.ascontiguousarray(cost, np.uint8)
+        if c.ndim not in (2, 3):
+            raise StereoNetError(-1, "navfn", f"cost of shape {c.shape}: (gh, gw) or (n, gh, gw) is needed")
+        n, (gh, gw) = (1 if c.ndim == 2 else c.shape[0]), c.shape[-2:]
+        prm = nav_params(params)
+        g = np.ascontiguousarray(np.asarray(goals, np.int32).reshape(n, 2))
+        s = None if starts is None else np.ascontiguousarray(np.asarray(starts, np.int32).reshape(n, 2))
+        outs = [np.zeros((n, gh, gw), np.uint32) if want[0] else None, np.full((n, prm.max_path, 2), -1, np.int32) if want[1] else None,
+                np.zeros((n, 5), np.uint32) if want[2] else None]
+        rounds = C.c_int(0)
+        self._check(self._lib.sn_navfn(self._h, n, c.ctypes.data, gw, gh, g.ctypes.data, _np_ptr(s), C.byref(prm), *[_np_ptr(a) for a in outs],
+                                       C.byref(rounds), SN_MEM_HOST, None), "sn_navfn")
+        return tuple(a if a is None or c.ndim == 3 else a[0] for a in outs) + (rounds.value,)
+
+    def navfn_device(self, n: int, cost_ptr: int, gw: int, gh: int, goals_ptr: int, starts_ptr: int, params, potential_ptr: int = 0,
+                     path_ptr: int = 0, stats_ptr: int = 0, stream: int = 0) -> int:
+        """sn_navfn on device pointers (0: that buffer is not given); stream = hipStream_t as int (0: the stage's own stream).
+        -> how many rounds did work, or -1 where the call only enqueued (max_rounds > 0 on a caller stream)."""
+        prm, rounds = nav_params(params), C.c_int(0)
+        self._check(self._lib.sn_navfn(self._h, n, cost_ptr or None, gw, gh, goals_ptr or None, starts_ptr or None, C.byref(prm),
+                                       potential_ptr or None, path_ptr or None, stats_ptr or None, C.byref(rounds), SN_MEM_DEVICE,
+                                       stream or None), "sn_navfn")
+        return rounds.value
 
     # -- ground plane -----------------------------------------------------------------------------------
     def ground(self, raw: np.ndarray, cam, params, labels: bool = True):

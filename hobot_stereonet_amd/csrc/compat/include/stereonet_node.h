@@ -22,6 +22,7 @@
 
 #include "rclcpp/rclcpp.hpp"
 #include "nav_msgs/msg/occupancy_grid.hpp"
+#include "nav_msgs/msg/path.hpp"
 #include "sensor_msgs/msg/image.hpp"
 #include "sensor_msgs/msg/laser_scan.hpp"
 #include "sensor_msgs/msg/point_cloud2.hpp"
@@ -71,6 +72,11 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   // this implementation's own: the robot's planar pose in the costmap's fixed frame (metres, radians), taken by every frame
   // processed after the call (STEREONET_COSTMAP).  Thread-safe; the default is the origin.
   void SetBasePose(double x, double y, double yaw);
+
+  // this implementation's own: the goal of the plan (STEREONET_PLAN), metres in the frame of the inflated grid's source (the
+  // costmap's fixed frame when the costmap is on), taken by every frame processed after the call.  Thread-safe; until the first
+  // call nothing is published on /stereonet_plan.
+  void SetGoal(double x_m, double y_m);
 
  protected:
   int SetNodePara() override;
@@ -140,6 +146,14 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // unset: off, nothing of it exists
     bool inflate = false;
     sn_inflate_params inflate_params{};
+    // this implementation's own: the navigation function over the inflated costs and the path that follows it (sn_navfn) from
+    // the robot's cell (the cell of SetBasePose in the costmap, of the base frame's origin in the obstacle grid) to the goal of
+    // SetGoal: nav_msgs/Path on /stereonet_plan, published right after /stereonet_inflated_grid with the header of its source,
+    // one pose per cell at the cell's centre in metres, start first.  A goal or a robot outside the grid is clamped to it per
+    // coordinate (a goal outside is logged once).  max_path must be 1..2^20.  STEREONET_PLAN=<parameter file> (navfn.save_params' `key value` lines; its
+    // goal and start lines are the tools') turns it on and requires STEREONET_INFLATE; unset: off, nothing of it exists
+    bool plan = false;
+    sn_nav_params plan_params{};
   };
 
   void DeclareAndReadParameters();
@@ -154,6 +168,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void PublishCostmap(const StereonetNodeOutput& request, const int8_t* occ, const float* ranges);
   void ReadInflateSettings();
   void PublishInflated(const nav_msgs::msg::OccupancyGrid& src);
+  void ReadPlanSettings();
+  void PublishPlan(const nav_msgs::msg::OccupancyGrid& src, const uint8_t* cost);
   bool FitGround(const int32_t* raw, sn_ground* out);
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
   void ReadTemporalSettings();
@@ -186,6 +202,10 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   sn_costmap* costmap_ = nullptr;                // one stream; only while STEREONET_COSTMAP is set and valid
   rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr costmap_out_;
   rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr inflated_out_;      // only while STEREONET_INFLATE is set and valid
+  rclcpp::Publisher<nav_msgs::msg::Path>::SharedPtr plan_out_;                    // only while STEREONET_PLAN is set and valid
+  double goal_[2] = {0.0, 0.0};                  // of SetGoal, under base_pose_mu_
+  bool has_goal_ = false;
+  std::atomic<bool> goal_clamp_logged_{false};
   std::mutex base_pose_mu_;
   double base_pose_[3] = {0.0, 0.0, 0.0};        // x, y, yaw of SetBasePose
   sn_rectify* rectify_ = nullptr;                // only while STEREONET_RECTIFY names a valid calibration

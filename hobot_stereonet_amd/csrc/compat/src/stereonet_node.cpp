@@ -110,6 +110,7 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
     obstacle_scan_out_ = create_publisher<sensor_msgs::msg::LaserScan>("/stereonet_scan", 10);
   ReadCostmapSettings();
   ReadInflateSettings();
+  ReadPlanSettings();
   ReadTemporalSettings();
   ready_ = true;
 }
@@ -808,12 +809,135 @@ void StereonetNode::PublishInflated(const nav_msgs::msg::OccupancyGrid& src) {
   out.header = src.header;
   out.info = src.info;
   out.data.resize(src.data.size());
-  if (sn_inflate_grid(net_->engine(), 1, src.data.data(), (int)src.info.width, (int)src.info.height, &cfg_.inflate_params, nullptr,
-                      out.data.data(), nullptr, nullptr, SN_MEM_HOST, nullptr) != SN_OK) {
+  std::vector<uint8_t> cost(cfg_.plan ? src.data.size() : 0);      // the plan reads the cost bytes, not their translation
+  if (sn_inflate_grid(net_->engine(), 1, src.data.data(), (int)src.info.width, (int)src.info.height, &cfg_.inflate_params,
+                      cfg_.plan ? cost.data() : nullptr, out.data.data(), nullptr, nullptr, SN_MEM_HOST, nullptr) != SN_OK) {
     RCLCPP_ERROR(kLog, "inflation failed: %s", sn_last_error(net_->engine()));
     return;
   }
   inflated_out_->publish(std::move(out));
+  if (cfg_.plan) PublishPlan(src, cost.data());
+}
+
+namespace {
+// navfn.load_params' text form: integers, one value a key; the tools' `goal x y` and `start x y` lines are read past
+bool load_plan_file(const char* path, sn_nav_params* p, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct IntKey {
+    const char* name;
+    int* v;
+  } ints[] = {{"neutral", &p->neutral},   {"lethal_cost", &p->lethal_cost}, {"unknown_cost", &p->unknown_cost},
+              {"flags", &p->flags},       {"max_rounds", &p->max_rounds},   {"max_path", &p->max_path}};
+  std::vector<std::string> seen;
+  std::string text;
+  for (int no = 1; std::getline(in, text); ++no) {
+    std::istringstream words(text.substr(0, text.find('#')));
+    std::string key, w;
+    if (!(words >> key)) continue;
+    std::vector<std::string> vals;
+    while (words >> w) vals.push_back(w);
+    const std::string at = "line " + std::to_string(no) + ": ";
+    for (const std::string& k : seen)
+      if (k == key) {
+        *err = at + key + " twice";
+        return false;
+      }
+    seen.push_back(key);
+    const bool cell = key == "goal" || key == "start";
+    bool known = cell, ok = vals.size() == (cell ? 2u : 1u);
+    for (const IntKey& f : ints) known = known || key == f.name;
+    for (const std::string& v : vals) {
+      char* end = nullptr;
+      const double d = strtod(v.c_str(), &end);
+      ok = ok && end != v.c_str() && !*end && d >= -1e9 && d <= 1e9 && d == (double)(int)d;      // the range first: the cast of a larger double is undefined
+      for (const IntKey& f : ints)
+        if (key == f.name) {
+          known = true;
+          if (ok) *f.v = (int)d;
+        }
+    }
+    if (!known || !ok) {
+      *err = at + (known ? "wrong values for " : "unknown key ") + key;
+      return false;
+    }
+  }
+  return true;
+}
+}  // namespace
+
+// parsed and validated once here: what sn_navfn would refuse turns the stage off instead of failing every frame
+void StereonetNode::ReadPlanSettings() {
+  const char* e = getenv("STEREONET_PLAN");
+  if (!e || !*e) return;
+  sn_nav_params& p = cfg_.plan_params;
+  p = sn_nav_params{50, 253, 0, 0, 0, 4096};      // navfn.NavParams' defaults
+  std::string bad;
+  if (!cfg_.inflate) bad = std::string("STEREONET_PLAN=") + e + " requires STEREONET_INFLATE";
+  else if (!load_plan_file(e, &p, &bad)) bad = std::string("STEREONET_PLAN=") + e + ": " + bad;
+  else if (p.neutral < 1 || p.neutral > 255 || p.lethal_cost < 1 || p.lethal_cost > 255 || p.unknown_cost < 0 || p.unknown_cost > 252 ||
+           (p.flags & ~SN_NAV_UNKNOWN_OK) || p.max_rounds < 0 || p.max_path < 1 || p.max_path > SN_NAV_MAX_CELLS)
+    bad = std::string("STEREONET_PLAN=") + e + ": parameters sn_navfn refuses, or max_path outside 1..2^20 (no path is longer than a grid has cells)";
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no plan");
+    return;
+  }
+  cfg_.plan = true;
+  plan_out_ = create_publisher<nav_msgs::msg::Path>("/stereonet_plan", 10);
+  RCLCPP_WARN_STREAM(kLog, "plan: /stereonet_inflated_grid to the goal of SetGoal on /stereonet_plan, neutral " << p.neutral << ", lethal from "
+                                                                                                                  << p.lethal_cost << ", at most " << p.max_path
+                                                                                                                  << " cells");
+}
+
+void StereonetNode::SetGoal(double x_m, double y_m) {
+  std::lock_guard<std::mutex> lk(base_pose_mu_);
+  goal_[0] = x_m, goal_[1] = y_m;
+  has_goal_ = true;
+}
+
+// nav_msgs/Path from the robot's cell to the goal's over the costs just made: one sn_navfn call; the header of the grid's source
+void StereonetNode::PublishPlan(const nav_msgs::msg::OccupancyGrid& src, const uint8_t* cost) {
+  double goal[2], robot[2] = {0.0, 0.0};      // the obstacle grid is in the base frame: the robot stands at its origin
+  {
+    std::lock_guard<std::mutex> lk(base_pose_mu_);
+    if (!has_goal_) return;
+    memcpy(goal, goal_, sizeof(goal));
+    if (costmap_) robot[0] = base_pose_[0], robot[1] = base_pose_[1];
+  }
+  const int gw = (int)src.info.width, gh = (int)src.info.height;
+  const double res = (double)src.info.resolution, ox = src.info.origin.position.x, oy = src.info.origin.position.y;
+  auto cell_of = [&](const double at[2], int32_t out[2]) {      // -> whether a coordinate was clamped
+    const double fx = std::floor((at[0] - ox) / res), fy = std::floor((at[1] - oy) / res);
+    const double cx = std::min(std::max(fx, 0.0), (double)(gw - 1)), cy = std::min(std::max(fy, 0.0), (double)(gh - 1));
+    out[0] = (int32_t)cx, out[1] = (int32_t)cy;
+    return cx != fx || cy != fy;
+  };
+  int32_t g[2], s[2];
+  if (cell_of(goal, g) && !goal_clamp_logged_.exchange(true))
+    RCLCPP_WARN(kLog, "plan: the goal (%.3f, %.3f) lies outside the grid and is clamped to cell (%d, %d)", goal[0], goal[1], g[0], g[1]);
+  cell_of(robot, s);
+  // allocated once per thread that publishes, not per frame; max_path was bounded at start-up
+  thread_local std::vector<int32_t> cells;
+  cells.resize((size_t)cfg_.plan_params.max_path * 2);
+  uint32_t stats[5];
+  if (sn_navfn(net_->engine(), 1, cost, gw, gh, g, s, &cfg_.plan_params, nullptr, cells.data(), stats, nullptr, SN_MEM_HOST, nullptr) != SN_OK) {
+    RCLCPP_ERROR(kLog, "plan failed: %s", sn_last_error(net_->engine()));
+    return;
+  }
+  nav_msgs::msg::Path out;
+  out.header = src.header;
+  const size_t n = std::min<size_t>(stats[2], (size_t)cfg_.plan_params.max_path);
+  out.poses.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    out.poses[i].header = src.header;
+    out.poses[i].pose.position.x = ox + ((double)cells[2 * i] + 0.5) * res;
+    out.poses[i].pose.position.y = oy + ((double)cells[2 * i + 1] + 0.5) * res;
+  }
+  if (stats[0]) RCLCPP_DEBUG(kLog, "plan: flags %u, %u cells", stats[0], stats[2]);
+  plan_out_->publish(std::move(out));
 }
 
 namespace {

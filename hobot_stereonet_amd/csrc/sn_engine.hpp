@@ -335,6 +335,14 @@ struct sn_handle {
     bool cached = false;               // buf[kTable] holds the table of `key`
     sn_inflate_params key{};
   } inf;
+  // sn_navfn.  the potential where the caller wants none, the tiles' marks and the work word, the pinned word the host reads it
+  // back into; host mode: cost, goals, starts, potential, path, stats
+  struct NavSlots {
+    enum { kMarks = 0, kPinWork, kCost, kGoals, kStarts, kPot, kPath, kStats, kCount };
+  };
+  struct Nav : Lane<NavSlots> {
+    Nav() { buf[kPinWork].pinned = true; }
+  } nav;
   // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
   // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
   // lock: calls on one handle must not overlap.

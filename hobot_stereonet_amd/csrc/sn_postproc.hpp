@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane, costmap and inflation.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp and sn_inflate.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane, costmap, inflation and the navigation function.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_inflate.hpp and sn_navfn.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -1655,6 +1655,84 @@ int sn_inflate_grid(sn_handle* h, int n, const int8_t* occ, int gw, int gh, cons
   else hipLaunchKernelGGL(k_inflate<4>, dim3(tiles, n), dim3(256), 0, st, a);
   HIP_TRY(h, hipGetLastError());
   return b.close();
+}
+
+// ---- navigation function and path (csrc/sn_navfn.hpp): a lane of the handle's.  The rounds of the relaxation are separate
+// launches; max_rounds == 0 reads the work word back every kNavChunk of them ----------------------------------------------------
+int sn_navfn(sn_handle* h, int n, const uint8_t* cost, int gw, int gh, const int32_t* goals, const int32_t* starts, const sn_nav_params* p,
+             uint32_t* potential, int32_t* path, uint32_t* stats, int* rounds_out, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_navfn: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!p || !cost || !goals) return refuse("a NULL pointer");
+  if (n <= 0 || n > h->max_batch) return refuse("n outside 1..max_batch");
+  if (gw < 1 || gh < 1 || gw > kNavMaxSide || gh > kNavMaxSide) return refuse("gw and gh must be 1..4096");
+  if ((long long)gw * gh > SN_NAV_MAX_CELLS) return refuse("gw * gh must be at most 2^20");
+  if (const char* why = nav_params_check(p)) return refuse(why);
+  if (!potential && !path && !stats) return refuse("one of potential, path and stats is needed");
+  if (path && (!starts || p->max_path == 0)) return refuse("path needs starts and max_path > 0");
+  if (((uintptr_t)goals | (uintptr_t)starts | (uintptr_t)potential | (uintptr_t)path | (uintptr_t)stats) & 3) return refuse("a misaligned buffer");
+  const size_t cells = (size_t)gw * gh, cost_bytes = n * cells, pot_bytes = cost_bytes * 4, cell_bytes = (size_t)n * 8,
+               path_bytes = (size_t)n * p->max_path * 8, stats_bytes = (size_t)n * 20;
+  {
+    const Span all[6] = {{cost, cost_bytes}, {goals, cell_bytes}, {starts, cell_bytes}, {potential, pot_bytes}, {path, path_bytes},
+                         {stats, stats_bytes}};
+    for (int i = 0; i < 6; ++i)
+      for (int j = i + 1; j < 6; ++j)
+        if (overlap({all[i]}, {all[j]})) return refuse("overlapping buffers");
+  }
+  using N = sn_handle::Nav;
+  N& lane = h->nav;
+  Bracket b(h, "sn_navfn", mem, stream, lane);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  const bool converge = p->max_rounds == 0;
+  if (converge) b.c.blocking = true;      // the host reads the work word between the chunks anyway
+  NavArgs a{};
+  a.gw = gw, a.gh = gh, a.maps = n;
+  a.tiles_x = (gw + kNavTW - 1) / kNavTW, a.tiles_y = (gh + kNavTH - 1) / kNavTH;
+  a.neutral = p->neutral, a.lethal = p->lethal_cost, a.unknown_cost = p->unknown_cost, a.flags = p->flags, a.max_path = p->max_path;
+  const size_t tiles = (size_t)a.tiles_x * a.tiles_y, marks_bytes = (1 + 2 * (size_t)n * tiles) * 4;
+  a.cost = s.in(N::kCost, cost, cost_bytes);
+  a.goals = s.in(N::kGoals, goals, cell_bytes);
+  a.starts = starts ? s.in(N::kStarts, starts, cell_bytes) : nullptr;
+  a.pot = s.out(N::kPot, potential, pot_bytes, true);
+  a.path = s.inout(N::kPath, path, path_bytes);      // entries past the path's length keep the caller's bytes
+  a.stats = s.out(N::kStats, stats, stats_bytes);
+  a.work = s.scratch<uint32_t>(N::kMarks, marks_bytes);
+  uint32_t* pin = s.scratch<uint32_t>(N::kPinWork, 4);
+  if (s.rc) return s.rc;
+  a.marks = a.work + 1;
+  HIP_TRY(h, hipMemsetAsync(a.work, 0, marks_bytes, st));
+  if (a.stats) HIP_TRY(h, hipMemsetAsync(a.stats, 0, stats_bytes, st));
+  const dim3 per_cell((unsigned)((cells + 255) / 256), n);
+  hipLaunchKernelGGL(k_nav_init, per_cell, dim3(256), 0, st, a);
+  int rounds = 0;
+  if (converge) {
+    // at most 1 + gw * gh rounds do work, so the loop ends; the cap only names a broken device
+    for (bool left = true; left;) {
+      for (int i = 0; i < kNavChunk; ++i) hipLaunchKernelGGL(k_nav_relax, dim3((unsigned)tiles, n), dim3(kNavThreads), 0, st, a, rounds++);
+      HIP_TRY(h, hipGetLastError());
+      HIP_TRY(h, hipMemcpyAsync(pin, a.work, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(h, hipStreamSynchronize(st));
+      left = (long long)*pin >= rounds;      // the chunk's last round was active
+      if (left && (size_t)rounds > cells + 1 + kNavChunk) {
+        set_err(h, "sn_navfn: the relaxation did not converge within 1 + gw * gh rounds");
+        return SN_ERR_DEVICE;
+      }
+    }
+  } else {
+    for (; rounds < p->max_rounds; ++rounds) hipLaunchKernelGGL(k_nav_relax, dim3((unsigned)tiles, n), dim3(kNavThreads), 0, st, a, rounds);
+  }
+  if (a.stats) hipLaunchKernelGGL(k_nav_stats, per_cell, dim3(256), 0, st, a, rounds, converge ? 0 : 1);
+  if (a.starts && (a.path || a.stats)) hipLaunchKernelGGL(k_nav_path, dim3(n), dim3(64), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  if (!converge && b.c.blocking) HIP_TRY(h, hipMemcpyAsync(pin, a.work, 4, hipMemcpyDeviceToHost, st));
+  if (int rc = b.close()) return rc;
+  if (rounds_out) *rounds_out = b.c.blocking ? (int)*pin : -1;
+  return SN_OK;
 }
 
 }  // extern "C"

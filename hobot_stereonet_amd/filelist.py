@@ -8,7 +8,8 @@ D1) needed to score the output against dataset ground truth.
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
         [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]] \
-        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]] [--inflate PARAMS_FILE]
+        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]] [--inflate PARAMS_FILE] \
+        [--plan PARAMS_FILE]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -87,6 +88,13 @@ to the nearest obstacle on the GPU (`sn_inflate_grid`): of the costmap's grid wi
 cell_m taken from the obstacle file.  <i>.inflated.pgm (the cost bytes: 254 lethal, 253 inscribed, 1..252 the fall-off, 0 free,
 255 unknown; row y of the grid is row y of the picture) is written into --out; the summary gains "inflate": per pair "lethal",
 "inscribed", "inflated", "free" and "unknown".
+
+--plan PARAMS_FILE (navfn.save_params' `key value` lines, with `goal x y` and `start x y` in cells of the inflated grid; needs
+--inflate) computes on the GPU (`sn_navfn`) the cost-to-go of every cell of the inflated grid to the goal and the path that follows
+it down from the start.  <i>.plan.pgm (the potential scaled to 0..254 by the frame's largest finite value, blocked and unreachable
+cells at 255) and <i>.path.txt (one `x y` line per cell, start first) are written into --out; the summary gains "plan": per pair
+"flags" (1 goal blocked, 2 start unreachable, 4 path truncated, 8 unconverged: a file
+with max_rounds > 0 whose rounds did not finish the field), "reached", "path_cells", "p_start" and "blocked".
 """
 import argparse
 import json
@@ -162,7 +170,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None, view=None, obstacle=None, ground=None, costmap=None, inflation=None) -> List[dict]:
+                jpeg=None, view=None, obstacle=None, ground=None, costmap=None, inflation=None, plan=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -199,7 +207,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     grid), "costmap_q" and "costmap_stats" = {"known", "occupied", "hit", "cleared"}, and <i>.costmap.pgm is written.
     inflation = an inflate.InflateParams whose cell_m is the obstacle grid's, with `obstacle` (gw > 0): engine.inflate of the
     costmap's grid (with `costmap`) or else of "occ"; the record gains "inflated" (the uint8 cost) and "inflate_stats" =
-    {"lethal", "inscribed", "inflated", "free", "unknown"}, and <i>.inflated.pgm is written."""
+    {"lethal", "inscribed", "inflated", "free", "unknown"}, and <i>.inflated.pgm is written.
+    plan = a navfn.NavParams with its goal (and start) in cells, with `inflation`: engine.navfn of "inflated"; the record gains
+    "potential" (uint32), "path" (int32 (cells, 2), empty without a start or a route) and "plan_stats" = navfn.STATS' keys, and
+    <i>.plan.pgm and <i>.path.txt are written."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -218,6 +229,8 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             raise FileListError(f"Poses size error! left_imgs.size: {len(left)}, poses.size: {len(costmap[1])}")
     if inflation is not None and (obstacle is None or not obstacle.gw):
         raise FileListError("the inflation needs the obstacle stage's grid")
+    if plan is not None and inflation is None:
+        raise FileListError("the plan needs the inflated grid")
     try:
         if costmap is not None:
             cm = (engine.costmap(obstacle, costmap[0]), costmap[1])
@@ -225,7 +238,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
         _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground, cm,
-              inflation)
+              inflation, plan)
     finally:
         if cm is not None:
             cm[0].close()
@@ -237,7 +250,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
 
 
 def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None,
-          obstacle=None, ground=None, cm=None, inflation=None):
+          obstacle=None, ground=None, cm=None, inflation=None, plan=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -321,6 +334,12 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             from . import inflate as infl
             cost, _, _, istats = engine.inflate(rec["costmap"] if cm is not None else occ, inflation, want=(True, False, False, True))
             rec.update(inflated=cost, inflate_stats=dict(zip(infl.STATS, (int(v) for v in istats))))
+        if plan is not None:          # over the costs just made
+            from . import navfn as nav
+            pot, cells, pstats, _ = engine.navfn(rec["inflated"], plan.goal, plan.start, plan, want=(True, plan.start is not None, True))
+            length = min(int(pstats[2]), plan.max_path) if cells is not None else 0
+            rec.update(potential=pot, path=cells[:length] if cells is not None else np.zeros((0, 2), np.int32),
+                       plan_stats=dict(zip(nav.STATS, (int(v) for v in pstats))))
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -376,6 +395,10 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             if inflation is not None:
                 from . import inflate as infl
                 infl.write_pgm(os.path.join(out_dir, f"{i}.inflated.pgm"), rec["inflated"])
+            if plan is not None:
+                from . import navfn as nav
+                nav.write_pgm(os.path.join(out_dir, f"{i}.plan.pgm"), rec["potential"])
+                nav.write_path(os.path.join(out_dir, f"{i}.path.txt"), rec["path"])
             if rect is not None:
                 from . import rectify as rct
                 images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
@@ -442,6 +465,9 @@ def main(argv=None) -> int:
     ap.add_argument("--inflate", default=None, metavar="PARAMS_FILE",
                     help="write <i>.inflated.pgm: the cost of every cell after inflation by the robot's radius on the GPU, of the "
                          "costmap's grid with --costmap, else of the obstacle grid; needs --obstacles with a grid")
+    ap.add_argument("--plan", default=None, metavar="PARAMS_FILE",
+                    help="write <i>.plan.pgm and <i>.path.txt: the cost-to-go of every cell of the inflated grid to the file's goal "
+                         "and the path from its start, in cells, on the GPU; needs --inflate")
     ap.add_argument("--render-true-colours", action="store_true", help="--render: the colour map's own colours, not the reference's R/B swap")
     ap.add_argument("--render-invalid-black", action="store_true", help="--render: pixels without a measurement (raw == 0) are black")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
@@ -602,13 +628,27 @@ def main(argv=None) -> int:
             imod.table(inflation)
         except (OSError, ValueError) as e:
             ap.error(f"--inflate {args.inflate}: {e}")
+    plan = None
+    if args.plan is not None:
+        from . import navfn as nmod
+        if inflation is None:
+            ap.error("--plan needs --inflate")
+        try:
+            plan = nmod.load_params(args.plan)
+            why = nmod.check(plan)
+            if why:
+                raise ValueError(why)
+            if plan.start is not None and plan.max_path == 0:
+                raise ValueError("a start needs max_path > 0")
+        except (OSError, ValueError) as e:
+            ap.error(f"--plan {args.plan}: {e}")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap, inflation=inflation)
+                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap, inflation=inflation, plan=plan)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -627,6 +667,9 @@ def main(argv=None) -> int:
     if inflation is not None and recs:
         from . import inflate as imod
         summary["inflate"] = {k: [r["inflate_stats"][k] for r in recs] for k in imod.STATS}
+    if plan is not None and recs:
+        from . import navfn as nmod
+        summary["plan"] = {k: [r["plan_stats"][k] for r in recs] for k in nmod.STATS}
     if gparams is not None and recs:
         for k in ("ground_found", "height_m", "pitch_deg", "roll_deg", "inliers"):
             summary[k] = [r[k] for r in recs]

@@ -1281,6 +1281,85 @@ int sn_inflate_grid(sn_handle *h, int n, const int8_t *occ /* [n][gh][gw] */, in
                     uint8_t *cost, int8_t *grid, uint16_t *dist2 /* each [n][gh][gw] */, uint32_t *stats /* [n][5] */,
                     int mem, void *stream);
 
+/* ---- navigation function and path to a goal over inflated grids (csrc/sn_navfn.hpp; hobot_stereonet_amd/navfn.py is the
+ * numpy twin, byte for byte) ---------------------------------------------------------------------------------------------------
+ * What every consumer of an inflated grid does next: a cost-to-go field from a goal cell (the navigation function of navfn)
+ * and the path that follows it down from the robot's cell.  sn_navfn does that for n cost grids as sn_inflate_grid writes
+ * them.  Everything is integer, and the field is the unique fixed point of min-plus relaxation, so any schedule that
+ * converges gives the same words: no tolerance appears anywhere.
+ *
+ * Input.  cost uint8 [n][gh][gw]: 0 free, 1..252 graded, 253 inscribed, 254 lethal, 255 unknown.  goals int32 [n][2] and
+ *   starts int32 [n][2] (nullable), each {x, y} in cells, in the same memory kind as the other buffers.
+ * Passable cells and their weight.  A cell of 255 is blocked unless flags has SN_NAV_UNKNOWN_OK, and with it is priced as
+ *   cost' = unknown_cost; 255 is tested first.  Any other cell is blocked when cost >= lethal_cost and has cost' = cost
+ *   otherwise.  A passable cell c weighs w(c) = neutral + cost'(c), 1..509.  Cells outside the grid are blocked.
+ * Moves.  The 8 neighbours inside the grid.  A diagonal move is allowed only if both cells it squeezes between (the two that
+ *   share an edge with both ends) are passable: no corner cutting.  Leaving cell b for a neighbour a costs k * w(b), k = 5 for
+ *   a straight move and k = 7 for a diagonal one; both ends of a move are passable.
+ * Potential, uint32 [n][gh][gw].  P(goal) = 0; for every other passable cell P(b) is the minimum over all allowed move
+ *   sequences b -> ... -> goal of the summed move costs: the largest field with P(goal) = 0 and P(b) <= P(a) + k(a,b) * w(b)
+ *   for every allowed move b -> a.  Blocked and unreachable cells hold 0xFFFFFFFF (SN_NAV_INF).
+ *   uint32 suffices: gw * gh > 2^20 is refused (gw, gh 1..4096 each), a cheapest route visits no cell twice, so it leaves at
+ *   most 2^20 - 1 cells, each at no more than 7 * (255 + 254) = 3563 (lethal_cost 255 lets a cell of 254 pass; 7 * 507 at
+ *   the natural 253): (2^20 - 1) * 3563 = 3 736 072 725 < 2^32 - 1.  Every word the relaxation ever stores is the cost of
+ *   such a route, and one further move added to it (3 736 076 288 at most) still fits.
+ * Path (only with starts; written only with path and max_path > 0): start, c1, c2, ..., goal.  From cell c the next cell is
+ *   the allowed neighbour a with the smallest P(a) + k(a,c) * w(c); ties go to the lowest index in the fixed order
+ *   E, NE, N, NW, W, SW, S, SE (north is y - 1, east is x + 1).  w >= 1 makes P strictly decrease along the path, so it ends
+ *   after fewer than gw * gh steps.  path int32 [n][max_path][2], {x, y} per cell; entries past the path's length are not
+ *   written; a path longer than max_path leaves its first max_path cells and SN_NAV_PATH_TRUNCATED.  The walk is counted to its
+ *   end whatever max_path is (stats reports the full length), one cell at a time by one wavefront per map, about a
+ *   microsecond a cell: a route of a few hundred cells is a fraction of a millisecond, the longest route a 2^20-cell maze
+ *   allows (some 5 * 10^5 cells) about half a second of one kernel.
+ * stats uint32 [n][5] = {flags, passable cells with finite P, path length in cells (the full length even when truncated, and
+ *   whether or not the path output is wanted; 0 without starts or without a route), P(start) or 0xFFFFFFFF (also without
+ *   starts), blocked cells}.  flags:
+ *   SN_NAV_GOAL_BLOCKED       the goal lies outside the grid or is blocked: every P is 0xFFFFFFFF and there is no path
+ *   SN_NAV_START_UNREACHABLE  starts given, and the start lies outside the grid, is blocked, or has an infinite P
+ *   SN_NAV_PATH_TRUNCATED     the path output is given and the path is longer than max_path (never without the output)
+ *   SN_NAV_UNCONVERGED        max_rounds > 0 and work was left after the last round (see below)
+ * potential, path and stats are each nullable, and at least one is required.
+ * SN_ERR_ARG is decided before anything is launched or written (sn_last_error(h) names the call): a NULL h, p, cost or goals,
+ *   n outside 1..max_batch, gw or gh outside 1..4096 or gw * gh > 2^20, neutral or lethal_cost outside 1..255, unknown_cost
+ *   outside 0..252, flags with bits other than SN_NAV_UNKNOWN_OK, max_rounds or max_path negative, no output, path without
+ *   starts or with max_path == 0, goals, starts, potential, path or stats not 4-byte aligned (cost may lie anywhere), any
+ *   buffer overlapping another, a bad mem.
+ * mem / stream as sn_inflate_grid: the stage has its own lane on the handle; a NULL stream is the lane's own (never the
+ *   inference stream); calls are serialised by the lane's mutex and may run beside sn_submit / sn_wait and the other stages.
+ * Rounds.  The field is relaxed tile by tile (SN_NAV_TILE_W x SN_NAV_TILE_H cells), one kernel launch per round.
+ *   max_rounds == 0: the call runs until converged and returns after completion, whatever mem and stream are: the exact P,
+ *     and SN_NAV_UNCONVERGED is never set.
+ *   max_rounds > 0: exactly that many relaxation launches are enqueued and the host never waits in between; the call returns
+ *     after completion when mem is SN_MEM_HOST or stream is NULL, and device buffers + a caller stream only enqueue, so
+ *     obstacles -> costmap -> inflate -> navfn run on one stream without a host round trip.  If work was left after the last
+ *     round SN_NAV_UNCONVERGED is set: every finite P is then the cost of a real route, an upper bound of the exact P, P
+ *     still strictly decreases along the path, and the path still ends at the goal.
+ *   rounds_out (host, nullable): how many rounds did work, for a call that returns after completion; -1 for one that only
+ *     enqueues.  It depends on the schedule and belongs to no byte-for-byte comparison.
+ * Not covered: the asynchronous sn_submit* slots, several goals per map, a goal tolerance, footprints with heading,
+ * gradient-interpolated (sub-cell) paths, path smoothing, replanning from the previous frame's field. */
+#define SN_NAV_TILE_W            32
+#define SN_NAV_TILE_H            32
+#define SN_NAV_MAX_CELLS         (1 << 20)   /* gw * gh */
+#define SN_NAV_INF               0xFFFFFFFFu
+#define SN_NAV_UNKNOWN_OK        1           /* params flags: a cell of 255 is passable at unknown_cost */
+#define SN_NAV_GOAL_BLOCKED      1           /* stats flags */
+#define SN_NAV_START_UNREACHABLE 2
+#define SN_NAV_PATH_TRUNCATED    4
+#define SN_NAV_UNCONVERGED       8
+typedef struct sn_nav_params {
+  int neutral;        /* 1..255: the price of a free cell */
+  int lethal_cost;    /* 1..255: a cell with cost >= lethal_cost is blocked; 253 is the natural value */
+  int unknown_cost;   /* 0..252: cost' of a cell of 255 under SN_NAV_UNKNOWN_OK */
+  int flags;          /* SN_NAV_UNKNOWN_OK or 0 */
+  int max_rounds;     /* >= 0; 0: until converged */
+  int max_path;       /* >= 0: capacity of path per map, in cells */
+} sn_nav_params;
+int sn_navfn(sn_handle *h, int n, const uint8_t *cost /* [n][gh][gw] */, int gw, int gh, const int32_t *goals /* [n][2] */,
+             const int32_t *starts /* [n][2], nullable */, const sn_nav_params *p, uint32_t *potential /* [n][gh][gw] */,
+             int32_t *path /* [n][max_path][2] */, uint32_t *stats /* [n][5] */, int *rounds_out /* host, nullable */, int mem,
+             void *stream);
+
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
  * workgroups per peer), so that the tax of the gather root's ingress on a concurrently running batch can be measured
