@@ -196,6 +196,27 @@ def nav_params(p) -> SnNavParams:
     return SnNavParams(p.neutral, p.lethal_cost, p.unknown_cost, p.flags, p.max_rounds, p.max_path)
 
 
+class SnRolloutParams(C.Structure):
+    """sn_rollout_params (include/stereonet_hip.h); rollout.RolloutParams is the Python face of it."""
+    _fields_ = [("cell_m", C.c_float), ("v_min", C.c_float), ("v_max", C.c_float), ("nv", C.c_int), ("w_min", C.c_float),
+                ("w_max", C.c_float), ("nw", C.c_int), ("sim_time_s", C.c_float), ("steps", C.c_int), ("lethal_cost", C.c_int),
+                ("centre_lethal_cost", C.c_int), ("unknown_cost", C.c_int), ("flags", C.c_int), ("w_goal", C.c_int), ("w_occ", C.c_int)]
+
+
+def rollout_params(p) -> SnRolloutParams:
+    """rollout.RolloutParams -> sn_rollout_params"""
+    if isinstance(p, SnRolloutParams):
+        return p
+    return SnRolloutParams(p.cell_m, p.v_min, p.v_max, p.nv, p.w_min, p.w_max, p.nw, p.sim_time_s, p.steps, p.lethal_cost,
+                           p.centre_lethal_cost, p.unknown_cost, p.flags, p.w_goal, p.w_occ)
+
+
+def _footprint(params, footprint) -> np.ndarray:
+    """float32 (nf, 2): `footprint`, or the one a rollout.RolloutParams carries"""
+    fp = getattr(params, "footprint", ()) if footprint is None else footprint
+    return np.ascontiguousarray(np.asarray(fp, np.float32).reshape(-1, 2))
+
+
 class SnRectifyInfo(C.Structure):
     _fields_ = [("src_w", C.c_int), ("src_h", C.c_int), ("w", C.c_int), ("h", C.c_int), ("valid_left", C.c_uint32),
                 ("valid_right", C.c_uint32)]
@@ -366,6 +387,10 @@ def load_library(path: Optional[str] = None):
     lib.sn_inflate_table.argtypes = [C.POINTER(SnInflateParams), u8p, C.POINTER(C.c_int)]
     lib.sn_inflate_grid.argtypes = [vp, ip, i8p, ip, ip, C.POINTER(SnInflateParams), u8p, i8p, vp, vp, ip, vp]
     lib.sn_navfn.argtypes = [vp, ip, u8p, ip, ip, i32p, i32p, C.POINTER(SnNavParams), vp, i32p, vp, C.POINTER(C.c_int), ip, vp]
+    lib.sn_rollout_tables.argtypes = [C.POINTER(SnRolloutParams), vp, ip, vp, vp]
+    lib.sn_rollout_pose_q.argtypes = [C.c_float, C.c_double, C.c_double, vp, vp]
+    lib.sn_rollout_velocity.argtypes = [C.POINTER(SnRolloutParams), ip, vp]
+    lib.sn_rollout.argtypes = [vp, ip, vp, vp, ip, ip, vp, vp, C.POINTER(SnRolloutParams), vp, ip, vp, vp, vp, ip, vp]
     lib.sn_infer_conf.argtypes = [vp, ip, vp, ip, ip, ip, C.POINTER(SnConfParams), i32p, fp, fp, u8p, vp, ip, vp]
     lib.sn_conf_mask.argtypes = [vp, ip, i32p, fp, C.POINTER(SnConfParams), i32p, fp, u8p, vp, ip, vp]
     lib.sn_get_refine_stats.argtypes = [vp, C.POINTER(SnRefineStats)]
@@ -379,7 +404,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_rollout_tables", "sn_rollout_pose_q", "sn_rollout_velocity", "sn_rollout", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -497,6 +522,43 @@ def inflate_table(params) -> np.ndarray:
     if rc:
         raise StereoNetError(rc, "sn_inflate_table")
     return T
+
+
+def rollout_tables(params, footprint=None):
+    """sn_rollout_tables (host only) -> (centres int32 (S, T+1, 3), offsets int32 (nw, T+1, nf, 2)); footprint (nf, 2) in metres,
+    or the one `params` carries; rollout.tables is the Python restatement (an entry may differ by one: two libms)."""
+    lib, prm, fp = load_library(), rollout_params(params), _footprint(params, footprint)
+    nf = fp.shape[0]
+    if lib.sn_rollout_tables(C.byref(prm), fp.ctypes.data, nf, None, None):      # the sizes below only mean something once accepted
+        raise StereoNetError(-1, "sn_rollout_tables")
+    centres = np.empty((prm.nv * prm.nw, prm.steps + 1, 3), np.int32)
+    offsets = np.empty((prm.nw, prm.steps + 1, nf, 2), np.int32)
+    rc = lib.sn_rollout_tables(C.byref(prm), fp.ctypes.data, nf, centres.ctypes.data, offsets.ctypes.data)
+    if rc:
+        raise StereoNetError(rc, "sn_rollout_tables")
+    return centres, offsets
+
+
+def rollout_pose_q(cell_m: float, origin_x_m: float, origin_y_m: float, poses) -> np.ndarray:
+    """sn_rollout_pose_q (host only): poses (x, y, yaw) or (n, 3) -> int32 (5,) or (n, 5) = {px, py, cq, sq, yaw_bam}"""
+    lib = load_library()
+    ps = np.ascontiguousarray(np.asarray(poses, np.float64))
+    flat = ps.reshape(-1, 3)
+    q = np.empty((flat.shape[0], 5), np.int32)
+    for k in range(flat.shape[0]):
+        rc = lib.sn_rollout_pose_q(cell_m, origin_x_m, origin_y_m, flat[k].ctypes.data, q[k].ctypes.data)
+        if rc:
+            raise StereoNetError(rc, "sn_rollout_pose_q")
+    return q[0] if ps.ndim == 1 else q
+
+
+def rollout_velocity(params, s: int):
+    """sn_rollout_velocity (host only): (v, w) of sample s"""
+    prm, out = rollout_params(params), (C.c_double * 2)()
+    rc = load_library().sn_rollout_velocity(C.byref(prm), s, out)
+    if rc:
+        raise StereoNetError(rc, "sn_rollout_velocity")
+    return out[0], out[1]
 
 
 def error_string(code: int) -> str:
@@ -858,6 +920,38 @@ class StereoNetHIP:
                                        potential_ptr or None, path_ptr or None, stats_ptr or None, C.byref(rounds), SN_MEM_DEVICE,
                                        stream or None), "sn_navfn")
         return rounds.value
+
+    # -- trajectory rollout -------------------------------------------------------------------------------
+    def rollout(self, cost: np.ndarray, potential: np.ndarray, poses_q, params, footprint=None, window=None, want=(True, True, True)):
+        """sn_rollout on host buffers: cost uint8 and potential uint32, (gh, gw) or (n, gh, gw) as inflate() and navfn() give them,
+        poses_q (n, 5) as rollout_pose_q gives it, window (n, 4) or None -> (samples uint32 (n, S, 2), best uint32 (n, 8), traj
+        int32 (n, T+1, 3), zeros where a map has no valid sample), None where `want` says an output is not asked for, leading n
+        dropped for a 2-D cost; rollout.reference is the twin.  params: rollout.RolloutParams."""
+        c = np.ascontiguousarray(cost, np.uint8)
+        if c.ndim not in (2, 3):
+            raise StereoNetError(-1, "rollout", f"cost of shape {c.shape}: (gh, gw) or (n, gh, gw) is needed")
+        n, (gh, gw) = (1 if c.ndim == 2 else c.shape[0]), c.shape[-2:]
+        pot = np.ascontiguousarray(potential, np.uint32)
+        if pot.shape != c.shape:
+            raise StereoNetError(-1, "rollout", f"potential of shape {pot.shape} over a cost of shape {c.shape}")
+        prm, fp = rollout_params(params), _footprint(params, footprint)
+        q = np.ascontiguousarray(np.asarray(poses_q, np.int32).reshape(n, 5))
+        win = None if window is None else np.ascontiguousarray(np.asarray(window, np.int32).reshape(n, 4))
+        S, T1 = max(prm.nv * prm.nw, 0), max(prm.steps + 1, 0)
+        outs = [np.zeros((n, S, 2), np.uint32) if want[0] else None, np.zeros((n, 8), np.uint32) if want[1] else None,
+                np.zeros((n, T1, 3), np.int32) if want[2] else None]
+        self._check(self._lib.sn_rollout(self._h, n, c.ctypes.data, pot.ctypes.data, gw, gh, q.ctypes.data, _np_ptr(win), C.byref(prm),
+                                         fp.ctypes.data, fp.shape[0], *[_np_ptr(a) for a in outs], SN_MEM_HOST, None), "sn_rollout")
+        return tuple(a if a is None or c.ndim == 3 else a[0] for a in outs)
+
+    def rollout_device(self, n: int, cost_ptr: int, potential_ptr: int, gw: int, gh: int, poses_ptr: int, params, footprint=None,
+                       window_ptr: int = 0, samples_ptr: int = 0, best_ptr: int = 0, traj_ptr: int = 0, stream: int = 0) -> None:
+        """sn_rollout on device pointers (0: that buffer is not given; the footprint is host memory); stream = hipStream_t as int
+        (0: the stage's own stream, and the call returns after completion)."""
+        prm, fp = rollout_params(params), _footprint(params, footprint)
+        self._check(self._lib.sn_rollout(self._h, n, cost_ptr or None, potential_ptr or None, gw, gh, poses_ptr or None, window_ptr or None,
+                                         C.byref(prm), fp.ctypes.data, fp.shape[0], samples_ptr or None, best_ptr or None, traj_ptr or None,
+                                         SN_MEM_DEVICE, stream or None), "sn_rollout")
 
     # -- ground plane -----------------------------------------------------------------------------------
     def ground(self, raw: np.ndarray, cam, params, labels: bool = True):

@@ -23,6 +23,7 @@
 #include "rclcpp/rclcpp.hpp"
 #include "nav_msgs/msg/occupancy_grid.hpp"
 #include "nav_msgs/msg/path.hpp"
+#include "geometry_msgs/msg/twist.hpp"
 #include "sensor_msgs/msg/image.hpp"
 #include "sensor_msgs/msg/laser_scan.hpp"
 #include "sensor_msgs/msg/point_cloud2.hpp"
@@ -77,6 +78,11 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   // costmap's fixed frame when the costmap is on), taken by every frame processed after the call.  Thread-safe; until the first
   // call nothing is published on /stereonet_plan.
   void SetGoal(double x_m, double y_m);
+
+  // this implementation's own: the robot's present velocity (m/s, rad/s) for the rollout (STEREONET_ROLLOUT), taken by every
+  // frame processed after the call: with the file's `acc` line it narrows the samples to those the motors reach (the window of
+  // sn_rollout).  Thread-safe; until the first call, or without an `acc` line, every sample is admitted.
+  void SetVelocity(double v, double w);
 
  protected:
   int SetNodePara() override;
@@ -154,6 +160,19 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // goal and start lines are the tools') turns it on and requires STEREONET_INFLATE; unset: off, nothing of it exists
     bool plan = false;
     sn_nav_params plan_params{};
+    // this implementation's own: the trajectory rollout (sn_rollout) over the inflated costs and the plan's potential from the
+    // robot's pose (SetBasePose in the costmap, the base frame's origin at yaw 0 in the obstacle grid): the best sample's velocity
+    // as geometry_msgs/Twist on /stereonet_cmd_vel (linear.x, angular.z; all zero without a valid sample) and its arc as
+    // nav_msgs/Path on /stereonet_local_plan (a pose per step in metres with the heading about z; empty without a valid sample),
+    // both right after /stereonet_plan with its header, so nothing before the first SetGoal.  STEREONET_ROLLOUT=<parameter file>
+    // (rollout.save_params' `key value` lines with its `point x y` footprint lines and the `acc acc_v acc_w dt` line of the
+    // window; cell_m is the source grid's, whatever the file says; the `pose` line is the tools') turns it on and requires
+    // STEREONET_PLAN; unset: off, nothing of it exists
+    bool rollout = false;
+    sn_rollout_params rollout_params{};
+    std::vector<float> rollout_footprint;         // [nf][2]
+    double rollout_acc[3] = {0.0, 0.0, 0.0};      // acc_v, acc_w, dt of the `acc` line
+    bool rollout_has_acc = false;
   };
 
   void DeclareAndReadParameters();
@@ -170,6 +189,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void PublishInflated(const nav_msgs::msg::OccupancyGrid& src);
   void ReadPlanSettings();
   void PublishPlan(const nav_msgs::msg::OccupancyGrid& src, const uint8_t* cost);
+  void ReadRolloutSettings();
+  void PublishRollout(const nav_msgs::msg::OccupancyGrid& src, const uint8_t* cost, const uint32_t* potential);
   bool FitGround(const int32_t* raw, sn_ground* out);
   void PublishPointCloud(const StereonetNodeOutput& request, const int32_t* raw);
   void ReadTemporalSettings();
@@ -206,6 +227,10 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   double goal_[2] = {0.0, 0.0};                  // of SetGoal, under base_pose_mu_
   bool has_goal_ = false;
   std::atomic<bool> goal_clamp_logged_{false};
+  rclcpp::Publisher<geometry_msgs::msg::Twist>::SharedPtr cmd_vel_out_;           // only while STEREONET_ROLLOUT is set and valid
+  rclcpp::Publisher<nav_msgs::msg::Path>::SharedPtr local_plan_out_;
+  double velocity_[2] = {0.0, 0.0};              // of SetVelocity, under base_pose_mu_
+  bool has_velocity_ = false;
   std::mutex base_pose_mu_;
   double base_pose_[3] = {0.0, 0.0, 0.0};        // x, y, yaw of SetBasePose
   sn_rectify* rectify_ = nullptr;                // only while STEREONET_RECTIFY names a valid calibration

@@ -111,6 +111,7 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
   ReadCostmapSettings();
   ReadInflateSettings();
   ReadPlanSettings();
+  ReadRolloutSettings();
   ReadTemporalSettings();
   ready_ = true;
 }
@@ -922,8 +923,11 @@ void StereonetNode::PublishPlan(const nav_msgs::msg::OccupancyGrid& src, const u
   // allocated once per thread that publishes, not per frame; max_path was bounded at start-up
   thread_local std::vector<int32_t> cells;
   cells.resize((size_t)cfg_.plan_params.max_path * 2);
+  thread_local std::vector<uint32_t> potential;      // the rollout scores its arcs by it
+  if (cfg_.rollout) potential.resize((size_t)gw * gh);
   uint32_t stats[5];
-  if (sn_navfn(net_->engine(), 1, cost, gw, gh, g, s, &cfg_.plan_params, nullptr, cells.data(), stats, nullptr, SN_MEM_HOST, nullptr) != SN_OK) {
+  if (sn_navfn(net_->engine(), 1, cost, gw, gh, g, s, &cfg_.plan_params, cfg_.rollout ? potential.data() : nullptr, cells.data(), stats, nullptr,
+               SN_MEM_HOST, nullptr) != SN_OK) {
     RCLCPP_ERROR(kLog, "plan failed: %s", sn_last_error(net_->engine()));
     return;
   }
@@ -938,6 +942,186 @@ void StereonetNode::PublishPlan(const nav_msgs::msg::OccupancyGrid& src, const u
   }
   if (stats[0]) RCLCPP_DEBUG(kLog, "plan: flags %u, %u cells", stats[0], stats[2]);
   plan_out_->publish(std::move(out));
+  if (cfg_.rollout) PublishRollout(src, cost, potential.data());
+}
+
+namespace {
+// rollout.load_params' text form: one value a key, `point x y` once per footprint point, `acc acc_v acc_w dt`; the tools'
+// `pose x y yaw` line is read past
+bool load_rollout_file(const char* path, sn_rollout_params* p, std::vector<float>* footprint, double* acc, bool* has_acc, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct FloatKey {
+    const char* name;
+    float* v;
+  } floats[] = {{"cell_m", &p->cell_m}, {"v_min", &p->v_min}, {"v_max", &p->v_max}, {"w_min", &p->w_min}, {"w_max", &p->w_max}, {"sim_time_s", &p->sim_time_s}};
+  struct IntKey {
+    const char* name;
+    int* v;
+  } ints[] = {{"nv", &p->nv},       {"nw", &p->nw},         {"steps", &p->steps},   {"lethal_cost", &p->lethal_cost}, {"centre_lethal_cost", &p->centre_lethal_cost},
+              {"unknown_cost", &p->unknown_cost}, {"flags", &p->flags}, {"w_goal", &p->w_goal}, {"w_occ", &p->w_occ}};
+  std::vector<std::string> seen;
+  std::string text;
+  for (int no = 1; std::getline(in, text); ++no) {
+    std::istringstream words(text.substr(0, text.find('#')));
+    std::string key, w;
+    if (!(words >> key)) continue;
+    std::vector<double> vals;
+    bool ok = true;
+    while (words >> w) {
+      char* end = nullptr;
+      vals.push_back(strtod(w.c_str(), &end));
+      ok = ok && end != w.c_str() && !*end;
+    }
+    const std::string at = "line " + std::to_string(no) + ": ";
+    if (key != "point") {
+      for (const std::string& k : seen)
+        if (k == key) {
+          *err = at + key + " twice";
+          return false;
+        }
+      seen.push_back(key);
+    }
+    bool known = true;
+    if (key == "point") {
+      ok = ok && vals.size() == 2;
+      if (ok) footprint->push_back((float)vals[0]), footprint->push_back((float)vals[1]);
+    } else if (key == "pose") {
+      ok = ok && vals.size() == 3;
+    } else if (key == "acc") {
+      ok = ok && vals.size() == 3;
+      if (ok) acc[0] = vals[0], acc[1] = vals[1], acc[2] = vals[2], *has_acc = true;
+    } else {
+      known = false;
+      ok = ok && vals.size() == 1;
+      for (const FloatKey& f : floats)
+        if (key == f.name) {
+          known = true;
+          if (ok) *f.v = (float)vals[0];
+        }
+      for (const IntKey& f : ints)
+        if (key == f.name) {
+          known = true;
+          ok = ok && vals[0] >= -1e9 && vals[0] <= 1e9 && vals[0] == (double)(int)vals[0];
+          if (ok) *f.v = (int)vals[0];
+        }
+    }
+    if (!known || !ok) {
+      *err = at + (known ? "wrong values for " : "unknown key ") + key;
+      return false;
+    }
+  }
+  return true;
+}
+
+// one axis of rollout.window_from_velocity: the lattice samples within `reach` of `at`, else the one nearest to it (the lower
+// on a tie); lattice(i) is sn_rollout_velocity's
+void window_axis(const sn_rollout_params& p, bool turn, double at, double reach, int32_t* lo, int32_t* hi) {
+  const int count = turn ? p.nw : p.nv;
+  int first = -1, last = -1, near = 0;
+  double near_d = 0.0;
+  for (int i = 0; i < count; ++i) {
+    double vw[2];
+    sn_rollout_velocity(&p, turn ? i : i * p.nw, vw);
+    const double l = vw[turn ? 1 : 0], d = std::fabs(l - at);
+    if (l >= at - reach && l <= at + reach) {
+      if (first < 0) first = i;
+      last = i;
+    }
+    if (i == 0 || d < near_d) near = i, near_d = d;
+  }
+  *lo = first < 0 ? near : first, *hi = first < 0 ? near : last;
+}
+}  // namespace
+
+// parsed and validated once here: what sn_rollout would refuse turns the stage off instead of failing every frame
+void StereonetNode::ReadRolloutSettings() {
+  const char* e = getenv("STEREONET_ROLLOUT");
+  if (!e || !*e) return;
+  sn_rollout_params& p = cfg_.rollout_params;
+  p = sn_rollout_params{0.05f, 0.f, 0.5f, 11, -1.f, 1.f, 21, 1.5f, 15, 254, 253, 0, 0, 1, 1};      // rollout.RolloutParams' defaults
+  std::string bad;
+  const double* a = cfg_.rollout_acc;
+  if (!cfg_.plan) bad = std::string("STEREONET_ROLLOUT=") + e + " requires STEREONET_PLAN";
+  else if (!load_rollout_file(e, &p, &cfg_.rollout_footprint, cfg_.rollout_acc, &cfg_.rollout_has_acc, &bad))
+    bad = std::string("STEREONET_ROLLOUT=") + e + ": " + bad;
+  else if (cfg_.rollout_footprint.size() > 2 * SN_ROLLOUT_MAX_POINTS ||
+           sn_rollout_tables(&p, cfg_.rollout_footprint.data(), (int)cfg_.rollout_footprint.size() / 2, nullptr, nullptr) != SN_OK)
+    bad = std::string("STEREONET_ROLLOUT=") + e + ": parameters or a footprint sn_rollout refuses";
+  else if (cfg_.rollout_has_acc && !(std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]) && a[0] >= 0.0 && a[1] >= 0.0 && a[2] >= 0.0))
+    bad = std::string("STEREONET_ROLLOUT=") + e + ": acc_v, acc_w and dt must be finite and not negative";
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no velocity command");
+    return;
+  }
+  cfg_.rollout = true;
+  cmd_vel_out_ = create_publisher<geometry_msgs::msg::Twist>("/stereonet_cmd_vel", 10);
+  local_plan_out_ = create_publisher<nav_msgs::msg::Path>("/stereonet_local_plan", 10);
+  RCLCPP_WARN_STREAM(kLog, "rollout: " << p.nv << " x " << p.nw << " samples over " << p.sim_time_s << " s in " << p.steps << " steps, "
+                                       << cfg_.rollout_footprint.size() / 2 << " footprint points, on /stereonet_cmd_vel and /stereonet_local_plan");
+}
+
+void StereonetNode::SetVelocity(double v, double w) {
+  std::lock_guard<std::mutex> lk(base_pose_mu_);
+  velocity_[0] = v, velocity_[1] = w;
+  has_velocity_ = true;
+}
+
+// geometry_msgs/Twist and nav_msgs/Path of the best velocity sample over the costs and the potential just made: one sn_rollout
+// call.  A frame whose pose or grid the call refuses, like one without a valid sample, commands a stop.
+void StereonetNode::PublishRollout(const nav_msgs::msg::OccupancyGrid& src, const uint8_t* cost, const uint32_t* potential) {
+  double pose[3] = {0.0, 0.0, 0.0}, vel[2];      // the obstacle grid is in the base frame: the robot stands at its origin, heading along x
+  bool moving;
+  {
+    std::lock_guard<std::mutex> lk(base_pose_mu_);
+    if (costmap_) memcpy(pose, base_pose_, sizeof(pose));
+    memcpy(vel, velocity_, sizeof(vel));
+    moving = has_velocity_;
+  }
+  const int gw = (int)src.info.width, gh = (int)src.info.height;
+  const double ox = src.info.origin.position.x, oy = src.info.origin.position.y;
+  sn_rollout_params p = cfg_.rollout_params;
+  p.cell_m = src.info.resolution;
+  const double cell = (double)p.cell_m;
+  int32_t q[5], window[4];
+  const bool windowed = moving && cfg_.rollout_has_acc && std::isfinite(vel[0]) && std::isfinite(vel[1]);
+  if (windowed) {
+    window_axis(p, false, vel[0], cfg_.rollout_acc[0] * cfg_.rollout_acc[2], &window[0], &window[1]);
+    window_axis(p, true, vel[1], cfg_.rollout_acc[1] * cfg_.rollout_acc[2], &window[2], &window[3]);
+  }
+  thread_local std::vector<int32_t> traj;
+  traj.resize((size_t)(p.steps + 1) * 3);
+  uint32_t best[8] = {SN_ROLLOUT_NO_VALID};
+  geometry_msgs::msg::Twist cmd;
+  nav_msgs::msg::Path arc;
+  arc.header = src.header;
+  if (sn_rollout_pose_q(p.cell_m, ox, oy, pose, q) != SN_OK) {
+    RCLCPP_ERROR(kLog, "rollout: the pose (%.3f, %.3f, %.3f) cannot be placed on the grid", pose[0], pose[1], pose[2]);
+  } else if (sn_rollout(net_->engine(), 1, cost, potential, gw, gh, q, windowed ? window : nullptr, &p, cfg_.rollout_footprint.data(),
+                        (int)cfg_.rollout_footprint.size() / 2, nullptr, best, traj.data(), SN_MEM_HOST, nullptr) != SN_OK) {
+    RCLCPP_ERROR(kLog, "rollout failed: %s", sn_last_error(net_->engine()));
+    best[0] = SN_ROLLOUT_NO_VALID;
+  }
+  if (!(best[0] & SN_ROLLOUT_NO_VALID)) {
+    double vw[2];
+    sn_rollout_velocity(&p, (int)best[1], vw);
+    cmd.linear.x = vw[0], cmd.angular.z = vw[1];
+    arc.poses.resize((size_t)p.steps + 1);
+    for (size_t t = 0; t < arc.poses.size(); ++t) {
+      const double half = (double)traj[3 * t + 2] / 65536.0 * 3.141592653589793;      // half the heading, in radians
+      arc.poses[t].header = src.header;
+      arc.poses[t].pose.position.x = ox + (double)traj[3 * t] / 256.0 * cell;
+      arc.poses[t].pose.position.y = oy + (double)traj[3 * t + 1] / 256.0 * cell;
+      arc.poses[t].pose.orientation.z = std::sin(half), arc.poses[t].pose.orientation.w = std::cos(half);
+    }
+  } else {
+    RCLCPP_DEBUG(kLog, "rollout: no valid sample (%u collide, %u without a route, %u outside the window)", best[5], best[6], best[7]);
+  }
+  cmd_vel_out_->publish(std::move(cmd));
+  local_plan_out_->publish(std::move(arc));
 }
 
 namespace {

@@ -343,6 +343,17 @@ struct sn_handle {
   struct Nav : Lane<NavSlots> {
     Nav() { buf[kPinWork].pinned = true; }
   } nav;
+  // sn_rollout.  the two tables of (key, key_fp), the samples' words where the caller wants none; host mode: cost, potential,
+  // poses, window, samples, best, traj
+  struct RolloutSlots {
+    enum { kCentres = 0, kOffsets, kCost, kPot, kPoses, kWindow, kSamples, kBest, kTraj, kCount };
+  };
+  struct Rollout : Lane<RolloutSlots> {
+    bool cached = false;               // buf[kCentres] and buf[kOffsets] hold the tables of (key, key_fp[0..2 * key_nf))
+    sn_rollout_params key{};
+    float key_fp[2 * SN_ROLLOUT_MAX_POINTS] = {};
+    int key_nf = 0;
+  } roll;
   // The staging of the calls that run on the inference stream (sn_depth_from_raw / sn_mirror_pair_i8 / sn_lr_check /
   // sn_infer_lrc / sn_infer_conf / sn_conf_mask): host-mode copies and the composites' intermediate maps.  Not a lane and no
   // lock: calls on one handle must not overlap.

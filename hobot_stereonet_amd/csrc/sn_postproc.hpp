@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane, costmap, inflation and the navigation function.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_inflate.hpp and sn_navfn.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane, costmap, inflation, the navigation function and the trajectory rollout.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_inflate.hpp, sn_navfn.hpp and sn_rollout.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -1733,6 +1733,112 @@ int sn_navfn(sn_handle* h, int n, const uint8_t* cost, int gw, int gh, const int
   if (int rc = b.close()) return rc;
   if (rounds_out) *rounds_out = b.c.blocking ? (int)*pin : -1;
   return SN_OK;
+}
+
+// ---- trajectory rollout (csrc/sn_rollout.hpp): a lane of the handle's; the tables of the last (parameters, footprint) pair stay
+// on the device, as the inflation lane keeps its cost table -----------------------------------------------------------------------
+int sn_rollout_tables(const sn_rollout_params* p, const float* footprint, int nf, int32_t* centres, int32_t* offsets) {
+  if (ro_params_check(p, footprint, nf)) return SN_ERR_ARG;
+  return ro_tables(p, footprint, nf, centres, offsets) ? SN_ERR_ARG : SN_OK;
+}
+
+int sn_rollout_pose_q(float cell_m, double origin_x_m, double origin_y_m, const double* pose, int32_t* q) {
+  if (!pose || !q) return SN_ERR_ARG;
+  int32_t tmp[5];
+  if (!ro_pose_q(cell_m, origin_x_m, origin_y_m, pose, tmp)) return SN_ERR_ARG;
+  memcpy(q, tmp, sizeof tmp);
+  return SN_OK;
+}
+
+int sn_rollout_velocity(const sn_rollout_params* p, int s, double* out) {
+  if (!out || ro_params_check(p, nullptr, 0) || s < 0 || s >= p->nv * p->nw) return SN_ERR_ARG;
+  out[0] = ro_lattice(p->v_min, p->v_max, p->nv, s / p->nw);
+  out[1] = ro_lattice(p->w_min, p->w_max, p->nw, s % p->nw);
+  return SN_OK;
+}
+
+int sn_rollout(sn_handle* h, int n, const uint8_t* cost, const uint32_t* potential, int gw, int gh, const int32_t* poses_q,
+               const int32_t* window, const sn_rollout_params* p, const float* footprint, int nf, uint32_t* samples, uint32_t* best,
+               int32_t* traj, int mem, void* stream) {
+  if (!h) return SN_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_rollout: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!p || !cost || !potential || !poses_q) return refuse("a NULL pointer");
+  if (n <= 0 || n > h->max_batch) return refuse("n outside 1..max_batch");
+  if (gw < 1 || gh < 1 || gw > kRoMaxSide || gh > kRoMaxSide) return refuse("gw and gh must be 1..4096");
+  if ((long long)gw * gh > SN_NAV_MAX_CELLS) return refuse("gw * gh must be at most 2^20");
+  if (const char* why = ro_params_check(p, footprint, nf)) return refuse(why);
+  if (!samples && !best && !traj) return refuse("one of samples, best and traj is needed");
+  if (((uintptr_t)potential | (uintptr_t)poses_q | (uintptr_t)window | (uintptr_t)samples | (uintptr_t)best | (uintptr_t)traj) & 3)
+    return refuse("a misaligned buffer");
+  const int S = p->nv * p->nw, steps1 = p->steps + 1;
+  const size_t cells = (size_t)gw * gh, cost_bytes = n * cells, pot_bytes = cost_bytes * 4, pose_bytes = (size_t)n * 20,
+               win_bytes = (size_t)n * 16, samples_bytes = (size_t)n * S * 8, best_bytes = (size_t)n * 32,
+               traj_bytes = (size_t)n * steps1 * 12;
+  {
+    const Span all[7] = {{cost, cost_bytes}, {potential, pot_bytes}, {poses_q, pose_bytes}, {window, win_bytes},
+                         {samples, samples_bytes}, {best, best_bytes}, {traj, traj_bytes}};
+    for (int i = 0; i < 7; ++i)
+      for (int j = i + 1; j < 7; ++j)
+        if (overlap({all[i]}, {all[j]})) return refuse("overlapping buffers");
+  }
+  using R = sn_handle::Rollout;
+  R& lane = h->roll;
+  const size_t centres_bytes = (size_t)S * steps1 * 12, offsets_bytes = (size_t)p->nw * steps1 * nf * 8;
+  auto cached = [&] {      // under the lane's lock: the device holds the tables of this (parameters, footprint) pair
+    return lane.cached && lane.key_nf == nf && !memcmp(&lane.key, p, sizeof *p) && (nf == 0 || !memcmp(lane.key_fp, footprint, (size_t)nf * 8));
+  };
+  // The key is tested first: a call with the pair of the one before builds no tables and uploads none.  A new pair is rare: its
+  // tables are built here, before the call is opened on any stream, so that a pair whose arcs reach too far is refused like
+  // every other bad argument; they are uploaded below, behind the lane's earlier calls, and waited for.
+  std::vector<int32_t> hc, ho;
+  auto build = [&]() -> const char* {
+    hc.resize(centres_bytes / 4), ho.resize(offsets_bytes / 4);
+    return ro_tables(p, footprint, nf, hc.data(), ho.data());
+  };
+  {
+    std::lock_guard<std::mutex> lk(lane.mu);
+    if (!cached())
+      if (const char* why = build()) return refuse(why);
+  }
+  Bracket b(h, "sn_rollout", mem, stream, lane);
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  if (s.rc) return s.rc;
+  const bool hit = cached();
+  if (!hit && hc.empty()) build();      // another thread's pair came in between; this one was accepted when it was cached
+  RoArgs a{};
+  int32_t* dcentres = s.scratch<int32_t>(R::kCentres, centres_bytes);
+  int32_t* doffsets = s.scratch<int32_t>(R::kOffsets, offsets_bytes ? offsets_bytes : 8);
+  if (s.rc) return s.rc;
+  if (!hit) {
+    lane.cached = false;
+    HIP_TRY(h, hipMemcpyAsync(dcentres, hc.data(), centres_bytes, hipMemcpyHostToDevice, st));
+    if (offsets_bytes) HIP_TRY(h, hipMemcpyAsync(doffsets, ho.data(), offsets_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    lane.key = *p, lane.key_nf = nf, lane.cached = true;
+    if (nf) memcpy(lane.key_fp, footprint, (size_t)nf * 8);
+  }
+  a.cost = s.in(R::kCost, cost, cost_bytes);
+  a.pot = s.in(R::kPot, potential, pot_bytes);
+  a.poses = s.in(R::kPoses, poses_q, pose_bytes);
+  a.window = window ? s.in(R::kWindow, window, win_bytes) : nullptr;
+  a.samples = s.out(R::kSamples, samples, samples_bytes, true);
+  a.best = s.out(R::kBest, best, best_bytes);
+  a.traj = s.inout(R::kTraj, traj, traj_bytes);      // a map without a valid sample keeps the caller's bytes
+  if (s.rc) return s.rc;
+  a.centres = dcentres, a.offsets = doffsets;
+  a.gw = gw, a.gh = gh, a.nv = p->nv, a.nw = p->nw, a.T = p->steps, a.nf = nf;
+  a.lethal = p->lethal_cost, a.centre_lethal = p->centre_lethal_cost, a.unknown_cost = p->unknown_cost, a.flags = p->flags;
+  a.w_goal = p->w_goal, a.w_occ = p->w_occ;
+  const unsigned groups = (unsigned)(p->nw * ((p->nv + kRoWaves - 1) / kRoWaves));
+  const size_t lds = std::max<size_t>((size_t)steps1 * nf * 8, 8);
+  hipLaunchKernelGGL(k_rollout_eval, dim3(groups, n), dim3(kRoThreads), lds, st, a);
+  if (a.best || a.traj) hipLaunchKernelGGL(k_rollout_best, dim3(n), dim3(kRoBestThreads), 0, st, a);
+  HIP_TRY(h, hipGetLastError());
+  return b.close();
 }
 
 }  // extern "C"

@@ -9,7 +9,7 @@ D1) needed to score the output against dataset ground truth.
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
         [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]] \
         [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]] [--inflate PARAMS_FILE] \
-        [--plan PARAMS_FILE]
+        [--plan PARAMS_FILE] [--rollout PARAMS_FILE]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
 (`images.bgr_to_nv12`) -> side-by-side frame -> `sn_infer_sbs_nv12` (split + pre-processing + network on the
@@ -95,6 +95,14 @@ it down from the start.  <i>.plan.pgm (the potential scaled to 0..254 by the fra
 cells at 255) and <i>.path.txt (one `x y` line per cell, start first) are written into --out; the summary gains "plan": per pair
 "flags" (1 goal blocked, 2 start unreachable, 4 path truncated, 8 unconverged: a file
 with max_rounds > 0 whose rounds did not finish the field), "reached", "path_cells", "p_start" and "blocked".
+
+--rollout PARAMS_FILE (rollout.save_params' `key value` lines with one `point x y` line per footprint point and an optional
+`pose x y yaw` in metres from the corner of the inflated grid; needs --plan) rolls a lattice of velocity commands forward over
+the inflated grid on the GPU (`sn_rollout`) and picks the one that ends nearest the goal without its footprint touching an
+obstacle.  The pose is the file's, else the centre of the plan's start cell (of cell (0, 0) without a start) at yaw 0; the file's
+cell_m must be the grid's.  <i>.rollout.txt (`cmd v w`, `best` and its eight words, then one `X Y heading` line per step in
+1/256 cell and 1/65536 turn) is written into --out; the summary gains "rollout": per pair "v", "w" (0 without a valid sample),
+"score" (null without one), "valid", "collided", "no_route" and "out_of_window".
 """
 import argparse
 import json
@@ -170,7 +178,7 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None, view=None, obstacle=None, ground=None, costmap=None, inflation=None, plan=None) -> List[dict]:
+                jpeg=None, view=None, obstacle=None, ground=None, costmap=None, inflation=None, plan=None, roll=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -210,7 +218,10 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     {"lethal", "inscribed", "inflated", "free", "unknown"}, and <i>.inflated.pgm is written.
     plan = a navfn.NavParams with its goal (and start) in cells, with `inflation`: engine.navfn of "inflated"; the record gains
     "potential" (uint32), "path" (int32 (cells, 2), empty without a start or a route) and "plan_stats" = navfn.STATS' keys, and
-    <i>.plan.pgm and <i>.path.txt are written."""
+    <i>.plan.pgm and <i>.path.txt are written.
+    roll = a rollout.RolloutParams with its footprint (and pose), with `plan`: engine.rollout of "inflated" and "potential"; the
+    record gains "rollout_best" (uint32 (8,)), "rollout_traj" (int32 (T+1, 3)) and "cmd" = (v, w), (0, 0) without a valid sample,
+    and <i>.rollout.txt is written."""
     left, right = read_pair_lists(left_list, right_list)
     gts = read_list(gt_list) if gt_list else None
     if gts is not None and len(gts) != len(left):
@@ -231,6 +242,8 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
         raise FileListError("the inflation needs the obstacle stage's grid")
     if plan is not None and inflation is None:
         raise FileListError("the plan needs the inflated grid")
+    if roll is not None and plan is None:
+        raise FileListError("the rollout needs the plan")
     try:
         if costmap is not None:
             cm = (engine.costmap(obstacle, costmap[0]), costmap[1])
@@ -238,7 +251,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
         _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground, cm,
-              inflation, plan)
+              inflation, plan, roll)
     finally:
         if cm is not None:
             cm[0].close()
@@ -250,7 +263,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
 
 
 def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None,
-          obstacle=None, ground=None, cm=None, inflation=None, plan=None):
+          obstacle=None, ground=None, cm=None, inflation=None, plan=None, rollp=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -340,6 +353,15 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             length = min(int(pstats[2]), plan.max_path) if cells is not None else 0
             rec.update(potential=pot, path=cells[:length] if cells is not None else np.zeros((0, 2), np.int32),
                        plan_stats=dict(zip(nav.STATS, (int(v) for v in pstats))))
+        if rollp is not None:          # over the costs and the field just made
+            from . import api, rollout as ro
+            cell = float(np.float32(rollp.cell_m))
+            sx, sy = plan.start if plan.start is not None else (0, 0)
+            pose = rollp.pose if rollp.pose is not None else ((sx + 0.5) * cell, (sy + 0.5) * cell, 0.0)
+            _, best, traj = engine.rollout(rec["inflated"], rec["potential"], api.rollout_pose_q(cell, 0.0, 0.0, pose), rollp,
+                                           want=(False, True, True))
+            found = not int(best[0]) & ro.NO_VALID
+            rec.update(rollout_best=best, rollout_traj=traj, cmd=api.rollout_velocity(rollp, int(best[1])) if found else (0.0, 0.0))
         if ply_dir:
             from . import pointcloud
             pts, cnt = engine.pointcloud(raw, camera, pointcloud.COMPACT, sbs, 2 * w)
@@ -399,6 +421,9 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
                 from . import navfn as nav
                 nav.write_pgm(os.path.join(out_dir, f"{i}.plan.pgm"), rec["potential"])
                 nav.write_path(os.path.join(out_dir, f"{i}.path.txt"), rec["path"])
+            if rollp is not None:
+                from . import rollout as ro
+                ro.write_rollout(os.path.join(out_dir, f"{i}.rollout.txt"), rec["cmd"][0], rec["cmd"][1], rec["rollout_best"], rec["rollout_traj"])
             if rect is not None:
                 from . import rectify as rct
                 images.write_ppm(os.path.join(out_dir, f"{i}.rect.ppm"), rct.sbs_to_rgb(sbs))
@@ -468,6 +493,9 @@ def main(argv=None) -> int:
     ap.add_argument("--plan", default=None, metavar="PARAMS_FILE",
                     help="write <i>.plan.pgm and <i>.path.txt: the cost-to-go of every cell of the inflated grid to the file's goal "
                          "and the path from its start, in cells, on the GPU; needs --inflate")
+    ap.add_argument("--rollout", default=None, metavar="PARAMS_FILE",
+                    help="write <i>.rollout.txt: the velocity command whose arc ends nearest the plan's goal without the file's "
+                         "footprint touching an obstacle of the inflated grid, and that arc, on the GPU; needs --plan")
     ap.add_argument("--render-true-colours", action="store_true", help="--render: the colour map's own colours, not the reference's R/B swap")
     ap.add_argument("--render-invalid-black", action="store_true", help="--render: pixels without a measurement (raw == 0) are black")
     ap.add_argument("--rectify", default=None, metavar="CALIB",
@@ -642,13 +670,27 @@ def main(argv=None) -> int:
                 raise ValueError("a start needs max_path > 0")
         except (OSError, ValueError) as e:
             ap.error(f"--plan {args.plan}: {e}")
+    roll = None
+    if args.rollout is not None:
+        from . import rollout as rmod
+        if plan is None:
+            ap.error("--rollout needs --plan")
+        try:
+            roll = rmod.load_params(args.rollout)
+            rmod.tables(roll)                      # every refusal of the stage, before the first pair is read
+            if np.float32(roll.cell_m) != np.float32(inflation.cell_m):
+                raise ValueError("cell_m is not the inflated grid's")
+            if roll.pose is not None:
+                rmod.pose_q(roll.cell_m, 0.0, 0.0, roll.pose)
+        except (OSError, ValueError) as e:
+            ap.error(f"--rollout {args.rollout}: {e}")
     prec = {"auto": api.PREC_AUTO, "f16": api.PREC_F16, "f16x3": api.PREC_F16X3, "fp32": api.PREC_FP32}[args.precision]
     try:
         read_pair_lists(args.left, args.right)          # fail on the lists before touching the GPU
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap, inflation=inflation, plan=plan)
+                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap, inflation=inflation, plan=plan, roll=roll)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -670,6 +712,11 @@ def main(argv=None) -> int:
     if plan is not None and recs:
         from . import navfn as nmod
         summary["plan"] = {k: [r["plan_stats"][k] for r in recs] for k in nmod.STATS}
+    if roll is not None and recs:
+        bests = [[int(x) for x in r["rollout_best"]] for r in recs]
+        summary["rollout"] = {"v": [r["cmd"][0] for r in recs], "w": [r["cmd"][1] for r in recs],
+                              "score": [None if b[0] & 1 else b[2] | b[3] << 32 for b in bests], "valid": [b[4] for b in bests],
+                              "collided": [b[5] for b in bests], "no_route": [b[6] for b in bests], "out_of_window": [b[7] for b in bests]}
     if gparams is not None and recs:
         for k in ("ground_found", "height_m", "pitch_deg", "roll_deg", "inliers"):
             summary[k] = [r[k] for r in recs]

@@ -1336,8 +1336,8 @@ int sn_inflate_grid(sn_handle *h, int n, const int8_t *occ /* [n][gh][gw] */, in
  *     still strictly decreases along the path, and the path still ends at the goal.
  *   rounds_out (host, nullable): how many rounds did work, for a call that returns after completion; -1 for one that only
  *     enqueues.  It depends on the schedule and belongs to no byte-for-byte comparison.
- * Not covered: the asynchronous sn_submit* slots, several goals per map, a goal tolerance, footprints with heading,
- * gradient-interpolated (sub-cell) paths, path smoothing, replanning from the previous frame's field. */
+ * Not covered: the asynchronous sn_submit* slots, several goals per map, a goal tolerance (footprints with heading are
+ * sn_rollout's, below), gradient-interpolated (sub-cell) paths, path smoothing, replanning from the previous frame's field. */
 #define SN_NAV_TILE_W            32
 #define SN_NAV_TILE_H            32
 #define SN_NAV_MAX_CELLS         (1 << 20)   /* gw * gh */
@@ -1359,6 +1359,108 @@ int sn_navfn(sn_handle *h, int n, const uint8_t *cost /* [n][gh][gw] */, int gw,
              const int32_t *starts /* [n][2], nullable */, const sn_nav_params *p, uint32_t *potential /* [n][gh][gw] */,
              int32_t *path /* [n][max_path][2] */, uint32_t *stats /* [n][5] */, int *rounds_out /* host, nullable */, int mem,
              void *stream);
+
+/* ---- trajectory rollout: from the plan to a velocity command (csrc/sn_rollout.hpp; hobot_stereonet_amd/rollout.py is the numpy
+ * twin, byte for byte) ----------------------------------------------------------------------------------------------------------
+ * The local planner of a navigation stack (base_local_planner / DWA), directly after the navigation function: sample velocity
+ * commands (v, w) on a fixed lattice, roll each forward along its constant-curvature arc for sim_time_s, reject the arcs on
+ * which the robot's footprint touches an obstacle, score the rest by the cost-to-go at the arc's end and the worst cost under
+ * the footprint, and take the cheapest.  sn_rollout does that for n maps: the cost grid of sn_inflate_grid, the potential of
+ * sn_navfn over the same grid, one pose per map.  The stage is stateless.  All trigonometry is in two host-built tables and
+ * the pose is quantised once on the host; everything below that is integer, so no tolerance appears anywhere.
+ *
+ * Samples.  S = nv * nw, sample s = iv * nw + iw, iv 0..nv-1, iw 0..nw-1.  The footprint is nf points {fx, fy} in metres in
+ *   the robot's frame (x ahead, y to the left), 0 <= nf <= SN_ROLLOUT_MAX_POINTS; the robot's centre is always checked as well.
+ * The host tables (sn_rollout_tables: pure host, no device), in double, in this order of operations, nothing contracted:
+ *   k256 = 256.0 / (double)cell_m
+ *   v(iv) = nv == 1 ? (double)v_min : (double)v_min + iv * (((double)v_max - (double)v_min) / (nv - 1)); w(iw) likewise
+ *   for t = 0..T (T = steps):  tau = ((double)sim_time_s * t) / T;  th = w * tau;
+ *     fabs(th) < 1e-6:  x = v * tau;  y = ((v * tau) * th) / 2;      otherwise  r = v / w;  x = r * sin(th);  y = r * (1 - cos(th))
+ *     centres int32 [S][T+1][3] = {llrint(x * k256), llrint(y * k256), llrint((th / 6.283185307179586) * 65536) & 0xFFFF}
+ *     offsets int32 [nw][T+1][nf][2] = {llrint((cos(th) * fx - sin(th) * fy) * k256), llrint((sin(th) * fx + cos(th) * fy) * k256)}
+ *       with fx, fy widened to double first
+ *   Either output may be NULL.  Two implementations of sin and cos may differ by an ulp, so an entry may differ by one between
+ *   them: a twin is fed the library's tables, as it is fed sn_inflate_table's.
+ *   SN_ERR_ARG: p NULL; cell_m, v_min, v_max, w_min, w_max or sim_time_s not finite; cell_m or sim_time_s <= 0; v_max < v_min or
+ *   w_max < w_min; nv or nw outside 1..64; steps outside 1..SN_ROLLOUT_MAX_STEPS; lethal_cost or centre_lethal_cost outside
+ *   1..255; unknown_cost outside 0..252; flags with bits other than SN_ROLLOUT_UNKNOWN_OK; w_goal or w_occ outside 0..32767 or
+ *   both 0; nf outside 0..64, a NULL footprint with nf > 0, a footprint value that is not finite; fabs(th) above 2^20 at any
+ *   step; any component of a centre, or of a centre plus an offset, above 2^21 in magnitude (8192 cells).
+ * sn_rollout_pose_q (pure host): q[5] = {px, py, cq, sq, yaw_bam} of a pose {x, y, yaw} (metres and radians, in the frame the
+ *   grid's origin is given in; origin = the outer corner of cell (0, 0)):  px = llrint((x - origin_x_m) * k256), py likewise:
+ *   grid coordinates in 1/256 cell;  cq = llrint(cos(yaw) * 2^30), sq = llrint(sin(yaw) * 2^30);  yaw_bam =
+ *   llrint((yaw / 6.283185307179586) * 65536) & 0xFFFF.  SN_ERR_ARG: a NULL pointer, cell_m not finite or <= 0, an origin or a
+ *   pose value that is not finite, fabs(yaw) above 2^20, |px| or |py| above 2^30.
+ * sn_rollout_velocity (pure host): out = {v(iv), w(iw)} of sample s as above; SN_ERR_ARG for parameters sn_rollout_tables
+ *   refuses or s outside 0..S-1.
+ *
+ * Per map, sample and step t = 0..T, all integer, int64 where written, >> arithmetic (it floors):
+ *   the centre is c = centres[s][t], footprint point f is c + offsets[iw][t][f], both {qx, qy} in 1/256 cell in the robot's frame
+ *   at step 0;  X = px + (((int64)cq * qx - (int64)sq * qy + 2^29) >> 30),  Y = py + (((int64)sq * qx + (int64)cq * qy + 2^29) >> 30);
+ *   the point lies in cell (X >> 8, Y >> 8).
+ *   A point outside the grid collides.  A cell of 255 collides unless flags has SN_ROLLOUT_UNKNOWN_OK, and with it is priced at
+ *   unknown_cost; 255 is tested first.  Any other cell collides when cost >= lethal_cost (a footprint point) or cost >=
+ *   centre_lethal_cost (the centre), and is priced at its cost otherwise.
+ *   A sample that collides anywhere has reason COLLISION, and its step is the smallest t at which any point collides.
+ *   Otherwise occ = the largest price over all steps and points, and g = potential at the centre's cell at step T;
+ *   g == SN_NAV_INF: reason NO_ROUTE.  Otherwise the sample is valid, score = (uint64)w_goal * g + (uint64)w_occ * occ < 2^48.
+ *   window int32 [n][4] = {iv_lo, iv_hi, iw_lo, iw_hi}, inclusive (nullable: every sample): a sample outside it is not walked and
+ *   has reason OUT_OF_WINDOW; an empty window is allowed.
+ * Outputs, each nullable, at least one required:
+ *   samples uint32 [n][S][2] = {g, info}: g is SN_NAV_INF unless the sample is valid; info = occ | reason << 8 | step << 16,
+ *     occ 0 unless valid, step 0 unless COLLISION.
+ *   best uint32 [n][8] = {flags, s_best, score_lo, score_hi, valid, collided, no_route, out_of_window}: the best sample is the
+ *     valid one with the smallest score, ties to the lowest s (the minimum of the word score << 16 | s, the same in any order
+ *     of reduction).  No valid sample: flags = SN_ROLLOUT_NO_VALID, s_best = score_lo = score_hi = 0xFFFFFFFF.  The four counts
+ *     sum to S.
+ *   traj int32 [n][T+1][3] = the best sample's centre per step, {X, Y, (yaw_bam + centres[s_best][t][2]) & 0xFFFF}: grid
+ *     coordinates in 1/256 cell and the heading in 1/65536 turn.  A map without a valid sample keeps the caller's bytes.
+ * SN_ERR_ARG is decided before anything is launched or written (sn_last_error(h) names the call): a NULL h, p, cost, potential
+ *   or poses_q, n outside 1..max_batch, gw or gh outside 1..4096 or gw * gh > 2^20, anything sn_rollout_tables refuses, no
+ *   output, potential, poses_q, window, samples, best or traj not 4-byte aligned (cost may lie anywhere), any buffer overlapping
+ *   another, a bad mem.  poses_q is as sn_rollout_pose_q writes it (|px|, |py| <= 2^30, |cq|, |sq| <= 2^30); with other words
+ *   nothing is read or written out of bounds, and the outputs mean nothing.
+ * mem / stream as sn_navfn with fixed rounds (for a call whose tables are cached, see below): the stage has its own lane on the handle; poses_q and window are in the same
+ *   memory kind as the grids, footprint is always host memory; the call returns after completion when mem is SN_MEM_HOST or
+ *   stream is NULL; device buffers + a caller stream only enqueue, so inflate -> navfn (fixed rounds) -> rollout run on one
+ *   stream without a host round trip.  May run beside sn_submit / sn_wait and the other stages.  Two kernel launches per call
+ *   (one where samples alone is wanted).  The tables of the last (parameters, footprint) pair stay on the device: a call with
+ *   the same pair builds and uploads nothing, one with another pair uploads its tables behind the lane's earlier calls and
+ *   waits for the upload.
+ * Not covered: the asynchronous sn_submit* slots, acceleration along the arc (each sample holds its velocity for the whole
+ * of sim_time_s; sn_rollout's caller narrows the window to what the motors reach), path-distance and oscillation terms,
+ * holonomic (sideways) samples, a score for rotation in place (such a sample ends where it began and is scored as that). */
+#define SN_ROLLOUT_MAX_STEPS      64          /* steps (T) */
+#define SN_ROLLOUT_MAX_POINTS     64          /* nf */
+#define SN_ROLLOUT_MAX_SIDE       64          /* nv, nw */
+#define SN_ROLLOUT_UNKNOWN_OK     1           /* params flags: a cell of 255 is priced at unknown_cost */
+#define SN_ROLLOUT_NO_VALID       1           /* best flags */
+#define SN_ROLLOUT_VALID          0           /* reasons */
+#define SN_ROLLOUT_OUT_OF_WINDOW  1
+#define SN_ROLLOUT_COLLISION      2
+#define SN_ROLLOUT_NO_ROUTE       3
+typedef struct sn_rollout_params {
+  float cell_m;               /* > 0, finite: the grid's cell */
+  float v_min, v_max;         /* m/s, v_min <= v_max */
+  int   nv;                   /* 1..64 */
+  float w_min, w_max;         /* rad/s, w_min <= w_max */
+  int   nw;                   /* 1..64 */
+  float sim_time_s;           /* > 0 */
+  int   steps;                /* T, 1..SN_ROLLOUT_MAX_STEPS */
+  int   lethal_cost;          /* 1..255: a footprint point collides when cost >= this; 254 is the natural value */
+  int   centre_lethal_cost;   /* 1..255: the same for the centre; 253 is the natural value */
+  int   unknown_cost;         /* 0..252: the price of a cell of 255 under SN_ROLLOUT_UNKNOWN_OK */
+  int   flags;                /* SN_ROLLOUT_UNKNOWN_OK or 0 */
+  int   w_goal, w_occ;        /* 0..32767 each, not both 0 */
+} sn_rollout_params;
+int sn_rollout_tables(const sn_rollout_params *p, const float *footprint /* [nf][2] */, int nf, int32_t *centres /* [S][T+1][3] */,
+                      int32_t *offsets /* [nw][T+1][nf][2] */);                                         /* pure host, no device */
+int sn_rollout_pose_q(float cell_m, double origin_x_m, double origin_y_m, const double *pose /* [3] */, int32_t *q /* [5] */);
+int sn_rollout_velocity(const sn_rollout_params *p, int s, double *out /* [2] */);
+int sn_rollout(sn_handle *h, int n, const uint8_t *cost /* [n][gh][gw] */, const uint32_t *potential /* [n][gh][gw] */, int gw,
+               int gh, const int32_t *poses_q /* [n][5] */, const int32_t *window /* [n][4], nullable */, const sn_rollout_params *p,
+               const float *footprint /* host [nf][2] */, int nf, uint32_t *samples /* [n][S][2] */, uint32_t *best /* [n][8] */,
+               int32_t *traj /* [n][T+1][3] */, int mem, void *stream);
 
 /* Measurement hook (bench.py --emulate-root-ingress): a device-to-device copy of `bytes` bytes by a kernel of exactly
  * `workgroups` workgroups of 256 threads on `stream` — the footprint of one RCCL receive (a few channels = a few
