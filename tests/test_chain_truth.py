@@ -4,7 +4,9 @@ tests/golden/scene_truth.py (an analytic world and a ray caster that share nothi
 What the stage tests cannot see is a convention that kernel, twin and loop got wrong together: the way y points, the sign of a
 yaw, the corner the window's origin names, window cells against world cells, the side an arc turns to, the way a ray clears.
 
-The chain and the checks are shared with tests/test_gpu_chain_truth.py, which feeds them what the kernels wrote.
+The chain and the checks are shared with tests/test_gpu_chain_truth.py, which feeds them what the kernels wrote.  Each check_*
+reads the api's arrays and hands cell centres in metres and values to a *_bounds function that holds the assertions;
+tests/test_node_truth.py hands the same functions what it decoded from the node's messages.
 
 Tolerances, all from the cell (c = 0.1 m), the map's depth step and the contracts' roundings; none from an output:
   dZ    half a step of the map's integer at the farthest wall ray of the scene, Z^2 * 192000 / (fx * B) * out_scale / 2;
@@ -188,33 +190,48 @@ def run_chain(scene, be, mistake=None):
 
 
 # ---- the checks: each takes a scene's name and what the chain made, prints its chain_truth line and asserts ------------------------------
-def check_grid(name, R):
+def grid_bounds(name, occupied, occupied_at, tag="chain_truth"):
     """Base frame, frame by frame.  An occupied cell's centre lies within sqrt(2)/2 c + dZ of a wall.  A cell that the truth gives
     at least min_obstacle_hits wall rays clear of every border (1e-3 c from a cell's edge and from the band's ends, plus E) is
     occupied: the rays that are clear fall in the cell whatever the others do.  That asks for every cell with min_obstacle_hits
     + 2 rays none of which is near a border, and for more.  The cells it leaves out are at most a fifth of those that received
-    any ray."""
+    any ray.
+
+    occupied[k]: the world xy (m, 2) of the centres of frame k's occupied cells; occupied_at(k, xy): whether the cell that holds
+    each base-frame point xy (m, 2) of frame k is occupied."""
     T = truth(name)
     scene, worst, must_all, any_all, missing = T["scene"], 0.0, 0, 0, []
     edge = 1e-3 + T["fit"] / CELL
     for k, pose in enumerate(scene.poses):
-        iy, ix = np.nonzero(R["occ"][k] == 100)
-        centres = st.to_world(pose, np.stack([GRID[0] + (ix + 0.5) * CELL, GRID[1] + (iy + 0.5) * CELL], -1))
-        if len(ix):
-            worst = max(worst, float(st.dist_to(T["segs"], centres).max()))
+        if len(occupied[k]):
+            worst = max(worst, float(st.dist_to(T["segs"], occupied[k]).max()))
         _, idx, near, _ = st.wall_rays(scene, pose, GRID, (Z_BAND[0] - T["fit"], Z_BAND[1] + T["fit"]), edge)
         key = idx[:, 1] * GRID[3] + idx[:, 0]
         cells = np.unique(key)
         sure = np.array([np.count_nonzero(~near[key == c]) for c in cells])
         must = cells[sure >= MIN_HITS]
         any_all, must_all = any_all + len(cells), must_all + len(must)
-        missing += [(k, int(c % GRID[3]), int(c // GRID[3])) for c in must if R["occ"][k].reshape(-1)[c] != 100]
+        got = occupied_at(k, np.stack([GRID[0] + (must % GRID[3] + 0.5) * CELL, GRID[1] + (must // GRID[3] + 0.5) * CELL], -1))
+        missing += [(k, int(c % GRID[3]), int(c // GRID[3])) for c in must[~np.asarray(got, bool)]]
     share = 1.0 - must_all / any_all
     bound = SQ2 / 2 * CELL + T["tol"]
-    print(f"chain_truth {name} | grid | occupied centre to wall {worst:.4f} m <= {bound:.4f} m | required cells {must_all} of {any_all}, left out {share:.3f} <= 0.2")
+    print(f"{tag} {name} | grid | occupied centre to wall {worst:.4f} m <= {bound:.4f} m | required cells {must_all} of {any_all}, left out {share:.3f} <= 0.2")
     assert worst <= bound, (worst, bound)
     assert share <= 0.2, share
     assert not missing, missing[:10]
+
+
+def check_grid(name, R):
+    """grid_bounds on the api's arrays: cell (ix, iy) of occ[k] covers [x_min + ix c, + c) x [y_min + iy c, + c) of the base frame"""
+    occupied = []
+    for k, pose in enumerate(truth(name)["scene"].poses):
+        iy, ix = np.nonzero(R["occ"][k] == 100)
+        occupied.append(st.to_world(pose, np.stack([GRID[0] + (ix + 0.5) * CELL, GRID[1] + (iy + 0.5) * CELL], -1)))
+
+    def occupied_at(k, xy):
+        ix, iy = np.floor((xy[:, 0] - GRID[0]) / CELL).astype(np.int64), np.floor((xy[:, 1] - GRID[1]) / CELL).astype(np.int64)
+        return R["occ"][k][iy, ix] == 100
+    grid_bounds(name, occupied, occupied_at)
 
 
 def _first_hit(origin, angles, segs):
@@ -231,60 +248,83 @@ def _first_hit(origin, angles, segs):
     return out
 
 
-def check_scan(name, R):
+def scan_bounds(name, ranges, sector, tag="chain_truth"):
     """Each finite range lies between the truth's nearest and farthest first wall along the beam, its two edges included, less
     and plus dZ: the form of test_obstacles.py's known answer, with the beam's inside sampled as well so that a wall's end or a
-    box's corner inside a beam is allowed for."""
+    box's corner inside a beam is allowed for.
+
+    ranges[k][b]: frame k's range of beam b; sector(b) -> the two base-frame angles between which beam b looks."""
     T = truth(name)
     scene, worst, count = T["scene"], -np.inf, 0
-    a0, da = float(np.float32(OP.angle_min_rad)), float(np.float32(OP.angle_increment_rad))
     for k, pose in enumerate(scene.poses):
-        for b in np.nonzero(np.isfinite(R["ranges"][k]))[0]:
-            hits = _first_hit(pose[:2], pose[2] + a0 + (b + np.linspace(0.0, 1.0, 65)) * da, T["segs"])
+        for b in np.nonzero(np.isfinite(ranges[k]))[0]:
+            lo, hi = sector(int(b))
+            hits = _first_hit(pose[:2], pose[2] + lo + np.linspace(0.0, 1.0, 65) * (hi - lo), T["segs"])
             hits = hits[np.isfinite(hits)]
             assert hits.size, (k, b, "a return where the truth has no wall")
-            r = float(R["ranges"][k][b])
+            r = float(ranges[k][b])
             over = max(hits.min() - r, r - hits.max())
             worst, count = max(worst, over), count + 1
-    print(f"chain_truth {name} | scan | {count} returns, furthest outside the truth's span {worst:.5f} m <= {T['tol']:.5f} m")
+    print(f"{tag} {name} | scan | {count} returns, furthest outside the truth's span {worst:.5f} m <= {T['tol']:.5f} m")
     assert count >= 10 * len(scene.poses) and worst <= T["tol"], (count, worst)
 
 
-def check_costmap(name, R):
-    """World frame, after the whole clip (see the module's docstring for D).  The window's origin is the cell of the pose less
-    half the window.  No known-free cell lies more than 1.5 c (+ E) inside what is hidden from every pose of the clip while also
-    more than sqrt(2) c from every wall: the shadow of a wall and the inside of a box stay unknown."""
+def check_scan(name, R):
+    """scan_bounds on the api's ranges: beam b covers [angle_min + b * increment, + increment)"""
+    a0, da = float(np.float32(OP.angle_min_rad)), float(np.float32(OP.angle_increment_rad))
+    scan_bounds(name, R["ranges"], lambda b: (a0 + b * da, a0 + (b + 1) * da))
+
+
+UNKNOWN, FREE, OCCUPIED = -1, 0, 1            # what costmap_bounds and scroll_bounds read a cell as
+
+
+def costmap_bounds(name, centres, state, tag="chain_truth"):
+    """World frame, after the whole clip (see the module's docstring for D).  No known-free cell lies more than 1.5 c (+ E)
+    inside what is hidden from every pose of the clip while also more than sqrt(2) c from every wall: the shadow of a wall and
+    the inside of a box stay unknown.
+
+    centres (mh, mw, 2): the world xy of every cell's centre; state (mh, mw): UNKNOWN, FREE or OCCUPIED."""
     T = truth(name)
     scene = T["scene"]
-    mw, mh = scene.window
-    assert R["origin"] == T["origins"][-1], (R["origin"], T["origins"][-1])
-    L = R["logodds"][-1]
-    centres = st.cell_centres(T["origins"][-1], CELL, mw, mh)
-    occupied = centres[L > 0]
+    occupied = centres[state == OCCUPIED]
     assert len(occupied) >= 10, "nothing is occupied"
     far = float(st.dist_to(T["any_ray"], occupied).max())
     lone = float(st.dist_to(occupied, T["sure"]).max())
-    free = (L < 0) & (L != costmap.UNKNOWN_L)
+    free = state == FREE
     # "beyond by more than 1.5 c": nothing within 1.5 c of the centre (the centre, and two rings around it) is seen from any pose
     ring = np.array([(0.0, 0.0)] + [(r * math.cos(a), r * math.sin(a)) for r, m in ((0.75, 16), (1.5, 32)) for a in np.arange(m) * 2 * math.pi / m])
     spots = centres[free][:, None, :] + ring[None] * (1.5 * CELL + T["fit"]) / 1.5
     seen = np.zeros(spots.shape[:2], bool)
     for pose in scene.poses:
         seen |= st.visible(scene, pose, spots)
-    hidden = np.zeros(L.shape, bool)
+    hidden = np.zeros(state.shape, bool)
     hidden[free] = ~seen.any(1)
     hidden &= st.dist_to(T["segs"], centres) > SQ2 * CELL + T["fit"]
-    print(f"chain_truth {name} | costmap | {len(occupied)} occupied, furthest from a seen wall point {far:.4f} m, seen wall point furthest from one "
+    print(f"{tag} {name} | costmap | {len(occupied)} occupied, furthest from a seen wall point {far:.4f} m, seen wall point furthest from one "
           f"{lone:.4f} m, both <= {T['D']:.4f} m | free cells {int(free.sum())}, hidden ones {int(hidden.sum())}")
     assert far <= T["D"], (far, T["D"])
     assert lone <= T["D"], (lone, T["D"])
     assert free.sum() >= 100 and not hidden.any(), centres[hidden][:5]
 
 
-def check_scroll(name, R):
+def logodds_state(L):
+    """the api's log-odds as costmap_bounds reads them: occupied is L > 0, free is L < 0"""
+    return np.where(L == costmap.UNKNOWN_L, UNKNOWN, np.where(L > 0, OCCUPIED, np.where(L < 0, FREE, 2))).astype(np.int8)
+
+
+def check_costmap(name, R):
+    """costmap_bounds on the api's log-odds, and: the window's origin is the cell of the pose less half the window"""
+    T = truth(name)
+    assert R["origin"] == T["origins"][-1], (R["origin"], T["origins"][-1])
+    costmap_bounds(name, st.cell_centres(T["origins"][-1], CELL, *T["scene"].window), logodds_state(R["logodds"][-1]))
+
+
+def scroll_bounds(name, known, tag="chain_truth"):
     """The clip that re-centres the window.  A cell of the final window that lay outside an earlier window is known only if it
     came into view (the image's horizontal field widened by 1.5 c) after it last came in: what scrolled out and back is unknown
-    again, however well it was seen before."""
+    again, however well it was seen before.
+
+    known (mh, mw): element [j][i] is the world cell (ox + i, oy + j) of the truth's final origin."""
     T = truth(name)
     scene = T["scene"]
     mw, mh = scene.window
@@ -302,29 +342,35 @@ def check_scroll(name, R):
         view = st.in_view(pose, centres, slack=1.5 * CELL + T["fit"])
         after |= view & (k >= entered)
         before |= view & (k < entered) & st.visible(scene, pose, centres)
-    known = R["logodds"][-1] != costmap.UNKNOWN_L
     back = before & ~after                      # seen once, scrolled out, back and not seen since
-    print(f"chain_truth {name} | scroll | the window moved by {shift} cells of {max(mw, mh)} | {int(back.sum())} cells seen, scrolled out and back: "
+    print(f"{tag} {name} | scroll | the window moved by {shift} cells of {max(mw, mh)} | {int(back.sum())} cells seen, scrolled out and back: "
           f"{int((back & known).sum())} known | known cells never in view since they came in: {int((known & ~after).sum())}")
     assert back.sum() >= 50, "no cell scrolled out and back"
     assert not (known & ~after).any()
 
 
-def check_inflation(name, R):
+def check_scroll(name, R):
+    scroll_bounds(name, R["logodds"][-1] != costmap.UNKNOWN_L)
+
+
+def inflation_bounds(name, centres, open_, tag="chain_truth"):
     """A cell whose cost is below 253, or 255 (unknown: sn_inflate_grid puts 253 or 254 over an unknown cell within the inscribed
-    radius), keeps the clearance from every seen wall point; a cell within the clearance of one is at 253 or 254."""
+    radius), keeps the clearance from every seen wall point; a cell within the clearance of one is at 253 or 254.
+
+    centres (mh, mw, 2): the world xy of every cell's centre; open_ (mh, mw): the cell is below 253 or unknown."""
     T = truth(name)
-    scene = T["scene"]
-    centres = st.cell_centres(T["origins"][-1], CELL, *scene.window)
     d = near_points(T["sure"], centres, T["clear"], T["segs"])
-    cost = R["cost"]
-    open_ = (cost < 253) | (cost == 255)
     nearest = float(d[open_].min())
     inside = d <= T["clear"]
-    print(f"chain_truth {name} | inflation | nearest passable cell to a seen wall point {nearest:.4f} m > {T['clear']:.4f} m | {int(inside.sum())} cells within "
+    print(f"{tag} {name} | inflation | nearest passable cell to a seen wall point {nearest:.4f} m > {T['clear']:.4f} m | {int(inside.sum())} cells within "
           f"that: {int((inside & open_).sum())} passable")
     assert inside.sum() >= 50
     assert nearest > T["clear"] and not (inside & open_).any()
+
+
+def check_inflation(name, R):
+    T = truth(name)
+    inflation_bounds(name, st.cell_centres(T["origins"][-1], CELL, *T["scene"].window), (R["cost"] < 253) | (R["cost"] == 255))
 
 
 def path_world(name, R):
@@ -360,6 +406,13 @@ def check_path(name, R):
     assert not blocked[cells[:, 1], cells[:, 0]].any()
     diag = np.abs(step).sum(1) == 2
     assert not (blocked[cells[:-1, 1] + step[:, 1], cells[:-1, 0]] | blocked[cells[:-1, 1], cells[:-1, 0] + step[:, 0]])[diag].any(), "a cut corner"
+    path_bounds(name, xy)
+
+
+def path_bounds(name, xy, tag="chain_truth"):
+    """the part of check_path that speaks of metres alone: xy (n, 2) are the world positions of the path's cells, start first"""
+    T = truth(name)
+    scene = T["scene"]
     clearance = float(near_points(T["sure"], xy, T["clear"] + 1.0, T["segs"]).min())
     assert not st.crosses_walls(scene, xy), "the path goes through a wall"
     gate = [st.crossing(a, b, *scene.gate) for a, b in zip(xy[:-1], xy[1:])]
@@ -369,7 +422,7 @@ def check_path(name, R):
     wit = st.witness(scene)
     assert st.witness_clearance(scene) >= INFLATION + 2 * CELL - 1e-9 and not st.crosses_walls(scene, st.geodesic(scene))
     hi = 1.0824 * 1.0102 * st.polyline_length(wit) + CELL * (len(wit) - 1)
-    print(f"chain_truth {name} | path | {len(cells)} cells, clearance {clearance:.4f} m > {T['clear']:.4f} m | crosses the opening at "
+    print(f"{tag} {name} | path | {len(xy)} cells, clearance {clearance:.4f} m > {T['clear']:.4f} m | crosses the opening at "
           f"{[tuple(round(float(v), 3) for v in p) for p in at]} | length {lo:.4f} <= {length:.4f} <= {hi:.4f} m")
     assert clearance > T["clear"]
     assert len(at) == 1, "the path does not cross the opening once"
@@ -381,6 +434,22 @@ def command(R):
     assert R["best"][0] == 0, ("no valid sample", R["best"].tolist())
     iv, iw = divmod(int(R["best"][1]), RP.nw)
     return RP.v_min + iv * (RP.v_max - RP.v_min) / (RP.nv - 1), RP.w_min + iw * (RP.w_max - RP.w_min) / (RP.nw - 1)
+
+
+def arc_bounds(name, v, w, xy, turns, arc_sign=1.0, tag="chain_truth"):
+    """check_rollout's bound on the best sample's trajectory (derived there): the world positions xy (steps + 1, 2) lie within
+    2 units of 1/256 cell per axis of the closed-form arc of (v, w) from the scene's last pose, and the headings `turns` (in
+    turns, any branch) within 2 units of 1/65536 turn of the arc's -> the arc (x, y, heading)"""
+    pose = np.asarray(truth(name)["scene"].poses[-1], np.float64)
+    t = RP.sim_time_s * np.arange(RP.steps + 1) / RP.steps
+    ax, ay, ah = st.arc(pose, v, arc_sign * w, t)
+    assert np.shape(xy) == (RP.steps + 1, 2) and np.shape(turns) == (RP.steps + 1,), (np.shape(xy), np.shape(turns))
+    off = float(np.abs(np.asarray(xy) - np.stack([ax, ay], -1)).max() / CELL * 256.0)
+    turn = (np.asarray(turns) * 65536.0 - ah / (2 * math.pi) * 65536.0 + 32768.0) % 65536.0 - 32768.0
+    print(f"{tag} {name} | rollout | command v {v:.3f} m/s w {w:+.2f} rad/s | traj off the arc by {off:.3f} <= 2 units of 1/256 cell, heading by "
+          f"{float(np.abs(turn).max()):.3f} <= 2 units of 1/65536 turn")
+    assert off <= 2.0 and np.abs(turn).max() <= 2.0, (off, float(np.abs(turn).max()))
+    return ax, ay, ah
 
 
 def check_rollout(name, R):
@@ -402,14 +471,8 @@ def check_rollout(name, R):
     pose = np.asarray(scene.poses[-1], np.float64)
     v, w = command(R)
     t = RP.sim_time_s * np.arange(RP.steps + 1) / RP.steps
-    ax, ay, ah = st.arc(pose, v, R["arc_sign"] * w, t)
     origin = np.asarray(T["origins"][-1], np.float64)
-    got = (origin + R["traj"][:, :2] / 256.0) * CELL
-    off = float(np.abs(got - np.stack([ax, ay], -1)).max() / CELL * 256.0)
-    turn = (R["traj"][:, 2] - ah / (2 * math.pi) * 65536.0 + 32768.0) % 65536.0 - 32768.0
-    print(f"chain_truth {name} | rollout | command v {v:.3f} m/s w {w:+.2f} rad/s | traj off the arc by {off:.3f} <= 2 units of 1/256 cell, heading by "
-          f"{float(np.abs(turn).max()):.3f} <= 2 units of 1/65536 turn")
-    assert off <= 2.0 and np.abs(turn).max() <= 2.0, (off, float(np.abs(turn).max()))
+    ax, ay, ah = arc_bounds(name, v, w, (origin + R["traj"][:, :2] / 256.0) * CELL, R["traj"][:, 2] / 65536.0, R["arc_sign"])
     centres = np.stack([ax, ay], -1)
     near = float(near_points(T["sure"], centres, T["clear"] + 1.0, T["segs"]).min())
     deepest, limit = 0.0, SQ2 * CELL + T["tol"]
@@ -454,22 +517,27 @@ def failures(name, R, checks=CHECKS):
     return out
 
 
-def check_mirror(a, b, Ra, Rb):
+def mirror_bounds(a, A, B, cmd_a, cmd_b, tag="chain_truth"):
     """The mirrored world as a whole: each occupied cell of either final costmap has an occupied cell of the other, flipped in
-    y, within one cell; the commands have the same v and opposite w within one step of the lattice."""
-    def cells(name, R, flip):
-        ox, oy = truth(name)["origins"][-1]
-        j, i = np.nonzero(R["logodds"][-1] > 0)
-        c = np.stack([i + ox, j + oy], -1)
-        return c * (1, -1) - (0, 1) if flip else c      # world cell cy covers [cy, cy + 1) c: its mirror image is cell -1 - cy
-    A, B = cells(a, Ra, False), cells(b, Rb, True)
-    gap = np.abs(A[:, None, :] - B[None, :, :]).max(-1)
-    (va, wa), (vb, wb) = command(Ra), command(Rb)
+    y, within one cell; the commands have the same v and opposite w within one step of the lattice.
+
+    A, B (m, 2): the world cells (cx, cy) that are occupied in the scene's and in its mirror image's final costmap."""
+    B = np.asarray(B) * (1, -1) - (0, 1)            # world cell cy covers [cy, cy + 1) c: its mirror image is cell -1 - cy
+    gap = np.abs(np.asarray(A)[:, None, :] - B[None, :, :]).max(-1)
+    (va, wa), (vb, wb) = cmd_a, cmd_b
     lattice = (RP.w_max - RP.w_min) / (RP.nw - 1)
-    print(f"chain_truth {a} | mirror | {len(A)} and {len(B)} occupied cells, furthest from its image {int(max(gap.min(1).max(), gap.min(0).max()))} <= 1 cell | "
+    print(f"{tag} {a} | mirror | {len(A)} and {len(B)} occupied cells, furthest from its image {int(max(gap.min(1).max(), gap.min(0).max()))} <= 1 cell | "
           f"commands ({va:.3f}, {wa:+.2f}) and ({vb:.3f}, {wb:+.2f})")
     assert gap.min(1).max() <= 1 and gap.min(0).max() <= 1
     assert va == vb and abs(wa + wb) <= lattice + 1e-12, (va, wa, vb, wb)
+
+
+def check_mirror(a, b, Ra, Rb):
+    def cells(name, R):
+        ox, oy = truth(name)["origins"][-1]
+        j, i = np.nonzero(R["logodds"][-1] > 0)
+        return np.stack([i + ox, j + oy], -1)
+    mirror_bounds(a, cells(a, Ra), cells(b, Rb), command(Ra), command(Rb))
 
 
 @functools.lru_cache(maxsize=None)
