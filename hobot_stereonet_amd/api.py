@@ -170,6 +170,21 @@ def costmap_params(p) -> SnCostmapParams:
     return SnCostmapParams(p.mw, p.mh, p.l_hit, p.l_miss, p.l_min, p.l_max, p.clear_margin_m, p.clear_min_m, p.clear_max_m)
 
 
+class SnElevationParams(C.Structure):
+    """sn_elevation_params (include/stereonet_hip.h); elevation.ElevationParams is the Python face of it."""
+    _fields_ = [("mw", C.c_int), ("mh", C.c_int), ("cell_m", C.c_float), ("base_from_cam", C.c_float * 12), ("z_min_m", C.c_float),
+                ("z_max_m", C.c_float), ("range_max_m", C.c_float), ("min_points", C.c_int), ("alpha", C.c_int),
+                ("max_step_mm", C.c_int), ("radius", C.c_int), ("flags", C.c_int)]
+
+
+def elevation_params(p) -> SnElevationParams:
+    """elevation.ElevationParams -> sn_elevation_params"""
+    if isinstance(p, SnElevationParams):
+        return p
+    return SnElevationParams(p.mw, p.mh, p.cell_m, (C.c_float * 12)(*p.base_from_cam), p.z_min_m, p.z_max_m, p.range_max_m,
+                             p.min_points, p.alpha, p.max_step_mm, p.radius, p.flags)
+
+
 class SnInflateParams(C.Structure):
     """sn_inflate_params (include/stereonet_hip.h); inflate.InflateParams is the Python face of it."""
     _fields_ = [("cell_m", C.c_float), ("inscribed_radius_m", C.c_float), ("inflation_radius_m", C.c_float), ("cost_scaling", C.c_float),
@@ -384,6 +399,12 @@ def load_library(path: Optional[str] = None):
     lib.sn_costmap_destroy.restype = None
     lib.sn_costmap_pose_q.argtypes = [vp, vp, i32p]
     lib.sn_costmap_push.argtypes = [vp, ip, vp, vp, i8p, fp, i8p, vp, vp, i32p, ip, vp]
+    lib.sn_elevation_create.argtypes = [vp, ip, C.POINTER(SnElevationParams), C.POINTER(vp)]
+    lib.sn_elevation_reset.argtypes = [vp, ip]
+    lib.sn_elevation_destroy.argtypes = [vp]
+    lib.sn_elevation_destroy.restype = None
+    lib.sn_elevation_pose_q.argtypes = [vp, vp, i32p]
+    lib.sn_elevation_push.argtypes = [vp, ip, vp, vp, vp, C.POINTER(SnCamera), vp, ip, vp, vp, vp, vp, vp, i32p, ip, vp]
     lib.sn_inflate_table.argtypes = [C.POINTER(SnInflateParams), u8p, C.POINTER(C.c_int)]
     lib.sn_inflate_grid.argtypes = [vp, ip, i8p, ip, ip, C.POINTER(SnInflateParams), u8p, i8p, vp, vp, ip, vp]
     lib.sn_navfn.argtypes = [vp, ip, u8p, ip, ip, i32p, i32p, C.POINTER(SnNavParams), vp, i32p, vp, C.POINTER(C.c_int), ip, vp]
@@ -404,7 +425,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_rollout_tables", "sn_rollout_pose_q", "sn_rollout_velocity", "sn_rollout", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_elevation_create", "sn_elevation_reset", "sn_elevation_pose_q", "sn_elevation_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_rollout_tables", "sn_rollout_pose_q", "sn_rollout_velocity", "sn_rollout", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -507,6 +528,27 @@ def costmap_pose_q(params, obstacle, poses) -> np.ndarray:
                 raise StereoNetError(rc, "sn_costmap_pose_q", f"pose {k}: {ps[k].tolist()}")
     finally:
         lib.sn_costmap_destroy(c)
+    return q[0] if np.ndim(poses) == 1 else q
+
+
+def elevation_pose_q(params, poses) -> np.ndarray:
+    """sn_elevation_pose_q (host only: an elevation object without an engine serves it): poses (x, y, yaw) or (n, 3) -> int32
+    (6,) or (n, 6) = {tx, ty, cq, sq, ox, oy}; elevation.pose_q is the Python twin (the two may differ by one unit in cq and sq:
+    two implementations of a double cos and sin)."""
+    lib, e = load_library(), C.c_void_p()
+    prm = elevation_params(params)
+    rc = lib.sn_elevation_create(None, 1, C.byref(prm), C.byref(e))
+    if rc:
+        raise StereoNetError(rc, "sn_elevation_create")
+    try:
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        q = np.empty((ps.shape[0], 6), np.int32)
+        for k in range(ps.shape[0]):
+            rc = lib.sn_elevation_pose_q(e, ps[k].ctypes.data, q[k].ctypes.data)
+            if rc:
+                raise StereoNetError(rc, "sn_elevation_pose_q", f"pose {k}: {ps[k].tolist()}")
+    finally:
+        lib.sn_elevation_destroy(e)
     return q[0] if np.ndim(poses) == 1 else q
 
 
@@ -1187,6 +1229,11 @@ class StereoNetHIP:
         (obstacles.ObstacleParams); params: costmap.CostmapParams.  Close it before the engine."""
         return Costmap(self, obstacle, params, streams)
 
+    def elevation(self, params, streams: int = 1) -> "Elevation":
+        """An Elevation (sn_elevation) of `streams` rolling elevation maps on this engine, fed by the engine's int32 maps;
+        params: elevation.ElevationParams.  Close it before the engine."""
+        return Elevation(self, params, streams)
+
     def rectifier(self, calib):
         """A Rectifier (sn_rectify) for this engine's model size from a rectify.Calib; close it before the engine."""
         return Rectifier(self, calib)
@@ -1833,6 +1880,78 @@ class Costmap(_Owned):
         self._eng._check(self._lib.sn_costmap_push(self._c, n, _np_ptr(ids), ps.ctypes.data, occ_ptr or None, ranges_ptr or None,
                                                    grid_ptr or None, logodds_ptr or None, stats_ptr or None, q.ctypes.data, SN_MEM_DEVICE,
                                                    stream or None), "sn_costmap_push")
+        return q
+
+
+class Elevation(_Owned):
+    """sn_elevation: a rolling elevation map with a step-height traversability verdict per stream, its state on the GPU
+    (elevation.Reference is the numpy twin).  A context object: the engine refuses to close while one of its maps is open."""
+    _destroy, _handle = "sn_elevation_destroy", "_e"
+    OUTPUTS = ("trav", "hi", "lo", "rise", "stats")
+
+    def __init__(self, engine: StereoNetHIP, params, streams: int = 1):
+        self._eng, self._lib, self._e = engine, engine._lib, C.c_void_p()
+        self.streams, self.params = int(streams), elevation_params(params)
+        engine._check(self._lib.sn_elevation_create(engine._h, self.streams, C.byref(self.params), C.byref(self._e)),
+                      "sn_elevation_create")
+
+    def reset(self, stream: int = -1):
+        """Stream `stream` (-1: all) starts afresh at its next push."""
+        self._eng._check(self._lib.sn_elevation_reset(self._e, int(stream)), "sn_elevation_reset")
+
+    def pose_q(self, poses) -> np.ndarray:
+        """sn_elevation_pose_q: (x, y, yaw) or (n, 3) -> int32 (6,) or (n, 6)"""
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        q = np.empty((ps.shape[0], 6), np.int32)
+        for k in range(ps.shape[0]):
+            self._eng._check(self._lib.sn_elevation_pose_q(self._e, ps[k].ctypes.data, q[k].ctypes.data), "sn_elevation_pose_q")
+        return q[0] if np.ndim(poses) == 1 else q
+
+    def _poses(self, poses, stream_of, n: int):
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        if ps.size != 3 * n:
+            raise StereoNetError(-1, "elevation push", f"{ps.size} pose numbers for {n} maps: (n, 3) is needed")
+        ids = None if stream_of is None else np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        if ids is not None and ids.size != n:
+            raise StereoNetError(-1, "elevation push", f"{ids.size} stream ids for {n} maps")
+        return ps, ids
+
+    def push(self, poses, raw: np.ndarray, cam, mounts: Optional[np.ndarray] = None, stream_of=None,
+             want=(True, True, True, True, True)):
+        """sn_elevation_push on host buffers: poses (n, 3) = x, y, yaw; raw int32 (H, W) or (n, H, W); cam a
+        pointcloud.Camera; mounts float32 (n, 12) or None (the parameters' mount); map k the next frame of stream stream_of[k]
+        (None: all of stream 0, one clip) -> (trav int8, hi int16, lo int16, rise uint16, each (n, mh, mw), stats uint32 (n, 4)
+        = {known, lethal, fused, points} per map, q int32 (n, 6)); `want` drops outputs (None in their place)."""
+        eng = self._eng
+        r = eng._maps(raw, "elevation push")
+        n = eng._count(r)
+        ps, ids = self._poses(poses, stream_of, n)
+        c = _sn_camera(cam, eng.width, eng.height)
+        m = None if mounts is None else np.ascontiguousarray(mounts, np.float32).reshape(-1)
+        if m is not None and m.size != 12 * n:
+            raise StereoNetError(-1, "elevation push", f"{m.size} mount numbers for {n} maps: (n, 12) is needed")
+        mh, mw = self.params.mh, self.params.mw
+        dts = (np.int8, np.int16, np.int16, np.uint16)
+        outs = [np.empty((n, mh, mw), d) if w_ else None for d, w_ in zip(dts, want)]
+        stats = np.zeros((n, 4), np.uint32) if want[4] else None
+        q = np.zeros((n, 6), np.int32)
+        eng._check(self._lib.sn_elevation_push(self._e, n, _np_ptr(ids), ps.ctypes.data, r.ctypes.data, C.byref(c), _np_ptr(m), 12,
+                                               *[_np_ptr(o) for o in outs], _np_ptr(stats), q.ctypes.data, SN_MEM_HOST, None),
+                   "sn_elevation_push")
+        return (*outs, stats, q)
+
+    def push_device(self, n: int, poses, raw_ptr: int, cam, mounts_ptr: int = 0, mount_stride: int = 12, stream_of=None,
+                    trav_ptr: int = 0, hi_ptr: int = 0, lo_ptr: int = 0, rise_ptr: int = 0, stats_ptr: int = 0,
+                    stream: int = 0) -> np.ndarray:
+        """sn_elevation_push on device pointers (0: absent / not wanted; poses and stream_of stay host sequences); stream =
+        hipStream_t as int (0: the object's own stream, and the call returns after completion) -> q int32 (n, 6)."""
+        ps, ids = self._poses(poses, stream_of, n)
+        c = _sn_camera(cam, self._eng.width, self._eng.height)
+        q = np.zeros((n, 6), np.int32)
+        self._eng._check(self._lib.sn_elevation_push(self._e, n, _np_ptr(ids), ps.ctypes.data, raw_ptr or None, C.byref(c),
+                                                     mounts_ptr or None, int(mount_stride), trav_ptr or None, hi_ptr or None,
+                                                     lo_ptr or None, rise_ptr or None, stats_ptr or None, q.ctypes.data,
+                                                     SN_MEM_DEVICE, stream or None), "sn_elevation_push")
         return q
 
 

@@ -145,6 +145,16 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // turns it on and requires STEREONET_OBSTACLES; unset: off, nothing of it exists
     sn_costmap_params costmap_params{};
     std::string costmap_frame = "odom";
+    // this implementation's own: a rolling elevation map with a step-height traversability verdict (sn_elevation_push) from the
+    // request's map at the pose of SetBasePose, with the frame's fitted mount while STEREONET_GROUND is on: the verdict as
+    // nav_msgs/OccupancyGrid on /stereonet_traversability, published after the obstacle topics (and the costmap's).
+    // STEREONET_ELEVATION=<parameter file> (elevation.save_params' `key value` lines, `frame` = the fixed frame's id, default
+    // odom) turns it on; it needs no STEREONET_OBSTACLES.  The file's line `feed_inflate 1` makes this grid the source of
+    // /stereonet_inflated_grid (and so of the plan and the rollout) in the place of the costmap's or the obstacle grid;
+    // without that line, or unset: nothing the node published before changes
+    sn_elevation_params elevation_params{};
+    std::string elevation_frame = "odom";
+    bool elevation_feeds_inflate = false;
     // this implementation's own: inflation by the robot's radius (sn_inflate_grid) of the grid a planner reads: nav_msgs/
     // OccupancyGrid on /stereonet_inflated_grid with the header and info of its source, published right after it: the costmap's
     // grid when the costmap is on, else the obstacle grid.  STEREONET_INFLATE=<parameter file> (inflate.save_params' `key value`
@@ -185,6 +195,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void ReadGroundSettings();
   void ReadCostmapSettings();
   void PublishCostmap(const StereonetNodeOutput& request, const int8_t* occ, const float* ranges);
+  void ReadElevationSettings();
+  void PublishElevation(const StereonetNodeOutput& request, const int32_t* raw, const float* mount);
   void ReadInflateSettings();
   void PublishInflated(const nav_msgs::msg::OccupancyGrid& src);
   void ReadPlanSettings();
@@ -222,6 +234,8 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   std::atomic<bool> render_no_frame_logged_{false};
   sn_costmap* costmap_ = nullptr;                // one stream; only while STEREONET_COSTMAP is set and valid
   rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr costmap_out_;
+  sn_elevation* elevation_ = nullptr;            // one stream; only while STEREONET_ELEVATION is set and valid
+  rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr traversability_out_;
   rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr inflated_out_;      // only while STEREONET_INFLATE is set and valid
   rclcpp::Publisher<nav_msgs::msg::Path>::SharedPtr plan_out_;                    // only while STEREONET_PLAN is set and valid
   double goal_[2] = {0.0, 0.0};                  // of SetGoal, under base_pose_mu_

@@ -109,6 +109,7 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
   if (cfg_.obstacles && cfg_.obstacle_params.beams)
     obstacle_scan_out_ = create_publisher<sensor_msgs::msg::LaserScan>("/stereonet_scan", 10);
   ReadCostmapSettings();
+  ReadElevationSettings();
   ReadInflateSettings();
   ReadPlanSettings();
   ReadRolloutSettings();
@@ -117,10 +118,12 @@ StereonetNode::StereonetNode(const std::string& node_name, const rclcpp::NodeOpt
 }
 
 StereonetNode::~StereonetNode() {
-  if (!temporal_ && !rectify_ && !costmap_) return;
+  if (!temporal_ && !rectify_ && !costmap_ && !elevation_) return;
   WaitIdle();      // requests in flight still pass through PostProcess; the engine is destroyed after the filter (~DnnNode)
   if (costmap_) sn_costmap_destroy(costmap_);
   costmap_ = nullptr;
+  if (elevation_) sn_elevation_destroy(elevation_);
+  elevation_ = nullptr;
   if (temporal_) sn_temporal_destroy(temporal_);
   temporal_ = nullptr;
   if (rectify_) sn_rectify_destroy(rectify_);
@@ -590,9 +593,10 @@ void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const i
     grid.info.height = p.gh;
     grid.info.origin.position.x = p.x_min_m;
     grid.info.origin.position.y = p.y_min_m;
-    if (cfg_.inflate && !costmap_) inflate_src = grid;      // the inflated grid follows this one
+    const bool feeds = cfg_.inflate && !costmap_ && !cfg_.elevation_feeds_inflate;
+    if (feeds) inflate_src = grid;      // the inflated grid follows this one
     obstacle_grid_out_->publish(std::move(grid));
-    if (cfg_.inflate && !costmap_) PublishInflated(inflate_src);
+    if (feeds) PublishInflated(inflate_src);
   }
   if (obstacle_scan_out_) {
     scan.header.stamp = request.msg_header->stamp;
@@ -717,9 +721,145 @@ void StereonetNode::PublishCostmap(const StereonetNodeOutput& request, const int
   map.info.origin.position.x = (double)q[4] * (double)cfg_.obstacle_params.cell_m;
   map.info.origin.position.y = (double)q[5] * (double)cfg_.obstacle_params.cell_m;
   nav_msgs::msg::OccupancyGrid inflate_src;
-  if (cfg_.inflate) inflate_src = map;      // the inflated grid follows this one
+  const bool feeds = cfg_.inflate && !cfg_.elevation_feeds_inflate;
+  if (feeds) inflate_src = map;      // the inflated grid follows this one
   costmap_out_->publish(std::move(map));
-  if (cfg_.inflate) PublishInflated(inflate_src);
+  if (feeds) PublishInflated(inflate_src);
+}
+
+namespace {
+// elevation.load_params' text form, as load_costmap_file; `feed_inflate` is the node's own key
+bool load_elevation_file(const char* path, sn_elevation_params* p, std::string* frame, bool* feed_inflate, std::string* err) {
+  std::ifstream in(path);
+  if (!in.good()) {
+    *err = "cannot be opened";
+    return false;
+  }
+  struct FloatKey {
+    const char* name;
+    float* v;
+  } floats[] = {{"cell_m", &p->cell_m}, {"z_min_m", &p->z_min_m}, {"z_max_m", &p->z_max_m}, {"range_max_m", &p->range_max_m}};
+  int feed = 0;
+  struct IntKey {
+    const char* name;
+    int* v;
+  } ints[] = {{"mw", &p->mw},         {"mh", &p->mh},   {"min_points", &p->min_points}, {"alpha", &p->alpha}, {"max_step_mm", &p->max_step_mm},
+              {"radius", &p->radius}, {"flags", &p->flags}, {"feed_inflate", &feed}};
+  std::vector<std::string> seen;
+  std::string text;
+  for (int no = 1; std::getline(in, text); ++no) {
+    std::istringstream words(text.substr(0, text.find('#')));
+    std::string key, w;
+    if (!(words >> key)) continue;
+    std::vector<std::string> vals;
+    while (words >> w) vals.push_back(w);
+    const std::string at = "line " + std::to_string(no) + ": ";
+    for (const std::string& k : seen)
+      if (k == key) {
+        *err = at + key + " twice";
+        return false;
+      }
+    seen.push_back(key);
+    auto number_of = [](const std::string& v, double* d) {
+      char* end = nullptr;
+      *d = strtod(v.c_str(), &end);
+      return end != v.c_str() && !*end;
+    };
+    double d = 0.0;
+    const bool number = vals.size() == 1 && number_of(vals[0], &d);
+    bool known = false, ok = true;
+    if (key == "frame") {
+      known = true, ok = vals.size() == 1;
+      if (ok) *frame = vals[0];
+    }
+    if (key == "base_from_cam") {
+      known = true, ok = vals.size() == 12;
+      for (size_t i = 0; ok && i < 12; ++i) {
+        ok = number_of(vals[i], &d);
+        p->base_from_cam[i] = (float)d;
+      }
+    }
+    for (const FloatKey& f : floats)
+      if (key == f.name) {
+        known = true, ok = number;
+        *f.v = (float)d;
+      }
+    for (const IntKey& f : ints)
+      if (key == f.name) {
+        known = true, ok = number && d == (double)(int)d;
+        *f.v = (int)d;
+      }
+    if (!known || !ok) {
+      *err = at + (known ? "wrong values for " : "unknown key ") + key;
+      return false;
+    }
+  }
+  if (feed != 0 && feed != 1) {
+    *err = "feed_inflate must be 0 or 1";
+    return false;
+  }
+  *feed_inflate = feed == 1;
+  return true;
+}
+}  // namespace
+
+// parsed and validated once here: what sn_elevation_create would refuse turns the stage off instead of failing every frame
+void StereonetNode::ReadElevationSettings() {
+  const char* e = getenv("STEREONET_ELEVATION");
+  if (!e || !*e) return;
+  // elevation.ElevationParams' defaults
+  sn_elevation_params& p = cfg_.elevation_params;
+  p = sn_elevation_params{};
+  p.mw = p.mh = 200, p.cell_m = 0.1f, p.z_min_m = -1.f, p.z_max_m = 1.5f, p.range_max_m = 6.f;
+  p.min_points = 3, p.alpha = 128, p.max_step_mm = 60, p.radius = 1;
+  std::string bad;
+  bool feed = false;
+  if (!load_elevation_file(e, &p, &cfg_.elevation_frame, &feed, &bad)) bad = std::string("STEREONET_ELEVATION=") + e + ": " + bad;
+  if (bad.empty() && cfg_.pointcloud_layout < 0 && !cfg_.obstacles && !cfg_.ground) ReadCamera(&bad);      // the point cloud's camera, read once
+  if (bad.empty() && sn_elevation_create(net_->engine(), 1, &p, &elevation_) != SN_OK) bad = sn_last_error(net_->engine());
+  if (!bad.empty()) {
+    RCLCPP_ERROR_STREAM(kLog, bad << ": no elevation map");
+    elevation_ = nullptr;
+    return;
+  }
+  cfg_.elevation_feeds_inflate = feed;
+  traversability_out_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/stereonet_traversability", 10);
+  RCLCPP_WARN_STREAM(kLog, "elevation: frame " << cfg_.elevation_frame << ", window " << p.mw << " x " << p.mh << " cells of " << p.cell_m
+                                               << " m on /stereonet_traversability, step " << p.max_step_mm << " mm over radius " << p.radius
+                                               << ", alpha " << p.alpha << (feed ? ", feeding the inflation" : ""));
+}
+
+// nav_msgs/OccupancyGrid of the traversability verdict after this frame: one sn_elevation_push call at the pose of SetBasePose
+// (with the frame's mount, from FitGround, where there is one), the stamp of the disparity message, the origin of the window
+// from the quantised pose
+void StereonetNode::PublishElevation(const StereonetNodeOutput& request, const int32_t* raw, const float* mount) {
+  const sn_elevation_params& p = cfg_.elevation_params;
+  double pose[3];
+  {
+    std::lock_guard<std::mutex> lk(base_pose_mu_);
+    memcpy(pose, base_pose_, sizeof(pose));
+  }
+  nav_msgs::msg::OccupancyGrid map;
+  map.data.resize((size_t)p.mw * p.mh);
+  int32_t q[6];
+  if (sn_elevation_push(elevation_, 1, nullptr, pose, raw, &cfg_.camera, mount, 12, map.data.data(), nullptr, nullptr, nullptr, nullptr, q,
+                        SN_MEM_HOST, nullptr) != SN_OK) {
+    RCLCPP_ERROR(kLog, "elevation failed: %s", sn_last_error(net_->engine()));
+    return;
+  }
+  map.header.stamp = request.msg_header->stamp;
+  map.header.frame_id = cfg_.elevation_frame;
+  map.info.map_load_time = request.msg_header->stamp;
+  map.info.resolution = p.cell_m;
+  map.info.width = p.mw;
+  map.info.height = p.mh;
+  map.info.origin.position.x = (double)q[4] * (double)p.cell_m;
+  map.info.origin.position.y = (double)q[5] * (double)p.cell_m;
+  nav_msgs::msg::OccupancyGrid inflate_src;
+  const bool feeds = cfg_.inflate && cfg_.elevation_feeds_inflate;
+  if (feeds) inflate_src = map;      // the inflated grid follows this one
+  traversability_out_->publish(std::move(map));
+  if (feeds) PublishInflated(inflate_src);
 }
 
 namespace {
@@ -786,10 +926,12 @@ void StereonetNode::ReadInflateSettings() {
   p = sn_inflate_params{0.05f, 0.2f, 0.4f, 10.f, 100, 0};
   std::string bad;
   int R = 0;
-  if (!cfg_.obstacles || !cfg_.obstacle_params.gw) bad = std::string("STEREONET_INFLATE=") + e + " requires STEREONET_OBSTACLES with a grid";
+  const bool from_elevation = elevation_ && cfg_.elevation_feeds_inflate;
+  if (!from_elevation && (!cfg_.obstacles || !cfg_.obstacle_params.gw))
+    bad = std::string("STEREONET_INFLATE=") + e + " requires STEREONET_OBSTACLES with a grid";
   else if (!load_inflate_file(e, &p, &bad)) bad = std::string("STEREONET_INFLATE=") + e + ": " + bad;
   else {
-    p.cell_m = cfg_.obstacle_params.cell_m;
+    p.cell_m = from_elevation ? cfg_.elevation_params.cell_m : cfg_.obstacle_params.cell_m;
     if (sn_inflate_table(&p, nullptr, &R) != SN_OK) bad = std::string("STEREONET_INFLATE=") + e + ": parameters sn_inflate_table refuses";
   }
   if (!bad.empty()) {
@@ -798,7 +940,8 @@ void StereonetNode::ReadInflateSettings() {
   }
   cfg_.inflate = true;
   inflated_out_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/stereonet_inflated_grid", 10);
-  RCLCPP_WARN_STREAM(kLog, "inflation: " << (costmap_ ? "/stereonet_costmap" : "/stereonet_obstacle_grid") << " on /stereonet_inflated_grid, inscribed "
+  RCLCPP_WARN_STREAM(kLog, "inflation: " << (from_elevation ? "/stereonet_traversability" : costmap_ ? "/stereonet_costmap" : "/stereonet_obstacle_grid")
+                                         << " on /stereonet_inflated_grid, inscribed "
                                          << p.inscribed_radius_m << " m, out to " << p.inflation_radius_m << " m (" << R << " cells), scaling "
                                          << p.cost_scaling << ", lethal from " << p.lethal_min);
 }
@@ -906,7 +1049,7 @@ void StereonetNode::PublishPlan(const nav_msgs::msg::OccupancyGrid& src, const u
     std::lock_guard<std::mutex> lk(base_pose_mu_);
     if (!has_goal_) return;
     memcpy(goal, goal_, sizeof(goal));
-    if (costmap_) robot[0] = base_pose_[0], robot[1] = base_pose_[1];
+    if (costmap_ || cfg_.elevation_feeds_inflate) robot[0] = base_pose_[0], robot[1] = base_pose_[1];      // a grid in the fixed frame
   }
   const int gw = (int)src.info.width, gh = (int)src.info.height;
   const double res = (double)src.info.resolution, ox = src.info.origin.position.x, oy = src.info.origin.position.y;
@@ -1077,7 +1220,7 @@ void StereonetNode::PublishRollout(const nav_msgs::msg::OccupancyGrid& src, cons
   bool moving;
   {
     std::lock_guard<std::mutex> lk(base_pose_mu_);
-    if (costmap_) memcpy(pose, base_pose_, sizeof(pose));
+    if (costmap_ || cfg_.elevation_feeds_inflate) memcpy(pose, base_pose_, sizeof(pose));      // a grid in the fixed frame
     memcpy(vel, velocity_, sizeof(vel));
     moving = has_velocity_;
   }
@@ -1518,11 +1661,12 @@ int StereonetNode::PostProcess(const std::shared_ptr<hobot::dnn_node::DnnNodeOut
   }
   if (pointcloud_out_ && !request->output_tensors.empty())
     PublishPointCloud(*request, static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr));
-  if ((cfg_.obstacles || cfg_.ground) && !request->output_tensors.empty()) {
+  if ((cfg_.obstacles || cfg_.ground || elevation_) && !request->output_tensors.empty()) {
     const int32_t* raw = static_cast<const int32_t*>(request->output_tensors[0]->sysMem[0].virAddr);
     sn_ground g;
     const bool fitted = cfg_.ground && FitGround(raw, &g);
     if (cfg_.obstacles) PublishObstacles(*request, raw, fitted ? g.base_from_cam : nullptr);
+    if (elevation_) PublishElevation(*request, raw, fitted ? g.base_from_cam : nullptr);
   }
   const auto& st = node_output->rt_stat;
   if (st && st->fps_updated)

@@ -365,6 +365,7 @@ struct sn_handle {
   std::atomic<int> temporal_live{0};   // sn_temporal objects created on this handle and not yet destroyed: sn_destroy refuses
   std::atomic<int> rectify_live{0};    // ... and sn_rectify objects
   std::atomic<int> costmap_live{0};    // ... and sn_costmap objects
+  std::atomic<int> elevation_live{0};  // ... and sn_elevation objects
 };
 
 // sn_temporal_*: the one post-processing stage with state: a lane per filter, plus the state planes and the per-stream
@@ -395,6 +396,25 @@ struct sn_costmap : Lane<sn_costmap_slots> {
   long long gx0 = 0, gy0 = 0, margin = 0, rmin = 0, cmax = 0;
   int16_t* state = nullptr;          // device [streams][mh][mw]
   float* edges = nullptr;            // device [beams + 1]
+  std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
+  std::vector<int> ox, oy;           // per stream: the origin of its last frame
+};
+
+// sn_elevation_*: the 2.5-D map beside the costmap, with state in the same way: a lane per object, plus the two int16 planes
+// and per stream the "fresh" flag and the last origin.  kAcc: the accumulators of a call's frames (cnt, fmax, fmin, one plane
+// each); kPlanes: the unrolled hi and lo where the caller takes neither (device mode).  host mode: the maps (and their pinned
+// staging), the mounts, trav, hi, lo, rise, stats
+struct sn_elevation_slots {
+  enum { kAcc = 0, kPlanes, kRaw, kPinRaw, kMounts, kTrav, kHi, kLo, kRise, kStats, kCount };
+};
+struct sn_elevation : Lane<sn_elevation_slots> {
+  sn_elevation() { buf[kPinRaw].pinned = true; }
+  sn_handle* h = nullptr;            // nullptr: a host-only object that serves sn_elevation_pose_q alone
+  int streams = 0;
+  sn_elevation_params p{};
+  double k256 = 0.0;
+  int zmin_mm = 0, zmax_mm = 0;
+  int16_t* state = nullptr;          // device: hi [streams][mh][mw], then lo [streams][mh][mw]
   std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
   std::vector<int> ox, oy;           // per stream: the origin of its last frame
 };

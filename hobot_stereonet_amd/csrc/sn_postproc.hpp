@@ -1,8 +1,8 @@
 // sn_postproc.hpp — the host side of everything that follows (or wraps) the network: the pieces the entry points share — the
 // entry preamble, the k_pre_nv12 launcher, the per-call host staging, the call bracket (Bracket: what opens and closes every
 // call, on a lane or on the inference stream), the pair-input staging, the overlap predicates, the guide's geometry — and
-// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane, costmap, inflation, the navigation function and the trajectory rollout.  The kernels are in
-// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_inflate.hpp, sn_navfn.hpp and sn_rollout.hpp.  Part of the single translation
+// the C ABI of depth, point cloud, mirror, left-right check, confidence, filter, smoother, temporal filter, JPEG encoder, rectifier, render, obstacles, ground plane, costmap, elevation map, inflation, the navigation function and the trajectory rollout.  The kernels are in
+// sn_pointcloud.hpp, sn_lrcheck.hpp, sn_confidence.hpp, sn_dispfilter.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_jpeg.hpp, sn_rectify.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_elevation.hpp, sn_inflate.hpp, sn_navfn.hpp and sn_rollout.hpp.  Part of the single translation
 // unit stereonet_hip.hip.
 #pragma once
 
@@ -1581,6 +1581,229 @@ int sn_costmap_push(sn_costmap* c, int n, const int* stream_of, const double* po
       const int id = a.stream[g];
       c->fresh[id] = 0, c->ox[id] = a.q[last[g]][4], c->oy[id] = a.q[last[g]][5];
     }
+  }
+  return b.close();
+}
+
+// ---- rolling elevation map and traversability (csrc/sn_elevation.hpp): an object with its own state and lane, as the costmap ----
+namespace {
+// the contract's q of one pose (sn_costmap_pose_q's rule); false where sn_elevation_pose_q refuses it
+bool el_pose_q(const sn_elevation* e, const double* pose, int32_t* q) {
+  const double x = pose[0], y = pose[1], yaw = pose[2], lim = 1073741824.0;
+  if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(yaw)) return false;
+  const double fx = x * e->k256, fy = y * e->k256;
+  if (!(std::fabs(fx) <= lim) || !(std::fabs(fy) <= lim)) return false;
+  const long long tx = std::llrint(fx), ty = std::llrint(fy);
+  q[0] = (int32_t)tx, q[1] = (int32_t)ty;
+  q[2] = (int32_t)std::llrint(std::cos(yaw) * lim), q[3] = (int32_t)std::llrint(std::sin(yaw) * lim);
+  q[4] = (int32_t)((tx >> 8) - e->p.mw / 2), q[5] = (int32_t)((ty >> 8) - e->p.mh / 2);
+  return true;
+}
+
+// (int)floorf(v * 1000.f) for |v| <= 32
+int el_mm(float v) {
+  volatile float prod = v * 1000.f;      // one rounded fp32 product
+  return (int)std::floor(prod);
+}
+}  // namespace
+
+int sn_elevation_create(sn_handle* h, int streams, const sn_elevation_params* p, sn_elevation** out) {
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_elevation_create: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (!p || !out) return refuse("a NULL pointer");
+  if (streams < 1 || (h && streams > h->max_batch)) return refuse("streams must be 1..max_batch");
+  if (p->mw < 1 || p->mh < 1 || p->mw > kElMaxWindow || p->mh > kElMaxWindow) return refuse("mw and mh must be 1..4096");
+  for (float v : p->base_from_cam)
+    if (!std::isfinite(v)) return refuse("base_from_cam must be finite");
+  for (float v : {p->cell_m, p->z_min_m, p->z_max_m, p->range_max_m})
+    if (!std::isfinite(v)) return refuse("every parameter must be finite");
+  if (!(p->cell_m > 0.f)) return refuse("cell_m must be positive");
+  if (p->z_min_m < -32.f || p->z_max_m > 32.f || p->z_min_m > p->z_max_m) return refuse("-32 <= z_min_m <= z_max_m <= 32 is required");
+  if (!(p->range_max_m > 0.f)) return refuse("range_max_m must be positive");
+  if (p->min_points < 1) return refuse("min_points must be at least 1");
+  if (p->alpha < 1 || p->alpha > 256) return refuse("alpha must be 1..256");
+  if (p->max_step_mm < 1 || p->max_step_mm > 32767) return refuse("max_step_mm must be 1..32767");
+  if (p->radius < 1 || p->radius > kElMaxRadius) return refuse("radius must be 1..3");
+  if (p->flags != 0) return refuse("flags must be 0");
+  std::unique_ptr<sn_elevation> e(new sn_elevation);
+  e->h = h, e->streams = streams, e->p = *p;
+  e->k256 = 256.0 / (double)p->cell_m;
+  e->zmin_mm = el_mm(p->z_min_m), e->zmax_mm = el_mm(p->z_max_m);
+  e->fresh.assign(streams, 1);
+  e->ox.assign(streams, 0), e->oy.assign(streams, 0);
+  if (h) {      // without a handle: a host-only object for sn_elevation_pose_q
+    const int rc = check_device(h);
+    if (rc) return rc;
+    if (hipMalloc(reinterpret_cast<void**>(&e->state), (size_t)streams * p->mw * p->mh * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      set_err(h, "sn_elevation_create: out of device memory");
+      return SN_ERR_NOMEM;
+    }
+    ++h->elevation_live;
+  }
+  *out = e.release();
+  return SN_OK;
+}
+
+int sn_elevation_reset(sn_elevation* e, int stream) {
+  if (!e) return SN_ERR_ARG;
+  if (stream < -1 || stream >= e->streams) {
+    set_err(e->h, "sn_elevation_reset: bad arguments");
+    return SN_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (stream < 0) std::fill(e->fresh.begin(), e->fresh.end(), (uint8_t)1);
+  else e->fresh[stream] = 1;
+  return SN_OK;
+}
+
+void sn_elevation_destroy(sn_elevation* e) {
+  if (!e) return;
+  if (e->h) {
+    (void)hipSetDevice(e->h->device);
+    e->destroy();
+    (void)hipFree(e->state);
+    --e->h->elevation_live;
+  }
+  delete e;
+}
+
+int sn_elevation_pose_q(const sn_elevation* e, const double pose[3], int32_t q[6]) {
+  return e && pose && q && el_pose_q(e, pose, q) ? SN_OK : SN_ERR_ARG;
+}
+
+int sn_elevation_push(sn_elevation* e, int n, const int* stream_of, const double* poses, const int32_t* raw, const sn_camera* cam,
+                      const float* mounts, int mount_stride, int8_t* trav, int16_t* hi, int16_t* lo, uint16_t* rise, uint32_t* stats,
+                      int32_t* pose_q_out, int mem, void* stream) {
+  if (!e || !e->h) return SN_ERR_ARG;
+  sn_handle* h = e->h;
+  auto refuse = [&](const char* why) {
+    set_err(h, std::string("sn_elevation_push: ") + why);
+    return SN_ERR_ARG;
+  };
+  if (n <= 0 || n > h->max_batch || !poses || !raw) return refuse("bad arguments");
+  if (!camera_ok(cam)) return refuse("a camera sn_pointcloud_from_raw refuses");
+  if (!trav && !hi && !lo && !rise && !stats) return refuse("no output");
+  for (int k = 0; stream_of && k < n; ++k)
+    if (stream_of[k] < 0 || stream_of[k] >= e->streams) return refuse("a stream id out of range");
+  if (((uintptr_t)raw & 3) || ((uintptr_t)stats & 3) || ((uintptr_t)mounts & 3) || ((uintptr_t)hi & 1) || ((uintptr_t)lo & 1) ||
+      ((uintptr_t)rise & 1))
+    return refuse("a misaligned buffer");
+  if (mounts && mount_stride < 12) return refuse("mount_stride must be at least 12");
+  std::vector<int32_t> q((size_t)n * 6);
+  for (int k = 0; k < n; ++k)
+    if (!el_pose_q(e, poses + 3 * k, q.data() + 6 * k)) return refuse("a pose that is not finite or too far from the origin");
+  const int W = h->W, H = h->H, step = cam->step;
+  const int Wo = (W + step - 1) / step, Ho = (H + step - 1) / step;
+  const size_t cells = (size_t)e->p.mw * e->p.mh, raw_bytes = (size_t)n * H * W * 4;
+  const size_t mounts_bytes = mounts ? ((size_t)(n - 1) * mount_stride + 12) * 4 : 0;
+  {
+    const Span in[2] = {{raw, raw_bytes}, {mounts, mounts_bytes}};
+    const Span o[5] = {{trav, n * cells}, {hi, n * cells * 2}, {lo, n * cells * 2}, {rise, n * cells * 2}, {stats, (size_t)n * 16}};
+    for (int a = 0; a < 5; ++a) {
+      if (overlap({in[0], in[1]}, {o[a]})) return refuse("overlapping buffers");
+      for (int b = a + 1; b < 5; ++b)
+        if (overlap({o[a]}, {o[b]})) return refuse("overlapping buffers");
+    }
+  }
+  using T = sn_elevation;
+  Bracket b(h, "sn_elevation_push", mem, stream, *e);      // the wait: the previous push (any stream) is done with the state too
+  Staging& s = b.s;
+  hipStream_t st = b.c.st;
+  const int32_t* draw = s.in_pinned(T::kPinRaw, T::kRaw, raw, raw_bytes);
+  std::vector<float> packed;      // host mode: the mounts, twelve a map (the call is blocking, so it outlives the copy)
+  const float* dmounts = mounts;
+  if (mounts && s.host) {
+    packed.resize((size_t)n * 12);
+    for (int k = 0; k < n; ++k) memcpy(&packed[(size_t)k * 12], mounts + (size_t)k * mount_stride, 48);
+    dmounts = s.in(T::kMounts, packed.data(), packed.size() * 4);
+  }
+  const int dstride = mounts && s.host ? 12 : mount_stride;
+  int8_t* dtrav = s.out(T::kTrav, trav, n * cells);
+  uint16_t* drise = s.out(T::kRise, rise, n * cells * 2);
+  uint32_t* dstats = s.out(T::kStats, stats, (size_t)n * 16);
+  // the verdict reads the unrolled planes: where the caller takes one, that is the plane; otherwise the scratch (in host mode
+  // a caller's plane is the staged copy that is downloaded)
+  int16_t* dhi = hi ? s.out(T::kHi, hi, n * cells * 2) : nullptr;
+  int16_t* dlo = lo ? s.out(T::kLo, lo, n * cells * 2) : nullptr;
+  if (!dhi || !dlo) {
+    int16_t* planes = s.scratch<int16_t>(T::kPlanes, n * cells * 4);
+    if (planes && !dhi) dhi = planes;
+    if (planes && !dlo) dlo = planes + n * cells;
+  }
+  uint32_t* acc = s.scratch<uint32_t>(T::kAcc, n * cells * 12);
+  if (s.rc) return s.rc;
+  if (pose_q_out) memcpy(pose_q_out, q.data(), q.size() * 4);
+  uint32_t* dcnt = acc;
+  int32_t* dfmax = reinterpret_cast<int32_t*>(acc + n * cells);
+  int32_t* dfmin = reinterpret_cast<int32_t*>(acc + 2 * n * cells);
+  {
+    const ElClearArgs c{dcnt, dfmax, dfmin, dstats, n * cells, dstats ? (size_t)n * 4 : 0};
+    hipLaunchKernelGGL(k_el_clear, dim3((unsigned)std::min<size_t>((n * cells + 255) / 256, 2048)), dim3(256), 0, st, c);
+  }
+  ElScatterArgs sa{};
+  sa.pc.W = W, sa.pc.H = H, sa.pc.Wo = Wo, sa.pc.Ho = Ho, sa.pc.step = step;
+  sa.pc.scale = kOutScale, sa.pc.fB = cam->fx * cam->baseline_mm, sa.pc.fx = cam->fx, sa.pc.fy = cam->fy, sa.pc.cx = cam->cx, sa.pc.cy = cam->cy;
+  sa.pc.zmin = cam->z_min_m, sa.pc.zmax = cam->z_max_m;
+  bool level = true;
+  for (float v : e->p.base_from_cam) level = level && v == 0.f;
+  const float level_mount[12] = {0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0};
+  memcpy(sa.m, level ? level_mount : e->p.base_from_cam, sizeof sa.m);
+  sa.mount_stride = dstride;
+  sa.k256f = (float)e->k256, sa.range_max = e->p.range_max_m, sa.zmin_mm = e->zmin_mm, sa.zmax_mm = e->zmax_mm;
+  sa.mw = e->p.mw, sa.mh = e->p.mh;
+  ElFuseArgs fa{};
+  fa.S = e->state, fa.lo_off = (size_t)e->streams * cells;
+  fa.mw = e->p.mw, fa.mh = e->p.mh, fa.min_points = e->p.min_points, fa.alpha = e->p.alpha;
+  const int cblocks = (Wo + 255) / 256;
+  const unsigned slot_chunks = (unsigned)((cells + 255) / 256);
+  for (int k0 = 0; k0 < n; k0 += kElSlice) {      // the frame lists and the poses of kElSlice maps fit the kernel arguments
+    const int m = std::min(kElSlice, n - k0);
+    // a workgroup is 256 columns of a chunk of rows: about 2048 workgroups a launch, and runs of at least 16 rows
+    sa.chunks = std::max(1, std::min((2048 + cblocks * m - 1) / (cblocks * m), (Ho + 15) / 16));
+    sa.rows = (Ho + sa.chunks - 1) / sa.chunks;
+    sa.chunks = (Ho + sa.rows - 1) / sa.rows;
+    sa.pc.raw = draw + (size_t)k0 * H * W;
+    sa.mounts = dmounts ? dmounts + (size_t)k0 * dstride : nullptr;
+    sa.cnt = dcnt + k0 * cells, sa.fmax = dfmax + k0 * cells, sa.fmin = dfmin + k0 * cells;
+    memcpy(sa.q, q.data() + (size_t)k0 * 6, (size_t)m * 24);
+    const dim3 grid(cblocks * sa.chunks, m);
+    if (dmounts) hipLaunchKernelGGL(k_el_scatter<true>, grid, dim3(256), 0, st, sa);
+    else hipLaunchKernelGGL(k_el_scatter<false>, grid, dim3(256), 0, st, sa);
+    fa.cnt = sa.cnt, fa.fmax = sa.fmax, fa.fmin = sa.fmin;
+    fa.hi = dhi + k0 * cells, fa.lo = dlo + k0 * cells;
+    fa.stats = dstats ? dstats + (size_t)k0 * 4 : nullptr;
+    for (int k = 0; k < m; ++k) fa.org[k][0] = sa.q[k][4], fa.org[k][1] = sa.q[k][5];
+    int groups = 0, filled = 0;      // group the slice's maps by stream, in order of first appearance, each in the order of k
+    for (int k = 0; k < m; ++k) {
+      const int id = stream_of ? stream_of[k0 + k] : 0;
+      bool known = false;
+      for (int g = 0; g < groups && !known; ++g) known = fa.stream[g] == id;
+      if (!known) fa.stream[groups++] = id;
+    }
+    int last[kElSlice];      // per group: its last map of the slice
+    for (int g = 0; g < groups; ++g) {
+      const int id = fa.stream[g];
+      fa.first[g] = filled;
+      fa.fresh[g] = e->fresh[id], fa.pox[g] = e->ox[id], fa.poy[g] = e->oy[id];
+      for (int k = 0; k < m; ++k)
+        if ((stream_of ? stream_of[k0 + k] : 0) == id) fa.map[filled++] = k, last[g] = k;
+    }
+    fa.first[groups] = filled;
+    hipLaunchKernelGGL(k_el_fuse, dim3(slot_chunks, groups), dim3(256), 0, st, fa);
+    HIP_TRY(h, hipGetLastError());
+    for (int g = 0; g < groups; ++g) {      // enqueued: the state now holds these frames
+      const int id = fa.stream[g];
+      e->fresh[id] = 0, e->ox[id] = fa.org[last[g]][0], e->oy[id] = fa.org[last[g]][1];
+    }
+  }
+  if (dtrav || drise || dstats) {
+    ElVerdictArgs va{dhi, dlo, dtrav, drise, dstats, e->p.mw, e->p.mh, e->p.radius, e->p.max_step_mm, (e->p.mw + kElTileW - 1) / kElTileW};
+    const int tiles_y = (e->p.mh + kElTileH - 1) / kElTileH;
+    hipLaunchKernelGGL(k_el_verdict, dim3(va.tiles_x * tiles_y, n), dim3(256), 0, st, va);
+    HIP_TRY(h, hipGetLastError());
   }
   return b.close();
 }

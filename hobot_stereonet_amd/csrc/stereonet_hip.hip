@@ -28,7 +28,7 @@
 #include "../../include/stereonet_hip.h"
 #include "sn_internal.h"
 #include "sn_switches.hpp"      // the SN_* environment switches
-#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_rectify.hpp, sn_jpeg.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_inflate.hpp, sn_navfn.hpp, sn_rollout.hpp)
+#include "sn_kernels.hpp"       // device code (with sn_pointcloud.hpp, sn_lrcheck.hpp, sn_dispfilter.hpp, sn_confidence.hpp, sn_smooth.hpp, sn_temporal.hpp, sn_rectify.hpp, sn_jpeg.hpp, sn_render.hpp, sn_obstacles.hpp, sn_ground.hpp, sn_costmap.hpp, sn_elevation.hpp, sn_inflate.hpp, sn_navfn.hpp, sn_rollout.hpp)
 #include "sn_pointcloud.hpp"
 #include "sn_lrcheck.hpp"
 #include "sn_dispfilter.hpp"
@@ -41,6 +41,7 @@
 #include "sn_obstacles.hpp"
 #include "sn_ground.hpp"
 #include "sn_costmap.hpp"
+#include "sn_elevation.hpp"
 #include "sn_inflate.hpp"
 #include "sn_navfn.hpp"
 #include "sn_rollout.hpp"
@@ -48,7 +49,7 @@
 #include "sn_weights.hpp"       // .snw reader, weight packing and upload
 #include "sn_launch.hpp"        // kernel launchers and tensor geometry
 #include "sn_forward.hpp"       // workspace allocation, forward pass, refinement statistic, SN_PREC_AUTO
-#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter, smoother, temporal filter, rectifier, JPEG encoder, render, obstacles, ground, costmap, inflation, navigation function, rollout
+#include "sn_postproc.hpp"      // shared host staging + the C ABI of depth, point cloud, left-right check, confidence, filter, smoother, temporal filter, rectifier, JPEG encoder, render, obstacles, ground, costmap, elevation map, inflation, navigation function, rollout
 #include "sn_dbg_hooks.hpp"     // sn_dbg_* parity hooks
 
 // =====================================================================================================
@@ -373,6 +374,10 @@ int sn_destroy(sn_handle* h) {
   }
   if (h->costmap_live.load() > 0) {
     set_err(h, "sn_destroy: the handle still has costmaps (sn_costmap_destroy them first)");
+    return SN_ERR_BUSY;
+  }
+  if (h->elevation_live.load() > 0) {
+    set_err(h, "sn_destroy: the handle still has elevation maps (sn_elevation_destroy them first)");
     return SN_ERR_BUSY;
   }
   hipSetDevice(h->device);

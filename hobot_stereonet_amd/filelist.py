@@ -8,7 +8,8 @@ D1) needed to score the output against dataset ground truth.
         [--speckle MAX_PX[,DIFF_PX]] [--fill MAX_PX] [--conf MIN] [--smooth RADIUS[,SIGMA[,MIN_VALID]]] \
         [--temporal ALPHA,DELTA_PX[,PERSIST[,LUMA_DELTA]]] [--rectify calib.txt] [--jpeg Q[,ROWS]]
         [--render jpeg[,Q[,ROWS]]|ppm [--render-true-colours] [--render-invalid-black]] \
-        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]] [--inflate PARAMS_FILE] \
+        [--obstacles PARAMS_FILE] [--ground PARAMS_FILE] [--costmap PARAMS_FILE[,POSES_FILE]] [--elevation PARAMS_FILE[,POSES_FILE]] \
+        [--inflate PARAMS_FILE] \
         [--plan PARAMS_FILE] [--rollout PARAMS_FILE]
 
 Per frame i (same order as the reference): read left[i] / right[i] (8-bit colour image) -> BGR -> NV12
@@ -82,6 +83,12 @@ accumulates every frame's grid and scan on the GPU (`sn_costmap_push`) into a ro
 travels with the robot.  POSES_FILE holds one `x y yaw` line per pair (metres and radians in the map's fixed frame); without
 it every pair stands at the origin.  <i>.costmap.pgm (0 occupied .. 255 free, 128 unknown, world x up) is written into --out;
 the summary gains "costmap": per pair "known", "occupied" (cells with positive log-odds), "hit" and "cleared" (cells this frame).
+
+--elevation PARAMS_FILE[,POSES_FILE] (elevation.save_params' `key value` lines) treats the list as ONE clip and fuses every frame's
+final map on the GPU (`sn_elevation_push`) into a rolling elevation map with a step-height traversability verdict, at the frame's
+pose and, with --ground, under the frame's fitted mount.  <i>.trav.pgm (0 lethal, 255 drivable, 128 unknown, world x up) and
+<i>.hi.pgm (the cells' upper heights, 0 unknown) are written into --out; the summary gains "elevation": per pair "known", "lethal"
+and "fused" (cells this frame).
 
 --inflate PARAMS_FILE (inflate.save_params' `key value` lines; needs --obstacles with a grid) charges every cell for its distance
 to the nearest obstacle on the GPU (`sn_inflate_grid`): of the costmap's grid with --costmap, else of the obstacle grid, with
@@ -178,7 +185,8 @@ def score(pred: np.ndarray, gt: np.ndarray, valid: Optional[np.ndarray], dmax: O
 def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] = None,
                 gt_list: Optional[str] = None, log=None, ply_dir: Optional[str] = None, camera=None,
                 lrc=None, flt=None, conf: Optional[float] = None, smooth=None, temporal=None, rectify=None,
-                jpeg=None, view=None, obstacle=None, ground=None, costmap=None, inflation=None, plan=None, roll=None) -> List[dict]:
+                jpeg=None, view=None, obstacle=None, ground=None, costmap=None, inflation=None, plan=None, roll=None,
+                elevation=None) -> List[dict]:
     """Feeds every (left[i], right[i]) pair through `engine` (api.StereoNetHIP).  Returns one record per frame:
     {"frame_id", "left", "right", "raw" (int32 HxW), "disp" (float32 HxW)[, "metrics"][, "points"]}; with `out_dir` also
     writes <i>.raw.bin, <i>.disp.pfm and <i>.depth.ppm (the render node's colour map); with `ply_dir` <i>.ply, the
@@ -232,7 +240,9 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     w, h = engine.width, engine.height
     results = []
     tf = engine.temporal_filter(1, *temporal) if temporal is not None else None
-    rect = cm = None
+    rect = cm = ev = None
+    if elevation is not None and elevation[1] is not None and len(elevation[1]) != len(left):
+        raise FileListError(f"Poses size error! left_imgs.size: {len(left)}, poses.size: {len(elevation[1])}")
     if costmap is not None:
         if obstacle is None:
             raise FileListError("the costmap needs the obstacle stage")
@@ -247,14 +257,18 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
     try:
         if costmap is not None:
             cm = (engine.costmap(obstacle, costmap[0]), costmap[1])
+        if elevation is not None:
+            ev = (engine.elevation(elevation[0]), elevation[1])
         if rectify is not None:
             rect = engine.rectifier(rectify)
             camera = camera or rect.camera
         _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect, jpeg, view, obstacle, ground, cm,
-              inflation, plan, roll)
+              inflation, plan, roll, ev)
     finally:
         if cm is not None:
             cm[0].close()
+        if ev is not None:
+            ev[0].close()
         if rect is not None:
             rect.close()
         if tf is not None:
@@ -263,7 +277,7 @@ def run_imglist(engine, left_list: str, right_list: str, out_dir: Optional[str] 
 
 
 def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, smooth, tf, log, results, rect=None, jpeg=None, view=None,
-          obstacle=None, ground=None, cm=None, inflation=None, plan=None, rollp=None):
+          obstacle=None, ground=None, cm=None, inflation=None, plan=None, rollp=None, ev=None):
     w, h = engine.width, engine.height
     iw, ih = (rect.src_w, rect.src_h) if rect is not None else (w, h)      # the size of the listed images
     valid = rect.info if rect is not None else None
@@ -343,6 +357,11 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             grid, _, cstats, q = cm[0].push(pose, occ if obstacle.gw else None, ranges if obstacle.beams else None, want=(True, False, True))
             rec.update(costmap=grid[0], costmap_q=q[0],
                        costmap_stats=dict(zip(("known", "occupied", "hit", "cleared"), (int(v) for v in cstats[0]))))
+        if ev is not None:            # the clip's elevation map after this frame, with the frame's fitted mount where there is one
+            pose = np.zeros(3) if ev[1] is None else np.asarray(ev[1][i], np.float64)
+            trav, hi, _, _, estats, q = ev[0].push(pose, raw, camera or pointcloud.Camera(), mounts=mounts, want=(True, True, False, False, True))
+            rec.update(trav=trav[0], elevation_hi=hi[0], elevation_q=q[0],
+                       elevation_stats=dict(zip(("known", "lethal", "fused", "points"), (int(v) for v in estats[0]))))
         if inflation is not None:     # of the clip's map, or else of this frame's grid
             from . import inflate as infl
             cost, _, _, istats = engine.inflate(rec["costmap"] if cm is not None else occ, inflation, want=(True, False, False, True))
@@ -414,6 +433,11 @@ def _feed(engine, left, right, gts, out_dir, ply_dir, camera, lrc, flt, conf, sm
             if cm is not None:
                 from . import costmap as cmap
                 cmap.write_pgm(os.path.join(out_dir, f"{i}.costmap.pgm"), rec["costmap"])
+            if ev is not None:
+                from . import elevation as elev
+                from . import obstacles as obs
+                obs.write_pgm(os.path.join(out_dir, f"{i}.trav.pgm"), elev.trav_image(rec["trav"]))
+                obs.write_pgm(os.path.join(out_dir, f"{i}.hi.pgm"), elev.height_image(rec["elevation_hi"]))
             if inflation is not None:
                 from . import inflate as infl
                 infl.write_pgm(os.path.join(out_dir, f"{i}.inflated.pgm"), rec["inflated"])
@@ -487,6 +511,10 @@ def main(argv=None) -> int:
     ap.add_argument("--costmap", default=None, metavar="PARAMS_FILE[,POSES_FILE]",
                     help="write <i>.costmap.pgm: the list is one clip whose grids and scans accumulate on the GPU into a rolling "
                          "log-odds map with ray clearing; POSES_FILE: one `x y yaw` line per pair (default: the origin); needs --obstacles")
+    ap.add_argument("--elevation", default=None, metavar="PARAMS_FILE[,POSES_FILE]",
+                    help="write <i>.trav.pgm and <i>.hi.pgm: the list is one clip whose maps are fused on the GPU into a rolling "
+                         "elevation map with a step-height traversability verdict; POSES_FILE: one `x y yaw` line per pair (default: "
+                         "the origin); with --ground the frame's fitted mount is used; needs --out")
     ap.add_argument("--inflate", default=None, metavar="PARAMS_FILE",
                     help="write <i>.inflated.pgm: the cost of every cell after inflation by the robot's radius on the GPU, of the "
                          "costmap's grid with --costmap, else of the obstacle grid; needs --obstacles with a grid")
@@ -642,6 +670,24 @@ def main(argv=None) -> int:
             cmap = (cparams, cposes)
         except (OSError, ValueError) as e:
             ap.error(f"--costmap {args.costmap}: {e}")
+    elevation = None
+    if args.elevation is not None:
+        from . import costmap as cmod
+        from . import elevation as emod
+        try:
+            files = args.elevation.split(",")
+            if len(files) > 2:
+                raise ValueError("takes PARAMS_FILE[,POSES_FILE]")
+            eparams = emod.load_params(files[0])
+            why = emod.check(eparams) or (None if args.out else "needs --out")
+            if why:
+                raise ValueError(why)
+            eposes = cmod.load_poses(files[1]) if len(files) == 2 else None
+            for pose in (eposes if eposes is not None else []):
+                emod.pose_q(eparams, pose)
+            elevation = (eparams, eposes)
+        except (OSError, ValueError) as e:
+            ap.error(f"--elevation {args.elevation}: {e}")
     inflation = None
     if args.inflate is not None:
         import dataclasses
@@ -690,7 +736,8 @@ def main(argv=None) -> int:
         with api.StereoNetHIP(args.model, device=args.device, precision=prec) as eng:
             recs = run_imglist(eng, args.left, args.right, args.out, args.gt, log=lambda s: print(s, file=sys.stderr),
                                ply_dir=args.ply, camera=cam, lrc=lrc, flt=flt, conf=conf, smooth=smooth, temporal=temporal, rectify=calib,
-                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap, inflation=inflation, plan=plan, roll=roll)
+                               jpeg=jpg, view=rnd, obstacle=obstacle, ground=gparams, costmap=cmap, inflation=inflation, plan=plan, roll=roll,
+                               elevation=elevation)
     except (FileListError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 5
@@ -706,6 +753,8 @@ def main(argv=None) -> int:
             summary[k] = [r[k] for r in recs]
     if cmap is not None and recs:
         summary["costmap"] = {k: [r["costmap_stats"][k] for r in recs] for k in ("known", "occupied", "hit", "cleared")}
+    if elevation is not None and recs:
+        summary["elevation"] = {k: [r["elevation_stats"][k] for r in recs] for k in ("known", "lethal", "fused")}
     if inflation is not None and recs:
         from . import inflate as imod
         summary["inflate"] = {k: [r["inflate_stats"][k] for r in recs] for k in imod.STATS}

@@ -1220,6 +1220,114 @@ int  sn_costmap_push(sn_costmap *c, int n, const int *stream_of, const double *p
                      int8_t *grid /* [n][mh][mw] */, int16_t *logodds /* [n][mh][mw] */, uint32_t *stats /* [n][4] */,
                      int32_t *pose_q_out /* host [n][6], nullable */, int mem, void *stream);
 
+/* ---- rolling elevation map and step-height traversability, one map per STREAM (csrc/sn_elevation.hpp;
+ * hobot_stereonet_amd/elevation.py is the numpy twin, byte for byte) ------------------------------------------------------------
+ * sn_obstacles_from_raw assumes a flat floor at z = 0 of the base frame: a ramp reads as a wall, a drop as nothing, a kerb
+ * below z_lo_m as free.  sn_elevation keeps a 2.5-D map instead (elevation mapping, grid_map): per cell of a window that travels
+ * with the robot the highest and the lowest height seen, fused over time, and judges a cell by the height differences to its
+ * neighbours, not by a fixed band.  The verdict is an OccupancyGrid payload, so sn_inflate_grid -> sn_navfn -> sn_rollout take
+ * it as they take the costmap's grid.  Everything below the pose quantisation is integer or a single rounded fp32 operation
+ * in a stated order, so no tolerance appears anywhere.
+ *
+ * Units.  A "sub" is 1/256 of a cell; heights are millimetres.  Host quantities, computed once:
+ *     k256 = 256.0 / (double)cell_m,  k256f = (float)k256,
+ *     zmin_mm = (int)floorf(z_min_m * 1000.f),  zmax_mm = (int)floorf(z_max_m * 1000.f)     (one rounded fp32 product each)
+ *   sn_elevation_pose_q (pure host, no device) is sn_costmap_pose_q's rule with this object's cell_m, mw, mh:
+ *     q = {tx, ty, cq, sq, ox, oy}, tx = llrint(x * k256), ty likewise, cq = llrint(cos(yaw) * 2^30), sq = llrint(sin(yaw) * 2^30),
+ *     ox = (tx >> 8) - mw/2, oy = (ty >> 8) - mh/2; SN_ERR_ARG for a pose that is not finite or has |x| * k256 or |y| * k256
+ *     above 2^30.  A twin is fed the library's q.
+ * State per stream: two int16 planes hi[mh][mw] and lo[mh][mw] in millimetres, -32768 = unknown (a cell is known where hi is
+ *   not unknown; lo is unknown exactly where hi is).  The planes live on the costmap's torus: world cell (cx, cy) in slot
+ *   (cx mod mw, cy mod mh) (floor modulo); after a frame with origin (ox, oy), slot (i, j) holds the world cell
+ *   cx = ox + ((i - ox) mod mw), cy = oy + ((j - oy) mod mh).  A fresh or reset stream is all unknown and has no previous origin.
+ * One frame of a stream at pose q, in this order:
+ *   1. Scroll.  Where the stream has a previous origin and a slot's world cell under it differs from the one under the new
+ *      origin, hi = lo = unknown (a jump of more than a window clears everything; nothing is copied).
+ *   2. Frame accumulators, per cell of the frame's window: cnt = 0, fmax = INT32_MIN, fmin = INT32_MAX, then every sample:
+ *      The samples are sn_pointcloud_from_raw's: (u, v) = (j*step, i*step) of the map; Z, X, Y and valid exactly as there,
+ *      cam's z_min_m / z_max_m / step honoured.  xb, yb, zb are sn_obstacles_from_raw's (the same device functions: fp32, left
+ *      to right, every operation rounded, no FMA), with m = base_from_cam (all twelve zero: the level forward mount), or, where
+ *      `mounts` is not NULL, map k's twelve floats at mounts + k * mount_stride used as they are (the semantics of
+ *      sn_obstacles_from_raw_mounts; base_from_cam is then ignored and need not be finite).  A sample counts nowhere unless it
+ *      passes every test of this list, in this order:
+ *        valid, and zb is not NaN;
+ *        zmm = (int)floorf(zb * 1000.f), saturated to int32, has zmin_mm <= zmm <= zmax_mm;
+ *        sqrtf(xb*xb + yb*yb) <= range_max_m (two rounded products, one rounded sum: the obstacle stage's r; NaN fails);
+ *        sx = floorf(xb * k256f), sy = floorf(yb * k256f) (one rounded product each) have |sx| < 2^30 and |sy| < 2^30,
+ *          compared in float;
+ *        in int64, >> arithmetic:  wx = tx + ((cq*sx - sq*sy + 2^29) >> 30),   wy = ty + ((sq*sx + cq*sy + 2^29) >> 30);
+ *          the world cell (wx >> 8, wy >> 8) lies in the window: ox <= (wx >> 8) < ox + mw and oy <= (wy >> 8) < oy + mh.
+ *      For the cell: cnt += 1, fmax = max(fmax, zmm), fmin = min(fmin, zmm).  Integer accumulators only: the order of arrival
+ *      cannot matter.  (|cq|, |sq| <= 2^30 and |sx|, |sy| < 2^30, so every product stays below 2^60.)
+ *   3. Fuse, per slot whose cell has cnt >= min_points, in int32 with an arithmetic shift:
+ *        unknown:    hi = clamp(fmax), lo = clamp(fmin);
+ *        otherwise:  hi = clamp(hi + (((fmax - hi) * alpha + 128) >> 8)),  lo = clamp(lo + (((fmin - lo) * alpha + 128) >> 8)),
+ *      clamp(v) = min(max(v, -32767), 32767).  alpha = 256 replaces the old value.  A slot with fewer points keeps its state.
+ *   4. Verdict, on the window's planes after the fuse.  For a known cell c, N = the known cells of its (2*radius + 1)^2
+ *      neighbourhood clipped to the window, c included:
+ *        rise(c) = max over n in N of max(hi_n - lo_c, hi_c - lo_n)      (>= hi_c - lo_c >= 0, <= 65534)
+ *        trav(c) = 100 where rise(c) > max_step_mm, else 0;   unknown cells: trav = -1, rise = 0.
+ *      Slopes.  A plane of slope s reads about (2*radius + 1) * cell_m * tan(s) between the far cells of the neighbourhood
+ *      (2*radius cells between their centres, plus a cell's own spread between its hi and its lo), so max_step_mm also sets
+ *      the steepest drivable ramp: tan(s_max) ~ max_step_mm / (1000 * (2*radius + 1) * cell_m).  With cell_m = 0.1, radius 1
+ *      and max_step_mm = 60 that is 11 degrees, and a 6 cm kerb inside one neighbourhood is lethal.  A separate slope or
+ *      roughness term is not covered.
+ * Outputs, unrolled in nav_msgs/OccupancyGrid order: element [cy - oy][cx - ox] of map k.  Each is nullable; one is required.
+ *   trav  int8   [n][mh][mw]
+ *   hi    int16  [n][mh][mw],  lo likewise (-32768 = unknown)
+ *   rise  uint16 [n][mh][mw]   (saturated to 65535)
+ *   stats uint32 [n][4] = {known cells, lethal cells (trav == 100), cells fused this frame (cnt >= min_points), points used
+ *                          (the sum of cnt over the window)}
+ *   pose_q_out (nullable, HOST, [n][6]) receives the q of every map.
+ * sn_elevation_create: `streams` independent maps (1 <= streams <= max_batch) on handle h, all fresh; the state
+ *   (4 * mh * mw * streams bytes), a stream, an event, the scratch and the host-mode staging are the object's own.
+ *   h == NULL makes a host-only object (any streams >= 1) that serves sn_elevation_pose_q alone and touches no device;
+ *   sn_elevation_push on it is SN_ERR_ARG.
+ *   SN_ERR_ARG: a NULL pointer, streams out of range, mw or mh outside 1..4096, a float that is not finite, cell_m <= 0,
+ *   z_min_m or z_max_m outside [-32, 32] or z_min_m > z_max_m, range_max_m <= 0, min_points < 1, alpha outside 1..256,
+ *   max_step_mm outside 1..32767, radius outside 1..3, flags != 0.  While an elevation object is alive sn_destroy(h) is REFUSED
+ *   with SN_ERR_BUSY, as for sn_costmap.
+ * sn_elevation_reset: stream `stream` (-1: all) is fresh again.  A host-side flag that takes effect at the next push.
+ *   SN_ERR_ARG: an id outside -1..streams-1.
+ * sn_elevation_push: n maps (1 <= n <= max_batch); map k is the next frame of stream stream_of[k] (a host array; NULL: all of
+ *   stream 0, one clip) at pose poses[k] = {x, y, yaw} (metres, radians; always HOST memory).  Maps with the same id are
+ *   consecutive frames in the order of k, and a push of n maps equals n single pushes in that order, bit for bit.
+ *   SN_ERR_ARG (sn_last_error(h) names the call; nothing is launched or written and no state changes): n out of range, raw,
+ *     cam or poses NULL, a camera sn_pointcloud_from_raw refuses, a pose sn_elevation_pose_q refuses, no output, an id outside
+ *     0..streams-1, raw, stats or mounts misaligned (4 bytes), hi, lo or rise misaligned (2 bytes), mounts with
+ *     mount_stride < 12, overlapping buffers (an input with an output, or two outputs), a bad mem.
+ *   Scratch, the object's own and grow-only: 12 bytes per cell and frame for the accumulators, and 2 more for each of hi and lo
+ *     that the caller does not take (the verdict reads them).  SN_ERR_NOMEM where it cannot be had; nothing is written then.
+ *   mem / stream as sn_costmap_push: a NULL stream is the object's own stream (never the inference stream); the call returns
+ *   after completion when mem is SN_MEM_HOST or stream is NULL; device buffers + a caller stream only enqueue, so
+ *   ground -> elevation -> inflate run on one stream without a host round trip (mounts = &ground[0].base_from_cam[0],
+ *   mount_stride = sizeof(sn_ground) / 4).  May run beside sn_submit / sn_wait and the other stages; calls are serialised by
+ *   the object's mutex.  Four kernel launches per call of up to 64 maps: clear, scatter, fuse, verdict (two more per further
+ *   64 maps).
+ * Not covered: the asynchronous sn_submit* slots, a slope or roughness term, several layers (bridges, tables), cells hidden
+ * below an edge (they stay unknown), variance-weighted fusion, poses with roll or pitch. */
+typedef struct sn_elevation_params {
+  int   mw, mh;                      /* window in cells, 1..4096 each */
+  float cell_m;                      /* > 0 */
+  float base_from_cam[12];           /* the mount, as sn_obstacle_params' (all twelve zero: the level forward mount) */
+  float z_min_m, z_max_m;            /* -32 <= z_min_m <= z_max_m <= 32; z_max_m is the robot's clearance: overhangs are ignored */
+  float range_max_m;                 /* > 0: stereo depth error grows with Z^2 */
+  int   min_points;                  /* >= 1: points a cell needs in a frame to be fused */
+  int   alpha;                       /* 1..256: the weight of the new frame in 1/256 */
+  int   max_step_mm;                 /* 1..32767 */
+  int   radius;                      /* 1..3: the neighbourhood of the verdict, in cells */
+  int   flags;                       /* none defined yet: must be 0 */
+} sn_elevation_params;
+typedef struct sn_elevation sn_elevation;
+int  sn_elevation_create(sn_handle *h, int streams, const sn_elevation_params *p, sn_elevation **out);
+int  sn_elevation_reset(sn_elevation *e, int stream);
+void sn_elevation_destroy(sn_elevation *e);
+int  sn_elevation_pose_q(const sn_elevation *e, const double pose[3] /* x, y, yaw */, int32_t q[6]);   /* pure host */
+int  sn_elevation_push(sn_elevation *e, int n, const int *stream_of, const double *poses /* host [n][3] */,
+                       const int32_t *raw /* [n][H][W] */, const sn_camera *cam, const float *mounts, int mount_stride,
+                       int8_t *trav, int16_t *hi, int16_t *lo, uint16_t *rise /* each [n][mh][mw] */, uint32_t *stats /* [n][4] */,
+                       int32_t *pose_q_out /* host [n][6], nullable */, int mem, void *stream);
+
 /* ---- inflation of occupancy grids by the robot's radius (csrc/sn_inflate.hpp; hobot_stereonet_amd/inflate.py is the numpy
  * twin, byte for byte) -----------------------------------------------------------------------------------------------------------
  * A planner treats the robot as a point, so every cell is first charged for how close it lies to an obstacle: lethal at the
