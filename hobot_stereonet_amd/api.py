@@ -510,46 +510,47 @@ def ground_gate(cam, params, w: int, h: int) -> np.ndarray:
     return gate
 
 
+def _pose_q_rows(fn, obj, poses):
+    """poses (x, y, yaw) or (n, 3) through the sn_*_pose_q `fn` of `obj` -> (q int32 (6,) or (n, 6), 0, n), or (None, rc, k)
+    at the first pose k that the library refuses"""
+    ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+    q = np.empty((ps.shape[0], 6), np.int32)
+    for k in range(ps.shape[0]):
+        rc = fn(obj, ps[k].ctypes.data, q[k].ctypes.data)
+        if rc:
+            return None, rc, k
+    return (q[0] if np.ndim(poses) == 1 else q), 0, ps.shape[0]
+
+
+def _host_pose_q(sym: str, create_args, poses) -> np.ndarray:
+    """sn_costmap_pose_q / sn_elevation_pose_q on an object made without an engine (`sym`_create(NULL, 1, ...))"""
+    lib, o = load_library(), C.c_void_p()
+    rc = getattr(lib, sym + "_create")(None, 1, *create_args, C.byref(o))
+    if rc:
+        raise StereoNetError(rc, sym + "_create")
+    try:
+        q, rc, k = _pose_q_rows(getattr(lib, sym + "_pose_q"), o, poses)
+    finally:
+        getattr(lib, sym + "_destroy")(o)
+    if rc:
+        raise StereoNetError(rc, sym + "_pose_q", f"pose {k}: {np.asarray(poses, np.float64).reshape(-1, 3)[k].tolist()}")
+    return q
+
+
 def costmap_pose_q(params, obstacle, poses) -> np.ndarray:
     """sn_costmap_pose_q (host only: a costmap without an engine serves it): poses (x, y, yaw) or (n, 3) -> int32 (6,) or
     (n, 6) = {tx, ty, cq, sq, ox, oy}; costmap.pose_q is the Python twin (the two may differ by one unit in cq and sq: two
     implementations of a double cos and sin)."""
-    lib, c = load_library(), C.c_void_p()
     prm, op = costmap_params(params), obstacle_params(obstacle)
-    rc = lib.sn_costmap_create(None, 1, C.byref(op), C.byref(prm), C.byref(c))
-    if rc:
-        raise StereoNetError(rc, "sn_costmap_create")
-    try:
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
-        q = np.empty((ps.shape[0], 6), np.int32)
-        for k in range(ps.shape[0]):
-            rc = lib.sn_costmap_pose_q(c, ps[k].ctypes.data, q[k].ctypes.data)
-            if rc:
-                raise StereoNetError(rc, "sn_costmap_pose_q", f"pose {k}: {ps[k].tolist()}")
-    finally:
-        lib.sn_costmap_destroy(c)
-    return q[0] if np.ndim(poses) == 1 else q
+    return _host_pose_q("sn_costmap", (C.byref(op), C.byref(prm)), poses)
 
 
 def elevation_pose_q(params, poses) -> np.ndarray:
     """sn_elevation_pose_q (host only: an elevation object without an engine serves it): poses (x, y, yaw) or (n, 3) -> int32
     (6,) or (n, 6) = {tx, ty, cq, sq, ox, oy}; elevation.pose_q is the Python twin (the two may differ by one unit in cq and sq:
     two implementations of a double cos and sin)."""
-    lib, e = load_library(), C.c_void_p()
     prm = elevation_params(params)
-    rc = lib.sn_elevation_create(None, 1, C.byref(prm), C.byref(e))
-    if rc:
-        raise StereoNetError(rc, "sn_elevation_create")
-    try:
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
-        q = np.empty((ps.shape[0], 6), np.int32)
-        for k in range(ps.shape[0]):
-            rc = lib.sn_elevation_pose_q(e, ps[k].ctypes.data, q[k].ctypes.data)
-            if rc:
-                raise StereoNetError(rc, "sn_elevation_pose_q", f"pose {k}: {ps[k].tolist()}")
-    finally:
-        lib.sn_elevation_destroy(e)
-    return q[0] if np.ndim(poses) == 1 else q
+    return _host_pose_q("sn_elevation", (C.byref(prm),), poses)
 
 
 def inflate_table(params) -> np.ndarray:
@@ -1766,10 +1767,44 @@ class _Owned:
         self.close()
 
 
-class TemporalFilter(_Owned):
+class _Streams(_Owned):
+    """An object with per-stream state on the GPU: `_sym` is the prefix of its functions in the library, `_what` its name in
+    this module's own messages."""
+    _sym = _what = ""
+
+    def reset(self, stream: int = -1):
+        """Stream `stream` (-1: all) starts afresh at its next push."""
+        self._eng._check(getattr(self._lib, self._sym + "_reset")(getattr(self, self._handle), int(stream)), self._sym + "_reset")
+
+    def _ids(self, stream_of, n: int):
+        if stream_of is None:
+            return None
+        ids = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        if ids.size != n:
+            raise StereoNetError(-1, f"{self._what} push", f"{ids.size} stream ids for {n} maps")
+        return ids
+
+
+class _TorusStreams(_Streams):
+    """... and the two rolling maps, whose frames come with a pose"""
+
+    def pose_q(self, poses) -> np.ndarray:
+        """sn_costmap_pose_q / sn_elevation_pose_q: (x, y, yaw) or (n, 3) -> int32 (6,) or (n, 6)"""
+        q, rc, _ = _pose_q_rows(getattr(self._lib, self._sym + "_pose_q"), getattr(self, self._handle), poses)
+        self._eng._check(rc, self._sym + "_pose_q")
+        return q
+
+    def _poses(self, poses, stream_of, n: int):
+        ps = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        if ps.size != 3 * n:
+            raise StereoNetError(-1, f"{self._what} push", f"{ps.size} pose numbers for {n} maps: (n, 3) is needed")
+        return ps, self._ids(stream_of, n)
+
+
+class TemporalFilter(_Streams):
     """sn_temporal: the temporal filter of disparity streams, with its per-stream state on the GPU (temporal.reference is the
     numpy twin).  A context object: the engine refuses to close while one of its filters is open."""
-    _destroy, _handle = "sn_temporal_destroy", "_t"
+    _destroy, _handle, _sym, _what = "sn_temporal_destroy", "_t", "sn_temporal", "temporal"
 
     def __init__(self, engine: StereoNetHIP, streams: int = 1, alpha: int = 64, delta_px: float = 0.5, persist: int = 2,
                  luma_delta: int = 0):
@@ -1777,18 +1812,6 @@ class TemporalFilter(_Owned):
         self.streams, self.params = int(streams), SnTemporalParams(int(alpha), delta_px, int(persist), int(luma_delta))
         engine._check(self._lib.sn_temporal_create(engine._h, self.streams, C.byref(self.params), C.byref(self._t)),
                       "sn_temporal_create")
-
-    def reset(self, stream: int = -1):
-        """Stream `stream` (-1: all) starts afresh at its next push."""
-        self._eng._check(self._lib.sn_temporal_reset(self._t, int(stream)), "sn_temporal_reset")
-
-    def _ids(self, stream_of, n: int):
-        if stream_of is None:
-            return None
-        ids = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
-        if ids.size != n:
-            raise StereoNetError(-1, "temporal push", f"{ids.size} stream ids for {n} maps")
-        return ids
 
     def push(self, raw: np.ndarray, guide: Optional[np.ndarray] = None, guide_kind: int = SN_GUIDE_NV12, guide_pitch: int = 0,
              stream_of=None, disp: Optional[np.ndarray] = None):
@@ -1818,37 +1841,16 @@ class TemporalFilter(_Owned):
                                                     counts_ptr or None, SN_MEM_DEVICE, stream or None), "sn_temporal_push")
 
 
-class Costmap(_Owned):
+class Costmap(_TorusStreams):
     """sn_costmap: a rolling log-odds costmap with ray clearing per stream, its state on the GPU (costmap.Reference is the numpy
     twin).  A context object: the engine refuses to close while one of its costmaps is open."""
-    _destroy, _handle = "sn_costmap_destroy", "_c"
+    _destroy, _handle, _sym, _what = "sn_costmap_destroy", "_c", "sn_costmap", "costmap"
 
     def __init__(self, engine: StereoNetHIP, obstacle, params, streams: int = 1):
         self._eng, self._lib, self._c = engine, engine._lib, C.c_void_p()
         self.streams, self.params, self.obstacle = int(streams), costmap_params(params), obstacle_params(obstacle)
         engine._check(self._lib.sn_costmap_create(engine._h, self.streams, C.byref(self.obstacle), C.byref(self.params), C.byref(self._c)),
                       "sn_costmap_create")
-
-    def reset(self, stream: int = -1):
-        """Stream `stream` (-1: all) starts afresh at its next push."""
-        self._eng._check(self._lib.sn_costmap_reset(self._c, int(stream)), "sn_costmap_reset")
-
-    def pose_q(self, poses) -> np.ndarray:
-        """sn_costmap_pose_q: (x, y, yaw) or (n, 3) -> int32 (6,) or (n, 6)"""
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
-        q = np.empty((ps.shape[0], 6), np.int32)
-        for k in range(ps.shape[0]):
-            self._eng._check(self._lib.sn_costmap_pose_q(self._c, ps[k].ctypes.data, q[k].ctypes.data), "sn_costmap_pose_q")
-        return q[0] if np.ndim(poses) == 1 else q
-
-    def _poses(self, poses, stream_of, n: int):
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1)
-        if ps.size != 3 * n:
-            raise StereoNetError(-1, "costmap push", f"{ps.size} pose numbers for {n} maps: (n, 3) is needed")
-        ids = None if stream_of is None else np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
-        if ids is not None and ids.size != n:
-            raise StereoNetError(-1, "costmap push", f"{ids.size} stream ids for {n} maps")
-        return ps, ids
 
     def push(self, poses, occ: Optional[np.ndarray] = None, ranges: Optional[np.ndarray] = None, stream_of=None,
              want=(True, True, True)):
@@ -1883,10 +1885,10 @@ class Costmap(_Owned):
         return q
 
 
-class Elevation(_Owned):
+class Elevation(_TorusStreams):
     """sn_elevation: a rolling elevation map with a step-height traversability verdict per stream, its state on the GPU
     (elevation.Reference is the numpy twin).  A context object: the engine refuses to close while one of its maps is open."""
-    _destroy, _handle = "sn_elevation_destroy", "_e"
+    _destroy, _handle, _sym, _what = "sn_elevation_destroy", "_e", "sn_elevation", "elevation"
     OUTPUTS = ("trav", "hi", "lo", "rise", "stats")
 
     def __init__(self, engine: StereoNetHIP, params, streams: int = 1):
@@ -1894,27 +1896,6 @@ class Elevation(_Owned):
         self.streams, self.params = int(streams), elevation_params(params)
         engine._check(self._lib.sn_elevation_create(engine._h, self.streams, C.byref(self.params), C.byref(self._e)),
                       "sn_elevation_create")
-
-    def reset(self, stream: int = -1):
-        """Stream `stream` (-1: all) starts afresh at its next push."""
-        self._eng._check(self._lib.sn_elevation_reset(self._e, int(stream)), "sn_elevation_reset")
-
-    def pose_q(self, poses) -> np.ndarray:
-        """sn_elevation_pose_q: (x, y, yaw) or (n, 3) -> int32 (6,) or (n, 6)"""
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
-        q = np.empty((ps.shape[0], 6), np.int32)
-        for k in range(ps.shape[0]):
-            self._eng._check(self._lib.sn_elevation_pose_q(self._e, ps[k].ctypes.data, q[k].ctypes.data), "sn_elevation_pose_q")
-        return q[0] if np.ndim(poses) == 1 else q
-
-    def _poses(self, poses, stream_of, n: int):
-        ps = np.ascontiguousarray(poses, np.float64).reshape(-1)
-        if ps.size != 3 * n:
-            raise StereoNetError(-1, "elevation push", f"{ps.size} pose numbers for {n} maps: (n, 3) is needed")
-        ids = None if stream_of is None else np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
-        if ids is not None and ids.size != n:
-            raise StereoNetError(-1, "elevation push", f"{ids.size} stream ids for {n} maps")
-        return ps, ids
 
     def push(self, poses, raw: np.ndarray, cam, mounts: Optional[np.ndarray] = None, stream_of=None,
              want=(True, True, True, True, True)):

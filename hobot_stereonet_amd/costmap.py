@@ -15,12 +15,11 @@ from typing import Optional
 
 import numpy as np
 
-from . import obstacles
+from . import obstacles, torus
 from .obstacles import ObstacleParams
 
 MAX_WINDOW = 4096                   # mw, mh
 UNKNOWN_L = -32768                  # the state of a cell nobody has observed
-Q30 = 1 << 30
 _FAR, _CAP = 1 << 40, 1 << 31       # where gx0 / gy0 and margin / rmin / cmax saturate
 
 
@@ -93,13 +92,7 @@ def units(p: CostmapParams, op: ObstacleParams) -> Units:
 def pose_q(p: CostmapParams, op: ObstacleParams, pose) -> np.ndarray:
     """sn_costmap_pose_q: (x, y, yaw) -> int32 (6,) = {tx, ty, cq, sq, ox, oy}.  ValueError for a pose that is not finite or too
     far.  The library's may differ by one unit in cq, sq: two implementations of a double cos and sin."""
-    x, y, yaw = (float(v) for v in pose)
-    k256 = units(p, op).k256
-    if not all(math.isfinite(v) for v in (x, y, yaw)) or abs(x * k256) > Q30 or abs(y * k256) > Q30:
-        raise ValueError("the pose must be finite and within 2^30 subs of the origin")
-    tx, ty = int(np.rint(x * k256)), int(np.rint(y * k256))
-    return np.array([tx, ty, int(np.rint(math.cos(yaw) * Q30)), int(np.rint(math.sin(yaw) * Q30)), (tx >> 8) - p.mw // 2,
-                     (ty >> 8) - p.mh // 2], np.int32)
+    return torus.pose_q(units(p, op).k256, p.mw, p.mh, pose)
 
 
 def return_subs(ranges: np.ndarray, k256: float) -> np.ndarray:
@@ -158,12 +151,9 @@ class Reference:
                   prev=self.origin[s], origin=(int(q[4]), int(q[5])))
         self.frames.append(br)
         tx, ty, cq, sq, ox, oy = (int(v) for v in q)
-        i, j = np.arange(p.mw, dtype=np.int64), np.arange(p.mh, dtype=np.int64)
-        cx, cy = ox + (i - ox) % p.mw, oy + (j - oy) % p.mh
+        cx, cy, moved, rows, cols = torus.view(p.mw, p.mh, (ox, oy), self.origin[s])
         L = self.L[s].astype(np.int64)
-        if self.origin[s] is not None:
-            pox, poy = self.origin[s]
-            moved = (cy != poy + (j - poy) % p.mh)[:, None] | (cx != pox + (i - pox) % p.mw)[None, :]
+        if moved is not None:
             br["scrolled"] = int((moved & (L != UNKNOWN_L)).sum())
             L[moved] = UNKNOWN_L
         dx, dy = (cx * 256 + 128 - tx)[None, :], (cy * 256 + 128 - ty)[:, None]
@@ -202,8 +192,6 @@ class Reference:
         span = p.l_max - p.l_min
         known = new != UNKNOWN_L
         g = np.where(known, ((new - p.l_min) * 100 + span // 2) // span, -1)
-        # unrolled: element [cy - oy][cx - ox]
-        rows, cols = (cy - oy)[:, None], (cx - ox)[None, :]
         grid, logodds = np.empty(L.shape, np.int8), np.empty(L.shape, np.int16)
         grid[rows, cols] = g
         logodds[rows, cols] = new

@@ -18,18 +18,16 @@
 //                 store consecutive elements except at the wrap column.
 //                 Traffic per cell: 2 + 2 bytes of state per launch; per frame grid 1 + logodds 2 where wanted, and at most one
 //                 byte of occ (L2-resident: the observation grid is read by many cells' neighbours).
-//                 stats: the four counters of a lane and frame are packed into two words of 16-bit fields, summed over the
-//                 wave by shuffles and added to an LDS table [frame][4] by one lane per wave; after the last frame one global
-//                 atomicAdd per workgroup, frame and non-zero counter (integer, order-free).
+//                 stats: sn_streams.hpp's stats_*.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sn_obstacles.hpp"      // kObMaxBeams, kObMaxCells
+#include "sn_streams.hpp"
 
 namespace sn {
 
-constexpr int kCmSlice = 64;            // maps per launch: the per-stream frame lists and the poses travel in the kernel arguments
 constexpr int kCmMaxWindow = 4096;      // mw, mh
 constexpr int kCmUnknown = -32768;
 
@@ -45,18 +43,10 @@ struct CmArgs {
   long long gx0, gy0, margin, rmin, cmax;
   int mw, mh, gw, gh, beams;
   int l_hit, l_miss, l_min, l_max;
-  int first[kCmSlice + 1];     // group g = entries first[g] .. first[g + 1] - 1 of map[]
-  int stream[kCmSlice];        // per group: which state it updates
-  int fresh[kCmSlice];         // per group: all unknown, no previous origin
-  int pox[kCmSlice], poy[kCmSlice];      // per group: the previous origin (unless fresh)
-  int map[kCmSlice];           // map indices of the launch, grouped by stream, each group in time order
-  int q[kCmSlice][6];          // per map of the launch: tx, ty, cq, sq, ox, oy
+  StreamGroups g;          // the launch's maps, sorted by stream; fresh: all unknown, no previous origin
+  TorusPrev t;
+  int q[kSlice][6];        // per map of the launch: tx, ty, cq, sq, ox, oy
 };
-
-__host__ __device__ __forceinline__ int cm_mod(int a, int m) {      // floor modulo, m > 0
-  const int r = a % m;
-  return r < 0 ? r + m : r;
-}
 
 // Rb of the contract: the return of a beam in subs, -1 without one
 __device__ __forceinline__ int cm_return_subs(float r, double k256) {
@@ -81,17 +71,11 @@ struct CmView {
   int o;
 };
 
-// (i - o) mod m for 0 <= i < m, with om = o mod m: no division per lane
-__device__ __forceinline__ int cm_unroll(int i, int om, int m) {
-  const int u = i - om;
-  return u < 0 ? u + m : u;
-}
-
 __device__ __forceinline__ CmView cm_view(const CmArgs& a, int k, int i, int j) {
   const int* q = a.q[k];
   const int tx = q[0], ty = q[1], cq = q[2], sq = q[3], ox = q[4], oy = q[5];
   CmView v;
-  v.ui = cm_unroll(i, cm_mod(ox, a.mw), a.mw), v.uj = cm_unroll(j, cm_mod(oy, a.mh), a.mh);      // the mod of the origin is the wave's, not the lane's
+  v.ui = torus_unroll(i, torus_mod(ox, a.mw), a.mw), v.uj = torus_unroll(j, torus_mod(oy, a.mh), a.mh);      // the mod of the origin is the wave's, not the lane's
   v.cx = ox + v.ui, v.cy = oy + v.uj;
   // |cx| <= 2^22 + 2^12 and |tx| <= 2^30, so cx*256 + 128 fits in 32 bits and every product below is 32 x 32 -> 64
   const int dx = v.cx * 256 + 128 - tx, dy = v.cy * 256 + 128 - ty;
@@ -108,42 +92,42 @@ __device__ __forceinline__ CmView cm_view(const CmArgs& a, int k, int i, int j) 
 // grid (ceil(mh*mw / 256), groups); dynamic LDS: (beams + 1) floats, then two tables of beams int32 (this frame's Rb and the next's)
 __global__ __launch_bounds__(256) void k_costmap(CmArgs a) {
   extern __shared__ __align__(16) uint32_t cm_lds[];
-  __shared__ uint32_t cnt[kCmSlice][4];
+  __shared__ uint32_t cnt[kSlice][4];
   float* E = reinterpret_cast<float*>(cm_lds);
   int* Rb2 = reinterpret_cast<int*>(cm_lds + a.beams + 1);
   const bool rays = a.ranges != nullptr;
-  const int g = blockIdx.y, f0 = a.first[g], f1 = a.first[g + 1];
+  const int g = blockIdx.y, f0 = a.g.first[g], f1 = a.g.first[g + 1];
   const int cells = a.mw * a.mh;      // <= 2^24
   const int p = blockIdx.x * 256 + threadIdx.x;
   const bool live = p < cells;
   const int j = live ? p / a.mw : 0, i = live ? p - j * a.mw : 0;
-  if (a.stats && (int)threadIdx.x < (f1 - f0) * 4) cnt[threadIdx.x >> 2][threadIdx.x & 3] = 0;
+  if (a.stats) stats_clear(cnt, f1 - f0);
   if (rays) {
     for (int b = threadIdx.x; b <= a.beams; b += 256) E[b] = a.edges[b];
-    for (int b = threadIdx.x; b < a.beams; b += 256) Rb2[b] = cm_return_subs(a.ranges[(size_t)a.map[f0] * a.beams + b], a.k256);
+    for (int b = threadIdx.x; b < a.beams; b += 256) Rb2[b] = cm_return_subs(a.ranges[(size_t)a.g.map[f0] * a.beams + b], a.k256);
   }
   __syncthreads();
-  const size_t sp = (size_t)a.stream[g] * cells + p;
-  bool seen = !a.fresh[g];
-  int pox = a.pox[g], poy = a.poy[g];
+  const size_t sp = (size_t)a.g.stream[g] * cells + p;
+  bool seen = !a.g.fresh[g];
+  int pox = a.t.pox[g], poy = a.t.poy[g];
   int L = kCmUnknown;
   if (live && seen) L = a.L[sp];
   const uint32_t span = (uint32_t)(a.l_max - a.l_min);      // <= 65534, and (L - l_min) * 100 < 2^23
-  CmView next = cm_view(a, a.map[f0], i, j);
+  CmView next = cm_view(a, a.g.map[f0], i, j);
 #pragma unroll 1
   for (int f = f0; f < f1; ++f) {
-    const int k = a.map[f], ox = a.q[k][4], oy = a.q[k][5];
+    const int k = a.g.map[f], ox = a.q[k][4], oy = a.q[k][5];
     const CmView v = next;
     const int* Rb = Rb2 + ((f - f0) & 1) * a.beams;
     // the next frame's inputs are asked for before this frame's are used: its first 256 returns and its grid word
     const bool more = f + 1 < f1;
-    const int kn = more ? a.map[f + 1] : k;
+    const int kn = more ? a.g.map[f + 1] : k;
     const float* rn = rays ? a.ranges + (size_t)kn * a.beams : nullptr;
     const float r_first = more && rays && (int)threadIdx.x < a.beams ? rn[threadIdx.x] : 0.f;
     if (more) next = cm_view(a, kn, i, j);
     uint32_t n_known = 0, n_pos = 0, n_hit = 0, n_clear = 0;
     if (live) {
-      if (seen && (v.cx != pox + cm_unroll(i, cm_mod(pox, a.mw), a.mw) || v.cy != poy + cm_unroll(j, cm_mod(poy, a.mh), a.mh))) L = kCmUnknown;
+      torus_if_rolled(seen, i, j, v.cx, v.cy, pox, poy, a.mw, a.mh, [&] { L = kCmUnknown; });
       bool ray = false;
       if (rays && v.o != 100 && v.o != 0 && v.bx > 0 && cm_edge_le(E[0], v.bx, v.by) && !cm_edge_le(E[a.beams], v.bx, v.by)) {
         int lo = 0, hi = a.beams;      // E[lo]*bx <= by, not E[hi]*bx <= by
@@ -169,21 +153,7 @@ __global__ __launch_bounds__(256) void k_costmap(CmArgs a) {
       if (a.logodds) a.logodds[op] = (int16_t)L;
     }
     seen = true, pox = ox, poy = oy;
-    if (a.stats) {      // wave-uniform
-      uint32_t lo = n_known | (n_pos << 16), hi = n_hit | (n_clear << 16);      // a wave's sums are at most 64
-#pragma unroll
-      for (int s = 32; s > 0; s >>= 1) {
-        lo += __shfl_xor(lo, s);
-        hi += __shfl_xor(hi, s);
-      }
-      if ((threadIdx.x & 63) == 0) {
-        uint32_t* c = cnt[f - f0];
-        if (lo & 0xffffu) atomicAdd(c + 0, lo & 0xffffu);
-        if (lo >> 16) atomicAdd(c + 1, lo >> 16);
-        if (hi & 0xffffu) atomicAdd(c + 2, hi & 0xffffu);
-        if (hi >> 16) atomicAdd(c + 3, hi >> 16);
-      }
-    }
+    if (a.stats) stats_frame(cnt[f - f0], n_known | (n_pos << 16), n_hit | (n_clear << 16));      // wave-uniform; a wave's sums are at most 64
     if (more && rays) {      // the other table: nobody reads it in this frame, and the barrier hands it to the next
       int* Rn = Rb2 + ((f + 1 - f0) & 1) * a.beams;
       if ((int)threadIdx.x < a.beams) Rn[threadIdx.x] = cm_return_subs(r_first, a.k256);
@@ -192,13 +162,7 @@ __global__ __launch_bounds__(256) void k_costmap(CmArgs a) {
     }
   }
   if (live && f1 > f0) a.L[sp] = (int16_t)L;
-  if (a.stats) {
-    __syncthreads();
-    if ((int)threadIdx.x < (f1 - f0) * 4) {
-      const uint32_t v = cnt[threadIdx.x >> 2][threadIdx.x & 3];
-      if (v) atomicAdd(a.stats + (size_t)a.map[f0 + (threadIdx.x >> 2)] * 4 + (threadIdx.x & 3), v);
-    }
-  }
+  if (a.stats) stats_flush(cnt, a.stats, a.g.map, f0, f1);
 }
 
 }  // namespace sn

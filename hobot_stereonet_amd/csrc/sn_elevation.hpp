@@ -25,12 +25,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sn_costmap.hpp"        // cm_mod, cm_unroll: the torus is the costmap's
 #include "sn_obstacles.hpp"      // ob_row, ob_height_mm, ob_range, kObAhead
+#include "sn_streams.hpp"        // the group lists and the torus
 
 namespace sn {
 
-constexpr int kElSlice = 64;            // maps per scatter / fuse launch: the frame lists and the poses travel in the kernel arguments
 constexpr int kElMaxWindow = 4096;      // mw, mh
 constexpr int kElUnknown = -32768;
 constexpr int kElTileW = 64, kElTileH = 16, kElMaxRadius = 3;
@@ -55,7 +54,7 @@ struct ElScatterArgs {
   int zmin_mm, zmax_mm;
   int mw, mh;
   int chunks, rows;       // row chunks per column block, output rows per chunk
-  int q[kElSlice][6];     // per map of the slice: tx, ty, cq, sq, ox, oy
+  int q[kSlice][6];     // per map of the slice: tx, ty, cq, sq, ox, oy
 };
 
 struct ElFuseArgs {
@@ -68,12 +67,9 @@ struct ElFuseArgs {
   int16_t* S;             // state: hi [streams][mh][mw], then lo at lo_off
   size_t lo_off;
   int mw, mh, min_points, alpha;
-  int first[kElSlice + 1];     // group g = entries first[g] .. first[g + 1] - 1 of map[]
-  int stream[kElSlice];        // per group: which state it updates
-  int fresh[kElSlice];         // per group: all unknown, no previous origin
-  int pox[kElSlice], poy[kElSlice];      // per group: the previous origin (unless fresh)
-  int map[kElSlice];           // map indices of the slice, grouped by stream, each group in time order
-  int org[kElSlice][2];        // per map of the slice: ox, oy
+  StreamGroups g;         // the slice's maps, sorted by stream; fresh: all unknown, no previous origin
+  TorusPrev t;
+  int org[kSlice][2];     // per map of the slice: ox, oy
 };
 
 struct ElVerdictArgs {
@@ -194,27 +190,26 @@ __device__ __forceinline__ int el_clamp(int v) { return min(max(v, -32767), 3276
 
 // grid (ceil(mh*mw / 256), groups)
 __global__ __launch_bounds__(256) void k_el_fuse(ElFuseArgs a) {
-  __shared__ uint32_t tab[kElSlice][3];
-  const int g = blockIdx.y, f0 = a.first[g], f1 = a.first[g + 1];
+  __shared__ uint32_t tab[kSlice][3];
+  const int g = blockIdx.y, f0 = a.g.first[g], f1 = a.g.first[g + 1];
   const int cells = a.mw * a.mh;      // <= 2^24
   const int p = blockIdx.x * 256 + threadIdx.x;
   const bool live = p < cells;
   const int j = live ? p / a.mw : 0, i = live ? p - j * a.mw : 0;
   if (a.stats && (int)threadIdx.x < (f1 - f0) * 3) tab[threadIdx.x / 3][threadIdx.x % 3] = 0;
   __syncthreads();
-  const size_t sp = (size_t)a.stream[g] * cells + p;
-  bool seen = !a.fresh[g];
-  int pox = a.pox[g], poy = a.poy[g];
+  const size_t sp = (size_t)a.g.stream[g] * cells + p;
+  bool seen = !a.g.fresh[g];
+  int pox = a.t.pox[g], poy = a.t.poy[g];
   int hi = kElUnknown, lo = kElUnknown;
   if (live && seen) hi = a.S[sp], lo = a.S[a.lo_off + sp];
 #pragma unroll 1
   for (int f = f0; f < f1; ++f) {
-    const int k = a.map[f], ox = a.org[k][0], oy = a.org[k][1];
+    const int k = a.g.map[f], ox = a.org[k][0], oy = a.org[k][1];
     uint32_t n_known = 0, n_fused = 0, n_pts = 0;
     if (live) {
-      const int ui = cm_unroll(i, cm_mod(ox, a.mw), a.mw), uj = cm_unroll(j, cm_mod(oy, a.mh), a.mh);
-      if (seen && (ox + ui != pox + cm_unroll(i, cm_mod(pox, a.mw), a.mw) || oy + uj != poy + cm_unroll(j, cm_mod(poy, a.mh), a.mh)))
-        hi = lo = kElUnknown;
+      const int ui = torus_unroll(i, torus_mod(ox, a.mw), a.mw), uj = torus_unroll(j, torus_mod(oy, a.mh), a.mh);
+      torus_if_rolled(seen, i, j, ox + ui, oy + uj, pox, poy, a.mw, a.mh, [&] { hi = lo = kElUnknown; });
       const size_t u = (size_t)k * cells + (size_t)uj * a.mw + ui;
       n_pts = a.cnt[u];
       if (n_pts >= (uint32_t)a.min_points) {
@@ -253,7 +248,7 @@ __global__ __launch_bounds__(256) void k_el_fuse(ElFuseArgs a) {
     if ((int)threadIdx.x < (f1 - f0) * 3) {
       const int f = threadIdx.x / 3, w = threadIdx.x % 3;
       const uint32_t v = tab[f][w];
-      if (v) atomicAdd(a.stats + (size_t)a.map[f0 + f] * 4 + (w == 0 ? 0 : w + 1), v);      // {known, -, fused, points}
+      if (v) atomicAdd(a.stats + (size_t)a.g.map[f0 + f] * 4 + (w == 0 ? 0 : w + 1), v);      // {known, -, fused, points}
     }
   }
 }

@@ -368,55 +368,55 @@ struct sn_handle {
   std::atomic<int> elevation_live{0};  // ... and sn_elevation objects
 };
 
-// sn_temporal_*: the one post-processing stage with state: a lane per filter, plus the state planes and the per-stream
-// "fresh" flags.  host mode: map (filtered in place), guide, float map, mask, counts
+// What the objects with per-stream state on the GPU share (sn_temporal, sn_costmap, sn_elevation)
+struct StreamObj {
+  sn_handle* h = nullptr;            // nullptr (the two maps only): a host-only object that serves *_pose_q alone
+  int streams = 0;
+  std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
+  void open(int n) { streams = n, fresh.assign(n, 1); }
+};
+// ... and the two rolling maps (the window is p.mw x p.mh of the derived object): per stream the origin of its last frame
+struct TorusObj : StreamObj {
+  double k256 = 0.0;                 // subs a metre
+  std::vector<int> ox, oy;
+  void open(int n) { StreamObj::open(n), ox.assign(n, 0), oy.assign(n, 0); }
+};
+
+// sn_temporal_*: the one post-processing stage with state: a lane per filter, plus the state planes.  host mode: map (filtered
+// in place), guide, float map, mask, counts
 struct sn_temporal_slots {
   enum { kRaw = 0, kGuide, kDisp, kMask, kCounts, kCount };
 };
-struct sn_temporal : Lane<sn_temporal_slots> {
-  sn_handle* h = nullptr;
-  int streams = 0;
+struct sn_temporal : Lane<sn_temporal_slots>, StreamObj {
   sn_temporal_params p{};
   long long q = 0;                   // delta_px in units of raw
   void* state = nullptr;             // one allocation: P int32 [streams][H*W], then Hs and Yp uint8 [streams][H*W]
-  std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
 };
 
-// sn_costmap_*: the tail of the chain, with state as sn_temporal: a lane per object, plus the int16 maps, the beam table and
-// per stream the "fresh" flag and the last origin.  host mode: occ, ranges, grid, logodds, stats
+// sn_costmap_*: the tail of the chain, with state as sn_temporal: a lane per object, plus the int16 maps and the beam table.
+// host mode: occ, ranges, grid, logodds, stats
 struct sn_costmap_slots {
   enum { kOcc = 0, kRanges, kGrid, kLog, kStats, kCount };
 };
-struct sn_costmap : Lane<sn_costmap_slots> {
-  sn_handle* h = nullptr;            // nullptr: a host-only object that serves sn_costmap_pose_q alone
-  int streams = 0;
+struct sn_costmap : Lane<sn_costmap_slots>, TorusObj {
   sn_costmap_params p{};
   int gw = 0, gh = 0, beams = 0;
-  double k256 = 0.0;
   long long gx0 = 0, gy0 = 0, margin = 0, rmin = 0, cmax = 0;
   int16_t* state = nullptr;          // device [streams][mh][mw]
   float* edges = nullptr;            // device [beams + 1]
-  std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
-  std::vector<int> ox, oy;           // per stream: the origin of its last frame
 };
 
-// sn_elevation_*: the 2.5-D map beside the costmap, with state in the same way: a lane per object, plus the two int16 planes
-// and per stream the "fresh" flag and the last origin.  kAcc: the accumulators of a call's frames (cnt, fmax, fmin, one plane
-// each); kPlanes: the unrolled hi and lo where the caller takes neither (device mode).  host mode: the maps (and their pinned
-// staging), the mounts, trav, hi, lo, rise, stats
+// sn_elevation_*: the 2.5-D map beside the costmap, with state in the same way: a lane per object, plus the two int16 planes.
+// kAcc: the accumulators of a call's frames (cnt, fmax, fmin, one plane each); kPlanes: the unrolled hi and lo where the
+// caller takes neither (device mode).  host mode: the maps (and their pinned staging), the mounts, trav, hi, lo, rise, stats
 struct sn_elevation_slots {
   enum { kAcc = 0, kPlanes, kRaw, kPinRaw, kMounts, kTrav, kHi, kLo, kRise, kStats, kCount };
 };
-struct sn_elevation : Lane<sn_elevation_slots> {
+struct sn_elevation : Lane<sn_elevation_slots>, TorusObj {
   sn_elevation() { buf[kPinRaw].pinned = true; }
-  sn_handle* h = nullptr;            // nullptr: a host-only object that serves sn_elevation_pose_q alone
-  int streams = 0;
   sn_elevation_params p{};
-  double k256 = 0.0;
   int zmin_mm = 0, zmax_mm = 0;
   int16_t* state = nullptr;          // device: hi [streams][mh][mw], then lo [streams][mh][mw]
-  std::vector<uint8_t> fresh;        // per stream: no frame since create / reset (the kernel then reads no state)
-  std::vector<int> ox, oy;           // per stream: the origin of its last frame
 };
 
 // sn_rectify_*: the head of the chain: a lane per object, plus the two maps.  host mode: the eyes' source spans (one merged

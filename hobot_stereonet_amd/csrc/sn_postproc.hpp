@@ -469,6 +469,59 @@ int render_launch(sn_handle* h, hipStream_t st, int n, const RenderCall& c, cons
   return SN_OK;
 }
 
+
+// ---- the objects with per-stream state (sn_engine.hpp's StreamObj and TorusObj): what sn_temporal_*, sn_costmap_* and
+// sn_elevation_* share.  The grouping of a push, its commit and the pose rule are in csrc/sn_stream_groups.hpp ------------------
+bool streams_ok(const sn_handle* h, int streams) { return streams >= 1 && (!h || streams <= h->max_batch); }
+
+// The tail of a create: the per-stream flags, and on a handle the device check, the allocations (all or none) and the live count
+template <class T>
+int stream_open(T* o, sn_handle* h, int streams, const char* who, std::atomic<int> sn_handle::*live,
+                std::initializer_list<std::pair<void**, size_t>> dev) {
+  o->h = h;
+  o->open(streams);
+  if (!h) return SN_OK;
+  if (const int rc = check_device(h)) return rc;
+  for (const auto& d : dev)
+    if (hipMalloc(d.first, d.second) != hipSuccess) {
+      (void)hipGetLastError();
+      for (const auto& u : dev) (void)hipFree(*u.first), *u.first = nullptr;
+      set_err(h, std::string(who) + ": out of device memory");
+      return SN_ERR_NOMEM;
+    }
+  ++(h->*live);
+  return SN_OK;
+}
+
+template <class T>
+int stream_reset(T* o, int stream, const char* who) {
+  if (!o) return SN_ERR_ARG;
+  if (stream < -1 || stream >= o->streams) {
+    set_err(o->h, std::string(who) + ": bad arguments");
+    return SN_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(o->mu);
+  if (stream < 0) std::fill(o->fresh.begin(), o->fresh.end(), (uint8_t)1);
+  else o->fresh[stream] = 1;
+  return SN_OK;
+}
+
+// dev: the members that hold the object's device allocations
+template <class T, class... M>
+void stream_destroy(T* o, std::atomic<int> sn_handle::*live, M T::*... dev) {
+  if (!o) return;
+  if (o->h) {      // not a host-only object
+    (void)hipSetDevice(o->h->device);
+    o->destroy();
+    ((void)hipFree(o->*dev), ...);
+    --(o->h->*live);
+  }
+  delete o;
+}
+
+// the contract's q of one pose on a rolling map's window; false where sn_costmap_pose_q / sn_elevation_pose_q refuse it
+template <class T>
+bool torus_pose_q(const T* o, const double* pose, int32_t* q) { return sn::torus_pose_q(o->k256, o->p.mw, o->p.mh, pose, q); }
 }  // namespace
 
 extern "C" {
@@ -1030,50 +1083,25 @@ int sn_smooth_raw(sn_handle* h, int n, const int32_t* raw, const void* guide, in
 // ---- temporal filter of disparity streams (csrc/sn_temporal.hpp): an object with its own state and lane ------------------------
 int sn_temporal_create(sn_handle* h, int streams, const sn_temporal_params* p, sn_temporal** out) {
   if (!h) return SN_ERR_ARG;
-  if (!p || !out || streams < 1 || streams > h->max_batch || p->alpha < 1 || p->alpha > 256 || !std::isfinite(p->delta_px) ||
+  if (!p || !out || !streams_ok(h, streams) || p->alpha < 1 || p->alpha > 256 || !std::isfinite(p->delta_px) ||
       p->delta_px < 0.f || p->persist < 0 || p->persist > 8 || p->luma_delta < 0 || p->luma_delta > 255) {
     set_err(h, "sn_temporal_create: bad arguments");
     return SN_ERR_ARG;
   }
-  const int rc = check_device(h);
-  if (rc) return rc;
   std::unique_ptr<sn_temporal> t(new sn_temporal);
-  t->h = h;
-  t->streams = streams;
   t->p = *p;
   const float q = floorf(p->delta_px / (float)((double)kOutScale * kWireFactor));      // sn_filter_raw's dq
   t->q = q >= 4294967296.f ? 4294967296ll : (long long)q;
-  t->fresh.assign(streams, 1);
-  if (hipMalloc(&t->state, (size_t)streams * h->H * h->W * 6) != hipSuccess) {
-    (void)hipGetLastError();
-    set_err(h, "sn_temporal_create: out of device memory");
-    return SN_ERR_NOMEM;
-  }
-  ++h->temporal_live;
+  if (const int rc = stream_open(t.get(), h, streams, "sn_temporal_create", &sn_handle::temporal_live,
+                                 {{&t->state, (size_t)streams * h->H * h->W * 6}}))
+    return rc;
   *out = t.release();
   return SN_OK;
 }
 
-int sn_temporal_reset(sn_temporal* t, int stream) {
-  if (!t) return SN_ERR_ARG;
-  if (stream < -1 || stream >= t->streams) {
-    set_err(t->h, "sn_temporal_reset: bad arguments");
-    return SN_ERR_ARG;
-  }
-  std::lock_guard<std::mutex> lk(t->mu);
-  if (stream < 0) std::fill(t->fresh.begin(), t->fresh.end(), (uint8_t)1);
-  else t->fresh[stream] = 1;
-  return SN_OK;
-}
+int sn_temporal_reset(sn_temporal* t, int stream) { return stream_reset(t, stream, "sn_temporal_reset"); }
 
-void sn_temporal_destroy(sn_temporal* t) {
-  if (!t) return;
-  (void)hipSetDevice(t->h->device);
-  t->destroy();
-  (void)hipFree(t->state);
-  --t->h->temporal_live;
-  delete t;
-}
+void sn_temporal_destroy(sn_temporal* t) { stream_destroy(t, &sn_handle::temporal_live, &sn_temporal::state); }
 
 int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t* raw, const void* guide, int guide_kind,
                      int guide_pitch, int32_t* out_raw, float* disp_inout, uint8_t* mask, uint32_t* counts, int mem,
@@ -1119,24 +1147,12 @@ int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t*
                    (!luma || (((uintptr_t)dguide | g.frame | (size_t)g.pitch) & 3) == 0);
   const unsigned chunks = (unsigned)((HW + (vec ? 1023 : 255)) / (vec ? 1024 : 256));
   const TmpArgs all = a;
-  for (int k0 = 0; k0 < n; k0 += kTmpSlice) {      // the frame lists of kTmpSlice maps fit the kernel arguments
-    const int m = std::min(kTmpSlice, n - k0);
+  for (int k0 = 0; k0 < n; k0 += kSlice) {      // the frame lists of kSlice maps fit the kernel arguments
+    const int m = std::min(kSlice, n - k0);
     at_slice(a, all, k0, HW, 4);
     a.luma = all.luma ? all.luma + (size_t)k0 * g.frame : nullptr;
-    int groups = 0, filled = 0;      // group the slice's maps by stream, in order of first appearance, each in the order of k
-    for (int k = 0; k < m; ++k) {
-      const int id = stream_of ? stream_of[k0 + k] : 0;
-      bool known = false;
-      for (int g = 0; g < groups && !known; ++g) known = a.stream[g] == id;
-      if (!known) a.stream[groups++] = id;
-    }
-    for (int g = 0; g < groups; ++g) {
-      a.first[g] = filled;
-      a.fresh[g] = t->fresh[a.stream[g]];
-      for (int k = 0; k < m; ++k)
-        if ((stream_of ? stream_of[k0 + k] : 0) == a.stream[g]) a.map[filled++] = k;
-    }
-    a.first[groups] = filled;
+    int last[kSlice];      // per group: its last map of the slice (the filter keeps nothing of it)
+    const int groups = group_slice(a.g, last, stream_of, k0, m, t->fresh.data());
     const dim3 grid(chunks, groups), block(256);
     switch ((vec ? 2 : 0) + (luma ? 1 : 0)) {
       case 0: hipLaunchKernelGGL((k_temporal<false, false>), grid, block, 0, st, a); break;
@@ -1145,7 +1161,7 @@ int sn_temporal_push(sn_temporal* t, int n, const int* stream_of, const int32_t*
       default: hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, st, a); break;
     }
     HIP_TRY(h, hipGetLastError());
-    for (int g = 0; g < groups; ++g) t->fresh[a.stream[g]] = 0;      // enqueued: the state now holds these frames
+    commit_slice(a.g, groups, t->fresh.data());
   }
   return b.close();
 }
@@ -1407,19 +1423,6 @@ int sn_rectify_nv12(sn_rectify* r, int n, const uint8_t* left, const uint8_t* ri
 namespace {
 // llrint(v) for a finite v, values beyond +-lim taken as +-lim
 long long cm_llrint_sat(double v, double lim) { return v >= lim ? (long long)lim : (v <= -lim ? -(long long)lim : std::llrint(v)); }
-
-// the contract's q of one pose; false where sn_costmap_pose_q refuses it
-bool cm_pose_q(const sn_costmap* c, const double* pose, int32_t* q) {
-  const double x = pose[0], y = pose[1], yaw = pose[2], lim = 1073741824.0;
-  if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(yaw)) return false;
-  const double fx = x * c->k256, fy = y * c->k256;
-  if (!(std::fabs(fx) <= lim) || !(std::fabs(fy) <= lim)) return false;
-  const long long tx = std::llrint(fx), ty = std::llrint(fy);
-  q[0] = (int32_t)tx, q[1] = (int32_t)ty;
-  q[2] = (int32_t)std::llrint(std::cos(yaw) * lim), q[3] = (int32_t)std::llrint(std::sin(yaw) * lim);
-  q[4] = (int32_t)((tx >> 8) - c->p.mw / 2), q[5] = (int32_t)((ty >> 8) - c->p.mh / 2);
-  return true;
-}
 }  // namespace
 
 int sn_costmap_create(sn_handle* h, int streams, const sn_obstacle_params* op, const sn_costmap_params* p, sn_costmap** out) {
@@ -1428,7 +1431,7 @@ int sn_costmap_create(sn_handle* h, int streams, const sn_obstacle_params* op, c
     return SN_ERR_ARG;
   };
   if (!op || !p || !out) return refuse("a NULL pointer");
-  if (streams < 1 || (h && streams > h->max_batch)) return refuse("streams must be 1..max_batch");
+  if (!streams_ok(h, streams)) return refuse("streams must be 1..max_batch");
   if (p->mw < 1 || p->mh < 1 || p->mw > kCmMaxWindow || p->mh > kCmMaxWindow) return refuse("mw and mh must be 1..4096");
   if (p->l_hit < 1 || p->l_hit > 32767 || p->l_miss < 1 || p->l_miss > 32767) return refuse("l_hit and l_miss must be 1..32767");
   if (!(p->l_min >= -32767 && p->l_min < 0 && p->l_max > 0 && p->l_max <= 32767)) return refuse("-32767 <= l_min < 0 < l_max <= 32767 is required");
@@ -1444,7 +1447,7 @@ int sn_costmap_create(sn_handle* h, int streams, const sn_obstacle_params* op, c
   if (op->beams > 0 && !ob_beam_edges(op->beams, op->angle_min_rad, op->angle_increment_rad, edges.data()))
     return refuse("the scan's sector must lie inside (-pi/2, pi/2) with increasing edges");
   std::unique_ptr<sn_costmap> c(new sn_costmap);
-  c->h = h, c->streams = streams, c->p = *p;
+  c->p = *p;
   c->gw = op->gw, c->gh = op->gh, c->beams = op->beams;
   c->k256 = 256.0 / (double)op->cell_m;
   const double far = 1099511627776.0, cap = 2147483648.0;      // 2^40, 2^31
@@ -1453,58 +1456,27 @@ int sn_costmap_create(sn_handle* h, int streams, const sn_obstacle_params* op, c
   c->margin = cm_llrint_sat((double)p->clear_margin_m * c->k256, cap);
   c->rmin = cm_llrint_sat((double)p->clear_min_m * c->k256, cap);
   c->cmax = cm_llrint_sat((double)p->clear_max_m * c->k256, cap);
-  c->fresh.assign(streams, 1);
-  c->ox.assign(streams, 0), c->oy.assign(streams, 0);
-  if (h) {      // without a handle: a host-only object for sn_costmap_pose_q
-    const int rc = check_device(h);
-    if (rc) return rc;
-    const size_t bytes = (size_t)streams * p->mw * p->mh * 2;
-    if (hipMalloc(reinterpret_cast<void**>(&c->state), bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->edges), edges.size() * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(c->state);
-      set_err(h, "sn_costmap_create: out of device memory");
-      return SN_ERR_NOMEM;
-    }
-    if (hipMemcpy(c->edges, edges.data(), edges.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(c->state);
-      (void)hipFree(c->edges);
-      set_err(h, "sn_costmap_create: the upload of the beam table failed");
-      return SN_ERR_DEVICE;
-    }
-    ++h->costmap_live;
+  // without a handle: a host-only object for sn_costmap_pose_q
+  if (const int rc = stream_open(c.get(), h, streams, "sn_costmap_create", &sn_handle::costmap_live,
+                                 {{reinterpret_cast<void**>(&c->state), (size_t)streams * p->mw * p->mh * 2},
+                                  {reinterpret_cast<void**>(&c->edges), edges.size() * 4}}))
+    return rc;
+  if (h && hipMemcpy(c->edges, edges.data(), edges.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    sn_costmap_destroy(c.release());
+    set_err(h, "sn_costmap_create: the upload of the beam table failed");
+    return SN_ERR_DEVICE;
   }
   *out = c.release();
   return SN_OK;
 }
 
-int sn_costmap_reset(sn_costmap* c, int stream) {
-  if (!c) return SN_ERR_ARG;
-  if (stream < -1 || stream >= c->streams) {
-    set_err(c->h, "sn_costmap_reset: bad arguments");
-    return SN_ERR_ARG;
-  }
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (stream < 0) std::fill(c->fresh.begin(), c->fresh.end(), (uint8_t)1);
-  else c->fresh[stream] = 1;
-  return SN_OK;
-}
+int sn_costmap_reset(sn_costmap* c, int stream) { return stream_reset(c, stream, "sn_costmap_reset"); }
 
-void sn_costmap_destroy(sn_costmap* c) {
-  if (!c) return;
-  if (c->h) {
-    (void)hipSetDevice(c->h->device);
-    c->destroy();
-    (void)hipFree(c->state);
-    (void)hipFree(c->edges);
-    --c->h->costmap_live;
-  }
-  delete c;
-}
+void sn_costmap_destroy(sn_costmap* c) { stream_destroy(c, &sn_handle::costmap_live, &sn_costmap::state, &sn_costmap::edges); }
 
 int sn_costmap_pose_q(const sn_costmap* c, const double pose[3], int32_t q[6]) {
-  return c && pose && q && cm_pose_q(c, pose, q) ? SN_OK : SN_ERR_ARG;
+  return c && pose && q && torus_pose_q(c, pose, q) ? SN_OK : SN_ERR_ARG;
 }
 
 int sn_costmap_push(sn_costmap* c, int n, const int* stream_of, const double* poses, const int8_t* occ, const float* ranges,
@@ -1525,7 +1497,7 @@ int sn_costmap_push(sn_costmap* c, int n, const int* stream_of, const double* po
   if (((uintptr_t)logodds & 1) || ((uintptr_t)stats & 3) || ((uintptr_t)ranges & 3)) return refuse("a misaligned buffer");
   std::vector<int32_t> q((size_t)n * 6);
   for (int k = 0; k < n; ++k)
-    if (!cm_pose_q(c, poses + 3 * k, q.data() + 6 * k)) return refuse("a pose that is not finite or too far from the origin");
+    if (!torus_pose_q(c, poses + 3 * k, q.data() + 6 * k)) return refuse("a pose that is not finite or too far from the origin");
   const size_t cells = (size_t)c->p.mw * c->p.mh, ocells = (size_t)c->gw * c->gh;
   {
     const Span i0{occ, n * ocells}, i1{ranges, (size_t)n * c->beams * 4}, o0{grid, n * cells}, o1{logodds, n * cells * 2},
@@ -1551,55 +1523,25 @@ int sn_costmap_push(sn_costmap* c, int n, const int* stream_of, const double* po
   if (dstats) HIP_TRY(h, hipMemsetAsync(dstats, 0, (size_t)n * 16, st));
   const unsigned chunks = (unsigned)((cells + 255) / 256);
   const size_t lds = dranges ? (size_t)(3 * c->beams + 1) * 4 : 0;      // E, and Rb twice
-  for (int k0 = 0; k0 < n; k0 += kCmSlice) {      // the frame lists and the poses of kCmSlice maps fit the kernel arguments
-    const int m = std::min(kCmSlice, n - k0);
+  for (int k0 = 0; k0 < n; k0 += kSlice) {      // the frame lists and the poses of kSlice maps fit the kernel arguments
+    const int m = std::min(kSlice, n - k0);
     a.occ = docc ? docc + k0 * ocells : nullptr;
     a.ranges = dranges ? dranges + (size_t)k0 * c->beams : nullptr;
     a.grid = dgrid ? dgrid + k0 * cells : nullptr;
     a.logodds = dlog ? dlog + k0 * cells : nullptr;
     a.stats = dstats ? dstats + (size_t)k0 * 4 : nullptr;
     memcpy(a.q, q.data() + (size_t)k0 * 6, (size_t)m * 24);
-    int groups = 0, filled = 0;      // group the slice's maps by stream, in order of first appearance, each in the order of k
-    for (int k = 0; k < m; ++k) {
-      const int id = stream_of ? stream_of[k0 + k] : 0;
-      bool known = false;
-      for (int g = 0; g < groups && !known; ++g) known = a.stream[g] == id;
-      if (!known) a.stream[groups++] = id;
-    }
-    int last[kCmSlice];      // per group: its last map of the slice
-    for (int g = 0; g < groups; ++g) {
-      const int id = a.stream[g];
-      a.first[g] = filled;
-      a.fresh[g] = c->fresh[id], a.pox[g] = c->ox[id], a.poy[g] = c->oy[id];
-      for (int k = 0; k < m; ++k)
-        if ((stream_of ? stream_of[k0 + k] : 0) == id) a.map[filled++] = k, last[g] = k;
-    }
-    a.first[groups] = filled;
+    int last[kSlice];      // per group: its last map of the slice
+    const int groups = group_slice(a.g, a.t, last, stream_of, k0, m, c->fresh.data(), c->ox.data(), c->oy.data());
     hipLaunchKernelGGL(k_costmap, dim3(chunks, groups), dim3(256), lds, st, a);
     HIP_TRY(h, hipGetLastError());
-    for (int g = 0; g < groups; ++g) {      // enqueued: the state now holds these frames
-      const int id = a.stream[g];
-      c->fresh[id] = 0, c->ox[id] = a.q[last[g]][4], c->oy[id] = a.q[last[g]][5];
-    }
+    commit_slice(a.g, groups, last, a.q, c->fresh.data(), c->ox.data(), c->oy.data());
   }
   return b.close();
 }
 
 // ---- rolling elevation map and traversability (csrc/sn_elevation.hpp): an object with its own state and lane, as the costmap ----
 namespace {
-// the contract's q of one pose (sn_costmap_pose_q's rule); false where sn_elevation_pose_q refuses it
-bool el_pose_q(const sn_elevation* e, const double* pose, int32_t* q) {
-  const double x = pose[0], y = pose[1], yaw = pose[2], lim = 1073741824.0;
-  if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(yaw)) return false;
-  const double fx = x * e->k256, fy = y * e->k256;
-  if (!(std::fabs(fx) <= lim) || !(std::fabs(fy) <= lim)) return false;
-  const long long tx = std::llrint(fx), ty = std::llrint(fy);
-  q[0] = (int32_t)tx, q[1] = (int32_t)ty;
-  q[2] = (int32_t)std::llrint(std::cos(yaw) * lim), q[3] = (int32_t)std::llrint(std::sin(yaw) * lim);
-  q[4] = (int32_t)((tx >> 8) - e->p.mw / 2), q[5] = (int32_t)((ty >> 8) - e->p.mh / 2);
-  return true;
-}
-
 // (int)floorf(v * 1000.f) for |v| <= 32
 int el_mm(float v) {
   volatile float prod = v * 1000.f;      // one rounded fp32 product
@@ -1613,7 +1555,7 @@ int sn_elevation_create(sn_handle* h, int streams, const sn_elevation_params* p,
     return SN_ERR_ARG;
   };
   if (!p || !out) return refuse("a NULL pointer");
-  if (streams < 1 || (h && streams > h->max_batch)) return refuse("streams must be 1..max_batch");
+  if (!streams_ok(h, streams)) return refuse("streams must be 1..max_batch");
   if (p->mw < 1 || p->mh < 1 || p->mw > kElMaxWindow || p->mh > kElMaxWindow) return refuse("mw and mh must be 1..4096");
   for (float v : p->base_from_cam)
     if (!std::isfinite(v)) return refuse("base_from_cam must be finite");
@@ -1628,50 +1570,23 @@ int sn_elevation_create(sn_handle* h, int streams, const sn_elevation_params* p,
   if (p->radius < 1 || p->radius > kElMaxRadius) return refuse("radius must be 1..3");
   if (p->flags != 0) return refuse("flags must be 0");
   std::unique_ptr<sn_elevation> e(new sn_elevation);
-  e->h = h, e->streams = streams, e->p = *p;
+  e->p = *p;
   e->k256 = 256.0 / (double)p->cell_m;
   e->zmin_mm = el_mm(p->z_min_m), e->zmax_mm = el_mm(p->z_max_m);
-  e->fresh.assign(streams, 1);
-  e->ox.assign(streams, 0), e->oy.assign(streams, 0);
-  if (h) {      // without a handle: a host-only object for sn_elevation_pose_q
-    const int rc = check_device(h);
-    if (rc) return rc;
-    if (hipMalloc(reinterpret_cast<void**>(&e->state), (size_t)streams * p->mw * p->mh * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      set_err(h, "sn_elevation_create: out of device memory");
-      return SN_ERR_NOMEM;
-    }
-    ++h->elevation_live;
-  }
+  // without a handle: a host-only object for sn_elevation_pose_q
+  if (const int rc = stream_open(e.get(), h, streams, "sn_elevation_create", &sn_handle::elevation_live,
+                                 {{reinterpret_cast<void**>(&e->state), (size_t)streams * p->mw * p->mh * 4}}))
+    return rc;
   *out = e.release();
   return SN_OK;
 }
 
-int sn_elevation_reset(sn_elevation* e, int stream) {
-  if (!e) return SN_ERR_ARG;
-  if (stream < -1 || stream >= e->streams) {
-    set_err(e->h, "sn_elevation_reset: bad arguments");
-    return SN_ERR_ARG;
-  }
-  std::lock_guard<std::mutex> lk(e->mu);
-  if (stream < 0) std::fill(e->fresh.begin(), e->fresh.end(), (uint8_t)1);
-  else e->fresh[stream] = 1;
-  return SN_OK;
-}
+int sn_elevation_reset(sn_elevation* e, int stream) { return stream_reset(e, stream, "sn_elevation_reset"); }
 
-void sn_elevation_destroy(sn_elevation* e) {
-  if (!e) return;
-  if (e->h) {
-    (void)hipSetDevice(e->h->device);
-    e->destroy();
-    (void)hipFree(e->state);
-    --e->h->elevation_live;
-  }
-  delete e;
-}
+void sn_elevation_destroy(sn_elevation* e) { stream_destroy(e, &sn_handle::elevation_live, &sn_elevation::state); }
 
 int sn_elevation_pose_q(const sn_elevation* e, const double pose[3], int32_t q[6]) {
-  return e && pose && q && el_pose_q(e, pose, q) ? SN_OK : SN_ERR_ARG;
+  return e && pose && q && torus_pose_q(e, pose, q) ? SN_OK : SN_ERR_ARG;
 }
 
 int sn_elevation_push(sn_elevation* e, int n, const int* stream_of, const double* poses, const int32_t* raw, const sn_camera* cam,
@@ -1694,7 +1609,7 @@ int sn_elevation_push(sn_elevation* e, int n, const int* stream_of, const double
   if (mounts && mount_stride < 12) return refuse("mount_stride must be at least 12");
   std::vector<int32_t> q((size_t)n * 6);
   for (int k = 0; k < n; ++k)
-    if (!el_pose_q(e, poses + 3 * k, q.data() + 6 * k)) return refuse("a pose that is not finite or too far from the origin");
+    if (!torus_pose_q(e, poses + 3 * k, q.data() + 6 * k)) return refuse("a pose that is not finite or too far from the origin");
   const int W = h->W, H = h->H, step = cam->step;
   const int Wo = (W + step - 1) / step, Ho = (H + step - 1) / step;
   const size_t cells = (size_t)e->p.mw * e->p.mh, raw_bytes = (size_t)n * H * W * 4;
@@ -1759,8 +1674,8 @@ int sn_elevation_push(sn_elevation* e, int n, const int* stream_of, const double
   fa.mw = e->p.mw, fa.mh = e->p.mh, fa.min_points = e->p.min_points, fa.alpha = e->p.alpha;
   const int cblocks = (Wo + 255) / 256;
   const unsigned slot_chunks = (unsigned)((cells + 255) / 256);
-  for (int k0 = 0; k0 < n; k0 += kElSlice) {      // the frame lists and the poses of kElSlice maps fit the kernel arguments
-    const int m = std::min(kElSlice, n - k0);
+  for (int k0 = 0; k0 < n; k0 += kSlice) {      // the frame lists and the poses of kSlice maps fit the kernel arguments
+    const int m = std::min(kSlice, n - k0);
     // a workgroup is 256 columns of a chunk of rows: about 2048 workgroups a launch, and runs of at least 16 rows
     sa.chunks = std::max(1, std::min((2048 + cblocks * m - 1) / (cblocks * m), (Ho + 15) / 16));
     sa.rows = (Ho + sa.chunks - 1) / sa.chunks;
@@ -1776,28 +1691,11 @@ int sn_elevation_push(sn_elevation* e, int n, const int* stream_of, const double
     fa.hi = dhi + k0 * cells, fa.lo = dlo + k0 * cells;
     fa.stats = dstats ? dstats + (size_t)k0 * 4 : nullptr;
     for (int k = 0; k < m; ++k) fa.org[k][0] = sa.q[k][4], fa.org[k][1] = sa.q[k][5];
-    int groups = 0, filled = 0;      // group the slice's maps by stream, in order of first appearance, each in the order of k
-    for (int k = 0; k < m; ++k) {
-      const int id = stream_of ? stream_of[k0 + k] : 0;
-      bool known = false;
-      for (int g = 0; g < groups && !known; ++g) known = fa.stream[g] == id;
-      if (!known) fa.stream[groups++] = id;
-    }
-    int last[kElSlice];      // per group: its last map of the slice
-    for (int g = 0; g < groups; ++g) {
-      const int id = fa.stream[g];
-      fa.first[g] = filled;
-      fa.fresh[g] = e->fresh[id], fa.pox[g] = e->ox[id], fa.poy[g] = e->oy[id];
-      for (int k = 0; k < m; ++k)
-        if ((stream_of ? stream_of[k0 + k] : 0) == id) fa.map[filled++] = k, last[g] = k;
-    }
-    fa.first[groups] = filled;
+    int last[kSlice];      // per group: its last map of the slice
+    const int groups = group_slice(fa.g, fa.t, last, stream_of, k0, m, e->fresh.data(), e->ox.data(), e->oy.data());
     hipLaunchKernelGGL(k_el_fuse, dim3(slot_chunks, groups), dim3(256), 0, st, fa);
     HIP_TRY(h, hipGetLastError());
-    for (int g = 0; g < groups; ++g) {      // enqueued: the state now holds these frames
-      const int id = fa.stream[g];
-      e->fresh[id] = 0, e->ox[id] = fa.org[last[g]][0], e->oy[id] = fa.org[last[g]][1];
-    }
+    commit_slice(fa.g, groups, last, sa.q, e->fresh.data(), e->ox.data(), e->oy.data());
   }
   if (dtrav || drise || dstats) {
     ElVerdictArgs va{dhi, dlo, dtrav, drise, dstats, e->p.mw, e->p.mh, e->p.radius, e->p.max_step_mm, (e->p.mw + kElTileW - 1) / kElTileW};

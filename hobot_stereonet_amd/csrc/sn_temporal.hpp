@@ -14,18 +14,15 @@
 //                 LUMA = false (luma_delta == 0): no guide is read, Yp is neither read nor written.
 //                 Traffic per pixel and frame: raw 4 + luma 1 + out 4 + mask 1 (+ disp 4 where it changes), and 6 (+ 6) bytes
 //                 of state per pixel and launch.
-//                 counts: the four counters of a lane and frame are packed into two words of 16-bit fields, summed over the
-//                 wave by shuffles and added to an LDS table [frame][4] by one lane per wave; after the last frame one global
-//                 atomicAdd per workgroup, frame and non-zero counter (integer, order-free).  No barrier inside the frame loop.
+//                 counts: sn_streams.hpp's stats_*.  No barrier inside the frame loop.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/stereonet_hip.h"   // SN_TMP_*
+#include "sn_streams.hpp"
 
 namespace sn {
-
-constexpr int kTmpSlice = 64;      // maps per launch: the per-stream frame lists travel in the kernel arguments
 
 struct TmpArgs {
   const int32_t* raw;    // [m][H][W]; may be out_raw
@@ -44,10 +41,7 @@ struct TmpArgs {
   int alpha, persist, luma_delta;
   long long q;
   float S;
-  int first[kTmpSlice + 1];   // group g = entries first[g] .. first[g + 1] - 1 of map[]
-  int stream[kTmpSlice];      // per group: which state it updates
-  int fresh[kTmpSlice];       // per group: the stream has seen no frame since it was created or reset
-  int map[kTmpSlice];         // map indices of the launch, grouped by stream, each group in time order
+  StreamGroups g;        // the launch's maps, sorted by stream
 };
 
 // the contract for one pixel and frame: updates P, Hs, Yp; returns the mask bits and sets *out
@@ -97,17 +91,17 @@ __device__ __forceinline__ uint32_t tmp_step(const TmpArgs& a, bool seen, int32_
 template <bool VEC, bool LUMA>
 __global__ __launch_bounds__(256) void k_temporal(TmpArgs a) {
   constexpr int PX = VEC ? 4 : 1;
-  __shared__ uint32_t cnt[kTmpSlice][4];
-  const int g = blockIdx.y, f0 = a.first[g], f1 = a.first[g + 1];
+  __shared__ uint32_t cnt[kSlice][4];
+  const int g = blockIdx.y, f0 = a.g.first[g], f1 = a.g.first[g + 1];
   const size_t HW = (size_t)a.H * a.W;
   const size_t p0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * PX;
   const bool live = p0 < HW;      // VEC: H*W is a multiple of 4, so the lane's four pixels are all inside or all outside
   if (a.counts) {
-    if ((int)threadIdx.x < (f1 - f0) * 4) cnt[threadIdx.x >> 2][threadIdx.x & 3] = 0;
+    stats_clear(cnt, f1 - f0);
     __syncthreads();
   }
-  const size_t sp = (size_t)a.stream[g] * HW + p0;
-  bool seen = !a.fresh[g];
+  const size_t sp = (size_t)a.g.stream[g] * HW + p0;
+  bool seen = !a.g.fresh[g];
   int32_t P[PX];
   uint32_t Hs[PX], Yp[PX];
 #pragma unroll
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(256) void k_temporal(TmpArgs a) {
   }
 #pragma unroll 1
   for (int f = f0; f < f1; ++f) {
-    const int k = a.map[f];
+    const int k = a.g.map[f];
     const size_t mp = (size_t)k * HW + p0;
     uint32_t n_valid = 0, n_blend = 0, n_held = 0, n_reset = 0;
     if (live) {
@@ -171,21 +165,7 @@ __global__ __launch_bounds__(256) void k_temporal(TmpArgs a) {
       }
     }
     seen = true;
-    if (a.counts) {      // wave-uniform
-      uint32_t lo = n_valid | (n_blend << 16), hi = n_held | (n_reset << 16);      // a wave's sums are at most 256
-#pragma unroll
-      for (int s = 32; s > 0; s >>= 1) {
-        lo += __shfl_xor(lo, s);
-        hi += __shfl_xor(hi, s);
-      }
-      if ((threadIdx.x & 63) == 0) {
-        uint32_t* c = cnt[f - f0];
-        if (lo & 0xffffu) atomicAdd(c + 0, lo & 0xffffu);
-        if (lo >> 16) atomicAdd(c + 1, lo >> 16);
-        if (hi & 0xffffu) atomicAdd(c + 2, hi & 0xffffu);
-        if (hi >> 16) atomicAdd(c + 3, hi >> 16);
-      }
-    }
+    if (a.counts) stats_frame(cnt[f - f0], n_valid | (n_blend << 16), n_held | (n_reset << 16));      // wave-uniform; a wave's sums are at most 256
   }
   if (live && f1 > f0) {
     if constexpr (VEC) {
@@ -198,13 +178,7 @@ __global__ __launch_bounds__(256) void k_temporal(TmpArgs a) {
       if (LUMA) a.Yp[sp] = (uint8_t)Yp[0];
     }
   }
-  if (a.counts) {
-    __syncthreads();
-    if ((int)threadIdx.x < (f1 - f0) * 4) {
-      const uint32_t v = cnt[threadIdx.x >> 2][threadIdx.x & 3];
-      if (v) atomicAdd(a.counts + (size_t)a.map[f0 + (threadIdx.x >> 2)] * 4 + (threadIdx.x & 3), v);
-    }
-  }
+  if (a.counts) stats_flush(cnt, a.counts, a.g.map, f0, f1);
 }
 
 }  // namespace sn

@@ -9,12 +9,11 @@ millimetres.
 from __future__ import annotations
 
 import dataclasses
-import math
 from typing import Optional, Tuple
 
 import numpy as np
 
-from . import obstacles, pointcloud, spec
+from . import obstacles, pointcloud, spec, torus
 
 MAX_WINDOW = 4096                   # mw, mh
 UNKNOWN = -32768                    # hi and lo of a cell nobody has observed
@@ -97,13 +96,7 @@ def units(p: ElevationParams) -> Units:
 def pose_q(p: ElevationParams, pose) -> np.ndarray:
     """sn_elevation_pose_q: (x, y, yaw) -> int32 (6,) = {tx, ty, cq, sq, ox, oy}.  ValueError for a pose that is not finite or
     too far.  The library's may differ by one unit in cq, sq: two implementations of a double cos and sin."""
-    x, y, yaw = (float(v) for v in pose)
-    k256 = units(p).k256
-    if not all(math.isfinite(v) for v in (x, y, yaw)) or abs(x * k256) > Q30 or abs(y * k256) > Q30:
-        raise ValueError("the pose must be finite and within 2^30 subs of the origin")
-    tx, ty = int(np.rint(x * k256)), int(np.rint(y * k256))
-    return np.array([tx, ty, int(np.rint(math.cos(yaw) * Q30)), int(np.rint(math.sin(yaw) * Q30)), (tx >> 8) - p.mw // 2,
-                     (ty >> 8) - p.mh // 2], np.int32)
+    return torus.pose_q(units(p).k256, p.mw, p.mh, pose)
 
 
 def base_points(raw: np.ndarray, cam: pointcloud.Camera, mounts: np.ndarray, out_scale: float = spec.OUT_SCALE):
@@ -202,15 +195,11 @@ class Reference:
         ox, oy = int(q[4]), int(q[5])
         br = dict(stream=s, scrolled=0, born=0, blended=0, clamped=0, up=0, down=0, prev=self.origin[s], origin=(ox, oy))
         self.frames.append(br)
-        i, j = np.arange(p.mw, dtype=np.int64), np.arange(p.mh, dtype=np.int64)
-        cx, cy = ox + (i - ox) % p.mw, oy + (j - oy) % p.mh
+        _, _, moved, rows, cols = torus.view(p.mw, p.mh, (ox, oy), self.origin[s])
         H, L = self.hi[s].astype(np.int64), self.lo[s].astype(np.int64)
-        if self.origin[s] is not None:
-            pox, poy = self.origin[s]
-            moved = (cy != poy + (j - poy) % p.mh)[:, None] | (cx != pox + (i - pox) % p.mw)[None, :]
+        if moved is not None:
             br["scrolled"] = int((moved & (H != UNKNOWN)).sum())
             H[moved], L[moved] = UNKNOWN, UNKNOWN
-        rows, cols = (cy - oy)[:, None], (cx - ox)[None, :]      # slot (i, j) is element [cy - oy][cx - ox] of the window
         c, fx, fn = cnt[rows, cols], fmax[rows, cols], fmin[rows, cols]
         fused, known = c >= p.min_points, H != UNKNOWN
         clamp = lambda v: np.clip(v, -32767, 32767)      # noqa: E731

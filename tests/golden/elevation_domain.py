@@ -1,5 +1,5 @@
 """The inputs the elevation map (sn_elevation_push) is judged on beside the constants of its launch: the geometries of
-postproc_domain.GEOMETRIES at camera step 1, 2 and 4, a push of more maps than a launch takes (kElSlice = 64) on three streams
+postproc_domain.GEOMETRIES at camera step 1, 2 and 4, a push of more maps than a launch takes (kSlice = 64) on three streams
 with a mount per map, a launch whose row chunks the workgroup cap lengthens, a window of more cells than one pass of k_el_clear covers (2048 workgroups of 256), windows at the declared
 limit of 4096 cells, and poses within a cell of the quantiser's limit.  tests/test_elevation_geometry.py checks on the CPU that
 these inputs do what they are there for (points used, branches taken, the last column block carrying points, the mutated readings
@@ -18,7 +18,7 @@ from hobot_stereonet_amd.pointcloud import Camera
 
 STEPS = (1, 2, 4)
 N = 3
-SLICE = 64                           # kElSlice (csrc/sn_elevation.hpp)
+SLICE = 64                           # kSlice (csrc/sn_stream_groups.hpp)
 CLEAR_PASS = 2048 * 256              # cells one pass of k_el_clear's grid covers
 BASE = ElevationParams(mw=21, mh=18, cell_m=0.25, z_min_m=-1.0, z_max_m=1.5, range_max_m=8.0, min_points=1, alpha=96, max_step_mm=70,
                        radius=1)

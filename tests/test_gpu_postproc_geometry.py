@@ -445,7 +445,7 @@ def test_infer_lrc_right_out_at_this_geometry(model_factory, w, h):
 
 
 # ---- the slice walks: more maps in one push than a launch takes --------------------------------------------------------------------
-SLICE = 64                 # kTmpSlice = kCmSlice (csrc/sn_temporal.hpp, csrc/sn_costmap.hpp)
+SLICE = 64                 # kSlice (csrc/sn_stream_groups.hpp)
 BIG, SECOND = 130, 70
 
 
