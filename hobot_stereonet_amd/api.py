@@ -344,6 +344,7 @@ def load_library(path: Optional[str] = None):
     lib.sn_dbg_read.argtypes = [vp, C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.sn_dbg_set_grid_cus.argtypes = [vp, ip]
     lib.sn_dbg_last_launch.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+    lib.sn_dbg_slot_graphs.argtypes = [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
     lib.sn_dbg_conv2d_n.argtypes = [vp, ip] + lib.sn_dbg_conv2d.argtypes[1:]
     lib.sn_dbg_down0_n.argtypes = [vp, ip] + lib.sn_dbg_down0.argtypes[1:]
     lib.sn_dbg_down01_n.argtypes = [vp, ip] + lib.sn_dbg_down01.argtypes[1:]
@@ -425,7 +426,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_elevation_create", "sn_elevation_reset", "sn_elevation_pose_q", "sn_elevation_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_rollout_tables", "sn_rollout_pose_q", "sn_rollout_velocity", "sn_rollout", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_slot_graphs", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_elevation_create", "sn_elevation_reset", "sn_elevation_pose_q", "sn_elevation_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_rollout_tables", "sn_rollout_pose_q", "sn_rollout_velocity", "sn_rollout", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -1372,6 +1373,14 @@ class StereoNetHIP:
         wgs, units = C.c_int(0), C.c_int(0)
         self._check(self._lib.sn_dbg_last_launch(self._h, C.byref(wgs), C.byref(units)), "sn_dbg_last_launch")
         return wgs.value, units.value
+
+    def dbg_slot_graphs(self):
+        """sn_dbg_slot_graphs -> (enabled, instantiated, launches): whether the async slots still replay hipGraphs (0 under
+        SN_NO_GRAPH, or after a capture failed and they fell back to plain launches), the graphs instantiated and the
+        requests served by hipGraphLaunch over the handle's life"""
+        en, inst, launches = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        self._check(self._lib.sn_dbg_slot_graphs(self._h, C.byref(en), C.byref(inst), C.byref(launches)), "sn_dbg_slot_graphs")
+        return en.value, inst.value, launches.value
 
     @staticmethod
     def _batch(x, dtype=np.float32):

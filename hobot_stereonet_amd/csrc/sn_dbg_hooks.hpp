@@ -270,6 +270,18 @@ int sn_dbg_last_launch(sn_handle* h, int* wgs, int* units) {
   return SN_OK;
 }
 
+// What the async slots did over the handle's life (submit_common): *enabled = hipGraph replay is still on (0: SN_NO_GRAPH, or
+// a capture failed and the slots fell back to plain launches), *instantiated = graphs instantiated, *launches = requests
+// served by hipGraphLaunch.  Tests only: not declared in include/stereonet_hip.h.
+int sn_dbg_slot_graphs(sn_handle* h, int* enabled, int* instantiated, int* launches) {
+  if (!h || !enabled || !instantiated || !launches) return SN_ERR_ARG;
+  std::lock_guard<std::mutex> lk(h->mu);
+  *enabled = h->use_graphs ? 1 : 0;
+  *instantiated = h->graphs_instantiated;
+  *launches = h->graph_launches;
+  return SN_OK;
+}
+
 int sn_dbg_conv2d_n(sn_handle* h, int n, const float* in, int cin, int h_px, int w, const float* wt, const float* bias,
                     int k, int stride, int dil, int lrelu, const float* residual, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path

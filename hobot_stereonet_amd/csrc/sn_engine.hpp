@@ -263,6 +263,9 @@ struct sn_handle {
   std::mutex mu;
   std::condition_variable cv;
   uint64_t next_ticket = 1;
+  // what the slots did over the handle's life (submit_common, under mu; read by sn_dbg_slot_graphs): graphs instantiated and
+  // requests served by hipGraphLaunch
+  int graphs_instantiated = 0, graph_launches = 0;
   // profiling
   bool profiling = false;
   hipEvent_t ev[8] = {};

@@ -266,6 +266,27 @@ __device__ __forceinline__ void refine_stat_commit(unsigned long long* stat, flo
   if (stat != nullptr && (threadIdx.x & 63) == 0)
     stat_commit_line(stat + (blockIdx.x % kStatSlots) * kStatLine, lane_sum, nonfinite);
 }
+// The same statistic for a kernel whose GRID may differ between two runs of one frame (the tail form of the streamed block: an
+// async request that shares the GPU runs it on 7/8 of the CUs, submit_common).  An fp32 partial sum rounded to fixed point once
+// per wave depends on which rows the wave owned; here every PIXEL goes to fixed point before any addition (stat_fixed), the
+// lanes and waves add integers, and the total is the same however the rows are cut into shares.  A pixel whose |D r| is not
+// finite adds nothing: its d is not finite either, so it is in the count already.
+__device__ __forceinline__ unsigned long long stat_fixed(float v) {
+  return stat_finite(v) ? (unsigned long long)(fminf(v, 4294967296.0f) * kStatScale + 0.5f) : 0ull;
+}
+__device__ __forceinline__ void refine_stat_commit_fixed(unsigned long long* stat, unsigned long long lane_sum, unsigned lane_nonfinite = 0u) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)lane_sum, off), hi = __shfl_xor((unsigned)(lane_sum >> 32), off);
+    lane_sum += ((unsigned long long)hi << 32) | lo;
+  }
+  const unsigned nonfinite = stat_wave_count(lane_nonfinite);
+  if (stat != nullptr && (threadIdx.x & 63) == 0) {
+    unsigned long long* line = stat + (blockIdx.x % kStatSlots) * kStatLine;
+    atomicAdd(line, lane_sum);
+    if (nonfinite) atomicAdd(line + kStatNonfinite, (unsigned long long)nonfinite);
+  }
+}
 // every thread of a (<= 512-thread) workgroup calls this: one atomic per workgroup
 __device__ __forceinline__ void refine_stat_commit_block(unsigned long long* stat, float lane_sum, unsigned lane_nonfinite = 0u) {
   __shared__ float s_stat[8];

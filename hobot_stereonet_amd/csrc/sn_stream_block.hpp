@@ -348,7 +348,8 @@ __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per
       return (int)sx;
     };
     int p4 = 0;                           // HEAD: (4 q) mod PROWS, the P ring position of slot q
-    float moved = 0.f;                    // HEAD: this lane's sum of |D r| (refinement statistic)
+    unsigned long long moved = 0ull;      // HEAD: this lane's sum of |D r| in 2^-20 px (refinement statistic; per pixel to fixed
+                                          // point: the total must not depend on the grid, refine_stat_commit_fixed)
     unsigned bad = 0u;                    // HEAD: this lane's written pixels whose d was not finite before the clamp
     dm.step(0, 0, f0, f1, sc.hsub);
     dma_issue(dm, 0);
@@ -407,7 +408,7 @@ __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per
             unsigned nf;
             const float d = head_value(up, ha.dmax, acc, mv, nf);
             if (lane >= 1 && lane <= T::OW && X < ha.W) {
-              moved += mv;
+              moved += stat_fixed(mv);
               bad += nf;
               head_store(ha.out_disp, ha.out_raw, ((size_t)fin_img * ha.H + o) * ha.W + X, d, ha.inv_q);
             }
@@ -501,7 +502,7 @@ __global__ __launch_bounds__(128 * NWR, NWR / 2) __attribute__((amdgpu_waves_per
       qt = qt + 1 == T::NTS ? 0 : qt + 1;
       p4 = p4 + R >= T::PROWS ? p4 + R - T::PROWS : p4 + R;
     }
-    if constexpr (HEAD) refine_stat_commit(ha.stat, moved, bad);
+    if constexpr (HEAD) refine_stat_commit_fixed(ha.stat, moved, bad);
     SN_STAMP_WG(1);
   } else {
     // ============================ conv2 waves: conv2 + residual + stores ============================

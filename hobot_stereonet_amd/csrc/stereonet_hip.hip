@@ -814,11 +814,14 @@ static int submit_common(sn_handle* h, const void* in, int kind, int32_t* out_i3
     if (!s->gexec[kind][mask][mi]) {
       (void)hipGetLastError();
       h->use_graphs = false;          // capture unsupported here: keep issuing plain launches (same kernels)
+    } else {
+      ++h->graphs_instantiated;
     }
   }
   HIP_TRY(h, hipEventRecord(s->ev0, s->stream));
   if (s->gexec[kind][mask][mi]) {
     HIP_TRY(h, hipGraphLaunch(s->gexec[kind][mask][mi], s->stream));
+    ++h->graph_launches;
   } else {
     rc = enqueue();
     if (rc) return rc;

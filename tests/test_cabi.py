@@ -25,6 +25,17 @@ def test_header_symbols_are_exported():
         assert hasattr(lib, s), f"{s} declared in stereonet_hip.h but not exported"
 
 
+def test_slot_graph_readout_is_exported_and_refuses_null():
+    """sn_dbg_slot_graphs (what the async slots' hipGraphs did; tests/test_gpu_async_graph.py) is a test hook: exported and
+    bound by api.py, not declared in the public header, and SN_ERR_ARG for a null handle or a null output without a device."""
+    lib = api.load_library()
+    assert hasattr(lib, "sn_dbg_slot_graphs") and hasattr(api.StereoNetHIP, "dbg_slot_graphs")
+    assert "sn_dbg_slot_graphs" not in declared_symbols()
+    a, b, c = ctypes.c_int(7), ctypes.c_int(7), ctypes.c_int(7)
+    assert lib.sn_dbg_slot_graphs(None, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) == -1      # SN_ERR_ARG
+    assert (a.value, b.value, c.value) == (7, 7, 7)             # nothing written
+
+
 def test_strerror_and_codes():
     assert api.error_string(0) == "ok"
     assert "gfx950" in api.error_string(-4)
