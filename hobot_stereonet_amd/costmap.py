@@ -15,7 +15,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import obstacles, torus
+from . import obstacles, paramfile, torus
 from .obstacles import ObstacleParams
 
 MAX_WINDOW = 4096                   # mw, mh
@@ -318,35 +318,18 @@ def boundary_clip():
 
 
 # ---- the parameter file: one `key value` per line, `#` comments, as obstacles.py's ------------------------------------------------
+_FILE = paramfile.spec(_FLOATS, _INTS, frame=paramfile.Key(1, str))
+
+
 def save_params(path: str, p: CostmapParams) -> None:
     """Floats as repr, so load_params(save_params(p)) == p exactly."""
-    with open(path, "w") as f:
-        f.write("# rolling log-odds costmap: window in cells of the obstacle grid's cell_m, log-odds in int16 units, metres\n")
-        for k in _INTS:
-            f.write(f"{k} {int(getattr(p, k))}\n")
-        for k in _FLOATS:
-            f.write(f"{k} {float(getattr(p, k))!r}\n")
-        f.write(f"frame {p.frame}\n")
+    paramfile.write(path, "rolling log-odds costmap: window in cells of the obstacle grid's cell_m, log-odds in int16 units, metres",
+                    _FILE, [(k, getattr(p, k)) for k in _INTS + _FLOATS + ("frame",)])
 
 
 def load_params(path: str) -> CostmapParams:
     """A key that is missing keeps CostmapParams' default; an unknown or repeated key, or a wrong number of values, is an error."""
-    got = {}
-    with open(path) as f:
-        for no, text in enumerate(f, 1):
-            words = text.split("#", 1)[0].split()
-            if not words:
-                continue
-            key, vals = words[0], words[1:]
-            if key not in _FLOATS + _INTS + ("frame",):
-                raise ValueError(f"{path}:{no}: unknown key {key!r}")
-            if key in got or len(vals) != 1:
-                raise ValueError(f"{path}:{no}: expected one `{key}` line with 1 value")
-            try:
-                got[key] = vals[0] if key == "frame" else int(vals[0]) if key in _INTS else float(vals[0])
-            except ValueError:
-                raise ValueError(f"{path}:{no}: not a number in {text.strip()!r}") from None
-    return CostmapParams(**got)
+    return CostmapParams(**paramfile.read(path, _FILE))
 
 
 def load_poses(path: str) -> np.ndarray:

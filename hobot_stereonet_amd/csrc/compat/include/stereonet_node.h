@@ -34,6 +34,7 @@
 #include "stereonet_hip.h"
 #include "bin_data.h"
 #include "preprocess.h"
+#include "stage_files.h"
 
 namespace hobot {
 namespace stereonet {
@@ -131,20 +132,20 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // rectifier's); unset: off, nothing of it exists
     bool obstacles = false;
     sn_obstacle_params obstacle_params{};
-    std::string obstacle_frame = "base_link";
+    std::string obstacle_frame = kDefaultBaseFrame;
     // this implementation's own: the ground plane of every frame's map (sn_ground_from_raw) ahead of the obstacle stage, which
     // then classifies with the frame's mount (sn_obstacles_from_raw_mounts) instead of the obstacle file's base_from_cam.
     // STEREONET_GROUND=<parameter file> (ground.save_params' `key value` lines) turns it on, with the camera of the point cloud
     // and the obstacle stage; height and tilt are logged when they change by more than the file's log_delta; unset: off
     bool ground = false;
     sn_ground_params ground_params{};
-    float ground_log_delta = 0.02f;
+    float ground_log_delta = kDefaultGroundLogDelta;
     // this implementation's own: a rolling log-odds costmap with ray clearing (sn_costmap_push) over the obstacle stage's grid and
     // scan, at the pose of SetBasePose: nav_msgs/OccupancyGrid on /stereonet_costmap, published after the obstacle topics.
     // STEREONET_COSTMAP=<parameter file> (costmap.save_params' `key value` lines, `frame` = the fixed frame's id, default odom)
     // turns it on and requires STEREONET_OBSTACLES; unset: off, nothing of it exists
     sn_costmap_params costmap_params{};
-    std::string costmap_frame = "odom";
+    std::string costmap_frame = kDefaultFixedFrame;
     // this implementation's own: a rolling elevation map with a step-height traversability verdict (sn_elevation_push) from the
     // request's map at the pose of SetBasePose, with the frame's fitted mount while STEREONET_GROUND is on: the verdict as
     // nav_msgs/OccupancyGrid on /stereonet_traversability, published after the obstacle topics (and the costmap's).
@@ -153,7 +154,7 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
     // /stereonet_inflated_grid (and so of the plan and the rollout) in the place of the costmap's or the obstacle grid;
     // without that line, or unset: nothing the node published before changes
     sn_elevation_params elevation_params{};
-    std::string elevation_frame = "odom";
+    std::string elevation_frame = kDefaultFixedFrame;
     bool elevation_feeds_inflate = false;
     // this implementation's own: inflation by the robot's radius (sn_inflate_grid) of the grid a planner reads: nav_msgs/
     // OccupancyGrid on /stereonet_inflated_grid with the header and info of its source, published right after it: the costmap's
@@ -208,6 +209,7 @@ class StereonetNode : public hobot::dnn_node::DnnNode {
   void ReadTemporalSettings();
   void ReadRectifySettings();
   hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr RectifyFrame(const hbm_img_msgs::msg::HbmMsg1080P::ConstSharedPtr& raw);
+  bool HasModelFrame(const StereonetNodeOutput& request) const;
   void FilterTemporal(const StereonetNodeOutput& request, int32_t* raw);
   void ReadRenderSettings();
   void PublishRender(const StereonetNodeOutput& request, const int32_t* raw);

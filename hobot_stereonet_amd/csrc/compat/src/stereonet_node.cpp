@@ -29,6 +29,7 @@
 #include "image_io.h"
 #include "jpeg_nv12.h"
 #include "jpeg_pool.h"
+#include "stage_files.h"
 
 namespace hobot {
 namespace stereonet {
@@ -197,63 +198,6 @@ void StereonetNode::ReadPointCloudSettings() {
                                            << " z " << c.z_min_m << ".." << c.z_max_m);
 }
 
-namespace {
-// rectify.load_calib's text form: one `key v v v...` per line, `#` comments, every key exactly once
-bool load_calib_file(const char* path, sn_stereo_calib* c, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct Key {
-    const char* name;
-    int count;
-    double* dst;
-  };
-  double size[2] = {0, 0}, kl[4] = {}, kr[4] = {}, proj[4] = {};
-  const Key keys[] = {{"size", 2, size},          {"left.K", 4, kl},           {"left.D", 5, c->left.d},
-                      {"left.R", 9, c->left.R},   {"right.K", 4, kr},          {"right.D", 5, c->right.d},
-                      {"right.R", 9, c->right.R}, {"P", 4, proj},              {"baseline_mm", 1, &c->baseline_mm}};
-  bool seen[9] = {};
-  std::string line;
-  for (int no = 1; std::getline(in, line); ++no) {
-    line = line.substr(0, line.find('#'));
-    std::istringstream ss(line);
-    std::string key;
-    if (!(ss >> key)) continue;
-    int k = 0;
-    while (k < 9 && key != keys[k].name) ++k;
-    std::vector<double> v;
-    for (std::string t; ss >> t;) {
-      char* end = nullptr;
-      v.push_back(strtod(t.c_str(), &end));
-      if (end == t.c_str() || *end) k = 9;
-    }
-    if (k == 9 || seen[k] || (int)v.size() != keys[k].count) {
-      *err = "line " + std::to_string(no) + " is not one of size, left.K/.D/.R, right.K/.D/.R, P, baseline_mm with its values";
-      return false;
-    }
-    seen[k] = true;
-    for (int i = 0; i < keys[k].count; ++i) keys[k].dst[i] = v[i];
-  }
-  for (int k = 0; k < 9; ++k)
-    if (!seen[k]) {
-      *err = std::string("has no `") + keys[k].name + "` line";
-      return false;
-    }
-  c->left.fx = kl[0], c->left.fy = kl[1], c->left.cx = kl[2], c->left.cy = kl[3];
-  c->right.fx = kr[0], c->right.fy = kr[1], c->right.cx = kr[2], c->right.cy = kr[3];
-  c->pfx = proj[0], c->pfy = proj[1], c->pcx = proj[2], c->pcy = proj[3];
-  c->src_w = (int)size[0];
-  c->src_h = (int)size[1];
-  if (c->src_w != size[0] || c->src_h != size[1]) {
-    *err = "size is not two integers";
-    return false;
-  }
-  return true;
-}
-}  // namespace
-
 // read and validated once here: a file sn_rectify_create would reject leaves the node as it is without the variable
 void StereonetNode::ReadRectifySettings() {
   const char* e = getenv("STEREONET_RECTIFY");
@@ -326,6 +270,13 @@ void StereonetNode::ReadTemporalSettings() {
                                                      << ", luma_delta " << p.luma_delta);
 }
 
+// whether the request carries a side-by-side NV12 frame of the model's size (the offline feeder's requests carry none)
+bool StereonetNode::HasModelFrame(const StereonetNodeOutput& request) const {
+  const auto& f = request.frame;
+  return f && (int)f->width == 2 * net_w_ && (int)f->height == net_h_ &&
+         f->data.size() >= (size_t)2 * net_w_ * (net_h_ + (net_h_ + 1) / 2);
+}
+
 // The request's int32 tensor, filtered in place as the next frame of the node's one stream.  DnnNode::CompletionLoop calls
 // PostProcess from one thread in submission order, and the synchronous path calls it inline, so the pushes arrive in frame
 // order.  With LUMA_DELTA > 0 the guide is the request's side-by-side frame (NV12, pitch 2W).  A request without a frame of
@@ -335,9 +286,7 @@ void StereonetNode::FilterTemporal(const StereonetNodeOutput& request, int32_t* 
   const auto& f = request.frame;
   const uint8_t* guide = nullptr;
   if (cfg_.temporal.luma_delta > 0) {
-    const bool guided = f && (int)f->width == 2 * net_w_ && (int)f->height == net_h_ &&
-                        f->data.size() >= (size_t)2 * net_w_ * (net_h_ + (net_h_ + 1) / 2);
-    if (!guided) {
+    if (!HasModelFrame(request)) {
       if (!temporal_unguided_logged_)
         RCLCPP_WARN(kLog, "temporal filter: no side-by-side frame of the model's size for this request, map not filtered");
       temporal_unguided_logged_ = true;
@@ -384,8 +333,7 @@ void StereonetNode::ReadRenderSettings() {
 // feeder's) has no left eye in NV12: nothing is published for it.
 void StereonetNode::PublishRender(const StereonetNodeOutput& request, const int32_t* raw) {
   const auto& f = request.frame;
-  if (!(f && (int)f->width == 2 * net_w_ && (int)f->height == net_h_ &&
-        f->data.size() >= (size_t)2 * net_w_ * (net_h_ + (net_h_ + 1) / 2))) {
+  if (!HasModelFrame(request)) {
     if (!render_no_frame_logged_.exchange(true))
       RCLCPP_WARN(kLog, "depth view: no side-by-side frame of the model's size for this request, nothing published");
     return;
@@ -414,8 +362,7 @@ void StereonetNode::PublishPointCloud(const StereonetNodeOutput& request, const 
   const sn_camera& cam = cfg_.camera;
   const int wo = (net_w_ + cam.step - 1) / cam.step, ho = (net_h_ + cam.step - 1) / cam.step;
   const auto& f = request.frame;
-  const bool colour = f && (int)f->width == 2 * net_w_ && (int)f->height == net_h_ &&
-                      f->data.size() >= (size_t)2 * net_w_ * (net_h_ + (net_h_ + 1) / 2);
+  const bool colour = HasModelFrame(request);
   if (!colour && !cloud_uncoloured_logged_.exchange(true))
     RCLCPP_WARN(kLog, "point cloud without colour: no side-by-side frame of the model's size for this request");
   sensor_msgs::msg::PointCloud2 msg;
@@ -454,85 +401,11 @@ void StereonetNode::PublishPointCloud(const StereonetNodeOutput& request, const 
   pointcloud_out_->publish(std::move(msg));
 }
 
-namespace {
-// obstacles.load_params' text form: one `key value...` per line, `#` comments, a key at most once; a key that is missing
-// keeps `p`'s value
-bool load_obstacle_file(const char* path, sn_obstacle_params* p, std::string* frame, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct FloatKey {
-    const char* name;
-    float* v;
-  } floats[] = {{"x_min_m", &p->x_min_m}, {"y_min_m", &p->y_min_m}, {"cell_m", &p->cell_m}, {"z_floor_m", &p->z_floor_m},
-                {"z_lo_m", &p->z_lo_m}, {"z_hi_m", &p->z_hi_m}, {"angle_min_rad", &p->angle_min_rad},
-                {"angle_increment_rad", &p->angle_increment_rad}, {"range_min_m", &p->range_min_m}, {"range_max_m", &p->range_max_m}};
-  struct IntKey {
-    const char* name;
-    int* v;
-  } ints[] = {{"gw", &p->gw}, {"gh", &p->gh}, {"min_obstacle_hits", &p->min_obstacle_hits}, {"min_ground_hits", &p->min_ground_hits},
-              {"beams", &p->beams}};
-  std::vector<std::string> seen;
-  std::string text;
-  for (int no = 1; std::getline(in, text); ++no) {
-    std::istringstream words(text.substr(0, text.find('#')));
-    std::string key, w;
-    if (!(words >> key)) continue;
-    std::vector<std::string> vals;
-    while (words >> w) vals.push_back(w);
-    const std::string at = "line " + std::to_string(no) + ": ";
-    for (const std::string& k : seen)
-      if (k == key) {
-        *err = at + key + " twice";
-        return false;
-      }
-    seen.push_back(key);
-    auto number = [&](const std::string& t, double* out) {
-      char* end = nullptr;
-      *out = strtod(t.c_str(), &end);
-      return end != t.c_str() && !*end;
-    };
-    bool known = false, ok = true;
-    double d = 0;
-    if (key == "frame") {
-      known = true, ok = vals.size() == 1;
-      if (ok) *frame = vals[0];
-    } else if (key == "base_from_cam") {
-      known = true, ok = vals.size() == 12;
-      for (int i = 0; ok && i < 12; ++i) {
-        ok = number(vals[i], &d);
-        p->base_from_cam[i] = (float)d;
-      }
-    }
-    for (const FloatKey& f : floats)
-      if (key == f.name) {
-        known = true, ok = vals.size() == 1 && number(vals[0], &d);
-        *f.v = (float)d;
-      }
-    for (const IntKey& f : ints)
-      if (key == f.name) {
-        known = true, ok = vals.size() == 1 && number(vals[0], &d) && d == (double)(int)d;
-        *f.v = (int)d;
-      }
-    if (!known || !ok) {
-      *err = at + (known ? "wrong values for " : "unknown key ") + key;
-      return false;
-    }
-  }
-  return true;
-}
-}  // namespace
-
 void StereonetNode::ReadObstacleSettings() {
   const char* e = getenv("STEREONET_OBSTACLES");
   if (!e || !*e) return;
-  // obstacles.ObstacleParams' defaults: a 10 m x 10 m grid of 0.1 m cells ahead of a level camera, no scan
   sn_obstacle_params& p = cfg_.obstacle_params;
-  p = sn_obstacle_params{};
-  p.y_min_m = -5.f, p.cell_m = 0.1f, p.gw = p.gh = 100;
-  p.z_floor_m = -0.15f, p.z_lo_m = 0.1f, p.z_hi_m = 1.5f, p.min_obstacle_hits = p.min_ground_hits = 3;
+  p = default_obstacle_params();
   std::string bad;
   if (!load_obstacle_file(e, &p, &cfg_.obstacle_frame, &bad)) bad = std::string("STEREONET_OBSTACLES=") + e + ": " + bad;
   if (bad.empty() && cfg_.pointcloud_layout < 0) ReadCamera(&bad);      // the point cloud's camera, read once
@@ -611,71 +484,12 @@ void StereonetNode::PublishObstacles(const StereonetNodeOutput& request, const i
   if (costmap_) PublishCostmap(request, p.gw ? occ_kept.data() : nullptr, p.beams ? ranges_kept.data() : nullptr);
 }
 
-namespace {
-// costmap.load_params' text form, as load_obstacle_file
-bool load_costmap_file(const char* path, sn_costmap_params* p, std::string* frame, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct FloatKey {
-    const char* name;
-    float* v;
-  } floats[] = {{"clear_margin_m", &p->clear_margin_m}, {"clear_min_m", &p->clear_min_m}, {"clear_max_m", &p->clear_max_m}};
-  struct IntKey {
-    const char* name;
-    int* v;
-  } ints[] = {{"mw", &p->mw}, {"mh", &p->mh}, {"l_hit", &p->l_hit}, {"l_miss", &p->l_miss}, {"l_min", &p->l_min}, {"l_max", &p->l_max}};
-  std::vector<std::string> seen;
-  std::string text;
-  for (int no = 1; std::getline(in, text); ++no) {
-    std::istringstream words(text.substr(0, text.find('#')));
-    std::string key, w;
-    if (!(words >> key)) continue;
-    std::vector<std::string> vals;
-    while (words >> w) vals.push_back(w);
-    const std::string at = "line " + std::to_string(no) + ": ";
-    for (const std::string& k : seen)
-      if (k == key) {
-        *err = at + key + " twice";
-        return false;
-      }
-    seen.push_back(key);
-    char* end = nullptr;
-    const double d = vals.size() == 1 ? strtod(vals[0].c_str(), &end) : 0.0;
-    const bool number = vals.size() == 1 && end != vals[0].c_str() && !*end;
-    bool known = false, ok = true;
-    if (key == "frame") {
-      known = true, ok = vals.size() == 1;
-      if (ok) *frame = vals[0];
-    }
-    for (const FloatKey& f : floats)
-      if (key == f.name) {
-        known = true, ok = number;
-        *f.v = (float)d;
-      }
-    for (const IntKey& f : ints)
-      if (key == f.name) {
-        known = true, ok = number && d == (double)(int)d;
-        *f.v = (int)d;
-      }
-    if (!known || !ok) {
-      *err = at + (known ? "wrong values for " : "unknown key ") + key;
-      return false;
-    }
-  }
-  return true;
-}
-}  // namespace
-
 // parsed and validated once here: what sn_costmap_create would refuse turns the stage off instead of failing every frame
 void StereonetNode::ReadCostmapSettings() {
   const char* e = getenv("STEREONET_COSTMAP");
   if (!e || !*e) return;
-  // costmap.CostmapParams' defaults: a 200 x 200 window, five hits to the upper clamp and five misses to the lower
   sn_costmap_params& p = cfg_.costmap_params;
-  p = sn_costmap_params{200, 200, 85, 40, -200, 350, 0.1f, 0.f, 0.f};
+  p = default_costmap_params();
   std::string bad;
   if (!cfg_.obstacles) bad = std::string("STEREONET_COSTMAP=") + e + " requires STEREONET_OBSTACLES";
   else if (!load_costmap_file(e, &p, &cfg_.costmap_frame, &bad)) bad = std::string("STEREONET_COSTMAP=") + e + ": " + bad;
@@ -727,91 +541,12 @@ void StereonetNode::PublishCostmap(const StereonetNodeOutput& request, const int
   if (feeds) PublishInflated(inflate_src);
 }
 
-namespace {
-// elevation.load_params' text form, as load_costmap_file; `feed_inflate` is the node's own key
-bool load_elevation_file(const char* path, sn_elevation_params* p, std::string* frame, bool* feed_inflate, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct FloatKey {
-    const char* name;
-    float* v;
-  } floats[] = {{"cell_m", &p->cell_m}, {"z_min_m", &p->z_min_m}, {"z_max_m", &p->z_max_m}, {"range_max_m", &p->range_max_m}};
-  int feed = 0;
-  struct IntKey {
-    const char* name;
-    int* v;
-  } ints[] = {{"mw", &p->mw},         {"mh", &p->mh},   {"min_points", &p->min_points}, {"alpha", &p->alpha}, {"max_step_mm", &p->max_step_mm},
-              {"radius", &p->radius}, {"flags", &p->flags}, {"feed_inflate", &feed}};
-  std::vector<std::string> seen;
-  std::string text;
-  for (int no = 1; std::getline(in, text); ++no) {
-    std::istringstream words(text.substr(0, text.find('#')));
-    std::string key, w;
-    if (!(words >> key)) continue;
-    std::vector<std::string> vals;
-    while (words >> w) vals.push_back(w);
-    const std::string at = "line " + std::to_string(no) + ": ";
-    for (const std::string& k : seen)
-      if (k == key) {
-        *err = at + key + " twice";
-        return false;
-      }
-    seen.push_back(key);
-    auto number_of = [](const std::string& v, double* d) {
-      char* end = nullptr;
-      *d = strtod(v.c_str(), &end);
-      return end != v.c_str() && !*end;
-    };
-    double d = 0.0;
-    const bool number = vals.size() == 1 && number_of(vals[0], &d);
-    bool known = false, ok = true;
-    if (key == "frame") {
-      known = true, ok = vals.size() == 1;
-      if (ok) *frame = vals[0];
-    }
-    if (key == "base_from_cam") {
-      known = true, ok = vals.size() == 12;
-      for (size_t i = 0; ok && i < 12; ++i) {
-        ok = number_of(vals[i], &d);
-        p->base_from_cam[i] = (float)d;
-      }
-    }
-    for (const FloatKey& f : floats)
-      if (key == f.name) {
-        known = true, ok = number;
-        *f.v = (float)d;
-      }
-    for (const IntKey& f : ints)
-      if (key == f.name) {
-        known = true, ok = number && d == (double)(int)d;
-        *f.v = (int)d;
-      }
-    if (!known || !ok) {
-      *err = at + (known ? "wrong values for " : "unknown key ") + key;
-      return false;
-    }
-  }
-  if (feed != 0 && feed != 1) {
-    *err = "feed_inflate must be 0 or 1";
-    return false;
-  }
-  *feed_inflate = feed == 1;
-  return true;
-}
-}  // namespace
-
 // parsed and validated once here: what sn_elevation_create would refuse turns the stage off instead of failing every frame
 void StereonetNode::ReadElevationSettings() {
   const char* e = getenv("STEREONET_ELEVATION");
   if (!e || !*e) return;
-  // elevation.ElevationParams' defaults
   sn_elevation_params& p = cfg_.elevation_params;
-  p = sn_elevation_params{};
-  p.mw = p.mh = 200, p.cell_m = 0.1f, p.z_min_m = -1.f, p.z_max_m = 1.5f, p.range_max_m = 6.f;
-  p.min_points = 3, p.alpha = 128, p.max_step_mm = 60, p.radius = 1;
+  p = default_elevation_params();
   std::string bad;
   bool feed = false;
   if (!load_elevation_file(e, &p, &cfg_.elevation_frame, &feed, &bad)) bad = std::string("STEREONET_ELEVATION=") + e + ": " + bad;
@@ -862,68 +597,13 @@ void StereonetNode::PublishElevation(const StereonetNodeOutput& request, const i
   if (feeds) PublishInflated(inflate_src);
 }
 
-namespace {
-// inflate.load_params' text form, as load_costmap_file
-bool load_inflate_file(const char* path, sn_inflate_params* p, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct FloatKey {
-    const char* name;
-    float* v;
-  } floats[] = {{"cell_m", &p->cell_m}, {"inscribed_radius_m", &p->inscribed_radius_m}, {"inflation_radius_m", &p->inflation_radius_m},
-                {"cost_scaling", &p->cost_scaling}};
-  struct IntKey {
-    const char* name;
-    int* v;
-  } ints[] = {{"lethal_min", &p->lethal_min}, {"flags", &p->flags}};
-  std::vector<std::string> seen;
-  std::string text;
-  for (int no = 1; std::getline(in, text); ++no) {
-    std::istringstream words(text.substr(0, text.find('#')));
-    std::string key, w;
-    if (!(words >> key)) continue;
-    std::vector<std::string> vals;
-    while (words >> w) vals.push_back(w);
-    const std::string at = "line " + std::to_string(no) + ": ";
-    for (const std::string& k : seen)
-      if (k == key) {
-        *err = at + key + " twice";
-        return false;
-      }
-    seen.push_back(key);
-    char* end = nullptr;
-    const double d = vals.size() == 1 ? strtod(vals[0].c_str(), &end) : 0.0;
-    const bool number = vals.size() == 1 && end != vals[0].c_str() && !*end;
-    bool known = false, ok = true;
-    for (const FloatKey& f : floats)
-      if (key == f.name) {
-        known = true, ok = number;
-        *f.v = (float)d;
-      }
-    for (const IntKey& f : ints)
-      if (key == f.name) {
-        known = true, ok = number && d >= -1e9 && d <= 1e9 && d == (double)(int)d;      // the range first: the cast of a larger double is undefined
-        if (ok) *f.v = (int)d;
-      }
-    if (!known || !ok) {
-      *err = at + (known ? "wrong values for " : "unknown key ") + key;
-      return false;
-    }
-  }
-  return true;
-}
-}  // namespace
-
 // parsed and validated once here: what sn_inflate_grid would refuse turns the stage off instead of failing every frame
 void StereonetNode::ReadInflateSettings() {
   const char* e = getenv("STEREONET_INFLATE");
   if (!e || !*e) return;
-  // inflate.InflateParams' defaults; the cell is that of the grid the stage follows, whatever the file says
+  // the cell is that of the grid the stage follows, whatever the file says
   sn_inflate_params& p = cfg_.inflate_params;
-  p = sn_inflate_params{0.05f, 0.2f, 0.4f, 10.f, 100, 0};
+  p = default_inflate_params();
   std::string bad;
   int R = 0;
   const bool from_elevation = elevation_ && cfg_.elevation_feeds_inflate;
@@ -963,62 +643,12 @@ void StereonetNode::PublishInflated(const nav_msgs::msg::OccupancyGrid& src) {
   if (cfg_.plan) PublishPlan(src, cost.data());
 }
 
-namespace {
-// navfn.load_params' text form: integers, one value a key; the tools' `goal x y` and `start x y` lines are read past
-bool load_plan_file(const char* path, sn_nav_params* p, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct IntKey {
-    const char* name;
-    int* v;
-  } ints[] = {{"neutral", &p->neutral},   {"lethal_cost", &p->lethal_cost}, {"unknown_cost", &p->unknown_cost},
-              {"flags", &p->flags},       {"max_rounds", &p->max_rounds},   {"max_path", &p->max_path}};
-  std::vector<std::string> seen;
-  std::string text;
-  for (int no = 1; std::getline(in, text); ++no) {
-    std::istringstream words(text.substr(0, text.find('#')));
-    std::string key, w;
-    if (!(words >> key)) continue;
-    std::vector<std::string> vals;
-    while (words >> w) vals.push_back(w);
-    const std::string at = "line " + std::to_string(no) + ": ";
-    for (const std::string& k : seen)
-      if (k == key) {
-        *err = at + key + " twice";
-        return false;
-      }
-    seen.push_back(key);
-    const bool cell = key == "goal" || key == "start";
-    bool known = cell, ok = vals.size() == (cell ? 2u : 1u);
-    for (const IntKey& f : ints) known = known || key == f.name;
-    for (const std::string& v : vals) {
-      char* end = nullptr;
-      const double d = strtod(v.c_str(), &end);
-      ok = ok && end != v.c_str() && !*end && d >= -1e9 && d <= 1e9 && d == (double)(int)d;      // the range first: the cast of a larger double is undefined
-      for (const IntKey& f : ints)
-        if (key == f.name) {
-          known = true;
-          if (ok) *f.v = (int)d;
-        }
-    }
-    if (!known || !ok) {
-      *err = at + (known ? "wrong values for " : "unknown key ") + key;
-      return false;
-    }
-  }
-  return true;
-}
-}  // namespace
-
 // parsed and validated once here: what sn_navfn would refuse turns the stage off instead of failing every frame
 void StereonetNode::ReadPlanSettings() {
   const char* e = getenv("STEREONET_PLAN");
   if (!e || !*e) return;
   sn_nav_params& p = cfg_.plan_params;
-  p = sn_nav_params{50, 253, 0, 0, 0, 4096};      // navfn.NavParams' defaults
+  p = default_plan_params();
   std::string bad;
   if (!cfg_.inflate) bad = std::string("STEREONET_PLAN=") + e + " requires STEREONET_INFLATE";
   else if (!load_plan_file(e, &p, &bad)) bad = std::string("STEREONET_PLAN=") + e + ": " + bad;
@@ -1089,77 +719,6 @@ void StereonetNode::PublishPlan(const nav_msgs::msg::OccupancyGrid& src, const u
 }
 
 namespace {
-// rollout.load_params' text form: one value a key, `point x y` once per footprint point, `acc acc_v acc_w dt`; the tools'
-// `pose x y yaw` line is read past
-bool load_rollout_file(const char* path, sn_rollout_params* p, std::vector<float>* footprint, double* acc, bool* has_acc, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct FloatKey {
-    const char* name;
-    float* v;
-  } floats[] = {{"cell_m", &p->cell_m}, {"v_min", &p->v_min}, {"v_max", &p->v_max}, {"w_min", &p->w_min}, {"w_max", &p->w_max}, {"sim_time_s", &p->sim_time_s}};
-  struct IntKey {
-    const char* name;
-    int* v;
-  } ints[] = {{"nv", &p->nv},       {"nw", &p->nw},         {"steps", &p->steps},   {"lethal_cost", &p->lethal_cost}, {"centre_lethal_cost", &p->centre_lethal_cost},
-              {"unknown_cost", &p->unknown_cost}, {"flags", &p->flags}, {"w_goal", &p->w_goal}, {"w_occ", &p->w_occ}};
-  std::vector<std::string> seen;
-  std::string text;
-  for (int no = 1; std::getline(in, text); ++no) {
-    std::istringstream words(text.substr(0, text.find('#')));
-    std::string key, w;
-    if (!(words >> key)) continue;
-    std::vector<double> vals;
-    bool ok = true;
-    while (words >> w) {
-      char* end = nullptr;
-      vals.push_back(strtod(w.c_str(), &end));
-      ok = ok && end != w.c_str() && !*end;
-    }
-    const std::string at = "line " + std::to_string(no) + ": ";
-    if (key != "point") {
-      for (const std::string& k : seen)
-        if (k == key) {
-          *err = at + key + " twice";
-          return false;
-        }
-      seen.push_back(key);
-    }
-    bool known = true;
-    if (key == "point") {
-      ok = ok && vals.size() == 2;
-      if (ok) footprint->push_back((float)vals[0]), footprint->push_back((float)vals[1]);
-    } else if (key == "pose") {
-      ok = ok && vals.size() == 3;
-    } else if (key == "acc") {
-      ok = ok && vals.size() == 3;
-      if (ok) acc[0] = vals[0], acc[1] = vals[1], acc[2] = vals[2], *has_acc = true;
-    } else {
-      known = false;
-      ok = ok && vals.size() == 1;
-      for (const FloatKey& f : floats)
-        if (key == f.name) {
-          known = true;
-          if (ok) *f.v = (float)vals[0];
-        }
-      for (const IntKey& f : ints)
-        if (key == f.name) {
-          known = true;
-          ok = ok && vals[0] >= -1e9 && vals[0] <= 1e9 && vals[0] == (double)(int)vals[0];
-          if (ok) *f.v = (int)vals[0];
-        }
-    }
-    if (!known || !ok) {
-      *err = at + (known ? "wrong values for " : "unknown key ") + key;
-      return false;
-    }
-  }
-  return true;
-}
-
 // one axis of rollout.window_from_velocity: the lattice samples within `reach` of `at`, else the one nearest to it (the lower
 // on a tie); lattice(i) is sn_rollout_velocity's
 void window_axis(const sn_rollout_params& p, bool turn, double at, double reach, int32_t* lo, int32_t* hi) {
@@ -1185,7 +744,7 @@ void StereonetNode::ReadRolloutSettings() {
   const char* e = getenv("STEREONET_ROLLOUT");
   if (!e || !*e) return;
   sn_rollout_params& p = cfg_.rollout_params;
-  p = sn_rollout_params{0.05f, 0.f, 0.5f, 11, -1.f, 1.f, 21, 1.5f, 15, 254, 253, 0, 0, 1, 1};      // rollout.RolloutParams' defaults
+  p = default_rollout_params();
   std::string bad;
   const double* a = cfg_.rollout_acc;
   if (!cfg_.plan) bad = std::string("STEREONET_ROLLOUT=") + e + " requires STEREONET_PLAN";
@@ -1267,83 +826,11 @@ void StereonetNode::PublishRollout(const nav_msgs::msg::OccupancyGrid& src, cons
   local_plan_out_->publish(std::move(arc));
 }
 
-namespace {
-// ground.load_params' text form, as load_obstacle_file
-bool load_ground_file(const char* path, sn_ground_params* p, float* log_delta, std::string* err) {
-  std::ifstream in(path);
-  if (!in.good()) {
-    *err = "cannot be opened";
-    return false;
-  }
-  struct FloatKey {
-    const char* name;
-    float* v;
-  } floats[] = {{"tol_px", &p->tol_px}, {"max_tilt_rad", &p->max_tilt_rad}, {"height_min_m", &p->height_min_m},
-                {"height_max_m", &p->height_max_m}, {"log_delta", log_delta}};
-  struct IntKey {
-    const char* name;
-    int* v;
-  } ints[] = {{"roi_x", &p->roi_x}, {"roi_y", &p->roi_y}, {"roi_w", &p->roi_w}, {"roi_h", &p->roi_h}, {"hypotheses", &p->hypotheses},
-              {"min_area", &p->min_area}, {"min_inliers", &p->min_inliers}, {"refits", &p->refits}};
-  std::vector<std::string> seen;
-  std::string text;
-  for (int no = 1; std::getline(in, text); ++no) {
-    std::istringstream words(text.substr(0, text.find('#')));
-    std::string key, w;
-    if (!(words >> key)) continue;
-    std::vector<std::string> vals;
-    while (words >> w) vals.push_back(w);
-    const std::string at = "line " + std::to_string(no) + ": ";
-    for (const std::string& k : seen)
-      if (k == key) {
-        *err = at + key + " twice";
-        return false;
-      }
-    seen.push_back(key);
-    auto number = [&](const std::string& t, double* out) {
-      char* end = nullptr;
-      *out = strtod(t.c_str(), &end);
-      return end != t.c_str() && !*end;
-    };
-    bool known = false, ok = true;
-    double d = 0;
-    if (key == "base_from_cam") {
-      known = true, ok = vals.size() == 12;
-      for (int i = 0; ok && i < 12; ++i) {
-        ok = number(vals[i], &d);
-        p->base_from_cam[i] = (float)d;
-      }
-    } else if (key == "seed") {
-      known = true, ok = vals.size() == 1 && number(vals[0], &d) && d >= 0 && d <= 4294967295.0 && d == (double)(uint32_t)d;
-      p->seed = (uint32_t)d;
-    }
-    for (const FloatKey& f : floats)
-      if (key == f.name) {
-        known = true, ok = vals.size() == 1 && number(vals[0], &d);
-        *f.v = (float)d;
-      }
-    for (const IntKey& f : ints)
-      if (key == f.name) {
-        known = true, ok = vals.size() == 1 && number(vals[0], &d) && d >= -2147483648.0 && d <= 2147483647.0 && d == (double)(int)d;
-        *f.v = (int)d;
-      }
-    if (!known || !ok) {
-      *err = at + (known ? "wrong values for " : "unknown key ") + key;
-      return false;
-    }
-  }
-  return true;
-}
-}  // namespace
-
 void StereonetNode::ReadGroundSettings() {
   const char* e = getenv("STEREONET_GROUND");
   if (!e || !*e) return;
-  // ground.GroundParams' defaults: the lower half of the image, 256 hypotheses, two refits, a level prior
   sn_ground_params& p = cfg_.ground_params;
-  p = sn_ground_params{};
-  p.hypotheses = 256, p.seed = 1, p.min_area = 64, p.min_inliers = 100, p.refits = 2;
-  p.tol_px = 0.1f, p.max_tilt_rad = 0.5f, p.height_min_m = 0.1f, p.height_max_m = 3.0f;
+  p = default_ground_params();
   std::string bad;
   if (!load_ground_file(e, &p, &cfg_.ground_log_delta, &bad)) bad = std::string("STEREONET_GROUND=") + e + ": " + bad;
   if (bad.empty() && cfg_.pointcloud_layout < 0 && !cfg_.obstacles) ReadCamera(&bad);      // the point cloud's camera, read once

@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import obstacles, pointcloud, spec, torus
+from . import obstacles, paramfile, pointcloud, spec, torus
 
 MAX_WINDOW = 4096                   # mw, mh
 UNKNOWN = -32768                    # hi and lo of a cell nobody has observed
@@ -353,39 +353,19 @@ def synthetic_clip(p: ElevationParams, w: int, h: int, cam: pointcloud.Camera, n
 
 
 # ---- the parameter file: one `key value` per line, `#` comments, as obstacles.py's ------------------------------------------------
+_FILE = paramfile.spec(_FLOATS, _INTS + ("feed_inflate",), base_from_cam=paramfile.Key(12), frame=paramfile.Key(1, str))
+
+
 def save_params(path: str, p: ElevationParams) -> None:
     """Floats as repr, so load_params(save_params(p)) == p exactly."""
-    with open(path, "w") as f:
-        f.write("# rolling elevation map: window in cells of cell_m, heights in metres and millimetres, base_from_cam row-major 3x4\n")
-        for k in _INTS:
-            f.write(f"{k} {int(getattr(p, k))}\n")
-        for k in _FLOATS:
-            f.write(f"{k} {float(getattr(p, k))!r}\n")
-        f.write("base_from_cam " + " ".join(repr(float(v)) for v in p.base_from_cam) + "\n")
-        f.write(f"frame {p.frame}\n")
-        f.write(f"feed_inflate {int(p.feed_inflate)}\n")
+    paramfile.write(path, "rolling elevation map: window in cells of cell_m, heights in metres and millimetres, base_from_cam row-major 3x4",
+                    _FILE, [(k, getattr(p, k)) for k in _INTS + _FLOATS + ("base_from_cam", "frame", "feed_inflate")])
 
 
 def load_params(path: str) -> ElevationParams:
     """A key that is missing keeps ElevationParams' default; an unknown or repeated key, or a wrong number of values, is an
     error."""
-    got = {}
-    with open(path) as f:
-        for no, text in enumerate(f, 1):
-            words = text.split("#", 1)[0].split()
-            if not words:
-                continue
-            key, vals = words[0], words[1:]
-            if key not in _FLOATS + _INTS + ("frame", "base_from_cam", "feed_inflate"):
-                raise ValueError(f"{path}:{no}: unknown key {key!r}")
-            want = 12 if key == "base_from_cam" else 1
-            if key in got or len(vals) != want:
-                raise ValueError(f"{path}:{no}: expected one `{key}` line with {want} value{'s' if want > 1 else ''}")
-            try:
-                got[key] = (vals[0] if key == "frame" else int(vals[0]) if key in _INTS + ("feed_inflate",) else
-                            tuple(float(v) for v in vals) if key == "base_from_cam" else float(vals[0]))
-            except ValueError:
-                raise ValueError(f"{path}:{no}: not a number in {text.strip()!r}") from None
+    got = paramfile.read(path, _FILE)
     if got.get("feed_inflate", 0) not in (0, 1):
         raise ValueError(f"{path}: feed_inflate must be 0 or 1")
     return ElevationParams(**got)

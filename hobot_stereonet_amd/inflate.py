@@ -15,6 +15,8 @@ from typing import Optional
 
 import numpy as np
 
+from . import paramfile
+
 MAX_R = 64                          # SN_INFLATE_MAX_R
 MAX_CELLS = 4096                    # gw, gh
 UNKNOWN = 1                         # SN_INFLATE_UNKNOWN
@@ -228,35 +230,18 @@ def boundary_scene():
 
 
 # ---- the parameter file: one `key value` per line, `#` comments, as costmap.py's ---------------------------------------------------
+_FILE = paramfile.spec(_FLOATS, _INTS)
+
+
 def save_params(path: str, p: InflateParams) -> None:
     """Floats as repr, so load_params(save_params(p)) == p exactly."""
-    with open(path, "w") as f:
-        f.write("# inflation by the robot's radius: metres; flags 1 = an unknown cell takes any cost > 0; the tools and the node\n"
-                "# take cell_m from the grid they inflate\n")
-        for k in _FLOATS:
-            f.write(f"{k} {float(getattr(p, k))!r}\n")
-        for k in _INTS:
-            f.write(f"{k} {int(getattr(p, k))}\n")
+    paramfile.write(path, "inflation by the robot's radius: metres; flags 1 = an unknown cell takes any cost > 0; the tools and the node\n"
+                    "# take cell_m from the grid they inflate", _FILE, [(k, getattr(p, k)) for k in _FLOATS + _INTS])
 
 
 def load_params(path: str) -> InflateParams:
     """A key that is missing keeps InflateParams' default; an unknown or repeated key, or a wrong number of values, is an error."""
-    got = {}
-    with open(path) as f:
-        for no, text in enumerate(f, 1):
-            words = text.split("#", 1)[0].split()
-            if not words:
-                continue
-            key, vals = words[0], words[1:]
-            if key not in _FLOATS + _INTS:
-                raise ValueError(f"{path}:{no}: unknown key {key!r}")
-            if key in got or len(vals) != 1:
-                raise ValueError(f"{path}:{no}: expected one `{key}` line with 1 value")
-            try:
-                got[key] = int(vals[0]) if key in _INTS else float(vals[0])
-            except ValueError:
-                raise ValueError(f"{path}:{no}: not a number in {text.strip()!r}") from None
-    return InflateParams(**got)
+    return InflateParams(**paramfile.read(path, _FILE))
 
 
 # ---- what `filelist --inflate` writes ---------------------------------------------------------------------------------------------

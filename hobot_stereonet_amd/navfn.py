@@ -15,6 +15,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from . import paramfile
+
 TILE_W, TILE_H = 32, 32             # SN_NAV_TILE_W, SN_NAV_TILE_H: the tile of k_nav_relax
 MAX_SIDE = 4096                     # gw, gh
 MAX_AREA = 1 << 20                  # SN_NAV_MAX_CELLS: gw * gh
@@ -223,37 +225,17 @@ def path_cost(path_cells, cost, p: NavParams) -> int:
 
 
 # ---- the parameter file: one `key value` per line, `#` comments, as inflate.py's; goal and start take two values -----------------
+_FILE = paramfile.spec(ints=_INTS, **{k: paramfile.Key(2, int) for k in _CELLS})
+
+
 def save_params(path: str, p: NavParams) -> None:
-    with open(path, "w") as f:
-        f.write("# navigation function: costs 0..255; flags 1 = unknown cells are passable at unknown_cost; goal and start in cells (x y)\n")
-        for k in _INTS:
-            f.write(f"{k} {int(getattr(p, k))}\n")
-        for k in _CELLS:
-            v = getattr(p, k)
-            if v is not None:
-                f.write(f"{k} {int(v[0])} {int(v[1])}\n")
+    paramfile.write(path, "navigation function: costs 0..255; flags 1 = unknown cells are passable at unknown_cost; goal and start in cells (x y)",
+                    _FILE, [(k, getattr(p, k)) for k in _INTS + _CELLS if getattr(p, k) is not None])
 
 
 def load_params(path: str) -> NavParams:
     """A key that is missing keeps NavParams' default; an unknown or repeated key, or a wrong number of values, is an error."""
-    got = {}
-    with open(path) as f:
-        for no, text in enumerate(f, 1):
-            words = text.split("#", 1)[0].split()
-            if not words:
-                continue
-            key, vals = words[0], words[1:]
-            if key not in _INTS + _CELLS:
-                raise ValueError(f"{path}:{no}: unknown key {key!r}")
-            want = 2 if key in _CELLS else 1
-            if key in got or len(vals) != want:
-                raise ValueError(f"{path}:{no}: expected one `{key}` line with {want} value{'s' if want > 1 else ''}")
-            try:
-                nums = [int(v) for v in vals]
-            except ValueError:
-                raise ValueError(f"{path}:{no}: not an integer in {text.strip()!r}") from None
-            got[key] = tuple(nums) if key in _CELLS else nums[0]
-    return NavParams(**got)
+    return NavParams(**paramfile.read(path, _FILE))
 
 
 # ---- what `filelist --plan` writes -------------------------------------------------------------------------------------------------

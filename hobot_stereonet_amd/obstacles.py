@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import pointcloud, spec
+from . import paramfile, pointcloud, spec
 
 MAX_CELLS = 4096                    # gw, gh
 MAX_BEAMS = 4096
@@ -173,38 +173,18 @@ def ground_and_wall(w: int, h: int, cam: pointcloud.Camera, cam_height_m: float,
 
 
 # ---- the parameter file: one `key value...` per line, `#` comments, as the calibration file ------------------------------------
+_FILE = paramfile.spec(_FLOATS, _INTS, base_from_cam=paramfile.Key(12), frame=paramfile.Key(1, str))
+
+
 def save_params(path: str, p: ObstacleParams) -> None:
     """Floats as repr, so load_params(save_params(p)) == p exactly."""
-    with open(path, "w") as f:
-        f.write("# obstacle grid and laser scan: base_from_cam = row-major 3x4 [R|t] (all zero: level forward mount), metres, radians\n")
-        f.write("base_from_cam " + " ".join(repr(float(v)) for v in p.base_from_cam) + "\n")
-        for k in _FLOATS:
-            f.write(f"{k} {float(getattr(p, k))!r}\n")
-        for k in _INTS:
-            f.write(f"{k} {int(getattr(p, k))}\n")
-        f.write(f"frame {p.frame}\n")
+    paramfile.write(path, "obstacle grid and laser scan: base_from_cam = row-major 3x4 [R|t] (all zero: level forward mount), metres, radians",
+                    _FILE, [(k, getattr(p, k)) for k in ("base_from_cam",) + _FLOATS + _INTS + ("frame",)])
 
 
 def load_params(path: str) -> ObstacleParams:
     """A key that is missing keeps ObstacleParams' default; an unknown or repeated key, or a wrong number of values, is an error."""
-    got = {}
-    with open(path) as f:
-        for no, text in enumerate(f, 1):
-            words = text.split("#", 1)[0].split()
-            if not words:
-                continue
-            key, vals = words[0], words[1:]
-            want = 12 if key == "base_from_cam" else 1
-            if key not in _FLOATS + _INTS + ("base_from_cam", "frame"):
-                raise ValueError(f"{path}:{no}: unknown key {key!r}")
-            if key in got or len(vals) != want:
-                raise ValueError(f"{path}:{no}: expected one `{key}` line with {want} value{'s' if want > 1 else ''}")
-            try:
-                got[key] = (tuple(float(v) for v in vals) if key == "base_from_cam" else vals[0] if key == "frame"
-                            else int(vals[0]) if key in _INTS else float(vals[0]))
-            except ValueError:
-                raise ValueError(f"{path}:{no}: not a number in {text.strip()!r}") from None
-    return ObstacleParams(**got)
+    return ObstacleParams(**paramfile.read(path, _FILE))
 
 
 # ---- what `filelist --obstacles` writes ------------------------------------------------------------------------------------------

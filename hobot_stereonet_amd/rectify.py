@@ -12,6 +12,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from . import paramfile
+
 SENTINEL = -2 ** 31
 KEYS = ("size", "left.K", "left.D", "left.R", "right.K", "right.D", "right.R", "P", "baseline_mm")
 IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
@@ -225,42 +227,20 @@ def nonvacuity(m: np.ndarray, sw: int, sh: int) -> dict:
 
 
 # ---- calibration files ------------------------------------------------------------------------------------------------------
+_FILE = {k: paramfile.Key(n, int if k == "size" else float) for k, n in zip(KEYS, (2, 4, 5, 9, 4, 5, 9, 4, 1))}
+
+
 def save_calib(path: str, c: Calib) -> None:
     """One `key v v v...` per line, `#` comments; doubles as repr, so load_calib(save_calib(c)) == c exactly."""
-    def line(key, vals):
-        return key + " " + " ".join(repr(float(v)) if not isinstance(v, int) else str(v) for v in vals) + "\n"
-    with open(path, "w") as f:
-        f.write("# stereo calibration: raw eye size, K = fx fy cx cy, D = k1 k2 p1 p2 k3, R row-major, P = pfx pfy pcx pcy\n")
-        f.write(line("size", (int(c.src_w), int(c.src_h))))
-        for name, e in (("left", c.left), ("right", c.right)):
-            f.write(line(name + ".K", (e.fx, e.fy, e.cx, e.cy)))
-            f.write(line(name + ".D", e.d))
-            f.write(line(name + ".R", e.R))
-        f.write(line("P", (c.pfx, c.pfy, c.pcx, c.pcy)))
-        f.write(line("baseline_mm", (c.baseline_mm,)))
+    eyes = [(name + k, v) for name, e in (("left", c.left), ("right", c.right)) for k, v in ((".K", (e.fx, e.fy, e.cx, e.cy)), (".D", e.d), (".R", e.R))]
+    paramfile.write(path, "stereo calibration: raw eye size, K = fx fy cx cy, D = k1 k2 p1 p2 k3, R row-major, P = pfx pfy pcx pcy", _FILE,
+                    [("size", (c.src_w, c.src_h))] + eyes + [("P", (c.pfx, c.pfy, c.pcx, c.pcy)), ("baseline_mm", c.baseline_mm)])
 
 
 def load_calib(path: str) -> Calib:
-    want = {"size": 2, "left.K": 4, "left.D": 5, "left.R": 9, "right.K": 4, "right.D": 5, "right.R": 9, "P": 4, "baseline_mm": 1}
-    got = {}
-    with open(path) as f:
-        for no, text in enumerate(f, 1):
-            words = text.split("#", 1)[0].split()
-            if not words:
-                continue
-            key, vals = words[0], words[1:]
-            if key not in want or key in got or len(vals) != want[key]:
-                raise ValueError(f"{path}:{no}: expected one `{key}` line with {want.get(key, '?')} values" if key in want
-                                 else f"{path}:{no}: unknown key {key!r}")
-            try:
-                got[key] = [int(v) for v in vals] if key == "size" else [float(v) for v in vals]
-            except ValueError:
-                raise ValueError(f"{path}:{no}: not a number in {text.strip()!r}") from None
-    missing = [k for k in KEYS if k not in got]
-    if missing:
-        raise ValueError(f"{path}: missing {', '.join(missing)}")
-    eyes = [Eye(*got[s + ".K"], tuple(got[s + ".D"]), tuple(got[s + ".R"])) for s in ("left", "right")]
-    return Calib(got["size"][0], got["size"][1], eyes[0], eyes[1], *got["P"], got["baseline_mm"][0])
+    got = paramfile.read(path, _FILE, required=True)
+    eyes = [Eye(*got[s + ".K"], got[s + ".D"], got[s + ".R"]) for s in ("left", "right")]
+    return Calib(*got["size"], *eyes, *got["P"], got["baseline_mm"])
 
 
 # ---- a calibration from extrinsics ----------------------------------------------------------------------------------------------

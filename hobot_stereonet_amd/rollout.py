@@ -15,6 +15,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import paramfile
+
 MAX_STEPS = 64                      # SN_ROLLOUT_MAX_STEPS
 MAX_POINTS = 64                     # SN_ROLLOUT_MAX_POINTS
 MAX_SIDE = 64                       # SN_ROLLOUT_MAX_SIDE: nv, nw
@@ -354,45 +356,22 @@ def window_from_velocity(p: RolloutParams, v: float, w: float, acc_v: float, acc
 
 # ---- the parameter file: one `key value` per line, `#` comments, as navfn.py's; `point x y` lines are the footprint, `pose x y yaw`
 # the tools' pose, `acc acc_v acc_w dt` the node's window ------------------------------------------------------------------------------------------------------------------------
+_FILE = paramfile.spec(_FLOATS, _INTS, point=paramfile.Key(2, float, repeat=True), pose=paramfile.Key(3), acc=paramfile.Key(3))
+
+
 def save_params(path: str, p: RolloutParams) -> None:
-    with open(path, "w") as f:
-        f.write("# trajectory rollout: velocities in m/s and rad/s; flags 1 = unknown cells are priced at unknown_cost; one `point x y`\n"
-                "# line per footprint point (metres, robot frame); pose x y yaw in the grid's frame; acc acc_v acc_w dt: the node's window\n")
-        for k in _FLOATS:
-            f.write(f"{k} {float(getattr(p, k))!r}\n")
-        for k in _INTS:
-            f.write(f"{k} {int(getattr(p, k))}\n")
-        for x, y in np.asarray(p.footprint, np.float64).reshape(-1, 2).tolist():
-            f.write(f"point {x!r} {y!r}\n")
-        for k in ("pose", "acc"):
-            if getattr(p, k) is not None:
-                f.write(k + " " + " ".join(repr(float(v)) for v in getattr(p, k)) + "\n")
+    paramfile.write(path, "trajectory rollout: velocities in m/s and rad/s; flags 1 = unknown cells are priced at unknown_cost; one `point x y`\n"
+                    "# line per footprint point (metres, robot frame); pose x y yaw in the grid's frame; acc acc_v acc_w dt: the node's window",
+                    _FILE, [(k, getattr(p, k)) for k in _FLOATS + _INTS] +
+                    [("point", xy) for xy in np.asarray(p.footprint, np.float64).reshape(-1, 2).tolist()] +
+                    [(k, getattr(p, k)) for k in ("pose", "acc") if getattr(p, k) is not None])
 
 
 def load_params(path: str) -> RolloutParams:
     """A key that is missing keeps RolloutParams' default; an unknown or repeated key (but `point`), or a wrong number of values,
     is an error."""
-    got, points = {}, []
-    with open(path) as f:
-        for no, text in enumerate(f, 1):
-            words = text.split("#", 1)[0].split()
-            if not words:
-                continue
-            key, vals = words[0], words[1:]
-            if key not in _FLOATS + _INTS + ("point", "pose", "acc"):
-                raise ValueError(f"{path}:{no}: unknown key {key!r}")
-            want = {"point": 2, "pose": 3, "acc": 3}.get(key, 1)
-            if (key != "point" and key in got) or len(vals) != want:
-                raise ValueError(f"{path}:{no}: expected one `{key}` line with {want} value{'s' if want > 1 else ''}")
-            try:
-                nums = [int(v) if key in _INTS else float(v) for v in vals]
-            except ValueError:
-                raise ValueError(f"{path}:{no}: not a number in {text.strip()!r}") from None
-            if key == "point":
-                points.append(tuple(nums))
-            else:
-                got[key] = tuple(nums) if key in ("pose", "acc") else nums[0]
-    return RolloutParams(footprint=tuple(points), **got)
+    got = paramfile.read(path, _FILE)
+    return RolloutParams(footprint=tuple(got.pop("point", ())), **got)
 
 
 # ---- what `filelist --rollout` writes ------------------------------------------------------------------------------------------------
