@@ -329,30 +329,23 @@ def load_library(path: Optional[str] = None):
     lib.sn_mgpu_ring_wait.argtypes = [vp, C.c_uint64, C.POINTER(ip)]
     lib.sn_mgpu_last_error.restype = C.c_char_p
     lib.sn_mgpu_last_error.argtypes = [vp]
-    lib.sn_dbg_conv2d.argtypes = [vp, fp, ip, ip, ip, fp, fp, ip, ip, ip, ip, fp, fp]
-    lib.sn_dbg_down0.argtypes = [vp, i8p, ip, ip, fp, fp, ip, fp]
+    # the parity hooks; tests/test_cabi.py holds every list to the parameter count of its prototype in the header
+    lib.sn_dbg_conv2d_n.argtypes = [vp, ip, fp, ip, ip, ip, fp, fp, ip, ip, ip, ip, ip, fp, fp]
+    lib.sn_dbg_conv3d.argtypes = [vp, fp, ip, ip, ip, fp, fp, ip, ip, fp]
+    lib.sn_dbg_down0_n.argtypes = [vp, ip, i8p, ip, ip, fp, fp, ip, fp]
     lib.sn_dbg_compose_down01.argtypes = [fp, fp, fp, fp, fp, fp]
     lib.sn_dbg_round_kernels_f16.argtypes = [fp, ip, fp]
-    lib.sn_dbg_down01.argtypes = [vp, i8p, ip, ip, fp, fp, fp, fp, fp]
-    lib.sn_dbg_refin.argtypes = [vp, fp, i8p, ip, ip, ip, fp, fp, ip, fp]
-    lib.sn_dbg_conv3d.argtypes = [vp, fp, ip, ip, ip, fp, fp, ip, fp]
-    lib.sn_dbg_ref_conv_f16.argtypes = [vp, fp, ip, ip, fp, fp, ip, ip, fp, fp]
-    lib.sn_dbg_ref_conv_f16x3.argtypes = [vp, fp, ip, ip, fp, fp, ip, ip, fp, fp]
-    lib.sn_dbg_ref_block_f16.argtypes = [vp, fp, ip, ip, fp, fp, fp, fp, ip, fp]
-    lib.sn_dbg_ref_block_f16x3.argtypes = [vp, fp, ip, ip, fp, fp, fp, fp, ip, ip, fp]
+    lib.sn_dbg_down01_n.argtypes = [vp, ip, i8p, ip, ip, fp, fp, fp, fp, fp]
+    lib.sn_dbg_refin_n.argtypes = [vp, ip, fp, i8p, ip, ip, ip, fp, fp, ip, fp]
+    lib.sn_dbg_ref_conv_f16_n.argtypes = [vp, ip, fp, ip, ip, fp, fp, ip, ip, ip, fp, fp]
+    lib.sn_dbg_ref_conv_f16x3_n.argtypes = [vp, ip, fp, ip, ip, fp, fp, ip, ip, fp, fp]
+    lib.sn_dbg_ref_block_f16_n.argtypes = [vp, ip, fp, ip, ip, fp, fp, fp, fp, ip, ip, fp]
+    lib.sn_dbg_ref_block_f16x3_n.argtypes = [vp, ip, fp, ip, ip, fp, fp, fp, fp, ip, ip, fp]
     lib.sn_dbg_ref_tail_f16.argtypes = [vp, ip, fp, ip, ip, fp, fp, fp, fp, fp, C.c_float, fp, ip, C.c_float, ip, ip, ip, fp, i32p]
     lib.sn_dbg_read.argtypes = [vp, C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.sn_dbg_set_grid_cus.argtypes = [vp, ip]
     lib.sn_dbg_last_launch.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
     lib.sn_dbg_slot_graphs.argtypes = [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
-    lib.sn_dbg_conv2d_n.argtypes = [vp, ip] + lib.sn_dbg_conv2d.argtypes[1:]
-    lib.sn_dbg_down0_n.argtypes = [vp, ip] + lib.sn_dbg_down0.argtypes[1:]
-    lib.sn_dbg_down01_n.argtypes = [vp, ip] + lib.sn_dbg_down01.argtypes[1:]
-    lib.sn_dbg_refin_n.argtypes = [vp, ip] + lib.sn_dbg_refin.argtypes[1:]
-    lib.sn_dbg_ref_conv_f16_n.argtypes = [vp, ip] + lib.sn_dbg_ref_conv_f16.argtypes[1:]
-    lib.sn_dbg_ref_conv_f16x3_n.argtypes = [vp, ip] + lib.sn_dbg_ref_conv_f16x3.argtypes[1:]
-    lib.sn_dbg_ref_block_f16_n.argtypes = [vp, ip] + lib.sn_dbg_ref_block_f16.argtypes[1:]
-    lib.sn_dbg_ref_block_f16x3_n.argtypes = [vp, ip] + lib.sn_dbg_ref_block_f16x3.argtypes[1:]
     u64p = C.POINTER(C.c_uint64)
     lib.sn_dbg_cost_volume.argtypes = [vp, fp, ip, ip, ip, ip, ip, fp]
     lib.sn_dbg_agg_first_f32.argtypes = [vp, fp, ip, ip, ip, ip, fp, fp, fp]
@@ -426,7 +419,7 @@ def load_library(path: Optional[str] = None):
                  "sn_infer_sbs_nv12", "sn_preprocess_sbs_nv12_batch", "sn_submit", "sn_submit_nv12", "sn_wait", "sn_synchronize", "sn_set_profiling",
                  "sn_get_stage_ms", "sn_get_dominant_kernel", "sn_mgpu_shard", "sn_mgpu_create", "sn_mgpu_destroy",
                  "sn_mgpu_get_info", "sn_mgpu_get_handle", "sn_mgpu_infer_batch", "sn_mgpu_infer_batch_device",
-                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_conv2d", "sn_dbg_down0", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_down01", "sn_dbg_refin", "sn_dbg_conv3d", "sn_dbg_ref_conv_f16", "sn_dbg_ref_conv_f16x3", "sn_dbg_ref_block_f16", "sn_dbg_ref_block_f16x3", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_slot_graphs", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_elevation_create", "sn_elevation_reset", "sn_elevation_pose_q", "sn_elevation_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_rollout_tables", "sn_rollout_pose_q", "sn_rollout_velocity", "sn_rollout", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
+                 "sn_mgpu_submit_device", "sn_mgpu_wait", "sn_mgpu_ring_init", "sn_mgpu_ring_submit", "sn_mgpu_ring_wait", "sn_dbg_compose_down01", "sn_dbg_round_kernels_f16", "sn_dbg_conv3d", "sn_dbg_ref_tail_f16", "sn_dbg_set_grid_cus", "sn_dbg_last_launch", "sn_dbg_slot_graphs", "sn_dbg_conv2d_n", "sn_dbg_down0_n", "sn_dbg_down01_n", "sn_dbg_refin_n", "sn_dbg_ref_conv_f16_n", "sn_dbg_ref_conv_f16x3_n", "sn_dbg_ref_block_f16_n", "sn_dbg_ref_block_f16x3_n", "sn_dbg_cost_volume", "sn_dbg_agg_first_f32", "sn_dbg_softargmin", "sn_dbg_agg_tail", "sn_dbg_head", "sn_dbg_img_pool2", "sn_dbg_read", "sn_dbg_copy_limited", "sn_depth_from_raw", "sn_pointcloud_from_raw", "sn_mirror_pair_i8", "sn_lr_check", "sn_infer_lrc", "sn_filter_raw", "sn_smooth_raw", "sn_temporal_create", "sn_temporal_reset", "sn_temporal_push", "sn_rectify_build_map", "sn_rectify_create", "sn_rectify_get_info", "sn_rectify_get_camera", "sn_rectify_get_map", "sn_rectify_nv12", "sn_jpeg_encode_nv12", "sn_dbg_jpeg_dct", "sn_render_tables", "sn_render", "sn_render_jpeg", "sn_obstacle_beam_edges", "sn_obstacles_from_raw", "sn_obstacles_from_raw_mounts", "sn_ground_gate", "sn_ground_from_raw", "sn_costmap_create", "sn_costmap_reset", "sn_costmap_pose_q", "sn_costmap_push", "sn_elevation_create", "sn_elevation_reset", "sn_elevation_pose_q", "sn_elevation_push", "sn_inflate_table", "sn_inflate_grid", "sn_navfn", "sn_rollout_tables", "sn_rollout_pose_q", "sn_rollout_velocity", "sn_rollout", "sn_infer_conf", "sn_conf_mask", "sn_get_refine_stats", "sn_auto_init", "sn_auto_observe"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -1388,127 +1381,107 @@ class StereoNetHIP:
         x = np.ascontiguousarray(x, dtype)
         return (x[None], True) if x.ndim == 3 else (x, False)
 
+    @staticmethod
+    def _f32(*arrays):
+        """contiguous float32 arrays (None stays None): the weights, biases and residual of a hook"""
+        return [None if a is None else np.ascontiguousarray(a, np.float32) for a in arrays]
+
+    def _hook(self, name, out, one, *args):
+        """hook `name`(handle, *args, out), arrays passed by address (None = NULL) -> out, without the batch axis if `one`"""
+        a = [_np_ptr(v) if v is None or isinstance(v, np.ndarray) else v for v in args]
+        self._check(getattr(self._lib, name)(self._h, *a, out.ctypes.data), name)
+        return out[0] if one else out
+
+    @staticmethod
+    def _conv_form(x3, slots, dma=False, tower32=False):
+        """the SN_DBG_CONV_* enumerator of the keywords; -1, which the hooks refuse, where there is none"""
+        if x3 != slots or (dma and not slots):
+            return -1
+        return (3 if dma else 2) if slots else (1 if tower32 else 0)
+
     def dbg_conv2d(self, x, wt, bias, k, stride=1, dil=1, lrelu=False, residual=None, x3=False, slots=False, tower32=False, dma=False):
         """x (cin, h, w) or (n, cin, h, w): n images in one launch.  dma (with x3 and slots): the kernel of the zero-bordered
         tensors — k_down_x3s_dma (5x5 stride 2) or k_feat_x3s_dma (3x3, also with a residual); the hook also checks that the
         borders stay zero"""
         x, one = self._batch(x)
-        wt = np.ascontiguousarray(wt, np.float32)
-        bias = np.ascontiguousarray(bias, np.float32)
+        wt, bias, res = self._f32(wt, bias, residual)
         n, cin, h, w = x.shape
         ho, wo = (h, w) if stride == 1 else (h // 2, w // 2)
         out = np.empty((n, 32, ho, wo), np.float32)
-        res = np.ascontiguousarray(residual, np.float32) if residual is not None else None
         assert res is None or res.size == out.size
-        self._check(self._lib.sn_dbg_conv2d_n(self._h, n, x.ctypes.data, cin, h, w, wt.ctypes.data, bias.ctypes.data, k,
-                                              stride, dil, int(lrelu) | (2 if x3 else 0) | (4 if slots else 0) | (8 if tower32 else 0) | (16 if dma else 0), _np_ptr(res),
-                                              out.ctypes.data),
-                    "sn_dbg_conv2d")
-        return out[0] if one else out
+        return self._hook("sn_dbg_conv2d_n", out, one, n, x, cin, h, w, wt, bias, k, stride, dil, int(bool(lrelu)),
+                          self._conv_form(x3, slots, dma, tower32), res)
 
     def dbg_down0(self, in6, wt, bias, tc=32):
         """in6 int8 (6,h,w) -> float32 (2, 32, ho, wo): first down-conv of both eyes on the fp16 MFMA; in6 (n,6,h,w): n pairs
         in one launch -> (2n, 32, ho, wo)."""
         x, _ = self._batch(in6, np.int8)
-        wt = np.ascontiguousarray(wt, np.float32)
-        bias = np.ascontiguousarray(bias, np.float32)
+        wt, bias = self._f32(wt, bias)
         n, _, h, w = x.shape
-        ho, wo = (h + 15) // 16 * 8, (w + 15) // 16 * 8
-        out = np.empty((2 * n, 32, ho, wo), np.float32)
-        self._check(self._lib.sn_dbg_down0_n(self._h, n, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, tc,
-                                             out.ctypes.data), "sn_dbg_down0")
-        return out
+        out = np.empty((2 * n, 32, (h + 15) // 16 * 8, (w + 15) // 16 * 8), np.float32)
+        return self._hook("sn_dbg_down0_n", out, False, n, x, h, w, wt, bias, tc)
 
     def dbg_down01(self, in6, w0, b0, w1, b1):
         """in6 int8 (6,h,w) -> float32 (2, 32, ho, wo), ho/wo = ceil16/4: the first two down-convs of both eyes as the
         folded 13x13 stride-4 convolution (k_down01_f16 + k_down01_border); in6 (n,6,h,w): n pairs in one launch -> (2n, ...)."""
         x, _ = self._batch(in6, np.int8)
-        w0, b0, w1, b1 = (np.ascontiguousarray(a, np.float32) for a in (w0, b0, w1, b1))
+        w0, b0, w1, b1 = self._f32(w0, b0, w1, b1)
         assert w0.shape == (32, 3, 5, 5) and w1.shape == (32, 32, 5, 5) and b0.shape == (32,) and b1.shape == (32,)
         n, _, h, w = x.shape
-        ho, wo = (h + 15) // 16 * 4, (w + 15) // 16 * 4
-        out = np.empty((2 * n, 32, ho, wo), np.float32)
-        self._check(self._lib.sn_dbg_down01_n(self._h, n, x.ctypes.data, h, w, w0.ctypes.data, b0.ctypes.data, w1.ctypes.data,
-                                              b1.ctypes.data, out.ctypes.data), "sn_dbg_down01")
-        return out
+        out = np.empty((2 * n, 32, (h + 15) // 16 * 4, (w + 15) // 16 * 4), np.float32)
+        return self._hook("sn_dbg_down01_n", out, False, n, x, h, w, w0, b0, w1, b1)
 
     def dbg_refin(self, disp_low, in6, dmax, wt, bias, split=False):
         """disp_low float32 (hp/16, wp/16), in6 int8 (6,h,w) -> float32 (32, hp, wp): refinement input conv; with a leading
         batch axis on both, n images in one launch."""
         x, one = self._batch(in6, np.int8)
-        dl = np.ascontiguousarray(disp_low, np.float32)
-        wt = np.ascontiguousarray(wt, np.float32)
-        bias = np.ascontiguousarray(bias, np.float32)
+        dl, wt, bias = self._f32(disp_low, wt, bias)
         n, _, h, w = x.shape
         hp, wp = (h + 15) // 16 * 16, (w + 15) // 16 * 16
         assert dl.shape == ((hp // 16, wp // 16) if one else (n, hp // 16, wp // 16))
         out = np.empty((n, 32, hp, wp), np.float32)
-        self._check(self._lib.sn_dbg_refin_n(self._h, n, dl.ctypes.data, x.ctypes.data, h, w, dmax, wt.ctypes.data,
-                                             bias.ctypes.data, int(split), out.ctypes.data), "sn_dbg_refin")
-        return out[0] if one else out
+        return self._hook("sn_dbg_refin_n", out, one, n, dl, x, h, w, dmax, wt, bias, int(split))
 
     def dbg_conv3d(self, x, wt, bias, lrelu=False, x3=False, slots=False, dma=False):
         """dma: the aggregation kernel on zero-bordered volumes (k_agg_x3s_dma; needs x3 and slots); the hook also checks that
         the kernel left the borders untouched"""
-        x = np.ascontiguousarray(x, np.float32)
-        wt = np.ascontiguousarray(wt, np.float32)
-        bias = np.ascontiguousarray(bias, np.float32)
+        x, wt, bias = self._f32(x, wt, bias)
         _, d, h, w = x.shape
-        out = np.empty_like(x)
-        self._check(self._lib.sn_dbg_conv3d(self._h, x.ctypes.data, d, h, w, wt.ctypes.data, bias.ctypes.data,
-                                            int(lrelu) | (2 if x3 else 0) | (4 if slots else 0) | (8 if dma else 0), out.ctypes.data),
-                    "sn_dbg_conv3d")
-        return out
+        return self._hook("sn_dbg_conv3d", np.empty_like(x), False, x, d, h, w, wt, bias, int(bool(lrelu)), self._conv_form(x3, slots, dma))
 
     def dbg_ref_conv_f16(self, x, wt, bias, dil=1, lrelu=False, residual=None, tile_w=0):
         """x (32, h, w) or (n, 32, h, w): n images in one launch.  tile_w: 0 = the width the engine would choose for this
         launch, 64 / 32 = force that variant (dilation 1, 2)"""
         x, one = self._batch(x)
-        wt = np.ascontiguousarray(wt, np.float32)
-        bias = np.ascontiguousarray(bias, np.float32)
+        wt, bias, res = self._f32(wt, bias, residual)
         n, _, h, w = x.shape
         out = np.empty((n, 32, h, w), np.float32)
-        res = np.ascontiguousarray(residual, np.float32) if residual is not None else None
         assert res is None or res.size == out.size
-        flags = int(bool(lrelu)) | (2 if tile_w == 64 else 4 if tile_w == 32 else 0)
-        self._check(self._lib.sn_dbg_ref_conv_f16_n(self._h, n, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, dil,
-                                                    flags, _np_ptr(res), out.ctypes.data), "sn_dbg_ref_conv_f16")
-        return out[0] if one else out
+        return self._hook("sn_dbg_ref_conv_f16_n", out, one, n, x, h, w, wt, bias, dil, int(bool(lrelu)),
+                          tile_w if tile_w in (64, 32) else 0, res)
 
     def dbg_ref_conv_f16x3(self, x, wt, bias, dil=1, lrelu=False, residual=None):
         x, one = self._batch(x)
-        wt = np.ascontiguousarray(wt, np.float32)
-        bias = np.ascontiguousarray(bias, np.float32)
+        wt, bias, res = self._f32(wt, bias, residual)
         n, _, h, w = x.shape
         out = np.empty((n, 32, h, w), np.float32)
-        res = np.ascontiguousarray(residual, np.float32) if residual is not None else None
         assert res is None or res.size == out.size
-        self._check(self._lib.sn_dbg_ref_conv_f16x3_n(self._h, n, x.ctypes.data, h, w, wt.ctypes.data, bias.ctypes.data, dil,
-                                                      int(lrelu), _np_ptr(res), out.ctypes.data), "sn_dbg_ref_conv_f16x3")
-        return out[0] if one else out
+        return self._hook("sn_dbg_ref_conv_f16x3_n", out, one, n, x, h, w, wt, bias, dil, int(bool(lrelu)), res)
 
     def dbg_ref_block_f16(self, x, w1, b1, w2, b2, dil=1, fused=0):
         """fused: 0 = two conv launches, 2 = row-streaming fused kernel (every dilation: 1, 2, 4, 8)"""
-        dil = dil | (fused << 8)
-        a = [np.ascontiguousarray(v, np.float32) for v in (w1, b1, w2, b2)]
         x, one = self._batch(x)
         n, _, h, w = x.shape
-        out = np.empty((n, 32, h, w), np.float32)
-        self._check(self._lib.sn_dbg_ref_block_f16_n(self._h, n, x.ctypes.data, h, w, a[0].ctypes.data, a[1].ctypes.data,
-                                                     a[2].ctypes.data, a[3].ctypes.data, dil, out.ctypes.data),
-                    "sn_dbg_ref_block_f16")
-        return out[0] if one else out
+        form = {0: 0, 2: 1}.get(fused, -1)          # -1: the hook refuses it
+        return self._hook("sn_dbg_ref_block_f16_n", np.empty((n, 32, h, w), np.float32), one, n, x, h, w,
+                          *self._f32(w1, b1, w2, b2), dil, form)
 
     def dbg_ref_block_f16x3(self, x, w1, b1, w2, b2, dil=1, streamed=False):
         """the same block on split operands (SN_PREC_F16X3): two k_ref_conv_f16x3 launches, or the row-streaming fused kernel"""
-        a = [np.ascontiguousarray(v, np.float32) for v in (w1, b1, w2, b2)]
         x, one = self._batch(x)
         n, _, h, w = x.shape
-        out = np.empty((n, 32, h, w), np.float32)
-        self._check(self._lib.sn_dbg_ref_block_f16x3_n(self._h, n, x.ctypes.data, h, w, a[0].ctypes.data, a[1].ctypes.data,
-                                                       a[2].ctypes.data, a[3].ctypes.data, dil, int(streamed), out.ctypes.data),
-                    "sn_dbg_ref_block_f16x3")
-        return out[0] if one else out
+        return self._hook("sn_dbg_ref_block_f16x3_n", np.empty((n, 32, h, w), np.float32), one, n, x, h, w,
+                          *self._f32(w1, b1, w2, b2), dil, int(streamed))
 
     def dbg_ref_tail_f16(self, x, w1, b1, w2, b2, head_w, head_b, low, ups, dnorm, h_out, w_out, form):
         """Last residual block + refinement head on x float32 (n, 32, hk, wk); low (n, hk/ups, wk/ups); form 0 = streamed

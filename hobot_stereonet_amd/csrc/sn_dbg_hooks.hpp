@@ -1,6 +1,7 @@
 // sn_dbg_hooks.hpp — the sn_dbg_* entry points (parity hooks: one kernel or block on caller-supplied tensors, as the
 // pipeline launches it) and the host-side marshalling they share: split-slot tensors, their zero-bordered grids
-// (PaddedSlots), the fp16 tower layout (RefHost) and its device allocation with front rows and slack (RefDev), the guarded
+// (PaddedSlots), the fp16 tower layout (RefHost), its device allocation with front rows and slack (RefDev) and the sequence
+// the tower hooks run around their launch line (TowerHook), the guarded
 // outputs of the mid-stage hooks (Guarded, HookStat), and the grid cap of the hooks (sn_dbg_set_grid_cus, dbg_cus).  Part of
 // the single translation unit stereonet_hip.hip.
 #pragma once
@@ -79,10 +80,11 @@ struct PaddedSlots {
 // Host image of the fp16 tower tensors: n images of 32 x h x w as NCHW8c inside the zero border of RefGeom g.  split: the
 // layout holds a lo tensor lo_slots behind the hi tensor; slack: each part is followed by ref_slack(g) slots.
 struct RefHost {
-  RefGeom g;
-  int n, h, w;
-  size_t lo_slots;
+  RefGeom g{};
+  int n = 0, h = 0, w = 0;
+  size_t lo_slots = 0;
   std::vector<_Float16> v;
+  RefHost() = default;
   RefHost(const RefGeom& g_, int n_, int h_, int w_, bool split, bool slack)
       : g(g_), n(n_), h(h_), w(w_), lo_slots(ref16_slots(g_, n_) + (slack ? ref_slack(g_) : 0)), v((split ? 2 : 1) * lo_slots * 8) {}
   size_t slots() const { return v.size() / 8; }
@@ -184,6 +186,85 @@ int dbg_cus(const sn_handle* h) { return h->dbg_grid_cus > 0 ? h->dbg_grid_cus :
     }                                                                               \
   } while (0)
 
+// What every tower hook does around its launch line.  begin(): the argument checks, the device, the geometry, the layers, the
+// two tensors as the pipeline allocates them and what they hold before the launch.  run(): the launch between a device
+// synchronisation (the uploads are hipMemcpy on the null stream, the launch goes onto h->stream) and the stream's, then the
+// read-back of EVERY tensor (front rows, border of all n images, slack) and the result.
+enum : unsigned {
+  kTowerSplit = 1,      // hi / lo operands (SN_PREC_F16X3): tensors [hi | slack | lo | slack], layers through upload_ref_f16x3
+  kTowerHiOnly = 2,     // (with kTowerSplit) the kernel writes the hi part alone: the lo part has to stay zero
+  kTowerBanded = 4,     // the launcher builds its grid in XCD bands (SN_DBG_BANDED)
+  kTowerQueue = 8,      // the launcher hands out tiles from ws.tile_ctr, which only an engine created in an fp16 mode has
+};
+struct TowerHook {
+  struct WB { const float *w, *b; };      // one 32 -> 32 3x3 layer: w [32][32][3][3], b [32]
+  sn_handle* const h;
+  const std::string what, what_other;     // whose fault a changed border is: of the result tensor, of the other one
+  DevScope ds;          // frees every tracked device buffer on every return path
+  RefHost t;            // the host image both tensors are filled from and read into
+  RefLayerF16 L[2];
+  RefDev x, y;          // x: the input (none when the hook has no tower tensor to read), y: the other tensor
+  uint4* res = nullptr; // the tensor that holds the result after the launch: y, unless the launch line says x
+  int parts = 1;
+  TowerHook(sn_handle* h_, const std::string& what_) : h(h_), what(what_), what_other(what_ + " (its other tensor)") {}
+  TowerHook(sn_handle* h_, const std::string& what_, const std::string& other) : h(h_), what(what_), what_other(other) {}
+
+  // need: the caller's pointers, none of which may be null.  in (nullable): fp32 [n][32][hgt][wid], packed into x.  residual
+  // (nullable): packed into y, the in-place form of the pipeline; without one y starts as the 0xff pattern, as every output
+  // that is not also an input.
+  int begin(std::initializer_list<const void*> need, int n, int hgt, int wid, int dil, unsigned flags, const float* in,
+            const float* residual, std::initializer_list<WB> layers) {
+    if (!h || n <= 0 || hgt <= 0 || wid <= 0 || (dil != 1 && dil != 2 && dil != 4 && dil != 8)) return SN_ERR_ARG;
+    for (const void* p : need)
+      if (!p) return SN_ERR_ARG;
+    if (flags & kTowerBanded) SN_DBG_BANDED(h);
+    int rc = check_device(h);
+    if (rc) return rc;
+    if ((flags & kTowerQueue) && !h->ws.tile_ctr) {
+      set_err(h, what + ": this hook needs an engine created in an fp16 mode");
+      return SN_ERR_ARG;
+    }
+    const RefGeom g = make_ref_geom(hgt, wid);
+    // the tower kernels add 32-bit byte offsets to a tensor's base (sn_create refuses such a workspace)
+    if ((ref16_slots(g, n) + ref_slack(g) + ref_front(g)) * 16 >= ((size_t)1 << 32)) return SN_ERR_ARG;
+    const bool split = (flags & kTowerSplit) != 0;
+    parts = split && !(flags & kTowerHiOnly) ? 2 : 1;
+    t = RefHost(g, n, hgt, wid, split, true);
+    RefLayerF16* l = L;
+    for (const WB& wb : layers) {
+      const HostLayer hl{wb.w, wb.b, kC, kC, 9};
+      if (!rc) rc = split ? upload_ref_f16x3(h, hl, l) : upload_ref_f16(h, hl, switches_at_create().w_round_sum_preserving, l);
+      ds.adopt(*l++);
+    }
+    if (rc) return rc;
+    if (in) {
+      HIP_TRY(h, x.alloc(ds, t));
+      t.pack(in, parts == 2);
+      HIP_TRY(h, to_dev(x.base, t.v));
+    }
+    HIP_TRY(h, y.alloc(ds, t));
+    if (residual) t.pack(residual, parts == 2);
+    else t.prefill(parts);
+    HIP_TRY(h, to_dev(y.base, t.v));
+    res = y.base;
+    if (flags & kTowerQueue) HIP_TRY(h, hipMemsetAsync(h->ws.tile_ctr, 0, kTileCtrBytes, h->stream));
+    return SN_OK;
+  }
+
+  // launch: () -> hipError_t, the hook's launch line(s).  out (nullable): fp32 [n][32][hgt][wid], the result tensor.
+  template <class Launch>
+  int run(float* out, Launch launch) {
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, launch());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const bool in_x = x.base && res == x.base;
+    if (x.base) SN_REF_GET(h, in_x ? y : x, t, parts, what_other);
+    SN_REF_GET(h, in_x ? x : y, t, parts, what);
+    if (out) t.unpack(out, parts == 2);
+    return SN_OK;
+  }
+};
+
 // A device output of a mid-stage hook between two guard bands of kGuardBytes known bytes (kGuardByte), owned by ds.  The
 // payload starts as the 0xff pattern (fp32 NaN, int32 -1, fp16 NaN): an element the kernel does not write shows.
 constexpr size_t kGuardBytes = 4096;
@@ -283,7 +364,7 @@ int sn_dbg_slot_graphs(sn_handle* h, int* enabled, int* instantiated, int* launc
 }
 
 int sn_dbg_conv2d_n(sn_handle* h, int n, const float* in, int cin, int h_px, int w, const float* wt, const float* bias,
-                    int k, int stride, int dil, int lrelu, const float* residual, float* out) {
+                    int k, int stride, int dil, int lrelu, int form, const float* residual, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
   if (!h || !in || !wt || !bias || !out || cin <= 0 || cin > kC || n <= 0) return SN_ERR_ARG;
   if (!((k == 3 && stride == 1) || (k == 5 && stride == 2 && dil == 1))) return SN_ERR_ARG;
@@ -292,12 +373,10 @@ int sn_dbg_conv2d_n(sn_handle* h, int n, const float* in, int cin, int h_px, int
   const int taps = k * k;
   const int Ho = stride == 1 ? h_px : h_px / 2, Wo = stride == 1 ? w : w / 2;
   if (stride == 2 && ((h_px & 1) || (w & 1))) return SN_ERR_ARG;
-  const bool x3 = (lrelu & 2) != 0, slots = (lrelu & 4) != 0;
-  const bool tower32 = (lrelu & 8) != 0;     // bit 3: the fp32 tower kernel (k_ref_conv_f32) instead of the generic one
-  const bool dma = (lrelu & 16) != 0;        // bit 4 (5x5 stride 2 on slots): k_down_x3s_dma on zero-bordered tensors
-  lrelu &= 1;
-  if (x3 != slots || (x3 && !(cin == kC && dil == 1))) return SN_ERR_ARG;     // the split-operand kernel reads slots
-  if (dma && !(slots && (k == 3 || !residual))) return SN_ERR_ARG;
+  if (form < SN_DBG_CONV_F32 || form > SN_DBG_CONV_SLOTS_DMA) return SN_ERR_ARG;
+  const bool dma = form == SN_DBG_CONV_SLOTS_DMA, slots = dma || form == SN_DBG_CONV_SLOTS, tower32 = form == SN_DBG_CONV_TOWER32;
+  if (slots && !(cin == kC && dil == 1)) return SN_ERR_ARG;     // the split-operand kernels
+  if (dma && k == 5 && residual) return SN_ERR_ARG;             // k_down_x3s_dma adds none
   if (slots) SN_DBG_BANDED(h);
   const int ncu = dbg_cus(h);
   LaunchInfo* const li = &h->dbg_launch;
@@ -391,11 +470,6 @@ int sn_dbg_conv2d_n(sn_handle* h, int n, const float* in, int cin, int h_px, int
   return SN_OK;
 }
 
-int sn_dbg_conv2d(sn_handle* h, const float* in, int cin, int h_px, int w, const float* wt, const float* bias,
-                  int k, int stride, int dil, int lrelu, const float* residual, float* out) {
-  return sn_dbg_conv2d_n(h, 1, in, cin, h_px, w, wt, bias, k, stride, dil, lrelu, residual, out);
-}
-
 int sn_dbg_down0_n(sn_handle* h, int n, const int8_t* in6, int h_px, int w, const float* wt, const float* bias, int tc,
                    float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
@@ -422,11 +496,6 @@ int sn_dbg_down0_n(sn_handle* h, int n, const int8_t* in6, int h_px, int w, cons
   HIP_TRY(h, from_dev(hs, dout));
   host_from_slots(hs, 2 * n, Ho, Wo, out);
   return SN_OK;
-}
-
-int sn_dbg_down0(sn_handle* h, const int8_t* in6, int h_px, int w, const float* wt, const float* bias, int tc,
-                 float* out) {
-  return sn_dbg_down0_n(h, 1, in6, h_px, w, wt, bias, tc, out);
 }
 
 int sn_dbg_round_kernels_f16(const float* w, int nkernels, float* out) {
@@ -475,65 +544,45 @@ int sn_dbg_down01_n(sn_handle* h, int n, const int8_t* in6, int h_px, int w, con
   return SN_OK;
 }
 
-int sn_dbg_down01(sn_handle* h, const int8_t* in6, int h_px, int w, const float* w0, const float* b0, const float* w1,
-                  const float* b1, float* out) {
-  return sn_dbg_down01_n(h, 1, in6, h_px, w, w0, b0, w1, b1, out);
-}
-
 int sn_dbg_refin_n(sn_handle* h, int n, const float* disp_low, const int8_t* in6, int h_px, int w, int dmax, const float* wt,
                    const float* bias, int split, float* out) {
-  DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !disp_low || !in6 || !wt || !bias || !out || h_px <= 0 || w <= 0 || dmax <= 0 || n <= 0) return SN_ERR_ARG;
-  int rc = check_device(h);
-  if (rc) return rc;
+  if (h_px <= 0 || w <= 0 || dmax <= 0) return SN_ERR_ARG;
   const int Hp = (h_px + 15) / 16 * 16, Wp = (w + 15) / 16 * 16, hl = Hp / 16, wl = Wp / 16;
-  RefHost t(make_ref_geom(Hp, Wp), n, Hp, Wp, true, true);      // [hi | slack | lo | slack] whatever `split` says
+  TowerHook th(h, "ref.in");
+  // no tower tensor to read, and [hi | slack | lo | slack] whatever `split` says
+  int rc = th.begin({disp_low, in6, wt, bias, out}, n, Hp, Wp, 1, kTowerSplit | (split ? 0 : kTowerHiOnly), nullptr, nullptr, {});
+  if (rc) return rc;
   Down0F16 L;
   rc = upload_refin_f16(h, HostLayer{wt, bias, kC, 4, 9}, &L);
-  ds.adopt(L);
+  th.ds.adopt(L);
   if (rc) return rc;
   float *ddl = nullptr, *dbias = nullptr;
   int8_t* din = nullptr;
-  RefDev dout;
-  const int parts = split ? 2 : 1;
-  HIP_TRY(h, ds.alloc(&ddl, (size_t)n * hl * wl));
-  HIP_TRY(h, ds.alloc(&dbias, kC));
-  HIP_TRY(h, ds.alloc(&din, (size_t)n * 6 * h_px * w));
-  HIP_TRY(h, dout.alloc(ds, t));
+  HIP_TRY(h, th.ds.alloc(&ddl, (size_t)n * hl * wl));
+  HIP_TRY(h, th.ds.alloc(&dbias, kC));
+  HIP_TRY(h, th.ds.alloc(&din, (size_t)n * 6 * h_px * w));
   HIP_TRY(h, hipMemcpy(ddl, disp_low, (size_t)n * hl * wl * 4, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(dbias, bias, kC * 4, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(din, in6, (size_t)n * 6 * h_px * w, hipMemcpyHostToDevice));
-  t.prefill(parts);
-  HIP_TRY(h, to_dev(dout.base, t.v));
-  HIP_TRY(h, hipDeviceSynchronize());
-  HIP_TRY(h, launch_refin_f16(h->stream, L, dbias, ddl, din, false, hl, wl, h_px, w, 1.0f / (float)dmax,
-                              UpScale{1.0f / 16.0f, 16.0f}, t.g, n, dout.base, split != 0, t.lo_slots * 16, dbg_cus(h),
-                              &h->dbg_launch));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  SN_REF_GET(h, dout, t, parts, "ref.in");
-  t.unpack(out, split != 0);
-  return SN_OK;
-}
-
-int sn_dbg_refin(sn_handle* h, const float* disp_low, const int8_t* in6, int h_px, int w, int dmax, const float* wt,
-                 const float* bias, int split, float* out) {
-  return sn_dbg_refin_n(h, 1, disp_low, in6, h_px, w, dmax, wt, bias, split, out);
+  return th.run(out, [&] {
+    return launch_refin_f16(h->stream, L, dbias, ddl, din, false, hl, wl, h_px, w, 1.0f / (float)dmax, UpScale{1.0f / 16.0f, 16.0f},
+                            th.t.g, n, th.y.base, split != 0, th.t.lo_slots * 16, dbg_cus(h), &h->dbg_launch);
+  });
 }
 
 int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const float* wt, const float* bias,
-                  int lrelu, float* out) {
+                  int lrelu, int form, float* out) {
   DevScope ds;      // frees every tracked device buffer on every return path
   if (!h || !in || !wt || !bias || !out || d <= 0) return SN_ERR_ARG;
   int rc = check_device(h);
   if (rc) return rc;
-  const bool x3 = (lrelu & 2) != 0, slots = (lrelu & 4) != 0, dma = (lrelu & 8) != 0;   // dma: zero-bordered volumes
-  lrelu &= 1;
-  if (slots != x3 || (dma && !slots)) return SN_ERR_ARG;        // the split-operand kernels read split-slot volumes
+  if (form != SN_DBG_CONV_F32 && form != SN_DBG_CONV_SLOTS && form != SN_DBG_CONV_SLOTS_DMA) return SN_ERR_ARG;
+  const bool dma = form == SN_DBG_CONV_SLOTS_DMA, slots = dma || form == SN_DBG_CONV_SLOTS;
   if (slots) SN_DBG_BANDED(h);
   h->dbg_launch = LaunchInfo{};
   ConvLayer L;
   rc = upload_conv3d(h, HostLayer{wt, bias, kC, kC, 27}, &L);
-  if (!rc && x3)
+  if (!rc && slots)
     rc = upload_x3(h, 96, [&](int co, int c, int tap) { return wt[(((size_t)co * kC + (c & 31)) * 3 + (c >> 5)) * 9 + tap]; }, &L);
   ds.adopt(L);
   if (rc) return rc;
@@ -592,230 +641,99 @@ int sn_dbg_conv3d(sn_handle* h, const float* in, int d, int h_px, int w, const f
 }
 
 int sn_dbg_ref_conv_f16_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
-                          int lrelu, const float* residual, float* out) {
-  DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
-  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
-  SN_DBG_BANDED(h);
-  int rc = check_device(h);
+                          int lrelu, int tile_w, const float* residual, float* out) {
+  if (tile_w != 0 && tile_w != 64 && tile_w != 32) return SN_ERR_ARG;
+  TowerHook th(h, "the fp16 conv");
+  const int rc = th.begin({in, wt, bias, out}, n, h_px, w, dil, kTowerBanded | kTowerQueue, in, residual, {{wt, bias}});
   if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), n, h_px, w, false, true);
-  RefLayerF16 L;
-  rc = upload_ref_f16(h, HostLayer{wt, bias, kC, kC, 9}, switches_at_create().w_round_sum_preserving, &L);
-  ds.adopt(L);
-  if (rc) return rc;
-  RefDev din, dout;
-  HIP_TRY(h, din.alloc(ds, t));
-  HIP_TRY(h, dout.alloc(ds, t));
-  t.pack(in, false);
-  HIP_TRY(h, to_dev(din.base, t.v));
-  if (residual) t.pack(residual, false);      // added in place, as the pipeline does
-  else t.prefill(1);
-  HIP_TRY(h, to_dev(dout.base, t.v));
-  unsigned* ctr = h->ws.tile_ctr;
-  if (!ctr) {
-    set_err(h, "sn_dbg_ref_conv_f16 needs an engine created in an fp16 mode");
-    return SN_ERR_ARG;
-  }
-  HIP_TRY(h, hipMemsetAsync(ctr, 0, kTileCtrBytes, h->stream));
-  // lrelu bits 1 / 2: force the 8x64 / 8x32 tile variant of the dilation-1 / -2 kernels (default: chosen per launch)
-  HIP_TRY(h, ref_conv_f16(h->stream, L, t.g, dbg_cus(h), dil, din.base, dout.base, residual ? dout.base : nullptr, n, (lrelu & 1) != 0,
-                          ctr, (lrelu & 2) ? 64 : (lrelu & 4) ? 32 : 0, &h->dbg_launch));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  SN_REF_GET(h, dout, t, 1, "the fp16 conv");      // the kernel never writes outside the valid area
-  t.unpack(out, false);
-  return SN_OK;
-}
-
-int sn_dbg_ref_conv_f16(sn_handle* h, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
-                        int lrelu, const float* residual, float* out) {
-  return sn_dbg_ref_conv_f16_n(h, 1, in, h_px, w, wt, bias, dil, lrelu, residual, out);
+  return th.run(out, [&] {
+    return ref_conv_f16(h->stream, th.L[0], th.t.g, dbg_cus(h), dil, th.x.base, th.y.base, residual ? th.y.base : nullptr, n,
+                        lrelu != 0, h->ws.tile_ctr, tile_w, &h->dbg_launch);
+  });
 }
 
 int sn_dbg_ref_conv_f16x3_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
                             int lrelu, const float* residual, float* out) {
-  DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !wt || !bias || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
-  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
-  SN_DBG_BANDED(h);
-  int rc = check_device(h);
+  TowerHook th(h, "the f16x3 conv");
+  const int rc = th.begin({in, wt, bias, out}, n, h_px, w, dil, kTowerSplit | kTowerBanded, in, residual, {{wt, bias}});
   if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), n, h_px, w, true, true);      // [hi | slack | lo | slack]
-  RefLayerF16 L;
-  rc = upload_ref_f16x3(h, HostLayer{wt, bias, kC, kC, 9}, &L);
-  ds.adopt(L);
-  if (rc) return rc;
-  RefDev din, dout;
-  HIP_TRY(h, din.alloc(ds, t));
-  HIP_TRY(h, dout.alloc(ds, t));
-  t.pack(in, true);
-  HIP_TRY(h, to_dev(din.base, t.v));
-  if (residual) t.pack(residual, true);
-  else t.prefill(2);
-  HIP_TRY(h, to_dev(dout.base, t.v));
-  HIP_TRY(h, hipDeviceSynchronize());
-  HIP_TRY(h, ref_conv_f16x3(h->stream, L, t.g, dbg_cus(h), dil, din.base, dout.base, residual ? dout.base : nullptr, t.lo_slots, n,
-                            lrelu != 0, &h->dbg_launch));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  SN_REF_GET(h, dout, t, 2, "the f16x3 conv");
-  t.unpack(out, true);
-  return SN_OK;
+  return th.run(out, [&] {
+    return ref_conv_f16x3(h->stream, th.L[0], th.t.g, dbg_cus(h), dil, th.x.base, th.y.base, residual ? th.y.base : nullptr,
+                          th.t.lo_slots, n, lrelu != 0, &h->dbg_launch);
+  });
 }
 
-int sn_dbg_ref_conv_f16x3(sn_handle* h, const float* in, int h_px, int w, const float* wt, const float* bias, int dil,
-                          int lrelu, const float* residual, float* out) {
-  return sn_dbg_ref_conv_f16x3_n(h, 1, in, h_px, w, wt, bias, dil, lrelu, residual, out);
-}
-
+// The block launchers take the input in *cur, use *oth as they see fit and leave the result in *cur: th.res is that cur.
 int sn_dbg_ref_block_f16x3_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* w1, const float* b1,
                              const float* w2, const float* b2, int dil, int form, float* out) {
-  DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
-  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
-  if (form != 0 && form != 1) return SN_ERR_ARG;            // 0 = two k_ref_conv_f16x3 launches, 1 = the streamed block
-  if (form == 1 && !stream_x3_supports(dil)) return SN_ERR_ARG;
-  if (form == 0) SN_DBG_BANDED(h);
-  int rc = check_device(h);
+  if ((form != 0 && form != 1) || (form == 1 && !stream_x3_supports(dil))) return SN_ERR_ARG;
+  TowerHook th(h, "the f16x3 residual block");
+  const int rc = th.begin({in, w1, b1, w2, b2, out}, n, h_px, w, dil, kTowerSplit | (form == 0 ? kTowerBanded : 0), in, nullptr,
+                          {{w1, b1}, {w2, b2}});
   if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), n, h_px, w, true, true);      // [hi | slack | lo | slack]
-  RefLayerF16 L1, L2;
-  rc = upload_ref_f16x3(h, HostLayer{w1, b1, kC, kC, 9}, &L1);
-  if (!rc) rc = upload_ref_f16x3(h, HostLayer{w2, b2, kC, kC, 9}, &L2);
-  ds.adopt(L1);
-  ds.adopt(L2);
-  if (rc) return rc;
-  RefDev a, b;
-  HIP_TRY(h, a.alloc(ds, t));
-  HIP_TRY(h, b.alloc(ds, t));
-  t.prefill(2);       // the other tensor (the streamed block's output, the two launches' intermediate) is never an input first
-  HIP_TRY(h, to_dev(b.base, t.v));
-  t.pack(in, true);
-  HIP_TRY(h, to_dev(a.base, t.v));
-  HIP_TRY(h, hipDeviceSynchronize());
-  uint4 *cur = a.base, *oth = b.base;
-  HIP_TRY(h, ref_block_f16x3(h->stream, L1, L2, t.g, dbg_cus(h), dil, &cur, &oth, t.lo_slots, n, form == 1, &h->dbg_launch));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  RefHost u = t;
-  SN_REF_GET(h, (cur == a.base ? b : a), u, 2, "the f16x3 residual block (its other tensor)");
-  SN_REF_GET(h, (cur == a.base ? a : b), t, 2, "the f16x3 residual block");
-  t.unpack(out, true);
-  return SN_OK;
-}
-
-int sn_dbg_ref_block_f16x3(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1, const float* w2,
-                           const float* b2, int dil, int form, float* out) {
-  return sn_dbg_ref_block_f16x3_n(h, 1, in, h_px, w, w1, b1, w2, b2, dil, form, out);
+  return th.run(out, [&] {
+    uint4* oth = th.y.base;
+    th.res = th.x.base;
+    return ref_block_f16x3(h->stream, th.L[0], th.L[1], th.t.g, dbg_cus(h), dil, &th.res, &oth, th.t.lo_slots, n, form == 1,
+                           &h->dbg_launch);
+  });
 }
 
 int sn_dbg_ref_block_f16_n(sn_handle* h, int n, const float* in, int h_px, int w, const float* w1, const float* b1,
-                           const float* w2, const float* b2, int dil, float* out) {
-  DevScope ds;      // frees every tracked device buffer on every return path
-  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !out || h_px <= 0 || w <= 0 || n <= 0) return SN_ERR_ARG;
-  // tests: bits 8.. select the form: 0 = two launches, 2 = row-streaming fused kernel (1 was the tile-fused kernel of round 2)
-  const int form = dil >> 8;
-  if (form != 0 && form != 2) return SN_ERR_ARG;
-  const int fuse_mode = form == 2 ? 4 : 0;
-  dil &= 0xff;
-  if (dil != 1 && dil != 2 && dil != 4 && dil != 8) return SN_ERR_ARG;
-  if (fuse_mode == 4 && !stream_block_supports(dil)) return SN_ERR_ARG;
-  if (form == 0) SN_DBG_BANDED(h);
-  int rc = check_device(h);
+                           const float* w2, const float* b2, int dil, int form, float* out) {
+  if ((form != 0 && form != 1) || (form == 1 && !stream_block_supports(dil))) return SN_ERR_ARG;
+  TowerHook th(h, "the fp16 residual block");
+  const int rc = th.begin({in, w1, b1, w2, b2, out}, n, h_px, w, dil, kTowerQueue | (form == 0 ? kTowerBanded : 0), in, nullptr,
+                          {{w1, b1}, {w2, b2}});
   if (rc) return rc;
-  RefHost t(make_ref_geom(h_px, w), n, h_px, w, false, true);
-  const bool sp = switches_at_create().w_round_sum_preserving;
-  RefLayerF16 L1, L2;
-  rc = upload_ref_f16(h, HostLayer{w1, b1, kC, kC, 9}, sp, &L1);
-  if (!rc) rc = upload_ref_f16(h, HostLayer{w2, b2, kC, kC, 9}, sp, &L2);
-  ds.adopt(L1);
-  ds.adopt(L2);
-  if (rc) return rc;
-  RefDev a, b;
-  HIP_TRY(h, a.alloc(ds, t));
-  HIP_TRY(h, b.alloc(ds, t));
-  t.prefill(1);       // the other tensor (the streamed block's output, the two launches' intermediate) is never an input first
-  HIP_TRY(h, to_dev(b.base, t.v));
-  t.pack(in, false);
-  HIP_TRY(h, to_dev(a.base, t.v));
-  if (!h->ws.tile_ctr) {
-    set_err(h, "sn_dbg_ref_block_f16 needs an engine created in an fp16 mode");
-    return SN_ERR_ARG;
-  }
-  HIP_TRY(h, hipMemsetAsync(h->ws.tile_ctr, 0, kTileCtrBytes, h->stream));
-  uint4 *cur = a.base, *oth = b.base;
-  HIP_TRY(h, ref_block_f16(h->stream, L1, L2, t.g, dbg_cus(h), dil, &cur, &oth, n, h->ws.tile_ctr, fuse_mode, h->dump, false,
-                           &h->dbg_launch));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  RefHost u = t;
-  SN_REF_GET(h, (cur == a.base ? b : a), u, 1, "the fp16 residual block (its other tensor)");
-  SN_REF_GET(h, (cur == a.base ? a : b), t, 1, "the fp16 residual block");
-  t.unpack(out, false);
-  return SN_OK;
-}
-
-int sn_dbg_ref_block_f16(sn_handle* h, const float* in, int h_px, int w, const float* w1, const float* b1,
-                         const float* w2, const float* b2, int dil, float* out) {
-  return sn_dbg_ref_block_f16_n(h, 1, in, h_px, w, w1, b1, w2, b2, dil, out);
+  return th.run(out, [&] {
+    uint4* oth = th.y.base;
+    th.res = th.x.base;
+    return ref_block_f16(h->stream, th.L[0], th.L[1], th.t.g, dbg_cus(h), dil, &th.res, &oth, n, h->ws.tile_ctr, form == 1 ? 4 : 0,
+                         h->dump, false, &h->dbg_launch);
+  });
 }
 
 int sn_dbg_ref_tail_f16(sn_handle* h, int n, const float* in, int hk, int wk, const float* w1, const float* b1, const float* w2,
                         const float* b2, const float* head_w, float head_b, const float* low, int ups, float dnorm, int h_out,
                         int w_out, int form, float* out_disp, int32_t* out_raw) {
-  DevScope ds;
-  if (!h || !in || !w1 || !b1 || !w2 || !b2 || !head_w || !low || !out_disp || !out_raw) return SN_ERR_ARG;
-  if (n <= 0 || hk <= 0 || wk <= 0 || h_out <= 0 || w_out <= 0 || h_out > hk || w_out > wk || (ups != 16 && ups != 2) ||
-      hk % ups || wk % ups || (form != 0 && form != 1) || !(dnorm > 0.f))
+  if (!h || !head_w || h_out <= 0 || w_out <= 0 || h_out > hk || w_out > wk || (ups != 16 && ups != 2) || hk % ups || wk % ups ||
+      (form != 0 && form != 1) || !(dnorm > 0.f))
     return SN_ERR_ARG;
   if (h->precision != SN_PREC_F16 && h->precision != SN_PREC_AUTO) {
     set_err(h, "sn_dbg_ref_tail_f16 needs an engine created with SN_PREC_F16 or SN_PREC_AUTO");
     return SN_ERR_ARG;
   }
-  int rc = check_device(h);
+  // y: written by form 0 only
+  TowerHook th(h, form == 1 ? "the tail form (the tensor it must not write)" : "the streamed block in front of the head",
+               "the tail (its input tensor)");
+  int rc = th.begin({in, w1, b1, w2, b2, low, out_disp, out_raw}, n, hk, wk, 1, 0, in, nullptr, {{w1, b1}, {w2, b2}});
   if (rc) return rc;
-  const RefGeom g = make_ref_geom(hk, wk);
-  if ((ref16_slots(g, n) + ref_slack(g) + ref_front(g)) * 16 >= ((size_t)1 << 32)) return SN_ERR_ARG;      // 32-bit byte offsets inside a tensor
-  RefHost t(g, n, hk, wk, false, true);
-  const bool sp = switches_at_create().w_round_sum_preserving;
-  RefLayerF16 L1, L2;
   HeadLayer hd;
-  rc = upload_ref_f16(h, HostLayer{w1, b1, kC, kC, 9}, sp, &L1);
-  if (!rc) rc = upload_ref_f16(h, HostLayer{w2, b2, kC, kC, 9}, sp, &L2);
-  if (!rc) rc = upload_head(h, HostLayer{head_w, &head_b, 1, kC, 9}, &hd);
-  ds.adopt(L1);
-  ds.adopt(L2);
-  ds.adopt(hd);
+  rc = upload_head(h, HostLayer{head_w, &head_b, 1, kC, 9}, &hd);
+  th.ds.adopt(hd);
   if (rc) return rc;
-  RefDev ta, tb;
-  HIP_TRY(h, ta.alloc(ds, t));
-  HIP_TRY(h, tb.alloc(ds, t));
-  t.prefill(1);        // y: written by form 0 only
-  HIP_TRY(h, to_dev(tb.base, t.v));
-  t.pack(in, false);
-  HIP_TRY(h, to_dev(ta.base, t.v));
-  uint4 *const da = ta.base, *const db = tb.base;
   const int sh = hk / ups, sw = wk / ups;
   const size_t nlow = (size_t)n * sh * sw, nout = (size_t)n * h_out * w_out;
   float *dlow = nullptr, *dd = nullptr;
   int32_t* dr = nullptr;
-  HIP_TRY(h, ds.alloc(&dlow, nlow));
-  HIP_TRY(h, ds.alloc(&dd, nout));
-  HIP_TRY(h, ds.alloc(&dr, nout));
+  HIP_TRY(h, th.ds.alloc(&dlow, nlow));
+  HIP_TRY(h, th.ds.alloc(&dd, nout));
+  HIP_TRY(h, th.ds.alloc(&dr, nout));
   HIP_TRY(h, hipMemcpy(dlow, low, nlow * 4, hipMemcpyHostToDevice));
   HIP_TRY(h, memset_now(dd, 0xff, nout * 4));        // NaN / -1: a pixel the kernel does not write shows up
   HIP_TRY(h, memset_now(dr, 0xff, nout * 4));
   const float inv_q = (float)(1.0 / (kWireFactor * (double)kOutScale));
   const UpScale us{1.0f / (float)ups, (float)ups};
   const HeadArgs ha{hd.w, dlow, dd, dr, hd.bias, dnorm, inv_q, sh, sw, h_out, w_out, us};
-  if (form == 1) {
-    HIP_TRY(h, ref_block_stream_tail(h->stream, L1, L2, g, dbg_cus(h), da, n, h->dump, ha, &h->dbg_launch));
-  } else {
-    HIP_TRY(h, ref_block_stream(h->stream, L1, L2, g, dbg_cus(h), 1, da, db, n, h->dump, &h->dbg_launch));
-    HIP_TRY(h, launch_head_final_f16(h->stream, false, db, 0, g, n, ha));
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  rc = th.run(nullptr, [&]() -> hipError_t {
+    if (form == 1) return ref_block_stream_tail(h->stream, th.L[0], th.L[1], th.t.g, dbg_cus(h), th.x.base, n, h->dump, ha, &h->dbg_launch);
+    const hipError_t e = ref_block_stream(h->stream, th.L[0], th.L[1], th.t.g, dbg_cus(h), 1, th.x.base, th.y.base, n, h->dump, &h->dbg_launch);
+    return e != hipSuccess ? e : launch_head_final_f16(h->stream, false, th.y.base, 0, th.t.g, n, ha);
+  });
+  if (rc) return rc;
   HIP_TRY(h, hipMemcpy(out_disp, dd, nout * 4, hipMemcpyDeviceToHost));
   HIP_TRY(h, hipMemcpy(out_raw, dr, nout * 4, hipMemcpyDeviceToHost));
-  SN_REF_GET(h, ta, t, 1, "the tail (its input tensor)");
-  SN_REF_GET(h, tb, t, 1, form == 1 ? "the tail form (the tensor it must not write)" : "the streamed block in front of the head");
   return SN_OK;
 }
 

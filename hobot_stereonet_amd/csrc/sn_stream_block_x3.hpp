@@ -22,7 +22,7 @@
 //     scratch) 1164-1176 (profiles/r06_x3_nwr_ab.txt);
 //   * the epilogues are k_ref_conv_f16x3's, expression for expression (v = acc0 + acc1 / 2048 [+ xh + xl / 2048], LeakyReLU,
 //     hi = fp16(v), lo = fp16((v - hi) 2048)): the streamed block is bit-identical to the two launches
-//     (tests/test_gpu_x3_stream.py through sn_dbg_ref_block_f16x3).
+//     (tests/test_gpu_x3_stream.py through sn_dbg_ref_block_f16x3_n).
 //   * conv2's waves read the residual rows of a slot into registers one super-step early (as the fp16 kernel's tail form
 //     does): the x ring holds five groups instead of six, which is what lets dilation 8 (80-column rows) fit.
 #pragma once

@@ -306,55 +306,39 @@ int sn_get_dominant_kernel(sn_handle *h, char *name, size_t name_cap, int *launc
                            double *flops_per_launch, double *bytes_per_launch);
 
 /* Parity hooks (tests only; they run the product kernels on caller data, host memory) -------- */
-/* one C->32 convolution through the MFMA kernel: in [cin][h][w] fp32, wt [32][cin][k][k], out [32][ho][wo].
- * lrelu bit 0 = LeakyReLU, bit 1 = use the split-operand fp16 kernel of the fp16 modes (cin 32; 3x3 stride 1 or
- * 5x5 stride 2), bit 2 (with bit 1) = run it on split-slot tensors (hi/lo fp16, the fp16 modes' low-resolution
- * activation format) through the weights-stationary kernel; the hook converts to and from that layout; bit 3 = the
- * fp32 tower kernel k_ref_conv_f32 (cin 32, 3x3, w % 4 == 0) instead of the generic fp32 kernel; bit 4 (with bits 1
- * and 2) = the kernel of the zero-bordered tensors: k_down_x3s_dma (5x5 stride 2, no residual) or k_feat_x3s_dma (3x3,
- * residual allowed: added in place as the feature tower does). */
-int sn_dbg_conv2d(sn_handle *h, const float *in, int cin, int h_px, int w, const float *wt,
-                  const float *bias, int k, int stride, int dil, int lrelu, const float *residual,
-                  float *out);
 /* The grid of the parity hooks.  Every hot kernel is persistent: its launcher sizes the grid from the CU count, and a
  * workgroup walks several tiles (or a share of the streamed blocks' flat rows).  sn_dbg_set_grid_cus makes the sn_dbg_* hooks
  * (and nothing else: the forward pass never reads it) hand their launchers `cus` in place of the device's CU count, so that a
  * small tensor runs the tile loops, queue and share boundaries a full-size one does.  cus = 1 .. the device's CU count, 0
  * restores the default; SN_ERR_ARG otherwise.  A hook whose launcher builds its grid in XCD bands of 8 (the split-slot
- * convolutions, sn_dbg_conv3d's slot forms, sn_dbg_agg_tail, sn_dbg_down01, sn_dbg_ref_conv_f16 / _f16x3 and the two-launch
+ * convolutions, sn_dbg_conv3d's slot forms, sn_dbg_agg_tail, sn_dbg_down01_n, sn_dbg_ref_conv_f16_n / _f16x3_n and the two-launch
  * forms of the blocks) returns SN_ERR_ARG with a message while the value is no multiple of 8.
  * sn_dbg_last_launch: workgroups and work units (tiles; half tiles for k_ref_conv_f32; flat rows for the streamed blocks) of
  * the last launch of the last hook call that went through a persistent launcher (0, 0 for one that did not). */
 int sn_dbg_set_grid_cus(sn_handle *h, int cus);
 int sn_dbg_last_launch(sn_handle *h, int *wgs, int *units);
-/* The _n forms of the one-image hooks: n images in ONE launch, as the pipeline batches them (in / residual / out
- * [n][32][h][w]; sn_dbg_refin_n: disp_low [n][hp/16][wp/16], in6 [n][6][h][w]); the one-image forms are n = 1.
- * The tower hooks (sn_dbg_refin, sn_dbg_ref_conv_*, sn_dbg_ref_block_*) allocate their tensors as the pipeline does
- * ([front rows | tensor | slack]); an output tensor that is not also an input (everything except the in-place residual) starts
- * with the 0xff pattern (fp16 NaN) in its valid area, and after the launch the zero border of all n images, the front rows and
- * the slack are read back: SN_ERR_DEVICE with a message if any of them changed. */
+/* The kernel a convolution hook runs (`form` of sn_dbg_conv2d_n and sn_dbg_conv3d; any other value: SN_ERR_ARG):
+ * F32 = the generic fp32-operand MFMA kernel.  TOWER32 (conv2d; cin 32, 3x3, w % 4 == 0) = the fp32 tower kernel
+ * k_ref_conv_f32; other shapes run as F32.  SLOTS (cin 32, dilation 1) = the split-operand kernel of the fp16 modes on
+ * split-slot tensors (hi / lo fp16, their low-resolution activation format; the hook converts to and from that layout)
+ * through the weights-stationary k_conv_x3s.  SLOTS_DMA = the same operands in zero-bordered tensors: k_feat_x3s_dma (3x3;
+ * a residual is added in place, as the feature tower does), k_down_x3s_dma (5x5 stride 2, no residual) or k_agg_x3s_dma
+ * (conv3d); the hook also checks that the borders stay zero. */
+enum { SN_DBG_CONV_F32 = 0, SN_DBG_CONV_TOWER32 = 1, SN_DBG_CONV_SLOTS = 2, SN_DBG_CONV_SLOTS_DMA = 3 };
+/* The hooks with a leading n run n images (pairs for the down-convs) in ONE launch, as the pipeline batches them.
+ * lrelu: 0, or 1 = LeakyReLU.  residual (nullable): added in place, as the pipeline does.
+ * sn_dbg_conv2d_n: one C->32 convolution, 3x3 stride 1 or 5x5 stride 2: in [n][cin][h][w] fp32, wt [32][cin][k][k],
+ * residual / out [n][32][ho][wo]. */
 int sn_dbg_conv2d_n(sn_handle *h, int n, const float *in, int cin, int h_px, int w, const float *wt,
-                    const float *bias, int k, int stride, int dil, int lrelu, const float *residual,
+                    const float *bias, int k, int stride, int dil, int lrelu, int form, const float *residual,
                     float *out);
-int sn_dbg_down0_n(sn_handle *h, int n, const int8_t *in6, int h_px, int w, const float *wt, const float *bias, int tc,
-                   float *out);       /* in6 [n][6][h][w] -> out [2n][32][ho][wo] */
-int sn_dbg_down01_n(sn_handle *h, int n, const int8_t *in6, int h_px, int w, const float *w0, const float *b0,
-                    const float *w1, const float *b1, float *out);
-int sn_dbg_refin_n(sn_handle *h, int n, const float *disp_low, const int8_t *in6, int h_px, int w, int dmax,
-                   const float *wt, const float *bias, int split, float *out);
-int sn_dbg_ref_conv_f16_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *wt, const float *bias,
-                          int dil, int lrelu, const float *residual, float *out);
-int sn_dbg_ref_conv_f16x3_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *wt, const float *bias,
-                            int dil, int lrelu, const float *residual, float *out);
-int sn_dbg_ref_block_f16_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *w1, const float *b1,
-                           const float *w2, const float *b2, int dil, float *out);
-int sn_dbg_ref_block_f16x3_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *w1, const float *b1,
-                             const float *w2, const float *b2, int dil, int form, float *out);
+/* one 3x3x3 32->32 conv3d (+bias): in [32][d][h][w] -> out [32][d][h][w]; form F32, SLOTS or SLOTS_DMA */
+int sn_dbg_conv3d(sn_handle *h, const float *in, int d, int h_px, int w, const float *wt,
+                  const float *bias, int lrelu, int form, float *out);
 /* the first down-conv (3->32, 5x5, stride 2, no activation) of both eyes through the fp16-MFMA kernel of the fp16
- * modes: in6 int8 [6][h][w] (model input), wt [32][3][5][5], out [2][32][ho][wo] with ho/wo = ceil16(h|w)/2;
- * tc = 32 or 64 selects the tile width */
-int sn_dbg_down0(sn_handle *h, const int8_t *in6, int h_px, int w, const float *wt, const float *bias, int tc,
-                 float *out);
+ * modes: in6 int8 [n][6][h][w] (model input), wt [32][3][5][5], out [2n][32][ho][wo] with ho/wo = ceil16(h|w)/2; tc = 32 */
+int sn_dbg_down0_n(sn_handle *h, int n, const int8_t *in6, int h_px, int w, const float *wt, const float *bias, int tc,
+                   float *out);
 /* The rounding SN_PREC_F16 applies to the 3x3 weights of its refinement towers at model load (host only, no device):
  * w [nkernels][9] fp32 -> out [nkernels][9], every value one of the two fp16 numbers enclosing its input, chosen per kernel
  * so that the SUM of the nine rounding errors is smallest (csrc/stereonet_hip.hip round_kernel_sum_preserving;
@@ -365,40 +349,37 @@ int sn_dbg_round_kernels_f16(const float *w, int nkernels, float *out);
  * sn_dbg_compose_down01 is the host-side fold alone (no device): w0 [32][3][5][5], b0 [32], w1 [32][32][5][5], b1 [32]
  * -> weff [9][32][3][13][13], beff [9][32]; class = 3 * row class + column class, each {first, inner, last} row / column
  * of the quarter-resolution map (down-conv 1's zero padding of the half-resolution map drops taps there).
- * sn_dbg_down01 runs both eyes through the pipeline's two kernels: in6 int8 [6][h][w] -> out [2][32][ho][wo] with
+ * sn_dbg_down01_n runs both eyes through the pipeline's two kernels: in6 int8 [n][6][h][w] -> out [2n][32][ho][wo] with
  * ho/wo = ceil16(h|w)/4. */
 int sn_dbg_compose_down01(const float *w0, const float *b0, const float *w1, const float *b1, float *weff,
                           float *beff);
-int sn_dbg_down01(sn_handle *h, const int8_t *in6, int h_px, int w, const float *w0, const float *b0,
-                  const float *w1, const float *b1, float *out);
-/* the refinement input conv (4->32, 3x3, LeakyReLU) through the fp16-MFMA kernel of the fp16 modes:
- * disp_low fp32 [hp/16][wp/16] (full-resolution px / 16 units as the soft-argmin head writes it), in6 int8 [6][h][w],
- * wt [32][4][3][3]; out fp32 [32][hp][wp] (hp/wp = ceil16) read back from the fp16 NCHW8c tensor(s); split != 0
- * selects the hi/lo output of SN_PREC_F16X3 */
-int sn_dbg_refin(sn_handle *h, const float *disp_low, const int8_t *in6, int h_px, int w, int dmax,
-                 const float *wt, const float *bias, int split, float *out);
-/* one 3x3x3 32->32 conv3d (+bias, optional LeakyReLU): in [32][d][h][w] -> out [32][d][h][w]; lrelu bits as above,
- * bit 3 (with bits 1 and 2): the aggregation kernel of the zero-bordered volumes (k_agg_x3s_dma) */
-int sn_dbg_conv3d(sn_handle *h, const float *in, int d, int h_px, int w, const float *wt,
-                  const float *bias, int lrelu, float *out);
-/* one 32->32 3x3 conv (dilation 1/2/4/8) through the fp16 refinement-tower kernel: in / residual / out are
- * fp32 [32][h][w] on the host; the hook converts to the kernel's fp16 NCHW8c layout and back.
- * lrelu bit 0 = LeakyReLU; bit 1 / bit 2 force the 8x64 / 8x32 tile variant of the dilation-1 / -2 kernel (default: the
- * width the engine picks for the launch from its tile count). */
-int sn_dbg_ref_conv_f16(sn_handle *h, const float *in, int h_px, int w, const float *wt, const float *bias,
-                        int dil, int lrelu, const float *residual, float *out);
-/* the same layer through the split-operand (SN_PREC_F16X3) kernel */
-int sn_dbg_ref_conv_f16x3(sn_handle *h, const float *in, int h_px, int w, const float *wt, const float *bias,
-                          int dil, int lrelu, const float *residual, float *out);
-/* one residual block y = lrelu(x + conv2(lrelu(conv1(x)+b1)) + b2) of the fp16 tower; fp32 [32][h][w] host tensors.
- * dil = 1 / 2 / 4 / 8 in bits 0..7; bits 8.. select the form: 0 = two convolution launches, 2 = the row-streaming fused
- * kernel the pipeline runs by default (every dilation). */
-int sn_dbg_ref_block_f16(sn_handle *h, const float *in, int h_px, int w, const float *w1, const float *b1,
-                         const float *w2, const float *b2, int dil, float *out);
-/* the same block on split operands (SN_PREC_F16X3): form 0 = two k_ref_conv_f16x3 launches, 1 = the row-streaming fused kernel
- * (sn_stream_block_x3.hpp) — bit-identical to form 0 */
-int sn_dbg_ref_block_f16x3(sn_handle *h, const float *in, int h_px, int w, const float *w1, const float *b1,
+int sn_dbg_down01_n(sn_handle *h, int n, const int8_t *in6, int h_px, int w, const float *w0, const float *b0,
+                    const float *w1, const float *b1, float *out);
+/* The tower hooks (sn_dbg_refin_n, sn_dbg_ref_conv_*, sn_dbg_ref_block_*, sn_dbg_ref_tail_f16) take fp32 host tensors
+ * [n][32][h][w], convert them to the kernels' fp16 NCHW8c layout and back (SN_PREC_F16X3: hi / lo), and allocate them as the
+ * pipeline does ([front rows | tensor | slack]).  A tensor that is not an input (everything except the input and the in-place
+ * residual) starts with the 0xff pattern (fp16 NaN) in its valid area, and after the launch the zero border of all n images,
+ * the front rows and the slack of EVERY tensor are read back: SN_ERR_DEVICE with a message if any of them changed.  dil = 1, 2,
+ * 4 or 8; a tensor too large for 32-bit byte offsets: SN_ERR_ARG.
+ * sn_dbg_refin_n: the refinement input conv (4->32, 3x3, LeakyReLU): disp_low fp32 [n][hp/16][wp/16] (full-resolution px / 16
+ * units as the soft-argmin head writes it), in6 int8 [n][6][h][w], wt [32][4][3][3]; out [n][32][hp][wp] (hp/wp = ceil16);
+ * split != 0 selects the hi/lo output of SN_PREC_F16X3. */
+int sn_dbg_refin_n(sn_handle *h, int n, const float *disp_low, const int8_t *in6, int h_px, int w, int dmax,
+                   const float *wt, const float *bias, int split, float *out);
+/* one 32->32 3x3 conv through the fp16 refinement-tower kernel (needs an engine created in an fp16 mode); tile_w = 64 / 32
+ * forces the 8x64 / 8x32 tile variant of the dilation-1 / -2 kernel, 0 = the width the engine picks for the launch from its
+ * tile count; and the same layer through the split-operand (SN_PREC_F16X3) kernel */
+int sn_dbg_ref_conv_f16_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *wt, const float *bias,
+                          int dil, int lrelu, int tile_w, const float *residual, float *out);
+int sn_dbg_ref_conv_f16x3_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *wt, const float *bias,
+                            int dil, int lrelu, const float *residual, float *out);
+/* one residual block y = lrelu(x + conv2(lrelu(conv1(x)+b1)) + b2) of the fp16 tower (needs an engine created in an fp16
+ * mode), and the same block on split operands (SN_PREC_F16X3).  form 0 = two convolution launches, 1 = the row-streaming fused
+ * kernel the pipeline runs by default (sn_stream_block.hpp, sn_stream_block_x3.hpp; on split operands bit-identical to form 0) */
+int sn_dbg_ref_block_f16_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *w1, const float *b1,
                            const float *w2, const float *b2, int dil, int form, float *out);
+int sn_dbg_ref_block_f16x3_n(sn_handle *h, int n, const float *in, int h_px, int w, const float *w1, const float *b1,
+                             const float *w2, const float *b2, int dil, int form, float *out);
 /* The LAST residual block of the fp16 tower followed by the refinement head (conv 3x3 32 -> 1, disp = relu(up + D r), wire
  * quantisation) on n images: fp32 host tensors in [n][32][hk][wk] (the level's padded activation, rounded to fp16 by the hook),
  * low [n][hk / ups][wk / ups] (the map the level starts from; ups = 16: soft-argmin map, 2: the level below), head_w [32][9].

@@ -1,4 +1,4 @@
-"""One fp32 tower layer (k_ref_conv_f32) at 1280x720 through sn_dbg_conv2d, a few launches: run under rocprofv3 --stats.
+"""One fp32 tower layer (k_ref_conv_f32) at 1280x720 through sn_dbg_conv2d_n, a few launches: run under rocprofv3 --stats.
     SN_F32_GRID=n   workgroups per launch (default: two per CU)"""
 import os
 import sys

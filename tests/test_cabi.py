@@ -25,6 +25,37 @@ def test_header_symbols_are_exported():
         assert hasattr(lib, s), f"{s} declared in stereonet_hip.h but not exported"
 
 
+def declared_parameter_counts():
+    """name -> number of parameters of every sn_* prototype in the header (commas at depth 0 of its parameter list)"""
+    src = open(os.path.join(ROOT, "include", "stereonet_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    counts = {}
+    for m in re.finditer(r"\b(sn_[a-z0-9_]+)\s*\(", src):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            c = src[i]
+            depth += (c == "(") - (c == ")")
+            commas += c == "," and depth == 1
+            i += 1
+        params = src[m.end():i - 1].strip()
+        counts[m.group(1)] = 0 if params in ("", "void") else commas + 1
+    return counts
+
+
+def test_bound_argtypes_have_the_headers_parameter_counts():
+    """api.py writes every argtypes list by hand: each declared function has one, as long as its prototype's parameter list
+    (a hook that gained a parameter would otherwise still be called with the old arguments).  Only a function without
+    parameters may go without a list (sn_abi_version)."""
+    lib = api.load_library()
+    counts = declared_parameter_counts()
+    assert len([s for s in counts if s.startswith("sn_dbg_")]) >= 20 and sorted(counts) == declared_symbols()
+    for name, n in counts.items():
+        argtypes = getattr(lib, name).argtypes
+        assert argtypes is not None or (n == 0 and not name.startswith("sn_dbg_")), f"{name}: api.py sets no argtypes"
+        assert len(argtypes or ()) == n, f"{name}: {len(argtypes or ())} argtypes bound, {n} parameters declared"
+
+
 def test_slot_graph_readout_is_exported_and_refuses_null():
     """sn_dbg_slot_graphs (what the async slots' hipGraphs did; tests/test_gpu_async_graph.py) is a test hook: exported and
     bound by api.py, not declared in the public header, and SN_ERR_ARG for a null handle or a null output without a device."""
